@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: forward+backward of the PDE diffusion layer (the hot path).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: set-up, W warm-up steps, K timed steps, one JSON line (`value`, `ms_per_step`
+= the time of one timed step).  `--dump-outputs DIR` writes what the last timed step computed (the layer's output and
+the gradients of its input and parameters) as DIR/<name>.npy, fp32, under 64 MB in all: arrays too large for that are
+written as a fixed seeded sample of their elements.  Inputs and parameters are seeded, so two builds run with the same
+arguments can be compared output for output.  `--full` adds everything else the line reports (see below).
 
 N = 1 runs in-process.  For N > 1 the file runs as one rank per GPU over RCCL: either the driver launches it
 under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or — called plainly as
@@ -14,8 +20,10 @@ synthetic N(0,1) input and upstream gradient, "trained-like" coefficients.  A st
 forward + backward of the layer over one batch; with N > 1 the batch is sharded (weak scaling)
 and the layer's parameter gradients are all-reduced over RCCL every step.
 Primary line: channel mixing disabled (diffusion path only — SURVEY.md §8d declares it the
-primary configuration; the C=64 mixing product is a GEMM outside the stencil path).  The
-same workload WITH channel mixing is reported under "secondary", and the other BASELINE.json
+primary configuration; the C=64 mixing product is a GEMM outside the stencil path).  With `--full`, the
+same loop under the default checkpoint policy, per-kernel device times and the roofline, the device-copy ceiling and
+a hipGraph replay are reported beside it, strong scaling when N > 1, the CPU path when N = 1, the
+same workload WITH channel mixing under "secondary", and the other BASELINE.json
 configurations (SURVEY §8d cfg1, cfg3 at C=1 and C=32, cfg4 bf16, cfg5) under "configs", each timed the same
 way (warm-up, K steps between synchronisations, max over ranks) with its algorithmic-bytes HBM fraction.
 """
@@ -29,6 +37,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -54,7 +63,9 @@ def build_layer(C, N, steps, dev, rank, mixing):
 
 def run_steps(layer, u, gy, n, dist_on, flat, spans=None):
     """`spans` (multi-rank runs): receives one (before, after) event pair per step around the wait for the gradient
-    all-reduce — what the stream waited for a collective that the backward's hooks had launched earlier."""
+    all-reduce — what the stream waited for a collective that the backward's hooks had launched earlier.  Returns the
+    last step's output (its gradients are in u.grad and the parameters' .grad)."""
+    y = None
     for _ in range(n):
         if dist_on:
             flat.zero()                         # the gradients are views of the flat bucket: one launch clears them
@@ -78,6 +89,7 @@ def run_steps(layer, u, gy, n, dist_on, flat, spans=None):
                 spans.append((e0, e1))
             else:
                 flat.finish()
+    return y
 
 
 PRECONDITION_BATCH = 50    # set-up (see main): untimed batches of this many steps of the headline workload ...
@@ -111,7 +123,8 @@ def precondition(layer, u, gy, dist_on, flat):
 LAST_DIAG = {}        # per-rank figures of the latest timed() call on a multi-rank run (rank 0 puts them in the JSON line)
 
 
-def timed(layer, u, gy, steps, warmup, dist_on, flat):
+def timed(layer, u, gy, steps, warmup, dist_on, flat, outputs=None):
+    """`outputs`: receives the output of the last timed step"""
     import torch.distributed as dist
     run_steps(layer, u, gy, warmup, dist_on, flat)
     if dist_on:
@@ -119,7 +132,7 @@ def timed(layer, u, gy, steps, warmup, dist_on, flat):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     spans = [] if dist_on else None
-    run_steps(layer, u, gy, steps, dist_on, flat, spans)
+    y = run_steps(layer, u, gy, steps, dist_on, flat, spans)
     torch.cuda.synchronize()
     own = time.perf_counter() - t0               # this rank alone, before it waits for the others
     if dist_on:
@@ -143,7 +156,34 @@ def timed(layer, u, gy, steps, warmup, dist_on, flat):
                                                    "note": "per step: stream time between the end of backward and the "
                                                            "completion of the gradient all-reduce its hooks launched "
                                                            "(events around GradBucket.finish())"}})
+    if outputs is not None:
+        outputs.append(y)
     return dt
+
+
+DUMP_BYTES = 60_000_000    # --dump-outputs: all arrays together, under 64 MB however counted
+
+
+def dump_outputs(path, arrays):
+    """Writes each tensor of `arrays` as <path>/<name>.npy in fp32 (fp64 stays fp64), DUMP_BYTES in all: the smallest
+    arrays whole, each one that does not fit its share of what is left as a sample of its flattened elements at fixed
+    indices (sorted, drawn from a generator seeded by the array's name, so the same in every run)."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = DUMP_BYTES - 1024 * len(items)       # the .npy headers
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = left // (len(items) - i) // (8 if dtype == torch.float64 else 4)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        print(f"[bench] dump: {name} {tuple(arrays[name].shape)} -> {a.size} values", file=sys.stderr, flush=True)
 
 
 def graph_replay_ms(layer, u, gy, reps):
@@ -410,6 +450,108 @@ def config_legs(dev, rank, world, dist_on, quick):
     return legs
 
 
+def headline_extras(a, layer, u, gy, dev, rank, world, dist_on, flat):
+    """--full: the measurements beside the headline, on its layer and inputs.  Rank 0 receives the fields they add to the
+    JSON line, the other ranks None: the same loop under the default checkpoint policy, per-kernel device times and the
+    roofline, the device-copy ceiling, the hipGraph replay."""
+    import cnn_with_pde_amd as P
+    B, C, N, steps = a.batch, a.channels, a.size, a.num_steps
+    out = None
+    layer.checkpoint_policy = "auto"
+    dt_auto = timed(layer, u, gy, min(a.steps, 30), 3, dist_on, flat)
+    auto_ms = dt_auto / min(a.steps, 30) * 1e3
+    layer.checkpoint_policy = "lagged"
+    elems = B * C * N * N
+
+    # per-kernel device time (HIP events on the launch stream, inside the library)
+    P.timing_enable(True)
+    run_steps(layer, u, gy, min(a.steps, 20), dist_on, flat)
+    f_ms, f_n, b_ms, b_n = P.timing_read()
+    P.timing_enable(False)
+    fwd_ms, bwd_ms = f_ms / max(f_n, 1), b_ms / max(b_n, 1)
+
+    # device-copy ceiling measured on this box (SURVEY §8d: report against the spec peak and against this)
+    src = torch.empty(256 << 20, dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+    for _ in range(3):
+        dst.copy_(src)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        dst.copy_(src)
+    torch.cuda.synchronize()
+    copy_gbs = 20 * 2 * src.numel() / (time.perf_counter() - t0) / 1e9
+    del src, dst
+
+    # the same step replayed from a hipGraph (extra information: `value` above is the eager autograd path)
+    graph_ms = None
+    if not dist_on:
+        try:
+            graph_ms = graph_replay_ms(layer, u, gy, a.steps)
+            layer.checkpoint_policy = "auto"
+        except Exception as e:
+            graph_ms = "capture failed: %s" % (str(e)[:120],)
+
+    # which kernel the backward of this schedule is (the hand-scheduled assembly kernel since round 4: include/pdecnn.h)
+    bwd_kernel = "adi_bwd_kernel"
+    try:
+        import ctypes
+        import cnn_with_pde_amd.functional as F_
+        import cnn_with_pde_amd._lib as L_
+        sw_ = [s_ for st_ in P.adi_schedule(layer.dt, layer.dx, layer.dy, steps) for s_ in st_]
+        d_ = F_._build_desc(B, C, N, L_.PDE_IO_F32, sw_, False, 10.0, 1e-6)
+        if L_.load().pde_adi_backward_kernel(ctypes.byref(d_), 0) == 1:
+            bwd_kernel = "adi_bwd_asm_n32_w" + os.environ.get("PDE_ASM_VARIANT", "8b")
+    except Exception:
+        pass
+    if rank == 0:
+        pmc, valu, pmc_src = None, None, None
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.isfile(pmc_path) and (B, C, N, steps) == (512, 64, 32, 10):     # counters were taken on this workload
+            with open(pmc_path) as f:
+                pj = json.load(f)
+            pmc = pj.get("adi_bwd_kernel_bytes_per_launch") if pj.get("bwd_kernel", "adi_bwd_kernel").startswith(bwd_kernel[:11]) else None
+            valu = pj.get("sq_insts_valu_per_launch")
+            pmc_src = {"file": "profiles/pmc_traffic.json", "taken_at_commit": pj.get("commit"), "passes": pj.get("source")}
+        ach = elems * BYTES_PER_ELEM["bwd"] / (bwd_ms * 1e-3) / 1e9
+        out = {
+            "eager_auto_policy": {"ms_per_step": auto_ms, "value": B * world / (auto_ms * 1e-3) / 1e6, "unit": "Msamples/s",
+                                  "note": "the same eager loop under the default policy (the backward waits for this call's "
+                                          "own maxima); differs from `value` only when the host is late"},
+            "hipgraph_replay": None if graph_ms is None else {
+                "ms_per_step": graph_ms,
+                "value": (B * world / (graph_ms * 1e-3) / 1e6) if isinstance(graph_ms, float) else None, "unit": "Msamples/s",
+                "note": "the same forward+backward captured once (cnn_with_pde_amd.graphs.GraphedStep, checkpoint plan "
+                        "frozen) and replayed: no Python/autograd/ctypes per step, but the replay also copies the gradients "
+                        "(134 MB for the input's) into the step's static output buffers; `value` above is the eager path"},
+            "roofline": {"bound": "hbm", "kernel": bwd_kernel, "achieved": ach, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": pmc, "traffic_source": pmc_src,
+                         "copy_ceiling_measured": copy_gbs,
+                         "algorithmic_bytes_per_launch": elems * BYTES_PER_ELEM["bwd"], "avg_launch_ms": bwd_ms},
+            "roofline_fwd": {"bound": "hbm", "kernel": "adi_fwd_kernel",
+                             "achieved": elems * BYTES_PER_ELEM["fwd"] / (fwd_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "avg_launch_ms": fwd_ms},
+        }
+        if valu:
+            # the second ceiling (DESIGN.md §4): VALU issue.  A SIMD takes one wave64 fp32 instruction per ~2 cycles from
+            # two or more waves (tools/ubench/sweep_pk.hip: 2.3 with two, 1.6 with three), one wave issues at most one
+            # per ~4.3 cycles; the backward has two waves per SIMD (246 VGPRs), the forward four.  1024 SIMDs at 2.4 GHz.
+            def floors(n_inst, waves_per_simd):
+                simd = n_inst * 2.0 / 1024 / 2.4e9 * 1e3
+                per_wave = n_inst * 4.3 / waves_per_simd / 1024 / 2.4e9 * 1e3
+                return simd, max(simd, per_wave)
+            sb, wb = floors(valu["adi_bwd_kernel"], 2)
+            sf, wf = floors(valu["adi_fwd_kernel"], 4)
+            out["valu_issue"] = {"note": "SQ_INSTS_VALU per launch (rocprofv3 --pmc, profiles/) at the SIMD's rate (2 cycles per "
+                                         "instruction) and at the per-wave issue limit (4.3 cycles, waves per SIMD: backward 2, "
+                                         "forward 4); frac = floor / measured launch time",
+                                 "adi_bwd_kernel": {"floor_ms_simd_rate": sb, "frac_simd_rate": sb / bwd_ms,
+                                                    "floor_ms_per_wave_limit": wb, "frac_per_wave_limit": wb / bwd_ms},
+                                 "adi_fwd_kernel": {"floor_ms_simd_rate": sf, "frac_simd_rate": sf / fwd_ms,
+                                                    "floor_ms_per_wave_limit": wf, "frac_per_wave_limit": wf / fwd_ms}}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -419,14 +561,21 @@ def main():
     ap.add_argument("--channels", type=int, default=64)
     ap.add_argument("--size", type=int, default=32)
     ap.add_argument("--num-steps", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the per-config legs (cfg1, cfg3, cfg4, cfg5)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output and gradients as DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the default checkpoint policy, per-kernel times and "
+                         "roofline, copy ceiling, hipGraph replay, strong scaling, secondary workload, configs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workload")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the per-config legs (cfg1, cfg3, cfg4, cfg5)")
     ap.add_argument("--cpu-sample", type=int, default=32, help="samples of the CPU baseline (SURVEY §8d: fixed B = 32)")
     ap.add_argument("--rehearse-one-device", action="store_true",
                     help="developer rehearsal of the multi-rank path on a ONE-GPU box: every rank uses cuda:0 and the "
                          "collectives run over gloo (RCCL refuses two ranks on one device); timings are meaningless")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -464,7 +613,7 @@ def main():
     B, C, N, steps = a.batch, a.channels, a.size, a.num_steps
     # the CPU path first, before the GPU legs hold host memory (fixed B = 32)
     cpu_base = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu_base = cpu_baseline(C, N, steps, a.cpu_sample)
     g = torch.Generator().manual_seed(1234 + rank)
     u = torch.randn(B, C, N, N, generator=g).to(dev).requires_grad_(True)
@@ -480,75 +629,28 @@ def main():
     # maxima ("lagged", layers.py — the policy meant for loops whose parameters move by optimiser steps).  The default
     # ("auto": this call's own maxima) makes the backward wait for the forward's factorisation kernel, so the host can run
     # at most one forward ahead of the device; a host that is late by more than that now and then (seen on 2 of 13
-    # boxes: +0.1 ms per step) shows in the step time.  The same loop under "auto" is timed beside it (`eager_auto_policy`).
+    # boxes: +0.1 ms per step) shows in the step time.  `--full` times the same loop under "auto" beside it (`eager_auto_policy`).
     layer.checkpoint_policy = "lagged"
     # Set-up, before the W warm-up steps and the K timed ones: the device and the allocator in their steady state.  A
     # chip that has been idle needs this load for a while before it holds its clocks (with 5 warm-up steps the first
     # timed leg read 0.499 ms per step on a box whose steady state is 0.456; a freshly leased box was still falling
     # after 150 steps), and torch's caching allocator takes its 134 MB blocks from the driver during the first steps.
     precond = precondition(layer, u, gy, dist_on, flat)
-    dt = timed(layer, u, gy, a.steps, a.warmup, dist_on, flat)
+    last = []
+    dt = timed(layer, u, gy, a.steps, a.warmup, dist_on, flat, last)
     headline_diag = dict(LAST_DIAG)
-    layer.checkpoint_policy = "auto"
-    dt_auto = timed(layer, u, gy, min(a.steps, 30), 3, dist_on, flat)
-    auto_ms = dt_auto / min(a.steps, 30) * 1e3
-    layer.checkpoint_policy = "lagged"
     ms_step = dt / a.steps * 1e3
     samples_s = B * world * a.steps / dt
-    elems = B * C * N * N
-
-    # per-kernel device time (HIP events on the launch stream, inside the library)
-    P.timing_enable(True)
-    run_steps(layer, u, gy, min(a.steps, 20), dist_on, flat)
-    f_ms, f_n, b_ms, b_n = P.timing_read()
-    P.timing_enable(False)
-    fwd_ms, bwd_ms = f_ms / max(f_n, 1), b_ms / max(b_n, 1)
-
-    # device-copy ceiling measured on this box (report against the spec peak and against this)
-    src = torch.empty(256 << 20, dtype=torch.uint8, device=dev)
-    dst = torch.empty_like(src)
-    for _ in range(3):
-        dst.copy_(src)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(20):
-        dst.copy_(src)
-    torch.cuda.synchronize()
-    copy_gbs = 20 * 2 * src.numel() / (time.perf_counter() - t0) / 1e9
-    del src, dst
-
-    # the same step replayed from a hipGraph (extra information: `value` above is the eager autograd path)
-    graph_ms = None
-    if not dist_on:
-        try:
-            graph_ms = graph_replay_ms(layer, u, gy, a.steps)
-            layer.checkpoint_policy = "auto"
-        except Exception as e:
-            graph_ms = "capture failed: %s" % (str(e)[:120],)
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (rank 0's shard when N > 1)
+        arrays = {"y": last[0], "grad_input": u.grad}
+        arrays.update({"grad_" + n: p.grad for n, p in layer.named_parameters() if p.grad is not None})
+        dump_outputs(a.dump_outputs, arrays)
+        del arrays
+    del last
 
     out = None
-    # which kernel the backward of this schedule is (the hand-scheduled assembly kernel since round 4: include/pdecnn.h)
-    bwd_kernel = "adi_bwd_kernel"
-    try:
-        import ctypes
-        import cnn_with_pde_amd.functional as F_
-        import cnn_with_pde_amd._lib as L_
-        sw_ = [s_ for st_ in P.adi_schedule(layer.dt, layer.dx, layer.dy, steps) for s_ in st_]
-        d_ = F_._build_desc(B, C, N, L_.PDE_IO_F32, sw_, False, 10.0, 1e-6)
-        if L_.load().pde_adi_backward_kernel(ctypes.byref(d_), 0) == 1:
-            bwd_kernel = "adi_bwd_asm_n32_w" + os.environ.get("PDE_ASM_VARIANT", "8b")
-    except Exception:
-        pass
     if rank == 0:
-        pmc, valu, pmc_src = None, None, None
-        pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.isfile(pmc_path) and (B, C, N, steps) == (512, 64, 32, 10):     # counters were taken on this workload
-            with open(pmc_path) as f:
-                pj = json.load(f)
-            pmc = pj.get("adi_bwd_kernel_bytes_per_launch") if pj.get("bwd_kernel", "adi_bwd_kernel").startswith(bwd_kernel[:11]) else None
-            valu = pj.get("sq_insts_valu_per_launch")
-            pmc_src = {"file": "profiles/pmc_traffic.json", "taken_at_commit": pj.get("commit"), "passes": pj.get("source")}
-        ach = elems * BYTES_PER_ELEM["bwd"] / (bwd_ms * 1e-3) / 1e9
         out = {
             "metric": "PDE-layer fwd+bwd Msamples/s", "value": samples_s / 1e6, "unit": "Msamples/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step,
@@ -564,59 +666,31 @@ def main():
                                                   "clocks and allocator pools in their steady state)"),
             "checkpoint_policy": "lagged (the backward's checkpoint plan comes from the previous step's coefficient maxima: no "
                                  "host wait inside the step; both plans are 'no checkpoints' on this workload)",
-            "eager_auto_policy": {"ms_per_step": auto_ms, "value": B * world / (auto_ms * 1e-3) / 1e6, "unit": "Msamples/s",
-                                  "note": "the same eager loop under the default policy (the backward waits for this call's "
-                                          "own maxima); differs from `value` only when the host is late"},
-            "hipgraph_replay": None if graph_ms is None else {
-                "ms_per_step": graph_ms,
-                "value": (B * world / (graph_ms * 1e-3) / 1e6) if isinstance(graph_ms, float) else None, "unit": "Msamples/s",
-                "note": "the same forward+backward captured once (cnn_with_pde_amd.graphs.GraphedStep, checkpoint plan "
-                        "frozen) and replayed: no Python/autograd/ctypes per step, but the replay also copies the gradients "
-                        "(134 MB for the input's) into the step's static output buffers; `value` above is the eager path"},
-            "roofline": {"bound": "hbm", "kernel": bwd_kernel, "achieved": ach, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": pmc, "traffic_source": pmc_src,
-                         "copy_ceiling_measured": copy_gbs,
-                         "algorithmic_bytes_per_launch": elems * BYTES_PER_ELEM["bwd"], "avg_launch_ms": bwd_ms},
-            "roofline_fwd": {"bound": "hbm", "kernel": "adi_fwd_kernel",
-                             "achieved": elems * BYTES_PER_ELEM["fwd"] / (fwd_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "avg_launch_ms": fwd_ms},
             "step_hbm": {"achieved": samples_s / world * C * N * N * BYTES_PER_ELEM["step"] / 1e9, "unit": "GB/s",
                          "frac": samples_s / world * C * N * N * BYTES_PER_ELEM["step"] / 1e9 / HBM_PEAK_GBS,
                          "note": "per GPU: samples/s x 20 B/element (whole step incl. launch gaps and small kernels)"},
         }
-        if valu:
-            # the second ceiling: VALU issue.  A SIMD takes one wave64 fp32 instruction per ~2 cycles from
-            # two or more waves (tools/ubench/sweep_pk.hip: 2.3 with two, 1.6 with three), one wave issues at most one
-            # per ~4.3 cycles; the backward has two waves per SIMD (246 VGPRs), the forward four.  1024 SIMDs at 2.4 GHz.
-            def floors(n_inst, waves_per_simd):
-                simd = n_inst * 2.0 / 1024 / 2.4e9 * 1e3
-                per_wave = n_inst * 4.3 / waves_per_simd / 1024 / 2.4e9 * 1e3
-                return simd, max(simd, per_wave)
-            sb, wb = floors(valu["adi_bwd_kernel"], 2)
-            sf, wf = floors(valu["adi_fwd_kernel"], 4)
-            out["valu_issue"] = {"note": "SQ_INSTS_VALU per launch (rocprofv3 --pmc, profiles/) at the SIMD's rate (2 cycles per "
-                                         "instruction) and at the per-wave issue limit (4.3 cycles, waves per SIMD: backward 2, "
-                                         "forward 4); frac = floor / measured launch time",
-                                 "adi_bwd_kernel": {"floor_ms_simd_rate": sb, "frac_simd_rate": sb / bwd_ms,
-                                                    "floor_ms_per_wave_limit": wb, "frac_per_wave_limit": wb / bwd_ms},
-                                 "adi_fwd_kernel": {"floor_ms_simd_rate": sf, "frac_simd_rate": sf / fwd_ms,
-                                                    "floor_ms_per_wave_limit": wf, "frac_per_wave_limit": wf / fwd_ms}}
+        if dist_on:
+            out["dist"] = headline_diag
+    if a.full:
+        extra = headline_extras(a, layer, u, gy, dev, rank, world, dist_on, flat)
+        if rank == 0:
+            out.update(extra)
 
-    if dist_on:
+    if a.full and dist_on:
         # strong scaling beside the weak line: the SAME global batch of `--batch` samples split over the ranks
         lo, hi = P.shard_range(B, rank, world)
         us = u.detach()[: hi - lo].clone().requires_grad_(True)
         gs = gy[: hi - lo].clone()
         dts = timed(layer, us, gs, a.steps, a.warmup, dist_on, flat)
         if rank == 0:
-            out["dist"] = headline_diag
             out["strong"] = {"dist": dict(LAST_DIAG),"scaling": "strong", "global_batch": B, "per_gpu_batch": hi - lo, "ms_per_step": dts / a.steps * 1e3,
                              "value": B * a.steps / dts / 1e6, "unit": "Msamples/s",
                              "note": "same layer, the global batch fixed at --batch and sharded over the ranks (contiguous "
                                      "shards, gradient all-reduce every step); `value` above is the weak-scaling line"}
         del us, gs
 
-    if not a.no_secondary:
+    if a.full and not a.no_secondary:
         layer2 = build_layer(C, N, steps, dev, rank, mixing=True)
         flat2 = P.GradBucket(layer2.parameters(), grads_as_views=True) if dist_on else None
         k2 = max(3, a.steps // 5)
@@ -635,7 +709,7 @@ def main():
                 out["secondary"]["traffic"] = tr
         del layer2
 
-    if not a.no_configs:
+    if a.full and not a.no_configs:
         del u, gy, layer
         torch.cuda.empty_cache()
         legs = config_legs(dev, rank, world, dist_on, quick=a.steps < 20)

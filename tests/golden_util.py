@@ -11,6 +11,9 @@ from oracle import pde_oracle as O
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MODEL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden_models")   # the reference's MODELS around the layers
+# how tools/make_golden.py runs the reference: MKL_CBWR=COMPATIBLE (tests/conftest.py) and this many CPU threads (a
+# product's summation order in MKL depends on the thread count)
+GOLDEN_THREADS = 4
 
 
 def names(prefixes=None, f64=None, directory=None):

@@ -2,7 +2,8 @@
 reference's own layer classes (tests/golden, made by tools/make_golden.py).
 
 K1 in fp32 must agree BITWISE (same op order as the reference); everything else
-within a few ulp.  These run on CPU (-m "not gpu")."""
+within a few ulp.  These run on CPU (-m "not gpu"), with MKL in its reproducible mode
+(tests/conftest.py) and the thread count the vectors were made with, so on any x86 host."""
 import pytest
 import torch
 
@@ -14,7 +15,12 @@ from oracle import pde_oracle as O
 def test_oracle_matches_reference_vectors(name):
     g = G.Golden(name)
     fn = g.oracle_fn()
-    y, gu, grads = O.value_and_grads(fn, g.u, g.params, g.gy)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(G.GOLDEN_THREADS)        # as the vectors were made (golden_util)
+    try:
+        y, gu, grads = O.value_and_grads(fn, g.u, g.params, g.gy)
+    finally:
+        torch.set_num_threads(threads)
     k1_f32 = g.family() == "adi" and g.dtype == torch.float32
     tol = 0.0 if k1_f32 else (1e-12 if g.dtype == torch.float64 else 2e-6)
     if name == "emotion_default_smooth":

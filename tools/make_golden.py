@@ -13,8 +13,11 @@ import json
 import os
 import sys
 
-import numpy as np
-import torch
+# MKL's reproducible mode, as tests/conftest.py runs the oracle (the products' rounding then does not depend on the CPU);
+# set before torch loads MKL.  The thread count is pinned in main().
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
@@ -246,6 +249,7 @@ def big_symmetric():
 
 
 def main():
+    torch.set_num_threads(4)            # tests/golden_util.py GOLDEN_THREADS
     os.makedirs(OUT, exist_ok=True)
     f32, f64 = torch.float32, torch.float64
     models()
