@@ -945,6 +945,358 @@ int launch_part32(const float* X, const float* W, int B, int D, int S, void* ws,
     return rh_waves32(B) == 2 ? launch_part32_wv<NT, 2>(X, W, B, D, S, ws, st) : launch_part32_wv<NT, 4>(X, W, B, D, S, ws, st);
 }
 
+// ---- the layer under CUDA fp16 autocast: fp16 operands on v_mfma_f32_32x32x16_f16, fp32 accumulators ----------------------
+// Same structure as the 32-column strips above (WV waves x 32 batch rows, the contraction of a strip split over S
+// workgroups, the partial tiles added in split order by the epilogue launch, which holds every row of its 8 columns and so
+// takes the BatchNorm statistics), with autocast's rounding points r() = round to fp16 (include/pdecnn.h):
+// P = r(r(X) K16^T), N = r(BN(P)), H = r(act(N)), Q = r(H K16), out = base + r(scale Q).  The fp32 operands (X, the
+// incoming gradient) are rounded when they are staged in LDS; P, H and dP are fp16 tensors.  A slab is 64 contraction
+// steps = four MFMAs per wave.  NT products read both operands row-wise (K16's rows are contiguous along k); the NN
+// products take K16's columns as the B operand through the transposing read ds_read_b64_tr_b16 of a [k][n] image.
+typedef _Float16 rh_h8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ unsigned short rh_f2h(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+__device__ __forceinline__ float rh_h2f(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ float rh_r16(float f) { return (float)(_Float16)f; }
+
+constexpr int kH16Bk = 64;                     // contraction steps per slab
+constexpr int kH16Pitch = kH16Bk * 2 + 16;      // bytes per row of a [row][k] image (144: 16 B of padding)
+constexpr int kH16NnPitch = kS32Cols * 2 + 16;  // bytes per k row of the NN product's [k][n] image of K16 (80)
+
+// A operand of a strip product: fp32 (X, the upstream gradient: a = r(x), then a = r(ascale a) where dbl) or fp16 bits
+struct RhPart16Args {
+    const void* A; const unsigned short* W; float* part;
+    int B, D, S, dbl;
+    float ascale;
+};
+
+template <bool NT, int WV, bool AF32>
+__global__ __launch_bounds__(WV * 64) void rh_part16_kernel(RhPart16Args a) {
+    constexpr int THREADS = WV * 64, ROWS = WV * 32, BK = kH16Bk;
+    constexpr int ABYTES = ROWS * kH16Pitch;
+    constexpr int WBYTES = NT ? kS32Cols * kH16Pitch : BK * kH16NnPitch;
+    constexpr int AC = AF32 ? BK / 4 : BK / 8;            // 16-byte loads per A row of a slab
+    constexpr int APT = ROWS * AC / THREADS;
+    constexpr int WC = NT ? BK / 8 : kS32Cols / 8;        // 16-byte loads per W row of a slab
+    constexpr int WPT = (NT ? kS32Cols : BK) * WC / THREADS;
+    static_assert(APT * THREADS == ROWS * AC && WPT * THREADS == (NT ? kS32Cols : BK) * WC, "whole loads per thread");
+    __shared__ __attribute__((aligned(16))) unsigned char sm[2][ABYTES + WBYTES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, jj = lane & 31, kh = lane >> 5;
+    const int strip = blockIdx.x, split = blockIdx.y, n0 = strip * kS32Cols;
+    const int klen = a.D / a.S, kb = split * klen;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    uint4 pa[APT], pw[WPT];
+    auto fetch = [&](int k0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int m = 0; m < APT; ++m) {
+            const int f = tid + THREADS * m, row = f / AC, c = f % AC;
+            const int rc = row < a.B ? row : a.B - 1;     // rows beyond the batch: re-read the last one, zeroed when staged
+            pa[m] = AF32 ? *reinterpret_cast<const uint4*>(static_cast<const float*>(a.A) + (size_t)rc * a.D + k0 + 4 * c)
+                         : *reinterpret_cast<const uint4*>(static_cast<const unsigned short*>(a.A) + (size_t)rc * a.D + k0 + 8 * c);
+        }
+#pragma unroll
+        for (int m = 0; m < WPT; ++m) {
+            const int f = tid + THREADS * m, row = f / WC, c = f % WC;
+            pw[m] = NT ? *reinterpret_cast<const uint4*>(a.W + (size_t)(n0 + row) * a.D + k0 + 8 * c)   // feature n0 + row
+                       : *reinterpret_cast<const uint4*>(a.W + (size_t)(k0 + row) * a.D + n0 + 8 * c);  // k0 + row
+        }
+    };
+    auto stage = [&](int buf) __attribute__((always_inline)) {
+        unsigned char* As = sm[buf];
+        unsigned char* Ws = As + ABYTES;
+#pragma unroll
+        for (int m = 0; m < APT; ++m) {
+            const int f = tid + THREADS * m, row = f / AC, c = f % AC;
+            if (AF32) {
+                const float v[4] = {__uint_as_float(pa[m].x), __uint_as_float(pa[m].y), __uint_as_float(pa[m].z),
+                                    __uint_as_float(pa[m].w)};
+                unsigned short h[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float x = rh_r16(v[j]);
+                    if (a.dbl) x = a.ascale * x;
+                    h[j] = row < a.B ? rh_f2h(x) : (unsigned short)0;
+                }
+                *reinterpret_cast<uint2*>(As + row * kH16Pitch + 8 * c) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+            } else {
+                *reinterpret_cast<uint4*>(As + row * kH16Pitch + 16 * c) = row < a.B ? pa[m] : make_uint4(0, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < WPT; ++m) {
+            const int f = tid + THREADS * m, row = f / WC, c = f % WC;
+            *reinterpret_cast<uint4*>(Ws + row * (NT ? kH16Pitch : kH16NnPitch) + 16 * c) = pw[m];
+        }
+    };
+    fetch(kb);
+    stage(0);
+    __syncthreads();
+    int buf = 0;
+    for (int k0 = 0; k0 < klen; k0 += BK) {
+        const bool more = k0 + BK < klen;
+        if (more) fetch(kb + k0 + BK);                    // global -> registers while the matrix cores work on this slab
+        const unsigned char* As = sm[buf];
+        const unsigned char* Ws = As + ABYTES;
+#pragma unroll
+        for (int t = 0; t < BK / 16; ++t) {               // lane (kh, jj): row / column jj, k = 16 t + 8 kh + (0..7)
+            const rh_h8 av = *reinterpret_cast<const rh_h8*>(As + (wave * 32 + jj) * kH16Pitch + (16 * t + 8 * kh) * 2);
+            rh_h8 bv;
+            if (NT) {
+                bv = *reinterpret_cast<const rh_h8*>(Ws + jj * kH16Pitch + (16 * t + 8 * kh) * 2);
+            } else {
+                bv = __builtin_bit_cast(rh_h8, rh_tr_operand<kH16NnPitch>(Ws + 16 * t * kH16NnPitch, 0, lane));
+            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, acc, 0, 0, 0);
+        }
+        if (more) stage(buf ^ 1);                         // the other buffer: last read one barrier ago
+        __syncthreads();
+        buf ^= 1;
+    }
+    strip32_store(acc, a.part, strip, split, a.S, tile32_floats(WV));
+}
+
+struct Rh16FwdArgs {
+    const float* gamma; const float* beta;
+    float* run_mean; float* run_var;
+    unsigned short* P; unsigned short* H; float* mean; float* invstd;
+    int B, D, act, training;
+    float momentum, eps;
+};
+
+// P = r(sum of the partial tiles); BatchNorm1d statistics in fp32 over the fp16 values of P; N = r(BN(P)), H = r(act(N))
+__global__ __launch_bounds__(256) void rh_fwd16_epi_kernel(Rh16FwdArgs a, const float* part, int S) {
+    __shared__ float red[32];
+    const Epi32 e(blockIdx.x, blockIdx.y);
+    f32x4 acc = strip32_sum(part, blockIdx.x, blockIdx.y, S, e);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = rh_r16(acc[r]);  // padded rows hold exact zeros
+    const int col = e.col;
+    float mu, istd;
+    if (a.training) {
+        mu = column_total8((acc[0] + acc[1]) + (acc[2] + acc[3]), red) / (float)a.B;
+        float q = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float dlt = acc[r] - mu;
+            if (e.row0 + r < a.B) q = fmaf(dlt, dlt, q);
+        }
+        const float var = column_total8(q, red) / (float)a.B;
+        istd = 1.0f / sqrtf(var + a.eps);
+        if (threadIdx.x < 8 && a.run_mean != nullptr) {
+            const float unb = a.B > 1 ? var * (float)a.B / (float)(a.B - 1) : var;
+            a.run_mean[col] = (1.f - a.momentum) * a.run_mean[col] + a.momentum * mu;
+            a.run_var[col] = (1.f - a.momentum) * a.run_var[col] + a.momentum * unb;
+        }
+    } else {
+        mu = a.run_mean[col];
+        istd = 1.0f / sqrtf(a.run_var[col] + a.eps);
+    }
+    if (threadIdx.x < 8) { a.mean[col] = mu; a.invstd[col] = istd; }
+    const float g = a.gamma[col], bt = a.beta[col];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = e.row0 + r;
+        if (row < a.B) {
+            const float p = acc[r];
+            const float n = rh_r16(fmaf((p - mu) * istd, g, bt));
+            a.P[(size_t)row * a.D + col] = rh_f2h(p);
+            a.H[(size_t)row * a.D + col] = rh_f2h(act_fwd(n, a.act));
+        }
+    }
+}
+
+struct Rh16OutArgs { const float* base; void* out; int B, D; float scale; };
+
+// Q = r(sum of the partial tiles); out = base + r(scale Q) in fp32, or r(scale Q) as fp16 without a base
+__global__ __launch_bounds__(256) void rh_out16_epi_kernel(Rh16OutArgs a, const float* part, int S) {
+    const Epi32 e(blockIdx.x, blockIdx.y);
+    const f32x4 acc = strip32_sum(part, blockIdx.x, blockIdx.y, S, e);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = e.row0 + r;
+        if (row < a.B) {
+            const size_t o = (size_t)row * a.D + e.col;
+            const float v = rh_r16(a.scale * rh_r16(acc[r]));
+            if (a.base != nullptr) static_cast<float*>(a.out)[o] = a.base[o] + v;
+            else static_cast<unsigned short*>(a.out)[o] = rh_f2h(v);
+        }
+    }
+}
+
+struct Rh16BwdArgs {
+    const float* gamma; const unsigned short* P; const unsigned short* H; const float* mean; const float* invstd;
+    unsigned short* dP; float* g_gamma; float* g_beta;
+    int B, D, act, training;
+};
+
+// dH = sum of the partial tiles of gQ K16^T (fp32); through the activation and the BatchNorm -> dP = r(...), dgamma, dbeta
+__global__ __launch_bounds__(256) void rh_bwd16_epi_kernel(Rh16BwdArgs a, const float* part, int S) {
+    __shared__ float red[32];
+    const Epi32 e(blockIdx.x, blockIdx.y);
+    f32x4 acc = strip32_sum(part, blockIdx.x, blockIdx.y, S, e);
+    const int col = e.col;
+    const float mu = a.mean[col], istd = a.invstd[col], g = a.gamma[col];
+    float sb = 0.f, sg = 0.f;
+    f32x4 xh;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = e.row0 + r;
+        float dhn = 0.f, xhat = 0.f;
+        if (row < a.B) {
+            const size_t o = (size_t)row * a.D + col;
+            dhn = acc[r] * act_bwd(rh_h2f(a.H[o]), a.act);
+            xhat = (rh_h2f(a.P[o]) - mu) * istd;
+        }
+        acc[r] = dhn;
+        xh[r] = xhat;
+        sb += dhn;
+        sg = fmaf(dhn, xhat, sg);
+    }
+    const float dbeta = column_total8(sb, red);
+    const float dgamma = column_total8(sg, red);
+    if (threadIdx.x < 8) { a.g_beta[col] = dbeta; a.g_gamma[col] = dgamma; }
+    const float inv_b = 1.0f / (float)a.B;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = e.row0 + r;
+        if (row < a.B) {
+            const float dhn = acc[r];
+            const float dp = a.training ? g * istd * (dhn - (dbeta + xh[r] * dgamma) * inv_b) : g * istd * dhn;
+            a.dP[(size_t)row * a.D + col] = rh_f2h(dp);
+        }
+    }
+}
+
+struct RhOuter16Args {
+    const unsigned short* A1; const float* B1; const unsigned short* A2; const float* B2;
+    float* out;
+    int B, D;
+    float s2;
+};
+
+// out[i][j] = sum_b A1[b][i] r(B1[b][j]) + sum_b A2[b][i] r(s2 r(B2[b][j])): dK = dP^T r(X) + H^T gQ with fp16 operands.
+// The 64 x 192 tiles of rh_outer_split_kernel with one fp16 piece instead of three bf16 ones: a slab is 16 batch rows
+// (one contraction group) deposited as [batch row][feature] images, both operands through ds_read_b64_tr_b16.
+template <int TI, int TJ>
+__global__ __launch_bounds__(kRhThreads) void rh_outer16_kernel(RhOuter16Args a) {
+    constexpr int BKB = 16, NI = TI / 64, NJ = TJ / 64;
+    constexpr int PA = TI * 2 + 16, PB = TJ * 2 + 16;      // bytes per image row (16 bytes of padding)
+    constexpr int IA = BKB * PA, BUF = BKB * (PA + PB);
+    constexpr int AC = TI / 8, BC = TJ / 4;                // 16-byte loads per batch row: fp16 A, fp32 B
+    constexpr int APT = (BKB * AC + kRhThreads - 1) / kRhThreads, BPT = BKB * BC / kRhThreads;
+    static_assert(BKB * BC % kRhThreads == 0 && TI % 64 == 0 && TJ % 64 == 0, "tile shape");
+    __shared__ __attribute__((aligned(16))) unsigned char S[2][BUF];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, jj = lane & 31, kh = lane >> 5;
+    const int i0 = blockIdx.y * TI, j0 = blockIdx.x * TJ;
+    const int wi = wave >> 1, wj = wave & 1;
+    f32x16 acc[NI][NJ];
+#pragma unroll
+    for (int p = 0; p < NI; ++p)
+#pragma unroll
+        for (int q = 0; q < NJ; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[p][q][r] = 0.f;
+    const int Bp = (a.B + BKB - 1) / BKB * BKB;           // (the two products are walked as 2 Bp virtual batch rows)
+    uint4 pa[APT];
+    float4 pb[BPT];
+    auto fetch = [&](int v) __attribute__((always_inline)) {
+        const bool second = v >= Bp;
+        const unsigned short* A = second ? a.A2 : a.A1;
+        const float* Bm = second ? a.B2 : a.B1;
+        const int b0 = second ? v - Bp : v;
+#pragma unroll
+        for (int m = 0; m < APT; ++m) {
+            const int f = tid + kRhThreads * m, row = f / AC, c = f % AC;
+            pa[m] = make_uint4(0, 0, 0, 0);
+            if (f < BKB * AC && b0 + row < a.B)           // (D is a multiple of 64: TI columns never straddle the edge)
+                pa[m] = *reinterpret_cast<const uint4*>(A + (size_t)(b0 + row) * a.D + i0 + 8 * c);
+        }
+#pragma unroll
+        for (int m = 0; m < BPT; ++m) {
+            const int f = tid + kRhThreads * m, row = f / BC, c = f % BC;
+            pb[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (b0 + row < a.B && j0 + 4 * c < a.D) pb[m] = *reinterpret_cast<const float4*>(Bm + (size_t)(b0 + row) * a.D + j0 + 4 * c);
+        }
+    };
+    auto stage = [&](int buf, bool second) __attribute__((always_inline)) {
+        unsigned char* base = S[buf];
+#pragma unroll
+        for (int m = 0; m < APT; ++m) {
+            const int f = tid + kRhThreads * m, row = f / AC, c = f % AC;
+            if (f < BKB * AC) *reinterpret_cast<uint4*>(base + row * PA + 16 * c) = pa[m];
+        }
+#pragma unroll
+        for (int m = 0; m < BPT; ++m) {
+            const int f = tid + kRhThreads * m, row = f / BC, c = f % BC;
+            const float v[4] = {pb[m].x, pb[m].y, pb[m].z, pb[m].w};
+            unsigned short h[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[j] = rh_f2h(second ? a.s2 * rh_r16(v[j]) : v[j]);
+            *reinterpret_cast<uint2*>(base + IA + row * PB + 8 * c) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+        }
+    };
+    const int total = 2 * Bp;
+    fetch(0);
+    stage(0, false);
+    __syncthreads();
+    int buf = 0;
+    for (int v = 0; v < total; v += BKB) {
+        const bool more = v + BKB < total;
+        if (more) fetch(v + BKB);
+        const unsigned char* ia = S[buf];
+        const unsigned char* ib = ia + IA;
+        rh_h8 af[NI];
+#pragma unroll
+        for (int p = 0; p < NI; ++p) af[p] = __builtin_bit_cast(rh_h8, rh_tr_operand<PA>(ia, wi * NI + p, lane));
+#pragma unroll
+        for (int q = 0; q < NJ; ++q) {
+            const rh_h8 bf = __builtin_bit_cast(rh_h8, rh_tr_operand<PB>(ib, wj * NJ + q, lane));
+#pragma unroll
+            for (int p = 0; p < NI; ++p) acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[p], bf, acc[p][q], 0, 0, 0);
+        }
+        if (more) stage(buf ^ 1, v + BKB >= Bp);          // the other buffer: last read one barrier ago
+        __syncthreads();
+        buf ^= 1;
+    }
+#pragma unroll
+    for (int p = 0; p < NI; ++p)
+#pragma unroll
+        for (int q = 0; q < NJ; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int i = i0 + (wi * NI + p) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int j = j0 + (wj * NJ + q) * 32 + jj;
+                if (i < a.D && j < a.D) a.out[(size_t)i * a.D + j] = acc[p][q][r];
+            }
+}
+
+// K16 = r(K), four elements per thread
+__global__ __launch_bounds__(256) void rh_k_to_f16_kernel(const float* __restrict__ K, unsigned short* __restrict__ K16, size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const float4 v = reinterpret_cast<const float4*>(K)[i];
+        reinterpret_cast<uint2*>(K16)[i] = make_uint2(rh_f2h(v.x) | (rh_f2h(v.y) << 16), rh_f2h(v.z) | (rh_f2h(v.w) << 16));
+    }
+}
+
+bool rh16_dims_ok(int B, int D) { return B >= 1 && B <= kRhRows32 && D >= 64 && (D % 64) == 0; }
+// split of a strip's contraction: slices of whole 64-wide slabs, at most 8 (96 strips x 8 at D = 3072)
+int rh_split16(int D) {
+    int S = 8;
+    while (S > 1 && D % (S * kH16Bk) != 0) S >>= 1;
+    return S;
+}
+size_t rh_split16_bytes(int B, int D) { return (size_t)(D / kS32Cols) * rh_split16(D) * tile32_floats(rh_waves32(B)) * sizeof(float); }
+
+template <bool NT, bool AF32>
+int launch_part16(const void* A, const unsigned short* W, int B, int D, float ascale, int dbl, void* ws, hipStream_t st) {
+    const int S = rh_split16(D);
+    RhPart16Args a{A, W, static_cast<float*>(ws), B, D, S, dbl, ascale};
+    if (rh_waves32(B) == 2) hipLaunchKernelGGL((rh_part16_kernel<NT, 2, AF32>), dim3(D / kS32Cols, S), dim3(128), 0, st, a);
+    else hipLaunchKernelGGL((rh_part16_kernel<NT, 4, AF32>), dim3(D / kS32Cols, S), dim3(256), 0, st, a);
+    return check_launch();
+}
+
 }  // namespace
 }  // namespace pde
 
@@ -1043,6 +1395,78 @@ int pde_sym_layer_backward(int32_t B, int32_t D, int32_t act, int32_t training, 
     static const bool split = getenv("PDE_RH_NO_SPLIT") == nullptr;
     if (split) return launch_outer_split<kOutTi, kOutTj>(o, D, st);
     hipLaunchKernelGGL(rh_outer_kernel, dim3((D + kOutTj - 1) / kOutTj, (D + kOutTi - 1) / kOutTi), dim3(kRhThreads), 0, st, o);
+    return check_launch();
+}
+
+}  // extern "C"
+
+// ---- the fp16-operand layer (CUDA fp16 autocast's rounding points) ----
+extern "C" {
+
+int pde_sym_layer_f16_supported(int32_t B, int32_t D) { return rh16_dims_ok(B, D) ? 1 : 0; }
+
+size_t pde_sym_layer_f16_workspace_bytes(int32_t B, int32_t D) { return rh16_dims_ok(B, D) ? rh_split16_bytes(B, D) : 0; }
+
+int pde_sym_k_to_f16(int32_t D, const float* K, uint16_t* K16, void* stream) {
+    if (D < 64 || (D % 64) != 0 || !K || !K16) return PDE_E_BADARG;
+    const size_t n4 = (size_t)D * D / 4;
+    const int blocks = (int)(n4 / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+    hipLaunchKernelGGL(rh_k_to_f16_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), K, K16, n4);
+    return check_launch();
+}
+
+int pde_sym_layer_f16_forward(int32_t B, int32_t D, int32_t act, int32_t training, const float* X, const uint16_t* K16,
+                              const float* bn_weight, const float* bn_bias, float* running_mean, float* running_var,
+                              float momentum, float eps, const float* base, float scale, uint16_t* P, uint16_t* H,
+                              float* mean, float* invstd, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!rh16_dims_ok(B, D)) return PDE_E_BADARG;
+    if (!X || !K16 || !bn_weight || !bn_bias || !P || !H || !mean || !invstd || !out) return PDE_E_BADARG;
+    if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
+    if (!training && (!running_mean || !running_var)) return PDE_E_BADARG;
+    if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = rh_split16(D), thr = 64 * rh_waves32(B);
+    const float* part = static_cast<const float*>(workspace);
+    int rc = launch_part16<true, true>(X, K16, B, D, 1.0f, 0, workspace, st);
+    if (rc != PDE_OK) return rc;
+    Rh16FwdArgs f{bn_weight, bn_bias, running_mean, running_var, P, H, mean, invstd, B, D, act, training ? 1 : 0, momentum, eps};
+    hipLaunchKernelGGL(rh_fwd16_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, f, part, S);
+    if ((rc = check_launch()) != PDE_OK) return rc;
+    rc = launch_part16<false, false>(H, K16, B, D, 1.0f, 0, workspace, st);
+    if (rc != PDE_OK) return rc;
+    Rh16OutArgs o{base, out, B, D, scale};
+    hipLaunchKernelGGL(rh_out16_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, o, part, S);
+    return check_launch();
+}
+
+int pde_sym_layer_f16_backward(int32_t B, int32_t D, int32_t act, int32_t training, const float* g_out, float scale,
+                               const float* X, const uint16_t* K16, const float* bn_weight, const uint16_t* P,
+                               const uint16_t* H, const float* mean, const float* invstd, uint16_t* dP, float* gX,
+                               float* gK, float* g_bn_weight, float* g_bn_bias, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    if (!rh16_dims_ok(B, D)) return PDE_E_BADARG;
+    if (!g_out || !X || !K16 || !bn_weight || !P || !H || !mean || !invstd || !dP || !gX || !gK || !g_bn_weight || !g_bn_bias)
+        return PDE_E_BADARG;
+    if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
+    if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = rh_split16(D), thr = 64 * rh_waves32(B);
+    const float* part = static_cast<const float*>(workspace);
+    int rc = launch_part16<true, true>(g_out, K16, B, D, scale, 1, workspace, st);       // gQ = r(scale r(g)) staged
+    if (rc != PDE_OK) return rc;
+    Rh16BwdArgs b{bn_weight, P, H, mean, invstd, dP, g_bn_weight, g_bn_bias, B, D, act, training ? 1 : 0};
+    hipLaunchKernelGGL(rh_bwd16_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, b, part, S);
+    if ((rc = check_launch()) != PDE_OK) return rc;
+    rc = launch_part16<false, false>(dP, K16, B, D, 1.0f, 0, workspace, st);
+    if (rc != PDE_OK) return rc;
+    RhAxpyArgs x{nullptr, nullptr, nullptr, gX, B, D, 1.0f};
+    hipLaunchKernelGGL(rh_axpy32_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, x, part, S);
+    if ((rc = check_launch()) != PDE_OK) return rc;
+    RhOuter16Args o{dP, X, H, g_out, gK, B, D, scale};
+    hipLaunchKernelGGL((rh_outer16_kernel<kOutTi, kOutTj>), dim3((D + kOutTj - 1) / kOutTj, (D + kOutTi - 1) / kOutTi),
+                       dim3(kRhThreads), 0, st, o);
     return check_launch();
 }
 

@@ -229,7 +229,10 @@ class SymmetricLayer(nn.Module):
     activation run on the fp32 matrix cores (``functional.sym_layer``, pde_rh.hip — SURVEY §8f-4: up to 128 rows each product
     as 32-column strips with the contraction split over workgroups plus a small epilogue launch);
     ``residual(base, X, scale)`` is the fused update ``base + scale * (act(BN(X K^T)) K)`` the two blocks below are made
-    of.  ``fused = False`` (or a shape the kernels do not take, or autocast) is plain torch, as in the reference."""
+    of.  Under ``torch.autocast("cuda", torch.float16)`` the same kernels run on fp16 operands with autocast's rounding
+    points (``functional.sym_layer(..., K16=...)``): ``forward`` returns fp16 and ``residual`` fp32, as plain
+    autocast does; the blocks below make K16 once per block forward and share it across their steps.  ``fused = False``
+    (or a shape the kernels do not take, or bf16 autocast) is plain torch, as in the reference."""
 
     def __init__(self, channels, spatial_size, activation="relu"):
         super().__init__()
@@ -246,13 +249,28 @@ class SymmetricLayer(nn.Module):
     def _fused_ok(self, X):
         return self.fused and F_.sym_layer_supported(X, self.norm)
 
-    def residual(self, base, X, scale):
-        """base + scale * (act(BN(X K^T)) K): one step of the Parabolic / Hamiltonian blocks."""
+    def k16(self, X):
+        """fp16 autocast's copy of K for calls on inputs like X, or None where the fp16-operand path does not run.  Made
+        afresh on every call: K changes in place between forwards (optimizer steps, a replayed graph)."""
+        if self.fused and F_.sym_layer_f16_supported(X, self.norm):
+            return F_.sym_k16(self.K.weight)
+        return None
+
+    def residual(self, base, X, scale, K16=None):
+        """base + scale * (act(BN(X K^T)) K): one step of the Parabolic / Hamiltonian blocks.  K16: ``k16(X)`` of this
+        block forward (made here when not given)."""
+        if K16 is None:
+            K16 = self.k16(X)
+        if K16 is not None:
+            return F_.sym_layer(X, self.K.weight, self.norm, self.act_name, base=base, scale=scale, K16=K16)
         if self._fused_ok(X):
             return F_.sym_layer(X, self.K.weight, self.norm, self.act_name, base=base, scale=scale)
         return base + scale * (-self.forward(X))
 
     def forward(self, Y):
+        K16 = self.k16(Y)
+        if K16 is not None:
+            return F_.sym_layer(Y, self.K.weight, self.norm, self.act_name, base=None, scale=-1.0, K16=K16)
         if self._fused_ok(Y):
             return F_.sym_layer(Y, self.K.weight, self.norm, self.act_name, base=None, scale=-1.0)
         B = Y.shape[0]
@@ -270,8 +288,9 @@ class ParabolicBlock(nn.Module):
         print(f"Parabolic Block: {num_steps} steps, dt={dt}")
 
     def forward(self, Y):
+        K16 = self.symmetric_layer.k16(Y)                              # one fp16 copy of K per forward under fp16 autocast
         for _ in range(self.num_steps):
-            Y = self.symmetric_layer.residual(Y, Y, -self.dt)          # Y + dt * F_sym(Y)
+            Y = self.symmetric_layer.residual(Y, Y, -self.dt, K16)     # Y + dt * F_sym(Y)
         return Y
 
 
@@ -287,9 +306,10 @@ class HamiltonianBlock(nn.Module):
 
     def forward(self, Y):
         Z = torch.zeros_like(Y)
+        KY, KZ = self.F_Y.k16(Y), self.F_Z.k16(Y)                     # one fp16 copy of each K per forward under fp16 autocast
         for _ in range(self.num_steps):
-            Y = self.F_Y.residual(Y, Z, self.dt)                       # Y - dt * F_Y(Z)
-            Z = self.F_Z.residual(Z, Y, self.dt)                       # Z - dt * F_Z(Y)
+            Y = self.F_Y.residual(Y, Z, self.dt, KY)                   # Y - dt * F_Y(Z)
+            Z = self.F_Z.residual(Z, Y, self.dt, KZ)                   # Z - dt * F_Z(Y)
         return Y
 
 

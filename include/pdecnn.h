@@ -405,6 +405,36 @@ int pde_sym_layer_backward(int32_t B, int32_t D, int32_t act, int32_t training,
                            float* dP, float* gX, float* gK, float* g_bn_weight, float* g_bn_bias,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same layer under CUDA fp16 autocast, on the fp16 matrix cores ---------------------- */
+
+/* The rounding points of torch.autocast("cuda", torch.float16) for the layer above, r() = round to fp16 (overflow to
+ * +-inf), accumulation in fp32:
+ *     P = r(r(X) K16^T);  N = r(BatchNorm1d(P));  H = r(act(N));  Q = r(H K16);  out = base + r(scale Q)
+ * K16: (D, D) fp16 = r(K) (pde_sym_k_to_f16, once per autocast region).  X, base: (B, D) fp32.  P, H: (B, D) fp16,
+ * written for the backward.  out: fp16 (B, D) = r(scale Q) when base is NULL (F_sym(Y) is scale = -1), fp32 (B, D)
+ * otherwise.  Statistics, running statistics, mean and invstd as in pde_sym_layer_forward.  1 <= B <= 128 and D a
+ * multiple of 64 (pde_sym_layer_f16_supported).  workspace: pde_sym_layer_f16_workspace_bytes(B, D) bytes, 16-byte
+ * aligned, not NULL (the partial tiles of the split products; no two calls that share it in flight at once).
+ * fp16 tensors are passed as their 16-bit patterns. */
+int pde_sym_layer_f16_supported(int32_t B, int32_t D);
+size_t pde_sym_layer_f16_workspace_bytes(int32_t B, int32_t D);
+/* K16 = r(K), K: (D, D) fp32 */
+int pde_sym_k_to_f16(int32_t D, const float* K, uint16_t* K16, void* stream);
+int pde_sym_layer_f16_forward(int32_t B, int32_t D, int32_t act, int32_t training,
+                              const float* X, const uint16_t* K16, const float* bn_weight, const float* bn_bias,
+                              float* running_mean, float* running_var, float momentum, float eps,
+                              const float* base, float scale,
+                              uint16_t* P, uint16_t* H, float* mean, float* invstd, void* out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* Backward for an fp32 upstream gradient g_out (B, D) of `out` (an fp16 one widened by the caller), with autocast's
+ * fp16 operands: gQ = r(scale r(g_out)), dP = r(BatchNorm backward of (gQ K16^T) act'(H)) written to dP (B, D) fp16;
+ * gX = dP K16, gK = dP^T r(X) + H^T gQ (D, D), g_bn_weight[D], g_bn_bias[D] in fp32.  X is the forward's fp32 input. */
+int pde_sym_layer_f16_backward(int32_t B, int32_t D, int32_t act, int32_t training,
+                               const float* g_out, float scale, const float* X, const uint16_t* K16, const float* bn_weight,
+                               const uint16_t* P, const uint16_t* H, const float* mean, const float* invstd,
+                               uint16_t* dP, float* gX, float* gK, float* g_bn_weight, float* g_bn_bias,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- utilities ------------------------------------------------------------------------- */
 
 /* Average device time (ms) per launch of the dominant kernel of the most recent
