@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("PDECNN_LIB") or os.path.join(HERE, "lib", "libpdecnn_
 
 PDE_MAX_SWEEPS = 96
 PDE_MAX_N = 32
-PDE_IO_F32, PDE_IO_BF16 = 0, 1
+PDE_IO_F32, PDE_IO_BF16, PDE_IO_F64 = 0, 1, 2
 PDE_AXIS_X, PDE_AXIS_Y = 0, 1
 
 ERRORS = {
@@ -35,6 +35,16 @@ class PdeAdiDesc(C.Structure):
                 ("clamp_max", C.c_float), ("eps", C.c_float), ("sweep", PdeSweep * PDE_MAX_SWEEPS)]
 
 
+class PdeSweepF64(C.Structure):
+    _fields_ = [("axis", C.c_int32), ("pad", C.c_int32), ("delta", C.c_double), ("h2", C.c_double), ("t", C.c_double)]
+
+
+class PdeAdiDescF64(C.Structure):
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("N", C.c_int32), ("io_dtype", C.c_int32),
+                ("num_sweeps", C.c_int32), ("smooth3", C.c_int32), ("has_clamp_max", C.c_int32), ("pad", C.c_int32),
+                ("clamp_max", C.c_double), ("eps", C.c_double), ("sweep", PdeSweepF64 * PDE_MAX_SWEEPS)]
+
+
 class PdeSmallLayer(C.Structure):
     """One of the layers that share an input in pde_adi_multi_* (include/pdecnn.h)."""
     _fields_ = [("desc", C.POINTER(PdeAdiDesc)), ("sweeps_per_step", C.c_int32), ("mode", C.c_int32),
@@ -53,8 +63,9 @@ class PdeError(RuntimeError):
     pass
 
 
-_vp, _fp, _sz, _i32, _f32 = C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_float
+_vp, _fp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
 _D = C.POINTER(PdeAdiDesc)
+_D64 = C.POINTER(PdeAdiDescF64)
 
 # name -> (restype, argtypes): must list every symbol include/pdecnn.h declares
 SIGNATURES = {
@@ -123,6 +134,26 @@ SIGNATURES = {
                                             _vp, _vp, _fp, _fp, _vp, _vp, _sz, _vp]),
     "pde_sym_layer_f16_backward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _f32, _fp, _vp, _fp, _vp, _vp, _fp, _fp,
                                              _vp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "pde_adi_f64_forward_workspace_bytes": (_sz, [_D64]),
+    "pde_adi_f64_backward_workspace_bytes": (_sz, [_D64, _i32]),
+    "pde_adi_f64_forward": (C.c_int, [_D64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_f64_backward": (C.c_int, [_D64, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_channel_mix_f64_forward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pde_channel_mix_f64_backward_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "pde_channel_mix_f64_backward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_channel_mix_f64_backward_steps": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _i32, _vp]),
+    "pde_skip_blend_f64_forward": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "pde_skip_blend_f64_backward_workspace_bytes": (_sz, [C.c_int64]),
+    "pde_skip_blend_f64_backward": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_explicit5_f64_forward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _vp, _vp,
+                                            _vp]),
+    "pde_explicit5_f64_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "pde_explicit5_f64_backward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32,
+                                             _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_jacobi_f64_forward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pde_jacobi_f64_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "pde_jacobi_f64_backward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pde_timing_enable": (C.c_int, [_i32]),
     "pde_timing_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int64)]),

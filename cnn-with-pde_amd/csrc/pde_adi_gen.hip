@@ -5,84 +5,107 @@
 // (mnist_test.py:151-198) per line, the adjoint as the transposed recurrences, the state rebuilt backwards or read from
 // checkpoints exactly as the fused backward does, the clamp mask and the transposed 3-tap smoothing applied per sweep.
 // Correct and deterministic, not tuned: a plane of 64 x 64 keeps 64 threads busy.
+// The family is generic over the arithmetic type T: float (the PdeAdiDesc entry points of pde_adi.hip) and double (the
+// pde_adi_f64_* entry points at the end of this file, PdeAdiDescF64: schedule, clamp bounds and eps in double too).
 #include "pde_common.h"
 #include "pde_adi_gen.h"
+
+#include <type_traits>
 
 namespace pde {
 namespace {
 
 constexpr int kGenArr = 4;                  // per (sweep, channel): coeff | c* | 1/den | clamp pass-through, each [k][line]
 
-struct GenSweep { int axis; float t, scale, pad; };     // device copy of the schedule: scale = delta/h2 as floats divide
+template <typename T> struct GenSweep { int axis; T t, scale, pad; };   // device copy of the schedule: scale = delta/h2 in T
 
+__device__ __forceinline__ float gen_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double gen_max(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ float gen_min(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double gen_min(double a, double b) { return fmin(a, b); }
+
+// SW: PdeSweep (T = float) | PdeSweepF64 (T = double)
+template <typename T, typename SW>
 struct GenFactorArgs {
-    const float *ab, *bb, *as, *bs;
-    float* fac;                              // [S][C][kGenArr][N*N]
-    GenSweep* tab;                           // [S]
-    float* kmax;                             // nullptr | [S], zeroed before the launch
+    const T *ab, *bb, *as, *bs;
+    T* fac;                                  // [S][C][kGenArr][N*N]
+    GenSweep<T>* tab;                        // [S]
+    T* kmax;                                 // nullptr | [S], zeroed before the launch
     int C, N, S, smooth3, has_max;
-    float cmax, eps;
-    PdeSweep sweep[PDE_MAX_SWEEPS];
+    T cmax, eps;
+    SW sweep[PDE_MAX_SWEEPS];
 };
 
-__device__ __forceinline__ float block_max(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+template <typename T>
+__device__ __forceinline__ T block_max(T v, T* red) {
+    for (int o = 32; o > 0; o >>= 1) v = gen_max(v, __shfl_xor(v, o));
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) red[w] = v;
     __syncthreads();
-    float m = red[0];
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, red[i]);
+    T m = red[0];
+    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) m = gen_max(m, red[i]);
     return m;
 }
 
+// coefficients are positive: their bit patterns order like the values
+__device__ __forceinline__ void gen_atomic_max(float* p, float m) { atomicMax(reinterpret_cast<int*>(p), __float_as_int(m)); }
+__device__ __forceinline__ void gen_atomic_max(double* p, double m) {
+    atomicMax(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(m));
+}
+
 // one workgroup per (sweep, channel), one thread per line
-__global__ void gen_factor_kernel(GenFactorArgs a) {
-    __shared__ float red[4];
+template <typename T, typename SW>
+__global__ void gen_factor_kernel(GenFactorArgs<T, SW> a) {
+    __shared__ T red[4];
     const int s = blockIdx.x / a.C, c = blockIdx.x % a.C, N = a.N, ln = threadIdx.x;
-    const PdeSweep sw = a.sweep[s];
+    const SW sw = a.sweep[s];
     const int ax = sw.axis;
-    if (a.tab && c == 0 && ln == 0) a.tab[s] = GenSweep{ax, sw.t, sw.delta / sw.h2, 0.f};
-    float kmx = 0.f;
+    if (a.tab && c == 0 && ln == 0) a.tab[s] = GenSweep<T>{ax, sw.t, sw.delta / sw.h2, T(0)};
+    T kmx = T(0);
     if (ln < N) {
-        const float* base = (ax == PDE_AXIS_X ? a.ab : a.bb) + (size_t)c * N * N;
-        const float* slope = (ax == PDE_AXIS_X ? a.as : a.bs) + (size_t)c * N * N;
+        const T* base = (ax == PDE_AXIS_X ? a.ab : a.bb) + (size_t)c * N * N;
+        const T* slope = (ax == PDE_AXIS_X ? a.as : a.bs) + (size_t)c * N * N;
         const int lstride = (ax == PDE_AXIS_X) ? N : 1, kstride = (ax == PDE_AXIS_X) ? 1 : N;
-        float* f = a.fac ? a.fac + ((size_t)s * a.C + c) * kGenArr * N * N : nullptr;   // nullptr: the maxima alone
+        T* f = a.fac ? a.fac + ((size_t)s * a.C + c) * kGenArr * N * N : nullptr;   // nullptr: the maxima alone
         auto raw = [&](int k) { const int i = ln * lstride + k * kstride; return base[i] + slope[i] * sw.t; };
         auto theta = [&](int k) {
-            float th = fmaxf(raw(k), a.eps);
-            if (a.has_max) th = fminf(th, a.cmax);
+            T th = gen_max(raw(k), a.eps);
+            if (a.has_max) th = gen_min(th, a.cmax);
             return th;
         };
-        const float third = 1.0f / 3.0f;
-        float cs_prev = 0.f;
+        const T third = T(1) / T(3);
+        T cs_prev = T(0);
         for (int k = 0; k < N; ++k) {
-            const float r = raw(k);
+            const T r = raw(k);
             const bool pass = (r >= a.eps) && (!a.has_max || r <= a.cmax);
-            float th = theta(k);
+            T th = theta(k);
             if (a.smooth3) th = (theta(k > 0 ? k - 1 : 0) * third + th * third) + theta(k + 1 < N ? k + 1 : N - 1) * third;
-            const float co = th * sw.delta / sw.h2;
-            const float b = (k == 0 || k == N - 1) ? 1.0f + co : 1.0f + 2.0f * co;
-            const float den = (k ? b + co * cs_prev : b) + a.eps;
-            const float cs = (k < N - 1) ? -co / den : 0.f;
+            const T co = th * sw.delta / sw.h2;
+            const T b = (k == 0 || k == N - 1) ? T(1) + co : T(1) + T(2) * co;
+            const T den = (k ? b + co * cs_prev : b) + a.eps;
+            const T cs = (k < N - 1) ? -co / den : T(0);
             if (f) {
                 const size_t o = (size_t)k * N + ln;
                 f[o] = co;
                 f[(size_t)N * N + o] = cs;
-                f[(size_t)2 * N * N + o] = 1.0f / den;
-                f[(size_t)3 * N * N + o] = pass ? 1.0f : 0.f;
+                f[(size_t)2 * N * N + o] = T(1) / den;
+                f[(size_t)3 * N * N + o] = pass ? T(1) : T(0);
             }
             cs_prev = cs;
-            kmx = fmaxf(kmx, co);
+            kmx = gen_max(kmx, co);
         }
     }
     if (a.kmax) {
-        const float m = block_max(kmx, red);
-        if (threadIdx.x == 0) atomicMax(reinterpret_cast<int*>(a.kmax) + s, __float_as_int(m));   // coefficients are positive
+        const T m = block_max(kmx, red);
+        if (threadIdx.x == 0) gen_atomic_max(a.kmax + s, m);
     }
 }
 
 template <typename IO> struct GenIo;
+template <> struct GenIo<double> {
+    __device__ static double ld(const void* p, size_t i) { return static_cast<const double*>(p)[i]; }
+    __device__ static void st(void* p, size_t i, double v) { static_cast<double*>(p)[i] = v; }
+};
 template <> struct GenIo<float> {
     __device__ static float ld(const void* p, size_t i) { return static_cast<const float*>(p)[i]; }
     __device__ static void st(void* p, size_t i, float v) { static_cast<float*>(p)[i] = v; }
@@ -95,16 +118,18 @@ template <> struct GenIo<gen_bf16> {
     __device__ static void st(void* p, size_t i, float v) { static_cast<unsigned short*>(p)[i] = f32_to_bf16_hw(v); }
 };
 
+template <typename T>
 struct GenSweepArgs {
     const void *in0, *in1;                   // forward: u, -; backward: gy, y
     void* out;                               // forward: y (nullptr: checkpoint pre-pass); backward: gu
-    const float* fac;
-    const GenSweep* tab;
-    float* ckpt;                             // [nck][B][C][N*N] fp32 | nullptr
-    float* part;                             // backward: [G][C][4][N*N]
+    const T* fac;
+    const GenSweep<T>* tab;
+    T* ckpt;                                 // [nck][B][C][N*N] in T | nullptr
+    T* part;                                 // backward: [G][C][4][N*N]
     unsigned long long ck[2];
     int B, C, N, S, G;
-    float eps;
+    T eps;
+    T* xg;                                   // backward with the state plane in global memory: [G*C][N][N+1] | nullptr
 };
 
 __device__ __forceinline__ int gen_ck_bit(const unsigned long long (&ck)[2], int s) { return (int)((ck[s >> 6] >> (s & 63)) & 1ull); }
@@ -121,25 +146,26 @@ __device__ __forceinline__ int gen_ck_slot(const unsigned long long (&ck)[2], in
 constexpr int kGenBatch = 8;
 
 // forward: one workgroup per plane; sweeps 0..S-1 on the plane in LDS ([row][N+1])
-template <typename IO>
-__global__ void gen_fwd_kernel(GenSweepArgs a) {
-    extern __shared__ float X[];
+template <typename TT, typename IO>
+__global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
+    extern __shared__ float gen_fsmem[];
+    TT* X = reinterpret_cast<TT*>(gen_fsmem);
     const int N = a.N, ld = N + 1, tid = threadIdx.x, T = blockDim.x, NN = N * N;
     const size_t plane = (size_t)NN, pb = (size_t)blockIdx.x * plane;         // blockIdx = b*C + c
     const int c = blockIdx.x % a.C;
     for (int e = tid; e < NN; e += T) X[(e / N) * ld + (e % N)] = GenIo<IO>::ld(a.in0, pb + e);
     __syncthreads();
     for (int s = 0; s < a.S; ++s) {
-        const GenSweep sw = a.tab[s];
+        const GenSweep<TT> sw = a.tab[s];
         if (tid < N) {
-            const float* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
-            float* v = X + (sw.axis == PDE_AXIS_X ? tid * ld : tid);
+            const TT* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
+            TT* v = X + (sw.axis == PDE_AXIS_X ? tid * ld : tid);
             const int st = (sw.axis == PDE_AXIS_X) ? 1 : ld;
             // d*_0 = d_0/den_0, d*_i = (d_i - a_i d*_{i-1})/den_i with a_i = -coeff_i   (mnist_test.py:167-185)
-            float prev = v[0] * f[2 * plane];
+            TT prev = v[0] * f[2 * plane];
             v[0] = prev;
             for (int k0 = 1; k0 < N; k0 += kGenBatch) {
-                float t[kGenBatch], co[kGenBatch], iv[kGenBatch];
+                TT t[kGenBatch], co[kGenBatch], iv[kGenBatch];
 #pragma unroll
                 for (int j = 0; j < kGenBatch; ++j) {
                     const int k = k0 + j < N ? k0 + j : N - 1;
@@ -156,7 +182,7 @@ __global__ void gen_fwd_kernel(GenSweepArgs a) {
             }
             // x_{N-1} = d*_{N-1}, x_i = d*_i - c*_i x_{i+1}                                (mnist_test.py:187-196)
             for (int k0 = N - 2; k0 >= 0; k0 -= kGenBatch) {
-                float t[kGenBatch], cs[kGenBatch];
+                TT t[kGenBatch], cs[kGenBatch];
 #pragma unroll
                 for (int j = 0; j < kGenBatch; ++j) {
                     const int k = k0 - j >= 0 ? k0 - j : 0;
@@ -173,7 +199,7 @@ __global__ void gen_fwd_kernel(GenSweepArgs a) {
         }
         __syncthreads();
         if (a.ckpt && gen_ck_bit(a.ck, s)) {
-            float* dst = a.ckpt + (size_t)gen_ck_slot(a.ck, s) * a.B * a.C * plane + pb;
+            TT* dst = a.ckpt + (size_t)gen_ck_slot(a.ck, s) * a.B * a.C * plane + pb;
             for (int e = tid; e < NN; e += T) dst[e] = X[(e / N) * ld + (e % N)];
         }
     }
@@ -186,22 +212,24 @@ __global__ void gen_fwd_kernel(GenSweepArgs a) {
 // ALDS: the four partial-sum images live in LDS beside the two planes and go to `part` once, at the end (chosen while four
 // workgroups still fit on a CU, see the launch); otherwise every update is a read-modify-write of global memory by the
 // owning thread.
-template <typename IO, bool ALDS>
-__global__ void gen_bwd_kernel(GenSweepArgs a, int smooth3) {
+// XG (T = double, N beyond the two-plane LDS limit): the state plane X lives in a global scratch slice the workgroup owns,
+// the adjoint plane R stays in LDS.
+template <typename TT, typename IO, bool ALDS, bool XG>
+__global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
     extern __shared__ float gen_smem[];
     const int N = a.N, ld = N + 1, tid = threadIdx.x, T = blockDim.x, NN = N * N;
-    float* X = gen_smem;
-    float* R = X + (size_t)N * ld;
-    float* ACC = R + (size_t)N * ld;                      // ALDS: [4][N][ld], indexed like the planes
+    TT* X = XG ? a.xg + (size_t)blockIdx.x * N * ld : reinterpret_cast<TT*>(gen_smem);
+    TT* R = XG ? reinterpret_cast<TT*>(gen_smem) : X + (size_t)N * ld;
+    TT* ACC = R + (size_t)N * ld;                         // ALDS: [4][N][ld], indexed like the planes
     const size_t plane = (size_t)NN;
     const int c = blockIdx.x % a.C, g = blockIdx.x / a.C;
-    float* part = a.part + ((size_t)g * a.C + c) * 4 * plane;
+    TT* part = a.part + ((size_t)g * a.C + c) * 4 * plane;
     if constexpr (ALDS) {
-        for (int e = tid; e < 4 * N * ld; e += T) ACC[e] = 0.f;
+        for (int e = tid; e < 4 * N * ld; e += T) ACC[e] = TT(0);
     } else {
-        for (size_t e = tid; e < 4 * plane; e += T) part[e] = 0.f;
+        for (size_t e = tid; e < 4 * plane; e += T) part[e] = TT(0);
     }
-    const float one_eps = 1.0f + a.eps, third = 1.0f / 3.0f;
+    const TT one_eps = TT(1) + a.eps, third = TT(1) / TT(3);
     for (int b = g; b < a.B; b += a.G) {
         const size_t pb = ((size_t)b * a.C + c) * plane;
         __syncthreads();
@@ -211,17 +239,17 @@ __global__ void gen_bwd_kernel(GenSweepArgs a, int smooth3) {
         }
         __syncthreads();
         for (int s = a.S - 1; s >= 0; --s) {
-            const GenSweep sw = a.tab[s];
+            const GenSweep<TT> sw = a.tab[s];
             if (tid < N) {
-                const float* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
+                const TT* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
                 const bool xs = sw.axis == PDE_AXIS_X;
-                float* r = R + (xs ? tid * ld : tid);
-                float* x = X + (xs ? tid * ld : tid);
+                TT* r = R + (xs ? tid * ld : tid);
+                TT* x = X + (xs ? tid * ld : tid);
                 const int st = xs ? 1 : ld;
                 // transposed recurrences: U^T w = r (unit lower, sub-diagonal c*), L^T lam = w (diagonal den, super-diagonal a)
-                float prev = r[0];
+                TT prev = r[0];
                 for (int k0 = 1; k0 < N; k0 += kGenBatch) {
-                    float t[kGenBatch], cs[kGenBatch];
+                    TT t[kGenBatch], cs[kGenBatch];
 #pragma unroll
                     for (int j = 0; j < kGenBatch; ++j) {
                         const int k = k0 + j < N ? k0 + j : N - 1;
@@ -238,7 +266,7 @@ __global__ void gen_bwd_kernel(GenSweepArgs a, int smooth3) {
                 prev = prev * f[2 * plane + (size_t)(N - 1) * N];
                 r[(N - 1) * st] = prev;
                 for (int k0 = N - 2; k0 >= 0; k0 -= kGenBatch) {
-                    float t[kGenBatch], co[kGenBatch], iv[kGenBatch];
+                    TT t[kGenBatch], co[kGenBatch], iv[kGenBatch];
 #pragma unroll
                     for (int j = 0; j < kGenBatch; ++j) {
                         const int k = k0 - j >= 0 ? k0 - j : 0;
@@ -256,14 +284,14 @@ __global__ void gen_bwd_kernel(GenSweepArgs a, int smooth3) {
                 // coefficient gradient -lam.q with the sweep's OUTPUT state, q = (Neumann second difference, sign flipped);
                 // x_old = (1+eps) x + coeff q; then the transposed smoothing (entry j is complete once k = j+1 is known),
                 // the clamp mask, and the two parameters: d/d base, d/d slope = t * d/d base
-                float* __restrict__ pbase = part + (xs ? 0 : 2) * plane;
-                float* __restrict__ pslope = pbase + plane;
+                TT* __restrict__ pbase = part + (xs ? 0 : 2) * plane;
+                TT* __restrict__ pslope = pbase + plane;
                 // partial sums in global memory are kept [k][line] for BOTH axes (threads of a wave then touch consecutive
                 // words; [line][k] made every x-sweep update a cache line of its own): the alpha images are stored
                 // transposed and gen_reduce_kernel turns them back
                 const int pl = tid, pk = N;
-                float* lbase = ACC + (xs ? 0 : 2) * N * ld + (xs ? tid * ld : tid);
-                auto add = [&](int j, float gv) __attribute__((always_inline)) {
+                TT* lbase = ACC + (xs ? 0 : 2) * N * ld + (xs ? tid * ld : tid);
+                auto add = [&](int j, TT gv) __attribute__((always_inline)) {
                     if constexpr (ALDS) {
                         lbase[j * st] += gv;
                         lbase[N * ld + j * st] += sw.t * gv;
@@ -272,33 +300,33 @@ __global__ void gen_bwd_kernel(GenSweepArgs a, int smooth3) {
                         pslope[pl + j * pk] += sw.t * gv;
                     }
                 };
-                float xm = 0.f, xc = x[0], g2 = 0.f, g1 = 0.f;            // x_{k-1}, x_k; gsm_{k-2}, gsm_{k-1}
+                TT xm = TT(0), xc = x[0], g2 = TT(0), g1 = TT(0);         // x_{k-1}, x_k; gsm_{k-2}, gsm_{k-1}
                 for (int k0 = 0; k0 < N; k0 += kGenBatch) {
-                    float xn[kGenBatch], lam[kGenBatch], co[kGenBatch], ps[kGenBatch], gout[kGenBatch];
+                    TT xn[kGenBatch], lam[kGenBatch], co[kGenBatch], ps[kGenBatch], gout[kGenBatch];
 #pragma unroll
                     for (int j = 0; j < kGenBatch; ++j) {
                         const int k = k0 + j < N ? k0 + j : N - 1;
-                        xn[j] = (k0 + j + 1 < N) ? x[(k0 + j + 1) * st] : 0.f;      // x_{k+1}
+                        xn[j] = (k0 + j + 1 < N) ? x[(k0 + j + 1) * st] : TT(0);    // x_{k+1}
                         lam[j] = r[k * st];
                         co[j] = f[(size_t)k * N];
                         ps[j] = f[3 * plane + (size_t)k * N];
                     }
-                    const float ps_before = k0 > 0 ? f[3 * plane + (size_t)(k0 - 1) * N] : 0.f;   // mask of entry k0-1 (smoothing)
+                    const TT ps_before = k0 > 0 ? f[3 * plane + (size_t)(k0 - 1) * N] : TT(0);   // mask of entry k0-1 (smoothing)
 #pragma unroll
                     for (int j = 0; j < kGenBatch; ++j) {
                         const int k = k0 + j;
-                        gout[j] = 0.f;
+                        gout[j] = TT(0);
                         if (k < N) {
-                            const float xp = xn[j];
-                            const float q = ((k == 0 || k == N - 1) ? xc : 2.0f * xc) - xm - xp;
-                            const float g0 = -lam[j] * q * sw.scale;
+                            const TT xp = xn[j];
+                            const TT q = ((k == 0 || k == N - 1) ? xc : TT(2) * xc) - xm - xp;
+                            const TT g0 = -lam[j] * q * sw.scale;
                             xn[j] = one_eps * xc + co[j] * q;                       // becomes x_old[k]
                             xm = xc;
                             xc = xp;
                             if (!smooth3) {
                                 gout[j] = g0 * ps[j];                               // entry k
                             } else if (k >= 1) {                                    // finishes entry k-1
-                                float gv = (g2 * third + g1 * third) + g0 * third;
+                                TT gv = (g2 * third + g1 * third) + g0 * third;
                                 if (k == 1) gv += g1 * third;                       // replicate end: theta_0 is used twice by sm_0
                                 gout[j] = gv * (j > 0 ? ps[j - 1] : ps_before);
                             }
@@ -317,13 +345,13 @@ __global__ void gen_bwd_kernel(GenSweepArgs a, int smooth3) {
                     }
                 }
                 if (smooth3) {                                             // entry N-1: (gsm_{N-2} + 2 gsm_{N-1}) / 3
-                    const float gv = (g2 * third + g1 * third) + g1 * third;
+                    const TT gv = (g2 * third + g1 * third) + g1 * third;
                     add(N - 1, gv * f[3 * plane + (size_t)(N - 1) * N]);
                 }
             }
             __syncthreads();
             if (s > 0 && a.ckpt && gen_ck_bit(a.ck, s - 1)) {             // the parked state instead of the rebuilt one
-                const float* src = a.ckpt + (size_t)gen_ck_slot(a.ck, s - 1) * a.B * a.C * plane + pb;
+                const TT* src = a.ckpt + (size_t)gen_ck_slot(a.ck, s - 1) * a.B * a.C * plane + pb;
                 for (int e = tid; e < NN; e += T) X[(e / N) * ld + (e % N)] = src[e];
                 __syncthreads();
             }
@@ -339,57 +367,166 @@ __global__ void gen_bwd_kernel(GenSweepArgs a, int smooth3) {
 }
 
 // the four parameter gradients: partial sums added over the groups in a fixed order
-__global__ void gen_reduce_kernel(const float* part, int G, int C, int N, float* g_ab, float* g_as, float* g_bb, float* g_bs) {
+template <typename T>
+__global__ void gen_reduce_kernel(const T* part, int G, int C, int N, T* g_ab, T* g_as, T* g_bb, T* g_bs) {
     const int NN = N * N, e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= C * NN) return;
     const int c = e / NN, p = e % NN, pt = (p % N) * N + p / N;        // the alpha images are stored transposed
-    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    T s[4] = {T(0), T(0), T(0), T(0)};
     for (int g = 0; g < G; ++g)
         for (int arr = 0; arr < 4; ++arr) s[arr] += part[(((size_t)g * C + c) * 4 + arr) * NN + (arr < 2 ? pt : p)];
     g_ab[e] = s[0]; g_as[e] = s[1]; g_bb[e] = s[2]; g_bs[e] = s[3];
 }
 
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-size_t fac_bytes(const PdeAdiDesc* d) { return up256((size_t)d->num_sweeps * d->C * kGenArr * d->N * d->N * sizeof(float)); }
-size_t tab_bytes_gen() { return up256(sizeof(GenSweep) * PDE_MAX_SWEEPS); }
-int gen_groups(const PdeAdiDesc* d) {
+template <typename T, typename D>
+size_t fac_bytes(const D* d) { return up256((size_t)d->num_sweeps * d->C * kGenArr * d->N * d->N * sizeof(T)); }
+template <typename T>
+size_t tab_bytes_gen() { return up256(sizeof(GenSweep<T>) * PDE_MAX_SWEEPS); }
+template <typename D>
+int gen_groups(const D* d) {
     int G = (1024 + d->C - 1) / d->C;
     return G > d->B ? d->B : (G < 1 ? 1 : G);
 }
 int gen_threads(int N) { return (N + 63) / 64 * 64; }
 
-int launch_gen_factor(const PdeAdiDesc* d, const float* ab, const float* bb, const float* as, const float* bs, float* fac,
-                      GenSweep* tab, float* kmax, hipStream_t st) {
-    GenFactorArgs fa;
+constexpr int kGenLdsMax = 160 * 1024;        // the CU's LDS (two fp32 128 x 129 planes are 132 KB)
+// one plane image [N][N+1] in T; the backward keeps two of them in LDS while they fit (fp32: every N; fp64: N <= 100), else
+// the state plane goes to a global scratch slice per workgroup (bwd_xg)
+template <typename T>
+size_t gen_img(int N) { return (size_t)N * (N + 1) * sizeof(T); }
+template <typename T>
+bool bwd_xg(int N) { return 2 * gen_img<T>(N) > (size_t)kGenLdsMax; }
+// workgroups of the backward: with the state in global memory (one workgroup per CU by its LDS) about one per CU
+template <typename T, typename D>
+int bwd_groups(const D* d) {
+    if (!bwd_xg<T>(d->N)) return gen_groups(d);
+    int G = (256 + d->C - 1) / d->C;
+    return G > d->B ? d->B : (G < 1 ? 1 : G);
+}
+
+template <typename T, typename D>
+int launch_gen_factor(const D* d, const T* ab, const T* bb, const T* as, const T* bs, T* fac, GenSweep<T>* tab, T* kmax,
+                      hipStream_t st) {
+    using SW = typename std::remove_cv<typename std::remove_reference<decltype(d->sweep[0])>::type>::type;
+    GenFactorArgs<T, SW> fa;
     fa.ab = ab; fa.bb = bb; fa.as = as; fa.bs = bs; fa.fac = fac; fa.tab = tab; fa.kmax = kmax;
     fa.C = d->C; fa.N = d->N; fa.S = d->num_sweeps; fa.smooth3 = d->smooth3; fa.has_max = d->has_clamp_max;
     fa.cmax = d->clamp_max; fa.eps = d->eps;
     for (int s = 0; s < d->num_sweeps; ++s) fa.sweep[s] = d->sweep[s];
-    if (kmax && hipMemsetAsync(kmax, 0, sizeof(float) * d->num_sweeps, st) != hipSuccess) return PDE_E_LAUNCH;
-    hipLaunchKernelGGL(gen_factor_kernel, dim3(d->num_sweeps * d->C), dim3(gen_threads(d->N)), 0, st, fa);
+    if (kmax && hipMemsetAsync(kmax, 0, sizeof(T) * d->num_sweeps, st) != hipSuccess) return PDE_E_LAUNCH;
+    hipLaunchKernelGGL((gen_factor_kernel<T, SW>), dim3(d->num_sweeps * d->C), dim3(gen_threads(d->N)), 0, st, fa);
     return check_launch();
 }
 
-constexpr int kGenLdsMax = 160 * 1024;        // the CU's LDS (two 128 x 129 planes are 132 KB)
 template <typename K>
 int gen_lds(K kernel, unsigned long long& done) { return ensure_dynamic_lds((const void*)kernel, kGenLdsMax, done); }
 
-int launch_gen_fwd(const PdeAdiDesc* d, const void* u, void* y, const float* fac, const GenSweep* tab, int S, float* ckpt,
+template <typename T, typename D>
+int launch_gen_fwd(const D* d, const void* u, void* y, const T* fac, const GenSweep<T>* tab, int S, T* ckpt,
                    const uint64_t ck[2], hipStream_t st) {
-    GenSweepArgs sa{};
+    GenSweepArgs<T> sa{};
     sa.in0 = u; sa.out = y; sa.fac = fac; sa.tab = tab; sa.ckpt = ckpt;
     sa.ck[0] = ck ? ck[0] : 0ull; sa.ck[1] = ck ? ck[1] : 0ull;
     sa.B = d->B; sa.C = d->C; sa.N = d->N; sa.S = S; sa.eps = d->eps;
-    const size_t lds = (size_t)d->N * (d->N + 1) * sizeof(float);
+    const size_t lds = gen_img<T>(d->N);
     static unsigned long long done_f = 0, done_b = 0;
     int rc;
-    if (d->io_dtype == PDE_IO_F32) {
-        if ((rc = gen_lds(gen_fwd_kernel<float>, done_f)) != PDE_OK) return rc;
-        hipLaunchKernelGGL(gen_fwd_kernel<float>, dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+    if constexpr (std::is_same<T, double>::value) {
+        if ((rc = gen_lds(gen_fwd_kernel<double, double>, done_f)) != PDE_OK) return rc;
+        hipLaunchKernelGGL((gen_fwd_kernel<double, double>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+    } else if (d->io_dtype == PDE_IO_F32) {
+        if ((rc = gen_lds(gen_fwd_kernel<float, float>, done_f)) != PDE_OK) return rc;
+        hipLaunchKernelGGL((gen_fwd_kernel<float, float>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
     } else {
-        if ((rc = gen_lds(gen_fwd_kernel<gen_bf16>, done_b)) != PDE_OK) return rc;
-        hipLaunchKernelGGL(gen_fwd_kernel<gen_bf16>, dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+        if ((rc = gen_lds(gen_fwd_kernel<float, gen_bf16>, done_b)) != PDE_OK) return rc;
+        hipLaunchKernelGGL((gen_fwd_kernel<float, gen_bf16>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
     }
+    return check_launch();
+}
+
+template <typename T, typename D>
+size_t fwd_ws_bytes(const D* d) { return fac_bytes<T>(d) + tab_bytes_gen<T>(); }
+
+template <typename T, typename D>
+size_t bwd_ws_bytes(const D* d, int nck) {
+    const int G = bwd_groups<T>(d);
+    return fac_bytes<T>(d) + tab_bytes_gen<T>() + up256((size_t)G * d->C * 4 * d->N * d->N * sizeof(T)) +
+           up256((size_t)nck * d->B * d->C * d->N * d->N * sizeof(T)) +
+           (bwd_xg<T>(d->N) ? up256((size_t)G * d->C * gen_img<T>(d->N)) : 0);
+}
+
+template <typename T, typename D>
+int factor_impl(const D* d, const T* ab, const T* bb, const T* as, const T* bs, T* kmax, void* workspace, hipStream_t st) {
+    char* ws = static_cast<char*>(workspace);
+    return launch_gen_factor<T>(d, ab, bb, as, bs, reinterpret_cast<T*>(ws), reinterpret_cast<GenSweep<T>*>(ws + fac_bytes<T>(d)),
+                                kmax, st);
+}
+
+template <typename T, typename D>
+int forward_sweeps_impl(const D* d, const void* u, void* y, const void* workspace, hipStream_t st) {
+    const char* ws = static_cast<const char*>(workspace);
+    return launch_gen_fwd<T>(d, u, y, reinterpret_cast<const T*>(ws), reinterpret_cast<const GenSweep<T>*>(ws + fac_bytes<T>(d)),
+                             d->num_sweeps, (T*)nullptr, nullptr, st);
+}
+
+template <typename T, typename D>
+int backward_impl(const D* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], int nck, int Sf,
+                  void* gu, const T* ab, const T* bb, const T* as, const T* bs, T* g_ab, T* g_bb, T* g_as, T* g_bs,
+                  const void* fwd_workspace, void* workspace, hipStream_t st) {
+    char* ws = static_cast<char*>(workspace);
+    const T* fac = reinterpret_cast<const T*>(ws);
+    const GenSweep<T>* tab = reinterpret_cast<const GenSweep<T>*>(ws + fac_bytes<T>(d));
+    ws += fac_bytes<T>(d) + tab_bytes_gen<T>();
+    const int G = bwd_groups<T>(d);
+    T* part = reinterpret_cast<T*>(ws);
+    ws += up256((size_t)G * d->C * 4 * d->N * d->N * sizeof(T));
+    T* ckpt = nck ? reinterpret_cast<T*>(ws) : nullptr;
+    ws += up256((size_t)nck * d->B * d->C * d->N * d->N * sizeof(T));
+    const bool xg = bwd_xg<T>(d->N);
+    T* xplanes = xg ? reinterpret_cast<T*>(ws) : nullptr;
+    int rc;
+    if (fwd_workspace) {
+        const char* fw = static_cast<const char*>(fwd_workspace);
+        fac = reinterpret_cast<const T*>(fw);
+        tab = reinterpret_cast<const GenSweep<T>*>(fw + fac_bytes<T>(d));
+    } else {
+        rc = launch_gen_factor<T>(d, ab, bb, as, bs, const_cast<T*>(fac), const_cast<GenSweep<T>*>(tab), (T*)nullptr, st);
+        if (rc != PDE_OK) return rc;
+    }
+    if (nck) {
+        rc = launch_gen_fwd<T>(d, u, nullptr, fac, tab, Sf, ckpt, ckpt_mask, st);
+        if (rc != PDE_OK) return rc;
+    }
+    GenSweepArgs<T> sa{};
+    sa.in0 = gy; sa.in1 = y; sa.out = gu; sa.fac = fac; sa.tab = tab; sa.ckpt = ckpt; sa.part = part; sa.xg = xplanes;
+    sa.ck[0] = nck ? ckpt_mask[0] : 0ull; sa.ck[1] = nck ? ckpt_mask[1] : 0ull;
+    sa.B = d->B; sa.C = d->C; sa.N = d->N; sa.S = d->num_sweeps; sa.G = G; sa.eps = d->eps;
+    const size_t img = gen_img<T>(d->N);
+    // the partial sums beside the planes while four workgroups still fit on a CU (fp32: N <= 40, fp64: N <= 28)
+    const bool alds = !xg && 4 * 6 * img <= (size_t)kGenLdsMax;
+    const size_t lds = xg ? img : (alds ? 6 : 2) * img;
+    static unsigned long long done[7] = {0, 0, 0, 0, 0, 0, 0};
+    const dim3 grid(G * d->C), block(gen_threads(d->N));
+#define PDE_GEN_BWD(TY, IO, AL, XG, SLOT)                                                                \
+    do {                                                                                                 \
+        if ((rc = gen_lds(gen_bwd_kernel<TY, IO, AL, XG>, done[SLOT])) != PDE_OK) return rc;             \
+        hipLaunchKernelGGL((gen_bwd_kernel<TY, IO, AL, XG>), grid, block, lds, st, sa, (int)d->smooth3); \
+    } while (0)
+    if constexpr (std::is_same<T, double>::value) {
+        if (xg) PDE_GEN_BWD(double, double, false, true, 4);
+        else if (alds) PDE_GEN_BWD(double, double, true, false, 5);
+        else PDE_GEN_BWD(double, double, false, false, 6);
+    } else if (d->io_dtype == PDE_IO_F32) {
+        if (alds) PDE_GEN_BWD(float, float, true, false, 0); else PDE_GEN_BWD(float, float, false, false, 1);
+    } else {
+        if (alds) PDE_GEN_BWD(float, gen_bf16, true, false, 2); else PDE_GEN_BWD(float, gen_bf16, false, false, 3);
+    }
+#undef PDE_GEN_BWD
+    if ((rc = check_launch()) != PDE_OK) return rc;
+    const int NN = d->N * d->N, total = d->C * NN;
+    hipLaunchKernelGGL((gen_reduce_kernel<T>), dim3((total + 255) / 256), dim3(256), 0, st, part, G, d->C, d->N, g_ab, g_as,
+                       g_bb, g_bs);
     return check_launch();
 }
 
@@ -397,79 +534,108 @@ int launch_gen_fwd(const PdeAdiDesc* d, const void* u, void* y, const float* fac
 
 bool gen_n_ok(int N) { return N >= 2 && N <= PDE_MAX_N_GENERIC; }
 
-size_t gen_forward_workspace_bytes(const PdeAdiDesc* d) { return fac_bytes(d) + tab_bytes_gen(); }
+size_t gen_forward_workspace_bytes(const PdeAdiDesc* d) { return fwd_ws_bytes<float>(d); }
 
-size_t gen_backward_workspace_bytes(const PdeAdiDesc* d, int nck) {
-    return fac_bytes(d) + tab_bytes_gen() + up256((size_t)gen_groups(d) * d->C * 4 * d->N * d->N * sizeof(float)) +
-           up256((size_t)nck * d->B * d->C * d->N * d->N * sizeof(float));
-}
+size_t gen_backward_workspace_bytes(const PdeAdiDesc* d, int nck) { return bwd_ws_bytes<float>(d, nck); }
 
 int gen_kappa_max(const PdeAdiDesc* d, const float* ab, const float* bb, const float* as, const float* bs, float* kmax,
                   hipStream_t st) {
-    return launch_gen_factor(d, ab, bb, as, bs, nullptr, nullptr, kmax, st);
+    return launch_gen_factor<float>(d, ab, bb, as, bs, nullptr, nullptr, kmax, st);
 }
 
 int gen_factor(const PdeAdiDesc* d, const float* ab, const float* bb, const float* as, const float* bs, float* kmax,
                void* workspace, hipStream_t st) {
-    char* ws = static_cast<char*>(workspace);
-    return launch_gen_factor(d, ab, bb, as, bs, reinterpret_cast<float*>(ws), reinterpret_cast<GenSweep*>(ws + fac_bytes(d)),
-                             kmax, st);
+    return factor_impl<float>(d, ab, bb, as, bs, kmax, workspace, st);
 }
 
 int gen_forward_sweeps(const PdeAdiDesc* d, const void* u, void* y, const void* workspace, hipStream_t st) {
-    const char* ws = static_cast<const char*>(workspace);
-    return launch_gen_fwd(d, u, y, reinterpret_cast<const float*>(ws), reinterpret_cast<const GenSweep*>(ws + fac_bytes(d)),
-                          d->num_sweeps, nullptr, nullptr, st);
+    return forward_sweeps_impl<float>(d, u, y, workspace, st);
 }
 
 int gen_backward(const PdeAdiDesc* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], int nck,
                  int Sf, void* gu, const float* ab, const float* bb, const float* as, const float* bs, float* g_ab,
                  float* g_bb, float* g_as, float* g_bs, const void* fwd_workspace, void* workspace, hipStream_t st) {
-    char* ws = static_cast<char*>(workspace);
-    const float* fac = reinterpret_cast<const float*>(ws);
-    const GenSweep* tab = reinterpret_cast<const GenSweep*>(ws + fac_bytes(d));
-    ws += fac_bytes(d) + tab_bytes_gen();
-    const int G = gen_groups(d);
-    float* part = reinterpret_cast<float*>(ws);
-    ws += up256((size_t)G * d->C * 4 * d->N * d->N * sizeof(float));
-    float* ckpt = nck ? reinterpret_cast<float*>(ws) : nullptr;
-    int rc;
-    if (fwd_workspace) {
-        const char* fw = static_cast<const char*>(fwd_workspace);
-        fac = reinterpret_cast<const float*>(fw);
-        tab = reinterpret_cast<const GenSweep*>(fw + fac_bytes(d));
-    } else {
-        rc = launch_gen_factor(d, ab, bb, as, bs, const_cast<float*>(fac), const_cast<GenSweep*>(tab), nullptr, st);
-        if (rc != PDE_OK) return rc;
-    }
-    if (nck) {
-        rc = launch_gen_fwd(d, u, nullptr, fac, tab, Sf, ckpt, ckpt_mask, st);
-        if (rc != PDE_OK) return rc;
-    }
-    GenSweepArgs sa{};
-    sa.in0 = gy; sa.in1 = y; sa.out = gu; sa.fac = fac; sa.tab = tab; sa.ckpt = ckpt; sa.part = part;
-    sa.ck[0] = nck ? ckpt_mask[0] : 0ull; sa.ck[1] = nck ? ckpt_mask[1] : 0ull;
-    sa.B = d->B; sa.C = d->C; sa.N = d->N; sa.S = d->num_sweeps; sa.G = G; sa.eps = d->eps;
-    const size_t img = (size_t)d->N * (d->N + 1) * sizeof(float);
-    const bool alds = 4 * 6 * img <= (size_t)kGenLdsMax;  // the partial sums beside the planes while four workgroups fit on a CU (N <= 40)
-    const size_t lds = (alds ? 6 : 2) * img;
-    static unsigned long long done[4] = {0, 0, 0, 0};
-    const dim3 grid(G * d->C), block(gen_threads(d->N));
-#define PDE_GEN_BWD(IO, AL, SLOT)                                                                        \
-    do {                                                                                                 \
-        if ((rc = gen_lds(gen_bwd_kernel<IO, AL>, done[SLOT])) != PDE_OK) return rc;                     \
-        hipLaunchKernelGGL((gen_bwd_kernel<IO, AL>), grid, block, lds, st, sa, (int)d->smooth3);         \
-    } while (0)
-    if (d->io_dtype == PDE_IO_F32) {
-        if (alds) PDE_GEN_BWD(float, true, 0); else PDE_GEN_BWD(float, false, 1);
-    } else {
-        if (alds) PDE_GEN_BWD(gen_bf16, true, 2); else PDE_GEN_BWD(gen_bf16, false, 3);
-    }
-#undef PDE_GEN_BWD
-    if ((rc = check_launch()) != PDE_OK) return rc;
-    const int NN = d->N * d->N, total = d->C * NN;
-    hipLaunchKernelGGL(gen_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, part, G, d->C, d->N, g_ab, g_as, g_bb, g_bs);
-    return check_launch();
+    return backward_impl<float>(d, gy, y, u, ckpt_mask, nck, Sf, gu, ab, bb, as, bs, g_ab, g_bb, g_as, g_bs, fwd_workspace,
+                                workspace, st);
 }
 
 }  // namespace pde
+
+// ---- float64 entry points (include/pdecnn.h): the same kernels instantiated for double ------------------------------
+using namespace pde;
+
+namespace {
+
+int check_desc_f64(const PdeAdiDescF64* d) {
+    if (!d) return PDE_E_BADARG;
+    if (d->B <= 0 || d->C <= 0 || d->num_sweeps <= 0) return PDE_E_BADARG;
+    if (!gen_n_ok(d->N)) return PDE_E_UNSUPPORTED_N;
+    if (d->num_sweeps > PDE_MAX_SWEEPS) return PDE_E_TOO_MANY_SWEEPS;
+    if (d->io_dtype != PDE_IO_F64) return PDE_E_BADARG;
+    for (int s = 0; s < d->num_sweeps; ++s)
+        if (d->sweep[s].axis != PDE_AXIS_X && d->sweep[s].axis != PDE_AXIS_Y) return PDE_E_BADARG;
+    return PDE_OK;
+}
+
+// checkpoint mask -> (count, number of forward sweeps to recompute); PDE_E_BADARG when inconsistent
+int ckpt_plan_f64(const PdeAdiDescF64* d, const uint64_t ckpt_mask[2], const void* u, int& nck, int& Sf) {
+    nck = ckpt_mask ? __builtin_popcountll(ckpt_mask[0]) + __builtin_popcountll(ckpt_mask[1]) : 0;
+    Sf = 0;
+    if (nck) {
+        if (!u) return PDE_E_BADARG;
+        for (int s = 0; s < 128; ++s)
+            if ((ckpt_mask[s >> 6] >> (s & 63)) & 1ull) {
+                if (s >= d->num_sweeps - 1) return PDE_E_BADARG;   // beyond the schedule, or the last state (y itself)
+                Sf = s + 1;
+            }
+    }
+    return PDE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pde_adi_f64_forward_workspace_bytes(const PdeAdiDescF64* d) {
+    if (check_desc_f64(d) != PDE_OK) return 0;
+    return fwd_ws_bytes<double>(d);
+}
+
+size_t pde_adi_f64_backward_workspace_bytes(const PdeAdiDescF64* d, int32_t num_checkpoints) {
+    if (check_desc_f64(d) != PDE_OK || num_checkpoints < 0 || num_checkpoints >= d->num_sweeps) return 0;
+    return bwd_ws_bytes<double>(d, num_checkpoints);
+}
+
+int pde_adi_f64_forward(const PdeAdiDescF64* d, const double* u, double* y, const double* alpha_base, const double* beta_base,
+                        const double* alpha_slope, const double* beta_slope, double* kappa_max, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    int rc = check_desc_f64(d);
+    if (rc != PDE_OK) return rc;
+    if (!u || !y || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    if (workspace_bytes < pde_adi_f64_forward_workspace_bytes(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = factor_impl<double>(d, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, workspace, st);
+    if (rc != PDE_OK) return rc;
+    return forward_sweeps_impl<double>(d, u, y, workspace, st);
+}
+
+int pde_adi_f64_backward(const PdeAdiDescF64* d, const double* gy, const double* y, const double* u,
+                         const uint64_t ckpt_mask[2], double* gu, const double* alpha_base, const double* beta_base,
+                         const double* alpha_slope, const double* beta_slope, double* g_alpha_base, double* g_beta_base,
+                         double* g_alpha_slope, double* g_beta_slope, const void* fwd_workspace, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    int rc = check_desc_f64(d);
+    if (rc != PDE_OK) return rc;
+    if (!gy || !y || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !g_alpha_base || !g_beta_base ||
+        !g_alpha_slope || !g_beta_slope || !workspace)
+        return PDE_E_BADARG;
+    int nck, Sf;
+    rc = ckpt_plan_f64(d, ckpt_mask, u, nck, Sf);
+    if (rc != PDE_OK) return rc;
+    if (workspace_bytes < pde_adi_f64_backward_workspace_bytes(d, nck) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    return backward_impl<double>(d, gy, y, u, ckpt_mask, nck, Sf, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                                 g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
+                                 static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

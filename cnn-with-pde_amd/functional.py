@@ -704,6 +704,18 @@ def adi_diffuse_multi(u, layers, weights=None, plane_sums=False, checkpoints="au
     if isinstance(checkpoints, list):
         checkpoints = tuple(checkpoints)
     nl = len(layers)
+    if _is_f64(u, weights, *flat):
+        # float64: one layer after another (adi_diffuse_mixed), the weighted sum and the plane sums in torch
+        ys = []
+        for i, ly in enumerate(layers):
+            ck = checkpoints[i] if isinstance(checkpoints, tuple) else checkpoints
+            ys.append(adi_diffuse_mixed(u, ly["alpha_base"], ly["beta_base"], ly["alpha_time_coeff"], ly["beta_time_coeff"],
+                                        ly["M"], specs[i][0], "pre", smooth3=specs[i][1], clamp_max=specs[i][2],
+                                        eps=specs[i][3], checkpoints=ck))
+        out = sum(w * y for w, y in zip(weights, ys)) if weights is not None else ys[-1]
+        if plane_sums:
+            return out, ys, [y.sum(dim=(2, 3)) for y in ys]
+        return out, ys
     H = L.host_ext()
     if H is not None and u.dim() == 4 and u.is_cuda and u.shape[0] > 0 and len({len(sp[0][0]) for sp in specs}) == 1:
         # the native host path (csrc/host_ext.cpp): the same call of the C ABI from a C++ autograd node
@@ -731,8 +743,9 @@ _small_ok_cache = {}
 
 
 def adi_small_supported(u, steps, smooth3=False, clamp_max=None, eps=1e-6) -> bool:
-    """True when ``adi_diffuse_small`` can run this layer call (C <= 4, N in {16, 28, 32}, Strang or Lie steps)."""
-    if u.dim() != 4 or u.shape[2] != u.shape[3] or not u.is_cuda:
+    """True when ``adi_diffuse_small`` can run this layer call (C <= 4, N in {16, 28, 32}, Strang or Lie steps; not
+    float64)."""
+    if u.dim() != 4 or u.shape[2] != u.shape[3] or not u.is_cuda or u.dtype == torch.float64:
         return False
     B, Cc, N, _ = u.shape
     if B == 0 or Cc > 4 or N > L.PDE_MAX_N or len(steps) * len(steps[0]) > L.PDE_MAX_SWEEPS:
@@ -757,6 +770,11 @@ def adi_diffuse_small(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
     if mode not in ("pre", "post"):
         raise ValueError(mode)
     steps = _as_schedule(steps)
+    if _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, skip_weight):
+        # float64: no one-launch kernels; the layer out of its pieces (adi_diffuse_mixed composes it per step)
+        y = adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode, smooth3=smooth3,
+                              clamp_max=clamp_max, eps=eps, checkpoints=checkpoints)
+        return y if skip_weight is None else skip_blend(u, y, skip_weight)
     if kmax_sink is None and (checkpoints == "auto" or isinstance(checkpoints, int)) and u.shape[0] > 0:
         H = L.host_ext()
         if H is not None and u.dim() == 4 and u.is_cuda:
@@ -786,10 +804,12 @@ def adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
     steps = tuple(tuple(st) for st in steps)
     if len({len(st) for st in steps}) != 1:
         raise ValueError("every step must have the same number of sweeps")
-    if u.dim() == 4 and u.is_cuda and L.load().pde_adi_line_length_path(int(u.shape[-1])) == 2:
+    if u.dim() == 4 and u.is_cuda and (L.load().pde_adi_line_length_path(int(u.shape[-1])) == 2 or
+                                       _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)):
         # a line length without fused kernels (pde_adi_line_length_path: any size up to PDE_MAX_N_GENERIC): the per-step
         # entry points do not exist there; compose the layer from its own pieces — the channel operator and the sweeps of
-        # one step per call, chained by autograd (the step-local checkpoint mask applies to every step unchanged)
+        # one step per call, chained by autograd (the step-local checkpoint mask applies to every step unchanged).  float64
+        # takes this route at every line length: its sweeps are the any-size kernels instantiated for double
         tickets = [] if kmax_sink is not None else None
         for st in steps:
             if mode == "pre":
@@ -819,6 +839,8 @@ def _empty_passthrough(u, *params):
     """Empty batch: nothing to launch.  Like the reference's torch ops, pass the empty tensor through and
     keep it connected to the parameters (their gradients are zeros, not None)."""
     _require_cuda(u, *params)
+    if _is_f64(u, *params):
+        u = u.to(torch.float64)
     tie = sum((p.sum() for p in params if isinstance(p, torch.Tensor)), u.new_zeros(()))
     return u + 0 * tie.to(u.dtype)
 
@@ -840,11 +862,13 @@ def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, swe
         return _empty_passthrough(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
     if not isinstance(sweeps, tuple):
         sweeps = tuple(sweeps)
+    if _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff):
+        return _AdiF64Fn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3), clamp_max,
+                               float(eps), checkpoints)
     if (kmax_sink is None and (checkpoints == "auto" or isinstance(checkpoints, int))) or \
             (kmax_sink is not None and isinstance(checkpoints, int)):
         H = L.host_ext()
-        if H is not None and u.dim() == 4 and u.is_cuda and u.dtype in (torch.float32, torch.bfloat16, torch.float16,
-                                                                        torch.float64):
+        if H is not None and u.dim() == 4 and u.is_cuda and u.dtype in (torch.float32, torch.bfloat16, torch.float16):
             # the native host path (csrc/host_ext.cpp): the same two calls of the C ABI from a C++ autograd node
             B, Cc, N, _ = u.shape
             d = _make_desc(B, Cc, N, L.PDE_IO_BF16 if u.dtype == torch.bfloat16 else L.PDE_IO_F32, sweeps, smooth3,
@@ -905,6 +929,8 @@ def channel_mix(u, M):
     """out[b,i,p] = sum_j M[i,j] u[b,j,p] — cifar10.py:65-72 and SVHN.py:78-86."""
     if u.shape[0] == 0:
         return _empty_passthrough(u, M)
+    if _is_f64(u, M):
+        return _MixF64Fn.apply(u, M)
     return _MixFn.apply(u, M)
 
 
@@ -1297,6 +1323,9 @@ def explicit5_step(u, alpha_base, channel_scaling, dt=0.01, eps=1e-6, max_coeff=
     """``num_steps`` relaxed explicit 5-point steps in one call — tiny_imagenet.py:38-49,53-72."""
     if u.shape[0] == 0 or num_steps < 1:
         return _empty_passthrough(u, alpha_base, channel_scaling)
+    if _is_f64(u, alpha_base, channel_scaling):
+        return _Explicit5F64Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
+                                     int(num_steps))
     return _Explicit5Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
                               int(num_steps))
 
@@ -1336,6 +1365,8 @@ def jacobi_diffuse(u, a_row, b_col, nt: int):
     """emotion_recognition.py:82-97 on (B,H,W): reflect-pad once, ``nt`` Jacobi updates."""
     if u.shape[0] == 0:
         return _empty_passthrough(u, a_row, b_col)
+    if _is_f64(u, a_row, b_col):
+        return _JacobiF64Fn.apply(u, a_row, b_col, int(nt))
     return _JacobiFn.apply(u, a_row, b_col, int(nt))
 
 
@@ -1375,10 +1406,243 @@ class _SkipBlendFn(torch.autograd.Function):
 
 def skip_blend(u0, u, skip_weight):
     """``sigmoid(skip_weight) * u0 + (1 - sigmoid(skip_weight)) * u`` — SVHN.py:73-74, one pass."""
+    f64 = _is_f64(u0, u, skip_weight)
     if u.numel() == 0:
+        if f64:
+            u0, u, skip_weight = u0.double(), u.double(), skip_weight.double()
         s = torch.sigmoid(skip_weight)
         return s * u0 + (1 - s) * u
+    if f64:
+        return _SkipBlendF64Fn.apply(u0, u, skip_weight)
     return _SkipBlendFn.apply(u0, u, skip_weight)
+
+
+# --------------------------------------------------------------------------- float64
+# A call takes the float64 path when its input or any floating parameter is float64 (torch's type promotion, which the
+# reference's ops follow): the output is float64 and every gradient comes back in its own tensor's dtype.  The functions
+# below run the pde_*_f64_* entry points (double arithmetic throughout); there is no float64 host-extension path.
+def _is_f64(*ts) -> bool:
+    return any(isinstance(t, torch.Tensor) and t.dtype == torch.float64 for t in ts)
+
+
+def _d64(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to(torch.float64).contiguous()
+
+
+_desc64_cache = {}
+
+
+def _make_desc64(B, Cc, N, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) -> L.PdeAdiDescF64:
+    key = (B, Cc, N, sweeps, bool(smooth3), clamp_max, float(eps))
+    d = _desc64_cache.get(key)
+    if d is None:
+        if len(sweeps) > L.PDE_MAX_SWEEPS:
+            raise L.PdeError(f"{len(sweeps)} sweeps in one launch exceed PDE_MAX_SWEEPS={L.PDE_MAX_SWEEPS}")
+        if len(_desc64_cache) > 256:
+            _desc64_cache.clear()
+        d = L.PdeAdiDescF64()
+        d.B, d.C, d.N, d.io_dtype, d.num_sweeps = B, Cc, N, L.PDE_IO_F64, len(sweeps)
+        d.smooth3 = int(bool(smooth3))
+        d.has_clamp_max = int(clamp_max is not None)
+        d.clamp_max = float(clamp_max) if clamp_max is not None else 0.0
+        d.eps = float(eps)
+        for i, sw in enumerate(sweeps):
+            d.sweep[i].axis, d.sweep[i].delta, d.sweep[i].h2, d.sweep[i].t = int(sw.axis), sw.delta, sw.h2, sw.t
+        _desc64_cache[key] = d
+    return d
+
+
+def _as_chw64(p: torch.Tensor, Cc: int, N: int) -> torch.Tensor:
+    q = p.detach()
+    if q.dim() == 2:
+        q = q.unsqueeze(0)
+    if tuple(q.shape) != (Cc, N, N):
+        raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{N})")
+    return q.to(torch.float64).contiguous()
+
+
+def _f64_ckpt_bits(ckpt, num_sweeps: int) -> int:
+    """The backward's checkpoint mask in float64: an int is honoured; "auto" / "lagged" keep the state after every sweep
+    (nothing is rebuilt, so no rounding is amplified: the plan needs no coefficient maxima)."""
+    if isinstance(ckpt, int) and not isinstance(ckpt, bool):
+        return int(ckpt)
+    return (1 << max(num_sweeps - 1, 0)) - 1
+
+
+class _AdiF64Fn(torch.autograd.Function):
+    """adi_diffuse in float64 (pde_adi_f64_*)."""
+
+    @staticmethod
+    def forward(ctx, u, ab, bb, asl, bsl, sweeps, smooth3, clamp_max, eps, ckpt):
+        lib = L.load()
+        _require_cuda(u, ab, bb, asl, bsl)
+        if u.dim() != 4 or u.shape[2] != u.shape[3]:
+            raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
+        B, Cc, N, _ = u.shape
+        u = u.to(torch.float64).contiguous()
+        p = [_as_chw64(t, Cc, N) for t in (ab, bb, asl, bsl)]
+        d = _make_desc64(B, Cc, N, sweeps, smooth3, clamp_max, eps)
+        y = torch.empty_like(u)
+        ws = _workspace(lib.pde_adi_f64_forward_workspace_bytes(C.byref(d)), u.device)
+        need_grad = any(ctx.needs_input_grad[:5])
+        bits = _f64_ckpt_bits(ckpt, len(sweeps))
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_adi_f64_forward(C.byref(d), _ptr(u), _ptr(y), *[_ptr(t) for t in p], None, _ptr(ws), ws.numel(),
+                                            _stream()), "pde_adi_f64_forward")
+        ctx.fwd_ws = ws if need_grad else None
+        ctx.save_for_backward(y, u if (need_grad and bits) else None, *p)
+        ctx.cfg = (sweeps, smooth3, clamp_max, eps, bits)
+        ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = L.load()
+        y, u, *p = ctx.saved_tensors
+        sweeps, smooth3, clamp_max, eps, bits = ctx.cfg
+        B, Cc, N, _ = y.shape
+        gy = gy.to(torch.float64).contiguous()
+        d = _make_desc64(B, Cc, N, sweeps, smooth3, clamp_max, eps)
+        gu = torch.empty_like(y)
+        gp = [torch.empty_like(t) for t in p]
+        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+        ws = _workspace(lib.pde_adi_f64_backward_workspace_bytes(C.byref(d), bin(bits).count("1")), y.device)
+        with torch.cuda.device(y.device):
+            L.check(lib.pde_adi_f64_backward(C.byref(d), _ptr(gy), _ptr(y), _ptr(u if bits else None), mask, _ptr(gu),
+                                             *[_ptr(t) for t in p], *[_ptr(t) for t in gp], _ptr(ctx.fwd_ws), _ptr(ws),
+                                             ws.numel(), _stream()), "pde_adi_f64_backward")
+        ctx.fwd_ws = None
+        gp = [g.reshape(s).to(dt) for g, (s, dt) in zip(gp, ctx.param_meta)]
+        return (gu, *gp, None, None, None, None, None)
+
+
+class _MixF64Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, M):
+        lib = L.load()
+        _require_cuda(u, M)
+        B, Cc = u.shape[0], u.shape[1]
+        HW = u[0, 0].numel()
+        u = u.to(torch.float64).contiguous()
+        Md = _d64(M)
+        out = torch.empty_like(u)
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_channel_mix_f64_forward(B, Cc, HW, _ptr(u), _ptr(Md), _ptr(out), _stream()),
+                    "pde_channel_mix_f64_forward")
+        ctx.save_for_backward(u, Md)
+        ctx.m_dtype = M.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = L.load()
+        u, Md = ctx.saved_tensors
+        B, Cc = u.shape[0], u.shape[1]
+        HW = u[0, 0].numel()
+        gout = gout.to(torch.float64).contiguous()
+        gu, gM = torch.empty_like(u), torch.empty_like(Md)
+        ws = _workspace(lib.pde_channel_mix_f64_backward_workspace_bytes(B, Cc, HW), u.device)
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_channel_mix_f64_backward(B, Cc, HW, _ptr(u), _ptr(gout), _ptr(Md), _ptr(gu), _ptr(gM), _ptr(ws),
+                                                     ws.numel(), _stream()), "pde_channel_mix_f64_backward")
+        return gu, gM.to(ctx.m_dtype)
+
+
+class _SkipBlendF64Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u0, u, skip_weight):
+        lib = L.load()
+        _require_cuda(u0, u, skip_weight)
+        if u0.shape != u.shape:
+            raise L.PdeError(f"shapes differ: {tuple(u0.shape)} vs {tuple(u.shape)}")
+        a, b = u0.to(torch.float64).contiguous(), u.to(torch.float64).contiguous()
+        w = _d64(skip_weight).reshape(1)
+        out = torch.empty_like(b)
+        with torch.cuda.device(b.device):
+            L.check(lib.pde_skip_blend_f64_forward(b.numel(), _ptr(a), _ptr(b), _ptr(w), _ptr(out), _stream()),
+                    "pde_skip_blend_f64_forward")
+        ctx.save_for_backward(a, b, w)
+        ctx.in_meta = (u0.dtype, u.dtype, skip_weight.dtype, skip_weight.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        a, b, w = ctx.saved_tensors
+        g = g.to(torch.float64).contiguous()
+        g_a, g_b = torch.empty_like(a), torch.empty_like(b)
+        g_w = torch.empty(1, dtype=torch.float64, device=b.device)
+        ws = _workspace(lib.pde_skip_blend_f64_backward_workspace_bytes(b.numel()), b.device)
+        with torch.cuda.device(b.device):
+            L.check(lib.pde_skip_blend_f64_backward(b.numel(), _ptr(g), _ptr(a), _ptr(b), _ptr(w), _ptr(g_a), _ptr(g_b),
+                                                    _ptr(g_w), _ptr(ws), ws.numel(), _stream()), "pde_skip_blend_f64_backward")
+        d0, d1, dw, shw = ctx.in_meta
+        return g_a.to(d0), g_b.to(d1), g_w.to(dw).reshape(shw)
+
+
+class _Explicit5F64Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, num_steps):
+        lib = L.load()
+        _require_cuda(u, alpha_base, channel_scaling)
+        u = u.to(torch.float64).contiguous()
+        B, Cc, H, W = u.shape
+        a, s = _d64(alpha_base), _d64(channel_scaling)
+        out = torch.empty_like(u)
+        states = torch.empty((num_steps - 1,) + tuple(u.shape), dtype=torch.float64, device=u.device) if num_steps > 1 else None
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_explicit5_f64_forward(B, Cc, H, W, _ptr(u), _ptr(a), _ptr(s), dt, eps, max_coeff, relax, num_steps,
+                                                  _ptr(states), _ptr(out), _stream()), "pde_explicit5_f64_forward")
+        ctx.save_for_backward(u, states, a, s)
+        ctx.cfg = (dt, eps, max_coeff, relax, num_steps)
+        ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = L.load()
+        u, states, a, s = ctx.saved_tensors
+        dt, eps, max_coeff, relax, num_steps = ctx.cfg
+        B, Cc, H, W = u.shape
+        gout = gout.to(torch.float64).contiguous()
+        gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
+        ws = _workspace(lib.pde_explicit5_f64_backward_workspace_bytes(B, Cc, H, W, num_steps), u.device)
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_explicit5_f64_backward(B, Cc, H, W, _ptr(u), _ptr(states), _ptr(gout), _ptr(a), _ptr(s), dt, eps,
+                                                   max_coeff, relax, num_steps, _ptr(gu), _ptr(ga), _ptr(gs), _ptr(ws),
+                                                   ws.numel(), _stream()), "pde_explicit5_f64_backward")
+        return gu, ga.to(ctx.p_dtypes[0]), gs.to(ctx.p_dtypes[1]), None, None, None, None, None
+
+
+class _JacobiF64Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, a_row, b_col, nt):
+        lib = L.load()
+        _require_cuda(u, a_row, b_col)
+        u = u.to(torch.float64).contiguous()
+        B, H, W = u.shape
+        a, b = _d64(a_row), _d64(b_col)
+        out = torch.empty_like(u)
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_jacobi_f64_forward(B, H, W, nt, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
+                    "pde_jacobi_f64_forward")
+        ctx.save_for_backward(u, a, b)
+        ctx.nt = nt
+        ctx.p_dtypes = (a_row.dtype, b_col.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = L.load()
+        u, a, b = ctx.saved_tensors
+        B, H, W = u.shape
+        gout = gout.to(torch.float64).contiguous()
+        gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
+        ws = _workspace(lib.pde_jacobi_f64_backward_workspace_bytes(B, H, W, ctx.nt), u.device)
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_jacobi_f64_backward(B, H, W, ctx.nt, _ptr(u), _ptr(gout), _ptr(a), _ptr(b), _ptr(gu), _ptr(ga),
+                                                _ptr(gb), _ptr(ws), ws.numel(), _stream()), "pde_jacobi_f64_backward")
+        return gu, ga.to(ctx.p_dtypes[0]), gb.to(ctx.p_dtypes[1]), None
 
 
 # --------------------------------------------------------------------------- timing

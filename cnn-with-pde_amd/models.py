@@ -42,7 +42,9 @@ def diffuse_shared_input(layers, x, weights=None, plane_sums=False):
     Returns ``(sum_i weights[i] * y_i or None, [y_1 .. y_L])``; with ``plane_sums`` also ``[sum_hw y_i]`` (B,C)."""
     steps = [ly._schedule() for ly in layers]
     same_split = len({len(st[0]) for st in steps}) == 1
-    fused = (same_split and len(layers) <= 4 and x.is_cuda and all(getattr(ly, "channel_mixing_enabled", True) for ly in layers)
+    f64 = x.dtype == torch.float64 or any(p.dtype == torch.float64 for ly in layers for p in ly.parameters())
+    fused = (same_split and len(layers) <= 4 and x.is_cuda and not f64    # float64: one layer after another
+             and all(getattr(ly, "channel_mixing_enabled", True) for ly in layers)
              and all(ly.small_channel_kernels and ly.checkpoint_policy != "lagged" for ly in layers)
              and (all(ly.checkpoint_policy == "auto" for ly in layers)
                   or all(isinstance(ly.checkpoint_policy, int) for ly in layers))          # frozen masks may differ per layer
@@ -162,7 +164,8 @@ class MultiScaleExtractor(nn.Module):
     def forward(self, x):
         att = (self.attention1, self.attention2, self.attention3)
         w = F.softmax(self.combine_weights, dim=0)
-        if not (self.fused_epilogue and x.is_cuda):
+        f64 = x.dtype == torch.float64 or self.combine_weights.dtype == torch.float64
+        if not (self.fused_epilogue and x.is_cuda) or f64:                # float64: the plain-torch epilogue
             _, ys = diffuse_shared_input([self.pde1, self.pde2, self.pde3], x)
             f1, f2, f3 = (a(y) for a, y in zip(att, ys))
             return w[0] * f1 + w[1] * f2 + w[2] * f3, f1, f2, f3

@@ -38,6 +38,7 @@ extern "C" {
 
 #define PDE_IO_F32 0
 #define PDE_IO_BF16 1
+#define PDE_IO_F64 2               /* PdeAdiDescF64 only: the pde_*_f64_* entry points */
 
 #define PDE_AXIS_X 0               /* solve along W with alpha (mnist_test.py:67-98)  */
 #define PDE_AXIS_Y 1               /* solve along H with beta  (mnist_test.py:100-133) */
@@ -434,6 +435,87 @@ int pde_sym_layer_f16_backward(int32_t B, int32_t D, int32_t act, int32_t traini
                                const uint16_t* P, const uint16_t* H, const float* mean, const float* invstd,
                                uint16_t* dP, float* gX, float* gK, float* g_bn_weight, float* g_bn_bias,
                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- float64: the same layers computed in double end to end -----------------------------------------
+ * A float64 input or parameter makes the reference's torch ops run in float64 (torch type promotion), `t` and the
+ * coefficient schedule included.  These entry points are that path: every tensor is float64 (double), every scalar of
+ * the schedule is a double, and the arithmetic is double with true division — the reference's own recurrences, no
+ * reciprocal approximations.  Parameter gradients are summed in a fixed order: two calls give the same bits.
+ * Semantics, checkpoint masks and error codes as in the float32 entry point each one names. */
+
+typedef struct PdeSweepF64 {
+    int32_t axis;       /* PDE_AXIS_X / PDE_AXIS_Y */
+    int32_t pad;
+    double  delta;      /* dt/2 or dt, as the reference's Python floats */
+    double  h2;         /* dx**2 or dy**2 */
+    double  t;          /* current_time */
+} PdeSweepF64;
+
+typedef struct PdeAdiDescF64 {
+    int32_t B, C, N;            /* H = W = N, 2 <= N <= PDE_MAX_N_GENERIC                */
+    int32_t io_dtype;           /* PDE_IO_F64                                            */
+    int32_t num_sweeps;
+    int32_t smooth3;
+    int32_t has_clamp_max;
+    int32_t pad;
+    double  clamp_max;
+    double  eps;
+    PdeSweepF64 sweep[PDE_MAX_SWEEPS];
+} PdeAdiDescF64;
+
+/* pde_adi_forward / pde_adi_backward in float64 (the any-size kernels at every N: one thread per line).  kappa_max: NULL
+ * or num_sweeps doubles on the device.  num_checkpoints: the number of bits set in the backward's ckpt_mask. */
+size_t pde_adi_f64_forward_workspace_bytes(const PdeAdiDescF64* d);
+size_t pde_adi_f64_backward_workspace_bytes(const PdeAdiDescF64* d, int32_t num_checkpoints);
+int pde_adi_f64_forward(const PdeAdiDescF64* d, const double* u, double* y,
+                        const double* alpha_base, const double* beta_base,
+                        const double* alpha_slope, const double* beta_slope,
+                        double* kappa_max, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_f64_backward(const PdeAdiDescF64* d, const double* gy, const double* y, const double* u,
+                         const uint64_t ckpt_mask[2], double* gu,
+                         const double* alpha_base, const double* beta_base,
+                         const double* alpha_slope, const double* beta_slope,
+                         double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
+                         const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pde_channel_mix_* in float64, 1 <= C <= 128.  _steps: gM spread over calls sharing `workspace` (accumulate = 0 starts
+ * the sums, 1 adds; finalize = 1 writes gM). */
+int pde_channel_mix_f64_forward(int32_t B, int32_t C, int32_t HW, const double* u, const double* M, double* out,
+                                void* stream);
+size_t pde_channel_mix_f64_backward_workspace_bytes(int32_t B, int32_t C, int32_t HW);
+int pde_channel_mix_f64_backward(int32_t B, int32_t C, int32_t HW, const double* u, const double* gout, const double* M,
+                                 double* gu, double* gM, void* workspace, size_t workspace_bytes, void* stream);
+int pde_channel_mix_f64_backward_steps(int32_t B, int32_t C, int32_t HW, const double* u, const double* gout,
+                                       const double* M, double* gu, double* gM, void* workspace, size_t workspace_bytes,
+                                       int32_t accumulate, int32_t finalize, void* stream);
+
+/* pde_skip_blend_* in float64: s = sigmoid(*skip_weight) in double, *g_skip_weight a double. */
+int pde_skip_blend_f64_forward(int64_t n, const double* u0, const double* u, const double* skip_weight, double* out,
+                               void* stream);
+size_t pde_skip_blend_f64_backward_workspace_bytes(int64_t n);
+int pde_skip_blend_f64_backward(int64_t n, const double* g, const double* u0, const double* u, const double* skip_weight,
+                                double* g_u0, double* g_u, double* g_skip_weight,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* pde_explicit5_* in float64, any plane size.  states: room for (num_steps-1) double tensors of u's shape, required
+ * when num_steps > 1 (the inputs of steps 2..num_steps). */
+int pde_explicit5_f64_forward(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* alpha_base,
+                              const double* channel_scaling, double dt, double eps, double max_coeff, double relax,
+                              int32_t num_steps, double* states, double* out, void* stream);
+size_t pde_explicit5_f64_backward_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_steps);
+int pde_explicit5_f64_backward(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* states,
+                               const double* gout, const double* alpha_base, const double* channel_scaling,
+                               double dt, double eps, double max_coeff, double relax, int32_t num_steps,
+                               double* gu, double* g_alpha_base, double* g_channel_scaling,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* pde_jacobi_* in float64, 2 <= H, W <= 64. */
+int pde_jacobi_f64_forward(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* a_row,
+                           const double* b_col, double* out, void* stream);
+size_t pde_jacobi_f64_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt);
+int pde_jacobi_f64_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* gout,
+                            const double* a_row, const double* b_col, double* gu, double* g_a_row, double* g_b_col,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- utilities ------------------------------------------------------------------------- */
 
