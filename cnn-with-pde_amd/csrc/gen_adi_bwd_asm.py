@@ -44,6 +44,8 @@ PLANE_B = N * N * 4
 
 
 class Emit:
+    HAZ = 2                      # wait states between a VALU write and a v_permlane32_swap reading it (and swap -> VALU)
+
     def __init__(self):
         self.out = []
         self.lgkm = []           # outstanding LDS ops in issue order: set of VGPRs they will write
@@ -51,13 +53,51 @@ class Emit:
         self.smem = False        # scalar loads outstanding (they return out of order: only lgkmcnt(0) is safe)
         self.nvalu = 0
         self.vop2_only = False   # diagnostic builds: time the stream with v_fmac in place of v_fma (wrong sign)
+        # wait-state history: per issued instruction (most recent last) the VGPRs a VALU wrote and whether it was a lane
+        # exchange; a forward branch keeps a copy for its target label, where the paths merge (worst case of each slot)
+        self.hist = []
+        self.pending = {}
+        self.count_haz = False   # MODE C: the wait states around lane exchanges come from the history, not fixed s_nops
 
     # -- plumbing
-    def raw(self, s, comment=None):
+    def _slot(self, writes=frozenset(), swap=False):
+        self.hist.append((frozenset(writes), swap))
+        del self.hist[:-self.HAZ]
+
+    def raw(self, s, comment=None, writes=frozenset(), swap=False):
         self.out.append("\t" + s + (f"\t; {comment}" if comment else ""))
+        op = s.split()[0]
+        if op == "s_nop":
+            for _ in range(int(s.split()[1]) + 1):
+                self._slot()
+            return
+        self._slot(writes, swap)
+        if op.startswith("s_cbranch") or op == "s_branch":
+            self.pending.setdefault(s.split()[1], []).append(list(self.hist))
 
     def label(self, name):
         self.out.append(f"{name}:")
+        for h in self.pending.pop(name, []):
+            a, b = [None] * (self.HAZ - len(self.hist)) + self.hist, [None] * (self.HAZ - len(h)) + h
+            self.hist = [(x or (frozenset(), False)) if y is None else (y if x is None else (x[0] | y[0], x[1] or y[1]))
+                         for x, y in zip(a, b)]
+
+    def wait_states(self, reads, swap):
+        """s_nop in front of an instruction reading `reads`: a lane exchange (swap=True) waits HAZ states behind any VALU
+        write of its operands, and any VALU waits HAZ states behind a lane exchange that wrote one of its sources"""
+        reads = set(reads)
+        for d, (w, was_swap) in enumerate(reversed(self.hist)):
+            if w & reads and (swap or was_swap):
+                self.raw(f"s_nop {self.HAZ - d - 1}")
+                return
+
+    def ool(self, fn):
+        """emit fn's instructions out of line (after the step loop): returns their text; the in-line state is kept"""
+        out, hist = self.out, list(self.hist)
+        self.out = []
+        fn()
+        text, self.out, self.hist = self.out, out, hist
+        return text
 
     def comment(self, s):
         self.out.append(f"\t; {s}")
@@ -108,7 +148,9 @@ class Emit:
             ops = [o.strip() for o in text[len("v_fma_f32 "):].split(",")]
             text = f"v_fmac_f32 {ops[0]}, {ops[1].lstrip('-')}, {ops[2]}"
         self.need(set(dst) | set(src))
-        self.raw(text, comment)
+        if self.count_haz:
+            self.wait_states(src, False)
+        self.raw(text, comment, writes=dst)
         self.nvalu += 1
 
     def salu(self, text, comment=None):
@@ -161,9 +203,13 @@ def gen(NW, ABL=0, MODE="A"):
     a sweep are HELD in registers — fetched for the NEXT sweep as the current sweep's pass frees them, kept across the twin x
     sweeps of neighbouring time steps —, two images per wave so that the re-layout writes ride inside the G passes, the next
     chunk's planes prefetched into 64 registers during the chunk's last time step, the time-weighted sums updated in the
-    latency shadow of the next sweep's junction exchange."""
-    assert NW in (8, 12, 16) and MODE in ("A", "B")
-    BM = MODE == "B"
+    latency shadow of the next sweep's junction exchange.  MODE "C": MODE B's arithmetic in the same order per element, with
+    the scalar work taken out of the time step (bases per chunk, running record / table pointers, the counter targets
+    carried from step to step, one poll for both counters, the rare paths out of line) and the wait states of the lane
+    exchanges counted by `Emit` instead of fixed `s_nop`s."""
+    assert NW in (8, 12, 16) and MODE in ("A", "B", "C")
+    BM = MODE in ("B", "C")
+    SC = MODE == "C"
     NT = NW * 64
     PPI = 2 * NW
     NPI = (3 * PIECES + NW - 1) // NW          # DMA pieces per wave and time step
@@ -183,7 +229,9 @@ def gen(NW, ABL=0, MODE="A"):
     assert (NW - 1) * WIMG_B < 65536           # the final reduction reaches every wave's image through the offset field
     e = Emit()
     e.vop2_only = bool(ABL & 64)
-    name = f"adi_bwd_asm_n32_w{NW}" + ("b" if BM else "") + (f"a{ABL}" if ABL else "")
+    e.count_haz = SC
+    name = f"adi_bwd_asm_n32_w{NW}" + {"A": "", "B": "b", "C": "c"}[MODE] + (f"a{ABL}" if ABL else "")
+    assert not (SC and ABL & (4 | 8 | 2048 | 8192 | 16384 | 65536)), "diagnostic bits of MODE B only"
 
     NMARK = 16
 
@@ -222,7 +270,9 @@ def gen(NW, ABL=0, MODE="A"):
 
     def stage(n):
         """Diagnostic stop: with the argument block's last word set to n the workgroup leaves here (results are then
-        garbage; used once to bisect a fault).  Production launches pass 0."""
+        garbage; used once to bisect a fault).  Production launches pass 0.  (MODE C: none; s31 holds S_RNKK.)"""
+        if SC:
+            return
         e.salu(f"s_cmp_eq_u32 s31, {n}")
         e.salu("s_cbranch_scc1 L_end")
 
@@ -295,6 +345,15 @@ def gen(NW, ABL=0, MODE="A"):
     S_DBG = 92                                  # 64-bit: stamp buffer (diagnostic builds)
     S_STAMP = 94                                # 64-bit: s_memtime value
     NSGPR = 96
+    if SC:
+        S_CNTC, S_CNTO = 6, 7                   # LDS byte address of ready[this set] and of ready[other set] (see flag_*)
+        S_RT, S_DT = S_TSTEP, S_KKN             # targets of ready[this set] and done[other set] in this time step
+        S_AJ = [96, 97, 98]                     # 3kk at which the x2 / y / x0 update adjusts (per chunk; -1: none)
+        S_PVH = 99                              # pieces to issue when the newest x record is held
+        S_SRCTOP = 100                          # 64-bit: source of step K-1 of a chunk
+        S_RNKK = 31                             # kk >= S_RNKK: load the newest x record's rows (K-1 with twins, else 0)
+        S_PFKK = 91                             # kk at which the next chunk's planes are prefetched (per chunk; -1: none)
+        NSGPR = 102
 
     # =============================================================================================================
     e.out.append('\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
@@ -430,6 +489,14 @@ def gen(NW, ABL=0, MODE="A"):
         e.salu(f"s_cmp_eq_u32 s{S_T1}, 0")                                  # record 0 of the set = the step's newest x sweep
         e.salu(f"s_cselect_b32 s{S_T3}, {1 << i}, 0")
         e.salu(f"s_or_b32 s{S_PX}, s{S_PX}, s{S_T3}")
+    if SC:
+        # with twin records (flags bit 1): the pieces of a step whose newest x record is held are all valid ones but
+        # those of record 0, and that record's rows are loaded at a chunk's first item (kk >= K-1) only, else always (kk >= 0)
+        e.salu(f"s_sub_u32 s{S_T1}, s{S_K}, 1")
+        e.salu(f"s_bitcmp1_b32 s{S_ACCP}, 1")
+        e.salu(f"s_cselect_b32 s{S_T0}, s{S_PX}, 0")
+        e.salu(f"s_cselect_b32 s{S_RNKK}, s{S_T1}, 0")
+        e.salu(f"s_andn2_b32 s{S_PVH}, s{S_PV}, s{S_T0}")
 
     def dma_step(kk_sgpr, set_expr_sgpr, skip_twin=False):
         """Bring the three records of time step kk into the set whose LDS base is in set_expr_sgpr (untracked: waited
@@ -464,6 +531,23 @@ def gen(NW, ABL=0, MODE="A"):
                 e.label(f"L_nodma_{dma_step.n}_{i}")
         dma_step.n += 1
     dma_step.n = 0
+
+    def dma_step_sc(set_sgpr, mask_sgpr):
+        """MODE C: the pieces of the step whose records start at S_SRC (kept from step to step) into the set at
+        set_sgpr; only the pieces that some wave may lack (record 0: held with twins; past the 42) branch on mask_sgpr.
+        M0 is written first so that the address adds cover its wait state."""
+        for i in range(NPI):
+            maybe = NW * i < PIECES or NW * i + NW > 3 * PIECES
+            if maybe:
+                e.salu(f"s_bitcmp1_b32 s{mask_sgpr}, {i}")
+                e.salu(f"s_cbranch_scc0 L_nodma_{dma_step.n}_{i}")
+            e.salu(f"s_add_u32 m0, s{set_sgpr}, s{S_DL[i]}")
+            e.salu(f"s_add_u32 s{S_A0}, s{S_SRC}, s{S_DS[i]}")
+            e.salu(f"s_addc_u32 s{S_A0 + 1}, s{S_SRC + 1}, 0")
+            e.raw(f"global_load_lds_dwordx4 {v(V_LANE16)}, s[{S_A0}:{S_A0 + 1}]")
+            if maybe:
+                e.label(f"L_nodma_{dma_step.n}_{i}")
+        dma_step.n += 1
 
     def load_dts(kk_sgpr):
         e.salu(f"s_mul_i32 s{S_T0}, s{kk_sgpr}, 12")
@@ -521,12 +605,58 @@ def gen(NW, ABL=0, MODE="A"):
         e.salu(f"s_branch L_poll_{tag}")
         e.label(f"L_polled_{tag}")
 
+    # MODE C: the same counters with done[] stored the other way round — ready[s] at CNT0 + 4s, done[s] at CNT0 + 12 - 4s —
+    # so that done[other set] lies 8 bytes above ready[this set] (one ds_read2_b32 polls both) and done[this set] 8 above
+    # ready[other set]; S_CNTC / S_CNTO hold the two ready addresses and swap with the set.  The targets NW*(t/2 + 1) of
+    # ready and NW*((t+1)/2) of done in time step t follow each other: RT(t+1) = DT(t) + NW, DT(t+1) = RT(t).
+    def flag_add_sc(addr_sgpr, off):
+        e.valu(f"v_mov_b32 {v(VDTS)}, s{addr_sgpr}", dst=[VDTS])
+        e.valu(f"v_mov_b32 {v(VADDR)}, 1", dst=[VADDR])
+        e.need({VDTS, VADDR})
+        e.raw("s_mov_b64 exec, 1")
+        e.raw(f"ds_add_u32 {v(VDTS)}, {v(VADDR)}" + (f" offset:{off}" if off else ""))
+        e.raw("s_mov_b64 exec, -1")
+        e.lgkm.append(set())
+
+    def flag_poll_sc():
+        """spin (bounded; the spin's tail out of line) until ready[this set] >= S_RT and done[other set] >= S_DT"""
+        a, b = NQ[0][0], NQ[0][1]
+        e.assert_idle()
+        e.valu(f"v_mov_b32 {v(VDTS)}, s{S_CNTC}", dst=[VDTS])
+        e.salu(f"s_mov_b32 s{S_T1}, 0")
+        e.label("L_poll")
+        e.raw(f"ds_read2_b32 {vp(a)}, {v(VDTS)} offset1:2")
+        e.raw("s_waitcnt lgkmcnt(0)")
+        e.raw(f"v_readfirstlane_b32 s{S_T2}, {v(a)}")
+        e.raw(f"v_readfirstlane_b32 s{S_T3}, {v(b)}")
+        e.salu(f"s_cmp_lt_u32 s{S_T2}, s{S_RT}")
+        e.salu("s_cbranch_scc1 L_poll_wait")
+        e.salu(f"s_cmp_lt_u32 s{S_T3}, s{S_DT}")
+        e.salu("s_cbranch_scc1 L_poll_wait")
+        e.label("L_polled")
+
+        def tail():
+            e.label("L_poll_wait")
+            e.salu(f"s_add_u32 s{S_T1}, s{S_T1}, 1")
+            e.salu(f"s_cmp_lt_u32 s{S_T1}, 0x100000")             # (never reached unless a count is wrong)
+            e.salu("s_cbranch_scc0 L_polled")
+            e.raw("s_sleep 1")
+            e.salu("s_branch L_poll")
+        OOL.append(e.ool(tail))
+
+    OOL = []                                    # MODE C: rare paths, placed behind the time-step loop
     if FLAGS:
         for i in range(4):
             e.valu(f"v_mov_b32 {v(IB[0] + i)}, 0", dst=[IB[0] + i])
         e.valu(f"v_mov_b32 {v(VADDR)}, {CNT0}", dst=[VADDR])
         e.ds_write(f"ds_write_b128 {v(VADDR)}, {vq(IB[0])}", [IB[0] + j for j in range(4)], VADDR)
-        e.salu(f"s_mov_b32 s{S_TSTEP}, 0")
+        if SC:
+            e.salu(f"s_mov_b32 s{S_CNTC}, {CNT0}")
+            e.salu(f"s_mov_b32 s{S_CNTO}, {CNT0 + 4}")
+            e.salu(f"s_mov_b32 s{S_RT}, {NW}")
+            e.salu(f"s_mov_b32 s{S_DT}, 0")
+        else:
+            e.salu(f"s_mov_b32 s{S_TSTEP}, 0")
     if bool(ABL & 8192) != BM:
         # the second-dispatched half of the waves loses the SIMD's arbitration against its older partner on every
         # instruction and reaches each step barrier ~2k cycles late (tools/asm_timeline.py): one static priority evens it
@@ -547,7 +677,10 @@ def gen(NW, ABL=0, MODE="A"):
     e.salu(f"s_mov_b32 s{S_Q}, s{S_g}")
     e.drain()
     e.raw("s_barrier")
-    if FLAGS:
+    if SC:
+        e.salu(f"s_mov_b64 s[{S_SRCTOP}:{S_SRCTOP + 1}], s[{S_SRC}:{S_SRC + 1}]")
+        flag_add_sc(S_CNTC, 0)                   # ready[set 0] += 1: the barrier above stands for the landing
+    elif FLAGS:
         flag_add(0, False)                       # ready[set 0] += 1: the barrier above stands for the landing
     stage(3)
 
@@ -887,9 +1020,11 @@ def gen(NW, ABL=0, MODE="A"):
         t_update(AY, TY, dts_sgpr, S_FIRSTY, S_TLY, "y")
 
     # ---- MODE B sweeps (coefficient rows held in CE / CI / CK) ----------------------------------------------------
-    def rd_row(base, off, q, addr):
+    def rd_row(base, off, q, addr, rec=0):
+        """(MODE C: addr is the set's base VADDRN for every record; the record is reached through the offset field)"""
         if ABL & 2:
             return
+        off += rec * RECP_B if SC else 0
         e.ds_read(f"ds_read_b128 {vq(base + 4 * q)}, {v(addr)} offset:{off + 16 * q}", [base + 4 * q + j for j in range(4)], addr)
 
     def rec_addr(vreg, rec_index):
@@ -904,8 +1039,24 @@ def gen(NW, ABL=0, MODE="A"):
         e.valu(f"v_add_u32 {v(VDTS)}, s{S_T0}, {v(VDTS)}", dst=[VDTS], src=[VDTS])
         e.ds_read(f"ds_read_b32 {v(JN)}, {v(VDTS)} offset:{OFF_JN}", [JN], VDTS)
 
+    def jn_addr():
+        """MODE C: VDTS = the set's junction-factor column (S_REC = the set's LDS base); the record is in the offset"""
+        e.valu(f"v_bfe_u32 {v(VDTS)}, {v(V_LANE16)}, 2, 7", dst=[VDTS], src=[V_LANE16])          # 4 * l
+        e.valu(f"v_add_u32 {v(VDTS)}, s{S_REC}, {v(VDTS)}", dst=[VDTS], src=[VDTS])
+
+    def jn_load(rec_index):
+        if not (ABL & 2):
+            e.ds_read(f"ds_read_b32 {v(JN)}, {v(VDTS)} offset:{rec_index * RECP_B + OFF_JN}", [JN], VDTS)
+
     def load_rows_now(rec_index):
         """all three rows and the junction factor of a record, at once (chunk start; schedules without twin records)"""
+        if SC:
+            jn_addr()
+            jn_load(rec_index)
+            for base, off in ((CE, OFF_E), (CI, OFF_INV), (CK, OFF_KAP)):
+                for q in range(4):
+                    rd_row(base, off, q, VADDRN, rec_index)
+            return
         rec_addr(VADDR, rec_index)
         rd_jn(rec_index)
         for q in range(4):
@@ -914,6 +1065,30 @@ def gen(NW, ABL=0, MODE="A"):
             rd_row(CI, OFF_INV, q, VADDR)
         for q in range(4):
             rd_row(CK, OFF_KAP, q, VADDR)
+
+    def t_update_sc(acc, tacc, dts_sgpr, aj_sgpr, tlast_sgpr, tag):
+        """MODE C form of t_update_b: S_SS = 3kk, aj_sgpr = the 3kk at which this update adjusts (the chunk's earliest
+        sweep of the axis, when another chunk follows); the adjusting path is out of line.  Same operations per element."""
+        if ABL & 256:
+            return
+        lab = f"L_tuc_{tag}_{t_update_b.n}"
+        t_update_b.n += 1
+        e.salu(f"s_cmp_eq_u32 s{S_SS}, s{aj_sgpr}")
+        e.salu(f"s_cbranch_scc1 {lab}_adj")
+
+        def adj():
+            e.label(f"{lab}_adj")
+            e.valu(f"v_mov_b32 {v(VDTS)}, s{dts_sgpr}", dst=[VDTS])
+            e.valu(f"v_subrev_f32 {v(VDTS)}, s{tlast_sgpr}, {v(VDTS)}", dst=[VDTS], src=[VDTS])
+            e.salu(f"s_branch {lab}_fma")
+        OOL.append(e.ool(adj))
+        e.salu(f"s_lshl_b32 s{S_T1}, s{dts_sgpr}, 1")                # SCC = (dts != +-0)
+        e.salu(f"s_cbranch_scc0 {lab}_skip")
+        e.valu(f"v_mov_b32 {v(VDTS)}, s{dts_sgpr}", dst=[VDTS])
+        e.label(f"{lab}_fma")
+        for k in range(16):
+            e.valu(f"v_fmac_f32 {v(tacc + k)}, {v(VDTS)}, {v(acc + k)}", dst=[tacc + k], src=[tacc + k, VDTS, acc + k])
+        e.label(f"{lab}_skip")
 
     def t_update_b(acc, tacc, dts_sgpr, first_sgpr, tlast_sgpr, ss_delta, tag):
         """as t_update, for the sweep S_SS + ss_delta, with VDTS as the scratch register"""
@@ -937,16 +1112,19 @@ def gen(NW, ABL=0, MODE="A"):
             e.valu(f"v_fmac_f32 {v(tacc + k)}, {v(VDTS)}, {v(acc + k)}", dst=[tacc + k], src=[tacc + k, VDTS, acc + k])
         e.label(f"{lab}_skip")
     t_update_b.n = 0
+    t_upd = t_update_sc if SC else t_update_b
 
     def swap(a, b):
         if ABL & 128:
             return
         e.need({a, b})
-        e.raw(f"v_permlane32_swap_b32 {v(a)}, {v(b)}")
+        if SC and not (ABL & 32):
+            e.wait_states({a, b}, True)
+        e.raw(f"v_permlane32_swap_b32 {v(a)}, {v(b)}", writes={a, b}, swap=True)
         e.nvalu += 1
 
     def nop2():
-        if not (ABL & 32):
+        if not (ABL & 32) and not SC:       # (MODE C: Emit counts the wait states in front of each exchange)
             e.raw("s_nop 1")
 
     def h_link(k):
@@ -1045,7 +1223,7 @@ def gen(NW, ABL=0, MODE="A"):
 
     def sweep_x_b(rec_index, next_rec, relayout_after, deferred, own_t):
         e.comment(f"==== x sweep (held rows), record {rec_index} of the set")
-        if next_rec is not None:
+        if next_rec is not None and not SC:
             rec_addr(VADDRN, next_rec)
         # partner half's innermost state (old values), exchanged between the first links of the H recurrence
         e.valu(f"v_mov_b32 {v(NQ[0][1])}, {v(X[0] + 15)}", dst=[NQ[0][1]], src=[X[0] + 15])
@@ -1071,10 +1249,12 @@ def gen(NW, ABL=0, MODE="A"):
                 nq = nqreg(p, 15)
                 e.valu(f"v_fmac_f32 {v(nq)}, {v(V_M2)}, {v(X[p] + 15)}", dst=[nq], src=[nq, V_M2, X[p] + 15])
 
-        sh1 = (lambda: t_update_b(*deferred)) if deferred else None
+        sh1 = (lambda: t_upd(*deferred)) if deferred else None
+        if SC and sh1 is None and next_rec is not None:
+            sh1 = jn_addr
         junction_b(sh1, nq15_a, nq15_b)
         if next_rec is not None:
-            rd_jn(next_rec)
+            jn_load(next_rec) if SC else rd_jn(next_rec)
         if relayout_after:
             relayout_bases(True)
         pend = None
@@ -1095,19 +1275,19 @@ def gen(NW, ABL=0, MODE="A"):
                     e.valu(f"v_fma_f32 {v(X[p] + kk_)}, -{v(CK + kk_)}, {v(nqreg(p, kk_))}, {v(X[p] + kk_)}",
                            dst=[X[p] + kk_], src=[CK + kk_, nqreg(p, kk_), X[p] + kk_])
                 if next_rec is not None and kk_ % 4 == 0:
-                    rd_row(CK, OFF_KAP, kk_ // 4, VADDRN)
+                    rd_row(CK, OFF_KAP, kk_ // 4, VADDRN, next_rec)
             if k >= 1:
                 for p in (0, 1):
                     e.valu(f"v_fmac_f32 {v(R[p] + k - 1)}, {v(CE + k)}, {v(R[p] + k)}", dst=[R[p] + k - 1], src=[R[p] + k - 1, CE + k, R[p] + k])
                 if next_rec is not None:
                     if k % 4 == 0:
-                        rd_row(CE, OFF_E, k // 4, VADDRN)
+                        rd_row(CE, OFF_E, k // 4, VADDRN, next_rec)
                     elif k == 1:
-                        rd_row(CE, OFF_E, 0, VADDRN)
+                        rd_row(CE, OFF_E, 0, VADDRN, next_rec)
             for p in (0, 1):
                 e.valu(f"v_mul_f32 {v(R[p] + k)}, {v(CI + k)}, {v(R[p] + k)}", dst=[R[p] + k], src=[CI + k, R[p] + k])
             if next_rec is not None and k % 4 == 0:
-                rd_row(CI, OFF_INV, k // 4, VADDRN)
+                rd_row(CI, OFF_INV, k // 4, VADDRN, next_rec)
             if relayout_after:
                 for p in (0, 1):
                     relayout_write(p, k)
@@ -1119,22 +1299,29 @@ def gen(NW, ABL=0, MODE="A"):
         for p in (0, 1):
             e.valu(f"v_fma_f32 {v(X[p])}, -{v(CK)}, {v(nqreg(p, 0))}, {v(X[p])}", dst=[X[p]], src=[CK, nqreg(p, 0), X[p]])
         if next_rec is not None:
-            rd_row(CK, OFF_KAP, 0, VADDRN)
+            rd_row(CK, OFF_KAP, 0, VADDRN, next_rec)
         if own_t:
-            t_update_b(*own_t)
+            t_upd(*own_t)
         if relayout_after:
             relayout_fix()
 
     def sweep_y_b(rec_index, next_rec, deferred):
         e.comment(f"==== y sweep (held rows), record {rec_index} of the set")
-        rec_addr(VADDRN, next_rec)
+        if not SC:
+            rec_addr(VADDRN, next_rec)
         mark(7)                                 # (drains: the adjoint has arrived in column layout)
         for k in range(1, 16):
             h_link(k)
         mark(8)
-        sh1 = (lambda: t_update_b(*deferred)) if deferred else None
-        junction_b(sh1, None, None)
-        rd_jn(next_rec)
+        sh1 = (lambda: t_upd(*deferred)) if deferred else None
+        if SC:
+            # the next record's junction-factor address in the two exchange gaps (VDTS is free once the update is done)
+            junction_b(sh1, lambda: e.valu(f"v_bfe_u32 {v(VDTS)}, {v(V_LANE16)}, 2, 7", dst=[VDTS], src=[V_LANE16]),
+                       lambda: e.valu(f"v_add_u32 {v(VDTS)}, s{S_REC}, {v(VDTS)}", dst=[VDTS], src=[VDTS]))
+            jn_load(next_rec)
+        else:
+            junction_b(sh1, None, None)
+            rd_jn(next_rec)
         relayout_bases(True)
         for k in range(15, -1, -1):
             if k == 7:
@@ -1143,13 +1330,13 @@ def gen(NW, ABL=0, MODE="A"):
                 for p in (0, 1):
                     e.valu(f"v_fmac_f32 {v(R[p] + k - 1)}, {v(CE + k)}, {v(R[p] + k)}", dst=[R[p] + k - 1], src=[R[p] + k - 1, CE + k, R[p] + k])
                 if k % 4 == 0:
-                    rd_row(CE, OFF_E, k // 4, VADDRN)
+                    rd_row(CE, OFF_E, k // 4, VADDRN, next_rec)
                 elif k == 1:
-                    rd_row(CE, OFF_E, 0, VADDRN)
+                    rd_row(CE, OFF_E, 0, VADDRN, next_rec)
             for p in (0, 1):
                 e.valu(f"v_mul_f32 {v(R[p] + k)}, {v(CI + k)}, {v(R[p] + k)}", dst=[R[p] + k], src=[CI + k, R[p] + k])
             if k % 4 == 0:
-                rd_row(CI, OFF_INV, k // 4, VADDRN)
+                rd_row(CI, OFF_INV, k // 4, VADDRN, next_rec)
             for p in (0, 1):
                 relayout_write(p, k)
         mark(9)
@@ -1177,7 +1364,76 @@ def gen(NW, ABL=0, MODE="A"):
                 e.valu(f"v_fma_f32 {v(X[p] + k)}, -{v(CK + k)}, {v(nq)}, {v(X[p] + k)}", dst=[X[p] + k], src=[CK + k, nq, X[p] + k])
             klast, plast = grp[-1]
             if plast == 1 and klast % 4 == 3:
-                rd_row(CK, OFF_KAP, klast // 4, VADDRN)
+                rd_row(CK, OFF_KAP, klast // 4, VADDRN, next_rec)
+
+    def step_sc():
+        """MODE C time step: the sweeps of MODE B in the same order; the scalar work is one add per use of a base kept
+        per chunk or carried from step to step, the rare paths (spin, adjusting update, plane prefetch) out of line."""
+        e.salu(f"s_mul_i32 s{S_SS}, s{S_KK}, 3")
+        flag_poll_sc()                           # my step's records have landed, nobody still reads the other set
+        e.salu(f"s_add_u32 s{S_REC}, s{S_SET}, {RING0}")
+        e.valu(f"v_add_u32 {v(VADDRN)}, s{S_REC}, {v(V_CROW)}", dst=[VADDRN], src=[V_CROW])   # the set's rows
+        # next step of my job: kk-1 of this chunk (records SWB3 lower), or K-1 of the next one
+        e.salu(f"s_sub_u32 s{S_SRC}, s{S_SRC}, s{S_SWB3}")
+        e.salu(f"s_subb_u32 s{S_SRC + 1}, s{S_SRC + 1}, 0")
+        e.salu(f"s_cmp_gt_i32 s{S_KK}, 0")
+        e.salu(f"s_cselect_b32 s{S_HASNEXT}, 1, s{S_MORE}")
+        e.salu(f"s_cselect_b64 s[{S_SRC}:{S_SRC + 1}], s[{S_SRC}:{S_SRC + 1}], s[{S_SRCTOP}:{S_SRCTOP + 1}]")
+        e.salu(f"s_cselect_b32 s{S_T3}, s{S_PVH}, s{S_PV}")        # a chunk's first item holds no rows
+        e.salu(f"s_mul_i32 s{S_T0}, s{S_KK}, 12")
+        e.s_load(f"s_load_dwordx4 s[{S_DTS[0]}:{S_DTS[0] + 3}], s[{S_DTSB}:{S_DTSB + 1}], s{S_T0}")   # (+ one spare)
+        e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
+        e.salu("s_cbranch_scc1 L_nonext")
+        if not (ABL & 4) and not (ABL & 2048):
+            e.salu(f"s_xor_b32 s{S_T2}, s{S_SET}, {3 * RECP_B}")
+            dma_step_sc(S_T2, S_T3)
+        e.label("L_nonext")
+        e.drain(vm=False)                        # (the time increments)
+        mark(1)
+        e.salu(f"s_cmp_ge_u32 s{S_KK}, s{S_RNKK}")
+        e.salu("s_cbranch_scc0 L_rows_held")
+        load_rows_now(0)
+        e.label("L_rows_held")
+        sweep_x_b(0, 1, True, None, None)
+        e.raw("s_waitcnt vmcnt(0)")              # my pieces of the next step's records (issued above) have landed
+        e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
+        e.salu("s_cbranch_scc1 L_noready")
+        flag_add_sc(S_CNTO, 0)                   # ready[other set] += 1
+        e.label("L_noready")
+        if not (ABL & 8):
+            e.salu(f"s_cmp_eq_u32 s{S_KK}, s{S_PFKK}")
+            e.salu("s_cbranch_scc1 L_prefetch")
+
+            def prefetch():
+                e.label("L_prefetch")
+                for d, pb in zip(PFR, S_PB):
+                    for i in range(4):
+                        e.raw(f"global_load_dwordx4 {vq(d + 4 * i)}, {v(V_LANE16)}, s[{pb}:{pb + 1}] offset:{1024 * i} nt")
+                e.salu("s_branch L_noprefetch")
+            OOL.append(e.ool(prefetch))
+            e.label("L_noprefetch")
+        mark(2)
+        sweep_y_b(1, 2, (AX, TX, S_DTS[2], S_AJ[0], S_TLX, "x2"))
+        flag_add_sc(S_CNTO, 8)                   # done[this set] += 1: the last sweep's rows are in registers
+        mark(3)
+        sweep_x_b(2, None, False, (AY, TY, S_DTS[1], S_AJ[1], S_TLY, "y"), (AX, TX, S_DTS[0], S_AJ[2], S_TLX, "x0"))
+        mark(4)
+        e.drain(vm=False)
+        e.salu(f"s_add_u32 s{S_T0}, s{S_DT}, {NW}")
+        e.salu(f"s_mov_b32 s{S_DT}, s{S_RT}")
+        e.salu(f"s_mov_b32 s{S_RT}, s{S_T0}")
+        e.salu(f"s_xor_b32 s{S_CNTC}, s{S_CNTC}, 4")
+        e.salu(f"s_xor_b32 s{S_CNTO}, s{S_CNTO}, 4")
+        mark(5)
+        mark(6)
+        e.salu(f"s_xor_b32 s{S_SET}, s{S_SET}, {3 * RECP_B}")
+        e.salu(f"s_sub_u32 s{S_KK}, s{S_KK}, 1")
+        e.salu(f"s_cmp_ge_i32 s{S_KK}, 0")
+        e.salu("s_cbranch_scc1 L_step")
+        e.salu("s_branch L_step_end")
+        for block in OOL:
+            e.out.extend(block)
+        e.label("L_step_end")
 
     # ---- main loops ---------------------------------------------------------------------------------------------
     e.salu(f"s_cmp_lt_u32 s{S_Q}, s{S_NCHUNK}")          # a group beyond the batch still publishes (zero) sums
@@ -1196,124 +1452,140 @@ def gen(NW, ABL=0, MODE="A"):
     else:
         load_planes()
     stage(4)
+    if SC:
+        # per chunk: the next chunk's plane bases (prefetched in this chunk's last time step, when there is one) and the
+        # time step in which each time-weighted update meets its axis' earliest sweep (-1: no adjusting in this chunk)
+        e.salu(f"s_add_u32 s{S_IT}, s{S_Q}, s{S_G}")
+        plane_bases(S_GY, [S_PB[0], S_PB[1]], S_IT)
+        plane_bases(S_Y, [S_PB[2], S_PB[3]], S_IT)
+        e.salu(f"s_sub_u32 s{S_AJ[0]}, s{S_FIRSTX}, 2")             # x2: sweep 3kk+2
+        e.salu(f"s_sub_u32 s{S_AJ[1]}, s{S_FIRSTY}, 1")             # y:  sweep 3kk+1
+        e.salu(f"s_cmp_lg_u32 s{S_MORE}, 0")
+        e.salu(f"s_cselect_b32 s{S_AJ[0]}, s{S_AJ[0]}, -1")
+        e.salu(f"s_cselect_b32 s{S_AJ[1]}, s{S_AJ[1]}, -1")
+        e.salu(f"s_cselect_b32 s{S_AJ[2]}, s{S_FIRSTX}, -1")        # x0: sweep 3kk
+        e.salu(f"s_cselect_b32 s{S_PFKK}, 0, -1")
     e.salu(f"s_sub_u32 s{S_KK}, s{S_K}, 1")
     e.label("L_step")
     e.assert_idle()
     mark(0)
-    if FLAGS:
-        # my step's records have landed (every wave counted its pieces), and nobody still reads the other set
-        e.salu(f"s_lshr_b32 s{S_T3}, s{S_TSTEP}, 1")
-        e.salu(f"s_add_u32 s{S_T3}, s{S_T3}, 1")
-        e.salu(f"s_mul_i32 s{S_T3}, s{S_T3}, {NW}")                      # NW * (t/2 + 1)
-        flag_wait(0, False, S_T3, "ready")
-        e.salu(f"s_cmp_eq_u32 s{S_TSTEP}, 0")
-        e.salu("s_cbranch_scc1 L_nodonewait")
-        e.salu(f"s_sub_u32 s{S_T3}, s{S_TSTEP}, 1")
-        e.salu(f"s_lshr_b32 s{S_T3}, s{S_T3}, 1")
-        e.salu(f"s_add_u32 s{S_T3}, s{S_T3}, 1")
-        e.salu(f"s_mul_i32 s{S_T3}, s{S_T3}, {NW}")                      # NW * ((t-1)/2 + 1)
-        flag_wait(1, True, S_T3, "done")
-        e.label("L_nodonewait")
-    # next step of my job: kk-1 of this chunk, or K-1 of the next one
-    e.salu(f"s_sub_u32 s{S_T0}, s{S_KK}, 1")
-    e.salu(f"s_sub_u32 s{S_T1}, s{S_K}, 1")
-    e.salu(f"s_cmp_gt_i32 s{S_KK}, 0")
-    e.salu(f"s_cselect_b32 s{S_HASNEXT}, 1, s{S_MORE}")
-    e.salu(f"s_cselect_b32 s{S_KKN}, s{S_T0}, s{S_T1}")
-    if FLAGS:
-        load_dts(S_KK)                           # this step's time increments: they arrive behind the DMA issue below
-    e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
-    e.salu("s_cbranch_scc1 L_nonext")
-    if not (ABL & 4) and not (ABL & 2048):
-        e.salu(f"s_xor_b32 s{S_T2}, s{S_SET}, {3 * RECP_B}")
-        dma_step(S_KKN, S_T2, skip_twin=BM)
-    e.label("L_nonext")
-    def prefetch_block():
-        # the chunk's last time step: the next chunk's planes start their way into the prefetch registers
-        e.salu(f"s_cmp_eq_u32 s{S_KK}, 0")
-        e.salu(f"s_cselect_b32 s{S_T0}, s{S_MORE}, 0")
-        e.salu(f"s_cmp_eq_u32 s{S_T0}, 0")
-        e.salu("s_cbranch_scc1 L_noprefetch")
-        e.salu(f"s_add_u32 s{S_IT}, s{S_Q}, s{S_G}")
-        fetch_planes(PFR, S_IT, False)
-        e.label("L_noprefetch")
-
-    if FLAGS:
-        e.drain(vm=False)                        # (the time increments)
-    if BM and not (ABL & 8) and not FLAGS:
-        # the chunk's last time step: the next chunk's planes start their way into the prefetch registers
-        e.salu(f"s_cmp_eq_u32 s{S_KK}, 0")
-        e.salu(f"s_cselect_b32 s{S_T0}, s{S_MORE}, 0")
-        e.salu(f"s_cmp_eq_u32 s{S_T0}, 0")
-        e.salu("s_cbranch_scc1 L_noprefetch")
-        e.salu(f"s_add_u32 s{S_IT}, s{S_Q}, s{S_G}")
-        fetch_planes(PFR, S_IT, False)
-        e.label("L_noprefetch")
-    mark(1)
-    e.salu(f"s_mul_i32 s{S_SS}, s{S_KK}, 3")
-    e.salu(f"s_add_u32 s{S_SS}, s{S_SS}, 2")
-    if BM:
-        # the newest x sweep of the step shares its record with the sweep processed just before it (the first x sweep of the
-        # next time step: same time, same increment) — unless this is the chunk's first item or the schedule has no such twins
-        e.salu(f"s_sub_u32 s{S_T0}, s{S_K}, 1")
-        e.salu(f"s_cmp_eq_u32 s{S_KK}, s{S_T0}")
-        e.salu("s_cbranch_scc1 L_rows_now")
-        e.salu(f"s_bitcmp1_b32 s{S_ACCP}, 1")            # flags bit 1: twin records
-        e.salu("s_cbranch_scc1 L_rows_held")
-        e.label("L_rows_now")
-        load_rows_now(0)
-        e.label("L_rows_held")
-        sweep_x_b(0, 1, True, None, None)
-        if FLAGS:
-            # my pieces of the next step's records (issued at the top of this step) have landed by now
-            e.raw("s_waitcnt vmcnt(0)")
-            e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
-            e.salu("s_cbranch_scc1 L_noready")
-            flag_add(0, True)
-            e.label("L_noready")
-            if not (ABL & 8):
-                prefetch_block()
-        mark(2)
-        e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
-        sweep_y_b(1, 2, (AX, TX, S_DTS[2], S_FIRSTX, S_TLX, 1, "x2"))
-        if FLAGS:
-            flag_add(1, False)                   # done[this set] += 1: the last sweep's rows are in registers
-        mark(3)
-        e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
-        sweep_x_b(2, None, False, (AY, TY, S_DTS[1], S_FIRSTY, S_TLY, 1, "y"), (AX, TX, S_DTS[0], S_FIRSTX, S_TLX, 0, "x0"))
-        mark(4)
+    if SC:
+        step_sc()
     else:
-        sweep_x(0, S_DTS[2])
-        mark(2)
-        e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
-        sweep_y(1, S_DTS[1])
-        mark(3)
-        e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
-        sweep_x(2, S_DTS[0])
-        mark(4)
-    e.drain(vm=False)
-    if FLAGS:
-        e.salu(f"s_add_u32 s{S_TSTEP}, s{S_TSTEP}, 1")
-        mark(5)
-        mark(6)
-    else:
+        if FLAGS:
+            # my step's records have landed (every wave counted its pieces), and nobody still reads the other set
+            e.salu(f"s_lshr_b32 s{S_T3}, s{S_TSTEP}, 1")
+            e.salu(f"s_add_u32 s{S_T3}, s{S_T3}, 1")
+            e.salu(f"s_mul_i32 s{S_T3}, s{S_T3}, {NW}")                      # NW * (t/2 + 1)
+            flag_wait(0, False, S_T3, "ready")
+            e.salu(f"s_cmp_eq_u32 s{S_TSTEP}, 0")
+            e.salu("s_cbranch_scc1 L_nodonewait")
+            e.salu(f"s_sub_u32 s{S_T3}, s{S_TSTEP}, 1")
+            e.salu(f"s_lshr_b32 s{S_T3}, s{S_T3}, 1")
+            e.salu(f"s_add_u32 s{S_T3}, s{S_T3}, 1")
+            e.salu(f"s_mul_i32 s{S_T3}, s{S_T3}, {NW}")                      # NW * ((t-1)/2 + 1)
+            flag_wait(1, True, S_T3, "done")
+            e.label("L_nodonewait")
+        # next step of my job: kk-1 of this chunk, or K-1 of the next one
+        e.salu(f"s_sub_u32 s{S_T0}, s{S_KK}, 1")
+        e.salu(f"s_sub_u32 s{S_T1}, s{S_K}, 1")
+        e.salu(f"s_cmp_gt_i32 s{S_KK}, 0")
+        e.salu(f"s_cselect_b32 s{S_HASNEXT}, 1, s{S_MORE}")
+        e.salu(f"s_cselect_b32 s{S_KKN}, s{S_T0}, s{S_T1}")
+        if FLAGS:
+            load_dts(S_KK)                           # this step's time increments: they arrive behind the DMA issue below
         e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
-        e.salu("s_cbranch_scc1 L_nodts")
-        load_dts(S_KKN)
-        e.label("L_nodts")
-        e.raw("s_waitcnt vmcnt(0)")              # my pieces of the next step's records (and the plane prefetch) have landed
-        e.vm = []
-        mark(5)
-        if not (ABL & 4) and not (ABL & 1024):
-            e.raw("s_barrier")
-        e.drain(vm=False)                        # the time increments arrive while the barrier waits
-        mark(6)
-    stage(5)
-    if not (ABL & 4):
-        e.salu(f"s_xor_b32 s{S_SET}, s{S_SET}, {3 * RECP_B}")
-    e.salu(f"s_sub_u32 s{S_KK}, s{S_KK}, 1")
-    e.salu(f"s_cmp_ge_i32 s{S_KK}, 0")
-    e.salu("s_cbranch_scc1 L_step")
+        e.salu("s_cbranch_scc1 L_nonext")
+        if not (ABL & 4) and not (ABL & 2048):
+            e.salu(f"s_xor_b32 s{S_T2}, s{S_SET}, {3 * RECP_B}")
+            dma_step(S_KKN, S_T2, skip_twin=BM)
+        e.label("L_nonext")
+        def prefetch_block():
+            # the chunk's last time step: the next chunk's planes start their way into the prefetch registers
+            e.salu(f"s_cmp_eq_u32 s{S_KK}, 0")
+            e.salu(f"s_cselect_b32 s{S_T0}, s{S_MORE}, 0")
+            e.salu(f"s_cmp_eq_u32 s{S_T0}, 0")
+            e.salu("s_cbranch_scc1 L_noprefetch")
+            e.salu(f"s_add_u32 s{S_IT}, s{S_Q}, s{S_G}")
+            fetch_planes(PFR, S_IT, False)
+            e.label("L_noprefetch")
+
+        if FLAGS:
+            e.drain(vm=False)                        # (the time increments)
+        if BM and not (ABL & 8) and not FLAGS:
+            # the chunk's last time step: the next chunk's planes start their way into the prefetch registers
+            e.salu(f"s_cmp_eq_u32 s{S_KK}, 0")
+            e.salu(f"s_cselect_b32 s{S_T0}, s{S_MORE}, 0")
+            e.salu(f"s_cmp_eq_u32 s{S_T0}, 0")
+            e.salu("s_cbranch_scc1 L_noprefetch")
+            e.salu(f"s_add_u32 s{S_IT}, s{S_Q}, s{S_G}")
+            fetch_planes(PFR, S_IT, False)
+            e.label("L_noprefetch")
+        mark(1)
+        e.salu(f"s_mul_i32 s{S_SS}, s{S_KK}, 3")
+        e.salu(f"s_add_u32 s{S_SS}, s{S_SS}, 2")
+        if BM:
+            # the newest x sweep of the step shares its record with the sweep processed just before it (the first x sweep of the
+            # next time step: same time, same increment) — unless this is the chunk's first item or the schedule has no such twins
+            e.salu(f"s_sub_u32 s{S_T0}, s{S_K}, 1")
+            e.salu(f"s_cmp_eq_u32 s{S_KK}, s{S_T0}")
+            e.salu("s_cbranch_scc1 L_rows_now")
+            e.salu(f"s_bitcmp1_b32 s{S_ACCP}, 1")            # flags bit 1: twin records
+            e.salu("s_cbranch_scc1 L_rows_held")
+            e.label("L_rows_now")
+            load_rows_now(0)
+            e.label("L_rows_held")
+            sweep_x_b(0, 1, True, None, None)
+            if FLAGS:
+                # my pieces of the next step's records (issued at the top of this step) have landed by now
+                e.raw("s_waitcnt vmcnt(0)")
+                e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
+                e.salu("s_cbranch_scc1 L_noready")
+                flag_add(0, True)
+                e.label("L_noready")
+                if not (ABL & 8):
+                    prefetch_block()
+            mark(2)
+            e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
+            sweep_y_b(1, 2, (AX, TX, S_DTS[2], S_FIRSTX, S_TLX, 1, "x2"))
+            if FLAGS:
+                flag_add(1, False)                   # done[this set] += 1: the last sweep's rows are in registers
+            mark(3)
+            e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
+            sweep_x_b(2, None, False, (AY, TY, S_DTS[1], S_FIRSTY, S_TLY, 1, "y"), (AX, TX, S_DTS[0], S_FIRSTX, S_TLX, 0, "x0"))
+            mark(4)
+        else:
+            sweep_x(0, S_DTS[2])
+            mark(2)
+            e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
+            sweep_y(1, S_DTS[1])
+            mark(3)
+            e.salu(f"s_sub_u32 s{S_SS}, s{S_SS}, 1")
+            sweep_x(2, S_DTS[0])
+            mark(4)
+        e.drain(vm=False)
+        if FLAGS:
+            e.salu(f"s_add_u32 s{S_TSTEP}, s{S_TSTEP}, 1")
+            mark(5)
+            mark(6)
+        else:
+            e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
+            e.salu("s_cbranch_scc1 L_nodts")
+            load_dts(S_KKN)
+            e.label("L_nodts")
+            e.raw("s_waitcnt vmcnt(0)")              # my pieces of the next step's records (and the plane prefetch) have landed
+            e.vm = []
+            mark(5)
+            if not (ABL & 4) and not (ABL & 1024):
+                e.raw("s_barrier")
+            e.drain(vm=False)                        # the time increments arrive while the barrier waits
+            mark(6)
+        stage(5)
+        if not (ABL & 4):
+            e.salu(f"s_xor_b32 s{S_SET}, s{S_SET}, {3 * RECP_B}")
+        e.salu(f"s_sub_u32 s{S_KK}, s{S_KK}, 1")
+        e.salu(f"s_cmp_ge_i32 s{S_KK}, 0")
+        e.salu("s_cbranch_scc1 L_step")
     stage(6)
     if FLAGS:
         e.raw("s_waitcnt vmcnt(0)")              # the prefetched planes of the next chunk
@@ -1467,11 +1739,46 @@ amdhsa.version:
     return "\n".join(e.out) + "\n" + desc, info
 
 
-if __name__ == "__main__":
-    spec = sys.argv[1]                       # "<waves>[b][a<bits>]": "12", "8b", "8ba31" (a...: diagnostic build, see gen())
+def parse_spec(spec):
+    """"<waves>[b|c][a<bits>]" -> (waves, ABL bits, MODE)"""
     head, _, abl = spec.partition("a")
-    mode = "B" if head.endswith("b") else "A"
-    text, info = gen(int(head.rstrip("b")), int(abl or 0), mode)
+    mode = {"b": "B", "c": "C"}.get(head[-1], "A")
+    return int(head.rstrip("bc")), int(abl or 0), mode
+
+
+def step_loop_counts(text):
+    """static instruction counts of the time-step loop (from `L_step:` to its back-edge) of generated assembly text, by
+    class: valu, salu (scalar ALU, branches, s_load, s_sleep, exec moves), lds, vmem, waitcnt, nop; 'swap' and 'total'"""
+    lines = text.split("\n")
+    i0 = lines.index("L_step:")
+    i1 = next(i for i in range(i0, len(lines)) if lines[i].split(";")[0].split() == ["s_cbranch_scc1", "L_step"])
+    c = dict(valu=0, salu=0, lds=0, vmem=0, waitcnt=0, nop=0, swap=0)
+    for ln in lines[i0 + 1:i1 + 1]:
+        t = ln.split(";")[0].split()
+        if not t or t[0].endswith(":") or t[0].startswith("."):
+            continue
+        op = t[0]
+        if op.startswith("v_"):
+            c["valu"] += 1
+            c["swap"] += op.startswith("v_permlane32_swap")
+        elif op.startswith("ds_"):
+            c["lds"] += 1
+        elif op.startswith(("global_", "buffer_")):
+            c["vmem"] += 1
+        elif op == "s_waitcnt":
+            c["waitcnt"] += 1
+        elif op == "s_nop":
+            c["nop"] += 1
+        else:
+            assert op.startswith("s_"), op
+            c["salu"] += 1
+    c["total"] = sum(v for k, v in c.items() if k != "swap")
+    return c
+
+
+if __name__ == "__main__":
+    spec = sys.argv[1]                       # "<waves>[b|c][a<bits>]": "12", "8b", "8c", "8ca4096" (a...: diagnostic build, see gen())
+    text, info = gen(*parse_spec(spec))
     with open(sys.argv[2], "w") as f:
         f.write(text)
     print(info, file=sys.stderr)
