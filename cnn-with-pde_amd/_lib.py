@@ -70,6 +70,7 @@ _D64 = C.POINTER(PdeAdiDescF64)
 # name -> (restype, argtypes): must list every symbol include/pdecnn.h declares
 SIGNATURES = {
     "pde_adi_line_length_path": (C.c_int, [_i32]),
+    "pde_adi_forward_kernel": (C.c_int, [C.POINTER(PdeAdiDesc)]),
     "pde_adi_backward_kernel": (C.c_int, [C.POINTER(PdeAdiDesc), _i32]),
     "pde_adi_forward_workspace_bytes": (_sz, [_D]),
     "pde_adi_backward_workspace_bytes": (_sz, [_D, _i32]),

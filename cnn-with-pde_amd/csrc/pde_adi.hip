@@ -658,10 +658,10 @@ int timed_launch(F&& f, hipStream_t st, bool is_fwd, bool timed) {
 #define PDE_N_LIST PDE_CASE(8) PDE_CASE(12) PDE_CASE(16) PDE_CASE(20) PDE_CASE(24) PDE_CASE(28) PDE_CASE(32)
 
 int dispatch_fwd(const PdeAdiDesc* d, int split, const SweepArgs& sa, int grid, size_t lds, hipStream_t st,
-                 bool timed = true) {
+                 bool timed = true, int ho = 0) {
     return timed_launch([&]() -> int {
         switch (d->N) {
-#define PDE_CASE(NN) case NN: return adi_launch_fwd_##NN(d->io_dtype, split, &sa, grid, lds, st);
+#define PDE_CASE(NN) case NN: return adi_launch_fwd_##NN(d->io_dtype, split, ho, &sa, grid, lds, st);
             PDE_N_LIST
 #undef PDE_CASE
         }
@@ -684,6 +684,17 @@ int count_ckpt(const uint64_t m[2]) { return m ? __builtin_popcountll(m[0]) + __
 
 bool asm_fwd_eligible(const PdeAdiDesc* d) {
     return asm_fwd_enabled() && d->N == 32 && d->io_dtype == PDE_IO_F32 && split_of(d) == kSplitStrang && d->num_sweeps >= 6;
+}
+
+// The forward's hand-over schedule (adi_fwd_kernel<..., HO = true>: counters in LDS instead of a barrier per sweep, a
+// four-slot record ring) serves N = 32 fp32 Strang launches whose records do not all stay resident.  PDE_FWD_SCHED=0
+// (read once per process) keeps the barrier schedule: the same arithmetic in the same order, for comparisons.
+bool fwd_ho_enabled() {
+    static const bool on = [] { const char* e = getenv("PDE_FWD_SCHED"); return !(e && e[0] == '0'); }();
+    return on;
+}
+bool fwd_ho_eligible(const PdeAdiDesc* d) {
+    return fwd_ho_enabled() && d->N == 32 && d->io_dtype == PDE_IO_F32 && split_of(d) == kSplitStrang && d->num_sweeps > kRing;
 }
 
 // ---- launch helpers shared by the whole-schedule entry points and the per-step ones -----------------
@@ -709,6 +720,10 @@ int launch_fwd_sweeps(const PdeAdiDesc* d, const void* u, void* y, const float* 
         aa.acc_part = sa.pair_x ? 2 : 0;
         const int xcd = sa.xcd_map;
         return timed_launch([&]() -> int { return asm_fwd_launch(aa, xcd, st); }, st, true, true);
+    }
+    if (fwd_ho_eligible(d)) {
+        const size_t lds = (size_t)(kRingHo * kRecFwdPad + kWaves * kImage + kRingHo) * sizeof(float);
+        return dispatch_fwd(d, split_of(d), sa, sa.G * d->C, lds, st, true, 1);
     }
     const size_t lds = (size_t)(kRing * kRecFwdPad + kWaves * kImage) * sizeof(float);
     return dispatch_fwd(d, split_of(d), sa, sa.G * d->C, lds, st);
@@ -877,6 +892,12 @@ using namespace pde;
 extern "C" {
 
 int pde_adi_line_length_path(int32_t N) { return fused_n(N) ? 1 : (gen_n_ok(N) ? 2 : 0); }
+
+int pde_adi_forward_kernel(const PdeAdiDesc* d) {
+    if (check_desc(d, true) != PDE_OK) return PDE_E_BADARG;
+    if (!fused_n(d->N)) return 2;
+    return asm_fwd_eligible(d) ? 1 : (fwd_ho_eligible(d) ? 3 : 0);
+}
 
 int pde_adi_backward_kernel(const PdeAdiDesc* d, int32_t num_checkpoints) {
     if (check_desc(d, true) != PDE_OK) return PDE_E_BADARG;

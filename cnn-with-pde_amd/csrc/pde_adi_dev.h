@@ -554,12 +554,23 @@ __device__ __forceinline__ void store_planes(IO* base, int q, int wave, int lane
 // SPLIT fixes the order of the axes inside a time step at compile time (straight-line code per
 // step, no per-sweep axis branch); kSplitAny reads the axis of every sweep from the table.
 // (second bound: waves per SIMD.  4 = two workgroups per CU; the bf16 instantiation otherwise takes 138 VGPRs and runs alone on its CU)
-template <int N, int J, typename IO, int SPLIT>
+//
+// HO (hand-over schedule; N = 32 fp32 Strang launches of more than kRing sweeps): no barrier per sweep.  The ring has
+// kRingHo slots and every wave stages record n+2 while it runs the sweep of record n.  One counter per slot in LDS counts
+// the waves past the hand-over point of the record in that slot: after the solve (its last read of the record) and after
+// its own DMA pieces of record n+2 have landed.  So "every wave past record n-2" means both that record n is complete
+// and that the slot of record n-2 may be overwritten: one poll per staged record.  The waves drift apart instead of
+// meeting at every sweep; there is no phase skew, the drift does its job.
+constexpr int kRingHo = 4;
+template <int N, int J, typename IO, int SPLIT, bool HO = false>
 __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kernel(SweepArgs a) {
     constexpr int M = Geo<N>::M;
+    constexpr int RING = HO ? kRingHo : kRing;
+    static_assert(!HO || SPLIT == kSplitStrang, "the hand-over schedule is written for the Strang pattern");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* cbuf = smem;                                   // [kRing][kRecFwdPad]
-    float* tbuf = smem + kRing * kRecFwdPad;              // [kWaves][kImage]
+    float* cbuf = smem;                                   // [RING][kRecFwdPad]
+    float* tbuf = smem + RING * kRecFwdPad;              // [kWaves][kImage]
+    unsigned* passed = reinterpret_cast<unsigned*>(tbuf + kWaves * kImage);   // HO: [kRingHo] hand-over counters
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hf = lane >> 5, l = lane & 31;
     int c, g;
@@ -578,12 +589,13 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
     // its records in the ring for the whole launch: no staging per sweep, no barrier per sweep, no skew — the waves of
     // a workgroup run free of each other, so one wave's plane loads and stores overlap the others' sweeps (with a
     // barrier per sweep every workgroup of the launch loaded, swept and stored in step with all the others).
-    const bool resident = a.S <= kRing;
-    const int lag = resident ? 0 : wave_lag(wave);
+    const bool resident = !HO && a.S <= kRing;
+    const int lag = (resident || HO) ? 0 : wave_lag(wave);
     young_half_priority(wave);
 
     // rows >= N of the wave images are never written: zero them once so idle lanes read zeros
     for (int e = tid; e < kWaves * kImage; e += kThreads) tbuf[e] = 0.f;
+    if (HO && tid < kRingHo) passed[tid] = 0u;
     // Sweeps are numbered along the whole job of this workgroup (item i = sweep i % S of chunk i / S).
     // In barrier interval t the lower waves run item t from ring slot t % 3, the upper waves item
     // t-1 from slot (t-1) % 3, and every wave brings its pieces of item t+1 into slot (t+1) % 3 by
@@ -613,9 +625,38 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
         for (int s = 0; s < a.S; ++s) dma_rec(s, s);
     } else {
         dma_rec(0, 0);
+        if (HO) dma_rec(1, 1);                            // (HO is only launched for a.S > kRing)
     }
     dma_wait_all();
     __syncthreads();
+    // HO: records are numbered in the order they are used (record n sits in ring slot n % kRingHo).  The first x sweep of
+    // a Strang step other than the first of a chunk keeps the rows of the sweep before it (pair_x), so its record is
+    // not staged at all: two records per step instead of three, and the ring spans two steps.
+    int n = 0;                                            // my next record
+    const int rpc = a.pair_x ? 1 + 2 * (a.S / 3) : a.S;   // records per chunk
+    const int ntot = ((nchunk - g + a.G - 1) / a.G) * rpc;
+    int dsw = 2;                                          // sweep of record n + 2, the next one to stage
+    // wait until every wave has passed the hand-over point of record n-2 (see the kernel's head comment)
+    auto ho_wait = [&]() __attribute__((always_inline)) {
+        if (n < 2) return;
+        const unsigned want = (unsigned)kWaves * (unsigned)(((n - 2) >> 2) + 1);
+        const unsigned* ctr = passed + ((n - 2) & (kRingHo - 1));
+        while ((unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < want)
+            __builtin_amdgcn_s_sleep(1);
+        asm volatile("" ::: "memory");                    // no LDS access of this record moves above the poll
+    };
+    auto ho_stage = [&]() __attribute__((always_inline)) {
+        if (n + 2 < ntot) dma_rec((n + 2) & (kRingHo - 1), dsw);
+        ++dsw;
+        if (dsw == a.S) dsw = 0;
+        else if (a.pair_x && dsw % 3 == 0) ++dsw;         // a twin: nothing to stage
+    };
+    // my hand-over point of record n: my reads of it are done, my pieces of record n+2 have landed
+    auto ho_pass = [&]() __attribute__((always_inline)) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(passed + (n & (kRingHo - 1)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        ++n;
+    };
     if (lag) {                                            // interval 0 of the upper waves: staging only
         dma_rec(1, a.S > 1 ? 1 : 0);
         dma_wait_all();
@@ -638,6 +679,21 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
         }
         auto sweep = [&](auto AXC, int s, auto TWINC) {
             constexpr int AX = decltype(AXC)::value;
+            if constexpr (HO) {                           // (never with checkpoints: the pre-pass runs kSplitAny)
+                const bool staged = !(decltype(TWINC)::value && a.pair_x != 0 && s != 0);
+                if (staged) {
+                    ho_wait();
+                    ho_stage();
+                }
+                const float* rec = cbuf + (n & (kRingHo - 1)) * kRecFwdPad;
+                // the y sweep's rows are requested before its re-layout, not after it
+                if (staged) load_fwd_rows<M>(rec, l, hf, ce, cinv, cjn);
+                if (AX == PDE_AXIS_Y) relayout_all<N, J>(v, T, l, hf);
+                solve_fwd_rows<M, J>(v, ce, cinv, cjn, hf);
+                if (staged) ho_pass();
+                if (AX == PDE_AXIS_Y) relayout_all<N, J>(v, T, l, hf);
+                return;
+            }
             int sp = s + lag + 1;                         // sweep of the item staged in this interval
             if (sp >= a.S) sp -= a.S;
             if (sp >= a.S) sp -= a.S;
@@ -677,7 +733,7 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
         }
         if (y != nullptr && !((PDE_ABL & 4) && q + a.G < nchunk)) store_planes<N, J, IO>(y, q, wave, lane, l, hf, a.B, a.C, c, T, v);
     }
-    if (!lag) __syncthreads();                            // the interval in which the upper waves finish
+    if (!HO && !lag) __syncthreads();                     // the interval in which the upper waves finish
 }
 
 // ---- backward -------------------------------------------------------------------------

@@ -29,8 +29,12 @@ int launch(K kernel, const SweepArgs& sa, int grid, size_t lds, hipStream_t st) 
 }
 
 template <typename IO>
-int fwd_io(int split, const SweepArgs& sa, int grid, size_t lds, hipStream_t st) {
+int fwd_io(int split, int ho, const SweepArgs& sa, int grid, size_t lds, hipStream_t st) {
     constexpr int N = PDE_INST_N;
+    if constexpr (N == 32 && std::is_same<IO, float>::value) {
+        if (ho && split == kSplitStrang) return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitStrang, true>, sa, grid, lds, st);
+    }
+    if (ho) return PDE_E_LAUNCH;
     switch (split) {
         case kSplitStrang: return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitStrang>, sa, grid, lds, st);
         case kSplitLie: return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitLie>, sa, grid, lds, st);
@@ -58,9 +62,9 @@ int bwd_io(int split, const SweepArgs& sa, int grid, hipStream_t st) {
 
 }  // namespace
 
-int PDE_CAT(adi_launch_fwd_, PDE_INST_N)(int io, int split, const void* args, int grid, size_t lds, hipStream_t st) {
+int PDE_CAT(adi_launch_fwd_, PDE_INST_N)(int io, int split, int ho, const void* args, int grid, size_t lds, hipStream_t st) {
     const SweepArgs& sa = *static_cast<const SweepArgs*>(args);
-    return io == PDE_IO_F32 ? fwd_io<float>(split, sa, grid, lds, st) : fwd_io<bf16_t>(split, sa, grid, lds, st);
+    return io == PDE_IO_F32 ? fwd_io<float>(split, ho, sa, grid, lds, st) : fwd_io<bf16_t>(split, ho, sa, grid, lds, st);
 }
 
 int PDE_CAT(adi_launch_bwd_, PDE_INST_N)(int io, int split, const void* args, int grid, hipStream_t st) {

@@ -76,6 +76,12 @@ typedef struct PdeAdiDesc {
  * 0 = unsupported. */
 int pde_adi_line_length_path(int32_t N);
 
+/* Which kernel pde_adi_forward runs for this schedule: 0 = the HIP kernel with a barrier per sweep (adi_fwd_kernel), 1 = the
+ * hand-scheduled assembly kernel (opt-in, PDE_ASM_FWD=1), 2 = the any-size kernels, 3 = the HIP kernel's hand-over schedule
+ * (N = 32, fp32 tensors, Strang steps, more sweeps than stay resident: counters in LDS instead of the barrier per sweep).
+ * Same arithmetic in the same order for 0, 1 and 3; PDE_FWD_SCHED=0 in the environment turns 3 into 0. */
+int pde_adi_forward_kernel(const PdeAdiDesc* d);
+
 /* Which kernel pde_adi_backward runs for this schedule's unmasked channels: 0 = the HIP kernel (adi_bwd_kernel), 1 = the
  * hand-scheduled gfx950 assembly kernel (csrc/gen_adi_bwd_asm.py: N = 32, fp32 tensors, Strang steps — mnist_test.py:55-63,
  * cifar10.py:84-110 — two or more of them, no checkpoints), 2 = the any-size kernels.  Same arithmetic either way: the
