@@ -54,7 +54,9 @@ def _compare(layer, spec_fn, u, gy, tol=TOL, dtype=torch.float32):
     (13, 3, 32, 4, 0.01, 0.5),       # ragged batch: not a multiple of the planes per workgroup iteration
     (1, 1, 32, 2, 0.02, 0.0),        # single sample, single channel
     (40, 5, 28, 3, 0.02, 1.0),       # odd channel count, N = 28
-    (70, 2, 16, 5, 0.05, 0.0),       # several chunks per workgroup
+    # C <= 4 runs on the whole-layer kernel (pde_adi_small.h): one workgroup per sample, at most 1024 of them
+    (70, 2, 16, 5, 0.05, 0.0),       # every workgroup takes one sample
+    (1100, 2, 16, 5, 0.05, 0.0),     # 76 workgroups walk a second sample (and prefetch its first record)
 ])
 def test_cifar10_semantics_vs_oracle(B, C, N, steps, dt, slope):
     import cnn_with_pde_amd as P
