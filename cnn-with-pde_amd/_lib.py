@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("PDECNN_LIB") or os.path.join(HERE, "lib", "libpdecnn_
 
 PDE_MAX_SWEEPS = 96
 PDE_MAX_N = 32
-PDE_IO_F32, PDE_IO_BF16, PDE_IO_F64 = 0, 1, 2
+PDE_IO_F32, PDE_IO_BF16, PDE_IO_F64, PDE_IO_F16 = 0, 1, 2, 3
 PDE_AXIS_X, PDE_AXIS_Y = 0, 1
 
 ERRORS = {
@@ -122,6 +122,9 @@ SIGNATURES = {
     "pde_jacobi_forward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _vp]),
     "pde_jacobi_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "pde_jacobi_backward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "pde_jacobi_io_forward": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _vp, _vp]),
+    "pde_jacobi_io_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "pde_jacobi_io_backward": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _fp, _fp, _vp, _fp, _fp, _vp, _sz, _vp]),
     "pde_sym_layer_supported": (C.c_int, [_i32, _i32]),
     "pde_sym_layer_workspace_bytes": (_sz, [_i32, _i32]),
     "pde_sym_layer_forward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _f32, _f32, _fp, _f32,

@@ -184,6 +184,14 @@ Tensor as_chw(const Tensor& p, int64_t C, int64_t N) {
     return q.contiguous();
 }
 
+// tensor types the kernels take as they are (functional._IO_TYPES; the caller widens an fp16 input off the float16 route)
+bool io_type(const Tensor& u) {
+    return u.scalar_type() == at::kFloat || u.scalar_type() == at::kBFloat16 || u.scalar_type() == at::kHalf;
+}
+int32_t io_of(const Tensor& u) {
+    return u.scalar_type() == at::kBFloat16 ? PDE_IO_BF16 : (u.scalar_type() == at::kHalf ? PDE_IO_F16 : PDE_IO_F32);
+}
+
 Tensor bytes(size_t n, const Tensor& like) {
     return at::empty({(int64_t)std::max<size_t>(n, 256)}, like.options().dtype(at::kByte));
 }
@@ -202,9 +210,9 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
         std::memcpy(&d, reinterpret_cast<const void*>(desc_addr), sizeof(d));
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
-        if (u.scalar_type() != at::kFloat && u.scalar_type() != at::kBFloat16) u = u.to(at::kFloat);
+        if (!io_type(u)) u = u.to(at::kFloat);
         u = u.contiguous();
-        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == (u.scalar_type() == at::kBFloat16 ? PDE_IO_BF16 : PDE_IO_F32),
+        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                     "descriptor does not match the tensor");
         Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
         const bool want_kmax = need_grad && (ckpt_mode == 1 || ckpt_mode == 2);
@@ -351,9 +359,9 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         std::memcpy(&d, reinterpret_cast<const void*>(desc_addr), sizeof(d));
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
-        if (u.scalar_type() != at::kFloat && u.scalar_type() != at::kBFloat16) u = u.to(at::kFloat);
+        if (!io_type(u)) u = u.to(at::kFloat);
         u = u.contiguous();
-        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == (u.scalar_type() == at::kBFloat16 ? PDE_IO_BF16 : PDE_IO_F32),
+        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                     "descriptor does not match the tensor");
         const int64_t K = d.num_sweeps / sps;
         Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
@@ -468,9 +476,9 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
         std::memcpy(&d, reinterpret_cast<const void*>(desc_addr), sizeof(d));
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
-        if (u.scalar_type() != at::kFloat && u.scalar_type() != at::kBFloat16) u = u.to(at::kFloat);
+        if (!io_type(u)) u = u.to(at::kFloat);
         u = u.contiguous();
-        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == (u.scalar_type() == at::kBFloat16 ? PDE_IO_BF16 : PDE_IO_F32),
+        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                     "descriptor does not match the tensor");
         const int64_t K = d.num_sweeps / sps;
         Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
@@ -571,7 +579,7 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         for (const auto& t : flat) PDE_REQUIRE(t.is_cuda(), "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
-        if (u.scalar_type() != at::kFloat && u.scalar_type() != at::kBFloat16) u = u.to(at::kFloat);
+        if (!io_type(u)) u = u.to(at::kFloat);
         u = u.contiguous();
         const bool want_kmax = need_grad && ckpt_mode == 1;
         ctx->set_materialize_grads(false);
@@ -587,7 +595,7 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         for (int i = 0; i < nl; ++i) {
             PdeAdiDesc& d = descs[i];
             std::memcpy(&d, reinterpret_cast<const void*>(desc_addrs[i]), sizeof(d));
-            PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == (u.scalar_type() == at::kBFloat16 ? PDE_IO_BF16 : PDE_IO_F32),
+            PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                         "descriptor does not match the tensor");
             const int64_t K = d.num_sweeps / sps;
             Tensor p[4];

@@ -509,7 +509,7 @@ int check_desc(const PdeAdiDesc* d, bool allow_generic = false) {
     if (d->B <= 0 || d->C <= 0 || d->num_sweeps <= 0) return PDE_E_BADARG;
     if (!fused_n(d->N) && !(allow_generic && gen_n_ok(d->N))) return PDE_E_UNSUPPORTED_N;
     if (d->num_sweeps > PDE_MAX_SWEEPS) return PDE_E_TOO_MANY_SWEEPS;
-    if (d->io_dtype != PDE_IO_F32 && d->io_dtype != PDE_IO_BF16) return PDE_E_BADARG;
+    if (d->io_dtype != PDE_IO_F32 && d->io_dtype != PDE_IO_BF16 && d->io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     for (int s = 0; s < d->num_sweeps; ++s)
         if (d->sweep[s].axis != PDE_AXIS_X && d->sweep[s].axis != PDE_AXIS_Y) return PDE_E_BADARG;
     return PDE_OK;
@@ -1103,7 +1103,7 @@ int pde_adi_param_grads(const PdeAdiDesc* d, int32_t sweeps_per_step, const floa
 // (one call from the binding instead of two per step: at the reference's own sizes, C = 3 and batch 128, the
 // layer is bound by the host's launch rate, and every Python -> ctypes transition costs as much as a launch)
 static size_t state_bytes(const PdeAdiDesc* d) {
-    return (size_t)d->B * d->C * d->N * d->N * (d->io_dtype == PDE_IO_BF16 ? 2 : 4);
+    return (size_t)d->B * d->C * d->N * d->N * (d->io_dtype == PDE_IO_F32 ? 4 : 2);
 }
 
 static int wide_forward(const PdeAdiDesc* d, int sps, int mode, const void* u, void* states, void* y, const float* M,
@@ -1279,6 +1279,7 @@ static int combine_slabs(const PdeAdiDesc* d, const SmallArgs& sa, void* out, hi
     for (int i = 0; i < sa.L; ++i) ca.slab[i] = sa.layer[i].slab;
     ca.out = out; ca.L = sa.L;
     ca.n4 = (size_t)d->B * d->C * d->N * d->N / 4;
+    if (d->io_dtype == PDE_IO_F16) return small_combine_io<half_t>(ca, st);
     return d->io_dtype == PDE_IO_F32 ? small_combine_io<float>(ca, st) : small_combine_io<bf16_t>(ca, st);
 }
 

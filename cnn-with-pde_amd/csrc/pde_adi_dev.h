@@ -297,6 +297,19 @@ template <> struct IoTraits<bf16_t> {
         __builtin_nontemporal_store(q, reinterpret_cast<u4*>(p));
     }
 };
+struct half_t { unsigned short v; };
+template <> struct IoTraits<half_t> {
+    __device__ static __forceinline__ float4 load4(const half_t* p) {
+        typedef unsigned short u4 __attribute__((ext_vector_type(4)));
+        const u4 q = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p));
+        return make_float4(f16_to_f32(q.x), f16_to_f32(q.y), f16_to_f32(q.z), f16_to_f32(q.w));
+    }
+    __device__ static __forceinline__ void store4(half_t* p, float4 v) {
+        typedef unsigned short u4 __attribute__((ext_vector_type(4)));
+        const u4 q = {f32_to_f16_hw(v.x), f32_to_f16_hw(v.y), f32_to_f16_hw(v.z), f32_to_f16_hw(v.w)};
+        __builtin_nontemporal_store(q, reinterpret_cast<u4*>(p));
+    }
+};
 
 template <int N>
 struct Geo {

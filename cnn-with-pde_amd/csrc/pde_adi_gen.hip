@@ -117,6 +117,11 @@ template <> struct GenIo<gen_bf16> {
     }
     __device__ static void st(void* p, size_t i, float v) { static_cast<unsigned short*>(p)[i] = f32_to_bf16_hw(v); }
 };
+struct gen_f16 { unsigned short v; };
+template <> struct GenIo<gen_f16> {
+    __device__ static float ld(const void* p, size_t i) { return f16_to_f32(static_cast<const unsigned short*>(p)[i]); }
+    __device__ static void st(void* p, size_t i, float v) { static_cast<unsigned short*>(p)[i] = f32_to_f16_hw(v); }
+};
 
 template <typename T>
 struct GenSweepArgs {
@@ -430,7 +435,7 @@ int launch_gen_fwd(const D* d, const void* u, void* y, const T* fac, const GenSw
     sa.ck[0] = ck ? ck[0] : 0ull; sa.ck[1] = ck ? ck[1] : 0ull;
     sa.B = d->B; sa.C = d->C; sa.N = d->N; sa.S = S; sa.eps = d->eps;
     const size_t lds = gen_img<T>(d->N);
-    static unsigned long long done_f = 0, done_b = 0;
+    static unsigned long long done_f = 0, done_b = 0, done_h = 0;
     int rc;
     if constexpr (std::is_same<T, double>::value) {
         if ((rc = gen_lds(gen_fwd_kernel<double, double>, done_f)) != PDE_OK) return rc;
@@ -438,6 +443,9 @@ int launch_gen_fwd(const D* d, const void* u, void* y, const T* fac, const GenSw
     } else if (d->io_dtype == PDE_IO_F32) {
         if ((rc = gen_lds(gen_fwd_kernel<float, float>, done_f)) != PDE_OK) return rc;
         hipLaunchKernelGGL((gen_fwd_kernel<float, float>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+    } else if (d->io_dtype == PDE_IO_F16) {
+        if ((rc = gen_lds(gen_fwd_kernel<float, gen_f16>, done_h)) != PDE_OK) return rc;
+        hipLaunchKernelGGL((gen_fwd_kernel<float, gen_f16>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
     } else {
         if ((rc = gen_lds(gen_fwd_kernel<float, gen_bf16>, done_b)) != PDE_OK) return rc;
         hipLaunchKernelGGL((gen_fwd_kernel<float, gen_bf16>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
@@ -506,7 +514,7 @@ int backward_impl(const D* d, const void* gy, const void* y, const void* u, cons
     // the partial sums beside the planes while four workgroups still fit on a CU (fp32: N <= 40, fp64: N <= 28)
     const bool alds = !xg && 4 * 6 * img <= (size_t)kGenLdsMax;
     const size_t lds = xg ? img : (alds ? 6 : 2) * img;
-    static unsigned long long done[7] = {0, 0, 0, 0, 0, 0, 0};
+    static unsigned long long done[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     const dim3 grid(G * d->C), block(gen_threads(d->N));
 #define PDE_GEN_BWD(TY, IO, AL, XG, SLOT)                                                                \
     do {                                                                                                 \
@@ -519,6 +527,8 @@ int backward_impl(const D* d, const void* gy, const void* y, const void* u, cons
         else PDE_GEN_BWD(double, double, false, false, 6);
     } else if (d->io_dtype == PDE_IO_F32) {
         if (alds) PDE_GEN_BWD(float, float, true, false, 0); else PDE_GEN_BWD(float, float, false, false, 1);
+    } else if (d->io_dtype == PDE_IO_F16) {
+        if (alds) PDE_GEN_BWD(float, gen_f16, true, false, 7); else PDE_GEN_BWD(float, gen_f16, false, false, 8);
     } else {
         if (alds) PDE_GEN_BWD(float, gen_bf16, true, false, 2); else PDE_GEN_BWD(float, gen_bf16, false, false, 3);
     }

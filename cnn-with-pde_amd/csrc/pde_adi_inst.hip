@@ -64,22 +64,26 @@ int bwd_io(int split, const SweepArgs& sa, int grid, hipStream_t st) {
 
 int PDE_CAT(adi_launch_fwd_, PDE_INST_N)(int io, int split, int ho, const void* args, int grid, size_t lds, hipStream_t st) {
     const SweepArgs& sa = *static_cast<const SweepArgs*>(args);
+    if (io == PDE_IO_F16) return fwd_io<half_t>(split, ho, sa, grid, lds, st);
     return io == PDE_IO_F32 ? fwd_io<float>(split, ho, sa, grid, lds, st) : fwd_io<bf16_t>(split, ho, sa, grid, lds, st);
 }
 
 int PDE_CAT(adi_launch_bwd_, PDE_INST_N)(int io, int split, const void* args, int grid, hipStream_t st) {
     const SweepArgs& sa = *static_cast<const SweepArgs*>(args);
+    if (io == PDE_IO_F16) return bwd_io<half_t>(split, sa, grid, st);
     return io == PDE_IO_F32 ? bwd_io<float>(split, sa, grid, st) : bwd_io<bf16_t>(split, sa, grid, st);
 }
 
 #ifdef PDE_INST_SMALL
 int PDE_CAT(adi_launch_small_fwd_, PDE_INST_N)(int io, int split, const void* args, int grid, size_t lds, hipStream_t st) {
     const SmallArgs& sa = *static_cast<const SmallArgs*>(args);
+    if (io == PDE_IO_F16) return small_fwd_io<PDE_INST_N, half_t>(split, sa, grid, lds, st);
     return io == PDE_IO_F32 ? small_fwd_io<PDE_INST_N, float>(split, sa, grid, lds, st)
                             : small_fwd_io<PDE_INST_N, bf16_t>(split, sa, grid, lds, st);
 }
 int PDE_CAT(adi_launch_small_bwd_, PDE_INST_N)(int io, int split, const void* args, int grid, size_t lds, hipStream_t st) {
     const SmallArgs& sa = *static_cast<const SmallArgs*>(args);
+    if (io == PDE_IO_F16) return small_bwd_io<PDE_INST_N, half_t>(split, sa, grid, lds, st);
     return io == PDE_IO_F32 ? small_bwd_io<PDE_INST_N, float>(split, sa, grid, lds, st)
                             : small_bwd_io<PDE_INST_N, bf16_t>(split, sa, grid, lds, st);
 }

@@ -103,6 +103,7 @@ __device__ __forceinline__ void image_get(const float* img, int l, int hf, float
 
 template <typename IO> __device__ __forceinline__ float round_io(float v) { return v; }
 template <> __device__ __forceinline__ float round_io<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
+template <> __device__ __forceinline__ float round_io<half_t>(float v) { return f16_to_f32(f32_to_f16_hw(v)); }
 
 // ---- forward ---------------------------------------------------------------------------------------------
 template <int N, typename IO, int SPLIT>

@@ -44,6 +44,26 @@ template <> struct Vec<bf16v> {
     __device__ static __forceinline__ float ld1(const bf16v* p) { return bf2f(p->v); }
     __device__ static __forceinline__ void st1(bf16v* p, float v) { p->v = f2bf(v); }
 };
+struct f16v { unsigned short v; };
+template <> struct Vec<f16v> {
+    __device__ static __forceinline__ void ld(const f16v* p, float (&x)[8]) {
+        const uint4 q = *reinterpret_cast<const uint4*>(p);
+        const unsigned int w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            x[2 * i] = f16_to_f32((unsigned short)(w[i] & 0xffffu));
+            x[2 * i + 1] = f16_to_f32((unsigned short)(w[i] >> 16));
+        }
+    }
+    __device__ static __forceinline__ void st(f16v* p, const float (&x)[8]) {
+        unsigned int w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = f32_to_f16_hw(x[2 * i]) | ((unsigned int)f32_to_f16_hw(x[2 * i + 1]) << 16);
+        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    __device__ static __forceinline__ float ld1(const f16v* p) { return f16_to_f32(p->v); }
+    __device__ static __forceinline__ void st1(f16v* p, float v) { p->v = f32_to_f16_hw(v); }
+};
 
 __device__ __forceinline__ float sigmoidf(float w) { return 1.0f / (1.0f + expf(-w)); }
 
@@ -129,6 +149,8 @@ int pde_skip_blend_forward(int64_t n, int32_t io_dtype, const void* u0, const vo
         hipLaunchKernelGGL(blend_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)u0, (const float*)u, skip_weight, (float*)out, (size_t)n);
     else if (io_dtype == PDE_IO_BF16)
         hipLaunchKernelGGL(blend_fwd_kernel<bf16v>, dim3(grid), dim3(256), 0, st, (const bf16v*)u0, (const bf16v*)u, skip_weight, (bf16v*)out, (size_t)n);
+    else if (io_dtype == PDE_IO_F16)
+        hipLaunchKernelGGL(blend_fwd_kernel<f16v>, dim3(grid), dim3(256), 0, st, (const f16v*)u0, (const f16v*)u, skip_weight, (f16v*)out, (size_t)n);
     else
         return PDE_E_BADARG;
     return check_launch();
@@ -148,6 +170,8 @@ int pde_skip_blend_backward(int64_t n, int32_t io_dtype, const void* g, const vo
         hipLaunchKernelGGL(blend_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)g, (const float*)u0, (const float*)u, skip_weight, (float*)g_u0, (float*)g_u, part, (size_t)n);
     else if (io_dtype == PDE_IO_BF16)
         hipLaunchKernelGGL(blend_bwd_kernel<bf16v>, dim3(grid), dim3(256), 0, st, (const bf16v*)g, (const bf16v*)u0, (const bf16v*)u, skip_weight, (bf16v*)g_u0, (bf16v*)g_u, part, (size_t)n);
+    else if (io_dtype == PDE_IO_F16)
+        hipLaunchKernelGGL(blend_bwd_kernel<f16v>, dim3(grid), dim3(256), 0, st, (const f16v*)g, (const f16v*)u0, (const f16v*)u, skip_weight, (f16v*)g_u0, (f16v*)g_u, part, (size_t)n);
     else
         return PDE_E_BADARG;
     hipLaunchKernelGGL(blend_reduce_kernel, dim3(1), dim3(256), 0, st, part, grid, skip_weight, g_skip_weight);

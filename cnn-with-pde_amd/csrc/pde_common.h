@@ -62,6 +62,10 @@ int mix_bf16_splits(int B, int C, int HW);
 int mix_bf16_apply(int B, int C, int HW, const void* u, const float* M, void* out, int trans, hipStream_t st);
 int mix_bf16_backward(int B, int C, int HW, const void* u, const void* g, const float* M, void* gu, float* part, int nsplit,
                       int accp, hipStream_t st);
+// fp16 tensors through the fp16 MFMA: the same kernels, the same shapes (mix_bf16_ok) and the same partial-sum count
+int mix_f16_apply(int B, int C, int HW, const void* u, const float* M, void* out, int trans, hipStream_t st);
+int mix_f16_backward(int B, int C, int HW, const void* u, const void* g, const float* M, void* gu, float* part, int nsplit,
+                     int accp, hipStream_t st);
 
 // fp32 tensors through the bf16 MFMA with every operand as three bf16 pieces (pde_mix_bf16.hip); C = 64, HW a multiple of 64
 bool mix_split_ok(int C, int HW);
@@ -72,6 +76,10 @@ int mix_split_backward(int B, int C, int HW, const void* u, const void* g, const
 // fp32 -> bf16, round to nearest even: one v_cvt_pk_bf16_f32 per pair on gfx950 (the bit-twiddling form costs
 // five VALU instructions per element, and a VALU instruction is what the sweep kernels run out of)
 __device__ __forceinline__ unsigned short f32_to_bf16_hw(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
+// fp32 <-> fp16, round to nearest even, overflow to +-inf (v_cvt_f16_f32 / v_cvt_pk_f16_f32 under the default rounding
+// mode; never v_cvt_pkrtz_f16_f32, which rounds toward zero and never gives inf)
+__device__ __forceinline__ unsigned short f32_to_f16_hw(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+__device__ __forceinline__ float f16_to_f32(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
 
 struct Timing {
     bool on = false;

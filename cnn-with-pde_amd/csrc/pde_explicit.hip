@@ -59,6 +59,37 @@ template <> struct V4<bf16e> {
         return make_float4(bf2f(f2bf(v.x)), bf2f(f2bf(v.y)), bf2f(f2bf(v.z)), bf2f(f2bf(v.w)));
     }
 };
+struct f16e { unsigned short v; };
+template <> struct V4<f16e> {
+    __device__ static __forceinline__ float4 ld(const f16e* p) {
+        const ushort4 q = *reinterpret_cast<const ushort4*>(p);
+        return make_float4(f16_to_f32(q.x), f16_to_f32(q.y), f16_to_f32(q.z), f16_to_f32(q.w));
+    }
+    __device__ static __forceinline__ void st(f16e* p, float4 v) {
+        ushort4 q; q.x = f32_to_f16_hw(v.x); q.y = f32_to_f16_hw(v.y); q.z = f32_to_f16_hw(v.z); q.w = f32_to_f16_hw(v.w);
+        *reinterpret_cast<ushort4*>(p) = q;
+    }
+    __device__ static __forceinline__ float ld1(const f16e* p) { return f16_to_f32(p->v); }
+    __device__ static __forceinline__ float4 ld_once(const f16e* p) { return ld(p); }
+    __device__ static __forceinline__ float4 round(float4 v) {
+        return make_float4(f16_to_f32(f32_to_f16_hw(v.x)), f16_to_f32(f32_to_f16_hw(v.y)), f16_to_f32(f32_to_f16_hw(v.z)),
+                           f16_to_f32(f32_to_f16_hw(v.w)));
+    }
+};
+// one element of a tensor of the layer's own type (the Jacobi kernels: the time loop itself is fp32 in LDS)
+template <typename IO> struct S1;
+template <> struct S1<float> {
+    __device__ static __forceinline__ float ld(const float* p) { return *p; }
+    __device__ static __forceinline__ void st(float* p, float v) { *p = v; }
+};
+template <> struct S1<bf16e> {
+    __device__ static __forceinline__ float ld(const bf16e* p) { return bf2f(p->v); }
+    __device__ static __forceinline__ void st(bf16e* p, float v) { p->v = f2bf(v); }
+};
+template <> struct S1<f16e> {
+    __device__ static __forceinline__ float ld(const f16e* p) { return f16_to_f32(p->v); }
+    __device__ static __forceinline__ void st(f16e* p, float v) { p->v = f32_to_f16_hw(v); }
+};
 
 // 5-point Laplacian with zero ghost cells of 4 consecutive columns (h, w0..w0+3) of one plane
 template <typename IO>
@@ -346,8 +377,9 @@ __device__ __forceinline__ void jacobi_step(const float* P, float* Q, const floa
     }
 }
 
-__global__ __launch_bounds__(256) void jacobi_fwd_kernel(const float* __restrict__ u, const float* __restrict__ a_row,
-                                                         const float* __restrict__ b_col, float* __restrict__ out,
+template <typename IO>
+__global__ __launch_bounds__(256) void jacobi_fwd_kernel(const IO* __restrict__ u, const float* __restrict__ a_row,
+                                                         const float* __restrict__ b_col, IO* __restrict__ out,
                                                          int H, int W, int nt) {
     extern __shared__ float sm[];
     const int Wp = W + 2, PN = (H + 2) * Wp;
@@ -355,12 +387,12 @@ __global__ __launch_bounds__(256) void jacobi_fwd_kernel(const float* __restrict
     float* Q = sm + PN;
     float* a = sm + 2 * PN;
     float* b = a + H;
-    const float* ub = u + (size_t)blockIdx.x * H * W;
+    const IO* ub = u + (size_t)blockIdx.x * H * W;
     for (int e = threadIdx.x; e < H; e += blockDim.x) a[e] = a_row[e];
     for (int e = threadIdx.x; e < W; e += blockDim.x) b[e] = b_col[e];
     for (int e = threadIdx.x; e < PN; e += blockDim.x) {
         const int i = e / Wp, j = e % Wp;
-        P[e] = ub[reflect_src(i, H) * W + reflect_src(j, W)];          // F.pad(..., mode='reflect')
+        P[e] = S1<IO>::ld(ub + reflect_src(i, H) * W + reflect_src(j, W));          // F.pad(..., mode='reflect')
     }
     __syncthreads();
     for (int n = 0; n < nt; ++n) {
@@ -368,14 +400,15 @@ __global__ __launch_bounds__(256) void jacobi_fwd_kernel(const float* __restrict
         __syncthreads();
         float* t = P; P = Q; Q = t;
     }
-    float* ob = out + (size_t)blockIdx.x * H * W;
-    for (int e = threadIdx.x; e < H * W; e += blockDim.x) ob[e] = P[(e / W + 1) * Wp + (e % W) + 1];
+    IO* ob = out + (size_t)blockIdx.x * H * W;
+    for (int e = threadIdx.x; e < H * W; e += blockDim.x) S1<IO>::st(ob + e, P[(e / W + 1) * Wp + (e % W) + 1]);
 }
 
 // workspace per sample: nt states of PN floats, then H+W partial sums
-__global__ __launch_bounds__(256) void jacobi_bwd_kernel(const float* __restrict__ u, const float* __restrict__ gout,
+template <typename IO>
+__global__ __launch_bounds__(256) void jacobi_bwd_kernel(const IO* __restrict__ u, const IO* __restrict__ gout,
                                                          const float* __restrict__ a_row,
-                                                         const float* __restrict__ b_col, float* __restrict__ gu,
+                                                         const float* __restrict__ b_col, IO* __restrict__ gu,
                                                          float* __restrict__ states, float* __restrict__ part,
                                                          int H, int W, int nt) {
     extern __shared__ float sm[];
@@ -387,13 +420,13 @@ __global__ __launch_bounds__(256) void jacobi_bwd_kernel(const float* __restrict
     float* ga = b + W;
     float* gb = ga + H;
     const int s = blockIdx.x;
-    const float* ub = u + (size_t)s * H * W;
+    const IO* ub = u + (size_t)s * H * W;
     float* st = states + (size_t)s * nt * PN;
     for (int e = threadIdx.x; e < H; e += blockDim.x) { a[e] = a_row[e]; ga[e] = 0.f; }
     for (int e = threadIdx.x; e < W; e += blockDim.x) { b[e] = b_col[e]; gb[e] = 0.f; }
     for (int e = threadIdx.x; e < PN; e += blockDim.x) {
         const int i = e / Wp, j = e % Wp;
-        P[e] = ub[reflect_src(i, H) * W + reflect_src(j, W)];
+        P[e] = S1<IO>::ld(ub + reflect_src(i, H) * W + reflect_src(j, W));
     }
     __syncthreads();
     // forward recompute: park the state BEFORE each step
@@ -406,10 +439,10 @@ __global__ __launch_bounds__(256) void jacobi_bwd_kernel(const float* __restrict
     // adjoint: G = dL/dP_nt (zero ring, gout inside)
     float* G = P;
     float* Gn = Q;
-    const float* gob = gout + (size_t)s * H * W;
+    const IO* gob = gout + (size_t)s * H * W;
     for (int e = threadIdx.x; e < PN; e += blockDim.x) {
         const int i = e / Wp, j = e % Wp;
-        G[e] = (i >= 1 && i <= H && j >= 1 && j <= W) ? gob[(i - 1) * W + (j - 1)] : 0.f;
+        G[e] = (i >= 1 && i <= H && j >= 1 && j <= W) ? S1<IO>::ld(gob + (i - 1) * W + (j - 1)) : 0.f;
     }
     __threadfence_block();
     __syncthreads();
@@ -453,7 +486,7 @@ __global__ __launch_bounds__(256) void jacobi_bwd_kernel(const float* __restrict
         float* t = G; G = Gn; Gn = t;
     }
     // adjoint of the reflect padding: fold the ring back onto rows/cols 1 and H-2 / W-2
-    float* gub = gu + (size_t)s * H * W;
+    IO* gub = gu + (size_t)s * H * W;
     for (int e = threadIdx.x; e < H * W; e += blockDim.x) {
         const int i = e / W, j = e % W;
         float v = 0.f;
@@ -473,7 +506,7 @@ __global__ __launch_bounds__(256) void jacobi_bwd_kernel(const float* __restrict
             }
             // rows 1 and H-2 coincide when H == 3; not supported (H,W >= 4 checked on the host)
         }
-        gub[e] = v;
+        S1<IO>::st(gub + e, v);
     }
     float* pp = part + (size_t)s * (H + W);
     for (int e = threadIdx.x; e < H; e += blockDim.x) pp[e] = ga[e];
@@ -491,6 +524,41 @@ __global__ void jacobi_pgrad_kernel(const float* __restrict__ part, float* __res
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
+// One step of the generic-size path: the tensors of the call are of type T (float, bf16e, f16e) — the layer's input is
+// read in the first step, its output written in the last; what passes between the steps is fp32.
+struct ExArgs {
+    const float *alpha, *scale;
+    int nplanes, C, H, W;
+    float dt, eps, maxc, relax;
+};
+template <typename TI, typename TO>
+void ex_fwd(const ExArgs& a, const void* src, void* dst, hipStream_t st) {
+    hipLaunchKernelGGL((explicit5_fwd_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha, a.scale,
+                       (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax);
+}
+template <typename T>
+void ex_fwd_step(const ExArgs& a, bool first, bool last, const void* src, void* dst, hipStream_t st) {
+    if (first && last) ex_fwd<T, T>(a, src, dst, st);
+    else if (first) ex_fwd<T, float>(a, src, dst, st);
+    else if (last) ex_fwd<float, T>(a, src, dst, st);
+    else ex_fwd<float, float>(a, src, dst, st);
+}
+// backward step k: u is the caller's (type T) for the first step, a parked fp32 state otherwise; the incoming gradient
+// is the caller's for the last step; gu is written to the caller's tensor at the first step
+template <typename TU, typename TG, typename TO>
+void ex_bwd(const ExArgs& a, const void* up, const void* gin, void* gdst, float* part, int acc, hipStream_t st) {
+    hipLaunchKernelGGL((explicit5_bwd_kernel<TU, TG, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up, (const TG*)gin,
+                       a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc);
+}
+template <typename T>
+void ex_bwd_step(const ExArgs& a, bool ufirst, bool gfirst, const void* up, const void* gin, void* gdst, float* part, int acc,
+                 hipStream_t st) {
+    if (ufirst && gfirst) ex_bwd<T, T, T>(a, up, gin, gdst, part, acc, st);
+    else if (ufirst) ex_bwd<T, float, T>(a, up, gin, gdst, part, acc, st);
+    else if (gfirst) ex_bwd<float, T, float>(a, up, gin, gdst, part, acc, st);
+    else ex_bwd<float, float, float>(a, up, gin, gdst, part, acc, st);
+}
+
 }  // namespace
 }  // namespace pde
 
@@ -503,13 +571,16 @@ int pde_explicit5_forward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io
                           float relax, int32_t num_steps, void* states, void* out, void* stream) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (W % 4) != 0 || num_steps < 1 || !u || !alpha_base || !channel_scaling || !out)
         return PDE_E_BADARG;
-    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16) return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nplanes = B * C;
     if (wave_plane_ok(H, W)) {                             // the plane stays in registers over all steps
         if (io_dtype == PDE_IO_F32)
             launch_fwd_wave<float>(H, (const float*)u, alpha_base, channel_scaling, (float*)out, (float*)states, nplanes, C,
                                    num_steps, dt, eps, max_coeff, relax, st);
+        else if (io_dtype == PDE_IO_F16)
+            launch_fwd_wave<f16e>(H, (const f16e*)u, alpha_base, channel_scaling, (f16e*)out, (float*)states, nplanes, C,
+                                  num_steps, dt, eps, max_coeff, relax, st);
         else
             launch_fwd_wave<bf16e>(H, (const bf16e*)u, alpha_base, channel_scaling, (bf16e*)out, (float*)states, nplanes, C,
                                    num_steps, dt, eps, max_coeff, relax, st);
@@ -518,20 +589,15 @@ int pde_explicit5_forward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io
     if (num_steps > 1 && !states) return PDE_E_BADARG;     // generic sizes: one launch per step through `states` (fp32)
     const size_t tf = (size_t)nplanes * H * W;
     float* sf = static_cast<float*>(states);
-    const bool bf = io_dtype == PDE_IO_BF16;
-#define PDE_EX_FWD(TI, TO, SRC, DST)                                                                                       \
-    hipLaunchKernelGGL((explicit5_fwd_kernel<TI, TO>), dim3(nplanes), dim3(256), 0, st, (const TI*)(SRC), alpha_base,        \
-                       channel_scaling, (TO*)(DST), C, H, W, dt, eps, max_coeff, relax)
+    const ExArgs ea{alpha_base, channel_scaling, nplanes, C, H, W, dt, eps, max_coeff, relax};
     for (int k = 0; k < num_steps; ++k) {
         const bool first = k == 0, last = k == num_steps - 1;
         const void* src = first ? u : static_cast<const void*>(sf + (size_t)(k - 1) * tf);
         void* dst = last ? out : static_cast<void*>(sf + (size_t)k * tf);
-        if (!bf || (!first && !last)) PDE_EX_FWD(float, float, src, dst);
-        else if (first && last) PDE_EX_FWD(bf16e, bf16e, src, dst);
-        else if (first) PDE_EX_FWD(bf16e, float, src, dst);
-        else PDE_EX_FWD(float, bf16e, src, dst);
+        if (io_dtype == PDE_IO_F32) ex_fwd_step<float>(ea, first, last, src, dst, st);
+        else if (io_dtype == PDE_IO_F16) ex_fwd_step<f16e>(ea, first, last, src, dst, st);
+        else ex_fwd_step<bf16e>(ea, first, last, src, dst, st);
     }
-#undef PDE_EX_FWD
     return check_launch();
 }
 
@@ -552,7 +618,7 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (W % 4) != 0 || num_steps < 1 || !u || !gout || !alpha_base ||
         !channel_scaling || !gu || !g_alpha_base || !g_channel_scaling || !workspace || (num_steps > 1 && !states))
         return PDE_E_BADARG;
-    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16) return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     if (workspace_bytes < pde_explicit5_backward_workspace_bytes(B, C, H, W, io_dtype, num_steps)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(workspace);
@@ -561,6 +627,9 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
         if (io_dtype == PDE_IO_F32)
             launch_bwd_wave<float>(H, (const float*)u, (const float*)states, (const float*)gout, alpha_base, channel_scaling,
                                    (float*)gu, part, nplanes, C, num_steps, dt, eps, max_coeff, relax, st);
+        else if (io_dtype == PDE_IO_F16)
+            launch_bwd_wave<f16e>(H, (const f16e*)u, (const float*)states, (const f16e*)gout, alpha_base, channel_scaling,
+                                  (f16e*)gu, part, nplanes, C, num_steps, dt, eps, max_coeff, relax, st);
         else
             launch_bwd_wave<bf16e>(H, (const bf16e*)u, (const float*)states, (const bf16e*)gout, alpha_base, channel_scaling,
                                    (bf16e*)gu, part, nplanes, C, num_steps, dt, eps, max_coeff, relax, st);
@@ -570,24 +639,18 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
         float* buf0 = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)nplanes * 2 * sizeof(float)));
         float* buf1 = reinterpret_cast<float*>(reinterpret_cast<char*>(buf0) + align256(tf * sizeof(float)));
         const float* sf = static_cast<const float*>(states);
-        const bool bf = io_dtype == PDE_IO_BF16;
+        const ExArgs ea{alpha_base, channel_scaling, nplanes, C, H, W, dt, eps, max_coeff, relax};
         const void* gin = gout;
-#define PDE_EX_BWD(TU, TG, TO, UP, GIN, GDST, ACC)                                                                          \
-    hipLaunchKernelGGL((explicit5_bwd_kernel<TU, TG, TO>), dim3(nplanes), dim3(256), 0, st, (const TU*)(UP), (const TG*)(GIN), \
-                       alpha_base, channel_scaling, (TO*)(GDST), part, C, H, W, dt, eps, max_coeff, relax, ACC)
         for (int k = num_steps; k >= 1; --k) {
             const bool ufirst = k == 1, gfirst = k == num_steps;       // u / gu are the caller's tensors, gout too
             const void* up = ufirst ? u : static_cast<const void*>(sf + (size_t)(k - 2) * tf);
             void* gdst = ufirst ? gu : static_cast<void*>(gin == buf0 ? buf1 : buf0);
             const int acc = gfirst ? 0 : 1;
-            if (!bf) PDE_EX_BWD(float, float, float, up, gin, gdst, acc);
-            else if (ufirst && gfirst) PDE_EX_BWD(bf16e, bf16e, bf16e, up, gin, gdst, acc);
-            else if (ufirst) PDE_EX_BWD(bf16e, float, bf16e, up, gin, gdst, acc);
-            else if (gfirst) PDE_EX_BWD(float, bf16e, float, up, gin, gdst, acc);
-            else PDE_EX_BWD(float, float, float, up, gin, gdst, acc);
+            if (io_dtype == PDE_IO_F32) ex_bwd_step<float>(ea, ufirst, gfirst, up, gin, gdst, part, acc, st);
+            else if (io_dtype == PDE_IO_F16) ex_bwd_step<f16e>(ea, ufirst, gfirst, up, gin, gdst, part, acc, st);
+            else ex_bwd_step<bf16e>(ea, ufirst, gfirst, up, gin, gdst, part, acc, st);
             gin = gdst;
         }
-#undef PDE_EX_BWD
     }
     hipLaunchKernelGGL(explicit5_pgrad_kernel, dim3(C), dim3(256), 0, st, part, alpha_base, channel_scaling,
                        g_alpha_base, g_channel_scaling, B, C, dt, eps, max_coeff, relax);
@@ -603,8 +666,23 @@ int pde_jacobi_forward(int32_t B, int32_t H, int32_t W, int32_t nt, const float*
                        const float* b_col, float* out, void* stream) {
     if (B <= 0 || H < 4 || W < 4 || H > kJMax || W > kJMax || nt < 0 || !u || !a_row || !b_col || !out)
         return PDE_E_BADARG;
+    return pde_jacobi_io_forward(B, H, W, nt, PDE_IO_F32, u, a_row, b_col, out, stream);
+}
+
+int pde_jacobi_io_forward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u, const float* a_row,
+                          const float* b_col, void* out, void* stream) {
+    if (B <= 0 || H < 4 || W < 4 || H > kJMax || W > kJMax || nt < 0 || !u || !a_row || !b_col || !out)
+        return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(jacobi_fwd_kernel, dim3(B), dim3(256), jacobi_lds(H, W, false), st, u, a_row, b_col, out, H, W, nt);
+    const size_t lds = jacobi_lds(H, W, false);
+    if (io_dtype == PDE_IO_F32)
+        hipLaunchKernelGGL(jacobi_fwd_kernel<float>, dim3(B), dim3(256), lds, st, (const float*)u, a_row, b_col, (float*)out, H, W, nt);
+    else if (io_dtype == PDE_IO_BF16)
+        hipLaunchKernelGGL(jacobi_fwd_kernel<bf16e>, dim3(B), dim3(256), lds, st, (const bf16e*)u, a_row, b_col, (bf16e*)out, H, W, nt);
+    else if (io_dtype == PDE_IO_F16)
+        hipLaunchKernelGGL(jacobi_fwd_kernel<f16e>, dim3(B), dim3(256), lds, st, (const f16e*)u, a_row, b_col, (f16e*)out, H, W, nt);
+    else
+        return PDE_E_BADARG;
     return check_launch();
 }
 
@@ -614,19 +692,40 @@ size_t pde_jacobi_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, int3
     return align256((size_t)B * nt * PN * sizeof(float)) + align256((size_t)B * (H + W) * sizeof(float));
 }
 
+size_t pde_jacobi_io_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype) {
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return 0;
+    return pde_jacobi_backward_workspace_bytes(B, H, W, nt);          // the parked states are fp32 whatever the tensors' type
+}
+
 int pde_jacobi_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const float* u, const float* gout,
                         const float* a_row, const float* b_col, float* gu, float* g_a_row, float* g_b_col,
                         void* workspace, size_t workspace_bytes, void* stream) {
+    return pde_jacobi_io_backward(B, H, W, nt, PDE_IO_F32, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace,
+                                  workspace_bytes, stream);
+}
+
+int pde_jacobi_io_backward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u, const void* gout,
+                           const float* a_row, const float* b_col, void* gu, float* g_a_row, float* g_b_col,
+                           void* workspace, size_t workspace_bytes, void* stream) {
     if (B <= 0 || H < 4 || W < 4 || H > kJMax || W > kJMax || nt < 0 || !u || !gout || !a_row || !b_col || !gu ||
         !g_a_row || !g_b_col || !workspace)
         return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     if (workspace_bytes < pde_jacobi_backward_workspace_bytes(B, H, W, nt)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t PN = (size_t)(H + 2) * (W + 2);
     float* states = static_cast<float*>(workspace);
     float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)B * nt * PN * sizeof(float)));
-    hipLaunchKernelGGL(jacobi_bwd_kernel, dim3(B), dim3(256), jacobi_lds(H, W, true), st, u, gout, a_row, b_col, gu,
-                       states, part, H, W, nt);
+    const size_t lds = jacobi_lds(H, W, true);
+    if (io_dtype == PDE_IO_F32)
+        hipLaunchKernelGGL(jacobi_bwd_kernel<float>, dim3(B), dim3(256), lds, st, (const float*)u, (const float*)gout, a_row,
+                           b_col, (float*)gu, states, part, H, W, nt);
+    else if (io_dtype == PDE_IO_BF16)
+        hipLaunchKernelGGL(jacobi_bwd_kernel<bf16e>, dim3(B), dim3(256), lds, st, (const bf16e*)u, (const bf16e*)gout, a_row,
+                           b_col, (bf16e*)gu, states, part, H, W, nt);
+    else
+        hipLaunchKernelGGL(jacobi_bwd_kernel<f16e>, dim3(B), dim3(256), lds, st, (const f16e*)u, (const f16e*)gout, a_row,
+                           b_col, (f16e*)gu, states, part, H, W, nt);
     hipLaunchKernelGGL(jacobi_pgrad_kernel, dim3((H + W + 63) / 64), dim3(64), 0, st, part, g_a_row, g_b_col, B, H, W);
     return check_launch();
 }

@@ -42,6 +42,16 @@ template <> struct G4<bf16g> {
         *reinterpret_cast<ushort4*>(p) = q;
     }
 };
+struct f16g { unsigned short v; };
+template <> struct G4<f16g> {
+    __device__ static __forceinline__ float4 ld(const f16g* p) {
+        const ushort4 q = *reinterpret_cast<const ushort4*>(p);
+        return make_float4(f16_to_f32(q.x), f16_to_f32(q.y), f16_to_f32(q.z), f16_to_f32(q.w));
+    }
+    __device__ static __forceinline__ void st(f16g* p, float4 v) {
+        *reinterpret_cast<ushort4*>(p) = make_ushort4(f32_to_f16_hw(v.x), f32_to_f16_hw(v.y), f32_to_f16_hw(v.z), f32_to_f16_hw(v.w));
+    }
+};
 
 template <typename IO>
 __global__ __launch_bounds__(256) void gate_combine_fwd_kernel(GateArgs a) {
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(256) void gate_combine_bwd_kernel(GateArgs a) {
 
 int gate_check(int L, int B, int C, int HW, int io) {
     if (L < 1 || L > kGateMaxL || B <= 0 || C <= 0 || HW <= 0 || (HW % 4) != 0) return PDE_E_BADARG;
-    if (io != PDE_IO_F32 && io != PDE_IO_BF16) return PDE_E_BADARG;
+    if (io != PDE_IO_F32 && io != PDE_IO_BF16 && io != PDE_IO_F16) return PDE_E_BADARG;
     return PDE_OK;
 }
 
@@ -125,6 +135,7 @@ int pde_gate_combine_forward(int32_t L, int32_t B, int32_t C, int32_t HW, int32_
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((a.planes + 3) / 4), block(256);
     if (io_dtype == PDE_IO_F32) hipLaunchKernelGGL((gate_combine_fwd_kernel<float>), grid, block, 0, st, a);
+    else if (io_dtype == PDE_IO_F16) hipLaunchKernelGGL((gate_combine_fwd_kernel<f16g>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((gate_combine_fwd_kernel<bf16g>), grid, block, 0, st, a);
     return check_launch();
 }
@@ -144,6 +155,7 @@ int pde_gate_combine_backward(int32_t L, int32_t B, int32_t C, int32_t HW, int32
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((a.planes + 3) / 4), block(256);
     if (io_dtype == PDE_IO_F32) hipLaunchKernelGGL((gate_combine_bwd_kernel<float>), grid, block, 0, st, a);
+    else if (io_dtype == PDE_IO_F16) hipLaunchKernelGGL((gate_combine_bwd_kernel<f16g>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((gate_combine_bwd_kernel<bf16g>), grid, block, 0, st, a);
     return check_launch();
 }

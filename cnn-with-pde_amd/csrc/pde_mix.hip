@@ -28,6 +28,11 @@ template <> struct Io<bf16s> {
     __device__ static __forceinline__ float ld(const bf16s* p) { return __uint_as_float((unsigned int)p->v << 16); }
     __device__ static __forceinline__ void st(bf16s* p, float f) { p->v = f32_to_bf16_hw(f); }
 };
+struct f16s { unsigned short v; };
+template <> struct Io<f16s> {
+    __device__ static __forceinline__ float ld(const f16s* p) { return f16_to_f32(p->v); }
+    __device__ static __forceinline__ void st(f16s* p, float f) { p->v = f32_to_f16_hw(f); }
+};
 
 constexpr int kOC = 8;   // output channels per pass
 
@@ -155,6 +160,15 @@ template <> struct Io4<bf16s> {
         bf16s t[4];
         Io<bf16s>::st(&t[0], v.x); Io<bf16s>::st(&t[1], v.y); Io<bf16s>::st(&t[2], v.z); Io<bf16s>::st(&t[3], v.w);
         *reinterpret_cast<ushort4*>(p) = make_ushort4(t[0].v, t[1].v, t[2].v, t[3].v);
+    }
+};
+template <> struct Io4<f16s> {
+    __device__ static __forceinline__ float4 ld(const f16s* p) {
+        const ushort4 q = *reinterpret_cast<const ushort4*>(p);
+        return make_float4(f16_to_f32(q.x), f16_to_f32(q.y), f16_to_f32(q.z), f16_to_f32(q.w));
+    }
+    __device__ static __forceinline__ void st(f16s* p, float4 v) {
+        *reinterpret_cast<ushort4*>(p) = make_ushort4(f32_to_f16_hw(v.x), f32_to_f16_hw(v.y), f32_to_f16_hw(v.z), f32_to_f16_hw(v.w));
     }
 };
 
@@ -487,6 +501,10 @@ int launch_apply_mfma(int B, int C, int HW, int io, const void* u, const float* 
         static unsigned long long cfg = 0;
         ensure_lds((const void*)mix_apply_mfma_kernel<float>, 65536, cfg);
         hipLaunchKernelGGL((mix_apply_mfma_kernel<float>), dim3((unsigned)grid), dim3(256), lds, st, (const float*)u, M, (float*)out, B, C, HW, trans);
+    } else if (io == PDE_IO_F16) {
+        static unsigned long long cfg = 0;
+        ensure_lds((const void*)mix_apply_mfma_kernel<f16s>, 65536, cfg);
+        hipLaunchKernelGGL((mix_apply_mfma_kernel<f16s>), dim3((unsigned)grid), dim3(256), lds, st, (const f16s*)u, M, (f16s*)out, B, C, HW, trans);
     } else {
         static unsigned long long cfg = 0;
         ensure_lds((const void*)mix_apply_mfma_kernel<bf16s>, 65536, cfg);
@@ -506,12 +524,15 @@ int pde_channel_mix_forward(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, 
                             void* out, void* stream) {
     if (B <= 0 || C <= 0 || HW <= 0 || !u || !M || !out) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16) return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     if (io_dtype == PDE_IO_BF16 && mix_bf16_ok(C, HW)) return mix_bf16_apply(B, C, HW, u, M, out, 0, st);
+    if (io_dtype == PDE_IO_F16 && mix_bf16_ok(C, HW)) return mix_f16_apply(B, C, HW, u, M, out, 0, st);
     if (mfma_apply_ok(C, HW)) return launch_apply_mfma(B, C, HW, io_dtype, u, M, out, 0, st);
     dim3 grid((HW + 255) / 256, B);
     if (io_dtype == PDE_IO_F32)
         hipLaunchKernelGGL((mix_apply_kernel<float, false>), grid, dim3(256), 0, st, (const float*)u, M, (float*)out, C, HW);
+    else if (io_dtype == PDE_IO_F16)
+        hipLaunchKernelGGL((mix_apply_kernel<f16s, false>), grid, dim3(256), 0, st, (const f16s*)u, M, (f16s*)out, C, HW);
     else
         hipLaunchKernelGGL((mix_apply_kernel<bf16s, false>), grid, dim3(256), 0, st, (const bf16s*)u, M, (bf16s*)out, C, HW);
     return check_launch();
@@ -543,13 +564,14 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
     if (B <= 0 || C <= 0 || HW <= 0 || !u || !gout || !M || !gu || !workspace || (finalize && !gM)) return PDE_E_BADARG;
     if (workspace_bytes < pde_channel_mix_backward_workspace_bytes(B, C, HW)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16) return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     dim3 grid((HW + 255) / 256, B);
     const int tiles = (C + kT - 1) / kT;
     float* part = static_cast<float*>(workspace);
-    if (io_dtype == PDE_IO_BF16 && mix_bf16_ok(C, HW)) {   // exact bf16 products on the bf16 MFMA
+    if (io_dtype != PDE_IO_F32 && mix_bf16_ok(C, HW)) {    // exact bf16 / fp16 products on the bf16 / fp16 MFMA
         const int nsplit = mix_bf16_splits(B, C, HW);
-        const int rc = mix_bf16_backward(B, C, HW, u, gout, M, gu, part, nsplit, accumulate, st);
+        const int rc = io_dtype == PDE_IO_BF16 ? mix_bf16_backward(B, C, HW, u, gout, M, gu, part, nsplit, accumulate, st)
+                                               : mix_f16_backward(B, C, HW, u, gout, M, gu, part, nsplit, accumulate, st);
         if (rc != PDE_OK) return rc;
         if (finalize) hipLaunchKernelGGL(mix_gm_reduce_kernel, dim3((C * C + 31) / 32), dim3(256), 0, st, part, gM, C * C, nsplit);
         return check_launch();
@@ -568,6 +590,11 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
             else if (C == 64) launch_fused<float, 64, 4, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
             else if (C == 96) launch_fused<float, 96, 3, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
             else launch_fused<float, 128, 8, false>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
+        } else if (io_dtype == PDE_IO_F16) {
+            if (C == 32) launch_fused<f16s, 32, 1, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
+            else if (C == 64) launch_fused<f16s, 64, 4, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
+            else if (C == 96) launch_fused<f16s, 96, 3, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
+            else launch_fused<f16s, 128, 8, false>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
         } else {
             if (C == 32) launch_fused<bf16s, 32, 1, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
             else if (C == 64) launch_fused<bf16s, 64, 4, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
@@ -583,6 +610,8 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
         if (rc != PDE_OK) return rc;
     } else if (io_dtype == PDE_IO_F32) {
         hipLaunchKernelGGL((mix_apply_kernel<float, true>), grid, dim3(256), 0, st, (const float*)gout, M, (float*)gu, C, HW);
+    } else if (io_dtype == PDE_IO_F16) {
+        hipLaunchKernelGGL((mix_apply_kernel<f16s, true>), grid, dim3(256), 0, st, (const f16s*)gout, M, (f16s*)gu, C, HW);
     } else {
         hipLaunchKernelGGL((mix_apply_kernel<bf16s, true>), grid, dim3(256), 0, st, (const bf16s*)gout, M, (bf16s*)gu, C, HW);
     }
@@ -595,6 +624,10 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
             static unsigned long long cfg = 0;
         ensure_lds((const void*)mix_gm_mfma_kernel<float>, 72 * 1024, cfg);
             hipLaunchKernelGGL((mix_gm_mfma_kernel<float>), dim3(nsplit), dim3(256), lds, st, (const float*)u, (const float*)gout, part, B, C, HW, nsplit, accumulate);
+        } else if (io_dtype == PDE_IO_F16) {
+            static unsigned long long cfg = 0;
+        ensure_lds((const void*)mix_gm_mfma_kernel<f16s>, 72 * 1024, cfg);
+            hipLaunchKernelGGL((mix_gm_mfma_kernel<f16s>), dim3(nsplit), dim3(256), lds, st, (const f16s*)u, (const f16s*)gout, part, B, C, HW, nsplit, accumulate);
         } else {
             static unsigned long long cfg = 0;
         ensure_lds((const void*)mix_gm_mfma_kernel<bf16s>, 72 * 1024, cfg);
@@ -605,6 +638,9 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
         if (io_dtype == PDE_IO_F32)
             hipLaunchKernelGGL((mix_gm_kernel<float>), dim3(tiles * tiles, nsplit), dim3(256), 0, st, (const float*)u,
                                (const float*)gout, part, B, C, HW, nsplit, accumulate);
+        else if (io_dtype == PDE_IO_F16)
+            hipLaunchKernelGGL((mix_gm_kernel<f16s>), dim3(tiles * tiles, nsplit), dim3(256), 0, st, (const f16s*)u,
+                               (const f16s*)gout, part, B, C, HW, nsplit, accumulate);
         else
             hipLaunchKernelGGL((mix_gm_kernel<bf16s>), dim3(tiles * tiles, nsplit), dim3(256), 0, st, (const bf16s*)u,
                                (const bf16s*)gout, part, B, C, HW, nsplit, accumulate);

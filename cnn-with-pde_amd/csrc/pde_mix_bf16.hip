@@ -33,10 +33,33 @@ constexpr int kRow = 144;               // bytes per tile row: 128 + 16 pad (16 
 __device__ __forceinline__ unsigned short f2bf(float f) { return f32_to_bf16_hw(f); }
 __device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float((unsigned int)h << 16); }
 
-// hi/lo bf16 fragments of M for the B operand, in LDS: [piece][tile][k-step][lane][8].
+// The 16-bit element types of the products below.  v_mfma_f32_32x32x16_bf16 and v_mfma_f32_32x32x16_f16 take their operands
+// in the same lane map (the one above); only the element format and the instruction differ.  fp16 tensors (PDE_IO_F16) run
+// the same kernels with MixF16: on that route M is fp16 as well (include/pdecnn.h), so M = hi exactly and there is no lo
+// piece — one MFMA per K = 16 instead of two, and the products are exact.
+struct MixBf16 {
+    static constexpr bool kLo = true;                   // fp32 M: hi + lo
+    typedef __bf16 v8 __attribute__((ext_vector_type(8)));
+    __device__ static __forceinline__ unsigned short rd(float f) { return f2bf(f); }
+    __device__ static __forceinline__ float wd(unsigned short h) { return bf2f(h); }
+    __device__ static __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+struct MixF16 {
+    static constexpr bool kLo = false;                  // fp16 M: hi alone
+    typedef _Float16 v8 __attribute__((ext_vector_type(8)));
+    __device__ static __forceinline__ unsigned short rd(float f) { return f32_to_f16_hw(f); }
+    __device__ static __forceinline__ float wd(unsigned short h) { return f16_to_f32(h); }
+    __device__ static __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+
+// LDS bytes of the fragment tables of M: hi and lo pieces (bf16) or hi alone (fp16), 16 bits per element each
+template <typename E, int C>
+constexpr size_t frag_bytes() { return (size_t)(E::kLo ? 4 : 2) * C * C; }
+
+// hi/lo 16-bit fragments of M for the B operand, in LDS: [piece][tile][k-step][lane][8].
 // TRANS = false (forward):  B[k = in j][col = out i]  = M[i][j]:  lane (h,r) of (ot,ks): M[32ot + r][16ks + 8h + jj]
 // TRANS = true  (backward): B[k = out i][col = in j]  = M[i][j]:  lane (h,r) of (jt,ks): M[16ks + 8h + jj][32jt + r]
-template <int C, bool TRANS>
+template <int C, bool TRANS, typename E = MixBf16>
 __device__ __forceinline__ void build_frags(const float* __restrict__ M, unsigned short* frag, int tid, int nthreads) {
     constexpr int T = C / 32, KS = C / 16;
     for (int e = tid; e < T * KS * 64; e += nthreads) {
@@ -46,13 +69,15 @@ __device__ __forceinline__ void build_frags(const float* __restrict__ M, unsigne
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) {
             const float w = TRANS ? M[(16 * ks + 8 * h + jj) * C + 32 * t + r] : M[(32 * t + r) * C + 16 * ks + 8 * h + jj];
-            hi[jj] = f2bf(w);
-            lo[jj] = f2bf(w - bf2f(hi[jj]));
+            hi[jj] = E::rd(w);
+            lo[jj] = E::rd(w - E::wd(hi[jj]));
         }
         uint4* dh = reinterpret_cast<uint4*>(frag + (size_t)e * 8);
-        uint4* dl = reinterpret_cast<uint4*>(frag + (size_t)(T * KS * 64 + e) * 8);
         *dh = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
-        *dl = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
+        if constexpr (E::kLo) {
+            uint4* dl = reinterpret_cast<uint4*>(frag + (size_t)(T * KS * 64 + e) * 8);
+            *dl = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
+        }
     }
 }
 
@@ -95,7 +120,8 @@ __device__ __forceinline__ void store_tile(unsigned short* __restrict__ dst, int
 }
 
 // A operand X^T from the natural image of X ([channel][pixel]): A[row = pixel 32pg + r][k = channel 16ks + 8h + jj]
-__device__ __forceinline__ v8bf tr_operand(const unsigned char* img, int pg, int ks, int lane) {
+template <typename E = MixBf16>
+__device__ __forceinline__ typename E::v8 tr_operand(const unsigned char* img, int pg, int ks, int lane) {
     const int grp = lane >> 4, i = lane & 15, h = lane >> 5;
     const int q = i >> 2, p = i & 3;
     // lane 4q+p of a 16-lane group supplies row q (of 4 channel rows), pixel columns 4p..4p+3 of the group's 16
@@ -103,38 +129,41 @@ __device__ __forceinline__ v8bf tr_operand(const unsigned char* img, int pg, int
     const v4s lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(a0));
     const v4s hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(a0 + 4 * kRow));
     const v8s all = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-    return __builtin_bit_cast(v8bf, all);
+    return __builtin_bit_cast(typename E::v8, all);
 }
-__device__ __forceinline__ v8bf frag_operand(const unsigned short* frag, int idx) {
-    return __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(frag + (size_t)idx * 8));
+template <typename E = MixBf16>
+__device__ __forceinline__ typename E::v8 frag_operand(const unsigned short* frag, int idx) {
+    return __builtin_bit_cast(typename E::v8, *reinterpret_cast<const v8s*>(frag + (size_t)idx * 8));
 }
 // row operand: 8 consecutive pixels of one channel row of the image
-__device__ __forceinline__ v8bf row_operand(const unsigned char* img, int row, int px) {
-    return __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(img + row * kRow + px * 2));
+template <typename E = MixBf16>
+__device__ __forceinline__ typename E::v8 row_operand(const unsigned char* img, int row, int px) {
+    return __builtin_bit_cast(typename E::v8, *reinterpret_cast<const v8s*>(img + row * kRow + px * 2));
 }
 // D tile [pixel][channel]: lane (h,r) holds channel 32t + r, pixels 32pg + 8q + 4h + 0..3 in regs 4q..4q+3
+template <typename E = MixBf16>
 __device__ __forceinline__ void put_result(unsigned char* img, const f32x16& acc, int t, int pg, int lane) {
     const int h = lane >> 5, r = lane & 31;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const unsigned int a = f2bf(acc[4 * q]) | ((unsigned int)f2bf(acc[4 * q + 1]) << 16);
-        const unsigned int b = f2bf(acc[4 * q + 2]) | ((unsigned int)f2bf(acc[4 * q + 3]) << 16);
+        const unsigned int a = E::rd(acc[4 * q]) | ((unsigned int)E::rd(acc[4 * q + 1]) << 16);
+        const unsigned int b = E::rd(acc[4 * q + 2]) | ((unsigned int)E::rd(acc[4 * q + 3]) << 16);
         *reinterpret_cast<uint2*>(img + (32 * t + r) * kRow + (32 * pg + 8 * q + 4 * h) * 2) = make_uint2(a, b);
     }
 }
 
 // ---- forward: out = M u -------------------------------------------------------------------------------
-template <int C>
+template <int C, typename E = MixBf16>
 __global__ __launch_bounds__(C * 4) void mix_apply_bf16_kernel(const unsigned short* __restrict__ u, const float* __restrict__ M,
                                                                unsigned short* __restrict__ out, int B, int HW, int trans) {
     constexpr int T = C / 32, KS = C / 16, NT = C * 4, FR = T * KS * 64;     // waves = 2 pixel groups x T channel tiles
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned short* frag = reinterpret_cast<unsigned short*>(smem);          // [2][FR][8] bf16 = 4*C*C bytes
-    unsigned char* img_in = smem + (size_t)4 * C * C;
+    unsigned short* frag = reinterpret_cast<unsigned short*>(smem);          // [2 or 1][FR][8]: frag_bytes<E, C>()
+    unsigned char* img_in = smem + frag_bytes<E, C>();
     unsigned char* img_out = img_in + C * kRow;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (trans) build_frags<C, true>(M, frag, tid, NT);
-    else build_frags<C, false>(M, frag, tid, NT);
+    if (trans) build_frags<C, true, E>(M, frag, tid, NT);
+    else build_frags<C, false, E>(M, frag, tid, NT);
     const int pg = wave & 1, ot = wave >> 1;
     const int per_sample = HW / kPx;
     const long total = (long)B * per_sample;
@@ -153,19 +182,19 @@ __global__ __launch_bounds__(C * 4) void mix_apply_bf16_kernel(const unsigned sh
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll 2
         for (int ks = 0; ks < KS; ++ks) {
-            const v8bf a = tr_operand(img_in, pg, ks, lane);
+            const typename E::v8 a = tr_operand<E>(img_in, pg, ks, lane);
             const int fi = (ot * KS + ks) * 64 + lane;
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, frag_operand(frag, fi), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, frag_operand(frag, FR + fi), acc, 0, 0, 0);
+            acc = E::mfma(a, frag_operand<E>(frag, fi), acc);
+            if constexpr (E::kLo) acc = E::mfma(a, frag_operand<E>(frag, FR + fi), acc);
         }
-        put_result(img_out, acc, ot, pg, lane);
+        put_result<E>(img_out, acc, ot, pg, lane);
         __syncthreads();
         store_tile<C>(out + (size_t)b * C * HW, HW, p0, img_out, tid, NT);
     }
 }
 
 // ---- backward: gu = M^T g and the partial sums of gM = g u^T ---------------------------------------------
-template <int C>
+template <int C, typename E = MixBf16>
 __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned short* __restrict__ u, const unsigned short* __restrict__ g,
                                                              const float* __restrict__ M, unsigned short* __restrict__ gu,
                                                              float* __restrict__ part, int B, int HW, int accp) {
@@ -173,12 +202,12 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned shor
     constexpr int NTM = T * T / W;                         // gM tiles per wave (C = 64: 1, C = 128: 2)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned short* frag = reinterpret_cast<unsigned short*>(smem);
-    unsigned char* img_g = smem + (size_t)4 * C * C;
+    unsigned char* img_g = smem + frag_bytes<E, C>();
     unsigned char* img_u = img_g + C * kRow;
     unsigned char* img_o = img_u + C * kRow;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, r = lane & 31;
-    build_frags<C, true>(M, frag, tid, NT);
+    build_frags<C, true, E>(M, frag, tid, NT);
     const int pg = wave & 1, jt = wave >> 1;               // my gu tile: pixel group, input-channel tile
     f32x16 acc_m[NTM];
 #pragma unroll
@@ -213,9 +242,9 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned shor
 #pragma unroll
             for (int t = 0; t < NTM; ++t) {
                 const int tl = wave + W * t, it = tl / T, jt2 = tl % T;
-                const v8bf a = row_operand(img_g, 32 * it + r, 16 * kp + 8 * h);
-                const v8bf bb = row_operand(img_u, 32 * jt2 + r, 16 * kp + 8 * h);
-                acc_m[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bb, acc_m[t], 0, 0, 0);
+                const typename E::v8 a = row_operand<E>(img_g, 32 * it + r, 16 * kp + 8 * h);
+                const typename E::v8 bb = row_operand<E>(img_u, 32 * jt2 + r, 16 * kp + 8 * h);
+                acc_m[t] = E::mfma(a, bb, acc_m[t]);
             }
         }
         // gu^T tile = g^T (hi + lo)
@@ -224,12 +253,12 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned shor
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll 2
         for (int ks = 0; ks < KS; ++ks) {
-            const v8bf a = tr_operand(img_g, pg, ks, lane);
+            const typename E::v8 a = tr_operand<E>(img_g, pg, ks, lane);
             const int fi = (jt * KS + ks) * 64 + lane;
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, frag_operand(frag, fi), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, frag_operand(frag, FR + fi), acc, 0, 0, 0);
+            acc = E::mfma(a, frag_operand<E>(frag, fi), acc);
+            if constexpr (E::kLo) acc = E::mfma(a, frag_operand<E>(frag, FR + fi), acc);
         }
-        put_result(img_o, acc, jt, pg, lane);
+        put_result<E>(img_o, acc, jt, pg, lane);
         __syncthreads();
         store_tile<C>(gu + (size_t)b * C * HW, HW, p0, img_o, tid, NT);
     }
@@ -440,24 +469,24 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_split_kernel(const float* __res
 
 inline void ensure_lds(const void* kernel, int bytes, unsigned long long& done) { (void)ensure_dynamic_lds(kernel, bytes, done); }
 
-template <int C>
+template <int C, typename E = MixBf16>
 void launch_apply(const void* u, const float* M, void* out, int B, int HW, int trans, hipStream_t st) {
-    const size_t lds = (size_t)4 * C * C + 2 * (size_t)C * kRow;
+    const size_t lds = frag_bytes<E, C>() + 2 * (size_t)C * kRow;
     static unsigned long long cfg = 0;
-    ensure_lds((const void*)mix_apply_bf16_kernel<C>, (int)lds, cfg);
+    ensure_lds((const void*)mix_apply_bf16_kernel<C, E>, (int)lds, cfg);
     const long tiles = (long)B * (HW / kPx);
     const int per_cu = C == 64 ? 4 : 1;                    // workgroups an LDS footprint of 34 / 100 KB allows
     const long grid = tiles < 256L * per_cu ? tiles : 256L * per_cu;
-    hipLaunchKernelGGL((mix_apply_bf16_kernel<C>), dim3((unsigned)grid), dim3(C * 4), lds, st, (const unsigned short*)u, M,
+    hipLaunchKernelGGL((mix_apply_bf16_kernel<C, E>), dim3((unsigned)grid), dim3(C * 4), lds, st, (const unsigned short*)u, M,
                        (unsigned short*)out, B, HW, trans);
 }
-template <int C>
+template <int C, typename E = MixBf16>
 void launch_bwd(const void* u, const void* g, const float* M, void* gu, float* part, int B, int HW, int nsplit, int accp,
                 hipStream_t st) {
-    const size_t lds = (size_t)4 * C * C + 3 * (size_t)C * kRow;
+    const size_t lds = frag_bytes<E, C>() + 3 * (size_t)C * kRow;
     static unsigned long long cfg = 0;
-    ensure_lds((const void*)mix_bwd_bf16_kernel<C>, (int)lds, cfg);
-    hipLaunchKernelGGL((mix_bwd_bf16_kernel<C>), dim3((unsigned)nsplit), dim3(C * 4), lds, st, (const unsigned short*)u,
+    ensure_lds((const void*)mix_bwd_bf16_kernel<C, E>, (int)lds, cfg);
+    hipLaunchKernelGGL((mix_bwd_bf16_kernel<C, E>), dim3((unsigned)nsplit), dim3(C * 4), lds, st, (const unsigned short*)u,
                        (const unsigned short*)g, M, (unsigned short*)gu, part, B, HW, accp);
 }
 
@@ -510,6 +539,17 @@ int mix_bf16_backward(int B, int C, int HW, const void* u, const void* g, const 
                       int accp, hipStream_t st) {
     if (C == 64) launch_bwd<64>(u, g, M, gu, part, B, HW, nsplit, accp, st);
     else launch_bwd<128>(u, g, M, gu, part, B, HW, nsplit, accp, st);
+    return check_launch();
+}
+int mix_f16_apply(int B, int C, int HW, const void* u, const float* M, void* out, int trans, hipStream_t st) {
+    if (C == 64) launch_apply<64, MixF16>(u, M, out, B, HW, trans, st);
+    else launch_apply<128, MixF16>(u, M, out, B, HW, trans, st);
+    return check_launch();
+}
+int mix_f16_backward(int B, int C, int HW, const void* u, const void* g, const float* M, void* gu, float* part, int nsplit,
+                     int accp, hipStream_t st) {
+    if (C == 64) launch_bwd<64, MixF16>(u, g, M, gu, part, B, HW, nsplit, accp, st);
+    else launch_bwd<128, MixF16>(u, g, M, gu, part, B, HW, nsplit, accp, st);
     return check_launch();
 }
 

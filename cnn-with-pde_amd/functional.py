@@ -100,7 +100,38 @@ def _io_dtype(t: torch.Tensor) -> int:
         return L.PDE_IO_F32
     if t.dtype == torch.bfloat16:
         return L.PDE_IO_BF16
-    raise L.PdeError(f"unsupported tensor dtype {t.dtype} (float32 or bfloat16)")
+    if t.dtype == torch.float16:
+        return L.PDE_IO_F16
+    raise L.PdeError(f"unsupported tensor dtype {t.dtype} (float32, bfloat16 or float16)")
+
+
+#: tensor types the kernels take as they are (anything else is widened to fp32 first)
+_IO_TYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+# float16: a call takes the float16 route only when its input AND every floating parameter it uses are float16 — the
+# model.half() case, the only one where torch's type promotion gives float16.  Tensors in and out are then fp16, the
+# arithmetic inside the kernels fp32, rounded to fp16 where the bf16 route rounds to bf16; parameter gradients are reduced
+# in fp32 and rounded once (autograd casts them to the parameter's dtype).  Any other mix with an fp16 input keeps the
+# behaviour from before the route existed: the input is widened to fp32 and the result is fp32 (autocast's fp32 layers).
+def _is_f16(u, *params) -> bool:
+    return (isinstance(u, torch.Tensor) and u.dtype == torch.float16 and
+            all(p.dtype == torch.float16 for p in params if isinstance(p, torch.Tensor) and p.is_floating_point()))
+
+
+def _io_in(u: torch.Tensor, *params) -> torch.Tensor:
+    """``u`` as the kernels take it: fp32 and bf16 as given, fp16 on the float16 route, anything else widened to fp32."""
+    if u.dtype in (torch.float32, torch.bfloat16) or (u.dtype == torch.float16 and _is_f16(u, *params)):
+        return u
+    return u.float()
+
+
+def route_input(u: torch.Tensor, *params) -> torch.Tensor:
+    """The input of a layer made of several calls, decided once for every parameter the layer uses (the float16 route needs
+    them all fp16): float64 anywhere leaves it to the float64 route, otherwise ``_io_in``."""
+    if _is_f64(u, *params):
+        return u
+    return _io_in(u, *params)
 
 
 _desc_cache = {}
@@ -340,7 +371,7 @@ class _AdiFn(torch.autograd.Function):
         if u.dim() != 4 or u.shape[2] != u.shape[3]:
             raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
         B, Cc, N, _ = u.shape
-        if u.dtype not in (torch.float32, torch.bfloat16):
+        if u.dtype not in _IO_TYPES:
             u = u.float()
         u = u.contiguous()
         p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
@@ -410,7 +441,7 @@ class _AdiMixedFn(torch.autograd.Function):
         if u.dim() != 4 or u.shape[2] != u.shape[3]:
             raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
         B, Cc, N, _ = u.shape
-        if u.dtype not in (torch.float32, torch.bfloat16):
+        if u.dtype not in _IO_TYPES:
             u = u.float()
         u = u.contiguous()
         sps, K = len(steps[0]), len(steps)
@@ -486,7 +517,7 @@ class _AdiSmallFn(torch.autograd.Function):
         lib = L.load()
         _require_cuda(u, ab, bb, asl, bsl, M, skip_weight)
         B, Cc, N, _ = u.shape
-        if u.dtype not in (torch.float32, torch.bfloat16):
+        if u.dtype not in _IO_TYPES:
             u = u.float()
         u = u.contiguous()
         sps, K = len(steps[0]), len(steps)
@@ -563,7 +594,7 @@ class _AdiMultiFn(torch.autograd.Function):
         nl = len(specs)
         _require_cuda(u, weights, *flat)
         B, Cc, N, _ = u.shape
-        if u.dtype not in (torch.float32, torch.bfloat16):
+        if u.dtype not in _IO_TYPES:
             u = u.float()
         u = u.contiguous()
         need_grad = any(ctx.needs_input_grad)
@@ -716,6 +747,8 @@ def adi_diffuse_multi(u, layers, weights=None, plane_sums=False, checkpoints="au
         if plane_sums:
             return out, ys, [y.sum(dim=(2, 3)) for y in ys]
         return out, ys
+    u = _io_in(u, weights, *flat)
+    f16 = u.dtype == torch.float16
     H = L.host_ext()
     if H is not None and u.dim() == 4 and u.is_cuda and u.shape[0] > 0 and len({len(sp[0][0]) for sp in specs}) == 1:
         # the native host path (csrc/host_ext.cpp): the same call of the C ABI from a C++ autograd node
@@ -727,15 +760,15 @@ def adi_diffuse_multi(u, layers, weights=None, plane_sums=False, checkpoints="au
                 raise L.PdeError(f"adi_diffuse_multi: {len(masks)} checkpoint masks for {nl} layers")
             mode = 0
         B, Cc, N, _ = u.shape
-        io = L.PDE_IO_BF16 if u.dtype == torch.bfloat16 else L.PDE_IO_F32
+        io = _io_dtype(u)
         addrs = [C.addressof(_make_desc(B, Cc, N, io, st.flat, sm, cm, ep)) for st, sm, cm, ep in specs]
         res = H.multi(u, weights, flat, addrs, len(specs[0][0][0]), bool(plane_sums), mode, masks, CKPT_AMAX)
-        if plane_sums:
-            return res[0], list(res[1:1 + nl]), list(res[1 + nl:])
-        return res[0], list(res[1:])
-    res = _AdiMultiFn.apply(u, weights, specs, bool(plane_sums), checkpoints, *flat)
+    else:
+        res = _AdiMultiFn.apply(u, weights, specs, bool(plane_sums), checkpoints, *flat)
     if plane_sums:
-        return res[0], list(res[1:1 + nl]), list(res[1 + nl:])
+        # the plane sums leave the kernel in fp32; on the float16 route they are fp16 like every other output
+        sums = [s.half() for s in res[1 + nl:]] if f16 else list(res[1 + nl:])
+        return res[0], list(res[1:1 + nl]), sums
     return res[0], list(res[1:])
 
 
@@ -750,7 +783,7 @@ def adi_small_supported(u, steps, smooth3=False, clamp_max=None, eps=1e-6) -> bo
     B, Cc, N, _ = u.shape
     if B == 0 or Cc > 4 or N > L.PDE_MAX_N or len(steps) * len(steps[0]) > L.PDE_MAX_SWEEPS:
         return False
-    io = L.PDE_IO_BF16 if u.dtype == torch.bfloat16 else L.PDE_IO_F32
+    io = {torch.bfloat16: L.PDE_IO_BF16, torch.float16: L.PDE_IO_F16}.get(u.dtype, L.PDE_IO_F32)
     steps = _as_schedule(steps)
     key = (B, Cc, N, io, steps.flat, bool(smooth3), clamp_max, float(eps), len(steps[0]))
     ok = _small_ok_cache.get(key)
@@ -775,13 +808,13 @@ def adi_diffuse_small(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
         y = adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode, smooth3=smooth3,
                               clamp_max=clamp_max, eps=eps, checkpoints=checkpoints)
         return y if skip_weight is None else skip_blend(u, y, skip_weight)
+    u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, skip_weight)
     if kmax_sink is None and (checkpoints == "auto" or isinstance(checkpoints, int)) and u.shape[0] > 0:
         H = L.host_ext()
         if H is not None and u.dim() == 4 and u.is_cuda:
             # the native host path (csrc/host_ext.cpp): the same call of the C ABI from a C++ autograd node
             B, Cc, N, _ = u.shape
-            d = _make_desc(B, Cc, N, L.PDE_IO_BF16 if u.dtype == torch.bfloat16 else L.PDE_IO_F32, steps.flat, smooth3,
-                           clamp_max, eps)
+            d = _make_desc(B, Cc, N, _io_dtype(u), steps.flat, smooth3, clamp_max, eps)
             return H.small(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, skip_weight, C.addressof(d),
                            len(steps[0]), 1 if mode == "pre" else 2, 1 if checkpoints == "auto" else 0,
                            0 if checkpoints == "auto" else int(checkpoints), CKPT_AMAX)
@@ -804,6 +837,8 @@ def adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
     steps = tuple(tuple(st) for st in steps)
     if len({len(st) for st in steps}) != 1:
         raise ValueError("every step must have the same number of sweeps")
+    if not _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M):
+        u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
     if u.dim() == 4 and u.is_cuda and (L.load().pde_adi_line_length_path(int(u.shape[-1])) == 2 or
                                        _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)):
         # a line length without fused kernels (pde_adi_line_length_path: any size up to PDE_MAX_N_GENERIC): the per-step
@@ -827,7 +862,7 @@ def adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
             # the native host path (csrc/host_ext.cpp): the same two calls of the C ABI from a C++ autograd node
             B, Cc, N, _ = u.shape
             flat = tuple(s for st in steps for s in st)
-            d = _make_desc(B, Cc, N, L.PDE_IO_BF16 if u.dtype == torch.bfloat16 else L.PDE_IO_F32, flat, smooth3, clamp_max, eps)
+            d = _make_desc(B, Cc, N, _io_dtype(u), flat, smooth3, clamp_max, eps)
             return H.mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, C.addressof(d), len(steps[0]),
                            1 if mode == "pre" else 2, 1 if checkpoints == "auto" else 0,
                            0 if checkpoints == "auto" else int(checkpoints), CKPT_AMAX)
@@ -865,14 +900,14 @@ def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, swe
     if _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff):
         return _AdiF64Fn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3), clamp_max,
                                float(eps), checkpoints)
+    u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
     if (kmax_sink is None and (checkpoints == "auto" or isinstance(checkpoints, int))) or \
             (kmax_sink is not None and isinstance(checkpoints, int)):
         H = L.host_ext()
-        if H is not None and u.dim() == 4 and u.is_cuda and u.dtype in (torch.float32, torch.bfloat16, torch.float16):
+        if H is not None and u.dim() == 4 and u.is_cuda and u.dtype in _IO_TYPES:
             # the native host path (csrc/host_ext.cpp): the same two calls of the C ABI from a C++ autograd node
             B, Cc, N, _ = u.shape
-            d = _make_desc(B, Cc, N, L.PDE_IO_BF16 if u.dtype == torch.bfloat16 else L.PDE_IO_F32, sweeps, smooth3,
-                           clamp_max, eps)
+            d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
             if checkpoints == "auto":
                 mode, lo, hi = 1, 0, 0
             else:
@@ -897,7 +932,7 @@ class _MixFn(torch.autograd.Function):
         _require_cuda(u, M)
         B, Cc = u.shape[0], u.shape[1]
         HW = u[0, 0].numel()
-        if u.dtype not in (torch.float32, torch.bfloat16):
+        if u.dtype not in _IO_TYPES:
             u = u.float()
         u = u.contiguous()
         Mf = M.detach().to(torch.float32).contiguous()
@@ -931,7 +966,7 @@ def channel_mix(u, M):
         return _empty_passthrough(u, M)
     if _is_f64(u, M):
         return _MixF64Fn.apply(u, M)
-    return _MixFn.apply(u, M)
+    return _MixFn.apply(_io_in(u, M), M)
 
 
 # --------------------------------------------------------------------------- BatchNorm2d + 4x4 avg/max pooling
@@ -1230,7 +1265,7 @@ class _GateCombineFn(torch.autograd.Function):
         ys, gates = rest[:nl], rest[nl:]
         _require_cuda(weights, *rest)
         y0 = ys[0]
-        dt = y0.dtype if y0.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        dt = y0.dtype if y0.dtype in (torch.float32, torch.bfloat16) or _is_f16(*ys, *gates, weights) else torch.float32
         ys_c = [y.to(dt).contiguous() for y in ys]
         B, Cc = y0.shape[:2]
         HW = y0[0, 0].numel()
@@ -1282,7 +1317,7 @@ class _Explicit5Fn(torch.autograd.Function):
     def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, num_steps):
         lib = L.load()
         _require_cuda(u, alpha_base, channel_scaling)
-        if u.dtype not in (torch.float32, torch.bfloat16):
+        if u.dtype not in _IO_TYPES:
             u = u.float()
         u = u.contiguous()
         B, Cc, H, W = u.shape
@@ -1326,23 +1361,29 @@ def explicit5_step(u, alpha_base, channel_scaling, dt=0.01, eps=1e-6, max_coeff=
     if _is_f64(u, alpha_base, channel_scaling):
         return _Explicit5F64Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
                                      int(num_steps))
-    return _Explicit5Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
-                              int(num_steps))
+    return _Explicit5Fn.apply(_io_in(u, alpha_base, channel_scaling), alpha_base, channel_scaling, float(dt), float(eps),
+                              float(max_coeff), float(relax), int(num_steps))
 
 
 class _JacobiFn(torch.autograd.Function):
+    """fp32 tensors (pde_jacobi_*), or fp16 ones on the float16 route (pde_jacobi_io_*: the same kernels with fp16 I/O)."""
+
     @staticmethod
     def forward(ctx, u, a_row, b_col, nt):
         lib = L.load()
         _require_cuda(u, a_row, b_col)
-        u = u.float().contiguous()
+        u = (u if u.dtype == torch.float16 else u.float()).contiguous()
         B, H, W = u.shape
         a = a_row.detach().float().contiguous()
         b = b_col.detach().float().contiguous()
         out = torch.empty_like(u)
         with torch.cuda.device(u.device):
-            L.check(lib.pde_jacobi_forward(B, H, W, nt, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
-                    "pde_jacobi_forward")
+            if u.dtype == torch.float16:
+                L.check(lib.pde_jacobi_io_forward(B, H, W, nt, L.PDE_IO_F16, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
+                        "pde_jacobi_io_forward")
+            else:
+                L.check(lib.pde_jacobi_forward(B, H, W, nt, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
+                        "pde_jacobi_forward")
         ctx.save_for_backward(u, a, b)
         ctx.nt = nt
         return out
@@ -1352,12 +1393,18 @@ class _JacobiFn(torch.autograd.Function):
         lib = L.load()
         u, a, b = ctx.saved_tensors
         B, H, W = u.shape
-        gout = gout.float().contiguous()
+        gout = gout.to(u.dtype).contiguous()
         gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
-        ws = _workspace(lib.pde_jacobi_backward_workspace_bytes(B, H, W, ctx.nt), u.device)
         with torch.cuda.device(u.device):
-            L.check(lib.pde_jacobi_backward(B, H, W, ctx.nt, _ptr(u), _ptr(gout), _ptr(a), _ptr(b), _ptr(gu), _ptr(ga),
-                                            _ptr(gb), _ptr(ws), ws.numel(), _stream()), "pde_jacobi_backward")
+            if u.dtype == torch.float16:
+                ws = _workspace(lib.pde_jacobi_io_backward_workspace_bytes(B, H, W, ctx.nt, L.PDE_IO_F16), u.device)
+                L.check(lib.pde_jacobi_io_backward(B, H, W, ctx.nt, L.PDE_IO_F16, _ptr(u), _ptr(gout), _ptr(a), _ptr(b),
+                                                   _ptr(gu), _ptr(ga), _ptr(gb), _ptr(ws), ws.numel(), _stream()),
+                        "pde_jacobi_io_backward")
+            else:
+                ws = _workspace(lib.pde_jacobi_backward_workspace_bytes(B, H, W, ctx.nt), u.device)
+                L.check(lib.pde_jacobi_backward(B, H, W, ctx.nt, _ptr(u), _ptr(gout), _ptr(a), _ptr(b), _ptr(gu), _ptr(ga),
+                                                _ptr(gb), _ptr(ws), ws.numel(), _stream()), "pde_jacobi_backward")
         return gu, ga, gb, None
 
 
@@ -1367,7 +1414,7 @@ def jacobi_diffuse(u, a_row, b_col, nt: int):
         return _empty_passthrough(u, a_row, b_col)
     if _is_f64(u, a_row, b_col):
         return _JacobiF64Fn.apply(u, a_row, b_col, int(nt))
-    return _JacobiFn.apply(u, a_row, b_col, int(nt))
+    return _JacobiFn.apply(_io_in(u, a_row, b_col), a_row, b_col, int(nt))
 
 
 # --------------------------------------------------------------------------- SVHN skip connection
@@ -1378,7 +1425,7 @@ class _SkipBlendFn(torch.autograd.Function):
         _require_cuda(u0, u, skip_weight)
         if u0.shape != u.shape:
             raise L.PdeError(f"shapes differ: {tuple(u0.shape)} vs {tuple(u.shape)}")
-        dt = u.dtype if u.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        dt = u.dtype if u.dtype in (torch.float32, torch.bfloat16) or _is_f16(u, u0, skip_weight) else torch.float32
         a, b = u0.to(dt).contiguous(), u.to(dt).contiguous()
         w = skip_weight.detach().to(torch.float32).reshape(1).contiguous()
         out = torch.empty_like(b)

@@ -156,6 +156,8 @@ class _AdiBase(nn.Module):
     def _run(self, u, steps, M=None, mode=None, skip_weight=None):
         """All steps of the layer.  One launch sequence holds at most PDE_MAX_SWEEPS sweeps: longer schedules
         (num_steps > 32 Strang steps) are cut into groups of whole steps, chained through autograd."""
+        # one route for the whole layer: its calls (sweeps, operator, skip blend) each see only some of the parameters
+        u = F_.route_input(u, self.alpha_base, self.beta_base, self.alpha_time_coeff, self.beta_time_coeff, M, skip_weight)
         per = max(1, L.PDE_MAX_SWEEPS // len(steps[0]))
         if len(steps) <= per:
             if M is None:

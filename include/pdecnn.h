@@ -39,6 +39,8 @@ extern "C" {
 #define PDE_IO_F32 0
 #define PDE_IO_BF16 1
 #define PDE_IO_F64 2               /* PdeAdiDescF64 only: the pde_*_f64_* entry points */
+#define PDE_IO_F16 3               /* float16 tensors (a half()-converted model): I/O rounded to fp16 where the bf16 route
+                                      rounds to bf16, math in fp32 */
 
 #define PDE_AXIS_X 0               /* solve along W with alpha (mnist_test.py:67-98)  */
 #define PDE_AXIS_Y 1               /* solve along H with beta  (mnist_test.py:100-133) */
@@ -56,7 +58,7 @@ typedef struct PdeSweep {
 /* Static description of one fused run of sweeps over a (B,C,N,N) tensor. */
 typedef struct PdeAdiDesc {
     int32_t B, C, N;            /* H = W = N                                             */
-    int32_t io_dtype;           /* PDE_IO_F32 | PDE_IO_BF16 (tensor I/O; math is fp32)   */
+    int32_t io_dtype;           /* PDE_IO_F32 | PDE_IO_BF16 | PDE_IO_F16 (tensor I/O; math is fp32) */
     int32_t num_sweeps;
     int32_t smooth3;            /* 1: 3-tap replicate average of the coefficient along the
                                    solve axis (mnist_test.py:135-149)                     */
@@ -277,7 +279,9 @@ int pde_adi_multi_backward(int32_t num_layers, const PdeSmallLayer* layers, cons
 
 /* out[b,i,p] = sum_j M[i,j] u[b,j,p]  — cifar10.py:65-72 apply_channel_mixing and
  * SVHN.py:78-86 apply_channel_coupling (both reduce to this).  M: (C,C) fp32 row-major.
- * u,out: (B,C,HW) of io_dtype; out must not alias u. */
+ * u,out: (B,C,HW) of io_dtype; out must not alias u.  With PDE_IO_F16 (the float16 route, where M is an fp16 parameter)
+ * M is expected to hold fp16 values: at C = 64 and 128 the products run on the fp16 matrix cores with M rounded to fp16,
+ * as torch's fp16 matmul takes it; every other width multiplies by the fp32 values given. */
 int pde_channel_mix_forward(int32_t B, int32_t C, int32_t HW, int32_t io_dtype,
                             const void* u, const float* M, void* out, void* stream);
 /* gu[b,j,p] = sum_i M[i,j] gout[b,i,p];  gM[i,j] = sum_{b,p} gout[b,i,p] u[b,j,p].
@@ -367,7 +371,8 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
 /* emotion_recognition.py:82-97: reflect-pad once, nt Jacobi updates of the interior with
  * row coefficients a_row[H] (multiplying the second difference along H) and column
  * coefficients b_col[W] (along W); the padded ring keeps its initial values.
- * u,out: (B,H,W) fp32 (the layer is single-channel).  H,W <= 64. */
+ * u,out: (B,H,W) fp32 (the layer is single-channel).  H,W <= 64.  pde_jacobi_io_*: the same with u, out, gout, gu of
+ * io_dtype (PDE_IO_F32 | PDE_IO_BF16 | PDE_IO_F16); the time loop stays fp32 in LDS. */
 int pde_jacobi_forward(int32_t B, int32_t H, int32_t W, int32_t nt,
                        const float* u, const float* a_row, const float* b_col,
                        float* out, void* stream);
@@ -378,6 +383,13 @@ int pde_jacobi_backward(int32_t B, int32_t H, int32_t W, int32_t nt,
                         const float* a_row, const float* b_col,
                         float* gu, float* g_a_row, float* g_b_col,
                         void* workspace, size_t workspace_bytes, void* stream);
+int pde_jacobi_io_forward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype,
+                          const void* u, const float* a_row, const float* b_col, void* out, void* stream);
+size_t pde_jacobi_io_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype);
+int pde_jacobi_io_backward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype,
+                           const void* u, const void* gout, const float* a_row, const float* b_col,
+                           void* gu, float* g_a_row, float* g_b_col,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Ruthotto-Haber symmetric layer on the fp32 matrix cores ------------- */
 
