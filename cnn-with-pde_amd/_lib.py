@@ -14,6 +14,8 @@ PDE_MAX_SWEEPS = 96
 PDE_MAX_N = 32
 PDE_IO_F32, PDE_IO_BF16, PDE_IO_F64, PDE_IO_F16 = 0, 1, 2, 3
 PDE_AXIS_X, PDE_AXIS_Y = 0, 1
+PDE_JACOBI_MAX_HW = 1024
+PDE_JACOBI_TILED_K = 10
 
 ERRORS = {
     -1: "PDE_E_BADARG (null pointer, bad dimension or enum)",
@@ -122,6 +124,9 @@ SIGNATURES = {
     "pde_jacobi_forward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _vp]),
     "pde_jacobi_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "pde_jacobi_backward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "pde_jacobi_plane_path": (C.c_int, [_i32, _i32]),
+    "pde_jacobi_forward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "pde_jacobi_io_forward_ws": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _vp, _vp, _sz, _vp]),
     "pde_jacobi_io_forward": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _vp, _vp]),
     "pde_jacobi_io_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "pde_jacobi_io_backward": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _fp, _fp, _vp, _fp, _fp, _vp, _sz, _vp]),

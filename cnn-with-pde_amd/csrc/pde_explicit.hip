@@ -18,9 +18,10 @@
 //
 // jacobi: emotion_recognition.py:82-97, P = reflect_pad(u); nt times
 //     P_int += A_i (P[i+1,j]-2P[i,j]+P[i-1,j]) + B_j (P[i,j+1]-2P[i,j]+P[i,j-1]); ring frozen.
-//   One workgroup per sample, the padded plane lives in LDS for the whole time loop.
+//   H, W <= 64: one workgroup per sample, the padded plane lives in LDS for the whole time loop.
 //   Backward recomputes the forward, parking each state in the workspace, then walks the
 //   adjoint back, accumulating dA_i, dB_j per sample; a second kernel sums over samples.
+//   Larger planes (up to PDE_JACOBI_MAX_HW): the tiled kernels of pde_jacobi_tiled.h.
 #include "pde_common.h"
 
 namespace pde {
@@ -524,6 +525,88 @@ __global__ void jacobi_pgrad_kernel(const float* __restrict__ part, float* __res
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
+#include "pde_jacobi_tiled.h"
+
+// 0: not served, 1: the one-workgroup kernels above, 2: the tiled kernels
+int jacobi_path(int H, int W) {
+    if (H < 4 || W < 4 || H > PDE_JACOBI_MAX_HW || W > PDE_JACOBI_MAX_HW) return 0;
+    return (H <= kJMax && W <= kJMax) ? 1 : 2;
+}
+// the tiled path's grid: one workgroup per (sample, tile), in an int
+bool jacobi_tiled_grid_ok(int B, int H, int W) { return (size_t)B * jtiles(H) * jtiles(W) <= 0x7fffffffu; }
+
+struct JTiledWs {       // the tiled backward's workspace: parked states 1..nt-1, two padded adjoint images, tile sums
+    size_t states, gimg, part;
+    size_t total() const { return states + 2 * gimg + part; }
+};
+JTiledWs jacobi_tiled_ws(int B, int H, int W, int nt) {
+    JTiledWs w;
+    w.states = align256((size_t)(nt > 1 ? nt - 1 : 0) * B * H * W * sizeof(float));
+    w.gimg = align256((size_t)B * (H + 2) * (W + 2) * sizeof(float));
+    w.part = align256((size_t)B * jtiles(H) * jtiles(W) * 2 * kJT * sizeof(float));
+    return w;
+}
+
+template <typename IO>
+int jacobi_tiled_forward(int B, int H, int W, int nt, const void* u, const float* a_row, const float* b_col, void* out,
+                         void* workspace, hipStream_t st) {
+    const int nTy = jtiles(H), nTx = jtiles(W);
+    const dim3 grid((unsigned)((size_t)B * nTy * nTx));
+    float* img[2] = {static_cast<float*>(workspace),
+                     workspace ? reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)B * H * W * sizeof(float)))
+                               : nullptr};
+    int n0 = 0, l = 0;
+    do {                                                    // nt = 0: one launch of no steps copies
+        const int k = nt - n0 < kJK ? nt - n0 : kJK;
+        const bool last = n0 + k == nt;
+        hipLaunchKernelGGL(jacobi_tiled_fwd_kernel<IO>, grid, dim3(256), 0, st, (const IO*)u,
+                           l == 0 ? (const float*)nullptr : (const float*)img[(l - 1) & 1], a_row, b_col,
+                           last ? out : (void*)img[l & 1], last ? 0 : 1, (float*)nullptr, (size_t)0, H, W, nTy, nTx, k);
+        n0 += k;
+        ++l;
+    } while (n0 < nt);
+    return check_launch();
+}
+
+template <typename IO>
+int jacobi_tiled_backward(int B, int H, int W, int nt, const void* u, const void* gout, const float* a_row,
+                          const float* b_col, void* gu, float* g_a_row, float* g_b_col, void* workspace, hipStream_t st) {
+    static unsigned long long configured = 0;
+    const size_t lds = kJBwdFloats * sizeof(float);
+    if (ensure_dynamic_lds(reinterpret_cast<const void*>(jacobi_tiled_bwd_kernel<IO>), (int)lds, configured) != PDE_OK)
+        return PDE_E_LAUNCH;
+    const int nTy = jtiles(H), nTx = jtiles(W);
+    const dim3 grid((unsigned)((size_t)B * nTy * nTx));
+    const JTiledWs w = jacobi_tiled_ws(B, H, W, nt);
+    char* base = static_cast<char*>(workspace);
+    float* states = reinterpret_cast<float*>(base);
+    float* gimg[2] = {reinterpret_cast<float*>(base + w.states), reinterpret_cast<float*>(base + w.states + w.gimg)};
+    float* part = reinterpret_cast<float*>(base + w.states + 2 * w.gimg);
+    const size_t stride = (size_t)B * H * W;
+    // forward again, parking P_1 .. P_{nt-1}; every launch continues from the last state the one before parked
+    for (int n0 = 0; n0 < nt - 1; n0 += kJK) {
+        const int k = nt - 1 - n0 < kJK ? nt - 1 - n0 : kJK;
+        hipLaunchKernelGGL(jacobi_tiled_fwd_kernel<IO>, grid, dim3(256), 0, st, (const IO*)u,
+                           n0 == 0 ? (const float*)nullptr : (const float*)(states + (size_t)(n0 - 1) * stride), a_row, b_col,
+                           (void*)nullptr, 0, states + (size_t)n0 * stride, stride, H, W, nTy, nTx, k);
+    }
+    int n_hi = nt, l = 0;
+    do {                                                    // nt = 0: one launch of no steps pads gout
+        const int k = n_hi < kJK ? n_hi : kJK;
+        hipLaunchKernelGGL(jacobi_tiled_bwd_kernel<IO>, grid, dim3(256), lds, st, (const IO*)u, (const float*)states, stride,
+                           l == 0 ? (const IO*)gout : (const IO*)nullptr, (const float*)gimg[(l + 1) & 1], gimg[l & 1], a_row,
+                           b_col, part, l == 0 ? 0 : 1, H, W, nTy, nTx, n_hi, k);
+        n_hi -= k;
+        ++l;
+    } while (n_hi > 0);
+    const int nRb = (H + 31) / 32, nCb = (W + 31) / 32;
+    hipLaunchKernelGGL(jacobi_tiled_fold_kernel<IO>, dim3((unsigned)((size_t)B * nRb * nCb)), dim3(256), 0, st,
+                       (const float*)gimg[(l - 1) & 1], (IO*)gu, H, W, nRb, nCb);
+    hipLaunchKernelGGL(jacobi_tiled_pgrad_kernel, dim3((H + W + 63) / 64), dim3(64), 0, st, (const float*)part, g_a_row,
+                       g_b_col, B, H, W, nTy, nTx);
+    return check_launch();
+}
+
 // One step of the generic-size path: the tensors of the call are of type T (float, bf16e, f16e) — the layer's input is
 // read in the first step, its output written in the last; what passes between the steps is fp32.
 struct ExArgs {
@@ -662,18 +745,38 @@ static size_t jacobi_lds(int H, int W, bool bwd) {
     return (2 * PN + (bwd ? 2 : 1) * (H + W)) * sizeof(float);
 }
 
+int pde_jacobi_plane_path(int32_t H, int32_t W) { return jacobi_path(H, W); }
+
 int pde_jacobi_forward(int32_t B, int32_t H, int32_t W, int32_t nt, const float* u, const float* a_row,
                        const float* b_col, float* out, void* stream) {
-    if (B <= 0 || H < 4 || W < 4 || H > kJMax || W > kJMax || nt < 0 || !u || !a_row || !b_col || !out)
-        return PDE_E_BADARG;
-    return pde_jacobi_io_forward(B, H, W, nt, PDE_IO_F32, u, a_row, b_col, out, stream);
+    return pde_jacobi_io_forward_ws(B, H, W, nt, PDE_IO_F32, u, a_row, b_col, out, nullptr, 0, stream);
 }
 
 int pde_jacobi_io_forward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u, const float* a_row,
                           const float* b_col, void* out, void* stream) {
-    if (B <= 0 || H < 4 || W < 4 || H > kJMax || W > kJMax || nt < 0 || !u || !a_row || !b_col || !out)
-        return PDE_E_BADARG;
+    return pde_jacobi_io_forward_ws(B, H, W, nt, io_dtype, u, a_row, b_col, out, nullptr, 0, stream);
+}
+
+size_t pde_jacobi_forward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt) {
+    if (B <= 0 || nt <= kJK || jacobi_path(H, W) != 2) return 0;
+    return 2 * align256((size_t)B * H * W * sizeof(float));     // two fp32 images for the launches to alternate between
+}
+
+int pde_jacobi_io_forward_ws(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u,
+                             const float* a_row, const float* b_col, void* out, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    const int path = jacobi_path(H, W);
+    if (B <= 0 || path == 0 || nt < 0 || !u || !a_row || !b_col || !out) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (path == 2) {
+        if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+        if (!jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
+        const size_t need = pde_jacobi_forward_workspace_bytes(B, H, W, nt);
+        if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))) return PDE_E_WORKSPACE;
+        if (io_dtype == PDE_IO_F32) return jacobi_tiled_forward<float>(B, H, W, nt, u, a_row, b_col, out, workspace, st);
+        if (io_dtype == PDE_IO_BF16) return jacobi_tiled_forward<bf16e>(B, H, W, nt, u, a_row, b_col, out, workspace, st);
+        return jacobi_tiled_forward<f16e>(B, H, W, nt, u, a_row, b_col, out, workspace, st);
+    }
     const size_t lds = jacobi_lds(H, W, false);
     if (io_dtype == PDE_IO_F32)
         hipLaunchKernelGGL(jacobi_fwd_kernel<float>, dim3(B), dim3(256), lds, st, (const float*)u, a_row, b_col, (float*)out, H, W, nt);
@@ -688,6 +791,7 @@ int pde_jacobi_io_forward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t i
 
 size_t pde_jacobi_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt) {
     if (B <= 0 || H <= 0 || W <= 0 || nt < 0) return 0;
+    if (H > kJMax || W > kJMax) return jacobi_path(H, W) == 2 ? jacobi_tiled_ws(B, H, W, nt).total() : 0;
     const size_t PN = (size_t)(H + 2) * (W + 2);
     return align256((size_t)B * nt * PN * sizeof(float)) + align256((size_t)B * (H + W) * sizeof(float));
 }
@@ -707,12 +811,21 @@ int pde_jacobi_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const float
 int pde_jacobi_io_backward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u, const void* gout,
                            const float* a_row, const float* b_col, void* gu, float* g_a_row, float* g_b_col,
                            void* workspace, size_t workspace_bytes, void* stream) {
-    if (B <= 0 || H < 4 || W < 4 || H > kJMax || W > kJMax || nt < 0 || !u || !gout || !a_row || !b_col || !gu ||
-        !g_a_row || !g_b_col || !workspace)
+    const int path = jacobi_path(H, W);
+    if (B <= 0 || path == 0 || nt < 0 || !u || !gout || !a_row || !b_col || !gu || !g_a_row || !g_b_col || !workspace)
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     if (workspace_bytes < pde_jacobi_backward_workspace_bytes(B, H, W, nt)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (path == 2) {
+        if (!jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
+        if ((uintptr_t)workspace & 3) return PDE_E_WORKSPACE;
+        if (io_dtype == PDE_IO_F32)
+            return jacobi_tiled_backward<float>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, st);
+        if (io_dtype == PDE_IO_BF16)
+            return jacobi_tiled_backward<bf16e>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, st);
+        return jacobi_tiled_backward<f16e>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, st);
+    }
     const size_t PN = (size_t)(H + 2) * (W + 2);
     float* states = static_cast<float*>(workspace);
     float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)B * nt * PN * sizeof(float)));

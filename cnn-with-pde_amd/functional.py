@@ -1378,7 +1378,13 @@ class _JacobiFn(torch.autograd.Function):
         b = b_col.detach().float().contiguous()
         out = torch.empty_like(u)
         with torch.cuda.device(u.device):
-            if u.dtype == torch.float16:
+            fws = lib.pde_jacobi_forward_workspace_bytes(B, H, W, nt)
+            if fws:     # a tiled plane with more steps than one launch takes: the launches chain through a workspace
+                ws = _workspace(fws, u.device)
+                L.check(lib.pde_jacobi_io_forward_ws(B, H, W, nt, L.PDE_IO_F16 if u.dtype == torch.float16 else L.PDE_IO_F32,
+                                                     _ptr(u), _ptr(a), _ptr(b), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+                        "pde_jacobi_io_forward_ws")
+            elif u.dtype == torch.float16:
                 L.check(lib.pde_jacobi_io_forward(B, H, W, nt, L.PDE_IO_F16, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
                         "pde_jacobi_io_forward")
             else:

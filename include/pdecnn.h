@@ -371,8 +371,26 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
 /* emotion_recognition.py:82-97: reflect-pad once, nt Jacobi updates of the interior with
  * row coefficients a_row[H] (multiplying the second difference along H) and column
  * coefficients b_col[W] (along W); the padded ring keeps its initial values.
- * u,out: (B,H,W) fp32 (the layer is single-channel).  H,W <= 64.  pde_jacobi_io_*: the same with u, out, gout, gu of
- * io_dtype (PDE_IO_F32 | PDE_IO_BF16 | PDE_IO_F16); the time loop stays fp32 in LDS. */
+ * u,out: (B,H,W) fp32 (the layer is single-channel), 4 <= H, W <= PDE_JACOBI_MAX_HW.  pde_jacobi_io_*: the same with
+ * u, out, gout, gu of io_dtype (PDE_IO_F32 | PDE_IO_BF16 | PDE_IO_F16); the time loop stays fp32 in LDS.
+ * Planes up to 64x64 run on the one-workgroup kernels (a sample's padded plane stays in the LDS of one workgroup for
+ * the whole time loop); a plane with H > 64 or W > 64 runs on the tiled kernels: a workgroup owns a 64x64 tile of one
+ * sample and advances it PDE_JACOBI_TILED_K steps per launch on a halo of that many cells; parked states and whatever
+ * passes between launches are fp32.  The float64 entry points (pde_jacobi_f64_*) stay at H, W <= 64. */
+#define PDE_JACOBI_MAX_HW 1024
+#define PDE_JACOBI_TILED_K 10
+/* which kernels serve an (H, W) plane: 0 none (PDE_E_BADARG), 1 the one-workgroup kernels (4 <= H, W <= 64), 2 the
+ * tiled kernels (up to PDE_JACOBI_MAX_HW).  The tiled kernels advance K = PDE_JACOBI_TILED_K = 10 time steps per
+ * launch: a forward of nt steps is ceil(nt / K) launches. */
+int pde_jacobi_plane_path(int32_t H, int32_t W);
+/* Tiled planes with nt > PDE_JACOBI_TILED_K: the launches of one forward hand the state on through two fp32 images,
+ * which pde_jacobi_io_forward_ws takes as `workspace` (pde_jacobi_forward_workspace_bytes; 0 for every other call, and
+ * workspace may then be NULL).  pde_jacobi_forward / pde_jacobi_io_forward are this call without a workspace: they
+ * serve every plane up to nt = PDE_JACOBI_TILED_K on the tiled path and return PDE_E_WORKSPACE beyond. */
+size_t pde_jacobi_forward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt);
+int pde_jacobi_io_forward_ws(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype,
+                             const void* u, const float* a_row, const float* b_col, void* out,
+                             void* workspace, size_t workspace_bytes, void* stream);
 int pde_jacobi_forward(int32_t B, int32_t H, int32_t W, int32_t nt,
                        const float* u, const float* a_row, const float* b_col,
                        float* out, void* stream);
@@ -527,7 +545,7 @@ int pde_explicit5_f64_backward(int32_t B, int32_t C, int32_t H, int32_t W, const
                                double* gu, double* g_alpha_base, double* g_channel_scaling,
                                void* workspace, size_t workspace_bytes, void* stream);
 
-/* pde_jacobi_* in float64, 2 <= H, W <= 64. */
+/* pde_jacobi_* in float64, 2 <= H, W <= 64 (the one-workgroup kernels only: no tiled path in float64). */
 int pde_jacobi_f64_forward(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* a_row,
                            const double* b_col, double* out, void* stream);
 size_t pde_jacobi_f64_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt);
