@@ -8,7 +8,8 @@
 //   rows of one float4 each), so every element is loaded from memory exactly once; east/west neighbours come
 //   from the neighbouring lane by DPP wave shifts, north/south from the lane's own registers, the two halo rows
 //   of a row group from the lanes W/4 away (__shfl); num_steps > 1 stay in registers between the steps.  Other
-//   plane sizes take the generic kernel (neighbours through L1/L2), one launch per step.
+//   plane sizes (any H, W >= 1) take the generic kernel (neighbours through L1/L2), one launch per step: in float4
+//   columns when W is a multiple of 4, in single columns otherwise.
 //   Backward (Lap0 is self-adjoint):
 //     gu   = (1-relax) g + relax*s_c*(g + a_c dt Lap0 g)
 //     gs_c = relax * sum (g + a_c dt Lap0 g) u
@@ -174,6 +175,71 @@ __global__ __launch_bounds__(256) void explicit5_bwd_kernel(const TU* __restrict
         V4<TO>::st(op + (size_t)h * W + w0, o);
         p1 += cg.x * cu.x + cg.y * cu.y + cg.z * cu.z + cg.w * cu.w;
         p2 += lg.x * cu.x + lg.y * cu.y + lg.z * cu.z + lg.w * cu.w;
+    }
+    const float s1 = block_sum_256(p1, sh);
+    const float s2 = block_sum_256(p2, sh);
+    if (threadIdx.x == 0) {
+        part[2 * (size_t)pc] = accumulate ? part[2 * (size_t)pc] + s1 : s1;
+        part[2 * (size_t)pc + 1] = accumulate ? part[2 * (size_t)pc + 1] + s2 : s2;
+    }
+}
+
+// Scalar-column variants for widths that are not a multiple of 4: a row then starts at any element, not on a 16-byte
+// boundary, so the float4 body above cannot simply get a tail.  One element per thread and pass, the same expressions
+// in the same order as lap0_4 and the kernels above.
+template <typename IO>
+__device__ __forceinline__ float lap0_1(const IO* plane, int H, int W, int h, int w, float c) {
+    const float n = (h > 0) ? S1<IO>::ld(plane + (size_t)(h - 1) * W + w) : 0.f;
+    const float s = (h + 1 < H) ? S1<IO>::ld(plane + (size_t)(h + 1) * W + w) : 0.f;
+    const float l = (w > 0) ? S1<IO>::ld(plane + (size_t)h * W + w - 1) : 0.f;
+    const float r = (w + 1 < W) ? S1<IO>::ld(plane + (size_t)h * W + w + 1) : 0.f;
+    return n + s + l + r - 4.f * c;
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void explicit5_fwd_col_kernel(const TI* __restrict__ u, const float* __restrict__ alpha,
+                                                                const float* __restrict__ scale, TO* __restrict__ out,
+                                                                int C, int H, int W, float dt, float eps, float maxc,
+                                                                float relax) {
+    const int pc = blockIdx.x;
+    const int c = pc % C;
+    const float a = fminf(fmaxf(alpha[c], eps), maxc) * dt;
+    const float s = scale[c];
+    const TI* plane = u + (size_t)pc * H * W;
+    TO* oplane = out + (size_t)pc * H * W;
+    for (int f = threadIdx.x; f < H * W; f += 256) {
+        const int h = f / W, w = f % W;
+        const float cu = S1<TI>::ld(plane + f);
+        const float lp = lap0_1<TI>(plane, H, W, h, w, cu);
+        const float v = s * cu;
+        const float nw = v + a * (s * lp);
+        S1<TO>::st(oplane + f, cu + relax * (nw - cu));
+    }
+}
+
+template <typename TU, typename TG, typename TO>
+__global__ __launch_bounds__(256) void explicit5_bwd_col_kernel(const TU* __restrict__ u, const TG* __restrict__ g,
+                                                                const float* __restrict__ alpha,
+                                                                const float* __restrict__ scale, TO* __restrict__ gu,
+                                                                float* __restrict__ part, int C, int H, int W, float dt,
+                                                                float eps, float maxc, float relax, int accumulate) {
+    __shared__ float sh[4];
+    const int pc = blockIdx.x;
+    const int c = pc % C;
+    const float a = fminf(fmaxf(alpha[c], eps), maxc) * dt;
+    const float s = scale[c];
+    const TU* up = u + (size_t)pc * H * W;
+    const TG* gp = g + (size_t)pc * H * W;
+    TO* op = gu + (size_t)pc * H * W;
+    float p1 = 0.f, p2 = 0.f;                          // sum g*u, sum Lap0(g)*u
+    for (int f = threadIdx.x; f < H * W; f += 256) {
+        const int h = f / W, w = f % W;
+        const float cg = S1<TG>::ld(gp + f);
+        const float cu = S1<TU>::ld(up + f);
+        const float lg = lap0_1<TG>(gp, H, W, h, w, cg);
+        S1<TO>::st(op + f, (1.f - relax) * cg + relax * s * (cg + a * lg));
+        p1 += cg * cu;
+        p2 += lg * cu;
     }
     const float s1 = block_sum_256(p1, sh);
     const float s2 = block_sum_256(p2, sh);
@@ -616,8 +682,12 @@ struct ExArgs {
 };
 template <typename TI, typename TO>
 void ex_fwd(const ExArgs& a, const void* src, void* dst, hipStream_t st) {
-    hipLaunchKernelGGL((explicit5_fwd_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha, a.scale,
-                       (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax);
+    if (a.W % 4)                                           // rows not 16-byte aligned: the scalar-column variant
+        hipLaunchKernelGGL((explicit5_fwd_col_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha,
+                           a.scale, (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax);
+    else
+        hipLaunchKernelGGL((explicit5_fwd_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha, a.scale,
+                           (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax);
 }
 template <typename T>
 void ex_fwd_step(const ExArgs& a, bool first, bool last, const void* src, void* dst, hipStream_t st) {
@@ -630,8 +700,12 @@ void ex_fwd_step(const ExArgs& a, bool first, bool last, const void* src, void* 
 // is the caller's for the last step; gu is written to the caller's tensor at the first step
 template <typename TU, typename TG, typename TO>
 void ex_bwd(const ExArgs& a, const void* up, const void* gin, void* gdst, float* part, int acc, hipStream_t st) {
-    hipLaunchKernelGGL((explicit5_bwd_kernel<TU, TG, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up, (const TG*)gin,
-                       a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc);
+    if (a.W % 4)
+        hipLaunchKernelGGL((explicit5_bwd_col_kernel<TU, TG, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up,
+                           (const TG*)gin, a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc);
+    else
+        hipLaunchKernelGGL((explicit5_bwd_kernel<TU, TG, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up, (const TG*)gin,
+                           a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc);
 }
 template <typename T>
 void ex_bwd_step(const ExArgs& a, bool ufirst, bool gfirst, const void* up, const void* gin, void* gdst, float* part, int acc,
@@ -652,7 +726,7 @@ extern "C" {
 int pde_explicit5_forward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype, const void* u,
                           const float* alpha_base, const float* channel_scaling, float dt, float eps, float max_coeff,
                           float relax, int32_t num_steps, void* states, void* out, void* stream) {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (W % 4) != 0 || num_steps < 1 || !u || !alpha_base || !channel_scaling || !out)
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !alpha_base || !channel_scaling || !out)
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -698,7 +772,7 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
                            float dt, float eps, float max_coeff, float relax, int32_t num_steps, void* gu,
                            float* g_alpha_base, float* g_channel_scaling, void* workspace, size_t workspace_bytes,
                            void* stream) {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (W % 4) != 0 || num_steps < 1 || !u || !gout || !alpha_base ||
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !gout || !alpha_base ||
         !channel_scaling || !gu || !g_alpha_base || !g_channel_scaling || !workspace || (num_steps > 1 && !states))
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;

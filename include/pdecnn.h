@@ -349,7 +349,10 @@ int pde_bn_pool_backward(int32_t B, int32_t C, int32_t N, const float* x, const 
 /* tiny_imagenet.py:34-72: `num_steps` relaxed explicit steps (the reference's loop :44-49), each
  *   a_c = clamp(alpha_base_c, eps, max_coeff);  v = s_c u;
  *   u <- u + relax*(v + a_c*dt*Lap0(v) - u)      (Lap0: zero ghost cells, padding=1)
- * u,out: (B,C,H,W) of io_dtype.  states: NULL, or room for (num_steps-1) FP32 tensors of u's shape (whatever io_dtype:
+ * u,out: (B,C,H,W) of io_dtype (PDE_IO_F32 | PDE_IO_BF16 | PDE_IO_F16), any plane with H >= 1 and W >= 1 (H or W <= 0:
+ * PDE_E_BADARG): 64x64, 32x32 and 16x16 run on the wave-per-plane kernels, every other plane on the generic kernel — in
+ * float4 columns when W is a multiple of 4, in single columns otherwise (rows then start off a 16-byte boundary; this
+ * variant is a correctness path and has not been timed).  states: NULL, or room for (num_steps-1) FP32 tensors of u's shape (whatever io_dtype:
  * with bf16 tensors only the layer's own input, output and gradients are bf16) that receive the inputs of steps
  * 2..num_steps (what pde_explicit5_backward needs); required for num_steps > 1 unless the plane is 64x64, 32x32 or 16x16
  * (those stay in registers over all steps, one launch). */

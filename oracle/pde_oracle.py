@@ -254,8 +254,9 @@ def adi_init_params(spec: AdiSpec, variant: str, dtype=torch.float32, gen: Optio
 # K2: explicit 5-point layers                                                  #
 # --------------------------------------------------------------------------- #
 def tiny_forward(u: torch.Tensor, params: Dict[str, torch.Tensor], dt: float = 0.01, num_steps: int = 1,
-                 eps: float = EPS, max_coeff: float = 0.15) -> torch.Tensor:
-    """tiny_imagenet.py:34-72: v = s_c u;  u <- u + 0.1 (v + a_c dt Lap0(v) - u), zero ghost cells."""
+                 eps: float = EPS, max_coeff: float = 0.15, relax: float = 0.1) -> torch.Tensor:
+    """tiny_imagenet.py:34-72: v = s_c u;  u <- u + 0.1 (v + a_c dt Lap0(v) - u), zero ghost cells.  ``relax``: the
+    0.1 of :49, which the library's entry points take as an argument."""
     C = u.shape[1]
     for _ in range(num_steps):
         a = torch.clamp(params["alpha_base"], min=eps, max=max_coeff)
@@ -263,7 +264,7 @@ def tiny_forward(u: torch.Tensor, params: Dict[str, torch.Tensor], dt: float = 0
         vp = F.pad(v, (1, 1, 1, 1))
         lap = vp[:, :, :-2, 1:-1] + vp[:, :, 2:, 1:-1] + vp[:, :, 1:-1, :-2] + vp[:, :, 1:-1, 2:] - 4 * v
         new = v + (a * dt).view(1, C, 1, 1) * lap
-        u = u + 0.1 * (new - u)
+        u = u + relax * (new - u)
     return u
 
 

@@ -62,6 +62,12 @@ def test_argument_validation_without_gpu():
     assert lib.pde_adi_forward(C.byref(d), None, None, None, None, None, None, None, None, None, None, 0, None) == -1   # null pointers
     assert lib.pde_channel_mix_forward(0, 3, 16, 0, None, None, None, None) == -1
     assert lib.pde_explicit5_forward(1, 1, 8, 6, 0, None, None, None, 0.01, 1e-6, 0.15, 0.1, 1, None, None, None) == -1
+    # any W >= 1 is served (W % 4 != 0 by the scalar-column kernels): W = 0 is refused whatever the pointers are
+    buf = (C.c_float * 64)()
+    vp, fp = C.cast(buf, C.c_void_p), C.cast(buf, C.POINTER(C.c_float))
+    assert lib.pde_explicit5_forward(1, 1, 8, 0, 0, vp, fp, fp, 0.01, 1e-6, 0.15, 0.1, 1, None, vp, None) == -1
+    assert lib.pde_explicit5_backward(1, 1, 8, 0, 0, vp, None, vp, fp, fp, 0.01, 1e-6, 0.15, 0.1, 1, vp, fp, fp, vp, 256,
+                                      None) == -1
     assert lib.pde_version().startswith(b"pdecnn-hip")
 
 
