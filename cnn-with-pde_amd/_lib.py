@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("PDECNN_LIB") or os.path.join(HERE, "lib", "libpdecnn_
 
 PDE_MAX_SWEEPS = 96
 PDE_MAX_N = 32
+PDE_MAX_N_GENERIC = 128
 PDE_IO_F32, PDE_IO_BF16, PDE_IO_F64, PDE_IO_F16 = 0, 1, 2, 3
 PDE_AXIS_X, PDE_AXIS_Y = 0, 1
 PDE_JACOBI_MAX_HW = 1024
@@ -19,8 +20,8 @@ PDE_JACOBI_TILED_K = 10
 
 ERRORS = {
     -1: "PDE_E_BADARG (null pointer, bad dimension or enum)",
-    -2: "PDE_E_UNSUPPORTED_N (line length outside [2, 128], or a per-step / one-launch entry point at a line length "
-        "without fused kernels: those exist for multiples of 4 in [8, 32])",
+    -2: "PDE_E_UNSUPPORTED_N (line length — either side of a rectangle — outside [2, 128], or a per-step / one-launch "
+        "entry point at a line length without fused kernels: those exist for multiples of 4 in [8, 32])",
     -3: "PDE_E_TOO_MANY_SWEEPS",
     -4: "PDE_E_LAUNCH (HIP launch failed)",
     -5: "PDE_E_WORKSPACE (workspace too small or misaligned)",
@@ -47,6 +48,19 @@ class PdeAdiDescF64(C.Structure):
                 ("clamp_max", C.c_double), ("eps", C.c_double), ("sweep", PdeSweepF64 * PDE_MAX_SWEEPS)]
 
 
+class PdeAdiRectDesc(C.Structure):
+    """PdeAdiDesc for a plane of H rows and W columns (the pde_adi_rect_* entry points)."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("io_dtype", C.c_int32),
+                ("num_sweeps", C.c_int32), ("smooth3", C.c_int32), ("has_clamp_max", C.c_int32),
+                ("clamp_max", C.c_float), ("eps", C.c_float), ("sweep", PdeSweep * PDE_MAX_SWEEPS)]
+
+
+class PdeAdiRectDescF64(C.Structure):
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("io_dtype", C.c_int32),
+                ("num_sweeps", C.c_int32), ("smooth3", C.c_int32), ("has_clamp_max", C.c_int32),
+                ("clamp_max", C.c_double), ("eps", C.c_double), ("sweep", PdeSweepF64 * PDE_MAX_SWEEPS)]
+
+
 class PdeSmallLayer(C.Structure):
     """One of the layers that share an input in pde_adi_multi_* (include/pdecnn.h)."""
     _fields_ = [("desc", C.POINTER(PdeAdiDesc)), ("sweeps_per_step", C.c_int32), ("mode", C.c_int32),
@@ -68,6 +82,8 @@ class PdeError(RuntimeError):
 _vp, _fp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
 _D = C.POINTER(PdeAdiDesc)
 _D64 = C.POINTER(PdeAdiDescF64)
+_DR = C.POINTER(PdeAdiRectDesc)
+_DR64 = C.POINTER(PdeAdiRectDescF64)
 
 # name -> (restype, argtypes): must list every symbol include/pdecnn.h declares
 SIGNATURES = {
@@ -163,6 +179,19 @@ SIGNATURES = {
     "pde_jacobi_f64_forward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pde_jacobi_f64_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "pde_jacobi_f64_backward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_supported": (C.c_int, [_i32, _i32]),
+    "pde_adi_rect_forward_workspace_bytes": (_sz, [_DR]),
+    "pde_adi_rect_backward_workspace_bytes": (_sz, [_DR, _i32]),
+    "pde_adi_rect_kappa_max": (C.c_int, [_DR, _fp, _fp, _fp, _fp, _fp, _vp]),
+    "pde_adi_rect_forward": (C.c_int, [_DR, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_backward": (C.c_int, [_DR, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _fp, _fp, _fp, _fp,
+                                        _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_f64_forward_workspace_bytes": (_sz, [_DR64]),
+    "pde_adi_rect_f64_backward_workspace_bytes": (_sz, [_DR64, _i32]),
+    "pde_adi_rect_f64_kappa_max": (C.c_int, [_DR64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pde_adi_rect_f64_forward": (C.c_int, [_DR64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_f64_backward": (C.c_int, [_DR64, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pde_timing_enable": (C.c_int, [_i32]),
     "pde_timing_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int64)]),

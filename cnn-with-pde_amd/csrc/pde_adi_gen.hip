@@ -1,12 +1,16 @@
-// K1 for ANY line length (2 <= N <= 128): the implicit sweeps of mnist_test.py:50-198 / cifar10.py:86-211 with one THREAD per
+// K1 for ANY plane (2 <= H, W <= 128): the implicit sweeps of mnist_test.py:50-198 / cifar10.py:86-211 with one THREAD per
 // line and the plane in LDS.  The fused kernels of pde_adi_dev.h hold a line in the registers of two lanes and exist for
 // N = 8, 12, ..., 32 — the sizes the reference's own call sites use; its classes take any `size` (mnist_test.py:12,
 // cifar10.py:25, SVHN.py:13), and this file is what serves the others: the reference's plain Thomas recurrences
 // (mnist_test.py:151-198) per line, the adjoint as the transposed recurrences, the state rebuilt backwards or read from
 // checkpoints exactly as the fused backward does, the clamp mask and the transposed 3-tap smoothing applied per sweep.
 // Correct and deterministic, not tuned: a plane of 64 x 64 keeps 64 threads busy.
+// The kernels take a plane of H rows and W columns: an x sweep is H lines of W unknowns, a y sweep W lines of H unknowns
+// (the reference's sweeps read B, C, H, W = u.shape and transpose for y: mnist_test.py:72,105, cifar10.py:126,152).  The
+// square entry points (PdeAdiDesc / PdeAdiDescF64, one N) call them with H = W = N; the pde_adi_rect_* entry points at the
+// end of this file (PdeAdiRectDesc / PdeAdiRectDescF64) with any H, W in [2, PDE_MAX_N_GENERIC].
 // The family is generic over the arithmetic type T: float (the PdeAdiDesc entry points of pde_adi.hip) and double (the
-// pde_adi_f64_* entry points at the end of this file, PdeAdiDescF64: schedule, clamp bounds and eps in double too).
+// pde_adi_f64_* / pde_adi_rect_f64_* entry points at the end of this file: schedule, clamp bounds and eps in double too).
 #include "pde_common.h"
 #include "pde_adi_gen.h"
 
@@ -28,10 +32,10 @@ __device__ __forceinline__ double gen_min(double a, double b) { return fmin(a, b
 template <typename T, typename SW>
 struct GenFactorArgs {
     const T *ab, *bb, *as, *bs;
-    T* fac;                                  // [S][C][kGenArr][N*N]
+    T* fac;                                  // [S][C][kGenArr][H*W]: x sweeps [k < W][line < H], y sweeps [k < H][line < W]
     GenSweep<T>* tab;                        // [S]
     T* kmax;                                 // nullptr | [S], zeroed before the launch
-    int C, N, S, smooth3, has_max;
+    int C, H, W, S, smooth3, has_max;
     T cmax, eps;
     SW sweep[PDE_MAX_SWEEPS];
 };
@@ -57,16 +61,18 @@ __device__ __forceinline__ void gen_atomic_max(double* p, double m) {
 template <typename T, typename SW>
 __global__ void gen_factor_kernel(GenFactorArgs<T, SW> a) {
     __shared__ T red[4];
-    const int s = blockIdx.x / a.C, c = blockIdx.x % a.C, N = a.N, ln = threadIdx.x;
+    const int s = blockIdx.x / a.C, c = blockIdx.x % a.C, ln = threadIdx.x;
     const SW sw = a.sweep[s];
     const int ax = sw.axis;
+    const int N = (ax == PDE_AXIS_X) ? a.W : a.H, L = (ax == PDE_AXIS_X) ? a.H : a.W;   // unknowns per line, lines
+    const size_t HW = (size_t)a.H * a.W;
     if (a.tab && c == 0 && ln == 0) a.tab[s] = GenSweep<T>{ax, sw.t, sw.delta / sw.h2, T(0)};
     T kmx = T(0);
-    if (ln < N) {
-        const T* base = (ax == PDE_AXIS_X ? a.ab : a.bb) + (size_t)c * N * N;
-        const T* slope = (ax == PDE_AXIS_X ? a.as : a.bs) + (size_t)c * N * N;
-        const int lstride = (ax == PDE_AXIS_X) ? N : 1, kstride = (ax == PDE_AXIS_X) ? 1 : N;
-        T* f = a.fac ? a.fac + ((size_t)s * a.C + c) * kGenArr * N * N : nullptr;   // nullptr: the maxima alone
+    if (ln < L) {
+        const T* base = (ax == PDE_AXIS_X ? a.ab : a.bb) + (size_t)c * HW;
+        const T* slope = (ax == PDE_AXIS_X ? a.as : a.bs) + (size_t)c * HW;
+        const int lstride = (ax == PDE_AXIS_X) ? a.W : 1, kstride = (ax == PDE_AXIS_X) ? 1 : a.W;
+        T* f = a.fac ? a.fac + ((size_t)s * a.C + c) * kGenArr * HW : nullptr;   // nullptr: the maxima alone
         auto raw = [&](int k) { const int i = ln * lstride + k * kstride; return base[i] + slope[i] * sw.t; };
         auto theta = [&](int k) {
             T th = gen_max(raw(k), a.eps);
@@ -85,11 +91,11 @@ __global__ void gen_factor_kernel(GenFactorArgs<T, SW> a) {
             const T den = (k ? b + co * cs_prev : b) + a.eps;
             const T cs = (k < N - 1) ? -co / den : T(0);
             if (f) {
-                const size_t o = (size_t)k * N + ln;
+                const size_t o = (size_t)k * L + ln;
                 f[o] = co;
-                f[(size_t)N * N + o] = cs;
-                f[(size_t)2 * N * N + o] = T(1) / den;
-                f[(size_t)3 * N * N + o] = pass ? T(1) : T(0);
+                f[HW + o] = cs;
+                f[2 * HW + o] = T(1) / den;
+                f[3 * HW + o] = pass ? T(1) : T(0);
             }
             cs_prev = cs;
             kmx = gen_max(kmx, co);
@@ -129,12 +135,12 @@ struct GenSweepArgs {
     void* out;                               // forward: y (nullptr: checkpoint pre-pass); backward: gu
     const T* fac;
     const GenSweep<T>* tab;
-    T* ckpt;                                 // [nck][B][C][N*N] in T | nullptr
-    T* part;                                 // backward: [G][C][4][N*N]
+    T* ckpt;                                 // [nck][B][C][H*W] in T | nullptr
+    T* part;                                 // backward: [G][C][4][H*W]
     unsigned long long ck[2];
-    int B, C, N, S, G;
+    int B, C, H, W, S, G;
     T eps;
-    T* xg;                                   // backward with the state plane in global memory: [G*C][N][N+1] | nullptr
+    T* xg;                                   // backward with the state plane in global memory: [G*C][H][W+1] | nullptr
 };
 
 __device__ __forceinline__ int gen_ck_bit(const unsigned long long (&ck)[2], int s) { return (int)((ck[s >> 6] >> (s & 63)) & 1ull); }
@@ -150,19 +156,20 @@ __device__ __forceinline__ int gen_ck_slot(const unsigned long long (&ck)[2], in
 // zero — and a thread pays a full LDS or L2 round trip per element.)
 constexpr int kGenBatch = 8;
 
-// forward: one workgroup per plane; sweeps 0..S-1 on the plane in LDS ([row][N+1])
+// forward: one workgroup per plane; sweeps 0..S-1 on the plane in LDS ([row < H][W+1])
 template <typename TT, typename IO>
 __global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
     extern __shared__ float gen_fsmem[];
     TT* X = reinterpret_cast<TT*>(gen_fsmem);
-    const int N = a.N, ld = N + 1, tid = threadIdx.x, T = blockDim.x, NN = N * N;
+    const int W = a.W, ld = W + 1, tid = threadIdx.x, T = blockDim.x, NN = a.H * W;
     const size_t plane = (size_t)NN, pb = (size_t)blockIdx.x * plane;         // blockIdx = b*C + c
     const int c = blockIdx.x % a.C;
-    for (int e = tid; e < NN; e += T) X[(e / N) * ld + (e % N)] = GenIo<IO>::ld(a.in0, pb + e);
+    for (int e = tid; e < NN; e += T) X[(e / W) * ld + (e % W)] = GenIo<IO>::ld(a.in0, pb + e);
     __syncthreads();
     for (int s = 0; s < a.S; ++s) {
         const GenSweep<TT> sw = a.tab[s];
-        if (tid < N) {
+        const int N = (sw.axis == PDE_AXIS_X) ? W : a.H, L = (sw.axis == PDE_AXIS_X) ? a.H : W;   // unknowns per line, lines
+        if (tid < L) {
             const TT* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
             TT* v = X + (sw.axis == PDE_AXIS_X ? tid * ld : tid);
             const int st = (sw.axis == PDE_AXIS_X) ? 1 : ld;
@@ -175,8 +182,8 @@ __global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
                 for (int j = 0; j < kGenBatch; ++j) {
                     const int k = k0 + j < N ? k0 + j : N - 1;
                     t[j] = v[k * st];
-                    co[j] = f[(size_t)k * N];
-                    iv[j] = f[2 * plane + (size_t)k * N];
+                    co[j] = f[(size_t)k * L];
+                    iv[j] = f[2 * plane + (size_t)k * L];
                 }
 #pragma unroll
                 for (int j = 0; j < kGenBatch; ++j)
@@ -192,7 +199,7 @@ __global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
                 for (int j = 0; j < kGenBatch; ++j) {
                     const int k = k0 - j >= 0 ? k0 - j : 0;
                     t[j] = v[k * st];
-                    cs[j] = f[plane + (size_t)k * N];
+                    cs[j] = f[plane + (size_t)k * L];
                 }
 #pragma unroll
                 for (int j = 0; j < kGenBatch; ++j)
@@ -205,32 +212,32 @@ __global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
         __syncthreads();
         if (a.ckpt && gen_ck_bit(a.ck, s)) {
             TT* dst = a.ckpt + (size_t)gen_ck_slot(a.ck, s) * a.B * a.C * plane + pb;
-            for (int e = tid; e < NN; e += T) dst[e] = X[(e / N) * ld + (e % N)];
+            for (int e = tid; e < NN; e += T) dst[e] = X[(e / W) * ld + (e % W)];
         }
     }
     if (a.out)
-        for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.out, pb + e, X[(e / N) * ld + (e % N)]);
+        for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.out, pb + e, X[(e / W) * ld + (e % W)]);
 }
 
 // backward: workgroup (c, g) walks the planes b = g, g+G, ... of channel c; adjoint in R, state in X (both LDS);
-// parameter-gradient partial sums in part[g][c][arr][N*N], every entry owned by one thread of this workgroup.
+// parameter-gradient partial sums in part[g][c][arr][H*W], every entry owned by one thread of this workgroup.
 // ALDS: the four partial-sum images live in LDS beside the two planes and go to `part` once, at the end (chosen while four
 // workgroups still fit on a CU, see the launch); otherwise every update is a read-modify-write of global memory by the
 // owning thread.
-// XG (T = double, N beyond the two-plane LDS limit): the state plane X lives in a global scratch slice the workgroup owns,
+// XG (two planes beyond the LDS limit: T = double at 128 x 128): the state plane X lives in a global scratch slice the workgroup owns,
 // the adjoint plane R stays in LDS.
 template <typename TT, typename IO, bool ALDS, bool XG>
 __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
     extern __shared__ float gen_smem[];
-    const int N = a.N, ld = N + 1, tid = threadIdx.x, T = blockDim.x, NN = N * N;
-    TT* X = XG ? a.xg + (size_t)blockIdx.x * N * ld : reinterpret_cast<TT*>(gen_smem);
-    TT* R = XG ? reinterpret_cast<TT*>(gen_smem) : X + (size_t)N * ld;
-    TT* ACC = R + (size_t)N * ld;                         // ALDS: [4][N][ld], indexed like the planes
+    const int H = a.H, W = a.W, ld = W + 1, tid = threadIdx.x, T = blockDim.x, NN = H * W;
+    TT* X = XG ? a.xg + (size_t)blockIdx.x * H * ld : reinterpret_cast<TT*>(gen_smem);
+    TT* R = XG ? reinterpret_cast<TT*>(gen_smem) : X + (size_t)H * ld;
+    TT* ACC = R + (size_t)H * ld;                         // ALDS: [4][H][ld], indexed like the planes
     const size_t plane = (size_t)NN;
     const int c = blockIdx.x % a.C, g = blockIdx.x / a.C;
     TT* part = a.part + ((size_t)g * a.C + c) * 4 * plane;
     if constexpr (ALDS) {
-        for (int e = tid; e < 4 * N * ld; e += T) ACC[e] = TT(0);
+        for (int e = tid; e < 4 * H * ld; e += T) ACC[e] = TT(0);
     } else {
         for (size_t e = tid; e < 4 * plane; e += T) part[e] = TT(0);
     }
@@ -239,15 +246,16 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
         const size_t pb = ((size_t)b * a.C + c) * plane;
         __syncthreads();
         for (int e = tid; e < NN; e += T) {
-            R[(e / N) * ld + (e % N)] = GenIo<IO>::ld(a.in0, pb + e);
-            X[(e / N) * ld + (e % N)] = GenIo<IO>::ld(a.in1, pb + e);
+            R[(e / W) * ld + (e % W)] = GenIo<IO>::ld(a.in0, pb + e);
+            X[(e / W) * ld + (e % W)] = GenIo<IO>::ld(a.in1, pb + e);
         }
         __syncthreads();
         for (int s = a.S - 1; s >= 0; --s) {
             const GenSweep<TT> sw = a.tab[s];
-            if (tid < N) {
+            const bool xs = sw.axis == PDE_AXIS_X;
+            const int N = xs ? W : H, L = xs ? H : W;             // unknowns per line, lines
+            if (tid < L) {
                 const TT* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
-                const bool xs = sw.axis == PDE_AXIS_X;
                 TT* r = R + (xs ? tid * ld : tid);
                 TT* x = X + (xs ? tid * ld : tid);
                 const int st = xs ? 1 : ld;
@@ -259,7 +267,7 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
                     for (int j = 0; j < kGenBatch; ++j) {
                         const int k = k0 + j < N ? k0 + j : N - 1;
                         t[j] = r[k * st];
-                        cs[j] = f[plane + (size_t)(k - 1) * N];
+                        cs[j] = f[plane + (size_t)(k - 1) * L];
                     }
 #pragma unroll
                     for (int j = 0; j < kGenBatch; ++j)
@@ -268,7 +276,7 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
                     for (int j = 0; j < kGenBatch; ++j)
                         if (k0 + j < N) r[(k0 + j) * st] = t[j];
                 }
-                prev = prev * f[2 * plane + (size_t)(N - 1) * N];
+                prev = prev * f[2 * plane + (size_t)(N - 1) * L];
                 r[(N - 1) * st] = prev;
                 for (int k0 = N - 2; k0 >= 0; k0 -= kGenBatch) {
                     TT t[kGenBatch], co[kGenBatch], iv[kGenBatch];
@@ -276,8 +284,8 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
                     for (int j = 0; j < kGenBatch; ++j) {
                         const int k = k0 - j >= 0 ? k0 - j : 0;
                         t[j] = r[k * st];
-                        co[j] = f[(size_t)(k + 1) * N];
-                        iv[j] = f[2 * plane + (size_t)k * N];
+                        co[j] = f[(size_t)(k + 1) * L];
+                        iv[j] = f[2 * plane + (size_t)k * L];
                     }
 #pragma unroll
                     for (int j = 0; j < kGenBatch; ++j)
@@ -293,13 +301,13 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
                 TT* __restrict__ pslope = pbase + plane;
                 // partial sums in global memory are kept [k][line] for BOTH axes (threads of a wave then touch consecutive
                 // words; [line][k] made every x-sweep update a cache line of its own): the alpha images are stored
-                // transposed and gen_reduce_kernel turns them back
-                const int pl = tid, pk = N;
-                TT* lbase = ACC + (xs ? 0 : 2) * N * ld + (xs ? tid * ld : tid);
+                // transposed ([k < W][line < H]) and gen_reduce_kernel turns them back
+                const int pl = tid, pk = L;
+                TT* lbase = ACC + (xs ? 0 : 2) * H * ld + (xs ? tid * ld : tid);
                 auto add = [&](int j, TT gv) __attribute__((always_inline)) {
                     if constexpr (ALDS) {
                         lbase[j * st] += gv;
-                        lbase[N * ld + j * st] += sw.t * gv;
+                        lbase[H * ld + j * st] += sw.t * gv;
                     } else {
                         pbase[pl + j * pk] += gv;
                         pslope[pl + j * pk] += sw.t * gv;
@@ -313,10 +321,10 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
                         const int k = k0 + j < N ? k0 + j : N - 1;
                         xn[j] = (k0 + j + 1 < N) ? x[(k0 + j + 1) * st] : TT(0);    // x_{k+1}
                         lam[j] = r[k * st];
-                        co[j] = f[(size_t)k * N];
-                        ps[j] = f[3 * plane + (size_t)k * N];
+                        co[j] = f[(size_t)k * L];
+                        ps[j] = f[3 * plane + (size_t)k * L];
                     }
-                    const TT ps_before = k0 > 0 ? f[3 * plane + (size_t)(k0 - 1) * N] : TT(0);   // mask of entry k0-1 (smoothing)
+                    const TT ps_before = k0 > 0 ? f[3 * plane + (size_t)(k0 - 1) * L] : TT(0);   // mask of entry k0-1 (smoothing)
 #pragma unroll
                     for (int j = 0; j < kGenBatch; ++j) {
                         const int k = k0 + j;
@@ -351,32 +359,32 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
                 }
                 if (smooth3) {                                             // entry N-1: (gsm_{N-2} + 2 gsm_{N-1}) / 3
                     const TT gv = (g2 * third + g1 * third) + g1 * third;
-                    add(N - 1, gv * f[3 * plane + (size_t)(N - 1) * N]);
+                    add(N - 1, gv * f[3 * plane + (size_t)(N - 1) * L]);
                 }
             }
             __syncthreads();
             if (s > 0 && a.ckpt && gen_ck_bit(a.ck, s - 1)) {             // the parked state instead of the rebuilt one
                 const TT* src = a.ckpt + (size_t)gen_ck_slot(a.ck, s - 1) * a.B * a.C * plane + pb;
-                for (int e = tid; e < NN; e += T) X[(e / N) * ld + (e % N)] = src[e];
+                for (int e = tid; e < NN; e += T) X[(e / W) * ld + (e % W)] = src[e];
                 __syncthreads();
             }
         }
-        for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.out, pb + e, R[(e / N) * ld + (e % N)]);
+        for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.out, pb + e, R[(e / W) * ld + (e % W)]);
     }
     if constexpr (ALDS) {
         __syncthreads();
         for (int arr = 0; arr < 4; ++arr)
             for (int e = tid; e < NN; e += T)              // alpha images transposed, as above
-                part[arr * plane + e] = ACC[arr * N * ld + (arr < 2 ? (e % N) * ld + (e / N) : (e / N) * ld + (e % N))];
+                part[arr * plane + e] = ACC[arr * H * ld + (arr < 2 ? (e % H) * ld + (e / H) : (e / W) * ld + (e % W))];
     }
 }
 
 // the four parameter gradients: partial sums added over the groups in a fixed order
 template <typename T>
-__global__ void gen_reduce_kernel(const T* part, int G, int C, int N, T* g_ab, T* g_as, T* g_bb, T* g_bs) {
-    const int NN = N * N, e = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void gen_reduce_kernel(const T* part, int G, int C, int H, int W, T* g_ab, T* g_as, T* g_bb, T* g_bs) {
+    const int NN = H * W, e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= C * NN) return;
-    const int c = e / NN, p = e % NN, pt = (p % N) * N + p / N;        // the alpha images are stored transposed
+    const int c = e / NN, p = e % NN, pt = (p % W) * H + p / W;        // the alpha images are stored transposed: [W][H]
     T s[4] = {T(0), T(0), T(0), T(0)};
     for (int g = 0; g < G; ++g)
         for (int arr = 0; arr < 4; ++arr) s[arr] += part[(((size_t)g * C + c) * 4 + arr) * NN + (arr < 2 ? pt : p)];
@@ -384,8 +392,16 @@ __global__ void gen_reduce_kernel(const T* part, int G, int C, int N, T* g_ab, T
 }
 
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+// rows and columns of a descriptor's plane: the square descriptors have one N, the rectangle ones H and W
+template <typename D> int rows_of(const D* d) { return d->N; }
+template <typename D> int cols_of(const D* d) { return d->N; }
+int rows_of(const PdeAdiRectDesc* d) { return d->H; }
+int cols_of(const PdeAdiRectDesc* d) { return d->W; }
+int rows_of(const PdeAdiRectDescF64* d) { return d->H; }
+int cols_of(const PdeAdiRectDescF64* d) { return d->W; }
+template <typename D> size_t plane_of(const D* d) { return (size_t)rows_of(d) * cols_of(d); }
 template <typename T, typename D>
-size_t fac_bytes(const D* d) { return up256((size_t)d->num_sweeps * d->C * kGenArr * d->N * d->N * sizeof(T)); }
+size_t fac_bytes(const D* d) { return up256((size_t)d->num_sweeps * d->C * kGenArr * plane_of(d) * sizeof(T)); }
 template <typename T>
 size_t tab_bytes_gen() { return up256(sizeof(GenSweep<T>) * PDE_MAX_SWEEPS); }
 template <typename D>
@@ -393,19 +409,23 @@ int gen_groups(const D* d) {
     int G = (1024 + d->C - 1) / d->C;
     return G > d->B ? d->B : (G < 1 ? 1 : G);
 }
-int gen_threads(int N) { return (N + 63) / 64 * 64; }
+// one thread per line of the longer axis' count: max(H, W) lines, whole waves
+template <typename D> int gen_threads(const D* d) {
+    const int n = rows_of(d) > cols_of(d) ? rows_of(d) : cols_of(d);
+    return (n + 63) / 64 * 64;
+}
 
 constexpr int kGenLdsMax = 160 * 1024;        // the CU's LDS (two fp32 128 x 129 planes are 132 KB)
-// one plane image [N][N+1] in T; the backward keeps two of them in LDS while they fit (fp32: every N; fp64: N <= 100), else
-// the state plane goes to a global scratch slice per workgroup (bwd_xg)
-template <typename T>
-size_t gen_img(int N) { return (size_t)N * (N + 1) * sizeof(T); }
-template <typename T>
-bool bwd_xg(int N) { return 2 * gen_img<T>(N) > (size_t)kGenLdsMax; }
+// one plane image [H][W+1] in T; the backward keeps two of them in LDS while their bytes fit (fp32: every plane; fp64 squares:
+// N <= 100), else the state plane goes to a global scratch slice per workgroup (bwd_xg)
+template <typename T, typename D>
+size_t gen_img(const D* d) { return (size_t)rows_of(d) * (cols_of(d) + 1) * sizeof(T); }
+template <typename T, typename D>
+bool bwd_xg(const D* d) { return 2 * gen_img<T>(d) > (size_t)kGenLdsMax; }
 // workgroups of the backward: with the state in global memory (one workgroup per CU by its LDS) about one per CU
 template <typename T, typename D>
 int bwd_groups(const D* d) {
-    if (!bwd_xg<T>(d->N)) return gen_groups(d);
+    if (!bwd_xg<T>(d)) return gen_groups(d);
     int G = (256 + d->C - 1) / d->C;
     return G > d->B ? d->B : (G < 1 ? 1 : G);
 }
@@ -416,11 +436,11 @@ int launch_gen_factor(const D* d, const T* ab, const T* bb, const T* as, const T
     using SW = typename std::remove_cv<typename std::remove_reference<decltype(d->sweep[0])>::type>::type;
     GenFactorArgs<T, SW> fa;
     fa.ab = ab; fa.bb = bb; fa.as = as; fa.bs = bs; fa.fac = fac; fa.tab = tab; fa.kmax = kmax;
-    fa.C = d->C; fa.N = d->N; fa.S = d->num_sweeps; fa.smooth3 = d->smooth3; fa.has_max = d->has_clamp_max;
+    fa.C = d->C; fa.H = rows_of(d); fa.W = cols_of(d); fa.S = d->num_sweeps; fa.smooth3 = d->smooth3; fa.has_max = d->has_clamp_max;
     fa.cmax = d->clamp_max; fa.eps = d->eps;
     for (int s = 0; s < d->num_sweeps; ++s) fa.sweep[s] = d->sweep[s];
     if (kmax && hipMemsetAsync(kmax, 0, sizeof(T) * d->num_sweeps, st) != hipSuccess) return PDE_E_LAUNCH;
-    hipLaunchKernelGGL((gen_factor_kernel<T, SW>), dim3(d->num_sweeps * d->C), dim3(gen_threads(d->N)), 0, st, fa);
+    hipLaunchKernelGGL((gen_factor_kernel<T, SW>), dim3(d->num_sweeps * d->C), dim3(gen_threads(d)), 0, st, fa);
     return check_launch();
 }
 
@@ -433,22 +453,22 @@ int launch_gen_fwd(const D* d, const void* u, void* y, const T* fac, const GenSw
     GenSweepArgs<T> sa{};
     sa.in0 = u; sa.out = y; sa.fac = fac; sa.tab = tab; sa.ckpt = ckpt;
     sa.ck[0] = ck ? ck[0] : 0ull; sa.ck[1] = ck ? ck[1] : 0ull;
-    sa.B = d->B; sa.C = d->C; sa.N = d->N; sa.S = S; sa.eps = d->eps;
-    const size_t lds = gen_img<T>(d->N);
+    sa.B = d->B; sa.C = d->C; sa.H = rows_of(d); sa.W = cols_of(d); sa.S = S; sa.eps = d->eps;
+    const size_t lds = gen_img<T>(d);
     static unsigned long long done_f = 0, done_b = 0, done_h = 0;
     int rc;
     if constexpr (std::is_same<T, double>::value) {
         if ((rc = gen_lds(gen_fwd_kernel<double, double>, done_f)) != PDE_OK) return rc;
-        hipLaunchKernelGGL((gen_fwd_kernel<double, double>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+        hipLaunchKernelGGL((gen_fwd_kernel<double, double>), dim3(d->B * d->C), dim3(gen_threads(d)), lds, st, sa);
     } else if (d->io_dtype == PDE_IO_F32) {
         if ((rc = gen_lds(gen_fwd_kernel<float, float>, done_f)) != PDE_OK) return rc;
-        hipLaunchKernelGGL((gen_fwd_kernel<float, float>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+        hipLaunchKernelGGL((gen_fwd_kernel<float, float>), dim3(d->B * d->C), dim3(gen_threads(d)), lds, st, sa);
     } else if (d->io_dtype == PDE_IO_F16) {
         if ((rc = gen_lds(gen_fwd_kernel<float, gen_f16>, done_h)) != PDE_OK) return rc;
-        hipLaunchKernelGGL((gen_fwd_kernel<float, gen_f16>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+        hipLaunchKernelGGL((gen_fwd_kernel<float, gen_f16>), dim3(d->B * d->C), dim3(gen_threads(d)), lds, st, sa);
     } else {
         if ((rc = gen_lds(gen_fwd_kernel<float, gen_bf16>, done_b)) != PDE_OK) return rc;
-        hipLaunchKernelGGL((gen_fwd_kernel<float, gen_bf16>), dim3(d->B * d->C), dim3(gen_threads(d->N)), lds, st, sa);
+        hipLaunchKernelGGL((gen_fwd_kernel<float, gen_bf16>), dim3(d->B * d->C), dim3(gen_threads(d)), lds, st, sa);
     }
     return check_launch();
 }
@@ -459,9 +479,9 @@ size_t fwd_ws_bytes(const D* d) { return fac_bytes<T>(d) + tab_bytes_gen<T>(); }
 template <typename T, typename D>
 size_t bwd_ws_bytes(const D* d, int nck) {
     const int G = bwd_groups<T>(d);
-    return fac_bytes<T>(d) + tab_bytes_gen<T>() + up256((size_t)G * d->C * 4 * d->N * d->N * sizeof(T)) +
-           up256((size_t)nck * d->B * d->C * d->N * d->N * sizeof(T)) +
-           (bwd_xg<T>(d->N) ? up256((size_t)G * d->C * gen_img<T>(d->N)) : 0);
+    return fac_bytes<T>(d) + tab_bytes_gen<T>() + up256((size_t)G * d->C * 4 * plane_of(d) * sizeof(T)) +
+           up256((size_t)nck * d->B * d->C * plane_of(d) * sizeof(T)) +
+           (bwd_xg<T>(d) ? up256((size_t)G * d->C * gen_img<T>(d)) : 0);
 }
 
 template <typename T, typename D>
@@ -488,10 +508,10 @@ int backward_impl(const D* d, const void* gy, const void* y, const void* u, cons
     ws += fac_bytes<T>(d) + tab_bytes_gen<T>();
     const int G = bwd_groups<T>(d);
     T* part = reinterpret_cast<T*>(ws);
-    ws += up256((size_t)G * d->C * 4 * d->N * d->N * sizeof(T));
+    ws += up256((size_t)G * d->C * 4 * plane_of(d) * sizeof(T));
     T* ckpt = nck ? reinterpret_cast<T*>(ws) : nullptr;
-    ws += up256((size_t)nck * d->B * d->C * d->N * d->N * sizeof(T));
-    const bool xg = bwd_xg<T>(d->N);
+    ws += up256((size_t)nck * d->B * d->C * plane_of(d) * sizeof(T));
+    const bool xg = bwd_xg<T>(d);
     T* xplanes = xg ? reinterpret_cast<T*>(ws) : nullptr;
     int rc;
     if (fwd_workspace) {
@@ -509,13 +529,13 @@ int backward_impl(const D* d, const void* gy, const void* y, const void* u, cons
     GenSweepArgs<T> sa{};
     sa.in0 = gy; sa.in1 = y; sa.out = gu; sa.fac = fac; sa.tab = tab; sa.ckpt = ckpt; sa.part = part; sa.xg = xplanes;
     sa.ck[0] = nck ? ckpt_mask[0] : 0ull; sa.ck[1] = nck ? ckpt_mask[1] : 0ull;
-    sa.B = d->B; sa.C = d->C; sa.N = d->N; sa.S = d->num_sweeps; sa.G = G; sa.eps = d->eps;
-    const size_t img = gen_img<T>(d->N);
-    // the partial sums beside the planes while four workgroups still fit on a CU (fp32: N <= 40, fp64: N <= 28)
+    sa.B = d->B; sa.C = d->C; sa.H = rows_of(d); sa.W = cols_of(d); sa.S = d->num_sweeps; sa.G = G; sa.eps = d->eps;
+    const size_t img = gen_img<T>(d);
+    // the partial sums beside the planes while four workgroups still fit on a CU (squares: fp32 N <= 40, fp64 N <= 28)
     const bool alds = !xg && 4 * 6 * img <= (size_t)kGenLdsMax;
     const size_t lds = xg ? img : (alds ? 6 : 2) * img;
     static unsigned long long done[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const dim3 grid(G * d->C), block(gen_threads(d->N));
+    const dim3 grid(G * d->C), block(gen_threads(d));
 #define PDE_GEN_BWD(TY, IO, AL, XG, SLOT)                                                                \
     do {                                                                                                 \
         if ((rc = gen_lds(gen_bwd_kernel<TY, IO, AL, XG>, done[SLOT])) != PDE_OK) return rc;             \
@@ -534,9 +554,9 @@ int backward_impl(const D* d, const void* gy, const void* y, const void* u, cons
     }
 #undef PDE_GEN_BWD
     if ((rc = check_launch()) != PDE_OK) return rc;
-    const int NN = d->N * d->N, total = d->C * NN;
-    hipLaunchKernelGGL((gen_reduce_kernel<T>), dim3((total + 255) / 256), dim3(256), 0, st, part, G, d->C, d->N, g_ab, g_as,
-                       g_bb, g_bs);
+    const int total = d->C * (int)plane_of(d);
+    hipLaunchKernelGGL((gen_reduce_kernel<T>), dim3((total + 255) / 256), dim3(256), 0, st, part, G, d->C, rows_of(d),
+                       cols_of(d), g_ab, g_as, g_bb, g_bs);
     return check_launch();
 }
 
@@ -588,7 +608,8 @@ int check_desc_f64(const PdeAdiDescF64* d) {
 }
 
 // checkpoint mask -> (count, number of forward sweeps to recompute); PDE_E_BADARG when inconsistent
-int ckpt_plan_f64(const PdeAdiDescF64* d, const uint64_t ckpt_mask[2], const void* u, int& nck, int& Sf) {
+template <typename D>
+int ckpt_plan(const D* d, const uint64_t ckpt_mask[2], const void* u, int& nck, int& Sf) {
     nck = ckpt_mask ? __builtin_popcountll(ckpt_mask[0]) + __builtin_popcountll(ckpt_mask[1]) : 0;
     Sf = 0;
     if (nck) {
@@ -600,6 +621,73 @@ int ckpt_plan_f64(const PdeAdiDescF64* d, const uint64_t ckpt_mask[2], const voi
             }
     }
     return PDE_OK;
+}
+
+// rectangle descriptors: both sides on the any-size path's range, io_dtype of the family (T = double: PDE_IO_F64 alone)
+template <typename T, typename D>
+int check_desc_rect(const D* d) {
+    constexpr bool f64 = std::is_same<T, double>::value;
+    if (!d) return PDE_E_BADARG;
+    if (d->B <= 0 || d->C <= 0 || d->num_sweeps <= 0) return PDE_E_BADARG;
+    if (!gen_n_ok(d->H) || !gen_n_ok(d->W)) return PDE_E_UNSUPPORTED_N;
+    if (d->num_sweeps > PDE_MAX_SWEEPS) return PDE_E_TOO_MANY_SWEEPS;
+    if (f64 ? d->io_dtype != PDE_IO_F64
+            : (d->io_dtype != PDE_IO_F32 && d->io_dtype != PDE_IO_BF16 && d->io_dtype != PDE_IO_F16))
+        return PDE_E_BADARG;
+    for (int s = 0; s < d->num_sweeps; ++s)
+        if (d->sweep[s].axis != PDE_AXIS_X && d->sweep[s].axis != PDE_AXIS_Y) return PDE_E_BADARG;
+    return PDE_OK;
+}
+
+template <typename T, typename D>
+size_t rect_fwd_bytes(const D* d) { return check_desc_rect<T>(d) != PDE_OK ? 0 : fwd_ws_bytes<T>(d); }
+
+template <typename T, typename D>
+size_t rect_bwd_bytes(const D* d, int nck) {
+    if (check_desc_rect<T>(d) != PDE_OK || nck < 0 || nck >= d->num_sweeps) return 0;
+    return bwd_ws_bytes<T>(d, nck);
+}
+
+template <typename T, typename D>
+int rect_kappa_max(const D* d, const T* ab, const T* bb, const T* as, const T* bs, T* kmax, void* stream) {
+    const int rc = check_desc_rect<T>(d);
+    if (rc != PDE_OK) return rc;
+    if (!ab || !bb || !as || !bs || !kmax) return PDE_E_BADARG;
+    return launch_gen_factor<T>(d, ab, bb, as, bs, (T*)nullptr, (GenSweep<T>*)nullptr, kmax, static_cast<hipStream_t>(stream));
+}
+
+// factorisation (+ maxima), the maxima's way to the host, the sweeps
+template <typename T, typename D>
+int rect_forward(const D* d, const void* u, void* y, const T* ab, const T* bb, const T* as, const T* bs, T* kmax,
+                 T* kmax_host, void* kappa_event, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_desc_rect<T>(d);
+    if (rc != PDE_OK) return rc;
+    if (!u || !y || !ab || !bb || !as || !bs || !workspace) return PDE_E_BADARG;
+    if (kmax_host && !kmax) return PDE_E_BADARG;
+    if (workspace_bytes < fwd_ws_bytes<T>(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = factor_impl<T>(d, ab, bb, as, bs, kmax, workspace, st);
+    if (rc != PDE_OK) return rc;
+    // the maxima leave for the host right behind the factorisation kernel, before the sweep launch (as pde_adi_forward)
+    if (kmax_host && hipMemcpyAsync(kmax_host, kmax, (size_t)d->num_sweeps * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return PDE_E_LAUNCH;
+    if (kappa_event && hipEventRecord(static_cast<hipEvent_t>(kappa_event), st) != hipSuccess) return PDE_E_LAUNCH;
+    return forward_sweeps_impl<T>(d, u, y, workspace, st);
+}
+
+template <typename T, typename D>
+int rect_backward(const D* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
+                  const T* ab, const T* bb, const T* as, const T* bs, T* g_ab, T* g_bb, T* g_as, T* g_bs,
+                  const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_desc_rect<T>(d);
+    if (rc != PDE_OK) return rc;
+    if (!gy || !y || !gu || !ab || !bb || !as || !bs || !g_ab || !g_bb || !g_as || !g_bs || !workspace) return PDE_E_BADARG;
+    int nck, Sf;
+    rc = ckpt_plan(d, ckpt_mask, u, nck, Sf);
+    if (rc != PDE_OK) return rc;
+    if (workspace_bytes < bwd_ws_bytes<T>(d, nck) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    return backward_impl<T>(d, gy, y, u, ckpt_mask, nck, Sf, gu, ab, bb, as, bs, g_ab, g_bb, g_as, g_bs, fwd_workspace,
+                            workspace, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -640,12 +728,70 @@ int pde_adi_f64_backward(const PdeAdiDescF64* d, const double* gy, const double*
         !g_alpha_slope || !g_beta_slope || !workspace)
         return PDE_E_BADARG;
     int nck, Sf;
-    rc = ckpt_plan_f64(d, ckpt_mask, u, nck, Sf);
+    rc = ckpt_plan(d, ckpt_mask, u, nck, Sf);
     if (rc != PDE_OK) return rc;
     if (workspace_bytes < pde_adi_f64_backward_workspace_bytes(d, nck) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
     return backward_impl<double>(d, gy, y, u, ckpt_mask, nck, Sf, gu, alpha_base, beta_base, alpha_slope, beta_slope,
                                  g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
                                  static_cast<hipStream_t>(stream));
+}
+
+// ---- rectangular planes (include/pdecnn.h): the same kernels with H != W, fp32 / bf16 / fp16 tensors and float64 -----
+int pde_adi_rect_supported(int32_t H, int32_t W) { return (gen_n_ok(H) && gen_n_ok(W)) ? 1 : 0; }
+
+size_t pde_adi_rect_forward_workspace_bytes(const PdeAdiRectDesc* d) { return rect_fwd_bytes<float>(d); }
+
+size_t pde_adi_rect_backward_workspace_bytes(const PdeAdiRectDesc* d, int32_t num_checkpoints) {
+    return rect_bwd_bytes<float>(d, num_checkpoints);
+}
+
+int pde_adi_rect_kappa_max(const PdeAdiRectDesc* d, const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                           const float* beta_slope, float* kappa_max, void* stream) {
+    return rect_kappa_max<float>(d, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, stream);
+}
+
+int pde_adi_rect_forward(const PdeAdiRectDesc* d, const void* u, void* y, const float* alpha_base, const float* beta_base,
+                         const float* alpha_slope, const float* beta_slope, float* kappa_max, float* kappa_max_host,
+                         void* kappa_event, void* workspace, size_t workspace_bytes, void* stream) {
+    return rect_forward<float>(d, u, y, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, kappa_max_host,
+                               kappa_event, workspace, workspace_bytes, stream);
+}
+
+int pde_adi_rect_backward(const PdeAdiRectDesc* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2],
+                          void* gu, const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                          const float* beta_slope, float* g_alpha_base, float* g_beta_base, float* g_alpha_slope,
+                          float* g_beta_slope, const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    return rect_backward<float>(d, gy, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base,
+                                g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace, workspace_bytes, stream);
+}
+
+size_t pde_adi_rect_f64_forward_workspace_bytes(const PdeAdiRectDescF64* d) { return rect_fwd_bytes<double>(d); }
+
+size_t pde_adi_rect_f64_backward_workspace_bytes(const PdeAdiRectDescF64* d, int32_t num_checkpoints) {
+    return rect_bwd_bytes<double>(d, num_checkpoints);
+}
+
+int pde_adi_rect_f64_kappa_max(const PdeAdiRectDescF64* d, const double* alpha_base, const double* beta_base,
+                               const double* alpha_slope, const double* beta_slope, double* kappa_max, void* stream) {
+    return rect_kappa_max<double>(d, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, stream);
+}
+
+int pde_adi_rect_f64_forward(const PdeAdiRectDescF64* d, const double* u, double* y, const double* alpha_base,
+                             const double* beta_base, const double* alpha_slope, const double* beta_slope, double* kappa_max,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    return rect_forward<double>(d, u, y, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, (double*)nullptr,
+                                nullptr, workspace, workspace_bytes, stream);
+}
+
+int pde_adi_rect_f64_backward(const PdeAdiRectDescF64* d, const double* gy, const double* y, const double* u,
+                              const uint64_t ckpt_mask[2], double* gu, const double* alpha_base, const double* beta_base,
+                              const double* alpha_slope, const double* beta_slope, double* g_alpha_base, double* g_beta_base,
+                              double* g_alpha_slope, double* g_beta_slope, const void* fwd_workspace, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    return rect_backward<double>(d, gy, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                                 g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
+                                 workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -166,19 +166,66 @@ def _build_desc(B, Cc, N, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) 
     return d
 
 
+_rect_desc_cache = {}
+
+
+def _make_rect_desc(B, Cc, H, W, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps):
+    """The launch descriptor of a rectangular plane: PdeAdiRectDesc, or PdeAdiRectDescF64 for ``io == PDE_IO_F64``.
+    Cached like ``_make_desc``, keyed on (H, W)."""
+    if not isinstance(sweeps, tuple):
+        sweeps = tuple(sweeps)
+    key = (B, Cc, H, W, io, sweeps, bool(smooth3), clamp_max, float(eps))
+    d = _rect_desc_cache.get(key)
+    if d is None:
+        if len(sweeps) > L.PDE_MAX_SWEEPS:
+            raise L.PdeError(f"{len(sweeps)} sweeps in one launch exceed PDE_MAX_SWEEPS={L.PDE_MAX_SWEEPS}")
+        if len(_rect_desc_cache) > 256:
+            _rect_desc_cache.clear()
+        d = L.PdeAdiRectDescF64() if io == L.PDE_IO_F64 else L.PdeAdiRectDesc()
+        d.B, d.C, d.H, d.W, d.io_dtype, d.num_sweeps = B, Cc, H, W, io, len(sweeps)
+        d.smooth3 = int(bool(smooth3))
+        d.has_clamp_max = int(clamp_max is not None)
+        d.clamp_max = float(clamp_max) if clamp_max is not None else 0.0
+        d.eps = float(eps)
+        for i, s in enumerate(sweeps):
+            d.sweep[i].axis, d.sweep[i].delta, d.sweep[i].h2, d.sweep[i].t = int(s.axis), s.delta, s.h2, s.t
+        _rect_desc_cache[key] = d
+    return d
+
+
+def _is_rect(u) -> bool:
+    """A (B, C, H, W) input with H != W: served by the pde_adi_rect_* entry points (squares keep their own)."""
+    return isinstance(u, torch.Tensor) and u.dim() == 4 and u.shape[2] != u.shape[3]
+
+
+def _check_rect(u, *params):
+    """Refuse, before any launch, a rectangle the library does not hold or parameters that are not (C, H, W) / (H, W)."""
+    _require_cuda(u, *params)
+    B, Cc, H, W = u.shape
+    if not L.load().pde_adi_rect_supported(H, W):
+        raise L.PdeError(f"plane {H}x{W}: both sides must be in [2, {L.PDE_MAX_N_GENERIC}] "
+                         f"({L.ERRORS[-2]})")
+    for p in params:
+        q = tuple(p.shape)
+        if q != (Cc, H, W) and not (len(q) == 2 and Cc == 1 and q == (H, W)):
+            raise L.PdeError(f"coefficient of shape {q} does not match ({Cc},{H},{W})")
+
+
 def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
-def _as_chw(p: torch.Tensor, Cc: int, N: int) -> torch.Tensor:
-    if p.dtype == torch.float32 and p.dim() == 3 and p.shape[0] == Cc and p.shape[1] == N and p.shape[2] == N \
+def _as_chw(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.Tensor:
+    """The parameter as a contiguous fp32 (C, N, N) tensor — (C, N, W) on a rectangle."""
+    W = N if W is None else W
+    if p.dtype == torch.float32 and p.dim() == 3 and p.shape[0] == Cc and p.shape[1] == N and p.shape[2] == W \
             and p.is_contiguous():
         return p.detach()
     q = p.detach()
     if q.dim() == 2:
         q = q.unsqueeze(0)
-    if tuple(q.shape) != (Cc, N, N):
-        raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{N})")
+    if tuple(q.shape) != (Cc, N, W):
+        raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{W})")
     return q.to(torch.float32).contiguous()
 
 
@@ -209,12 +256,17 @@ def kappa_max_async(u_like, alpha_base, beta_base, alpha_time_coeff, beta_time_c
     Returns an object with ``.host`` / ``.event``; the values are valid once ``event.query()`` is True."""
     lib = L.load()
     _require_cuda(u_like, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
-    B, Cc, N, _ = u_like.shape
-    p = [_as_chw(t, Cc, N) for t in (alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)]
-    d = _make_desc(max(B, 1), Cc, N, L.PDE_IO_F32, sweeps, smooth3, clamp_max, eps)   # independent of the batch
+    B, Cc, N, W = u_like.shape
+    p = [_as_chw(t, Cc, N, W) for t in (alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)]
     kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u_like.device)
     with torch.cuda.device(u_like.device):
-        L.check(lib.pde_adi_kappa_max(C.byref(d), *[_ptr(t) for t in p], _ptr(kdev), _stream()), "pde_adi_kappa_max")
+        if N != W:                                         # a rectangle: the pde_adi_rect_* entry points
+            d = _make_rect_desc(max(B, 1), Cc, N, W, L.PDE_IO_F32, sweeps, smooth3, clamp_max, eps)
+            L.check(lib.pde_adi_rect_kappa_max(C.byref(d), *[_ptr(t) for t in p], _ptr(kdev), _stream()),
+                    "pde_adi_rect_kappa_max")
+        else:
+            d = _make_desc(max(B, 1), Cc, N, L.PDE_IO_F32, sweeps, smooth3, clamp_max, eps)   # independent of the batch
+            L.check(lib.pde_adi_kappa_max(C.byref(d), *[_ptr(t) for t in p], _ptr(kdev), _stream()), "pde_adi_kappa_max")
         host = torch.empty(len(sweeps), dtype=torch.float32, pin_memory=True)
         host.copy_(kdev, non_blocking=True)
         ev = torch.cuda.Event()
@@ -423,6 +475,78 @@ class _AdiFn(torch.autograd.Function):
         ctx.fwd_ws = None
         gp = [g.reshape(s) for g, s in zip(gp, ctx.param_shapes)]
         return (gu, *gp, None, None, None, None, None, None)
+
+
+class _AdiRectFn(torch.autograd.Function):
+    """adi_diffuse on a rectangular plane (pde_adi_rect_* / pde_adi_rect_f64_*): ``_AdiFn`` and ``_AdiF64Fn`` for
+    H != W.  ``f64``: every tensor in double, the checkpoint plan of ``_f64_ckpt_bits`` (no coefficient maxima)."""
+
+    @staticmethod
+    def forward(ctx, u, ab, bb, asl, bsl, sweeps, smooth3, clamp_max, eps, ckpt, kmax_sink, f64):
+        lib = L.load()
+        if u.dim() != 4:
+            raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
+        _check_rect(u, ab, bb, asl, bsl)
+        B, Cc, H, W = u.shape
+        if f64:
+            u = u.to(torch.float64).contiguous()
+            p = [_as_chw64(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
+            io, kt, fam = L.PDE_IO_F64, torch.float64, "pde_adi_rect_f64_"
+        else:
+            if u.dtype not in _IO_TYPES:
+                u = u.float()
+            u = u.contiguous()
+            p = [_as_chw(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
+            io, kt, fam = _io_dtype(u), torch.float32, "pde_adi_rect_"
+        d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps)
+        y = torch.empty_like(u)
+        ws = _workspace(getattr(lib, fam + "forward_workspace_bytes")(C.byref(d)), u.device)
+        need_grad = any(ctx.needs_input_grad[:5])
+        if f64:
+            ckpt = _f64_ckpt_bits(ckpt, len(sweeps))
+        want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
+        kdev = torch.empty(len(sweeps), dtype=kt, device=u.device) if want_kmax else None
+        with torch.cuda.device(u.device):
+            if f64:
+                L.check(lib.pde_adi_rect_f64_forward(C.byref(d), _ptr(u), _ptr(y), *[_ptr(t) for t in p], None, _ptr(ws),
+                                                     ws.numel(), _stream()), "pde_adi_rect_f64_forward")
+                tk = None
+            else:
+                # the coefficient maxima reach the host through the same pinned ring as a square call's
+                tk = _kmax_channel(len(sweeps)) if want_kmax else None
+                L.check(lib.pde_adi_rect_forward(C.byref(d), _ptr(u), _ptr(y), *[_ptr(t) for t in p], _ptr(kdev),
+                                                 _ptr(tk.host if tk else None), C.c_void_p(tk.event.cuda_event if tk else 0),
+                                                 _ptr(ws), ws.numel(), _stream()), "pde_adi_rect_forward")
+            ctx.kmax = tk
+            if tk is not None and kmax_sink is not None:
+                kmax_sink.append(tk)
+        ctx.fwd_ws = ws if need_grad else None       # factorisation reused by the backward
+        ctx.save_for_backward(y, u if (need_grad and ckpt != 0) else None, *p)
+        ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt, f64)
+        ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = L.load()
+        y, u, *p = ctx.saved_tensors
+        sweeps, smooth3, clamp_max, eps, ckpt, f64 = ctx.cfg
+        B, Cc, H, W = y.shape
+        gy = gy.to(y.dtype).contiguous()
+        d = _make_rect_desc(B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(y), sweeps, smooth3, clamp_max, eps)
+        gu = torch.empty_like(y)
+        gp = [torch.empty_like(t) for t in p]
+        bits = plan_checkpoints(ctx.kmax.wait()) if ckpt == "auto" else int(ckpt)
+        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+        fam = "pde_adi_rect_f64_" if f64 else "pde_adi_rect_"
+        ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(C.byref(d), bin(bits).count("1")), y.device)
+        with torch.cuda.device(y.device):          # autograd thread: set device, fetch the stream here
+            L.check(getattr(lib, fam + "backward")(C.byref(d), _ptr(gy), _ptr(y), _ptr(u if bits else None), mask, _ptr(gu),
+                                                   *[_ptr(t) for t in p], *[_ptr(t) for t in gp], _ptr(ctx.fwd_ws),
+                                                   _ptr(ws), ws.numel(), _stream()), fam + "backward")
+        ctx.fwd_ws = None
+        gp = [g.reshape(s).to(dt) for g, (s, dt) in zip(gp, ctx.param_meta)]
+        return (gu, *gp, None, None, None, None, None, None, None)
 
 
 class _AdiMixedFn(torch.autograd.Function):
@@ -735,8 +859,9 @@ def adi_diffuse_multi(u, layers, weights=None, plane_sums=False, checkpoints="au
     if isinstance(checkpoints, list):
         checkpoints = tuple(checkpoints)
     nl = len(layers)
-    if _is_f64(u, weights, *flat):
-        # float64: one layer after another (adi_diffuse_mixed), the weighted sum and the plane sums in torch
+    if _is_f64(u, weights, *flat) or _is_rect(u):
+        # float64, or a rectangular plane (H != W: no one-launch kernels): one layer after another (adi_diffuse_mixed),
+        # the weighted sum and the plane sums in torch
         ys = []
         for i, ly in enumerate(layers):
             ck = checkpoints[i] if isinstance(checkpoints, tuple) else checkpoints
@@ -839,8 +964,11 @@ def adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
         raise ValueError("every step must have the same number of sweeps")
     if not _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M):
         u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
-    if u.dim() == 4 and u.is_cuda and (L.load().pde_adi_line_length_path(int(u.shape[-1])) == 2 or
+    if _is_rect(u):
+        _check_rect(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)   # before the first operator launch
+    if u.dim() == 4 and u.is_cuda and (_is_rect(u) or L.load().pde_adi_line_length_path(int(u.shape[-1])) == 2 or
                                        _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)):
+        # a rectangle (H != W: no per-step entry points either), or
         # a line length without fused kernels (pde_adi_line_length_path: any size up to PDE_MAX_N_GENERIC): the per-step
         # entry points do not exist there; compose the layer from its own pieces — the channel operator and the sweeps of
         # one step per call, chained by autograd (the step-local checkpoint mask applies to every step unchanged).  float64
@@ -883,7 +1011,8 @@ def _empty_passthrough(u, *params):
 def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps: Sequence[Sweep],
                 smooth3: bool = False, clamp_max: Optional[float] = None, eps: float = 1e-6, checkpoints="auto",
                 kmax_sink: Optional[list] = None):
-    """Run ``sweeps`` (a flat list) of implicit diffusion on ``u`` (B,C,N,N) in one fused launch.
+    """Run ``sweeps`` (a flat list) of implicit diffusion on ``u`` (B,C,N,N) in one fused launch; a rectangular
+    ``u`` (B,C,H,W) with (C,H,W) parameters, both sides in [2, 128], runs on the any-size kernels (pde_adi_rect_*).
 
     Replaces the reference's time loop over diffuse_x/diffuse_y/thomas_solver_batch
     (mnist_test.py:44-198, cifar10.py:74-211) and its autograd backward.
@@ -897,6 +1026,14 @@ def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, swe
         return _empty_passthrough(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
     if not isinstance(sweeps, tuple):
         sweeps = tuple(sweeps)
+    if _is_rect(u):
+        # H != W: the rectangle entry points through the ctypes autograd function (no host-extension path); float64 and
+        # float16 by the same rules as a square call
+        f64 = _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+        if not f64:
+            u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+        return _AdiRectFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3),
+                                clamp_max, float(eps), checkpoints, kmax_sink, f64)
     if _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff):
         return _AdiF64Fn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3), clamp_max,
                                float(eps), checkpoints)
@@ -1505,12 +1642,13 @@ def _make_desc64(B, Cc, N, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) -> 
     return d
 
 
-def _as_chw64(p: torch.Tensor, Cc: int, N: int) -> torch.Tensor:
+def _as_chw64(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.Tensor:
+    W = N if W is None else W
     q = p.detach()
     if q.dim() == 2:
         q = q.unsqueeze(0)
-    if tuple(q.shape) != (Cc, N, N):
-        raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{N})")
+    if tuple(q.shape) != (Cc, N, W):
+        raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{W})")
     return q.to(torch.float64).contiguous()
 
 

@@ -30,8 +30,25 @@ __all__ = ["MnistDiffusionLayer", "FashionDiffusionLayer", "SvhnDiffusionLayer",
            "LearnableDiffusionLayer", "ImprovedDiffusionLayer", "PDELayer"]
 
 
+def _plane(size):
+    """(H, W) of a layer's ``size``: an int is the reference's square ``size x size``, a pair is a rectangle of H rows
+    and W columns (the reference's sweeps are shape-generic, mnist_test.py:45,72,105; only its constructors fix the
+    square)."""
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise ValueError(f"size must be an int or a pair (H, W), got {size!r}")
+        return int(size[0]), int(size[1])
+    return size, size
+
+
+def _size_attr(size):
+    """What ``layer.size`` keeps: the int as given, or the pair as a tuple."""
+    return tuple(_plane(size)) if isinstance(size, (tuple, list)) else size
+
+
 class _AdiBase(nn.Module):
-    """Shared machinery of the implicit (Thomas) layers."""
+    """Shared machinery of the implicit (Thomas) layers.  ``size`` is an int (a square, every kernel family) or a pair
+    (H, W) with H != W (the any-size kernels behind pde_adi_rect_*, both sides in [2, 128])."""
     _split = "strang"
     _smooth3 = False
     _clamp_max = None
@@ -106,8 +123,8 @@ class _AdiBase(nn.Module):
         2 in error amplification); call again after large parameter changes.  ``example`` is accepted for compatibility and
         ignored.  Returns the mask (an int) or, for schedules that run as several launch groups, one mask per group."""
         ab = self.alpha_base
-        Cc, N = (1, ab.shape[-1]) if ab.dim() == 2 else (ab.shape[0], ab.shape[-1])
-        like = torch.empty((1, Cc, N, N), dtype=torch.float32, device=ab.device)
+        Cc = 1 if ab.dim() == 2 else ab.shape[0]
+        like = torch.empty((1, Cc, ab.shape[-2], ab.shape[-1]), dtype=torch.float32, device=ab.device)
         args = (self.alpha_base, self.beta_base, self.alpha_time_coeff, self.beta_time_coeff)
         kw = dict(smooth3=self._smooth3, clamp_max=self._clamp_max, eps=self.stability_eps)
         masks = []
@@ -156,6 +173,11 @@ class _AdiBase(nn.Module):
     def _run(self, u, steps, M=None, mode=None, skip_weight=None):
         """All steps of the layer.  One launch sequence holds at most PDE_MAX_SWEEPS sweeps: longer schedules
         (num_steps > 32 Strang steps) are cut into groups of whole steps, chained through autograd."""
+        # a rectangle on either side must match exactly; a square input on a square layer of another size is left to the
+        # calls below, which refuse it as they always have (existing behaviour, empty batches included, stays as it is)
+        hw, phw = tuple(u.shape[-2:]), tuple(self.alpha_base.shape[-2:])
+        if u.dim() == 4 and hw != phw and (hw[0] != hw[1] or phw[0] != phw[1]):
+            raise L.PdeError(f"input plane {hw[0]}x{hw[1]} does not match the layer's {phw[0]}x{phw[1]} coefficients")
         # one route for the whole layer: its calls (sweeps, operator, skip blend) each see only some of the parameters
         u = F_.route_input(u, self.alpha_base, self.beta_base, self.alpha_time_coeff, self.beta_time_coeff, M, skip_weight)
         per = max(1, L.PDE_MAX_SWEEPS // len(steps[0]))
@@ -210,22 +232,24 @@ class _AdiBase(nn.Module):
 
 
 class MnistDiffusionLayer(_AdiBase):
-    """mnist_test.py:11-219.  (B,1,size,size) -> same; Strang split, smoothed coefficients."""
+    """mnist_test.py:11-219.  (B,1,size,size) -> same — or (B,1,H,W) with ``size=(H, W)``; Strang split, smoothed
+    coefficients."""
     _smooth3 = True
 
     def __init__(self, size=28, dt=0.001, dx=1.0, dy=1.0, num_steps=10):
         super().__init__()
-        self.size, self.dt, self.dx, self.dy, self.num_steps = size, dt, dx, dy, num_steps
-        self.alpha_base = nn.Parameter(torch.ones(size, size) * 2.0)
-        self.beta_base = nn.Parameter(torch.ones(size, size) * 2.0)
-        self.alpha_time_coeff = nn.Parameter(torch.zeros(size, size))
-        self.beta_time_coeff = nn.Parameter(torch.zeros(size, size))
+        self.size, self.dt, self.dx, self.dy, self.num_steps = _size_attr(size), dt, dx, dy, num_steps
+        hw = _plane(size)
+        self.alpha_base = nn.Parameter(torch.ones(*hw) * 2.0)
+        self.beta_base = nn.Parameter(torch.ones(*hw) * 2.0)
+        self.alpha_time_coeff = nn.Parameter(torch.zeros(*hw))
+        self.beta_time_coeff = nn.Parameter(torch.zeros(*hw))
         self.stability_eps = 1e-6
         print(f"Initialized DiffusionLayer with dx={dx}, dy={dy}")
 
     def forward(self, u):
         if u.dim() != 4 or u.shape[1] != 1:
-            raise ValueError(f"expected (B,1,{self.size},{self.size}), got {tuple(u.shape)}")
+            raise ValueError("expected (B,1,%d,%d), got %s" % (*_plane(self.size), tuple(u.shape)))
         return self._run(u, self._schedule())
 
     def get_numerical_stability_info(self):
@@ -245,16 +269,17 @@ class FashionDiffusionLayer(_AdiBase):
 
     def __init__(self, size=28, dt=0.3, dx=1.0, num_steps=4):
         super().__init__()
-        self.size, self.dt, self.dx, self.num_steps = size, dt, dx, num_steps
-        self.alpha_base = nn.Parameter(torch.ones(size, size) * 1.8)
-        self.beta_base = nn.Parameter(torch.ones(size, size) * 1.8)
-        self.alpha_time_coeff = nn.Parameter(torch.zeros(size, size))
-        self.beta_time_coeff = nn.Parameter(torch.zeros(size, size))
+        self.size, self.dt, self.dx, self.num_steps = _size_attr(size), dt, dx, num_steps
+        hw = _plane(size)
+        self.alpha_base = nn.Parameter(torch.ones(*hw) * 1.8)
+        self.beta_base = nn.Parameter(torch.ones(*hw) * 1.8)
+        self.alpha_time_coeff = nn.Parameter(torch.zeros(*hw))
+        self.beta_time_coeff = nn.Parameter(torch.zeros(*hw))
         self.stability_eps = 1e-6
 
     def forward(self, u):
         if u.dim() != 4 or u.shape[1] != 1:
-            raise ValueError(f"expected (B,1,{self.size},{self.size}), got {tuple(u.shape)}")
+            raise ValueError("expected (B,1,%d,%d), got %s" % (*_plane(self.size), tuple(u.shape)))
         return self._run(u, self._schedule())
 
 
@@ -265,11 +290,12 @@ class SvhnDiffusionLayer(_AdiBase):
 
     def __init__(self, size=32, channels=3, dt=0.01, dx=1.0, num_steps=10):
         super().__init__()
-        self.size, self.channels, self.dt, self.dx, self.num_steps = size, channels, dt, dx, num_steps
-        self.alpha_base = nn.Parameter(torch.ones(channels, size, size) * 0.1)
-        self.beta_base = nn.Parameter(torch.ones(channels, size, size) * 0.1)
-        self.alpha_time_coeff = nn.Parameter(torch.randn(channels, size, size) * 0.001)
-        self.beta_time_coeff = nn.Parameter(torch.randn(channels, size, size) * 0.001)
+        self.size, self.channels, self.dt, self.dx, self.num_steps = _size_attr(size), channels, dt, dx, num_steps
+        hw = _plane(size)
+        self.alpha_base = nn.Parameter(torch.ones(channels, *hw) * 0.1)
+        self.beta_base = nn.Parameter(torch.ones(channels, *hw) * 0.1)
+        self.alpha_time_coeff = nn.Parameter(torch.randn(channels, *hw) * 0.001)
+        self.beta_time_coeff = nn.Parameter(torch.randn(channels, *hw) * 0.001)
         self.channel_coupling = nn.Parameter(torch.eye(channels) * 0.01)
         self.stability_eps = 1e-6
         self.skip_weight = nn.Parameter(torch.tensor(0.9))
@@ -293,22 +319,24 @@ class EnhancedDiffusionLayer(_AdiBase):
 
     def __init__(self, size=32, channels=3, dt=0.001, dx=1.0, dy=1.0, num_steps=10, *, channel_mixing_enabled=True):
         super().__init__()
-        self.size, self.channels, self.dt, self.dx, self.dy, self.num_steps = size, channels, dt, dx, dy, num_steps
-        self.alpha_base = nn.Parameter(torch.ones(channels, size, size) * 1.0)
-        self.beta_base = nn.Parameter(torch.ones(channels, size, size) * 1.0)
-        self.alpha_time_coeff = nn.Parameter(torch.zeros(channels, size, size) * 0.1)
-        self.beta_time_coeff = nn.Parameter(torch.zeros(channels, size, size) * 0.1)
+        self.size, self.channels, self.dt, self.dx, self.dy, self.num_steps = _size_attr(size), channels, dt, dx, dy, num_steps
+        hw = _plane(size)
+        self.alpha_base = nn.Parameter(torch.ones(channels, *hw) * 1.0)
+        self.beta_base = nn.Parameter(torch.ones(channels, *hw) * 1.0)
+        self.alpha_time_coeff = nn.Parameter(torch.zeros(channels, *hw) * 0.1)
+        self.beta_time_coeff = nn.Parameter(torch.zeros(channels, *hw) * 0.1)
         self.channel_mixing = nn.Parameter(torch.eye(channels) + torch.randn(channels, channels) * 0.01)
         self.stability_eps = 1e-6
         self.channel_mixing_enabled = channel_mixing_enabled
         self._banner()
 
     def _banner(self):
-        print(f"Alpha/Beta-Focused DiffusionLayer: {self.size}x{self.size}x{self.channels}")
+        h, w = _plane(self.size)
+        print(f"Alpha/Beta-Focused DiffusionLayer: {h}x{w}x{self.channels}")
         print(f"  Spatial: dx={self.dx}, dy={self.dy}")
         print(f"  Temporal: dt={self.dt}, steps={self.num_steps}")
-        print(f"  Learnable parameters: α matrices ({self.channels}x{self.size}x{self.size}), "
-              f"β matrices ({self.channels}x{self.size}x{self.size})")
+        print(f"  Learnable parameters: α matrices ({self.channels}x{h}x{w}), "
+              f"β matrices ({self.channels}x{h}x{w})")
 
     def _uses_operator(self):
         return bool(self.channel_mixing_enabled)
@@ -325,9 +353,10 @@ class LearnableDiffusionLayer(EnhancedDiffusionLayer):
     _split = "lie"
 
     def _banner(self):
-        print(f"Learnable Diffusion Layer: {self.size}x{self.size}x{self.channels}")
-        print(f"  Learnable α coefficients: {self.channels}x{self.size}x{self.size}")
-        print(f"  Learnable β coefficients: {self.channels}x{self.size}x{self.size}")
+        h, w = _plane(self.size)
+        print(f"Learnable Diffusion Layer: {h}x{w}x{self.channels}")
+        print(f"  Learnable α coefficients: {self.channels}x{h}x{w}")
+        print(f"  Learnable β coefficients: {self.channels}x{h}x{w}")
         print(f"  Temporal: dt={self.dt}, steps={self.num_steps}")
 
 

@@ -556,6 +556,87 @@ int pde_jacobi_f64_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const d
                             const double* a_row, const double* b_col, double* gu, double* g_a_row, double* g_b_col,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K1 on rectangular planes (H != W) -------------------------------------------------------------------
+ * The reference's sweep functions read B, C, H, W = u.shape and transpose for the y direction (mnist_test.py:45,72,105;
+ * cifar10.py:67,76,126,152); only its constructors fix size x size.  These entry points run the implicit time loop on
+ * a (B,C,H,W) tensor with (C,H,W) parameters: an x sweep (PDE_AXIS_X) solves H lines of W unknowns with alpha, a y sweep
+ * (PDE_AXIS_Y) W lines of H unknowns with beta, exactly as in the square case.  They are served by the any-size kernels
+ * (one thread per line, plane in LDS — path 2 of pde_adi_line_length_path) at every shape, H == W and the fused line
+ * lengths included: 2 <= H, W <= PDE_MAX_N_GENERIC, otherwise PDE_E_UNSUPPORTED_N.  There is no per-step, one-launch or
+ * wide family for rectangles: a layer with a channel operator is composed per step by the caller (pde_channel_mix_* on
+ * H*W pixels + one-step schedules).  With H == W == N the results are bit for bit those of pde_adi_forward /
+ * pde_adi_backward at a line length N on the any-size path.  Same conventions as above: caller-owned device buffers,
+ * asynchronous on `stream`, no allocation, validation on the host before anything touches the device (null pointers
+ * PDE_E_BADARG, a short or misaligned workspace PDE_E_WORKSPACE). */
+typedef struct PdeAdiRectDesc {
+    int32_t B, C, H, W;         /* rows H (y direction, beta), columns W (x direction, alpha) */
+    int32_t io_dtype;           /* PDE_IO_F32 | PDE_IO_BF16 | PDE_IO_F16 (tensor I/O; math is fp32) */
+    int32_t num_sweeps;
+    int32_t smooth3;            /* as PdeAdiDesc: along the solve axis                    */
+    int32_t has_clamp_max;
+    float   clamp_max;
+    float   eps;
+    PdeSweep sweep[PDE_MAX_SWEEPS];
+} PdeAdiRectDesc;
+
+/* 1 when both sides are in [2, PDE_MAX_N_GENERIC], else 0 */
+int pde_adi_rect_supported(int32_t H, int32_t W);
+/* scratch of the two calls below (0 for a refused descriptor); num_checkpoints: bits set in the backward's ckpt_mask */
+size_t pde_adi_rect_forward_workspace_bytes(const PdeAdiRectDesc* d);
+size_t pde_adi_rect_backward_workspace_bytes(const PdeAdiRectDesc* d, int32_t num_checkpoints);
+/* pde_adi_kappa_max on a rectangle: the per-sweep maximum coefficient, kappa_max[num_sweeps] on the device */
+int pde_adi_rect_kappa_max(const PdeAdiRectDesc* d,
+                           const float* alpha_base, const float* beta_base,
+                           const float* alpha_slope, const float* beta_slope,
+                           float* kappa_max, void* stream);
+/* pde_adi_forward on a rectangle (the time loop of mnist_test.py:44-198 / cifar10.py:74-211 on H x W planes): u, y
+ * (B,C,H,W) of io_dtype, parameters (C,H,W) fp32.  kappa_max / kappa_max_host / kappa_event as in pde_adi_forward: the
+ * maxima are copied to the pinned host buffer and the event is recorded behind the factorisation kernel, before the
+ * sweep launch.  The workspace then holds the factorisation and may be handed to the backward as fwd_workspace. */
+int pde_adi_rect_forward(const PdeAdiRectDesc* d, const void* u, void* y,
+                         const float* alpha_base, const float* beta_base,
+                         const float* alpha_slope, const float* beta_slope,
+                         float* kappa_max, float* kappa_max_host, void* kappa_event,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* pde_adi_backward on a rectangle (the reference gets it from autograd): gu and the four (C,H,W) parameter gradients,
+ * overwritten; ckpt_mask, u and fwd_workspace as in pde_adi_backward. */
+int pde_adi_rect_backward(const PdeAdiRectDesc* d, const void* gy, const void* y, const void* u,
+                          const uint64_t ckpt_mask[2], void* gu,
+                          const float* alpha_base, const float* beta_base,
+                          const float* alpha_slope, const float* beta_slope,
+                          float* g_alpha_base, float* g_beta_base,
+                          float* g_alpha_slope, float* g_beta_slope,
+                          const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same in float64 (pde_adi_f64_* on a rectangle): every tensor and every scalar of the schedule a double. */
+typedef struct PdeAdiRectDescF64 {
+    int32_t B, C, H, W;
+    int32_t io_dtype;           /* PDE_IO_F64 */
+    int32_t num_sweeps;
+    int32_t smooth3;
+    int32_t has_clamp_max;
+    double  clamp_max;
+    double  eps;
+    PdeSweepF64 sweep[PDE_MAX_SWEEPS];
+} PdeAdiRectDescF64;
+
+size_t pde_adi_rect_f64_forward_workspace_bytes(const PdeAdiRectDescF64* d);
+size_t pde_adi_rect_f64_backward_workspace_bytes(const PdeAdiRectDescF64* d, int32_t num_checkpoints);
+int pde_adi_rect_f64_kappa_max(const PdeAdiRectDescF64* d,
+                               const double* alpha_base, const double* beta_base,
+                               const double* alpha_slope, const double* beta_slope,
+                               double* kappa_max, void* stream);
+int pde_adi_rect_f64_forward(const PdeAdiRectDescF64* d, const double* u, double* y,
+                             const double* alpha_base, const double* beta_base,
+                             const double* alpha_slope, const double* beta_slope,
+                             double* kappa_max, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_rect_f64_backward(const PdeAdiRectDescF64* d, const double* gy, const double* y, const double* u,
+                              const uint64_t ckpt_mask[2], double* gu,
+                              const double* alpha_base, const double* beta_base,
+                              const double* alpha_slope, const double* beta_slope,
+                              double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
+                              const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- utilities ------------------------------------------------------------------------- */
 
 /* Average device time (ms) per launch of the dominant kernel of the most recent

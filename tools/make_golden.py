@@ -8,6 +8,7 @@ returned: ``y``, ``gu`` and one gradient per parameter.  Nothing of the
 reference's source is stored.
 
     python tools/make_golden.py            # rewrite every fixture
+    python tools/make_golden.py rect       # only tests/golden/rect/ (the layer classes on rectangular planes)
 """
 import json
 import os
@@ -39,7 +40,7 @@ def _run(layer, u, gy):
     return out
 
 
-def _save(name, script, cls, ctor, layer, u, gy, dtype):
+def _save(name, script, cls, ctor, layer, u, gy, dtype, extra_meta=None):
     bufin = {"bufin_" + n: b.detach().clone() for n, b in layer.named_buffers()} if getattr(layer, "keep_buffers", False) else {}
     res = _run(layer, u, gy)
     blob = {"u": u, "gy": gy}
@@ -51,6 +52,7 @@ def _save(name, script, cls, ctor, layer, u, gy, dtype):
     blob.update(res)
     arrays = {k: v.detach().cpu().numpy() for k, v in blob.items()}
     meta = {"script": script, "cls": cls, "ctor": ctor, "dtype": str(dtype).replace("torch.", "")}
+    meta.update(extra_meta or {})
     arrays["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **arrays)
@@ -95,6 +97,44 @@ def _make(name, script, cls, ctor, B, g, dtype, tweak, u_fn, mod):
         u = u_fn(u)
     gy = torch.randn(B, C, N, N, generator=g, dtype=dtype)
     _save(name, script, cls, ctor, layer, u, gy, dtype)
+
+
+def make_rect(name, script, cls, ctor, hw, B, seed, rel=0.2, slope=0.4):
+    """A K1 class of the reference on a rectangular plane ``hw`` = (H, W): its constructors fix size x size, its sweeps
+    read B, C, H, W from the input (mnist_test.py:45,72,105; cifar10.py:67,76,126,152), so the four coefficient
+    parameters are replaced by (H, W) / (C, H, W) tensors — the constructor's own initial value, perturbed — and the
+    layer is run as it is.  Written to tests/golden/rect/ (apart from the square fixtures, whose tests construct the
+    product's layers from ``ctor`` alone); ``plane`` in the meta says what the parameters' plane is."""
+    mod = ref_loader.load(script)
+    g = torch.Generator().manual_seed(seed)
+    torch.manual_seed(seed)
+    with ref_loader.quiet():
+        layer = getattr(mod, cls)(**ctor)
+    C = getattr(layer, "channels", 1)
+    with torch.no_grad():
+        for n in ("alpha_base", "beta_base", "alpha_time_coeff", "beta_time_coeff"):
+            old = getattr(layer, n)
+            shape = tuple(old.shape[:-2]) + tuple(hw)
+            if n.endswith("_base"):
+                new = float(old.flatten()[0]) * (1 + rel * torch.randn(shape, generator=g))
+            else:
+                new = slope * torch.randn(shape, generator=g)
+            setattr(layer, n, torch.nn.Parameter(new))
+        if hasattr(layer, "channel_mixing"):
+            layer.channel_mixing.copy_(torch.eye(C) + 0.1 * torch.randn(C, C, generator=g))
+    u = torch.randn(B, C, *hw, generator=g)
+    gy = torch.randn(B, C, *hw, generator=g)
+    os.makedirs(os.path.join(OUT, "rect"), exist_ok=True)
+    with ref_loader.quiet():
+        _save(os.path.join("rect", name), script, cls, ctor, layer, u, gy, torch.float32, extra_meta={"plane": list(hw)})
+
+
+def rect():
+    torch.set_num_threads(4)            # tests/golden_util.py GOLDEN_THREADS
+    make_rect("mnist_20x36", "mnist_test", "DiffusionLayer", {"size": 20, "dt": 0.01, "dx": 1.0, "dy": 1.3, "num_steps": 3},
+              (20, 36), 3, 81)
+    make_rect("cifar10_c3_24x40", "cifar10", "EnhancedDiffusionLayer",
+              {"size": 24, "channels": 3, "dt": 0.02, "num_steps": 3}, (24, 40), 2, 82, slope=0.5)
 
 
 def make_model(name, script, cls, ctor, shape, seed, tweak=None, out_index=0, eval_mode=True, buffers=False):
@@ -379,9 +419,13 @@ def main():
         torch.nn.functional.pad(u, (4, 4, 4, 4), mode="reflect"), 9, stride=1)
     make("emotion_default_smooth", "emotion_recognition", "PDELayer", {}, 2, 73, u_fn=smooth)
 
+    rect()
+
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "models":
         models()
+    elif len(sys.argv) > 1 and sys.argv[1] == "rect":
+        rect()
     else:
         main()
