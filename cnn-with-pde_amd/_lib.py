@@ -15,6 +15,7 @@ PDE_MAX_N = 32
 PDE_MAX_N_GENERIC = 128
 PDE_IO_F32, PDE_IO_BF16, PDE_IO_F64, PDE_IO_F16 = 0, 1, 2, 3
 PDE_AXIS_X, PDE_AXIS_Y = 0, 1
+PDE_MIX_PATH_SCALAR, PDE_MIX_PATH_MFMA_F32, PDE_MIX_PATH_MFMA_16, PDE_MIX_PATH_SPLIT3, PDE_MIX_PATH_FUSED = 0, 1, 2, 3, 4
 PDE_JACOBI_MAX_HW = 1024
 PDE_JACOBI_TILED_K = 10
 
@@ -129,6 +130,8 @@ SIGNATURES = {
     "pde_channel_mix_backward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _fp, _vp, _fp, _vp, _sz, _vp]),
     "pde_channel_mix_backward_steps": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _fp, _vp, _fp, _vp, _sz, _i32, _i32,
                                                  _vp]),
+    "pde_channel_mix_path": (C.c_int, [_i32, _i32, _i32, _i32, _i32]),
+    "pde_channel_mix_splits": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64)]),
     "pde_skip_blend_forward": (C.c_int, [C.c_int64, _i32, _vp, _vp, _fp, _vp, _vp]),
     "pde_skip_blend_backward_workspace_bytes": (_sz, [C.c_int64]),
     "pde_skip_blend_backward": (C.c_int, [C.c_int64, _i32, _vp, _vp, _vp, _fp, _vp, _vp, _fp, _vp, _sz, _vp]),

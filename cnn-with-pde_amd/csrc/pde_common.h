@@ -59,6 +59,7 @@ __host__ __device__ inline int half_pos(int j, int N) { return (j < N / 2) ? j :
 // bf16 tensors through the bf16 MFMA (pde_mix_bf16.hip); C = 64 / 128, HW a multiple of 64
 bool mix_bf16_ok(int C, int HW);
 int mix_bf16_splits(int B, int C, int HW);
+int mix_bf16_apply_grid(int B, int C, int HW, long* tiles = nullptr);   // workgroups of the forward kernel and the tiles they walk
 int mix_bf16_apply(int B, int C, int HW, const void* u, const float* M, void* out, int trans, hipStream_t st);
 int mix_bf16_backward(int B, int C, int HW, const void* u, const void* g, const float* M, void* gu, float* part, int nsplit,
                       int accp, hipStream_t st);

@@ -313,7 +313,8 @@ __global__ __launch_bounds__(256) void mix_gm_mfma_kernel(const IO* __restrict__
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int i = 32 * it + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                dst[i * C + 32 * jt + jj] = acc[t][r];
+                float* o = dst + i * C + 32 * jt + jj;
+                *o = accp ? *o + acc[t][r] : acc[t][r];
             }
         }
     }
@@ -491,12 +492,15 @@ int gm_splits(int B, int C, int HW) {
     return (int)n;
 }
 
+long apply_mfma_blocks(int B, int HW) { return (long)B * ((HW + 127) / 128); }   // 128 pixels per wave and trip
+int apply_mfma_grid(int B, int HW) {
+    const long grid = (apply_mfma_blocks(B, HW) + 3) / 4;                         // four waves per workgroup
+    return (int)(grid > 1024 ? 1024 : grid);
+}
 int launch_apply_mfma(int B, int C, int HW, int io, const void* u, const float* M, void* out, int trans,
                       hipStream_t st) {
     const size_t lds = (size_t)C * C * sizeof(float);
-    const long nblk = (long)B * ((HW + 127) / 128);
-    long grid = (nblk + 3) / 4;
-    if (grid > 1024) grid = 1024;
+    const int grid = apply_mfma_grid(B, HW);
     if (io == PDE_IO_F32) {
         static unsigned long long cfg = 0;
         ensure_lds((const void*)mix_apply_mfma_kernel<float>, 65536, cfg);
@@ -513,6 +517,30 @@ int launch_apply_mfma(int B, int C, int HW, int io, const void* u, const float* 
     return check_launch();
 }
 
+// The one place where a call's kernel family is chosen: pde_channel_mix_path / _splits report it, the entry points
+// dispatch on it.  path: PDE_MIX_PATH_* (include/pdecnn.h) or PDE_E_BADARG; walkers / chunks: pde_channel_mix_splits.
+struct MixPlan { int path; int walkers; long chunks; };
+MixPlan mix_plan(int B, int C, int HW, int io, bool backward) {
+    if (B <= 0 || C <= 0 || HW <= 0 || (io != PDE_IO_F32 && io != PDE_IO_BF16 && io != PDE_IO_F16)) return {PDE_E_BADARG, 0, 0};
+    if (!backward) {
+        if (io != PDE_IO_F32 && mix_bf16_ok(C, HW)) {
+            long tiles = 0;
+            const int grid = mix_bf16_apply_grid(B, C, HW, &tiles);
+            return {PDE_MIX_PATH_MFMA_16, grid, tiles};
+        }
+        if (mfma_apply_ok(C, HW)) return {PDE_MIX_PATH_MFMA_F32, 4 * apply_mfma_grid(B, HW), apply_mfma_blocks(B, HW)};
+        const long blocks = (long)B * ((HW + 255) / 256);
+        return {PDE_MIX_PATH_SCALAR, (int)blocks, blocks};
+    }
+    const long chunks = (long)B * ((HW + kGmKP - 1) / kGmKP);                      // 64 pixels in every backward kernel
+    static_assert(kGmKP == kK, "one chunk size");
+    if (io != PDE_IO_F32 && mix_bf16_ok(C, HW)) return {PDE_MIX_PATH_MFMA_16, mix_bf16_splits(B, C, HW), chunks};
+    if (io == PDE_IO_F32 && mix_split_ok(C, HW)) return {PDE_MIX_PATH_SPLIT3, mix_split_splits(B, C, HW), chunks};
+    if (mfma_fused_ok(C, HW) && getenv("PDE_MIX_UNFUSED") == nullptr) return {PDE_MIX_PATH_FUSED, fused_splits(B, C, HW), chunks};
+    if (mfma_gm_ok(C, HW)) return {PDE_MIX_PATH_MFMA_F32, gm_mfma_splits(B, HW), chunks};
+    return {PDE_MIX_PATH_SCALAR, gm_splits(B, C, HW), chunks};
+}
+
 }  // namespace
 }  // namespace pde
 
@@ -524,10 +552,11 @@ int pde_channel_mix_forward(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, 
                             void* out, void* stream) {
     if (B <= 0 || C <= 0 || HW <= 0 || !u || !M || !out) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
-    if (io_dtype == PDE_IO_BF16 && mix_bf16_ok(C, HW)) return mix_bf16_apply(B, C, HW, u, M, out, 0, st);
-    if (io_dtype == PDE_IO_F16 && mix_bf16_ok(C, HW)) return mix_f16_apply(B, C, HW, u, M, out, 0, st);
-    if (mfma_apply_ok(C, HW)) return launch_apply_mfma(B, C, HW, io_dtype, u, M, out, 0, st);
+    const MixPlan plan = mix_plan(B, C, HW, io_dtype, false);
+    if (plan.path < 0) return plan.path;
+    if (plan.path == PDE_MIX_PATH_MFMA_16)
+        return io_dtype == PDE_IO_BF16 ? mix_bf16_apply(B, C, HW, u, M, out, 0, st) : mix_f16_apply(B, C, HW, u, M, out, 0, st);
+    if (plan.path == PDE_MIX_PATH_MFMA_F32) return launch_apply_mfma(B, C, HW, io_dtype, u, M, out, 0, st);
     dim3 grid((HW + 255) / 256, B);
     if (io_dtype == PDE_IO_F32)
         hipLaunchKernelGGL((mix_apply_kernel<float, false>), grid, dim3(256), 0, st, (const float*)u, M, (float*)out, C, HW);
@@ -536,6 +565,17 @@ int pde_channel_mix_forward(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, 
     else
         hipLaunchKernelGGL((mix_apply_kernel<bf16s, false>), grid, dim3(256), 0, st, (const bf16s*)u, M, (bf16s*)out, C, HW);
     return check_launch();
+}
+
+int pde_channel_mix_path(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, int32_t backward) {
+    return mix_plan(B, C, HW, io_dtype, backward != 0).path;
+}
+
+int pde_channel_mix_splits(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, int32_t backward, int64_t* chunks) {
+    const MixPlan plan = mix_plan(B, C, HW, io_dtype, backward != 0);
+    if (plan.path < 0) return plan.path;
+    if (chunks) *chunks = plan.chunks;
+    return plan.walkers;
 }
 
 size_t pde_channel_mix_backward_workspace_bytes(int32_t B, int32_t C, int32_t HW) {
@@ -564,27 +604,26 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
     if (B <= 0 || C <= 0 || HW <= 0 || !u || !gout || !M || !gu || !workspace || (finalize && !gM)) return PDE_E_BADARG;
     if (workspace_bytes < pde_channel_mix_backward_workspace_bytes(B, C, HW)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    const MixPlan plan = mix_plan(B, C, HW, io_dtype, true);
+    if (plan.path < 0) return plan.path;
+    const int nsplit = plan.walkers;
     dim3 grid((HW + 255) / 256, B);
     const int tiles = (C + kT - 1) / kT;
     float* part = static_cast<float*>(workspace);
-    if (io_dtype != PDE_IO_F32 && mix_bf16_ok(C, HW)) {    // exact bf16 / fp16 products on the bf16 / fp16 MFMA
-        const int nsplit = mix_bf16_splits(B, C, HW);
+    if (plan.path == PDE_MIX_PATH_MFMA_16) {               // exact bf16 / fp16 products on the bf16 / fp16 MFMA
         const int rc = io_dtype == PDE_IO_BF16 ? mix_bf16_backward(B, C, HW, u, gout, M, gu, part, nsplit, accumulate, st)
                                                : mix_f16_backward(B, C, HW, u, gout, M, gu, part, nsplit, accumulate, st);
         if (rc != PDE_OK) return rc;
         if (finalize) hipLaunchKernelGGL(mix_gm_reduce_kernel, dim3((C * C + 31) / 32), dim3(256), 0, st, part, gM, C * C, nsplit);
         return check_launch();
     }
-    if (io_dtype == PDE_IO_F32 && mix_split_ok(C, HW)) {   // fp32 tensors, three bf16 pieces per operand on the bf16 MFMA
-        const int nsplit = mix_split_splits(B, C, HW);
+    if (plan.path == PDE_MIX_PATH_SPLIT3) {                // fp32 tensors, three bf16 pieces per operand on the bf16 MFMA
         const int rc = mix_split_backward(B, C, HW, u, gout, M, gu, part, nsplit, accumulate, st);
         if (rc != PDE_OK) return rc;
         if (finalize) hipLaunchKernelGGL(mix_gm_reduce_kernel, dim3((C * C + 31) / 32), dim3(256), 0, st, part, gM, C * C, nsplit);
         return check_launch();
     }
-    if (mfma_fused_ok(C, HW) && getenv("PDE_MIX_UNFUSED") == nullptr) {
-        const int nsplit = fused_splits(B, C, HW);
+    if (plan.path == PDE_MIX_PATH_FUSED) {
         if (io_dtype == PDE_IO_F32) {
             if (C == 32) launch_fused<float, 32, 1, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
             else if (C == 64) launch_fused<float, 64, 4, true>(u, gout, M, gu, part, B, HW, nsplit, accumulate, st);
@@ -605,7 +644,7 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
         return check_launch();
     }
     // gu = M^T gout
-    if (mfma_apply_ok(C, HW)) {
+    if (plan.path == PDE_MIX_PATH_MFMA_F32) {
         const int rc = launch_apply_mfma(B, C, HW, io_dtype, gout, M, gu, 1, st);
         if (rc != PDE_OK) return rc;
     } else if (io_dtype == PDE_IO_F32) {
@@ -616,9 +655,7 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
         hipLaunchKernelGGL((mix_apply_kernel<bf16s, true>), grid, dim3(256), 0, st, (const bf16s*)gout, M, (bf16s*)gu, C, HW);
     }
     // gM = G U^T
-    int nsplit;
-    if (mfma_gm_ok(C, HW)) {
-        nsplit = gm_mfma_splits(B, HW);
+    if (plan.path == PDE_MIX_PATH_MFMA_F32) {
         const size_t lds = (size_t)2 * C * kGmLd * sizeof(float);
         if (io_dtype == PDE_IO_F32) {
             static unsigned long long cfg = 0;
@@ -634,7 +671,6 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
             hipLaunchKernelGGL((mix_gm_mfma_kernel<bf16s>), dim3(nsplit), dim3(256), lds, st, (const bf16s*)u, (const bf16s*)gout, part, B, C, HW, nsplit, accumulate);
         }
     } else {
-        nsplit = gm_splits(B, C, HW);
         if (io_dtype == PDE_IO_F32)
             hipLaunchKernelGGL((mix_gm_kernel<float>), dim3(tiles * tiles, nsplit), dim3(256), 0, st, (const float*)u,
                                (const float*)gout, part, B, C, HW, nsplit, accumulate);

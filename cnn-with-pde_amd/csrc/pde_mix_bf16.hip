@@ -474,9 +474,7 @@ void launch_apply(const void* u, const float* M, void* out, int B, int HW, int t
     const size_t lds = frag_bytes<E, C>() + 2 * (size_t)C * kRow;
     static unsigned long long cfg = 0;
     ensure_lds((const void*)mix_apply_bf16_kernel<C, E>, (int)lds, cfg);
-    const long tiles = (long)B * (HW / kPx);
-    const int per_cu = C == 64 ? 4 : 1;                    // workgroups an LDS footprint of 34 / 100 KB allows
-    const long grid = tiles < 256L * per_cu ? tiles : 256L * per_cu;
+    const int grid = mix_bf16_apply_grid(B, C, HW);
     hipLaunchKernelGGL((mix_apply_bf16_kernel<C, E>), dim3((unsigned)grid), dim3(C * 4), lds, st, (const unsigned short*)u, M,
                        (unsigned short*)out, B, HW, trans);
 }
@@ -529,6 +527,12 @@ int mix_bf16_splits(int B, int C, int HW) {
     const long tiles = (long)B * (HW / kPx);
     const long want = C == 64 ? 768 : 256;                 // resident workgroups (LDS 43 / 118 KB each)
     return (int)(tiles < want ? tiles : want);
+}
+int mix_bf16_apply_grid(int B, int C, int HW, long* ntiles) {
+    const long tiles = (long)B * (HW / kPx);
+    if (ntiles) *ntiles = tiles;
+    const int per_cu = C == 64 ? 4 : 1;                    // workgroups an LDS footprint of 34 / 100 KB allows
+    return (int)(tiles < 256L * per_cu ? tiles : 256L * per_cu);
 }
 int mix_bf16_apply(int B, int C, int HW, const void* u, const float* M, void* out, int trans, hipStream_t st) {
     if (C == 64) launch_apply<64>(u, M, out, B, HW, trans, st);

@@ -299,6 +299,33 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
                                    void* gu, float* gM,
                                    void* workspace, size_t workspace_bytes,
                                    int32_t accumulate, int32_t finalize, void* stream);
+/* Which kernel family pde_channel_mix_forward (backward = 0) or pde_channel_mix_backward[_steps] (backward = 1) runs
+ * for these arguments; the entry points dispatch on the value this function returns.  PDE_E_BADARG for dimensions or an
+ * io_dtype they refuse.  The PDE_MIX_NO_BF16_MFMA, PDE_MIX_NO_SPLIT and PDE_MIX_UNFUSED environment switches are read
+ * on every call, here as there.
+ *   code                     forward                             backward
+ *   PDE_MIX_PATH_SCALAR      mix_apply_kernel                    transposed mix_apply_kernel + mix_gm_kernel
+ *   PDE_MIX_PATH_MFMA_F32    mix_apply_mfma_kernel               unfused: transposed mix_apply_mfma_kernel + mix_gm_mfma_kernel
+ *                            (C % 32 == 0, C <= 128, HW % 4 == 0)  (the same shapes, where no fused kernel takes them)
+ *   PDE_MIX_PATH_MFMA_16     mix_apply_bf16_kernel<MixBf16|MixF16>  mix_bwd_bf16_kernel<MixBf16|MixF16>, exact products
+ *                            (bf16 / fp16 tensors, C = 64 or 128, HW % 64 == 0)
+ *   PDE_MIX_PATH_SPLIT3      -                                   mix_bwd_split_kernel, three bf16 pieces per operand
+ *                                                                (fp32 tensors, C = 32, 64 or 96, HW % 4 == 0)
+ *   PDE_MIX_PATH_FUSED       -                                   mix_bwd_fused_kernel (C = 32, 64, 96: M^T fragments in LDS;
+ *                                                                C = 128: in the workspace), HW % 4 == 0
+ * Every backward ends in mix_gm_reduce_kernel when finalize = 1. */
+#define PDE_MIX_PATH_SCALAR   0
+#define PDE_MIX_PATH_MFMA_F32 1
+#define PDE_MIX_PATH_MFMA_16  2
+#define PDE_MIX_PATH_SPLIT3   3
+#define PDE_MIX_PATH_FUSED    4
+int pde_channel_mix_path(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, int32_t backward);
+/* How that path spreads its work: the return value is the number of walkers — workgroups of a backward kernel (= partial
+ * matrices in the workspace), workgroups of the 16-bit forward kernel, waves of the fp32-MFMA forward kernel — and
+ * *chunks (optional) the number of pixel chunks they share out, chunk c going to walker c % walkers.  chunks > walkers
+ * means some walkers take more than one trip of their loop.  The scalar forward kernel has no loop: walkers = chunks.
+ * PDE_E_BADARG as above. */
+int pde_channel_mix_splits(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, int32_t backward, int64_t* chunks);
 
 /* SVHN.py:73-74 skip connection: out = s*u0 + (1-s)*u with s = sigmoid(*skip_weight) (device scalar), n
  * elements of io_dtype, one pass.  Backward: g_u0 = s*g, g_u = (1-s)*g,
