@@ -162,6 +162,13 @@ SIGNATURES = {
                                             _vp, _vp, _fp, _fp, _vp, _vp, _sz, _vp]),
     "pde_sym_layer_f16_backward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _f32, _fp, _vp, _fp, _vp, _vp, _fp, _fp,
                                              _vp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "pde_sym_layer_bf16_supported": (C.c_int, [_i32, _i32]),
+    "pde_sym_layer_bf16_workspace_bytes": (_sz, [_i32, _i32]),
+    "pde_sym_k_to_bf16": (C.c_int, [_i32, _fp, _vp, _vp]),
+    "pde_sym_layer_bf16_forward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _vp, _fp, _fp, _fp, _fp, _f32, _f32, _fp, _f32,
+                                             _vp, _vp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_sym_layer_bf16_backward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _f32, _fp, _vp, _fp, _vp, _vp, _fp, _fp,
+                                              _vp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "pde_adi_f64_forward_workspace_bytes": (_sz, [_D64]),
     "pde_adi_f64_backward_workspace_bytes": (_sz, [_D64, _i32]),
     "pde_adi_f64_forward": (C.c_int, [_D64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -861,28 +861,57 @@ Tensor sym(const Tensor& X, const Tensor& K, const Tensor& gamma, const Tensor& 
     return SymFn::apply(X, K, gamma, beta, opt(base), opt(run_mean), opt(run_var), training, momentum, eps, scale, act, need_grad);
 }
 
-// ---- the same layer under fp16 autocast (functional._SymLayerF16Fn): fp16 operands, K16 = r(K) precomputed by the caller ----
-// out is fp16 without a base (F_sym), fp32 with one.  Scratch comes from the caching allocator for every call: nothing is
-// kept between calls (a captured graph owns what its capture allocated).
-Tensor sym_k16(const Tensor& K) {
+// ---- the same layer under fp16 / bf16 autocast (functional._SymLayerF16Fn, _SymLayerBf16Fn): 16-bit operands, K16 = r(K)
+// precomputed by the caller.  out is a 16-bit tensor without a base (F_sym), fp32 with one.  Scratch comes from the caching
+// allocator for every call: nothing is kept between calls (a captured graph owns what its capture allocated).
+// One implementation over the element's dtype and entry points; the two nodes differ in those alone.
+struct F16Api {
+    static constexpr at::ScalarType dtype = at::kHalf;
+    static constexpr auto k_to = &pde_sym_k_to_f16;
+    static constexpr auto workspace_bytes = &pde_sym_layer_f16_workspace_bytes;
+    static constexpr auto forward = &pde_sym_layer_f16_forward;
+    static constexpr auto backward = &pde_sym_layer_f16_backward;
+    static constexpr const char* k_to_name = "pde_sym_k_to_f16";
+    static constexpr const char* forward_name = "pde_sym_layer_f16_forward";
+    static constexpr const char* backward_name = "pde_sym_layer_f16_backward";
+    static constexpr const char* k16_msg = "expected X (B, D) and a contiguous fp16 K16 (D, D)";
+};
+struct Bf16Api {
+    static constexpr at::ScalarType dtype = at::kBFloat16;
+    static constexpr auto k_to = &pde_sym_k_to_bf16;
+    static constexpr auto workspace_bytes = &pde_sym_layer_bf16_workspace_bytes;
+    static constexpr auto forward = &pde_sym_layer_bf16_forward;
+    static constexpr auto backward = &pde_sym_layer_bf16_backward;
+    static constexpr const char* k_to_name = "pde_sym_k_to_bf16";
+    static constexpr const char* forward_name = "pde_sym_layer_bf16_forward";
+    static constexpr const char* backward_name = "pde_sym_layer_bf16_backward";
+    static constexpr const char* k16_msg = "expected X (B, D) and a contiguous bf16 K16 (D, D)";
+};
+
+template <class Api>
+Tensor sym_k16_as(const Tensor& K) {
     PDE_REQUIRE(K.is_cuda() && K.dim() == 2 && K.size(0) == K.size(1), "expected a square CUDA K");
     Tensor Kf = as_f32(K.detach());
     c10::hip::HIPGuardMasqueradingAsCUDA guard(K.device());
     hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(K.device().index()).stream();
-    Tensor K16 = at::empty(K.sizes(), Kf.options().dtype(at::kHalf));
-    check(pde_sym_k_to_f16((int32_t)K.size(0), Kf.data_ptr<float>(), reinterpret_cast<uint16_t*>(K16.data_ptr()), (void*)st),
-          "pde_sym_k_to_f16");
+    Tensor K16 = at::empty(K.sizes(), Kf.options().dtype(Api::dtype));
+    check(Api::k_to((int32_t)K.size(0), Kf.data_ptr<float>(), reinterpret_cast<uint16_t*>(K16.data_ptr()), (void*)st),
+          Api::k_to_name);
     return K16;
 }
+Tensor sym_k16(const Tensor& K) { return sym_k16_as<F16Api>(K); }
+Tensor sym_kbf16(const Tensor& K) { return sym_k16_as<Bf16Api>(K); }
 
-Tensor sym_f16_workspace(int64_t B, int64_t D, const Tensor& like) {
-    const size_t n = pde_sym_layer_f16_workspace_bytes((int32_t)B, (int32_t)D);
+template <class Api>
+Tensor sym16_workspace(int64_t B, int64_t D, const Tensor& like) {
+    const size_t n = Api::workspace_bytes((int32_t)B, (int32_t)D);
     return at::empty({(int64_t)n}, like.options().dtype(at::kByte));
 }
 
 uint16_t* h16(const Tensor& t) { return reinterpret_cast<uint16_t*>(t.data_ptr()); }
 
-struct SymF16Fn : public torch::autograd::Function<SymF16Fn> {
+template <class Fn, class Api>
+struct Sym16Node : public torch::autograd::Function<Fn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& X, const Tensor& K, const Tensor& K16, const Tensor& gamma,
                           const Tensor& beta, const std::optional<Tensor>& base, const std::optional<Tensor>& run_mean,
                           const std::optional<Tensor>& run_var, bool training, double momentum, double eps, double scale,
@@ -890,25 +919,25 @@ struct SymF16Fn : public torch::autograd::Function<SymF16Fn> {
         PDE_REQUIRE(X.is_cuda() && K16.is_cuda() && gamma.is_cuda() && beta.is_cuda() && (!base.has_value() || base->is_cuda()),
                     "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
         PDE_REQUIRE(X.dim() == 2 && K16.dim() == 2 && K16.size(0) == X.size(1) && K16.size(1) == X.size(1) &&
-                    K16.scalar_type() == at::kHalf && K16.is_contiguous(), "expected X (B, D) and a contiguous fp16 K16 (D, D)");
+                    K16.scalar_type() == Api::dtype && K16.is_contiguous(), Api::k16_msg);
         const int64_t B = X.size(0), D = X.size(1);
         Tensor Xf = as_f32(X), gm = as_f32(gamma), bt = as_f32(beta);
         Tensor bs = base.has_value() ? as_f32(*base) : Tensor();
         c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(X.device().index()).stream();
-        const auto h = Xf.options().dtype(at::kHalf);
+        const auto h = Xf.options().dtype(Api::dtype);
         Tensor P = at::empty({B, D}, h), H = at::empty({B, D}, h);
         Tensor out = bs.defined() ? at::empty({B, D}, Xf.options()) : at::empty({B, D}, h);
         Tensor mean = at::empty({D}, Xf.options()), invstd = at::empty({D}, Xf.options());
-        Tensor ws = sym_f16_workspace(B, D, Xf);
+        Tensor ws = sym16_workspace<Api>(B, D, Xf);
         float* rm = run_mean.has_value() ? run_mean->data_ptr<float>() : nullptr;
         float* rv = run_var.has_value() ? run_var->data_ptr<float>() : nullptr;
-        check(pde_sym_layer_f16_forward((int32_t)B, (int32_t)D, (int32_t)act, training ? 1 : 0, Xf.data_ptr<float>(), h16(K16),
-                                        gm.data_ptr<float>(), bt.data_ptr<float>(), rm, rv, (float)momentum, (float)eps,
-                                        bs.defined() ? bs.data_ptr<float>() : nullptr, (float)scale, h16(P), h16(H),
-                                        mean.data_ptr<float>(), invstd.data_ptr<float>(), out.data_ptr(), ws.data_ptr(),
-                                        (size_t)ws.numel(), (void*)st),
-              "pde_sym_layer_f16_forward");
+        check(Api::forward((int32_t)B, (int32_t)D, (int32_t)act, training ? 1 : 0, Xf.data_ptr<float>(), h16(K16),
+                           gm.data_ptr<float>(), bt.data_ptr<float>(), rm, rv, (float)momentum, (float)eps,
+                           bs.defined() ? bs.data_ptr<float>() : nullptr, (float)scale, h16(P), h16(H),
+                           mean.data_ptr<float>(), invstd.data_ptr<float>(), out.data_ptr(), ws.data_ptr(),
+                           (size_t)ws.numel(), (void*)st),
+              Api::forward_name);
         if (need_grad) {
             ctx->save_for_backward({Xf, K16, gm, P, H, mean, invstd});
             ctx->saved_data["cfg"] = std::vector<int64_t>{training ? 1 : 0, act, base.has_value() ? 1 : 0};
@@ -930,26 +959,29 @@ struct SymF16Fn : public torch::autograd::Function<SymF16Fn> {
         g = g.contiguous();
         Tensor dP = at::empty({B, D}, P.options()), gX = at::empty_like(Xf), gK = at::empty({D, D}, Xf.options());
         Tensor gg = at::empty({D}, Xf.options()), gb = at::empty({D}, Xf.options());
-        Tensor ws = sym_f16_workspace(B, D, Xf);
-        check(pde_sym_layer_f16_backward((int32_t)B, (int32_t)D, (int32_t)cfg[1], (int32_t)cfg[0], g.data_ptr<float>(), (float)scale,
-                                         Xf.data_ptr<float>(), h16(K16), gm.data_ptr<float>(), h16(P), h16(H),
-                                         mean.data_ptr<float>(), invstd.data_ptr<float>(), h16(dP), gX.data_ptr<float>(),
-                                         gK.data_ptr<float>(), gg.data_ptr<float>(), gb.data_ptr<float>(), ws.data_ptr(),
-                                         (size_t)ws.numel(), (void*)st),
-              "pde_sym_layer_f16_backward");
+        Tensor ws = sym16_workspace<Api>(B, D, Xf);
+        check(Api::backward((int32_t)B, (int32_t)D, (int32_t)cfg[1], (int32_t)cfg[0], g.data_ptr<float>(), (float)scale,
+                            Xf.data_ptr<float>(), h16(K16), gm.data_ptr<float>(), h16(P), h16(H),
+                            mean.data_ptr<float>(), invstd.data_ptr<float>(), h16(dP), gX.data_ptr<float>(),
+                            gK.data_ptr<float>(), gg.data_ptr<float>(), gb.data_ptr<float>(), ws.data_ptr(),
+                            (size_t)ws.numel(), (void*)st),
+              Api::backward_name);
         return {gX, gK, Tensor(), gg, gb, cfg[2] ? g : Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
                 Tensor(), Tensor()};
     }
 };
+struct SymF16Fn : public Sym16Node<SymF16Fn, F16Api> {};
+struct SymBf16Fn : public Sym16Node<SymBf16Fn, Bf16Api> {};
 
-Tensor sym_f16(const Tensor& X, const Tensor& K, const Tensor& K16, const Tensor& gamma, const Tensor& beta,
-               const std::optional<Tensor>& base, const std::optional<Tensor>& run_mean, const std::optional<Tensor>& run_var,
-               bool training, double momentum, double eps, double scale, int64_t act) {
+template <class Fn>
+Tensor sym16(const Tensor& X, const Tensor& K, const Tensor& K16, const Tensor& gamma, const Tensor& beta,
+             const std::optional<Tensor>& base, const std::optional<Tensor>& run_mean, const std::optional<Tensor>& run_var,
+             bool training, double momentum, double eps, double scale, int64_t act) {
     const bool need_grad = at::GradMode::is_enabled() && (X.requires_grad() || K.requires_grad() || gamma.requires_grad() ||
                                                           beta.requires_grad() || (base.has_value() && base->requires_grad()));
     auto opt = [](const std::optional<Tensor>& t) { return (t.has_value() && t->defined()) ? t : std::optional<Tensor>(); };
-    return SymF16Fn::apply(X, K, K16, gamma, beta, opt(base), opt(run_mean), opt(run_var), training, momentum, eps, scale, act,
-                           need_grad);
+    return Fn::apply(X, K, K16, gamma, beta, opt(base), opt(run_mean), opt(run_var), training, momentum, eps, scale, act,
+                     need_grad);
 }
 
 }  // namespace
@@ -988,7 +1020,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("running_var"), py::arg("training"), py::arg("momentum"), py::arg("eps"), py::arg("scale"), py::arg("act"));
     m.def("sym_k16", &sym_k16, "K16 = r(K): the fp16 copy of a symmetric layer's weight (one per autocast block forward)",
           py::arg("K"));
-    m.def("sym_f16", &sym_f16, "functional.sym_layer's fp16-operand autograd node (fp16 autocast's rounding points)",
+    m.def("sym_f16", &sym16<SymF16Fn>, "functional.sym_layer's fp16-operand autograd node (fp16 autocast's rounding points)",
+          py::arg("X"), py::arg("K"), py::arg("K16"), py::arg("gamma"), py::arg("beta"), py::arg("base"), py::arg("running_mean"),
+          py::arg("running_var"), py::arg("training"), py::arg("momentum"), py::arg("eps"), py::arg("scale"), py::arg("act"));
+    m.def("sym_kbf16", &sym_kbf16, "K16 = r(K): the bf16 copy of a symmetric layer's weight (one per autocast block forward)",
+          py::arg("K"));
+    m.def("sym_bf16", &sym16<SymBf16Fn>, "functional.sym_layer's bf16-operand autograd node (bf16 autocast's rounding points)",
           py::arg("X"), py::arg("K"), py::arg("K16"), py::arg("gamma"), py::arg("beta"), py::arg("base"), py::arg("running_mean"),
           py::arg("running_var"), py::arg("training"), py::arg("momentum"), py::arg("eps"), py::arg("scale"), py::arg("act"));
     m.def("set_error_class", [](py::object cls) {

@@ -945,12 +945,12 @@ int launch_part32(const float* X, const float* W, int B, int D, int S, void* ws,
     return rh_waves32(B) == 2 ? launch_part32_wv<NT, 2>(X, W, B, D, S, ws, st) : launch_part32_wv<NT, 4>(X, W, B, D, S, ws, st);
 }
 
-// ---- the layer under CUDA fp16 autocast: fp16 operands on v_mfma_f32_32x32x16_f16, fp32 accumulators ----------------------
+// ---- the layer under CUDA fp16 / bf16 autocast: 16-bit operands on v_mfma_f32_32x32x16_{f16,bf16}, fp32 accumulators --------
 // Same structure as the 32-column strips above (WV waves x 32 batch rows, the contraction of a strip split over S
 // workgroups, the partial tiles added in split order by the epilogue launch, which holds every row of its 8 columns and so
-// takes the BatchNorm statistics), with autocast's rounding points r() = round to fp16 (include/pdecnn.h):
+// takes the BatchNorm statistics), with autocast's rounding points r() = round to fp16 or to bf16 (include/pdecnn.h):
 // P = r(r(X) K16^T), N = r(BN(P)), H = r(act(N)), Q = r(H K16), out = base + r(scale Q).  The fp32 operands (X, the
-// incoming gradient) are rounded when they are staged in LDS; P, H and dP are fp16 tensors.  A slab is 64 contraction
+// incoming gradient) are rounded when they are staged in LDS; P, H and dP are 16-bit tensors.  A slab is 64 contraction
 // steps = four MFMAs per wave.  NT products read both operands row-wise (K16's rows are contiguous along k); the NN
 // products take K16's columns as the B operand through the transposing read ds_read_b64_tr_b16 of a [k][n] image.
 typedef _Float16 rh_h8 __attribute__((ext_vector_type(8)));
@@ -958,18 +958,37 @@ __device__ __forceinline__ unsigned short rh_f2h(float f) { return __builtin_bit
 __device__ __forceinline__ float rh_h2f(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
 __device__ __forceinline__ float rh_r16(float f) { return (float)(_Float16)f; }
 
-constexpr int kH16Bk = 64;                     // contraction steps per slab
+// The 16-bit element of the layer: every kernel below is written once over E.  RhF16 is fp16 autocast; RhBf16 is bf16
+// autocast — the same contract with r() = round to nearest even to bf16 (v_cvt_pk_bf16_f32; fp32's exponent range, so
+// nothing overflows) on v_mfma_f32_32x32x16_bf16, whose operand and accumulator lane maps are those of the f16 form:
+// lane (h, r) holds A[r][8h + j] and B[8h + j][r] in element j = 0..7 (what rh_outer_split_kernel above relies on too).
+struct RhF16 {
+    typedef rh_h8 v8;
+    static __device__ __forceinline__ unsigned short bits(float f) { return rh_f2h(f); }
+    static __device__ __forceinline__ float val(unsigned short h) { return rh_h2f(h); }
+    static __device__ __forceinline__ float r(float f) { return rh_r16(f); }
+    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+struct RhBf16 {
+    typedef rh_v8bf v8;
+    static __device__ __forceinline__ unsigned short bits(float f) { return rh_f2bf(f); }
+    static __device__ __forceinline__ float val(unsigned short h) { return rh_bf2f(h); }
+    static __device__ __forceinline__ float r(float f) { return rh_bf2f(rh_f2bf(f)); }
+    static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+
+constexpr int kH16Bk = 64;                    // contraction steps per slab
 constexpr int kH16Pitch = kH16Bk * 2 + 16;      // bytes per row of a [row][k] image (144: 16 B of padding)
 constexpr int kH16NnPitch = kS32Cols * 2 + 16;  // bytes per k row of the NN product's [k][n] image of K16 (80)
 
-// A operand of a strip product: fp32 (X, the upstream gradient: a = r(x), then a = r(ascale a) where dbl) or fp16 bits
+// A operand of a strip product: fp32 (X, the upstream gradient: a = r(x), then a = r(ascale a) where dbl) or 16-bit patterns
 struct RhPart16Args {
     const void* A; const unsigned short* W; float* part;
     int B, D, S, dbl;
     float ascale;
 };
 
-template <bool NT, int WV, bool AF32>
+template <class E, bool NT, int WV, bool AF32>
 __global__ __launch_bounds__(WV * 64) void rh_part16_kernel(RhPart16Args a) {
     constexpr int THREADS = WV * 64, ROWS = WV * 32, BK = kH16Bk;
     constexpr int ABYTES = ROWS * kH16Pitch;
@@ -1014,9 +1033,9 @@ __global__ __launch_bounds__(WV * 64) void rh_part16_kernel(RhPart16Args a) {
                 unsigned short h[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float x = rh_r16(v[j]);
+                    float x = E::r(v[j]);
                     if (a.dbl) x = a.ascale * x;
-                    h[j] = row < a.B ? rh_f2h(x) : (unsigned short)0;
+                    h[j] = row < a.B ? E::bits(x) : (unsigned short)0;
                 }
                 *reinterpret_cast<uint2*>(As + row * kH16Pitch + 8 * c) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
             } else {
@@ -1040,14 +1059,15 @@ __global__ __launch_bounds__(WV * 64) void rh_part16_kernel(RhPart16Args a) {
         const unsigned char* Ws = As + ABYTES;
 #pragma unroll
         for (int t = 0; t < BK / 16; ++t) {               // lane (kh, jj): row / column jj, k = 16 t + 8 kh + (0..7)
-            const rh_h8 av = *reinterpret_cast<const rh_h8*>(As + (wave * 32 + jj) * kH16Pitch + (16 * t + 8 * kh) * 2);
-            rh_h8 bv;
+            typedef typename E::v8 v8;
+            const v8 av = *reinterpret_cast<const v8*>(As + (wave * 32 + jj) * kH16Pitch + (16 * t + 8 * kh) * 2);
+            v8 bv;
             if (NT) {
-                bv = *reinterpret_cast<const rh_h8*>(Ws + jj * kH16Pitch + (16 * t + 8 * kh) * 2);
+                bv = *reinterpret_cast<const v8*>(Ws + jj * kH16Pitch + (16 * t + 8 * kh) * 2);
             } else {
-                bv = __builtin_bit_cast(rh_h8, rh_tr_operand<kH16NnPitch>(Ws + 16 * t * kH16NnPitch, 0, lane));
+                bv = __builtin_bit_cast(v8, rh_tr_operand<kH16NnPitch>(Ws + 16 * t * kH16NnPitch, 0, lane));
             }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, acc, 0, 0, 0);
+            acc = E::mfma(av, bv, acc);
         }
         if (more) stage(buf ^ 1);                         // the other buffer: last read one barrier ago
         __syncthreads();
@@ -1064,13 +1084,14 @@ struct Rh16FwdArgs {
     float momentum, eps;
 };
 
-// P = r(sum of the partial tiles); BatchNorm1d statistics in fp32 over the fp16 values of P; N = r(BN(P)), H = r(act(N))
+// P = r(sum of the partial tiles); BatchNorm1d statistics in fp32 over the 16-bit values of P; N = r(BN(P)), H = r(act(N))
+template <class E>
 __global__ __launch_bounds__(256) void rh_fwd16_epi_kernel(Rh16FwdArgs a, const float* part, int S) {
     __shared__ float red[32];
     const Epi32 e(blockIdx.x, blockIdx.y);
     f32x4 acc = strip32_sum(part, blockIdx.x, blockIdx.y, S, e);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = rh_r16(acc[r]);  // padded rows hold exact zeros
+    for (int r = 0; r < 4; ++r) acc[r] = E::r(acc[r]);    // padded rows hold exact zeros
     const int col = e.col;
     float mu, istd;
     if (a.training) {
@@ -1099,16 +1120,17 @@ __global__ __launch_bounds__(256) void rh_fwd16_epi_kernel(Rh16FwdArgs a, const 
         const int row = e.row0 + r;
         if (row < a.B) {
             const float p = acc[r];
-            const float n = rh_r16(fmaf((p - mu) * istd, g, bt));
-            a.P[(size_t)row * a.D + col] = rh_f2h(p);
-            a.H[(size_t)row * a.D + col] = rh_f2h(act_fwd(n, a.act));
+            const float n = E::r(fmaf((p - mu) * istd, g, bt));
+            a.P[(size_t)row * a.D + col] = E::bits(p);
+            a.H[(size_t)row * a.D + col] = E::bits(act_fwd(n, a.act));
         }
     }
 }
 
 struct Rh16OutArgs { const float* base; void* out; int B, D; float scale; };
 
-// Q = r(sum of the partial tiles); out = base + r(scale Q) in fp32, or r(scale Q) as fp16 without a base
+// Q = r(sum of the partial tiles); out = base + r(scale Q) in fp32, or r(scale Q) as a 16-bit tensor without a base
+template <class E>
 __global__ __launch_bounds__(256) void rh_out16_epi_kernel(Rh16OutArgs a, const float* part, int S) {
     const Epi32 e(blockIdx.x, blockIdx.y);
     const f32x4 acc = strip32_sum(part, blockIdx.x, blockIdx.y, S, e);
@@ -1117,9 +1139,9 @@ __global__ __launch_bounds__(256) void rh_out16_epi_kernel(Rh16OutArgs a, const 
         const int row = e.row0 + r;
         if (row < a.B) {
             const size_t o = (size_t)row * a.D + e.col;
-            const float v = rh_r16(a.scale * rh_r16(acc[r]));
+            const float v = E::r(a.scale * E::r(acc[r]));
             if (a.base != nullptr) static_cast<float*>(a.out)[o] = a.base[o] + v;
-            else static_cast<unsigned short*>(a.out)[o] = rh_f2h(v);
+            else static_cast<unsigned short*>(a.out)[o] = E::bits(v);
         }
     }
 }
@@ -1131,6 +1153,7 @@ struct Rh16BwdArgs {
 };
 
 // dH = sum of the partial tiles of gQ K16^T (fp32); through the activation and the BatchNorm -> dP = r(...), dgamma, dbeta
+template <class E>
 __global__ __launch_bounds__(256) void rh_bwd16_epi_kernel(Rh16BwdArgs a, const float* part, int S) {
     __shared__ float red[32];
     const Epi32 e(blockIdx.x, blockIdx.y);
@@ -1145,8 +1168,8 @@ __global__ __launch_bounds__(256) void rh_bwd16_epi_kernel(Rh16BwdArgs a, const 
         float dhn = 0.f, xhat = 0.f;
         if (row < a.B) {
             const size_t o = (size_t)row * a.D + col;
-            dhn = acc[r] * act_bwd(rh_h2f(a.H[o]), a.act);
-            xhat = (rh_h2f(a.P[o]) - mu) * istd;
+            dhn = acc[r] * act_bwd(E::val(a.H[o]), a.act);
+            xhat = (E::val(a.P[o]) - mu) * istd;
         }
         acc[r] = dhn;
         xh[r] = xhat;
@@ -1163,7 +1186,7 @@ __global__ __launch_bounds__(256) void rh_bwd16_epi_kernel(Rh16BwdArgs a, const 
         if (row < a.B) {
             const float dhn = acc[r];
             const float dp = a.training ? g * istd * (dhn - (dbeta + xh[r] * dgamma) * inv_b) : g * istd * dhn;
-            a.dP[(size_t)row * a.D + col] = rh_f2h(dp);
+            a.dP[(size_t)row * a.D + col] = E::bits(dp);
         }
     }
 }
@@ -1175,15 +1198,15 @@ struct RhOuter16Args {
     float s2;
 };
 
-// out[i][j] = sum_b A1[b][i] r(B1[b][j]) + sum_b A2[b][i] r(s2 r(B2[b][j])): dK = dP^T r(X) + H^T gQ with fp16 operands.
-// The 64 x 192 tiles of rh_outer_split_kernel with one fp16 piece instead of three bf16 ones: a slab is 16 batch rows
+// out[i][j] = sum_b A1[b][i] r(B1[b][j]) + sum_b A2[b][i] r(s2 r(B2[b][j])): dK = dP^T r(X) + H^T gQ with 16-bit operands.
+// The 64 x 192 tiles of rh_outer_split_kernel with one piece (fp16 or bf16) instead of three bf16 ones: a slab is 16 batch rows
 // (one contraction group) deposited as [batch row][feature] images, both operands through ds_read_b64_tr_b16.
-template <int TI, int TJ>
+template <class E, int TI, int TJ>
 __global__ __launch_bounds__(kRhThreads) void rh_outer16_kernel(RhOuter16Args a) {
     constexpr int BKB = 16, NI = TI / 64, NJ = TJ / 64;
     constexpr int PA = TI * 2 + 16, PB = TJ * 2 + 16;      // bytes per image row (16 bytes of padding)
     constexpr int IA = BKB * PA, BUF = BKB * (PA + PB);
-    constexpr int AC = TI / 8, BC = TJ / 4;                // 16-byte loads per batch row: fp16 A, fp32 B
+    constexpr int AC = TI / 8, BC = TJ / 4;                // 16-byte loads per batch row: 16-bit A, fp32 B
     constexpr int APT = (BKB * AC + kRhThreads - 1) / kRhThreads, BPT = BKB * BC / kRhThreads;
     static_assert(BKB * BC % kRhThreads == 0 && TI % 64 == 0 && TJ % 64 == 0, "tile shape");
     __shared__ __attribute__((aligned(16))) unsigned char S[2][BUF];
@@ -1232,7 +1255,7 @@ __global__ __launch_bounds__(kRhThreads) void rh_outer16_kernel(RhOuter16Args a)
             const float v[4] = {pb[m].x, pb[m].y, pb[m].z, pb[m].w};
             unsigned short h[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) h[j] = rh_f2h(second ? a.s2 * rh_r16(v[j]) : v[j]);
+            for (int j = 0; j < 4; ++j) h[j] = E::bits(second ? a.s2 * E::r(v[j]) : v[j]);
             *reinterpret_cast<uint2*>(base + IA + row * PB + 8 * c) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
         }
     };
@@ -1246,14 +1269,15 @@ __global__ __launch_bounds__(kRhThreads) void rh_outer16_kernel(RhOuter16Args a)
         if (more) fetch(v + BKB);
         const unsigned char* ia = S[buf];
         const unsigned char* ib = ia + IA;
-        rh_h8 af[NI];
+        typedef typename E::v8 v8;
+        v8 af[NI];
 #pragma unroll
-        for (int p = 0; p < NI; ++p) af[p] = __builtin_bit_cast(rh_h8, rh_tr_operand<PA>(ia, wi * NI + p, lane));
+        for (int p = 0; p < NI; ++p) af[p] = __builtin_bit_cast(v8, rh_tr_operand<PA>(ia, wi * NI + p, lane));
 #pragma unroll
         for (int q = 0; q < NJ; ++q) {
-            const rh_h8 bf = __builtin_bit_cast(rh_h8, rh_tr_operand<PB>(ib, wj * NJ + q, lane));
+            const v8 bf = __builtin_bit_cast(v8, rh_tr_operand<PB>(ib, wj * NJ + q, lane));
 #pragma unroll
-            for (int p = 0; p < NI; ++p) acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[p], bf, acc[p][q], 0, 0, 0);
+            for (int p = 0; p < NI; ++p) acc[p][q] = E::mfma(af[p], bf, acc[p][q]);
         }
         if (more) stage(buf ^ 1, v + BKB >= Bp);          // the other buffer: last read one barrier ago
         __syncthreads();
@@ -1272,10 +1296,11 @@ __global__ __launch_bounds__(kRhThreads) void rh_outer16_kernel(RhOuter16Args a)
 }
 
 // K16 = r(K), four elements per thread
+template <class E>
 __global__ __launch_bounds__(256) void rh_k_to_f16_kernel(const float* __restrict__ K, unsigned short* __restrict__ K16, size_t n4) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         const float4 v = reinterpret_cast<const float4*>(K)[i];
-        reinterpret_cast<uint2*>(K16)[i] = make_uint2(rh_f2h(v.x) | (rh_f2h(v.y) << 16), rh_f2h(v.z) | (rh_f2h(v.w) << 16));
+        reinterpret_cast<uint2*>(K16)[i] = make_uint2(E::bits(v.x) | (E::bits(v.y) << 16), E::bits(v.z) | (E::bits(v.w) << 16));
     }
 }
 
@@ -1288,12 +1313,80 @@ int rh_split16(int D) {
 }
 size_t rh_split16_bytes(int B, int D) { return (size_t)(D / kS32Cols) * rh_split16(D) * tile32_floats(rh_waves32(B)) * sizeof(float); }
 
-template <bool NT, bool AF32>
+template <class E, bool NT, bool AF32>
 int launch_part16(const void* A, const unsigned short* W, int B, int D, float ascale, int dbl, void* ws, hipStream_t st) {
     const int S = rh_split16(D);
     RhPart16Args a{A, W, static_cast<float*>(ws), B, D, S, dbl, ascale};
-    if (rh_waves32(B) == 2) hipLaunchKernelGGL((rh_part16_kernel<NT, 2, AF32>), dim3(D / kS32Cols, S), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL((rh_part16_kernel<NT, 4, AF32>), dim3(D / kS32Cols, S), dim3(256), 0, st, a);
+    if (rh_waves32(B) == 2) hipLaunchKernelGGL((rh_part16_kernel<E, NT, 2, AF32>), dim3(D / kS32Cols, S), dim3(128), 0, st, a);
+    else hipLaunchKernelGGL((rh_part16_kernel<E, NT, 4, AF32>), dim3(D / kS32Cols, S), dim3(256), 0, st, a);
+    return check_launch();
+}
+
+
+// host side of the 16-bit layer, once over E: argument checks, then the launches in a fixed order
+template <class E>
+int sym16_k_to(int32_t D, const float* K, uint16_t* K16, void* stream) {
+    if (D < 64 || (D % 64) != 0 || !K || !K16) return PDE_E_BADARG;
+    const size_t n4 = (size_t)D * D / 4;
+    const int blocks = (int)(n4 / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+    hipLaunchKernelGGL(rh_k_to_f16_kernel<E>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), K, K16, n4);
+    return check_launch();
+}
+
+template <class E>
+int sym16_forward(int32_t B, int32_t D, int32_t act, int32_t training, const float* X, const uint16_t* K16,
+                  const float* bn_weight, const float* bn_bias, float* running_mean, float* running_var,
+                  float momentum, float eps, const float* base, float scale, uint16_t* P, uint16_t* H,
+                  float* mean, float* invstd, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!rh16_dims_ok(B, D)) return PDE_E_BADARG;
+    if (!X || !K16 || !bn_weight || !bn_bias || !P || !H || !mean || !invstd || !out) return PDE_E_BADARG;
+    if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
+    if (!training && (!running_mean || !running_var)) return PDE_E_BADARG;
+    if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = rh_split16(D), thr = 64 * rh_waves32(B);
+    const float* part = static_cast<const float*>(workspace);
+    int rc = launch_part16<E, true, true>(X, K16, B, D, 1.0f, 0, workspace, st);
+    if (rc != PDE_OK) return rc;
+    Rh16FwdArgs f{bn_weight, bn_bias, running_mean, running_var, P, H, mean, invstd, B, D, act, training ? 1 : 0, momentum, eps};
+    hipLaunchKernelGGL(rh_fwd16_epi_kernel<E>, dim3(D / kS32Cols, 4), dim3(thr), 0, st, f, part, S);
+    if ((rc = check_launch()) != PDE_OK) return rc;
+    rc = launch_part16<E, false, false>(H, K16, B, D, 1.0f, 0, workspace, st);
+    if (rc != PDE_OK) return rc;
+    Rh16OutArgs o{base, out, B, D, scale};
+    hipLaunchKernelGGL(rh_out16_epi_kernel<E>, dim3(D / kS32Cols, 4), dim3(thr), 0, st, o, part, S);
+    return check_launch();
+}
+
+template <class E>
+int sym16_backward(int32_t B, int32_t D, int32_t act, int32_t training, const float* g_out, float scale,
+                   const float* X, const uint16_t* K16, const float* bn_weight, const uint16_t* P,
+                   const uint16_t* H, const float* mean, const float* invstd, uint16_t* dP, float* gX,
+                   float* gK, float* g_bn_weight, float* g_bn_bias, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+    if (!rh16_dims_ok(B, D)) return PDE_E_BADARG;
+    if (!g_out || !X || !K16 || !bn_weight || !P || !H || !mean || !invstd || !dP || !gX || !gK || !g_bn_weight || !g_bn_bias)
+        return PDE_E_BADARG;
+    if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
+    if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = rh_split16(D), thr = 64 * rh_waves32(B);
+    const float* part = static_cast<const float*>(workspace);
+    int rc = launch_part16<E, true, true>(g_out, K16, B, D, scale, 1, workspace, st);    // gQ = r(scale r(g)) staged
+    if (rc != PDE_OK) return rc;
+    Rh16BwdArgs b{bn_weight, P, H, mean, invstd, dP, g_bn_weight, g_bn_bias, B, D, act, training ? 1 : 0};
+    hipLaunchKernelGGL(rh_bwd16_epi_kernel<E>, dim3(D / kS32Cols, 4), dim3(thr), 0, st, b, part, S);
+    if ((rc = check_launch()) != PDE_OK) return rc;
+    rc = launch_part16<E, false, false>(dP, K16, B, D, 1.0f, 0, workspace, st);
+    if (rc != PDE_OK) return rc;
+    RhAxpyArgs x{nullptr, nullptr, nullptr, gX, B, D, 1.0f};
+    hipLaunchKernelGGL(rh_axpy32_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, x, part, S);
+    if ((rc = check_launch()) != PDE_OK) return rc;
+    RhOuter16Args o{dP, X, H, g_out, gK, B, D, scale};
+    hipLaunchKernelGGL((rh_outer16_kernel<E, kOutTi, kOutTj>), dim3((D + kOutTj - 1) / kOutTj, (D + kOutTi - 1) / kOutTi),
+                       dim3(kRhThreads), 0, st, o);
     return check_launch();
 }
 
@@ -1407,37 +1500,14 @@ int pde_sym_layer_f16_supported(int32_t B, int32_t D) { return rh16_dims_ok(B, D
 
 size_t pde_sym_layer_f16_workspace_bytes(int32_t B, int32_t D) { return rh16_dims_ok(B, D) ? rh_split16_bytes(B, D) : 0; }
 
-int pde_sym_k_to_f16(int32_t D, const float* K, uint16_t* K16, void* stream) {
-    if (D < 64 || (D % 64) != 0 || !K || !K16) return PDE_E_BADARG;
-    const size_t n4 = (size_t)D * D / 4;
-    const int blocks = (int)(n4 / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(rh_k_to_f16_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), K, K16, n4);
-    return check_launch();
-}
+int pde_sym_k_to_f16(int32_t D, const float* K, uint16_t* K16, void* stream) { return sym16_k_to<RhF16>(D, K, K16, stream); }
 
 int pde_sym_layer_f16_forward(int32_t B, int32_t D, int32_t act, int32_t training, const float* X, const uint16_t* K16,
                               const float* bn_weight, const float* bn_bias, float* running_mean, float* running_var,
                               float momentum, float eps, const float* base, float scale, uint16_t* P, uint16_t* H,
                               float* mean, float* invstd, void* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!rh16_dims_ok(B, D)) return PDE_E_BADARG;
-    if (!X || !K16 || !bn_weight || !bn_bias || !P || !H || !mean || !invstd || !out) return PDE_E_BADARG;
-    if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
-    if (!training && (!running_mean || !running_var)) return PDE_E_BADARG;
-    if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return PDE_E_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int S = rh_split16(D), thr = 64 * rh_waves32(B);
-    const float* part = static_cast<const float*>(workspace);
-    int rc = launch_part16<true, true>(X, K16, B, D, 1.0f, 0, workspace, st);
-    if (rc != PDE_OK) return rc;
-    Rh16FwdArgs f{bn_weight, bn_bias, running_mean, running_var, P, H, mean, invstd, B, D, act, training ? 1 : 0, momentum, eps};
-    hipLaunchKernelGGL(rh_fwd16_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, f, part, S);
-    if ((rc = check_launch()) != PDE_OK) return rc;
-    rc = launch_part16<false, false>(H, K16, B, D, 1.0f, 0, workspace, st);
-    if (rc != PDE_OK) return rc;
-    Rh16OutArgs o{base, out, B, D, scale};
-    hipLaunchKernelGGL(rh_out16_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, o, part, S);
-    return check_launch();
+    return sym16_forward<RhF16>(B, D, act, training, X, K16, bn_weight, bn_bias, running_mean, running_var, momentum, eps, base,
+                              scale, P, H, mean, invstd, out, workspace, workspace_bytes, stream);
 }
 
 int pde_sym_layer_f16_backward(int32_t B, int32_t D, int32_t act, int32_t training, const float* g_out, float scale,
@@ -1445,29 +1515,36 @@ int pde_sym_layer_f16_backward(int32_t B, int32_t D, int32_t act, int32_t traini
                                const uint16_t* H, const float* mean, const float* invstd, uint16_t* dP, float* gX,
                                float* gK, float* g_bn_weight, float* g_bn_bias, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    if (!rh16_dims_ok(B, D)) return PDE_E_BADARG;
-    if (!g_out || !X || !K16 || !bn_weight || !P || !H || !mean || !invstd || !dP || !gX || !gK || !g_bn_weight || !g_bn_bias)
-        return PDE_E_BADARG;
-    if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
-    if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return PDE_E_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int S = rh_split16(D), thr = 64 * rh_waves32(B);
-    const float* part = static_cast<const float*>(workspace);
-    int rc = launch_part16<true, true>(g_out, K16, B, D, scale, 1, workspace, st);       // gQ = r(scale r(g)) staged
-    if (rc != PDE_OK) return rc;
-    Rh16BwdArgs b{bn_weight, P, H, mean, invstd, dP, g_bn_weight, g_bn_bias, B, D, act, training ? 1 : 0};
-    hipLaunchKernelGGL(rh_bwd16_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, b, part, S);
-    if ((rc = check_launch()) != PDE_OK) return rc;
-    rc = launch_part16<false, false>(dP, K16, B, D, 1.0f, 0, workspace, st);
-    if (rc != PDE_OK) return rc;
-    RhAxpyArgs x{nullptr, nullptr, nullptr, gX, B, D, 1.0f};
-    hipLaunchKernelGGL(rh_axpy32_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, x, part, S);
-    if ((rc = check_launch()) != PDE_OK) return rc;
-    RhOuter16Args o{dP, X, H, g_out, gK, B, D, scale};
-    hipLaunchKernelGGL((rh_outer16_kernel<kOutTi, kOutTj>), dim3((D + kOutTj - 1) / kOutTj, (D + kOutTi - 1) / kOutTi),
-                       dim3(kRhThreads), 0, st, o);
-    return check_launch();
+    return sym16_backward<RhF16>(B, D, act, training, g_out, scale, X, K16, bn_weight, P, H, mean, invstd, dP, gX, gK,
+                               g_bn_weight, g_bn_bias, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+// ---- the bf16-operand layer (CUDA bf16 autocast's rounding points): same shapes, same workspace, same checks ----
+extern "C" {
+
+int pde_sym_layer_bf16_supported(int32_t B, int32_t D) { return rh16_dims_ok(B, D) ? 1 : 0; }
+
+size_t pde_sym_layer_bf16_workspace_bytes(int32_t B, int32_t D) { return rh16_dims_ok(B, D) ? rh_split16_bytes(B, D) : 0; }
+
+int pde_sym_k_to_bf16(int32_t D, const float* K, uint16_t* K16, void* stream) { return sym16_k_to<RhBf16>(D, K, K16, stream); }
+
+int pde_sym_layer_bf16_forward(int32_t B, int32_t D, int32_t act, int32_t training, const float* X, const uint16_t* K16,
+                              const float* bn_weight, const float* bn_bias, float* running_mean, float* running_var,
+                              float momentum, float eps, const float* base, float scale, uint16_t* P, uint16_t* H,
+                              float* mean, float* invstd, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return sym16_forward<RhBf16>(B, D, act, training, X, K16, bn_weight, bn_bias, running_mean, running_var, momentum, eps, base,
+                              scale, P, H, mean, invstd, out, workspace, workspace_bytes, stream);
+}
+
+int pde_sym_layer_bf16_backward(int32_t B, int32_t D, int32_t act, int32_t training, const float* g_out, float scale,
+                               const float* X, const uint16_t* K16, const float* bn_weight, const uint16_t* P,
+                               const uint16_t* H, const float* mean, const float* invstd, uint16_t* dP, float* gX,
+                               float* gK, float* g_bn_weight, float* g_bn_bias, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    return sym16_backward<RhBf16>(B, D, act, training, g_out, scale, X, K16, bn_weight, P, H, mean, invstd, dP, gX, gK,
+                               g_bn_weight, g_bn_bias, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

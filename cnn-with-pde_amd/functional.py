@@ -19,7 +19,7 @@ from . import _lib as L
 
 __all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_mixed", "adi_diffuse_small", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse",
            "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
-           "sym_layer_f16_supported", "sym_k16"]
+           "sym_layer_f16_supported", "sym_layer_bf16_supported", "sym_k16"]
 
 
 @dataclass(frozen=True)
@@ -1267,17 +1267,24 @@ def sym_layer_supported(X, bn) -> bool:
     return bool(L.load().pde_sym_layer_supported(B, D))
 
 
-def sym_k16(K):
-    """``K16 = r(K)``: the fp16 copy of a symmetric layer's (D, D) weight that fp16 autocast makes once per region; the
-    fp16-operand ``sym_layer`` takes it.  Not differentiable (the layer's gradient goes to K)."""
+def sym_k16(K, dtype=torch.float16):
+    """``K16 = r(K)``: the 16-bit copy of a symmetric layer's (D, D) weight that autocast makes once per region — fp16
+    (the default) or ``torch.bfloat16``; the 16-bit-operand ``sym_layer`` takes it and picks its route by the copy's
+    dtype.  Not differentiable (the layer's gradient goes to K)."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"sym_k16 makes an fp16 or a bf16 copy, not {dtype}")
+    bf = dtype == torch.bfloat16
     H_ = L.host_ext()
     if H_ is not None and K.is_cuda:
-        return H_.sym_k16(K)
+        return H_.sym_kbf16(K) if bf else H_.sym_k16(K)
     _require_cuda(K)
     Kf = K.detach().to(torch.float32).contiguous()
-    K16 = torch.empty(K.shape, dtype=torch.float16, device=K.device)
+    K16 = torch.empty(K.shape, dtype=dtype, device=K.device)
     with torch.cuda.device(K.device):
-        L.check(L.load().pde_sym_k_to_f16(K.shape[0], _ptr(Kf), _ptr(K16), _stream()), "pde_sym_k_to_f16")
+        if bf:
+            L.check(L.load().pde_sym_k_to_bf16(K.shape[0], _ptr(Kf), _ptr(K16), _stream()), "pde_sym_k_to_bf16")
+        else:
+            L.check(L.load().pde_sym_k_to_f16(K.shape[0], _ptr(Kf), _ptr(K16), _stream()), "pde_sym_k_to_f16")
     return K16
 
 
@@ -1298,6 +1305,70 @@ def sym_layer_f16_supported(X, bn) -> bool:
     return bool(L.load().pde_sym_layer_f16_supported(B, X[0].numel()))
 
 
+def sym_layer_bf16_supported(X, bn) -> bool:
+    """Whether the bf16-operand ``sym_layer`` takes this input under ``torch.autocast("cuda", torch.bfloat16)``: the
+    rules of ``sym_layer_f16_supported`` with autocast on for CUDA in bf16."""
+    dtype = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+    if not (torch.is_autocast_enabled() and dtype == torch.bfloat16):
+        return False
+    if not (X.is_cuda and X.dtype == torch.float32 and X.dim() >= 2 and X.shape[0] > 0):
+        return False
+    if bn.weight is None or bn.bias is None or (bn.momentum is None and bn.track_running_stats):
+        return False
+    B = X.shape[0]
+    if B > SYM_LAYER_MAX_ROWS or (B == 1 and (bn.training or bn.running_mean is None)):
+        return False
+    return bool(L.load().pde_sym_layer_bf16_supported(B, X[0].numel()))
+
+
+def _sym16_forward(ctx, tag, dtype, X, K16, gamma, beta, base, running_mean, running_var, training, momentum, eps, scale, act):
+    """Forward of the 16-bit-operand symmetric layer through ``pde_sym_layer_<tag>_forward`` (tag "f16" or "bf16")."""
+    lib = L.load()
+    _require_cuda(X, K16, gamma, beta, base)
+    B, D = X.shape
+    Xf = X.to(torch.float32).contiguous()
+    gm = gamma.detach().to(torch.float32).contiguous()
+    bt = beta.detach().to(torch.float32).contiguous()
+    bs = None if base is None else base.to(torch.float32).contiguous()
+    dev = X.device
+    P = torch.empty((B, D), dtype=dtype, device=dev)
+    H = torch.empty_like(P)
+    out = torch.empty((B, D), dtype=dtype if bs is None else torch.float32, device=dev)
+    mean = torch.empty(D, dtype=torch.float32, device=dev)
+    invstd = torch.empty_like(mean)
+    name = f"pde_sym_layer_{tag}_forward"
+    with torch.cuda.device(dev):
+        ws = torch.empty(getattr(lib, f"pde_sym_layer_{tag}_workspace_bytes")(B, D), dtype=torch.uint8, device=dev)
+        L.check(getattr(lib, name)(B, D, act, 1 if training else 0, _ptr(Xf), _ptr(K16), _ptr(gm), _ptr(bt),
+                                   _ptr(running_mean), _ptr(running_var), float(momentum), float(eps), _ptr(bs),
+                                   float(scale), _ptr(P), _ptr(H), _ptr(mean), _ptr(invstd), _ptr(out), _ptr(ws),
+                                   ws.numel(), _stream()), name)
+    ctx.save_for_backward(Xf, K16, gm, P, H, mean, invstd)
+    ctx.cfg = (bool(training), float(scale), int(act), base is not None)
+    return out
+
+
+def _sym16_backward(ctx, tag, gout):
+    lib = L.load()
+    Xf, K16, gm, P, H, mean, invstd = ctx.saved_tensors
+    training, scale, act, has_base = ctx.cfg
+    B, D = Xf.shape
+    g = gout.to(torch.float32).contiguous()
+    dev = Xf.device
+    dP = torch.empty_like(P)
+    gX = torch.empty_like(Xf)
+    gK = torch.empty((D, D), dtype=torch.float32, device=dev)
+    gg = torch.empty(D, dtype=torch.float32, device=dev)
+    gb = torch.empty_like(gg)
+    name = f"pde_sym_layer_{tag}_backward"
+    with torch.cuda.device(dev):
+        ws = torch.empty(getattr(lib, f"pde_sym_layer_{tag}_workspace_bytes")(B, D), dtype=torch.uint8, device=dev)
+        L.check(getattr(lib, name)(B, D, act, 1 if training else 0, _ptr(g), float(scale), _ptr(Xf), _ptr(K16), _ptr(gm),
+                                   _ptr(P), _ptr(H), _ptr(mean), _ptr(invstd), _ptr(dP), _ptr(gX), _ptr(gK), _ptr(gg),
+                                   _ptr(gb), _ptr(ws), ws.numel(), _stream()), name)
+    return gX, gK, None, gg, gb, (g if has_base else None), None, None, None, None, None, None, None
+
+
 class _SymLayerF16Fn(torch.autograd.Function):
     """The fp16-operand symmetric layer (pde_rh.hip: fp16 autocast's rounding points on the fp16 matrix cores): ctypes twin
     of the C++ node ``sym_f16`` (csrc/host_ext.cpp), same calls in the same order.  Scratch from the caching allocator
@@ -1305,49 +1376,26 @@ class _SymLayerF16Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, K, K16, gamma, beta, base, running_mean, running_var, training, momentum, eps, scale, act):
-        lib = L.load()
-        _require_cuda(X, K16, gamma, beta, base)
-        B, D = X.shape
-        Xf = X.to(torch.float32).contiguous()
-        gm = gamma.detach().to(torch.float32).contiguous()
-        bt = beta.detach().to(torch.float32).contiguous()
-        bs = None if base is None else base.to(torch.float32).contiguous()
-        dev = X.device
-        P = torch.empty((B, D), dtype=torch.float16, device=dev)
-        H = torch.empty_like(P)
-        out = torch.empty((B, D), dtype=torch.float16 if bs is None else torch.float32, device=dev)
-        mean = torch.empty(D, dtype=torch.float32, device=dev)
-        invstd = torch.empty_like(mean)
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.pde_sym_layer_f16_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
-            L.check(lib.pde_sym_layer_f16_forward(B, D, act, 1 if training else 0, _ptr(Xf), _ptr(K16), _ptr(gm), _ptr(bt),
-                                                  _ptr(running_mean), _ptr(running_var), float(momentum), float(eps),
-                                                  _ptr(bs), float(scale), _ptr(P), _ptr(H), _ptr(mean), _ptr(invstd),
-                                                  _ptr(out), _ptr(ws), ws.numel(), _stream()), "pde_sym_layer_f16_forward")
-        ctx.save_for_backward(Xf, K16, gm, P, H, mean, invstd)
-        ctx.cfg = (bool(training), float(scale), int(act), base is not None)
-        return out
+        return _sym16_forward(ctx, "f16", torch.float16, X, K16, gamma, beta, base, running_mean, running_var, training,
+                              momentum, eps, scale, act)
 
     @staticmethod
     def backward(ctx, gout):
-        lib = L.load()
-        Xf, K16, gm, P, H, mean, invstd = ctx.saved_tensors
-        training, scale, act, has_base = ctx.cfg
-        B, D = Xf.shape
-        g = gout.to(torch.float32).contiguous()
-        dev = Xf.device
-        dP = torch.empty_like(P)
-        gX = torch.empty_like(Xf)
-        gK = torch.empty((D, D), dtype=torch.float32, device=dev)
-        gg = torch.empty(D, dtype=torch.float32, device=dev)
-        gb = torch.empty_like(gg)
-        with torch.cuda.device(dev):
-            ws = torch.empty(lib.pde_sym_layer_f16_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
-            L.check(lib.pde_sym_layer_f16_backward(B, D, act, 1 if training else 0, _ptr(g), float(scale), _ptr(Xf),
-                                                   _ptr(K16), _ptr(gm), _ptr(P), _ptr(H), _ptr(mean), _ptr(invstd),
-                                                   _ptr(dP), _ptr(gX), _ptr(gK), _ptr(gg), _ptr(gb), _ptr(ws), ws.numel(),
-                                                   _stream()), "pde_sym_layer_f16_backward")
-        return gX, gK, None, gg, gb, (g if has_base else None), None, None, None, None, None, None, None
+        return _sym16_backward(ctx, "f16", gout)
+
+
+class _SymLayerBf16Fn(torch.autograd.Function):
+    """The same under bf16 autocast (bf16 rounding points on the bf16 matrix cores): ctypes twin of the C++ node
+    ``sym_bf16``."""
+
+    @staticmethod
+    def forward(ctx, X, K, K16, gamma, beta, base, running_mean, running_var, training, momentum, eps, scale, act):
+        return _sym16_forward(ctx, "bf16", torch.bfloat16, X, K16, gamma, beta, base, running_mean, running_var, training,
+                              momentum, eps, scale, act)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return _sym16_backward(ctx, "bf16", gout)
 
 
 def sym_layer(X, K, bn, activation: str = "relu", base=None, scale: float = -1.0, K16=None):
@@ -1356,10 +1404,11 @@ def sym_layer(X, K, bn, activation: str = "relu", base=None, scale: float = -1.0
     HamiltonianBlock's ``base=Y, scale=+dt`` on Z and ``base=Z, scale=+dt`` on Y).  X: (B, ...) flattened to (B, D); the result
     has X's shape.  Updates the module's running statistics in training mode exactly as the module would.
 
-    ``K16`` (``sym_k16(K)``): the fp16-operand form, with CUDA fp16 autocast's rounding points (include/pdecnn.h,
-    DESIGN §5) on the fp16 matrix cores; the result is fp16 without ``base`` (as autocast's ``F_sym``) and fp32 with one
-    (``base + r(scale Q)``, as ``Y + dt * F_sym``).  The gradient reaches ``K`` (fp32), not ``K16``.  X must be fp32 and
-    ``sym_layer_f16_supported`` hold."""
+    ``K16`` (``sym_k16(K)`` or ``sym_k16(K, torch.bfloat16)``): the 16-bit-operand form, with CUDA fp16 or bf16 autocast's
+    rounding points (include/pdecnn.h) on the matrix cores of that type, chosen by ``K16.dtype``; the result has
+    K16's dtype without ``base`` (as autocast's ``F_sym``) and is fp32 with one (``base + r(scale Q)``, as
+    ``Y + dt * F_sym``).  The gradient reaches ``K`` (fp32), not ``K16``.  X must be fp32 and
+    ``sym_layer_f16_supported`` / ``sym_layer_bf16_supported`` hold."""
     shape = X.shape
     B = shape[0]
     X2 = X.reshape(B, -1)
@@ -1373,14 +1422,15 @@ def sym_layer(X, K, bn, activation: str = "relu", base=None, scale: float = -1.0
     mom = bn.momentum if bn.momentum is not None else 0.0
     H_ = L.host_ext()
     if K16 is not None:
-        if X2.dtype != torch.float32 or K16.dtype != torch.float16:
-            raise TypeError("sym_layer(K16=...) takes an fp32 X and an fp16 K16")
+        if X2.dtype != torch.float32 or K16.dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError("sym_layer(K16=...) takes an fp32 X and an fp16 or bf16 K16")
+        bf = K16.dtype == torch.bfloat16
         if H_ is not None and X2.is_cuda:
-            out = H_.sym_f16(X2, K, K16, bn.weight, bn.bias, b2, rm, rv, bool(training), float(mom), float(bn.eps),
-                             float(scale), _ACT_CODE[activation])
+            out = (H_.sym_bf16 if bf else H_.sym_f16)(X2, K, K16, bn.weight, bn.bias, b2, rm, rv, bool(training), float(mom),
+                                                      float(bn.eps), float(scale), _ACT_CODE[activation])
         else:
-            out = _SymLayerF16Fn.apply(X2, K, K16, bn.weight, bn.bias, b2, rm, rv, training, mom, bn.eps, scale,
-                                       _ACT_CODE[activation])
+            out = (_SymLayerBf16Fn if bf else _SymLayerF16Fn).apply(X2, K, K16, bn.weight, bn.bias, b2, rm, rv, training, mom,
+                                                                    bn.eps, scale, _ACT_CODE[activation])
         return out.view(shape)
     if H_ is not None and X2.is_cuda:
         # the native host path (csrc/host_ext.cpp): the same two calls of the C ABI from a C++ autograd node

@@ -232,10 +232,10 @@ class SymmetricLayer(nn.Module):
     activation run on the fp32 matrix cores (``functional.sym_layer``, pde_rh.hip — SURVEY §8f-4: up to 128 rows each product
     as 32-column strips with the contraction split over workgroups plus a small epilogue launch);
     ``residual(base, X, scale)`` is the fused update ``base + scale * (act(BN(X K^T)) K)`` the two blocks below are made
-    of.  Under ``torch.autocast("cuda", torch.float16)`` the same kernels run on fp16 operands with autocast's rounding
-    points (``functional.sym_layer(..., K16=...)``): ``forward`` returns fp16 and ``residual`` fp32, as plain
-    autocast does; the blocks below make K16 once per block forward and share it across their steps.  ``fused = False``
-    (or a shape the kernels do not take, or bf16 autocast) is plain torch, as in the reference."""
+    of.  Under ``torch.autocast("cuda", ...)`` in fp16 or bf16 the same kernels run on operands of that type with
+    autocast's rounding points (``functional.sym_layer(..., K16=...)``): ``forward`` returns the autocast dtype
+    and ``residual`` fp32, as plain autocast does; the blocks below make K16 once per block forward and share it across
+    their steps.  ``fused = False`` (or a shape the kernels do not take) is plain torch, as in the reference."""
 
     def __init__(self, channels, spatial_size, activation="relu"):
         super().__init__()
@@ -253,10 +253,13 @@ class SymmetricLayer(nn.Module):
         return self.fused and F_.sym_layer_supported(X, self.norm)
 
     def k16(self, X):
-        """fp16 autocast's copy of K for calls on inputs like X, or None where the fp16-operand path does not run.  Made
-        afresh on every call: K changes in place between forwards (optimizer steps, a replayed graph)."""
+        """Autocast's copy of K (fp16 or bf16, as the region's dtype) for calls on inputs like X, or None where the
+        16-bit-operand path does not run.  Made afresh on every call: K changes in place between forwards (optimizer
+        steps, a replayed graph)."""
         if self.fused and F_.sym_layer_f16_supported(X, self.norm):
             return F_.sym_k16(self.K.weight)
+        if self.fused and F_.sym_layer_bf16_supported(X, self.norm):
+            return F_.sym_k16(self.K.weight, torch.bfloat16)
         return None
 
     def residual(self, base, X, scale, K16=None):
@@ -291,7 +294,7 @@ class ParabolicBlock(nn.Module):
         print(f"Parabolic Block: {num_steps} steps, dt={dt}")
 
     def forward(self, Y):
-        K16 = self.symmetric_layer.k16(Y)                              # one fp16 copy of K per forward under fp16 autocast
+        K16 = self.symmetric_layer.k16(Y)                              # one 16-bit copy of K per forward under autocast
         for _ in range(self.num_steps):
             Y = self.symmetric_layer.residual(Y, Y, -self.dt, K16)     # Y + dt * F_sym(Y)
         return Y
@@ -309,7 +312,7 @@ class HamiltonianBlock(nn.Module):
 
     def forward(self, Y):
         Z = torch.zeros_like(Y)
-        KY, KZ = self.F_Y.k16(Y), self.F_Z.k16(Y)                     # one fp16 copy of each K per forward under fp16 autocast
+        KY, KZ = self.F_Y.k16(Y), self.F_Z.k16(Y)                     # one 16-bit copy of each K per forward under autocast
         for _ in range(self.num_steps):
             Y = self.F_Y.residual(Y, Z, self.dt, KY)                   # Y - dt * F_Y(Z)
             Z = self.F_Z.residual(Z, Y, self.dt, KZ)                   # Z - dt * F_Z(Y)

@@ -8,14 +8,16 @@ with the diffusion layer taken from this package and data parallelism over RCCL:
     python examples/train_synthetic.py --variant mnist --steps 200        # single GPU, fp32: the step is ONE hipGraph
     python examples/train_synthetic.py --variant mnist --steps 200 --eager  # the same, one eager autograd step at a time
     python examples/train_synthetic.py --variant cifar10_noconv --amp          # cifar10.py:318-361 under fp16 autocast
+    python examples/train_synthetic.py --variant cifar10_noconv --amp bf16     # the same under bf16 autocast, no GradScaler
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         examples/train_synthetic.py --variant svhn_model --steps 200
 
 Variants: ``mnist`` / ``cifar10`` are small stand-ins; ``mnist_model``, ``fashion_model``, ``svhn_model``,
 ``cifar10_noconv``, ``tiny_model`` and ``emotion_model`` are the counterparts of the reference's own models
 (cnn_with_pde_amd.models: mnist_test.py:223-237, fashion_mnist.py:200-224, SVHN.py:234-270, cifar10.py:318-361,
-tiny_imagenet.py:237-305, emotion_recognition.py:170-195).  ``--amp`` runs the step under fp16 autocast with a
-GradScaler, as cifar10.py:440,458-467 does.
+tiny_imagenet.py:237-305, emotion_recognition.py:170-195).  ``--amp`` (or ``--amp fp16``) runs the step under fp16
+autocast with a GradScaler, as cifar10.py:440,458-467 does; ``--amp bf16`` under bf16 autocast, which has fp32's range
+and needs no loss scaling.
 
 There is no dataset on the box: every rank draws its shard of a fixed synthetic classification task
 (one smooth random template per class plus noise), so the loss has something to learn and the run is
@@ -143,7 +145,8 @@ def train_graphed(a, model, templates, classes, crit, gen, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--variant", choices=sorted(VARIANTS), default="mnist")
-    ap.add_argument("--amp", action="store_true", help="fp16 autocast + GradScaler (cifar10.py:440,458-467)")
+    ap.add_argument("--amp", nargs="?", const="fp16", default=None, choices=["fp16", "bf16"],
+                    help="bare or fp16: fp16 autocast + GradScaler (cifar10.py:440,458-467); bf16: bf16 autocast, no loss scaling")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch")
     ap.add_argument("--lr", type=float, default=1e-3)
@@ -175,7 +178,7 @@ def main():
         with torch.no_grad():
             for n, v in dict(alpha_w1=0.05, alpha_w2=0.02, alpha_w3=-0.01, beta_w1=0.04, beta_w2=0.015, beta_w3=0.01).items():
                 getattr(model.pde, n).fill_(v)
-    scaler = torch.amp.GradScaler("cuda", enabled=a.amp)
+    scaler = torch.amp.GradScaler("cuda", enabled=a.amp == "fp16")      # bf16 and fp32: switched off, every call passes through
     templates = synthetic_task(a.variant, classes, torch.Generator().manual_seed(7)).to(dev)
     opt = torch.optim.AdamW(model.parameters(), lr=a.lr, weight_decay=1e-4)
     sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=a.steps)
@@ -197,7 +200,7 @@ def main():
         labels = torch.randint(0, classes, (a.batch,), generator=gen, device=dev)
         x = templates[labels] + 1.0 * torch.randn(a.batch, *templates.shape[1:], generator=gen, device=dev)
         opt.zero_grad(set_to_none=True)
-        with torch.autocast("cuda", dtype=torch.float16, enabled=a.amp):
+        with torch.autocast("cuda", dtype=torch.bfloat16 if a.amp == "bf16" else torch.float16, enabled=a.amp is not None):
             out = model(x)
             loss = crit(out, labels)
         scaler.scale(loss).backward()

@@ -502,6 +502,30 @@ int pde_sym_layer_f16_backward(int32_t B, int32_t D, int32_t act, int32_t traini
                                uint16_t* dP, float* gX, float* gK, float* g_bn_weight, float* g_bn_bias,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same layer under CUDA bf16 autocast, on the bf16 matrix cores ---------------------- */
+
+/* The fp16-autocast contract above with r() = round to nearest even to bf16 — the rounding points of
+ * torch.autocast("cuda", torch.bfloat16); bf16 has fp32's exponent range, so no r() overflows:
+ *     K16 = r(K);  P = r(r(X) K16^T);  N = r(BatchNorm1d(P));  H = r(act(N));  Q = r(H K16);  out = base + r(scale Q)
+ * Argument lists, shapes (1 <= B <= 128, D a multiple of 64), workspace size, argument checks and error codes are those
+ * of the pde_sym_layer_f16_* functions; K16, P, H, dP and a base-less `out` are bf16, passed as their 16-bit patterns.
+ * Backward: gQ = r(scale r(g_out)), dP = r(...), gX = dP K16, gK = dP^T r(X) + H^T gQ, all accumulated in fp32. */
+int pde_sym_layer_bf16_supported(int32_t B, int32_t D);
+size_t pde_sym_layer_bf16_workspace_bytes(int32_t B, int32_t D);
+/* K16 = r(K), K: (D, D) fp32 */
+int pde_sym_k_to_bf16(int32_t D, const float* K, uint16_t* K16, void* stream);
+int pde_sym_layer_bf16_forward(int32_t B, int32_t D, int32_t act, int32_t training,
+                               const float* X, const uint16_t* K16, const float* bn_weight, const float* bn_bias,
+                               float* running_mean, float* running_var, float momentum, float eps,
+                               const float* base, float scale,
+                               uint16_t* P, uint16_t* H, float* mean, float* invstd, void* out,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int pde_sym_layer_bf16_backward(int32_t B, int32_t D, int32_t act, int32_t training,
+                                const float* g_out, float scale, const float* X, const uint16_t* K16, const float* bn_weight,
+                                const uint16_t* P, const uint16_t* H, const float* mean, const float* invstd,
+                                uint16_t* dP, float* gX, float* gK, float* g_bn_weight, float* g_bn_bias,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- float64: the same layers computed in double end to end -----------------------------------------
  * A float64 input or parameter makes the reference's torch ops run in float64 (torch type promotion), `t` and the
  * coefficient schedule included.  These entry points are that path: every tensor is float64 (double), every scalar of

@@ -1,9 +1,9 @@
-"""Event-timed on a warm device: the Ruthotto-Haber symmetric layer under fp16 autocast, three ways at B = 64 and 128,
-D = 3072 (3 x 32 x 32) — the fused fp16-operand path (pde_rh.hip, fp16 MFMAs), plain-torch autocast (fused = False) and
-the fused fp32 path without autocast:
+"""Event-timed on a warm device: the Ruthotto-Haber symmetric layer under fp16 (or, with --bf16, bf16) autocast, three ways
+at B = 64 and 128, D = 3072 (3 x 32 x 32) — the fused 16-bit-operand path (pde_rh.hip, fp16 / bf16 MFMAs), plain-torch
+autocast (fused = False) and the fused fp32 path without autocast:
   layer  one SymmetricLayer forward + backward;
   rh     the RH part of a HybridPDEExtractor step: ParabolicBlock (4 steps) + HamiltonianBlock (3 steps), forward + backward.
-Usage: python tools/perf_rh_amp.py [iters] [--json out.json]"""
+Usage: python tools/perf_rh_amp.py [iters] [--bf16] [--json out.json]"""
 import contextlib
 import io
 import json
@@ -15,7 +15,8 @@ import torch  # noqa: E402
 import cnn_with_pde_amd as P  # noqa: E402
 
 ITERS = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 50
-WAYS = [("fused_f16", True, True), ("torch_amp", False, True), ("fused_f32", True, False)]
+AMP, TAG = (torch.bfloat16, "bf16") if "--bf16" in sys.argv else (torch.float16, "f16")
+WAYS = [("fused_" + TAG, True, True), ("torch_amp", False, True), ("fused_f32", True, False)]
 
 
 def quiet(f, *a, **k):
@@ -46,7 +47,7 @@ def step_fn(mods, x, gy, amp):
     def step():
         for p in params:
             p.grad = None
-        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+        with torch.autocast("cuda", dtype=AMP, enabled=amp):
             outs = [m(x) for m in mods]
         torch.autograd.backward(outs, [gy.to(o.dtype) for o in outs])
     return step
@@ -92,7 +93,7 @@ def main():
                     res[name] = time_ms(step_fn(mods, x, gy, amp), ITERS)
             row = {"B": B, "what": what, **{k: round(v[0], 4) for k, v in res.items()},
                    "spread": {k: [round(v[1], 4), round(v[2], 4)] for k, v in res.items()}}
-            row["f16_vs_torch_amp"] = round(res["torch_amp"][0] / res["fused_f16"][0], 3)
+            row[TAG + "_vs_torch_amp"] = round(res["torch_amp"][0] / res["fused_" + TAG][0], 3)
             rows.append(row)
             print(json.dumps(row), flush=True)
     if "--json" in sys.argv:
