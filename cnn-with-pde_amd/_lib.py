@@ -96,6 +96,10 @@ SIGNATURES = {
     "pde_adi_forward": (C.c_int, [_D, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
     "pde_adi_backward": (C.c_int, [_D, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _fp, _fp, _fp, _fp,
                                    _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_forward_states": (C.c_int, [_D, _vp, _vp, _vp, C.POINTER(C.c_uint64), _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp,
+                                         _sz, _vp]),
+    "pde_adi_backward_states": (C.c_int, [_D, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(C.c_uint64), _vp,
+                                          _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
     "pde_adi_kappa_max": (C.c_int, [_D, _fp, _fp, _fp, _fp, _fp, _vp]),
     "pde_adi_steps_workspace_bytes": (_sz, [_D, _i32]),
     "pde_adi_factor_steps": (C.c_int, [_D, _i32, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
@@ -174,6 +178,10 @@ SIGNATURES = {
     "pde_adi_f64_forward": (C.c_int, [_D64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pde_adi_f64_backward": (C.c_int, [_D64, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_f64_forward_states": (C.c_int, [_D64, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                             _vp]),
+    "pde_adi_f64_backward_states": (C.c_int, [_D64, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(C.c_uint64), _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pde_channel_mix_f64_forward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "pde_channel_mix_f64_backward_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "pde_channel_mix_f64_backward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -196,12 +204,20 @@ SIGNATURES = {
     "pde_adi_rect_forward": (C.c_int, [_DR, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
     "pde_adi_rect_backward": (C.c_int, [_DR, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _fp, _fp, _fp, _fp,
                                         _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_forward_states": (C.c_int, [_DR, _vp, _vp, _vp, C.POINTER(C.c_uint64), _fp, _fp, _fp, _fp, _fp, _fp, _vp,
+                                              _vp, _sz, _vp]),
+    "pde_adi_rect_backward_states": (C.c_int, [_DR, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(C.c_uint64), _vp,
+                                               _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
     "pde_adi_rect_f64_forward_workspace_bytes": (_sz, [_DR64]),
     "pde_adi_rect_f64_backward_workspace_bytes": (_sz, [_DR64, _i32]),
     "pde_adi_rect_f64_kappa_max": (C.c_int, [_DR64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pde_adi_rect_f64_forward": (C.c_int, [_DR64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pde_adi_rect_f64_backward": (C.c_int, [_DR64, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_f64_forward_states": (C.c_int, [_DR64, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _sz, _vp]),
+    "pde_adi_rect_f64_backward_states": (C.c_int, [_DR64, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(C.c_uint64),
+                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pde_timing_enable": (C.c_int, [_i32]),
     "pde_timing_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int64)]),

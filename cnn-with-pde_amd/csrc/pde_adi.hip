@@ -680,6 +680,28 @@ int dispatch_bwd(const PdeAdiDesc* d, int split, const SweepArgs& sa, int grid, 
     }, st, false, true);
 }
 
+int dispatch_fwd_emit(const PdeAdiDesc* d, int split, const SweepArgs& sa, int grid, size_t lds, hipStream_t st) {
+    return timed_launch([&]() -> int {
+        switch (d->N) {
+#define PDE_CASE(NN) case NN: return adi_launch_fwd_emit_##NN(d->io_dtype, split, &sa, grid, lds, st);
+            PDE_N_LIST
+#undef PDE_CASE
+        }
+        return PDE_E_UNSUPPORTED_N;
+    }, st, true, true);
+}
+
+int dispatch_bwd_emit(const PdeAdiDesc* d, int split, const SweepArgs& sa, int grid, hipStream_t st) {
+    return timed_launch([&]() -> int {
+        switch (d->N) {
+#define PDE_CASE(NN) case NN: return adi_launch_bwd_emit_##NN(d->io_dtype, split, &sa, grid, st);
+            PDE_N_LIST
+#undef PDE_CASE
+        }
+        return PDE_E_UNSUPPORTED_N;
+    }, st, false, true);
+}
+
 int count_ckpt(const uint64_t m[2]) { return m ? __builtin_popcountll(m[0]) + __builtin_popcountll(m[1]) : 0; }
 
 bool asm_fwd_eligible(const PdeAdiDesc* d) {
@@ -699,8 +721,10 @@ bool fwd_ho_eligible(const PdeAdiDesc* d) {
 
 // ---- launch helpers shared by the whole-schedule entry points and the per-step ones -----------------
 // forward sweeps of `d` (a whole schedule or one step of it) with records/table already in place
+// `states` / `emit` (pde_adi_forward_states, a non-empty mask): the emitting variant of the HIP kernel on the
+// barrier-per-sweep schedule; neither the assembly kernel nor the hand-over schedule writes states
 int launch_fwd_sweeps(const PdeAdiDesc* d, const void* u, void* y, const float* coef, const SweepTab* tab,
-                      hipStream_t st) {
+                      hipStream_t st, void* states = nullptr, const uint64_t* emit = nullptr) {
     SweepArgs sa{};
     sa.in0 = u; sa.out = y; sa.coef = coef; sa.tab = tab;
     sa.B = d->B; sa.C = d->C; sa.S = d->num_sweeps;
@@ -708,6 +732,11 @@ int launch_fwd_sweeps(const PdeAdiDesc* d, const void* u, void* y, const float* 
     sa.one_eps = 1.0f + d->eps;
     sa.xcd_map = use_xcd_map(d);
     sa.pair_x = (split_of(d) == kSplitStrang && strang_pairs_identical(d)) ? 1 : 0;
+    if (emit) {
+        sa.states = states; sa.em[0] = emit[0]; sa.em[1] = emit[1];
+        const size_t lds = (size_t)(kRing * kRecFwdPad + kWaves * kImage) * sizeof(float);
+        return dispatch_fwd_emit(d, split_of(d), sa, sa.G * d->C, lds, st);
+    }
     // N = 32, fp32 tensors, Strang schedules of two or more steps: the hand-scheduled assembly kernel (gen_adi_fwd_asm.py:
     // 16 waves, four planes per lane, rows held in registers, the record ring handed over by counters)
     if (asm_fwd_eligible(d)) {
@@ -743,6 +772,16 @@ int axis_weights(const PdeAdiDesc* d, AxisWeights& w) {
     return PDE_OK;
 }
 
+// emission mask -> count; PDE_E_BADARG for a bit at or above S-1 (the last state is y itself) or a missing tensor
+int emit_plan(int num_sweeps, const uint64_t emit_mask[2], const void* states, int& nem) {
+    nem = count_ckpt(emit_mask);
+    if (!nem) return PDE_OK;
+    if (!states) return PDE_E_BADARG;
+    for (int s = num_sweeps > 0 ? num_sweeps - 1 : 0; s < 128; ++s)
+        if ((emit_mask[s >> 6] >> (s & 63)) & 1ull) return PDE_E_BADARG;
+    return PDE_OK;
+}
+
 // checkpoint mask -> (count, number of forward sweeps to recompute); PDE_E_BADARG when inconsistent
 int ckpt_plan(const PdeAdiDesc* d, const uint64_t ckpt_mask[2], const void* u, int& nck, int& Sf) {
     nck = count_ckpt(ckpt_mask);
@@ -770,7 +809,8 @@ bool asm_bwd_eligible(const PdeAdiDesc* d, int nck) {
 // of one layer call: every workgroup owns its slots, so this is race-free and order-independent).
 int launch_bwd_sweeps(const PdeAdiDesc* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2],
                       int nck, int Sf, void* gu, const float* coef, const SweepTab* tab, const int* varying,
-                      float* part, void* dbg, float* ckpt, int G, int accumulate, hipStream_t st) {
+                      float* part, void* dbg, float* ckpt, int G, int accumulate, hipStream_t st,
+                      const void* gstates = nullptr, const uint64_t* emit = nullptr) {
     SweepArgs sa{};
     sa.in0 = gy; sa.in1 = y; sa.in2 = u; sa.out = gu; sa.coef = coef; sa.part = part; sa.tab = tab;
     sa.varying = varying; sa.ckpt = ckpt;
@@ -798,6 +838,10 @@ int launch_bwd_sweeps(const PdeAdiDesc* d, const void* gy, const void* y, const 
     // N = 32, fp32 tensors, Strang steps, no checkpoints: the fast body runs as the hand-scheduled assembly kernel
     // (gen_adi_bwd_asm.py: 168 VGPRs, three waves per SIMD), the masked body as a launch of its own over the same groups
     const int split = split_of(d);
+    if (emit) {                                           // upstream gradients of emitted states: the HIP backward's emitting variant
+        sa.states = const_cast<void*>(gstates); sa.em[0] = emit[0]; sa.em[1] = emit[1];
+        return dispatch_bwd_emit(d, split, sa, 2 * G * d->C, st);
+    }
     const int nw = asm_bwd_waves();
     if (asm_bwd_eligible(d, nck)) {
         AsmBwdArgs aa{};
@@ -921,12 +965,18 @@ size_t pde_adi_backward_workspace_bytes(const PdeAdiDesc* d, int32_t num_checkpo
     return b;
 }
 
-int pde_adi_forward(const PdeAdiDesc* d, const void* u, void* y, const float* alpha_base, const float* beta_base,
-                    const float* alpha_slope, const float* beta_slope, float* kappa_max, float* kappa_max_host,
-                    void* kappa_event, void* workspace, size_t workspace_bytes, void* stream) {
+// pde_adi_forward and pde_adi_forward_states (states / emit_mask null or empty: the plain call, launch for launch)
+static int adi_forward_impl(const PdeAdiDesc* d, const void* u, void* y, void* states, const uint64_t* emit_mask,
+                            const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                            const float* beta_slope, float* kappa_max, float* kappa_max_host, void* kappa_event,
+                            void* workspace, size_t workspace_bytes, void* stream) {
     int rc = check_desc(d, true);
     if (rc != PDE_OK) return rc;
     if (!u || !y || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    int nem;
+    rc = emit_plan(d->num_sweeps, emit_mask, states, nem);
+    if (rc != PDE_OK) return rc;
+    const uint64_t* emit = nem ? emit_mask : nullptr;
     if (workspace_bytes < pde_adi_forward_workspace_bytes(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!fused_n(d->N)) {                                 // any other line length: one thread per line (pde_adi_gen.hip)
@@ -935,7 +985,7 @@ int pde_adi_forward(const PdeAdiDesc* d, const void* u, void* y, const float* al
         if (rc != PDE_OK) return rc;
         rc = publish_kmax(kappa_max, kappa_max_host, kappa_event, d->num_sweeps, st);
         if (rc != PDE_OK) return rc;
-        return gen_forward_sweeps(d, u, y, workspace, st);
+        return gen_forward_sweeps(d, u, y, workspace, st, states, emit);
     }
     float* coef = static_cast<float*>(workspace);
     SweepTab* tab = reinterpret_cast<SweepTab*>(static_cast<char*>(workspace) + coef_bytes(d));
@@ -945,19 +995,40 @@ int pde_adi_forward(const PdeAdiDesc* d, const void* u, void* y, const float* al
     if (rc != PDE_OK) return rc;
     rc = publish_kmax(kappa_max, kappa_max_host, kappa_event, d->num_sweeps, st, km != nullptr);
     if (rc != PDE_OK) return rc;
-    return launch_fwd_sweeps(d, u, y, coef, tab, st);
+    return launch_fwd_sweeps(d, u, y, coef, tab, st, states, emit);
 }
 
-int pde_adi_backward(const PdeAdiDesc* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2],
-                     void* gu, const float* alpha_base, const float* beta_base, const float* alpha_slope,
-                     const float* beta_slope, float* g_alpha_base, float* g_beta_base, float* g_alpha_slope,
-                     float* g_beta_slope, const void* fwd_workspace, void* workspace, size_t workspace_bytes,
-                     void* stream) {
+int pde_adi_forward(const PdeAdiDesc* d, const void* u, void* y, const float* alpha_base, const float* beta_base,
+                    const float* alpha_slope, const float* beta_slope, float* kappa_max, float* kappa_max_host,
+                    void* kappa_event, void* workspace, size_t workspace_bytes, void* stream) {
+    return adi_forward_impl(d, u, y, nullptr, nullptr, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max,
+                            kappa_max_host, kappa_event, workspace, workspace_bytes, stream);
+}
+
+int pde_adi_forward_states(const PdeAdiDesc* d, const void* u, void* y, void* states, const uint64_t emit_mask[2],
+                           const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                           const float* beta_slope, float* kappa_max, float* kappa_max_host, void* kappa_event,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    return adi_forward_impl(d, u, y, states, emit_mask, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max,
+                            kappa_max_host, kappa_event, workspace, workspace_bytes, stream);
+}
+
+// pde_adi_backward and pde_adi_backward_states (gstates / emit_mask null or empty: the plain call, launch for launch)
+static int adi_backward_impl(const PdeAdiDesc* d, const void* gy, const void* gstates, const uint64_t* emit_mask,
+                             const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
+                             const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                             const float* beta_slope, float* g_alpha_base, float* g_beta_base, float* g_alpha_slope,
+                             float* g_beta_slope, const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                             void* stream) {
     int rc = check_desc(d, true);
     if (rc != PDE_OK) return rc;
     if (!gy || !y || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !g_alpha_base ||
         !g_beta_base || !g_alpha_slope || !g_beta_slope || !workspace)
         return PDE_E_BADARG;
+    int nem;
+    rc = emit_plan(d->num_sweeps, emit_mask, gstates, nem);
+    if (rc != PDE_OK) return rc;
+    const uint64_t* emit = nem ? emit_mask : nullptr;
     int nck, Sf;
     rc = ckpt_plan(d, ckpt_mask, u, nck, Sf);
     if (rc != PDE_OK) return rc;
@@ -965,7 +1036,7 @@ int pde_adi_backward(const PdeAdiDesc* d, const void* gy, const void* y, const v
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!fused_n(d->N))
         return gen_backward(d, gy, y, u, ckpt_mask, nck, Sf, gu, alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base,
-                            g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace, st);
+                            g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace, st, gstates, emit);
     const int G = groups_per_channel(d, kWaves * kJBwd, 8 / kWaves);
     char* ws = static_cast<char*>(workspace);
     float* coef = reinterpret_cast<float*>(ws);           ws += coef_bytes(d);
@@ -988,10 +1059,31 @@ int pde_adi_backward(const PdeAdiDesc* d, const void* gy, const void* y, const v
     AxisWeights w;
     rc = axis_weights(d, w);
     if (rc != PDE_OK) return rc;
-    rc = launch_bwd_sweeps(d, gy, y, u, ckpt_mask, nck, Sf, gu, coef, tab, varying, part, dbg, ckpt, G, 0, st);
+    rc = launch_bwd_sweeps(d, gy, y, u, ckpt_mask, nck, Sf, gu, coef, tab, varying, part, dbg, ckpt, G, 0, st, gstates, emit);
     if (rc != PDE_OK) return rc;
     return launch_pgrad(d, w, alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base, g_beta_base, g_alpha_slope,
                         g_beta_slope, varying, part, G, st);
+}
+
+int pde_adi_backward(const PdeAdiDesc* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2],
+                     void* gu, const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                     const float* beta_slope, float* g_alpha_base, float* g_beta_base, float* g_alpha_slope,
+                     float* g_beta_slope, const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    return adi_backward_impl(d, gy, nullptr, nullptr, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                             g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
+                             workspace_bytes, stream);
+}
+
+int pde_adi_backward_states(const PdeAdiDesc* d, const void* gy, const void* gstates, const uint64_t emit_mask[2],
+                            const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
+                            const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                            const float* beta_slope, float* g_alpha_base, float* g_beta_base, float* g_alpha_slope,
+                            float* g_beta_slope, const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    return adi_backward_impl(d, gy, gstates, emit_mask, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                             g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
+                             workspace_bytes, stream);
 }
 
 // ---- one layer call as a sequence of per-step launches (layers with a channel operator between the steps) ----

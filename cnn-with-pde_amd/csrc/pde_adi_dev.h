@@ -72,6 +72,10 @@ struct SweepArgs {
                             // (same time, same increment): its rows are loaded from LDS once for the two sweeps
     void* dbg;              // diagnostic builds only
     int only_masked;        // bwd: the grid is C*G blocks of the MASKED body alone (the fast body ran as the assembly kernel)
+    // emitting variants only (EMIT = true; nothing else reads these): bit s of em = the state after sweep s leaves the
+    // launch.  fwd: the true state, to states[slot][B][C][N][N] of the I/O type; bwd: the same layout holds dL/d(state)
+    void* states;
+    unsigned long long em[2];
 };
 
 // The sweep table and the channel flags are written by an earlier kernel and only read here.
@@ -563,6 +567,43 @@ __device__ __forceinline__ void store_planes(IO* base, int q, int wave, int lane
     });
 }
 
+// r += sc * (the J planes of a lane at `base`), one plane at a time through the wave's image (plane_to_rows with the
+// half row consumed four values at a time): 16 registers of raw data, then 4, in flight beside the caller's state — the
+// backward adds the upstream gradient of an emitted state while both its adjoint and its state are live
+template <int N, int J, typename IO>
+__device__ __forceinline__ void add_planes(const IO* base, int q, int wave, int lane, int l, int hf, int B, int C, int c,
+                                           float* T, float sc, typename Pack<J>::P (&r)[N / 2]) {
+    constexpr int PPI = kWaves * J, M = N / 2;
+    sfor<0, J>([&](auto CC) __attribute__((always_inline)) {
+        constexpr int j = decltype(CC)::value;
+        float4 raw[Geo<N>::kLoads];
+        const int b = q * PPI + wave * J + j;
+        plane_fetch<N, IO>(base + ((size_t)b * C + c) * (size_t)(N * N), b < B, lane, raw);
+#pragma unroll
+        for (int i = 0; i < Geo<N>::kLoads; ++i) {
+            const int f = i * 64 + lane;
+            if ((i + 1) * 64 <= Geo<N>::NN4 || f < Geo<N>::NN4) {
+                const int row = f / Geo<N>::R4, w0 = 4 * (f % Geo<N>::R4);
+                bool s0, s1;
+                const int a0 = pair_slot<N>(row, w0, s0), a1 = pair_slot<N>(row, w0 + 2, s1);
+                *reinterpret_cast<float2*>(&T[a0]) = s0 ? make_float2(raw[i].y, raw[i].x) : make_float2(raw[i].x, raw[i].y);
+                *reinterpret_cast<float2*>(&T[a1]) = s1 ? make_float2(raw[i].w, raw[i].z) : make_float2(raw[i].z, raw[i].w);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        const float* src = T + l * kLineStride + hf * kHalfPad;
+        sfor<0, (M + 3) / 4>([&](auto IC) __attribute__((always_inline)) {
+            constexpr int i = decltype(IC)::value;
+            const float4 x = *reinterpret_cast<const float4*>(src + 4 * i);
+            pk_set<j>(r[4 * i], fmaf(sc, x.x, pk_get<j>(r[4 * i])));
+            if constexpr (4 * i + 1 < M) pk_set<j>(r[4 * i + 1], fmaf(sc, x.y, pk_get<j>(r[4 * i + 1])));
+            if constexpr (4 * i + 2 < M) pk_set<j>(r[4 * i + 2], fmaf(sc, x.z, pk_get<j>(r[4 * i + 2])));
+            if constexpr (4 * i + 3 < M) pk_set<j>(r[4 * i + 3], fmaf(sc, x.w, pk_get<j>(r[4 * i + 3])));
+        });
+        __builtin_amdgcn_wave_barrier();
+    });
+}
+
 // ---- forward kernel ---------------------------------------------------------------------
 // SPLIT fixes the order of the axes inside a time step at compile time (straight-line code per
 // step, no per-sweep axis branch); kSplitAny reads the axis of every sweep from the table.
@@ -574,12 +615,17 @@ __device__ __forceinline__ void store_planes(IO* base, int q, int wave, int lane
 // its own DMA pieces of record n+2 have landed.  So "every wave past record n-2" means both that record n is complete
 // and that the slot of record n-2 may be overwritten: one poll per staged record.  The waves drift apart instead of
 // meeting at every sweep; there is no phase skew, the drift does its job.
+//
+// EMIT (pde_adi_*_forward_states): the state after every sweep whose bit is set in a.em also goes to a.states, rounded to
+// the I/O type once; the time loop goes on in fp32 registers.  A variant of its own so that the plain kernels compile
+// to what they were; it runs on the barrier-per-sweep (or resident) schedule.
 constexpr int kRingHo = 4;
-template <int N, int J, typename IO, int SPLIT, bool HO = false>
+template <int N, int J, typename IO, int SPLIT, bool HO = false, bool EMIT = false>
 __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kernel(SweepArgs a) {
     constexpr int M = Geo<N>::M;
     constexpr int RING = HO ? kRingHo : kRing;
     static_assert(!HO || SPLIT == kSplitStrang, "the hand-over schedule is written for the Strang pattern");
+    static_assert(!(HO && EMIT), "emission runs on the barrier schedule");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* cbuf = smem;                                   // [RING][kRecFwdPad]
     float* tbuf = smem + RING * kRecFwdPad;              // [kWaves][kImage]
@@ -720,9 +766,15 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
             abl_loaded = true;
             solve_fwd_rows<M, J>(v, ce, cinv, cjn, hf);
             if (axs == PDE_AXIS_Y && !(PDE_ABL & 2)) relayout_all<N, J>(v, T, l, hf);
-            if (a.ckpt != nullptr && ck_bit(a.ck, s)) {   // backward pre-pass: park this state (fp32)
+            if (!EMIT && a.ckpt != nullptr && ck_bit(a.ck, s)) {   // backward pre-pass: park this state (fp32); never an emitting launch
                 float* slot = a.ckpt + (size_t)ck_slot(a.ck, s) * a.B * a.C * plane;
                 store_planes<N, J, float>(slot, q, wave, lane, l, hf, a.B, a.C, c, T, v);
+            }
+            if constexpr (EMIT) {
+                if (ck_bit(a.em, s)) {
+                    IO* slot = static_cast<IO*>(a.states) + (size_t)ck_slot(a.em, s) * a.B * a.C * plane;
+                    store_planes<N, J, IO>(slot, q, wave, lane, l, hf, a.B, a.C, c, T, v);
+                }
             }
             if (!resident && !((PDE_ABL & 8) && s > 0)) {
                 dma_wait_all();                           // my pieces of the next record have landed
@@ -949,7 +1001,10 @@ struct BwdStage {
     static constexpr int kFloats = kStep ? kSlots * kRecPad : 2 * kRecPad;
 };
 
-template <int N, int J, typename IO, bool MASKED, int SPLIT>
+// EMIT (pde_adi_*_backward_states): a.states holds dL/d(state after sweep s) for every bit s of a.em; it joins the
+// adjoint when the walk has undone sweep s+1.  The adjoint carries one factor (1+eps) per undone sweep (INVB in
+// pde_common.h), so the plane comes in times (1+eps)^(S-1-s) = 1/ysc[s].
+template <int N, int J, typename IO, bool MASKED, int SPLIT, bool EMIT = false>
 __device__ __forceinline__ void adi_bwd_body(const SweepArgs& a, int blk) {
     constexpr int M = Geo<N>::M;
     using ST = BwdStage<MASKED, SPLIT>;
@@ -1093,6 +1148,12 @@ __device__ __forceinline__ void adi_bwd_body(const SweepArgs& a, int blk) {
 #pragma unroll
             for (int k = 0; k < M; ++k) x[k] = x[k] * pk_bc<P>(sc);
         }
+        if constexpr (EMIT) {
+            if (s > 0 && ck_bit(a.em, s - 1)) {
+                const IO* slot = static_cast<const IO*>(a.states) + (size_t)ck_slot(a.em, s - 1) * a.B * a.C * plane;
+                add_planes<N, J, IO>(slot, q, wave, lane, l, hf, a.B, a.C, c, T, 1.0f / tab->ysc[s - 1], r);
+            }
+        }
     };
     // Plane traffic of a chunk.  All 2J planes of a chunk are fetched together (their destination registers are dead at that
     // point): one memory round trip instead of 2J (-21 us of 345 on the 512x64x32x32 launch).
@@ -1184,9 +1245,11 @@ __device__ __forceinline__ void adi_bwd_body(const SweepArgs& a, int blk) {
                             if (s == a.S - 1) chunk_in();
                         }
                         // Strang, newest sweep of a step (an x sweep): its record equals that of the sweep processed just
-                        // before it, the first x sweep of the next step
+                        // before it, the first x sweep of the next step.  (Not in the emitting variant: the upstream
+                        // gradient of a step's state comes in between exactly these two sweeps, and rows kept across
+                        // its loads do not fit beside adjoint, state and the four sums: 20 registers spilled at N = 32.)
                         body(std::integral_constant<int, AX>{}, AX, s, cbuf + (size_t)slot * RECP, dts_of(s),
-                             std::bool_constant<(SPLIT == kSplitStrang && pos == 0 && !MASKED)>{});
+                             std::bool_constant<(SPLIT == kSplitStrang && pos == 0 && !MASKED && !EMIT)>{});
                         if constexpr (pos == SPS - 1) {
                             if (s == 0) {
                                 chunk_turn();
@@ -1271,18 +1334,18 @@ __device__ __forceinline__ void adi_bwd_body(const SweepArgs& a, int blk) {
 #ifndef PDE_BWD_MINW
 #define PDE_BWD_MINW 1
 #endif
-template <int N, int J, typename IO, int SPLIT>
+template <int N, int J, typename IO, int SPLIT, bool EMIT = false>
 __global__ __launch_bounds__(kThreads, PDE_BWD_MINW) void adi_bwd_kernel(SweepArgs a) {
     const int nb = a.C * a.G;
     if (a.only_masked) {
 #ifndef PDE_BWD_NO_MASKED
-        adi_bwd_body<N, 1, IO, true, kSplitAny>(a, (int)blockIdx.x);
+        adi_bwd_body<N, 1, IO, true, kSplitAny, EMIT>(a, (int)blockIdx.x);
 #endif
         return;
     }
-    if ((int)blockIdx.x < nb) adi_bwd_body<N, J, IO, false, SPLIT>(a, (int)blockIdx.x);
+    if ((int)blockIdx.x < nb) adi_bwd_body<N, J, IO, false, SPLIT, EMIT>(a, (int)blockIdx.x);
 #ifndef PDE_BWD_NO_MASKED        // diagnostic builds: the fast body alone (its own register allocation)
-    else adi_bwd_body<N, 1, IO, true, kSplitAny>(a, (int)blockIdx.x - nb);
+    else adi_bwd_body<N, 1, IO, true, kSplitAny, EMIT>(a, (int)blockIdx.x - nb);
 #endif
 }
 

@@ -14,10 +14,13 @@ int gen_kappa_max(const PdeAdiDesc* d, const float* ab, const float* bb, const f
 int gen_factor(const PdeAdiDesc* d, const float* ab, const float* bb, const float* as, const float* bs, float* kmax,
                void* workspace, hipStream_t st);
 // all sweeps of d on u -> y with the factorisation in `workspace`
-int gen_forward_sweeps(const PdeAdiDesc* d, const void* u, void* y, const void* workspace, hipStream_t st);
+// (states / emit: the emitting variants — nullptr, or a tensor and a non-empty mask already checked by the caller)
+int gen_forward_sweeps(const PdeAdiDesc* d, const void* u, void* y, const void* workspace, hipStream_t st,
+                       void* states = nullptr, const uint64_t* emit = nullptr);
 // adjoint + the four parameter gradients; nck / Sf from the checkpoint mask as in the fused path
 int gen_backward(const PdeAdiDesc* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], int nck,
                  int Sf, void* gu, const float* ab, const float* bb, const float* as, const float* bs, float* g_ab,
-                 float* g_bb, float* g_as, float* g_bs, const void* fwd_workspace, void* workspace, hipStream_t st);
+                 float* g_bb, float* g_as, float* g_bs, const void* fwd_workspace, void* workspace, hipStream_t st,
+                 const void* gstates = nullptr, const uint64_t* emit = nullptr);
 
 }  // namespace pde

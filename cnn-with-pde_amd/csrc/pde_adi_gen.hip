@@ -142,6 +142,16 @@ struct GenSweepArgs {
     T eps;
     T* xg;                                   // backward with the state plane in global memory: [G*C][H][W+1] | nullptr
 };
+// The emitting variants (EMIT = true) take their own argument structure, so the plain kernels keep theirs to the byte.
+// Bit s of em = the state after sweep s leaves the launch; forward: written to states[slot][B][C][H*W] in the I/O type;
+// backward: the same layout holds dL/d(state).
+template <typename T>
+struct GenEmitArgs : GenSweepArgs<T> {
+    void* states;
+    unsigned long long em[2];
+};
+template <typename T, bool EMIT>
+using GenArgs = typename std::conditional<EMIT, GenEmitArgs<T>, GenSweepArgs<T>>::type;
 
 __device__ __forceinline__ int gen_ck_bit(const unsigned long long (&ck)[2], int s) { return (int)((ck[s >> 6] >> (s & 63)) & 1ull); }
 __device__ __forceinline__ int gen_ck_slot(const unsigned long long (&ck)[2], int s) {
@@ -157,8 +167,9 @@ __device__ __forceinline__ int gen_ck_slot(const unsigned long long (&ck)[2], in
 constexpr int kGenBatch = 8;
 
 // forward: one workgroup per plane; sweeps 0..S-1 on the plane in LDS ([row < H][W+1])
-template <typename TT, typename IO>
-__global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
+// EMIT (the *_forward_states entry points): the plane also goes to a.states after every sweep whose bit is set in a.em
+template <typename TT, typename IO, bool EMIT = false>
+__global__ void gen_fwd_kernel(GenArgs<TT, EMIT> a) {
     extern __shared__ float gen_fsmem[];
     TT* X = reinterpret_cast<TT*>(gen_fsmem);
     const int W = a.W, ld = W + 1, tid = threadIdx.x, T = blockDim.x, NN = a.H * W;
@@ -214,6 +225,13 @@ __global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
             TT* dst = a.ckpt + (size_t)gen_ck_slot(a.ck, s) * a.B * a.C * plane + pb;
             for (int e = tid; e < NN; e += T) dst[e] = X[(e / W) * ld + (e % W)];
         }
+        if constexpr (EMIT) {
+            if (gen_ck_bit(a.em, s)) {
+                const size_t o = (size_t)gen_ck_slot(a.em, s) * a.B * a.C * plane + pb;
+                for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.states, o + e, X[(e / W) * ld + (e % W)]);
+                __syncthreads();             // the copy reads other threads' lines: all of it before the next sweep writes them
+            }
+        }
     }
     if (a.out)
         for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.out, pb + e, X[(e / W) * ld + (e % W)]);
@@ -226,8 +244,10 @@ __global__ void gen_fwd_kernel(GenSweepArgs<TT> a) {
 // owning thread.
 // XG (two planes beyond the LDS limit: T = double at 128 x 128): the state plane X lives in a global scratch slice the workgroup owns,
 // the adjoint plane R stays in LDS.
-template <typename TT, typename IO, bool ALDS, bool XG>
-__global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
+// EMIT (the *_backward_states entry points): a.states holds dL/d(state after sweep s) for every bit s of a.em; the plane is
+// added to the adjoint once sweep s+1 has been undone (state and adjoint are the true ones here: no scale).
+template <typename TT, typename IO, bool ALDS, bool XG, bool EMIT = false>
+__global__ void gen_bwd_kernel(GenArgs<TT, EMIT> a, int smooth3) {
     extern __shared__ float gen_smem[];
     const int H = a.H, W = a.W, ld = W + 1, tid = threadIdx.x, T = blockDim.x, NN = H * W;
     TT* X = XG ? a.xg + (size_t)blockIdx.x * H * ld : reinterpret_cast<TT*>(gen_smem);
@@ -368,6 +388,13 @@ __global__ void gen_bwd_kernel(GenSweepArgs<TT> a, int smooth3) {
                 for (int e = tid; e < NN; e += T) X[(e / W) * ld + (e % W)] = src[e];
                 __syncthreads();
             }
+            if constexpr (EMIT) {
+                if (s > 0 && gen_ck_bit(a.em, s - 1)) {
+                    const size_t o = (size_t)gen_ck_slot(a.em, s - 1) * a.B * a.C * plane + pb;
+                    for (int e = tid; e < NN; e += T) R[(e / W) * ld + (e % W)] += GenIo<IO>::ld(a.states, o + e);
+                    __syncthreads();
+                }
+            }
         }
         for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.out, pb + e, R[(e / W) * ld + (e % W)]);
     }
@@ -449,7 +476,7 @@ int gen_lds(K kernel, unsigned long long& done) { return ensure_dynamic_lds((con
 
 template <typename T, typename D>
 int launch_gen_fwd(const D* d, const void* u, void* y, const T* fac, const GenSweep<T>* tab, int S, T* ckpt,
-                   const uint64_t ck[2], hipStream_t st) {
+                   const uint64_t ck[2], hipStream_t st, void* states = nullptr, const uint64_t* emit = nullptr) {
     GenSweepArgs<T> sa{};
     sa.in0 = u; sa.out = y; sa.fac = fac; sa.tab = tab; sa.ckpt = ckpt;
     sa.ck[0] = ck ? ck[0] : 0ull; sa.ck[1] = ck ? ck[1] : 0ull;
@@ -457,6 +484,23 @@ int launch_gen_fwd(const D* d, const void* u, void* y, const T* fac, const GenSw
     const size_t lds = gen_img<T>(d);
     static unsigned long long done_f = 0, done_b = 0, done_h = 0;
     int rc;
+    if (emit) {
+        GenEmitArgs<T> ea{};
+        static_cast<GenSweepArgs<T>&>(ea) = sa;
+        ea.states = states; ea.em[0] = emit[0]; ea.em[1] = emit[1];
+        static unsigned long long done_e[3] = {0, 0, 0};
+#define PDE_GEN_FWD_EMIT(TY, IO, SLOT)                                                                                  \
+    do {                                                                                                                \
+        if ((rc = gen_lds(gen_fwd_kernel<TY, IO, true>, done_e[SLOT])) != PDE_OK) return rc;                            \
+        hipLaunchKernelGGL((gen_fwd_kernel<TY, IO, true>), dim3(d->B * d->C), dim3(gen_threads(d)), lds, st, ea);      \
+    } while (0)
+        if constexpr (std::is_same<T, double>::value) PDE_GEN_FWD_EMIT(double, double, 0);
+        else if (d->io_dtype == PDE_IO_F32) PDE_GEN_FWD_EMIT(float, float, 0);
+        else if (d->io_dtype == PDE_IO_F16) PDE_GEN_FWD_EMIT(float, gen_f16, 1);
+        else PDE_GEN_FWD_EMIT(float, gen_bf16, 2);
+#undef PDE_GEN_FWD_EMIT
+        return check_launch();
+    }
     if constexpr (std::is_same<T, double>::value) {
         if ((rc = gen_lds(gen_fwd_kernel<double, double>, done_f)) != PDE_OK) return rc;
         hipLaunchKernelGGL((gen_fwd_kernel<double, double>), dim3(d->B * d->C), dim3(gen_threads(d)), lds, st, sa);
@@ -492,16 +536,18 @@ int factor_impl(const D* d, const T* ab, const T* bb, const T* as, const T* bs, 
 }
 
 template <typename T, typename D>
-int forward_sweeps_impl(const D* d, const void* u, void* y, const void* workspace, hipStream_t st) {
+int forward_sweeps_impl(const D* d, const void* u, void* y, const void* workspace, hipStream_t st, void* states = nullptr,
+                        const uint64_t* emit = nullptr) {
     const char* ws = static_cast<const char*>(workspace);
     return launch_gen_fwd<T>(d, u, y, reinterpret_cast<const T*>(ws), reinterpret_cast<const GenSweep<T>*>(ws + fac_bytes<T>(d)),
-                             d->num_sweeps, (T*)nullptr, nullptr, st);
+                             d->num_sweeps, (T*)nullptr, nullptr, st, states, emit);
 }
 
 template <typename T, typename D>
 int backward_impl(const D* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], int nck, int Sf,
                   void* gu, const T* ab, const T* bb, const T* as, const T* bs, T* g_ab, T* g_bb, T* g_as, T* g_bs,
-                  const void* fwd_workspace, void* workspace, hipStream_t st) {
+                  const void* fwd_workspace, void* workspace, hipStream_t st, const void* gstates = nullptr,
+                  const uint64_t* emit = nullptr) {
     char* ws = static_cast<char*>(workspace);
     const T* fac = reinterpret_cast<const T*>(ws);
     const GenSweep<T>* tab = reinterpret_cast<const GenSweep<T>*>(ws + fac_bytes<T>(d));
@@ -530,16 +576,24 @@ int backward_impl(const D* d, const void* gy, const void* y, const void* u, cons
     sa.in0 = gy; sa.in1 = y; sa.out = gu; sa.fac = fac; sa.tab = tab; sa.ckpt = ckpt; sa.part = part; sa.xg = xplanes;
     sa.ck[0] = nck ? ckpt_mask[0] : 0ull; sa.ck[1] = nck ? ckpt_mask[1] : 0ull;
     sa.B = d->B; sa.C = d->C; sa.H = rows_of(d); sa.W = cols_of(d); sa.S = d->num_sweeps; sa.G = G; sa.eps = d->eps;
+    GenEmitArgs<T> ea{};
+    static_cast<GenSweepArgs<T>&>(ea) = sa;
+    if (emit) { ea.states = const_cast<void*>(gstates); ea.em[0] = emit[0]; ea.em[1] = emit[1]; }
     const size_t img = gen_img<T>(d);
     // the partial sums beside the planes while four workgroups still fit on a CU (squares: fp32 N <= 40, fp64 N <= 28)
     const bool alds = !xg && 4 * 6 * img <= (size_t)kGenLdsMax;
     const size_t lds = xg ? img : (alds ? 6 : 2) * img;
-    static unsigned long long done[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    static unsigned long long done[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, done_e[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     const dim3 grid(G * d->C), block(gen_threads(d));
-#define PDE_GEN_BWD(TY, IO, AL, XG, SLOT)                                                                \
-    do {                                                                                                 \
-        if ((rc = gen_lds(gen_bwd_kernel<TY, IO, AL, XG>, done[SLOT])) != PDE_OK) return rc;             \
-        hipLaunchKernelGGL((gen_bwd_kernel<TY, IO, AL, XG>), grid, block, lds, st, sa, (int)d->smooth3); \
+#define PDE_GEN_BWD(TY, IO, AL, XG, SLOT)                                                                          \
+    do {                                                                                                           \
+        if (emit) {                                                                                                \
+            if ((rc = gen_lds(gen_bwd_kernel<TY, IO, AL, XG, true>, done_e[SLOT])) != PDE_OK) return rc;           \
+            hipLaunchKernelGGL((gen_bwd_kernel<TY, IO, AL, XG, true>), grid, block, lds, st, ea, (int)d->smooth3); \
+        } else {                                                                                                   \
+            if ((rc = gen_lds(gen_bwd_kernel<TY, IO, AL, XG>, done[SLOT])) != PDE_OK) return rc;                   \
+            hipLaunchKernelGGL((gen_bwd_kernel<TY, IO, AL, XG>), grid, block, lds, st, sa, (int)d->smooth3);       \
+        }                                                                                                          \
     } while (0)
     if constexpr (std::is_same<T, double>::value) {
         if (xg) PDE_GEN_BWD(double, double, false, true, 4);
@@ -578,15 +632,17 @@ int gen_factor(const PdeAdiDesc* d, const float* ab, const float* bb, const floa
     return factor_impl<float>(d, ab, bb, as, bs, kmax, workspace, st);
 }
 
-int gen_forward_sweeps(const PdeAdiDesc* d, const void* u, void* y, const void* workspace, hipStream_t st) {
-    return forward_sweeps_impl<float>(d, u, y, workspace, st);
+int gen_forward_sweeps(const PdeAdiDesc* d, const void* u, void* y, const void* workspace, hipStream_t st, void* states,
+                       const uint64_t* emit) {
+    return forward_sweeps_impl<float>(d, u, y, workspace, st, states, emit);
 }
 
 int gen_backward(const PdeAdiDesc* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], int nck,
                  int Sf, void* gu, const float* ab, const float* bb, const float* as, const float* bs, float* g_ab,
-                 float* g_bb, float* g_as, float* g_bs, const void* fwd_workspace, void* workspace, hipStream_t st) {
+                 float* g_bb, float* g_as, float* g_bs, const void* fwd_workspace, void* workspace, hipStream_t st,
+                 const void* gstates, const uint64_t* emit) {
     return backward_impl<float>(d, gy, y, u, ckpt_mask, nck, Sf, gu, ab, bb, as, bs, g_ab, g_bb, g_as, g_bs, fwd_workspace,
-                                workspace, st);
+                                workspace, st, gstates, emit);
 }
 
 }  // namespace pde
@@ -620,6 +676,18 @@ int ckpt_plan(const D* d, const uint64_t ckpt_mask[2], const void* u, int& nck, 
                 Sf = s + 1;
             }
     }
+    return PDE_OK;
+}
+
+// emission mask -> the mask to launch with (nullptr: empty, the plain call); PDE_E_BADARG for a bit at or above S-1 (the
+// last state is y itself) or a missing tensor
+int emit_plan(int num_sweeps, const uint64_t emit_mask[2], const void* states, const uint64_t*& emit) {
+    emit = nullptr;
+    if (!emit_mask || !(emit_mask[0] | emit_mask[1])) return PDE_OK;
+    if (!states) return PDE_E_BADARG;
+    for (int s = num_sweeps > 0 ? num_sweeps - 1 : 0; s < 128; ++s)
+        if ((emit_mask[s >> 6] >> (s & 63)) & 1ull) return PDE_E_BADARG;
+    emit = emit_mask;
     return PDE_OK;
 }
 
@@ -659,10 +727,13 @@ int rect_kappa_max(const D* d, const T* ab, const T* bb, const T* as, const T* b
 // factorisation (+ maxima), the maxima's way to the host, the sweeps
 template <typename T, typename D>
 int rect_forward(const D* d, const void* u, void* y, const T* ab, const T* bb, const T* as, const T* bs, T* kmax,
-                 T* kmax_host, void* kappa_event, void* workspace, size_t workspace_bytes, void* stream) {
+                 T* kmax_host, void* kappa_event, void* workspace, size_t workspace_bytes, void* stream,
+                 void* states = nullptr, const uint64_t* emit_mask = nullptr) {
     int rc = check_desc_rect<T>(d);
     if (rc != PDE_OK) return rc;
     if (!u || !y || !ab || !bb || !as || !bs || !workspace) return PDE_E_BADARG;
+    const uint64_t* emit;
+    if ((rc = emit_plan(d->num_sweeps, emit_mask, states, emit)) != PDE_OK) return rc;
     if (kmax_host && !kmax) return PDE_E_BADARG;
     if (workspace_bytes < fwd_ws_bytes<T>(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -672,22 +743,25 @@ int rect_forward(const D* d, const void* u, void* y, const T* ab, const T* bb, c
     if (kmax_host && hipMemcpyAsync(kmax_host, kmax, (size_t)d->num_sweeps * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess)
         return PDE_E_LAUNCH;
     if (kappa_event && hipEventRecord(static_cast<hipEvent_t>(kappa_event), st) != hipSuccess) return PDE_E_LAUNCH;
-    return forward_sweeps_impl<T>(d, u, y, workspace, st);
+    return forward_sweeps_impl<T>(d, u, y, workspace, st, states, emit);
 }
 
 template <typename T, typename D>
 int rect_backward(const D* d, const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
                   const T* ab, const T* bb, const T* as, const T* bs, T* g_ab, T* g_bb, T* g_as, T* g_bs,
-                  const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+                  const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream,
+                  const void* gstates = nullptr, const uint64_t* emit_mask = nullptr) {
     int rc = check_desc_rect<T>(d);
     if (rc != PDE_OK) return rc;
     if (!gy || !y || !gu || !ab || !bb || !as || !bs || !g_ab || !g_bb || !g_as || !g_bs || !workspace) return PDE_E_BADARG;
+    const uint64_t* emit;
+    if ((rc = emit_plan(d->num_sweeps, emit_mask, gstates, emit)) != PDE_OK) return rc;
     int nck, Sf;
     rc = ckpt_plan(d, ckpt_mask, u, nck, Sf);
     if (rc != PDE_OK) return rc;
     if (workspace_bytes < bwd_ws_bytes<T>(d, nck) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
     return backward_impl<T>(d, gy, y, u, ckpt_mask, nck, Sf, gu, ab, bb, as, bs, g_ab, g_bb, g_as, g_bs, fwd_workspace,
-                            workspace, static_cast<hipStream_t>(stream));
+                            workspace, static_cast<hipStream_t>(stream), gstates, emit);
 }
 
 }  // namespace
@@ -704,17 +778,49 @@ size_t pde_adi_f64_backward_workspace_bytes(const PdeAdiDescF64* d, int32_t num_
     return bwd_ws_bytes<double>(d, num_checkpoints);
 }
 
-int pde_adi_f64_forward(const PdeAdiDescF64* d, const double* u, double* y, const double* alpha_base, const double* beta_base,
-                        const double* alpha_slope, const double* beta_slope, double* kappa_max, void* workspace,
-                        size_t workspace_bytes, void* stream) {
+int pde_adi_f64_forward_states(const PdeAdiDescF64* d, const double* u, double* y, double* states, const uint64_t emit_mask[2],
+                               const double* alpha_base, const double* beta_base, const double* alpha_slope,
+                               const double* beta_slope, double* kappa_max, void* workspace, size_t workspace_bytes,
+                               void* stream) {
     int rc = check_desc_f64(d);
     if (rc != PDE_OK) return rc;
     if (!u || !y || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    const uint64_t* emit;
+    if ((rc = emit_plan(d->num_sweeps, emit_mask, states, emit)) != PDE_OK) return rc;
     if (workspace_bytes < pde_adi_f64_forward_workspace_bytes(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = factor_impl<double>(d, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, workspace, st);
     if (rc != PDE_OK) return rc;
-    return forward_sweeps_impl<double>(d, u, y, workspace, st);
+    return forward_sweeps_impl<double>(d, u, y, workspace, st, states, emit);
+}
+
+int pde_adi_f64_forward(const PdeAdiDescF64* d, const double* u, double* y, const double* alpha_base, const double* beta_base,
+                        const double* alpha_slope, const double* beta_slope, double* kappa_max, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    return pde_adi_f64_forward_states(d, u, y, nullptr, nullptr, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max,
+                                      workspace, workspace_bytes, stream);
+}
+
+int pde_adi_f64_backward_states(const PdeAdiDescF64* d, const double* gy, const double* gstates, const uint64_t emit_mask[2],
+                                const double* y, const double* u, const uint64_t ckpt_mask[2], double* gu,
+                                const double* alpha_base, const double* beta_base, const double* alpha_slope,
+                                const double* beta_slope, double* g_alpha_base, double* g_beta_base, double* g_alpha_slope,
+                                double* g_beta_slope, const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    int rc = check_desc_f64(d);
+    if (rc != PDE_OK) return rc;
+    if (!gy || !y || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !g_alpha_base || !g_beta_base ||
+        !g_alpha_slope || !g_beta_slope || !workspace)
+        return PDE_E_BADARG;
+    const uint64_t* emit;
+    if ((rc = emit_plan(d->num_sweeps, emit_mask, gstates, emit)) != PDE_OK) return rc;
+    int nck, Sf;
+    rc = ckpt_plan(d, ckpt_mask, u, nck, Sf);
+    if (rc != PDE_OK) return rc;
+    if (workspace_bytes < pde_adi_f64_backward_workspace_bytes(d, nck) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    return backward_impl<double>(d, gy, y, u, ckpt_mask, nck, Sf, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                                 g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
+                                 static_cast<hipStream_t>(stream), gstates, emit);
 }
 
 int pde_adi_f64_backward(const PdeAdiDescF64* d, const double* gy, const double* y, const double* u,
@@ -722,18 +828,9 @@ int pde_adi_f64_backward(const PdeAdiDescF64* d, const double* gy, const double*
                          const double* alpha_slope, const double* beta_slope, double* g_alpha_base, double* g_beta_base,
                          double* g_alpha_slope, double* g_beta_slope, const void* fwd_workspace, void* workspace,
                          size_t workspace_bytes, void* stream) {
-    int rc = check_desc_f64(d);
-    if (rc != PDE_OK) return rc;
-    if (!gy || !y || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !g_alpha_base || !g_beta_base ||
-        !g_alpha_slope || !g_beta_slope || !workspace)
-        return PDE_E_BADARG;
-    int nck, Sf;
-    rc = ckpt_plan(d, ckpt_mask, u, nck, Sf);
-    if (rc != PDE_OK) return rc;
-    if (workspace_bytes < pde_adi_f64_backward_workspace_bytes(d, nck) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
-    return backward_impl<double>(d, gy, y, u, ckpt_mask, nck, Sf, gu, alpha_base, beta_base, alpha_slope, beta_slope,
-                                 g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
-                                 static_cast<hipStream_t>(stream));
+    return pde_adi_f64_backward_states(d, gy, nullptr, nullptr, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope,
+                                       beta_slope, g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace,
+                                       workspace, workspace_bytes, stream);
 }
 
 // ---- rectangular planes (include/pdecnn.h): the same kernels with H != W, fp32 / bf16 / fp16 tensors and float64 -----
@@ -766,6 +863,25 @@ int pde_adi_rect_backward(const PdeAdiRectDesc* d, const void* gy, const void* y
                                 g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace, workspace_bytes, stream);
 }
 
+int pde_adi_rect_forward_states(const PdeAdiRectDesc* d, const void* u, void* y, void* states, const uint64_t emit_mask[2],
+                                const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                                const float* beta_slope, float* kappa_max, float* kappa_max_host, void* kappa_event,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    return rect_forward<float>(d, u, y, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, kappa_max_host,
+                               kappa_event, workspace, workspace_bytes, stream, states, emit_mask);
+}
+
+int pde_adi_rect_backward_states(const PdeAdiRectDesc* d, const void* gy, const void* gstates, const uint64_t emit_mask[2],
+                                 const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
+                                 const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                                 const float* beta_slope, float* g_alpha_base, float* g_beta_base, float* g_alpha_slope,
+                                 float* g_beta_slope, const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    return rect_backward<float>(d, gy, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base,
+                                g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace, workspace_bytes, stream,
+                                gstates, emit_mask);
+}
+
 size_t pde_adi_rect_f64_forward_workspace_bytes(const PdeAdiRectDescF64* d) { return rect_fwd_bytes<double>(d); }
 
 size_t pde_adi_rect_f64_backward_workspace_bytes(const PdeAdiRectDescF64* d, int32_t num_checkpoints) {
@@ -792,6 +908,25 @@ int pde_adi_rect_f64_backward(const PdeAdiRectDescF64* d, const double* gy, cons
     return rect_backward<double>(d, gy, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope,
                                  g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
                                  workspace_bytes, stream);
+}
+
+int pde_adi_rect_f64_forward_states(const PdeAdiRectDescF64* d, const double* u, double* y, double* states,
+                                    const uint64_t emit_mask[2], const double* alpha_base, const double* beta_base,
+                                    const double* alpha_slope, const double* beta_slope, double* kappa_max, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    return rect_forward<double>(d, u, y, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, (double*)nullptr,
+                                nullptr, workspace, workspace_bytes, stream, states, emit_mask);
+}
+
+int pde_adi_rect_f64_backward_states(const PdeAdiRectDescF64* d, const double* gy, const double* gstates,
+                                     const uint64_t emit_mask[2], const double* y, const double* u,
+                                     const uint64_t ckpt_mask[2], double* gu, const double* alpha_base,
+                                     const double* beta_base, const double* alpha_slope, const double* beta_slope,
+                                     double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
+                                     const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    return rect_backward<double>(d, gy, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                                 g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
+                                 workspace_bytes, stream, gstates, emit_mask);
 }
 
 }  // extern "C"

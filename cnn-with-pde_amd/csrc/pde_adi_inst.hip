@@ -42,6 +42,20 @@ int fwd_io(int split, int ho, const SweepArgs& sa, int grid, size_t lds, hipStre
     }
 }
 
+// the emitting variant (pde_adi_*_forward_states): barrier-per-sweep schedule at every N and I/O type.  At N = 32 the
+// step-pattern bodies do not fit 128 VGPRs (the plain ones spill 3-13 registers there too): the emitting call takes the
+// table-driven body, which does (110 VGPRs, no scratch) — the same arithmetic in the same order, the axis read per sweep
+template <typename IO>
+int fwd_emit_io(int split, const SweepArgs& sa, int grid, size_t lds, hipStream_t st) {
+    constexpr int N = PDE_INST_N;
+    if constexpr (N == 32) return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitAny, false, true>, sa, grid, lds, st);
+    else switch (split) {
+        case kSplitStrang: return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitStrang, false, true>, sa, grid, lds, st);
+        case kSplitLie: return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitLie, false, true>, sa, grid, lds, st);
+        default: return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitAny, false, true>, sa, grid, lds, st);
+    }
+}
+
 template <bool MASKED, int SPLIT>
 constexpr size_t bwd_lds() { return (size_t)(BwdStage<MASKED, SPLIT>::kFloats + kWaves * kImage) * sizeof(float); }
 template <int SPLIT>
@@ -60,7 +74,29 @@ int bwd_io(int split, const SweepArgs& sa, int grid, hipStream_t st) {
     }
 }
 
+template <typename IO>
+int bwd_emit_io(int split, const SweepArgs& sa, int grid, hipStream_t st) {
+    constexpr int N = PDE_INST_N;
+    switch (split) {
+        case kSplitStrang: return launch(adi_bwd_kernel<N, kJBwd, IO, kSplitStrang, true>, sa, grid, bwd_lds_dual<kSplitStrang>(), st);
+        case kSplitLie: return launch(adi_bwd_kernel<N, kJBwd, IO, kSplitLie, true>, sa, grid, bwd_lds_dual<kSplitLie>(), st);
+        default: return launch(adi_bwd_kernel<N, 1, IO, kSplitAny, true>, sa, grid, bwd_lds_dual<kSplitAny>(), st);
+    }
+}
+
 }  // namespace
+
+int PDE_CAT(adi_launch_fwd_emit_, PDE_INST_N)(int io, int split, const void* args, int grid, size_t lds, hipStream_t st) {
+    const SweepArgs& sa = *static_cast<const SweepArgs*>(args);
+    if (io == PDE_IO_F16) return fwd_emit_io<half_t>(split, sa, grid, lds, st);
+    return io == PDE_IO_F32 ? fwd_emit_io<float>(split, sa, grid, lds, st) : fwd_emit_io<bf16_t>(split, sa, grid, lds, st);
+}
+
+int PDE_CAT(adi_launch_bwd_emit_, PDE_INST_N)(int io, int split, const void* args, int grid, hipStream_t st) {
+    const SweepArgs& sa = *static_cast<const SweepArgs*>(args);
+    if (io == PDE_IO_F16) return bwd_emit_io<half_t>(split, sa, grid, st);
+    return io == PDE_IO_F32 ? bwd_emit_io<float>(split, sa, grid, st) : bwd_emit_io<bf16_t>(split, sa, grid, st);
+}
 
 int PDE_CAT(adi_launch_fwd_, PDE_INST_N)(int io, int split, int ho, const void* args, int grid, size_t lds, hipStream_t st) {
     const SweepArgs& sa = *static_cast<const SweepArgs*>(args);

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_mixed", "adi_diffuse_small", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse",
+__all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse",
            "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
            "sym_layer_f16_supported", "sym_layer_bf16_supported", "sym_k16"]
 
@@ -973,17 +973,9 @@ def adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
         # entry points do not exist there; compose the layer from its own pieces — the channel operator and the sweeps of
         # one step per call, chained by autograd (the step-local checkpoint mask applies to every step unchanged).  float64
         # takes this route at every line length: its sweeps are the any-size kernels instantiated for double
-        tickets = [] if kmax_sink is not None else None
-        for st in steps:
-            if mode == "pre":
-                u = channel_mix(u, M)
-            u = adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, st, smooth3=smooth3,
-                            clamp_max=clamp_max, eps=eps, checkpoints=checkpoints, kmax_sink=tickets)
-            if mode == "post":
-                u = channel_mix(u, M)
-        if tickets and len(tickets) == len(steps):           # the whole layer's maxima, step after step (lagged plans)
-            kmax_sink.append(_KmaxConcat(tickets))
-        return u
+        return adi_diffuse_mixed_per_step(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode,
+                                          smooth3=smooth3, clamp_max=clamp_max, eps=eps, checkpoints=checkpoints,
+                                          kmax_sink=kmax_sink)
     if kmax_sink is None and (checkpoints == "auto" or isinstance(checkpoints, int)):
         H = L.host_ext()
         if H is not None and u.dim() == 4 and u.is_cuda and u.shape[2] == u.shape[3]:
@@ -996,6 +988,29 @@ def adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
                            0 if checkpoints == "auto" else int(checkpoints), CKPT_AMAX)
     return _AdiMixedFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode, bool(smooth3),
                              clamp_max, float(eps), checkpoints, kmax_sink)
+
+
+def adi_diffuse_mixed_per_step(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode: str,
+                               smooth3: bool = False, clamp_max: Optional[float] = None, eps: float = 1e-6,
+                               checkpoints="auto", kmax_sink: Optional[list] = None, states: Optional[list] = None):
+    """A layer with a channel operator composed from its own pieces, at every C and every plane: the operator and the sweeps
+    of one step per call, chained by autograd (the step-local checkpoint mask applies to every step unchanged).  This is
+    how ``adi_diffuse_mixed`` runs rectangles, line lengths without fused kernels and float64.  ``states``: a list that
+    receives the state after every step — after the step's sweeps and, in "post" mode, after its operator; each one is a
+    node of the autograd graph, so a loss may be put on any of them."""
+    tickets = [] if kmax_sink is not None else None
+    for st in steps:
+        if mode == "pre":
+            u = channel_mix(u, M)
+        u = adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, st, smooth3=smooth3,
+                        clamp_max=clamp_max, eps=eps, checkpoints=checkpoints, kmax_sink=tickets)
+        if mode == "post":
+            u = channel_mix(u, M)
+        if states is not None:
+            states.append(u)
+    if tickets and len(tickets) == len(steps):           # the whole layer's maxima, step after step (lagged plans)
+        kmax_sink.append(_KmaxConcat(tickets))
+    return u
 
 
 def _empty_passthrough(u, *params):
@@ -1059,6 +1074,127 @@ def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, swe
             return H.adi(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, C.addressof(d), mode, lo, hi, CKPT_AMAX)
     return _AdiFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff,
                         sweeps, bool(smooth3), clamp_max, float(eps), checkpoints, kmax_sink)
+
+
+class _AdiStatesFn(torch.autograd.Function):
+    """adi_diffuse that also returns the state after chosen sweeps, out of the same launch (pde_adi*_forward_states /
+    pde_adi*_backward_states): one node for the four families — squares and rectangles, fp32 / bf16 / fp16 tensors
+    and float64.  The result is ONE tensor (K', B, C, H, W); the library's ``y`` is its last slice."""
+
+    @staticmethod
+    def forward(ctx, u, ab, bb, asl, bsl, sweeps, emit, smooth3, clamp_max, eps, ckpt, kmax_sink, f64):
+        lib = L.load()
+        if u.dim() != 4:
+            raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
+        rect = u.shape[2] != u.shape[3]
+        if rect:
+            _check_rect(u, ab, bb, asl, bsl)
+        else:
+            _require_cuda(u, ab, bb, asl, bsl)
+        B, Cc, H, W = u.shape
+        if f64:
+            u = u.to(torch.float64).contiguous()
+            p = [_as_chw64(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
+            io = L.PDE_IO_F64
+            d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps) if rect else \
+                _make_desc64(B, Cc, H, sweeps, smooth3, clamp_max, eps)
+            ckpt = _f64_ckpt_bits(ckpt, len(sweeps))
+        else:
+            if u.dtype not in _IO_TYPES:
+                u = u.float()
+            u = u.contiguous()
+            p = [_as_chw(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
+            io = _io_dtype(u)
+            d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps) if rect else \
+                _make_desc(B, Cc, H, io, sweeps, smooth3, clamp_max, eps)
+        fam = "pde_adi_" + ("rect_" if rect else "") + ("f64_" if f64 else "")
+        K = len(emit)
+        out = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
+        bits = sum(1 << s for s in emit[:-1])
+        em = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+        ws = _workspace(getattr(lib, fam + "forward_workspace_bytes")(C.byref(d)), u.device)
+        need_grad = any(ctx.needs_input_grad[:5])
+        want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
+        kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
+        with torch.cuda.device(u.device):
+            tk = _kmax_channel(len(sweeps)) if want_kmax else None
+            head = (C.byref(d), _ptr(u), _ptr(out[K - 1]), _ptr(out), em, *[_ptr(t) for t in p])
+            if f64:
+                rc = getattr(lib, fam + "forward_states")(*head, None, _ptr(ws), ws.numel(), _stream())
+            else:
+                rc = getattr(lib, fam + "forward_states")(*head, _ptr(kdev), _ptr(tk.host if tk else None),
+                                                          C.c_void_p(tk.event.cuda_event if tk else 0), _ptr(ws),
+                                                          ws.numel(), _stream())
+            L.check(rc, fam + "forward_states")
+            ctx.kmax = tk
+            if tk is not None and kmax_sink is not None:
+                kmax_sink.append(tk)
+        ctx.fwd_ws = ws if need_grad else None       # factorisation reused by the backward
+        ctx.save_for_backward(out, u if (need_grad and ckpt != 0) else None, *p)
+        ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt, f64, rect, bits)
+        ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        out, u, *p = ctx.saved_tensors
+        sweeps, smooth3, clamp_max, eps, ckpt, f64, rect, ebits = ctx.cfg
+        K, B, Cc, H, W = out.shape
+        g = g.to(out.dtype).contiguous()             # slots 0..K-2 are gstates, the last slice is gy
+        io = L.PDE_IO_F64 if f64 else _io_dtype(out)
+        if rect:
+            d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps)
+        else:
+            d = _make_desc64(B, Cc, H, sweeps, smooth3, clamp_max, eps) if f64 else \
+                _make_desc(B, Cc, H, io, sweeps, smooth3, clamp_max, eps)
+        fam = "pde_adi_" + ("rect_" if rect else "") + ("f64_" if f64 else "")
+        gu = torch.empty_like(out[0])
+        gp = [torch.empty_like(t) for t in p]
+        bits = plan_checkpoints(ctx.kmax.wait()) if ckpt == "auto" else int(ckpt)
+        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+        em = (C.c_uint64 * 2)(ebits & _M64, ebits >> 64)
+        ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(C.byref(d), bin(bits).count("1")), out.device)
+        with torch.cuda.device(out.device):          # autograd thread: set device, fetch the stream here
+            L.check(getattr(lib, fam + "backward_states")(C.byref(d), _ptr(g[K - 1]), _ptr(g), em, _ptr(out[K - 1]),
+                                                          _ptr(u if bits else None), mask, _ptr(gu),
+                                                          *[_ptr(t) for t in p], *[_ptr(t) for t in gp],
+                                                          _ptr(ctx.fwd_ws), _ptr(ws), ws.numel(), _stream()),
+                    fam + "backward_states")
+        ctx.fwd_ws = None
+        gp = [t.reshape(s).to(dt) for t, (s, dt) in zip(gp, ctx.param_meta)]
+        return (gu, *gp, None, None, None, None, None, None, None, None)
+
+
+def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps: Sequence[Sweep], emit,
+                       smooth3: bool = False, clamp_max: Optional[float] = None, eps: float = 1e-6, checkpoints="auto",
+                       kmax_sink: Optional[list] = None):
+    """``adi_diffuse`` that returns the trajectory: the state after every sweep listed in ``emit`` (strictly increasing
+    0-based sweep indices; the last sweep is always included) as ONE tensor (K', B, C, H, W), out of the same single
+    launch per pass.  With 16-bit tensors an emitted state is the fp32 state rounded once; the time loop goes on
+    unrounded, so the last slice is bit for bit what ``adi_diffuse`` returns.  Differentiable: ``u`` and the four
+    coefficient tensors receive the gradient of a loss on any of the returned states.  Squares and rectangles, fp32 /
+    bf16 / fp16 tensors and float64 by the rules of ``adi_diffuse``; always the ctypes path (the native host extension
+    does not know this call).  ``checkpoints`` / ``kmax_sink`` as in ``adi_diffuse``."""
+    if not isinstance(sweeps, tuple):
+        sweeps = tuple(sweeps)
+    S = len(sweeps)
+    emit = [int(s) for s in emit]
+    if any(s < 0 or s >= S for s in emit) or any(b <= a for a, b in zip(emit, emit[1:])):
+        raise ValueError(f"emit must be strictly increasing sweep indices in 0..{S - 1}, got {emit}")
+    if S == 0:
+        raise ValueError("no sweeps")
+    if not emit or emit[-1] != S - 1:
+        emit.append(S - 1)
+    emit = tuple(emit)
+    f64 = _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+    if u.shape[0] == 0:
+        y = _empty_passthrough(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+        return torch.stack([y] * len(emit))
+    if not f64:
+        u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+    return _AdiStatesFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, emit, bool(smooth3),
+                              clamp_max, float(eps), checkpoints, kmax_sink, f64)
 
 
 # --------------------------------------------------------------------------- channel mixing

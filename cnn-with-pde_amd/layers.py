@@ -191,6 +191,96 @@ class _AdiBase(nn.Module):
                  else self._diffuse_mixed(u, grp, M, mode, gi=gi))
         return u if skip_weight is None else F_.skip_blend(u0, u, skip_weight)
 
+    # ---- the trajectory: the states after chosen time steps --------------------------------------------------------
+    #: layers whose forward takes (B,1,H,W) only (mnist, fashion)
+    _single_channel = False
+
+    def _operator(self):
+        """(M, mode) of the channel operator between the steps, or (None, None)."""
+        return None, None
+
+    def _diffuse_states(self, u, sweeps, emit, gi=0):
+        """``_diffuse`` returning the states after the sweeps in ``emit`` too (functional.adi_diffuse_states): the same
+        checkpoint policies, one sweep launch per pass."""
+        args = (self.alpha_base, self.beta_base, self.alpha_time_coeff, self.beta_time_coeff)
+        kw = dict(smooth3=self._smooth3, clamp_max=self._clamp_max, eps=self.stability_eps)
+        ck = self._policy_of_group(gi, len(sweeps))
+        if not (torch.is_grad_enabled() and (u.requires_grad or any(p.requires_grad for p in args))):
+            ck = 0
+        if ck != "lagged":
+            return F_.adi_diffuse_states(u, *args, sweeps, emit, checkpoints=ck, **kw)
+        old, cache, key = self._lagged_plan(("plain", len(sweeps), sweeps[0].t), u, args, kw, sweeps,
+                                            lambda km: F_.plan_checkpoints(km, F_.CKPT_AMAX / 2))
+        sink = []
+        y = F_.adi_diffuse_states(u, *args, sweeps, emit, checkpoints=old[1], kmax_sink=sink, **kw)
+        cache[key] = (sink[0], old[1]) if sink else old
+        return y
+
+    def trajectory(self, u, steps=None):
+        """The diffusion trajectory: a tensor (K', B, C, H, W) whose slice ``i`` is the state after time step
+        ``steps[i]`` — what the reference's time loop holds at the end of that iteration: after the step's sweeps, for
+        SVHN after the coupling that follows them, for a "pre" mixing layer what the next step's mixing would read; never
+        the SVHN skip blend (``skip_weight`` is not used and gets no gradient).  It equals the output of the same layer
+        built with ``num_steps=steps[i]``.
+
+        ``steps``: None (every step) or a strictly increasing sequence of 1-based step numbers in 1..num_steps; the
+        schedule is cut after ``max(steps)``.  Inputs are routed as in ``forward`` (fp32, bf16, ``model.half()``,
+        float64; squares and rectangles; ``checkpoint_policy``; launch groups beyond 32 steps); with 16-bit tensors a
+        returned state is the fp32 state rounded once while the time loop goes on unrounded, so ``trajectory(u)[-1]`` is
+        bit for bit ``forward(u)`` of a layer without skip blend.  Differentiable in ``u``, the four coefficient
+        tensors and the channel operator.
+
+        A layer without a channel operator returns all states out of the launches ``forward`` makes (one sweep launch
+        per pass and launch group).  A layer with an operator runs step by step (functional.adi_diffuse_mixed_per_step,
+        at every C): the one-launch C <= 4 and wide kernels do not emit states; "lagged" plans there as "auto"."""
+        K = int(self.num_steps)
+        if steps is None:
+            sel = list(range(1, K + 1))
+        else:
+            try:
+                raw = list(steps)
+                sel = [int(k) for k in raw]
+                exact = all(float(k) == int(k) for k in raw)
+            except (TypeError, ValueError):
+                raise ValueError(f"steps must be None or a sequence of step numbers, got {steps!r}") from None
+            if not exact:
+                raise ValueError(f"steps must be whole step numbers, got {steps!r}")
+        if not sel or sel[0] < 1 or sel[-1] > K or any(b <= a for a, b in zip(sel, sel[1:])):
+            raise ValueError(f"steps must be strictly increasing step numbers in 1..{K}, got {steps!r}")
+        if self._single_channel and (u.dim() != 4 or u.shape[1] != 1):
+            raise ValueError("expected (B,1,%d,%d), got %s" % (*_plane(self.size), tuple(u.shape)))
+        sched = self._schedule()
+        if sel[-1] < K:                                        # the first k steps of a schedule are the schedule of k steps
+            sched = F_.Schedule(sched[:sel[-1]])
+        M, mode = self._operator()
+        hw, phw = tuple(u.shape[-2:]), tuple(self.alpha_base.shape[-2:])
+        if u.dim() == 4 and hw != phw and (hw[0] != hw[1] or phw[0] != phw[1]):
+            raise L.PdeError(f"input plane {hw[0]}x{hw[1]} does not match the layer's {phw[0]}x{phw[1]} coefficients")
+        u = F_.route_input(u, self.alpha_base, self.beta_base, self.alpha_time_coeff, self.beta_time_coeff, M)
+        sps = len(sched[0])
+        per = max(1, L.PDE_MAX_SWEEPS // sps)
+        if M is not None:
+            args = (self.alpha_base, self.beta_base, self.alpha_time_coeff, self.beta_time_coeff)
+            kw = dict(smooth3=self._smooth3, clamp_max=self._clamp_max, eps=self.stability_eps)
+            live = (M,) + args
+            grad = torch.is_grad_enabled() and (u.requires_grad or any(p.requires_grad for p in live))
+            states = []
+            for gi, grp in enumerate(self._step_groups(sched)):
+                ck = self._policy_of_group(gi) if grad else 0
+                u = F_.adi_diffuse_mixed_per_step(u, *args, M, grp, mode, checkpoints="auto" if ck == "lagged" else ck,
+                                                  states=states, **kw)
+            return torch.stack([states[k - 1] for k in sel])
+        pieces = []
+        for gi, grp in enumerate(self._step_groups(sched)):
+            first = gi * per                                   # steps first+1 .. first+len(grp) are this group's
+            mine = [k - first for k in sel if first < k <= first + len(grp)]
+            out = self._diffuse_states(u, [s for st in grp for s in st], [k * sps - 1 for k in mine], gi)
+            u = out[-1]
+            if len(grp) == len(sched) and len(mine) == out.shape[0]:
+                return out                                     # one group, its last step wanted: the launch's own tensor
+            pieces.append(out if mine and mine[-1] == len(grp) else out[:-1])
+        return torch.cat(pieces)
+
     #: False forces the per-step launch path (pde_adi_mixed_*) where the single-launch C <= 4 kernels would apply
     small_channel_kernels = True
 
@@ -235,6 +325,7 @@ class MnistDiffusionLayer(_AdiBase):
     """mnist_test.py:11-219.  (B,1,size,size) -> same — or (B,1,H,W) with ``size=(H, W)``; Strang split, smoothed
     coefficients."""
     _smooth3 = True
+    _single_channel = True
 
     def __init__(self, size=28, dt=0.001, dx=1.0, dy=1.0, num_steps=10):
         super().__init__()
@@ -266,6 +357,7 @@ class MnistDiffusionLayer(_AdiBase):
 class FashionDiffusionLayer(_AdiBase):
     """fashion_mnist.py:18-196: the mnist layer with dy == dx, dt=0.3, 4 steps, base 1.8."""
     _smooth3 = True
+    _single_channel = True
 
     def __init__(self, size=28, dt=0.3, dx=1.0, num_steps=4):
         super().__init__()
@@ -302,6 +394,9 @@ class SvhnDiffusionLayer(_AdiBase):
 
     def _uses_operator(self):
         return True
+
+    def _operator(self):
+        return self.channel_coupling, "post"
 
     def forward(self, u):
         # SVHN.py:55-76: sweeps, coupling after every step, then sigmoid(w) u0 + (1 - sigmoid(w)) u
@@ -340,6 +435,9 @@ class EnhancedDiffusionLayer(_AdiBase):
 
     def _uses_operator(self):
         return bool(self.channel_mixing_enabled)
+
+    def _operator(self):
+        return (self.channel_mixing, "pre") if self.channel_mixing_enabled else (None, None)
 
     def forward(self, u):
         steps = self._schedule()

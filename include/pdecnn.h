@@ -136,6 +136,35 @@ int pde_adi_backward(const PdeAdiDesc* d, const void* gy, const void* y, const v
                                                   pde_adi_forward call (same desc, same parameters) */,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the trajectory: intermediate states of the time loop out of the SAME launch ------------------------
+ * pde_adi_forward that also returns the state after chosen sweeps, and the backward that takes an upstream gradient for
+ * every one of them.  emit_mask is shaped like ckpt_mask (sweep s is bit s%64 of emit_mask[s/64]); only bits
+ * 0 .. num_sweeps-2 may be set (the state after the last sweep is y itself).
+ * forward_states: bit s set = the true state after sweep s is written to states[slot(s)][B][C][N][N] in io_dtype (slots
+ * in the order of the set bits; with 16-bit tensors the fp32 state rounded once — the time loop goes on unrounded).  y is
+ * the final state as in the plain call; a caller that wants one stacked tensor points y at the slice behind the last slot.
+ * backward_states: gstates has the layout of states and holds dL/d(state); when the reverse walk has undone sweep s+1
+ * and is about to enter sweep s the adjoint gets += gstates[slot(s)].  State rebuild, checkpoints, masked channels and
+ * the parameter-gradient sums are those of pde_adi_backward.
+ * Workspaces are those of the plain calls (pde_adi_forward_workspace_bytes / pde_adi_backward_workspace_bytes).
+ * Checked on the host before any launch: states / gstates NULL with a non-empty mask, or a bit at or above
+ * num_sweeps-1: PDE_E_BADARG.  An empty (or NULL) mask is the plain call exactly, states / gstates are then not read.
+ * A non-empty mask runs the emitting variants of the HIP kernels: the forward on the barrier-per-sweep schedule, the HIP
+ * backward — never the assembly kernels (pde_adi_forward_kernel / pde_adi_backward_kernel answer for the plain call).
+ * One sweep launch per pass, as the plain call. */
+int pde_adi_forward_states(const PdeAdiDesc* d, const void* u, void* y, void* states, const uint64_t emit_mask[2],
+                           const float* alpha_base, const float* beta_base,
+                           const float* alpha_slope, const float* beta_slope,
+                           float* kappa_max, float* kappa_max_host, void* kappa_event,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_backward_states(const PdeAdiDesc* d, const void* gy, const void* gstates, const uint64_t emit_mask[2],
+                            const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
+                            const float* alpha_base, const float* beta_base,
+                            const float* alpha_slope, const float* beta_slope,
+                            float* g_alpha_base, float* g_beta_base,
+                            float* g_alpha_slope, float* g_beta_slope,
+                            const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
 /* max over the tensor of coeff_s = theta_s*delta_s/h2_s for every sweep, written to
  * kappa_max[num_sweeps] (device, fp32).  Host code uses it to choose ckpt_mask.  */
 int pde_adi_kappa_max(const PdeAdiDesc* d,
@@ -568,6 +597,20 @@ int pde_adi_f64_backward(const PdeAdiDescF64* d, const double* gy, const double*
                          double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
                          const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
 
+/* pde_adi_forward_states / pde_adi_backward_states in float64: states, gstates (slots, B, C, N, N) doubles. */
+int pde_adi_f64_forward_states(const PdeAdiDescF64* d, const double* u, double* y, double* states,
+                               const uint64_t emit_mask[2],
+                               const double* alpha_base, const double* beta_base,
+                               const double* alpha_slope, const double* beta_slope,
+                               double* kappa_max, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_f64_backward_states(const PdeAdiDescF64* d, const double* gy, const double* gstates,
+                                const uint64_t emit_mask[2], const double* y, const double* u,
+                                const uint64_t ckpt_mask[2], double* gu,
+                                const double* alpha_base, const double* beta_base,
+                                const double* alpha_slope, const double* beta_slope,
+                                double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
+                                const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
 /* pde_channel_mix_* in float64, 1 <= C <= 128.  _steps: gM spread over calls sharing `workspace` (accumulate = 0 starts
  * the sums, 1 adds; finalize = 1 writes gM). */
 int pde_channel_mix_f64_forward(int32_t B, int32_t C, int32_t HW, const double* u, const double* M, double* out,
@@ -659,6 +702,21 @@ int pde_adi_rect_backward(const PdeAdiRectDesc* d, const void* gy, const void* y
                           float* g_alpha_slope, float* g_beta_slope,
                           const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
 
+/* pde_adi_forward_states / pde_adi_backward_states on a rectangle: states, gstates (slots, B, C, H, W) of io_dtype; the
+ * same rules, the same workspaces as pde_adi_rect_forward / pde_adi_rect_backward. */
+int pde_adi_rect_forward_states(const PdeAdiRectDesc* d, const void* u, void* y, void* states, const uint64_t emit_mask[2],
+                                const float* alpha_base, const float* beta_base,
+                                const float* alpha_slope, const float* beta_slope,
+                                float* kappa_max, float* kappa_max_host, void* kappa_event,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_rect_backward_states(const PdeAdiRectDesc* d, const void* gy, const void* gstates, const uint64_t emit_mask[2],
+                                 const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
+                                 const float* alpha_base, const float* beta_base,
+                                 const float* alpha_slope, const float* beta_slope,
+                                 float* g_alpha_base, float* g_beta_base,
+                                 float* g_alpha_slope, float* g_beta_slope,
+                                 const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The same in float64 (pde_adi_f64_* on a rectangle): every tensor and every scalar of the schedule a double. */
 typedef struct PdeAdiRectDescF64 {
     int32_t B, C, H, W;
@@ -687,6 +745,19 @@ int pde_adi_rect_f64_backward(const PdeAdiRectDescF64* d, const double* gy, cons
                               const double* alpha_slope, const double* beta_slope,
                               double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
                               const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
+int pde_adi_rect_f64_forward_states(const PdeAdiRectDescF64* d, const double* u, double* y, double* states,
+                                    const uint64_t emit_mask[2],
+                                    const double* alpha_base, const double* beta_base,
+                                    const double* alpha_slope, const double* beta_slope,
+                                    double* kappa_max, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_rect_f64_backward_states(const PdeAdiRectDescF64* d, const double* gy, const double* gstates,
+                                     const uint64_t emit_mask[2], const double* y, const double* u,
+                                     const uint64_t ckpt_mask[2], double* gu,
+                                     const double* alpha_base, const double* beta_base,
+                                     const double* alpha_slope, const double* beta_slope,
+                                     double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
+                                     const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- utilities ------------------------------------------------------------------------- */
 
