@@ -1,6 +1,8 @@
 // SVHN skip connection (SVHN.py:73-74): out = s*u0 + (1-s)*u,  s = sigmoid(skip_weight), in one pass
 // over the tensors (torch needs four elementwise kernels forward and six backward for it).
 //   backward:  g_u0 = s*g,  g_u = (1-s)*g,  g_skip_weight = s*(1-s) * sum g*(u0 - u)
+// 1 - s is taken as sigmoid(-skip_weight): the fp32 difference 1.0f - s keeps the absolute error of s (6e-8), which at
+// skip_weight = 6 (1 - s = 2.5e-3) is a relative error of 2e-5 in every element of g_u; the direct form holds 1e-7 at any weight.
 // The sum is taken per workgroup and added up in a fixed order by a second tiny kernel (no float atomics).  It is a sum of
 // differences of nearly equal numbers that cancels heavily (u is u0 after a few small diffusion steps), so every stage of
 // it — per thread, per wave, per workgroup, over the workgroups — is carried in DOUBLE precision: what is left of the
@@ -70,7 +72,7 @@ __device__ __forceinline__ float sigmoidf(float w) { return 1.0f / (1.0f + expf(
 template <typename IO>
 __global__ __launch_bounds__(256) void blend_fwd_kernel(const IO* __restrict__ u0, const IO* __restrict__ u,
                                                         const float* __restrict__ skip_weight, IO* __restrict__ out, size_t n) {
-    const float s = sigmoidf(*skip_weight), t = 1.0f - s;
+    const float s = sigmoidf(*skip_weight), t = sigmoidf(-*skip_weight);      // 1 - s, without its cancellation
     const size_t stride = (size_t)gridDim.x * 256 * 8;
     for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8; i < n; i += stride) {
         if (i + 8 <= n) {
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(256) void blend_bwd_kernel(const IO* __restrict__ g
                                                         const float* __restrict__ skip_weight, IO* __restrict__ g_u0,
                                                         IO* __restrict__ g_u, double* __restrict__ part, size_t n) {
     __shared__ double sh[4];
-    const float s = sigmoidf(*skip_weight), t = 1.0f - s;
+    const float s = sigmoidf(*skip_weight), t = sigmoidf(-*skip_weight);      // 1 - s, without its cancellation
     const size_t stride = (size_t)gridDim.x * 256 * 8;
     double acc = 0.0;
     for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8; i < n; i += stride) {

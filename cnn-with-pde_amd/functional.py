@@ -1287,11 +1287,11 @@ class _BnPoolFn(torch.autograd.Function):
 
 def bn_pool_supported(x, bn) -> bool:
     """Whether ``bn_pool`` takes (x, bn): fp32 CUDA tensor (B,C,N,N), N a multiple of 4 up to 64, a BatchNorm2d with a
-    fixed momentum (or no running statistics)."""
+    fixed momentum (or no running statistics).  A module without running statistics is taken in eval mode too: torch
+    normalises with the batch statistics there, and so does ``bn_pool``."""
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[2] == x.shape[3] and x.shape[2] % 4 == 0
             and 4 <= x.shape[2] <= 64 and x.shape[0] > 0 and not torch.is_autocast_enabled()
-            and (bn.momentum is not None or not bn.track_running_stats)
-            and (bn.training or bn.running_mean is not None))
+            and (bn.momentum is not None or not bn.track_running_stats))
 
 
 def bn_pool(x, bn):
