@@ -16,6 +16,8 @@ PDE_MAX_N_GENERIC = 128
 PDE_IO_F32, PDE_IO_BF16, PDE_IO_F64, PDE_IO_F16 = 0, 1, 2, 3
 PDE_AXIS_X, PDE_AXIS_Y = 0, 1
 PDE_MIX_PATH_SCALAR, PDE_MIX_PATH_MFMA_F32, PDE_MIX_PATH_MFMA_16, PDE_MIX_PATH_SPLIT3, PDE_MIX_PATH_FUSED = 0, 1, 2, 3, 4
+PDE_RH_PATH_STRIP32, PDE_RH_PATH_STRIP16, PDE_RH_PATH_ROW_BLOCKS = 0, 1, 2
+PDE_RH_DK_SPLIT3, PDE_RH_DK_MFMA_F32 = 0, 1
 PDE_JACOBI_MAX_HW = 1024
 PDE_JACOBI_TILED_K = 10
 
@@ -159,6 +161,8 @@ SIGNATURES = {
                                         _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "pde_sym_layer_backward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _f32, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                          _fp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "pde_sym_layer_path": (C.c_int, [_i32, _i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "pde_sym_layer_dk_path": (C.c_int, [_i32, _i32]),
     "pde_sym_layer_f16_supported": (C.c_int, [_i32, _i32]),
     "pde_sym_layer_f16_workspace_bytes": (_sz, [_i32, _i32]),
     "pde_sym_k_to_f16": (C.c_int, [_i32, _fp, _vp, _vp]),

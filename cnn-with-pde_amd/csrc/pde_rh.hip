@@ -913,18 +913,39 @@ bool rh_dims_ok(int B, int D) { return B >= 1 && D >= 64 && (D % 64) == 0; }
 // slices of whole 32-wide slabs and at least two of them, three workgroups per CU at D = 3072;
 // 0 = this batch / width keeps the 16-column kernels
 int rh_waves32(int B) { return B <= 64 ? 2 : 4; }
+// (the PDE_RH_* switches are read on every call, as the PDE_MIX_* ones are: a test selects a path in its own process)
 int rh_split32(int B, int D) {
-    static const bool off = getenv("PDE_RH_NO_STRIP32") != nullptr;
-    if (off || B > kRhRows32) return 0;
+    if (getenv("PDE_RH_NO_STRIP32") != nullptr || B > kRhRows32) return 0;
     const int wv = rh_waves32(B);
     int S = 8;                                           // (two waves: 16 slices measured slower, 171 us against 158 per layer)
-    static const int forced = getenv("PDE_RH_SPLIT") ? atoi(getenv("PDE_RH_SPLIT")) : 0;     // diagnostics: the starting split
+    const char* forced_env = getenv("PDE_RH_SPLIT");     // diagnostics: the starting split
+    const int forced = forced_env ? atoi(forced_env) : 0;
     if (forced >= 2 && forced <= 16 && (forced & (forced - 1)) == 0) S = forced;
     while (S > 1 && (D % (S * 2 * kS32Bk) != 0 || (D / kS32Cols) * S > (wv == 2 ? 2048 : 1024))) S >>= 1;
     return S >= 2 ? S : 0;
 }
-size_t rh_split32_bytes(int B, int D, int S) {
-    return S < 2 ? 0 : (size_t)(D / kS32Cols) * S * tile32_floats(rh_waves32(B)) * sizeof(float);
+
+// The one place where a call's kernels are chosen: pde_sym_layer_path / _dk_path report it, pde_sym_layer_forward,
+// _backward and _workspace_bytes dispatch on it.
+//   family      PDE_RH_PATH_* (include/pdecnn.h), or PDE_E_BADARG for what rh_dims_ok refuses
+//   split       slices of a strip's contraction (STRIP32: 2..16), 0 otherwise
+//   waves       per strip workgroup: 2 or 4 (STRIP32), kRhWaves (the 16-column kernels)
+//   row_blocks  workgroups along the batch: 1 up to 128 rows
+//   dk          PDE_RH_DK_*: the kernel of the gradient of K
+struct RhPlan { int family, split, waves, row_blocks, dk; };
+RhPlan rh_plan(int B, int D, bool has_workspace) {
+    if (!rh_dims_ok(B, D)) return {PDE_E_BADARG, 0, 0, 0, 0};
+    // three-piece bf16 products on the same 64 x 192 tiles (57 us against 66 at B = 128, D = 3072; 128 x 192 and 128 x 128
+    // tiles: 66 and 63 us); PDE_RH_NO_SPLIT=1 selects the fp32-MFMA kernel
+    const int dk = getenv("PDE_RH_NO_SPLIT") == nullptr ? PDE_RH_DK_SPLIT3 : PDE_RH_DK_MFMA_F32;
+    const int nblk = (B + kRhRows - 1) / kRhRows;
+    if (nblk > 1) return {PDE_RH_PATH_ROW_BLOCKS, 0, kRhWaves, nblk, dk};
+    const int S = has_workspace ? rh_split32(B, D) : 0;   // no workspace: the 16-column kernels (one workgroup per strip)
+    if (S >= 2) return {PDE_RH_PATH_STRIP32, S, rh_waves32(B), 1, dk};
+    return {PDE_RH_PATH_STRIP16, 0, kRhWaves, 1, dk};
+}
+size_t rh_plan_bytes(const RhPlan& p, int D) {
+    return p.family != PDE_RH_PATH_STRIP32 ? 0 : (size_t)(D / kS32Cols) * p.split * tile32_floats(p.waves) * sizeof(float);
 }
 constexpr size_t strip32_lds(int wv) {
     return (size_t)(2 * wv * 32 * kS32Lda + 2 * (kS32Cols * kS32Lda > kS32Bk * kS32LdN ? kS32Cols * kS32Lda : kS32Bk * kS32LdN))
@@ -941,8 +962,8 @@ int launch_part32_wv(const float* X, const float* W, int B, int D, int S, void* 
     return check_launch();
 }
 template <bool NT>
-int launch_part32(const float* X, const float* W, int B, int D, int S, void* ws, hipStream_t st) {
-    return rh_waves32(B) == 2 ? launch_part32_wv<NT, 2>(X, W, B, D, S, ws, st) : launch_part32_wv<NT, 4>(X, W, B, D, S, ws, st);
+int launch_part32(const float* X, const float* W, int B, int D, const RhPlan& p, void* ws, hipStream_t st) {
+    return p.waves == 2 ? launch_part32_wv<NT, 2>(X, W, B, D, p.split, ws, st) : launch_part32_wv<NT, 4>(X, W, B, D, p.split, ws, st);
 }
 
 // ---- the layer under CUDA fp16 / bf16 autocast: 16-bit operands on v_mfma_f32_32x32x16_{f16,bf16}, fp32 accumulators --------
@@ -1400,93 +1421,104 @@ extern "C" {
 int pde_sym_layer_supported(int32_t B, int32_t D) { return rh_dims_ok(B, D) ? 1 : 0; }
 
 size_t pde_sym_layer_workspace_bytes(int32_t B, int32_t D) {
-    if (!rh_dims_ok(B, D)) return 0;
-    return rh_split32_bytes(B, D, rh_split32(B, D));
+    const RhPlan plan = rh_plan(B, D, true);
+    return plan.family < 0 ? 0 : rh_plan_bytes(plan, D);
+}
+
+int pde_sym_layer_path(int32_t B, int32_t D, int32_t has_workspace, int32_t* split, int32_t* waves, int32_t* row_blocks) {
+    const RhPlan plan = rh_plan(B, D, has_workspace != 0);
+    if (plan.family < 0) return plan.family;
+    if (split) *split = plan.split;
+    if (waves) *waves = plan.waves;
+    if (row_blocks) *row_blocks = plan.row_blocks;
+    return plan.family;
+}
+
+int pde_sym_layer_dk_path(int32_t B, int32_t D) {
+    const RhPlan plan = rh_plan(B, D, false);
+    return plan.family < 0 ? plan.family : plan.dk;
 }
 
 int pde_sym_layer_forward(int32_t B, int32_t D, int32_t act, int32_t training, const float* X, const float* K,
                           const float* bn_weight, const float* bn_bias, float* running_mean, float* running_var,
                           float momentum, float eps, const float* base, float scale, float* P, float* H, float* mean,
                           float* invstd, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!rh_dims_ok(B, D)) return PDE_E_BADARG;
+    const RhPlan plan = rh_plan(B, D, workspace != nullptr);
+    if (plan.family < 0) return PDE_E_BADARG;
     if (!X || !K || !bn_weight || !bn_bias || !P || !H || !mean || !invstd || !out) return PDE_E_BADARG;
     if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
     if (!training && (!running_mean || !running_var)) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     RhFwdArgs f{X, K, bn_weight, bn_bias, running_mean, running_var, P, H, mean, invstd, B, D, act, training ? 1 : 0, momentum, eps};
-    const int nblk = (B + kRhRows - 1) / kRhRows;
     int rc;
-    const int S = workspace ? rh_split32(B, D) : 0;       // no workspace: the 16-column kernels (one workgroup per strip)
-    if (S >= 2) {
-        if (workspace_bytes < rh_split32_bytes(B, D, S) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return PDE_E_WORKSPACE;
+    if (plan.family == PDE_RH_PATH_STRIP32) {
+        if (workspace_bytes < rh_plan_bytes(plan, D) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return PDE_E_WORKSPACE;
         const float* part = static_cast<const float*>(workspace);
-        rc = launch_part32<true>(X, K, B, D, S, workspace, st);
+        const int S = plan.split, thr = 64 * plan.waves;
+        rc = launch_part32<true>(X, K, B, D, plan, workspace, st);
         if (rc != PDE_OK) return rc;
-        hipLaunchKernelGGL(rh_fwd32_epi_kernel, dim3(D / kS32Cols, 4), dim3(64 * rh_waves32(B)), 0, st, f, part, S);
-        rc = launch_part32<false>(H, K, B, D, S, workspace, st);
+        hipLaunchKernelGGL(rh_fwd32_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, f, part, S);
+        rc = launch_part32<false>(H, K, B, D, plan, workspace, st);
         if (rc != PDE_OK) return rc;
         RhAxpyArgs x{H, K, base, out, B, D, scale};
-        hipLaunchKernelGGL(rh_axpy32_epi_kernel, dim3(D / kS32Cols, 4), dim3(64 * rh_waves32(B)), 0, st, x, part, S);
+        hipLaunchKernelGGL(rh_axpy32_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, x, part, S);
         return check_launch();
     }
-    if (nblk == 1) {                                      // the whole batch in one strip workgroup: statistics as epilogue
+    if (plan.family == PDE_RH_PATH_STRIP16) {             // the whole batch in one strip workgroup: statistics as epilogue
         rc = launch_strip(rh_fwd_strip_kernel<1>, f, D, 1, st);
     } else {                                              // product by row blocks, then the statistics over all of them
         RhAxpyArgs p{X, K, nullptr, P, B, D, 1.0f};
-        rc = launch_strip(rh_nt_strip_kernel<1>, p, D, nblk, st);
+        rc = launch_strip(rh_nt_strip_kernel<1>, p, D, plan.row_blocks, st);
         if (rc != PDE_OK) return rc;
         hipLaunchKernelGGL(rh_bn_fwd_kernel, dim3(D / kBnCols), dim3(256), 0, st, f);
         rc = check_launch();
     }
     if (rc != PDE_OK) return rc;
     RhAxpyArgs x{H, K, base, out, B, D, scale};
-    return launch_strip(rh_axpy_strip_kernel<1>, x, D, nblk, st);
+    return launch_strip(rh_axpy_strip_kernel<1>, x, D, plan.row_blocks, st);
 }
 
 int pde_sym_layer_backward(int32_t B, int32_t D, int32_t act, int32_t training, const float* g_out, float scale,
                            const float* X, const float* K, const float* bn_weight, const float* P, const float* H,
                            const float* mean, const float* invstd, float* dP, float* gX, float* gK,
                            float* g_bn_weight, float* g_bn_bias, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!rh_dims_ok(B, D)) return PDE_E_BADARG;
+    const RhPlan plan = rh_plan(B, D, workspace != nullptr);
+    if (plan.family < 0) return PDE_E_BADARG;
     if (!g_out || !X || !K || !bn_weight || !P || !H || !mean || !invstd || !dP || !gX || !gK || !g_bn_weight || !g_bn_bias)
         return PDE_E_BADARG;
     if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     RhBwdArgs b{g_out, K, bn_weight, P, H, mean, invstd, dP, g_bn_weight, g_bn_bias, B, D, act, training ? 1 : 0, scale};
-    const int nblk = (B + kRhRows - 1) / kRhRows;
     int rc;
-    const int S = workspace ? rh_split32(B, D) : 0;
-    if (S >= 2) {
-        if (workspace_bytes < rh_split32_bytes(B, D, S) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return PDE_E_WORKSPACE;
+    if (plan.family == PDE_RH_PATH_STRIP32) {
+        if (workspace_bytes < rh_plan_bytes(plan, D) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return PDE_E_WORKSPACE;
         const float* part = static_cast<const float*>(workspace);
-        rc = launch_part32<true>(g_out, K, B, D, S, workspace, st);
+        const int S = plan.split, thr = 64 * plan.waves;
+        rc = launch_part32<true>(g_out, K, B, D, plan, workspace, st);
         if (rc != PDE_OK) return rc;
-        hipLaunchKernelGGL(rh_bwd32_epi_kernel, dim3(D / kS32Cols, 4), dim3(64 * rh_waves32(B)), 0, st, b, part, S);
-        rc = launch_part32<false>(dP, K, B, D, S, workspace, st);
+        hipLaunchKernelGGL(rh_bwd32_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, b, part, S);
+        rc = launch_part32<false>(dP, K, B, D, plan, workspace, st);
         if (rc != PDE_OK) return rc;
         RhAxpyArgs x32{dP, K, nullptr, gX, B, D, 1.0f};
-        hipLaunchKernelGGL(rh_axpy32_epi_kernel, dim3(D / kS32Cols, 4), dim3(64 * rh_waves32(B)), 0, st, x32, part, S);
+        hipLaunchKernelGGL(rh_axpy32_epi_kernel, dim3(D / kS32Cols, 4), dim3(thr), 0, st, x32, part, S);
         rc = check_launch();
-    } else if (nblk == 1) {
+    } else if (plan.family == PDE_RH_PATH_STRIP16) {
         rc = launch_strip(rh_bwd_strip_kernel<1>, b, D, 1, st);
     } else {
         RhAxpyArgs p{g_out, K, nullptr, dP, B, D, 1.0f};
-        rc = launch_strip(rh_nt_strip_kernel<1>, p, D, nblk, st);
+        rc = launch_strip(rh_nt_strip_kernel<1>, p, D, plan.row_blocks, st);
         if (rc != PDE_OK) return rc;
         hipLaunchKernelGGL(rh_bn_bwd_kernel, dim3(D / kBnCols), dim3(256), 0, st, b);
         rc = check_launch();
     }
     if (rc != PDE_OK) return rc;
-    if (S < 2) {
+    if (plan.family != PDE_RH_PATH_STRIP32) {
         RhAxpyArgs x{dP, K, nullptr, gX, B, D, 1.0f};
-        rc = launch_strip(rh_axpy_strip_kernel<1>, x, D, nblk, st);
+        rc = launch_strip(rh_axpy_strip_kernel<1>, x, D, plan.row_blocks, st);
         if (rc != PDE_OK) return rc;
     }
     RhOuterArgs o{dP, X, H, g_out, gK, B, D, scale};
-    // three-piece bf16 products on the same 64 x 192 tiles (57 us against 66 at B = 128, D = 3072; 128 x 192 and 128 x 128
-    // tiles: 66 and 63 us); PDE_RH_NO_SPLIT=1 selects the fp32-MFMA kernel
-    static const bool split = getenv("PDE_RH_NO_SPLIT") == nullptr;
-    if (split) return launch_outer_split<kOutTi, kOutTj>(o, D, st);
+    if (plan.dk == PDE_RH_DK_SPLIT3) return launch_outer_split<kOutTi, kOutTj>(o, D, st);
     hipLaunchKernelGGL(rh_outer_kernel, dim3((D + kOutTj - 1) / kOutTj, (D + kOutTi - 1) / kOutTi), dim3(kRhThreads), 0, st, o);
     return check_launch();
 }

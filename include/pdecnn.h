@@ -331,7 +331,8 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
 /* Which kernel family pde_channel_mix_forward (backward = 0) or pde_channel_mix_backward[_steps] (backward = 1) runs
  * for these arguments; the entry points dispatch on the value this function returns.  PDE_E_BADARG for dimensions or an
  * io_dtype they refuse.  The PDE_MIX_NO_BF16_MFMA, PDE_MIX_NO_SPLIT and PDE_MIX_UNFUSED environment switches are read
- * on every call, here as there.
+ * on every call, here as there; so are PDE_RH_NO_STRIP32, PDE_RH_SPLIT and PDE_RH_NO_SPLIT of the symmetric layer
+ * (pde_sym_layer_path below).
  *   code                     forward                             backward
  *   PDE_MIX_PATH_SCALAR      mix_apply_kernel                    transposed mix_apply_kernel + mix_gm_kernel
  *   PDE_MIX_PATH_MFMA_F32    mix_apply_mfma_kernel               unfused: transposed mix_apply_mfma_kernel + mix_gm_mfma_kernel
@@ -500,6 +501,29 @@ int pde_sym_layer_backward(int32_t B, int32_t D, int32_t act, int32_t training,
                            const float* P, const float* H, const float* mean, const float* invstd,
                            float* dP, float* gX, float* gK, float* g_bn_weight, float* g_bn_bias,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* Which kernels pde_sym_layer_forward / _backward run for these dimensions, with (has_workspace != 0) or without a
+ * workspace; the entry points and pde_sym_layer_workspace_bytes dispatch on the same function.  Returns the family, or
+ * PDE_E_BADARG for what pde_sym_layer_supported refuses (the out-pointers are then left alone); each out-pointer may be
+ * NULL.  The PDE_RH_NO_STRIP32, PDE_RH_SPLIT and PDE_RH_NO_SPLIT environment switches are read on every call, here as
+ * there (as the PDE_MIX_* ones are), so a process can select a path between two calls.
+ *   family                  products and epilogues                                        *split  *waves  *row_blocks
+ *   PDE_RH_PATH_STRIP32     rh_part32_kernel + rh_fwd32_epi / rh_bwd32_epi / rh_axpy32_epi  S       2 | 4   1
+ *                           (B <= 128, a workspace, S >= 2; two waves up to 64 rows)
+ *   PDE_RH_PATH_STRIP16     rh_fwd_strip / rh_bwd_strip / rh_axpy_strip_kernel              0       8       1
+ *                           (B <= 128 otherwise: no workspace, S < 2, PDE_RH_NO_STRIP32)
+ *   PDE_RH_PATH_ROW_BLOCKS  rh_nt_strip + rh_bn_fwd / rh_bn_bwd + rh_axpy_strip_kernel      0       8       ceil(B / 128)
+ * S: the slices of a strip's contraction — the largest power of two <= 8 (or <= PDE_RH_SPLIT, a power of two in 2..16)
+ * with D % (64 S) == 0 and (D / 32) S <= 2048 workgroups with two waves, 1024 with four.  The workspace holds
+ * (D / 32) * S * waves * 1024 floats. */
+#define PDE_RH_PATH_STRIP32    0
+#define PDE_RH_PATH_STRIP16    1
+#define PDE_RH_PATH_ROW_BLOCKS 2
+int pde_sym_layer_path(int32_t B, int32_t D, int32_t has_workspace, int32_t* split, int32_t* waves, int32_t* row_blocks);
+/* The kernel of the gradient of K in pde_sym_layer_backward: PDE_RH_DK_SPLIT3 (rh_outer_split_kernel, every fp32 operand
+ * as three bf16 pieces) or, under PDE_RH_NO_SPLIT, PDE_RH_DK_MFMA_F32 (rh_outer_kernel); PDE_E_BADARG as above. */
+#define PDE_RH_DK_SPLIT3   0
+#define PDE_RH_DK_MFMA_F32 1
+int pde_sym_layer_dk_path(int32_t B, int32_t D);
 
 /* ---- the same layer under CUDA fp16 autocast, on the fp16 matrix cores ---------------------- */
 

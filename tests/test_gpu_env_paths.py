@@ -1,5 +1,7 @@
-"""GPU parity of the paths an environment switch selects (each switch is read once per process, so the cases run in
-a child interpreter):
+"""GPU parity of the paths an environment switch selects, with the switch set for a whole process: each case runs in a
+child interpreter.  PDE_KMAX_MAPPED and PDE_WIDE are read once per process and can only be set this way; the PDE_MIX_* and
+PDE_RH_* switches are read on every call (tests/test_gpu_mix_paths.py and tests/test_gpu_rh_paths.py also set them
+in-process, case by case), and here they hold from the first call to the last:
 
     PDE_KMAX_MAPPED=0   the per-sweep coefficient maxima reach the host through a device buffer and an asynchronous
                         copy instead of the factor epilogue writing straight into the caller's pinned buffer — the
@@ -9,7 +11,8 @@ a child interpreter):
     PDE_MIX_NO_SPLIT=1  the channel operator's backward on fp32 tensors at C = 64 on the fp32 MFMA (mix_bwd_fused_kernel)
                         instead of the three-piece bf16 products that are the default since round 3
     PDE_RH_NO_SPLIT=1   the symmetric layer's gradient of K on the fp32 MFMA (rh_outer_kernel) instead of the three-piece
-                        bf16 kernel
+                        bf16 kernel (tests/test_gpu_rh_paths.py also sets it in-process, case by case; here it holds for the
+                        whole process, every case of that file included)
 
 Each child runs a slice of the ordinary parity tests (golden vectors whose backward plans checkpoints from those
 maxima; the BASELINE configurations as layers against the oracle)."""
@@ -49,4 +52,4 @@ def test_per_step_launches_with_the_one_launch_forward_off():
 def test_fp32_mfma_kernels_behind_the_three_piece_products():
     _child({"PDE_MIX_NO_SPLIT": "1", "PDE_RH_NO_SPLIT": "1"},
            ["tests/test_gpu_configs.py", "-k", "cfg2", "tests/test_gpu_parity.py::test_channel_mix_vs_fp64",
-            "tests/test_gpu_rh.py", "-k", "cfg2 or channel_mix_vs_fp64 or rh"])
+            "tests/test_gpu_rh.py", "tests/test_gpu_rh_paths.py", "-k", "cfg2 or channel_mix_vs_fp64 or rh"])
