@@ -121,6 +121,11 @@ SIGNATURES = {
     "pde_adi_small_backward_workspace_bytes": (_sz, [_D, _i32, _i32]),
     "pde_adi_small_backward": (C.c_int, [_D, _i32, _i32, _vp, _vp, _vp, _fp, _fp, C.POINTER(C.c_uint64), _vp,
                                          _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_small_forward_states": (C.c_int, [_D, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _fp, _fp, _fp, _fp,
+                                               _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_small_backward_states": (C.c_int, [_D, _i32, _i32, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _fp,
+                                                C.POINTER(C.c_uint64), _vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                _vp, _vp, _sz, _vp]),
     "pde_adi_multi_forward": (C.c_int, [_i32, C.POINTER(PdeSmallLayer), _vp, _vp, _vp, _vp]),
     "pde_adi_multi_backward": (C.c_int, [_i32, C.POINTER(PdeSmallLayer), _vp, _vp, _vp, _vp]),
     "pde_gate_combine_forward": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _fp,

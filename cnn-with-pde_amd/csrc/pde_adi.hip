@@ -1323,8 +1323,18 @@ int pde_adi_mixed_backward(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t
 // (pde_adi_small.h; the reference's own models: cifar10.py:253-258 C = 3 mixing before every step,
 // SVHN.py:238 C = 3 coupling after every step + skip blend)
 static int small_grid(const PdeAdiDesc* d) { return d->B < 1024 ? d->B : 1024; }
-static int dispatch_small(bool fwd, const PdeAdiDesc* d, int split, const SmallArgs& sa, size_t lds, hipStream_t st) {
+static int dispatch_small(bool fwd, const PdeAdiDesc* d, int split, const SmallArgs& sa, size_t lds, hipStream_t st,
+                          bool emit = false) {
     const int grid = small_grid(d) * (sa.par ? sa.L : 1);
+    if (emit) {                                            // the emitting variants (SmallArgs::traj, SmallArgs::em)
+        switch (d->N) {
+#define PDE_SMALL_CASE(NN) case NN: return fwd ? adi_launch_small_fwd_emit_##NN(d->io_dtype, split, &sa, grid, lds, st) \
+                                               : adi_launch_small_bwd_emit_##NN(d->io_dtype, split, &sa, grid, lds, st);
+            PDE_SMALL_N_LIST
+#undef PDE_SMALL_CASE
+        }
+        return PDE_E_UNSUPPORTED_N;
+    }
     switch (d->N) {
 #define PDE_SMALL_CASE(NN) case NN: return fwd ? adi_launch_small_fwd_##NN(d->io_dtype, split, &sa, grid, lds, st) \
                                                : adi_launch_small_bwd_##NN(d->io_dtype, split, &sa, grid, lds, st);
@@ -1392,8 +1402,21 @@ static int multi_check(int32_t L, const PdeSmallLayer* layers) {
     return PDE_OK;
 }
 
-int pde_adi_multi_forward(int32_t num_layers, const PdeSmallLayer* layers, const void* u, void* out, void* kappa_event,
-                          void* stream) {
+// the emission mask of a one-layer call (pde_adi_small_*_states), checked before anything is launched: bits 0 .. K-2
+// only (the state after the last step is y), and a tensor to go with a non-empty mask.  `any`: whether a bit is set
+static int small_emit_check(const PdeAdiDesc* d, int32_t sweeps_per_step, const void* traj, const uint64_t* emit_mask,
+                            bool& any) {
+    any = emit_mask && (emit_mask[0] | emit_mask[1]);
+    if (!any) return PDE_OK;
+    if (!pde_adi_small_supported(d, sweeps_per_step)) return PDE_E_BADARG;
+    const int K = d->num_sweeps / sweeps_per_step;         // <= PDE_MAX_SWEEPS / 2 < 64
+    if (!traj || emit_mask[1] || (emit_mask[0] >> (K - 1))) return PDE_E_BADARG;
+    return PDE_OK;
+}
+
+// pde_adi_multi_forward; traj / em (one layer only, em not null = a non-empty checked mask): the emitting kernel
+static int small_forward_impl(int32_t num_layers, const PdeSmallLayer* layers, const void* u, void* out, void* kappa_event,
+                              void* stream, void* traj, const uint64_t* em) {
     int rc = multi_check(num_layers, layers);
     if (rc != PDE_OK) return rc;
     if (!u || !out) return PDE_E_BADARG;
@@ -1402,6 +1425,7 @@ int pde_adi_multi_forward(int32_t num_layers, const PdeSmallLayer* layers, const
     SmallArgs sa{};
     sa.u = u; sa.out = out; sa.B = d0->B; sa.C = d0->C; sa.L = num_layers;
     sa.par = multi_parallel(num_layers, d0);
+    if (em) { sa.traj = traj; sa.em[0] = em[0]; sa.em[1] = em[1]; }
     for (int i = 0; i < num_layers; ++i) {
         const PdeSmallLayer& y = layers[i];
         bool wrote = false;
@@ -1416,9 +1440,14 @@ int pde_adi_multi_forward(int32_t num_layers, const PdeSmallLayer* layers, const
         sa.layer[i].slab = static_cast<char*>(y.steps_workspace) + steps_wide_offset(y.desc, y.sweeps_per_step);
     }
     if (kappa_event && hipEventRecord(static_cast<hipEvent_t>(kappa_event), st) != hipSuccess) return PDE_E_LAUNCH;
-    rc = dispatch_small(true, d0, small_split(d0, layers[0].sweeps_per_step), sa, small_lds_fwd(d0->C), st);
+    rc = dispatch_small(true, d0, small_split(d0, layers[0].sweeps_per_step), sa, small_lds_fwd(d0->C), st, em != nullptr);
     if (rc != PDE_OK || !sa.par) return rc;
     return combine_slabs(d0, sa, out, st);
+}
+
+int pde_adi_multi_forward(int32_t num_layers, const PdeSmallLayer* layers, const void* u, void* out, void* kappa_event,
+                          void* stream) {
+    return small_forward_impl(num_layers, layers, u, out, kappa_event, stream, nullptr, nullptr);
 }
 
 size_t pde_adi_small_backward_workspace_bytes(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t num_checkpoints) {
@@ -1430,8 +1459,11 @@ size_t pde_adi_small_backward_workspace_bytes(const PdeAdiDesc* d, int32_t sweep
            align_up((size_t)K * num_checkpoints * d->B * d->C * d->N * d->N * sizeof(float), 256);
 }
 
-int pde_adi_multi_backward(int32_t num_layers, const PdeSmallLayer* layers, const void* gy, const void* u, void* gu,
-                           void* stream) {
+// pde_adi_multi_backward; gtraj / em as in small_forward_impl: the emitting kernel (and, so that the states parked
+// inside the steps are those of the forward, the emitting forward for the checkpoint pre-pass: it rounds the sweep
+// output of every step of 16-bit tensors as the emitting forward did, and with out == null it emits nothing)
+static int small_backward_impl(int32_t num_layers, const PdeSmallLayer* layers, const void* gy, const void* u, void* gu,
+                               void* stream, const void* gtraj, const uint64_t* em) {
     int rc = multi_check(num_layers, layers);
     if (rc != PDE_OK) return rc;
     if (!u || !gu) return PDE_E_BADARG;
@@ -1441,6 +1473,7 @@ int pde_adi_multi_backward(int32_t num_layers, const PdeSmallLayer* layers, cons
     SmallArgs sa{};
     sa.u = u; sa.gy = gy; sa.out = gu; sa.B = d0->B; sa.C = d0->C; sa.L = num_layers;
     sa.par = multi_parallel(num_layers, d0);
+    if (em) { sa.traj = const_cast<void*>(gtraj); sa.em[0] = em[0]; sa.em[1] = em[1]; }
     bool any_ck = false;
     for (int i = 0; i < num_layers; ++i) {
         const PdeSmallLayer& y = layers[i];
@@ -1469,7 +1502,7 @@ int pde_adi_multi_backward(int32_t num_layers, const PdeSmallLayer* layers, cons
     if (any_ck) {                                          // pre-pass: the forward again, parking the states inside the steps
         SmallArgs fa = sa;
         fa.out = nullptr; fa.gy = nullptr;
-        rc = dispatch_small(true, d0, split, fa, small_lds_fwd(d0->C), st);
+        rc = dispatch_small(true, d0, split, fa, small_lds_fwd(d0->C), st, em != nullptr);
         if (rc != PDE_OK) return rc;
     }
     for (int i = 0; i < num_layers; ++i) {
@@ -1477,7 +1510,7 @@ int pde_adi_multi_backward(int32_t num_layers, const PdeSmallLayer* layers, cons
         sa.layer[i].gys = layers[i].gys;
         sa.layer[i].roff = layers[i].g_plane_sums;
     }
-    rc = dispatch_small(false, d0, split, sa, small_lds_bwd(d0->C), st);
+    rc = dispatch_small(false, d0, split, sa, small_lds_bwd(d0->C), st, em != nullptr);
     if (rc == PDE_OK && sa.par) rc = combine_slabs(d0, sa, gu, st);
     if (rc != PDE_OK) return rc;
     for (int i = 0; i < num_layers; ++i) {
@@ -1491,6 +1524,11 @@ int pde_adi_multi_backward(int32_t num_layers, const PdeSmallLayer* layers, cons
         if (rc != PDE_OK) return rc;
     }
     return PDE_OK;
+}
+
+int pde_adi_multi_backward(int32_t num_layers, const PdeSmallLayer* layers, const void* gy, const void* u, void* gu,
+                           void* stream) {
+    return small_backward_impl(num_layers, layers, gy, u, gu, stream, nullptr, nullptr);
 }
 
 // one layer: thin wrappers
@@ -1521,6 +1559,43 @@ int pde_adi_small_backward(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t
     l.g_beta_slope = g_beta_slope; l.gM = gM; l.g_skip_weight = g_skip_weight; l.workspace = workspace;
     l.workspace_bytes = workspace_bytes;
     return pde_adi_multi_backward(1, &l, gy, u, gu, stream);
+}
+
+// the trajectory of one layer: the plain calls (no skip blend) with the emission mask checked first
+int pde_adi_small_forward_states(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode, const void* u, void* y,
+                                 void* states, void* traj, const uint64_t emit_mask[2], const float* M,
+                                 const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                                 const float* beta_slope, float* kappa_max, float* kappa_max_host, void* kappa_event,
+                                 void* steps_workspace, size_t workspace_bytes, void* stream) {
+    bool any;
+    const int rc = small_emit_check(d, sweeps_per_step, traj, emit_mask, any);
+    if (rc != PDE_OK) return rc;
+    PdeSmallLayer l{};
+    l.desc = d; l.sweeps_per_step = sweeps_per_step; l.mode = mode; l.M = M;
+    l.alpha_base = alpha_base; l.beta_base = beta_base; l.alpha_slope = alpha_slope; l.beta_slope = beta_slope;
+    l.weight = 1.0f; l.states = states; l.steps_workspace = steps_workspace; l.steps_workspace_bytes = workspace_bytes;
+    l.kappa_max = kappa_max; l.kappa_max_host = kappa_max_host;
+    return small_forward_impl(1, &l, u, y, kappa_event, stream, traj, any ? emit_mask : nullptr);
+}
+
+int pde_adi_small_backward_states(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode, const void* gy,
+                                  const void* gtraj, const uint64_t emit_mask[2], const void* u, const void* states,
+                                  const float* M, const uint64_t ckpt_mask[2], void* gu, const float* alpha_base,
+                                  const float* beta_base, const float* alpha_slope, const float* beta_slope,
+                                  float* g_alpha_base, float* g_beta_base, float* g_alpha_slope, float* g_beta_slope,
+                                  float* gM, const void* steps_workspace, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    bool any;
+    const int rc = small_emit_check(d, sweeps_per_step, gtraj, emit_mask, any);
+    if (rc != PDE_OK) return rc;
+    if (!gy) return PDE_E_BADARG;
+    PdeSmallLayer l{};
+    l.desc = d; l.sweeps_per_step = sweeps_per_step; l.mode = mode; l.M = M;
+    l.alpha_base = alpha_base; l.beta_base = beta_base; l.alpha_slope = alpha_slope; l.beta_slope = beta_slope;
+    l.weight = 1.0f; l.states = const_cast<void*>(states); l.steps_workspace = const_cast<void*>(steps_workspace);
+    l.ckpt_mask = ckpt_mask; l.g_alpha_base = g_alpha_base; l.g_beta_base = g_beta_base; l.g_alpha_slope = g_alpha_slope;
+    l.g_beta_slope = g_beta_slope; l.gM = gM; l.workspace = workspace; l.workspace_bytes = workspace_bytes;
+    return small_backward_impl(1, &l, gy, u, gu, stream, gtraj, any ? emit_mask : nullptr);
 }
 
 int pde_adi_kappa_max(const PdeAdiDesc* d, const float* alpha_base, const float* beta_base, const float* alpha_slope,

@@ -123,6 +123,19 @@ int PDE_CAT(adi_launch_small_bwd_, PDE_INST_N)(int io, int split, const void* ar
     return io == PDE_IO_F32 ? small_bwd_io<PDE_INST_N, float>(split, sa, grid, lds, st)
                             : small_bwd_io<PDE_INST_N, bf16_t>(split, sa, grid, lds, st);
 }
+// the emitting variants (pde_adi_small_*_states): SmallArgs::traj, SmallArgs::em
+int PDE_CAT(adi_launch_small_fwd_emit_, PDE_INST_N)(int io, int split, const void* args, int grid, size_t lds, hipStream_t st) {
+    const SmallArgs& sa = *static_cast<const SmallArgs*>(args);
+    if (io == PDE_IO_F16) return small_fwd_io<PDE_INST_N, half_t, true>(split, sa, grid, lds, st);
+    return io == PDE_IO_F32 ? small_fwd_io<PDE_INST_N, float, true>(split, sa, grid, lds, st)
+                            : small_fwd_io<PDE_INST_N, bf16_t, true>(split, sa, grid, lds, st);
+}
+int PDE_CAT(adi_launch_small_bwd_emit_, PDE_INST_N)(int io, int split, const void* args, int grid, size_t lds, hipStream_t st) {
+    const SmallArgs& sa = *static_cast<const SmallArgs*>(args);
+    if (io == PDE_IO_F16) return small_bwd_io<PDE_INST_N, half_t, true>(split, sa, grid, lds, st);
+    return io == PDE_IO_F32 ? small_bwd_io<PDE_INST_N, float, true>(split, sa, grid, lds, st)
+                            : small_bwd_io<PDE_INST_N, bf16_t, true>(split, sa, grid, lds, st);
+}
 #endif
 
 #ifdef PDE_INST_WIDE

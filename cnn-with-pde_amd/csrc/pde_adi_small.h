@@ -59,6 +59,11 @@ struct SmallArgs {
     int par;                // 1: the layers run side by side, workgroup x works on layer x % L of sample x / L, and writes
                             // its term of `out` / `gu` to the layer's slab; small_combine_kernel adds the slabs up
     SmallLayer layer[kSmallMaxL];
+    // emitting variants only (EMIT = true, L = 1, no par; nothing else reads these): bit k of em = the state after time
+    // step k — mode 1 the step's sweep output, mode 2 what its coupling gives — goes to (fwd) / its gradient comes from
+    // (bwd) traj[slot][B][C][N][N] of the tensor type, slots in the order of the set bits
+    void* traj;
+    unsigned long long em[2];
 };
 // The layer descriptors are read where they lie, in the kernel-argument segment, with scalar loads at a run-time
 // index (an argument array indexed at run time would be held whole in SGPRs and spilled).
@@ -106,7 +111,11 @@ template <> __device__ __forceinline__ float round_io<bf16_t>(float v) { return 
 template <> __device__ __forceinline__ float round_io<half_t>(float v) { return f16_to_f32(f32_to_f16_hw(v)); }
 
 // ---- forward ---------------------------------------------------------------------------------------------
-template <int N, typename IO, int SPLIT>
+// EMIT (pde_adi_small_forward_states): the state after every time step whose bit is set in a.em also goes to a.traj,
+// rounded to the tensor type once; with 16-bit tensors the time loop then ALWAYS goes on from the rounded sweep output
+// (kept states or not), so inference and training return the same trajectory and the backward reads what the forward
+// went on from.  The checkpoint pre-pass (out == null) emits nothing.
+template <int N, typename IO, int SPLIT, bool EMIT = false>
 __global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_fwd_kernel(SmallArgs a) {
     constexpr int M = Geo<N>::M;
     constexpr int SPS = SPLIT == kSplitStrang ? 3 : 2;
@@ -186,6 +195,7 @@ __global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_fwd_kernel(SmallArg
             small_load<N, 0, IO>(u, b, nC, c, lane, l, hf, T, u0);
 #pragma unroll
             for (int q = 0; q < M; ++q) v[q] = u0[q];
+            int eslot = 0;                                                // EMIT: the next free slot of a.traj
             for (int k = 0; k < K; ++k) {
                 if (mode == 1) mix(v);                                    // cifar10.py:91
                 sfor<0, SPS>([&](auto SI) __attribute__((always_inline)) {
@@ -214,8 +224,17 @@ __global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_fwd_kernel(SmallArg
 #pragma unroll
                         for (int q = 0; q < M; ++q) v[q] = round_io<IO>(v[q]);
                     }
+                } else if (EMIT && sizeof(IO) < 4) {                     // the same trajectory with and without kept states
+#pragma unroll
+                    for (int q = 0; q < M; ++q) v[q] = round_io<IO>(v[q]);
                 }
                 if (mode == 2) mix(v);                                    // SVHN.py:71
+                if constexpr (EMIT) {
+                    if (y != nullptr && ck_bit(a.em, k)) {                // what the reference's loop holds after iteration k
+                        small_store<N, 0, IO>(static_cast<IO*>(a.traj) + (size_t)eslot * tens, b, nC, c, lane, l, hf, T, v);
+                        ++eslot;
+                    }
+                }
             }
             if (y != nullptr) {
                 if (skp != nullptr) {                                     // SVHN.py:74  sigmoid(w) u0 + (1 - sigmoid(w)) u
@@ -296,7 +315,10 @@ __device__ __forceinline__ void small_adj_sweep(float (&r)[N / 2], float (&x)[N 
     for (int k = 0; k < M; ++k) { A[k] += G[k]; Tm[k] = fmaf(tau, G[k], Tm[k]); }
 }
 
-template <int N, typename IO, int SPLIT>
+// EMIT (pde_adi_small_backward_states): a.traj holds dL/d(state after time step k) for every bit k of a.em; it joins
+// the adjoint at the top of the reverse iteration of step k, where r is in true scale (mode 2: before the adjoint of
+// the coupling, mode 1: before the step's adjoint sweeps).  Nothing else differs from the plain kernel.
+template <int N, typename IO, int SPLIT, bool EMIT = false>
 __global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_bwd_kernel(SmallArgs a) {
     constexpr int M = Geo<N>::M;
     constexpr int SPS = SPLIT == kSplitStrang ? 3 : 2;
@@ -433,7 +455,17 @@ __global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_bwd_kernel(SmallArg
 #pragma unroll
                 for (int k = 0; k < M; ++k) wsum += live ? g0[k] * x[k] : 0.f;                   // d out / d w_i = y_i
             }
+            int eslot = EMIT ? ck_slot(a.em, K) : 0;                      // EMIT: one behind the newest slot of a.traj
             for (int k = K - 1; k >= 0; --k) {
+                if constexpr (EMIT) {
+                    if (ck_bit(a.em, k)) {                                // dL/d(state after step k); T is free here
+                        float gi[M];
+                        --eslot;
+                        small_load<N, 0, IO>(static_cast<const IO*>(a.traj) + (size_t)eslot * tens, b, nC, c, lane, l, hf, T, gi);
+#pragma unroll
+                        for (int q = 0; q < M; ++q) r[q] += gi[q];
+                    }
+                }
                 if (mode == 2) {                                          // SVHN: the coupling came after the sweeps
                     small_load<N, 0, IO>(st + (size_t)k * tens, b, nC, c, lane, l, hf, TX, x);
                     mix_adjoint(r, x, skp != nullptr && k == K - 1, gsk, b);
@@ -518,27 +550,27 @@ int small_combine_io(const CombineArgs& ca, hipStream_t st) {
     return check_launch();
 }
 
-template <int N, typename IO>
+template <int N, typename IO, bool EMIT = false>
 int small_fwd_io(int split, const SmallArgs& sa, int grid, size_t lds, hipStream_t st) {
     static unsigned long long cfg[2] = {0, 0};
     if (split == kSplitStrang) {
-        if (ensure_dynamic_lds((const void*)adi_small_fwd_kernel<N, IO, kSplitStrang>, (int)lds, cfg[0]) != PDE_OK) return PDE_E_LAUNCH;
-        hipLaunchKernelGGL((adi_small_fwd_kernel<N, IO, kSplitStrang>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
+        if (ensure_dynamic_lds((const void*)adi_small_fwd_kernel<N, IO, kSplitStrang, EMIT>, (int)lds, cfg[0]) != PDE_OK) return PDE_E_LAUNCH;
+        hipLaunchKernelGGL((adi_small_fwd_kernel<N, IO, kSplitStrang, EMIT>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
     } else {
-        if (ensure_dynamic_lds((const void*)adi_small_fwd_kernel<N, IO, kSplitLie>, (int)lds, cfg[1]) != PDE_OK) return PDE_E_LAUNCH;
-        hipLaunchKernelGGL((adi_small_fwd_kernel<N, IO, kSplitLie>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
+        if (ensure_dynamic_lds((const void*)adi_small_fwd_kernel<N, IO, kSplitLie, EMIT>, (int)lds, cfg[1]) != PDE_OK) return PDE_E_LAUNCH;
+        hipLaunchKernelGGL((adi_small_fwd_kernel<N, IO, kSplitLie, EMIT>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
     }
     return check_launch();
 }
-template <int N, typename IO>
+template <int N, typename IO, bool EMIT = false>
 int small_bwd_io(int split, const SmallArgs& sa, int grid, size_t lds, hipStream_t st) {
     static unsigned long long cfg[2] = {0, 0};
     if (split == kSplitStrang) {
-        if (ensure_dynamic_lds((const void*)adi_small_bwd_kernel<N, IO, kSplitStrang>, (int)lds, cfg[0]) != PDE_OK) return PDE_E_LAUNCH;
-        hipLaunchKernelGGL((adi_small_bwd_kernel<N, IO, kSplitStrang>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
+        if (ensure_dynamic_lds((const void*)adi_small_bwd_kernel<N, IO, kSplitStrang, EMIT>, (int)lds, cfg[0]) != PDE_OK) return PDE_E_LAUNCH;
+        hipLaunchKernelGGL((adi_small_bwd_kernel<N, IO, kSplitStrang, EMIT>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
     } else {
-        if (ensure_dynamic_lds((const void*)adi_small_bwd_kernel<N, IO, kSplitLie>, (int)lds, cfg[1]) != PDE_OK) return PDE_E_LAUNCH;
-        hipLaunchKernelGGL((adi_small_bwd_kernel<N, IO, kSplitLie>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
+        if (ensure_dynamic_lds((const void*)adi_small_bwd_kernel<N, IO, kSplitLie, EMIT>, (int)lds, cfg[1]) != PDE_OK) return PDE_E_LAUNCH;
+        hipLaunchKernelGGL((adi_small_bwd_kernel<N, IO, kSplitLie, EMIT>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
     }
     return check_launch();
 }

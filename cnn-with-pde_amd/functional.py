@@ -17,7 +17,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse",
+__all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small", "adi_diffuse_small_states", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse",
            "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
            "sym_layer_f16_supported", "sym_layer_bf16_supported", "sym_k16"]
 
@@ -1195,6 +1195,117 @@ def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coe
         u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
     return _AdiStatesFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, emit, bool(smooth3),
                               clamp_max, float(eps), checkpoints, kmax_sink, f64)
+
+
+class _AdiSmallStatesFn(torch.autograd.Function):
+    """``_AdiSmallFn`` without the skip blend that also returns the state after chosen time steps, out of the same launch
+    per pass (pde_adi_small_forward_states / pde_adi_small_backward_states).  The result is ONE tensor (K', B, C, N, N);
+    the library's ``y`` is its last slice."""
+
+    @staticmethod
+    def forward(ctx, u, ab, bb, asl, bsl, M, steps, emit, mode, smooth3, clamp_max, eps, ckpt, kmax_sink):
+        lib = L.load()
+        _require_cuda(u, ab, bb, asl, bsl, M)
+        B, Cc, N, _ = u.shape
+        if u.dtype not in _IO_TYPES:
+            u = u.float()
+        u = u.contiguous()
+        sps, K = len(steps[0]), len(steps)
+        sweeps = steps.flat
+        p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
+        Mf = M.detach().to(torch.float32).contiguous()
+        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
+        sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
+        need_grad = any(ctx.needs_input_grad[:6])
+        want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
+        kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
+        Ke = len(emit)
+        out = torch.empty((Ke,) + tuple(u.shape), dtype=u.dtype, device=u.device)
+        bits = sum(1 << k for k in emit[:-1])
+        # an empty mask is the plain call, which goes on from the rounded sweep outputs of 16-bit tensors only when it
+        # keeps them: keep them then, so that the result is the same tensor in grad mode and without
+        keep = need_grad or (bits == 0 and u.element_size() < 4)
+        states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if keep else None
+        em = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+        with torch.cuda.device(u.device):
+            tk = _kmax_channel(len(sweeps)) if want_kmax else None
+            L.check(lib.pde_adi_small_forward_states(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(out[Ke - 1]),
+                                                     _ptr(states), _ptr(out), em, _ptr(Mf), *[_ptr(t) for t in p], _ptr(kdev),
+                                                     _ptr(tk.host if tk else None),
+                                                     C.c_void_p(tk.event.cuda_event if tk else 0),
+                                                     _ptr(sws), sws.numel(), _stream()), "pde_adi_small_forward_states")
+            ctx.kmax = tk
+            if want_kmax and kmax_sink is not None:
+                kmax_sink.append(tk)
+        if need_grad:
+            ctx.save_for_backward(u, states, Mf, *p)
+            ctx.sws = sws
+        ctx.cfg = (steps, mode, smooth3, clamp_max, eps, ckpt, bits, Ke)
+        ctx.param_shapes = [t.shape for t in (ab, bb, asl, bsl)]
+        ctx.M_dtype = M.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        u, states, Mf, *p = ctx.saved_tensors
+        steps, mode, smooth3, clamp_max, eps, ckpt, ebits, Ke = ctx.cfg
+        B, Cc, N, _ = u.shape
+        sps, K = len(steps[0]), len(steps)
+        sweeps = steps.flat
+        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
+        if ckpt == "auto":
+            km = ctx.kmax.wait()
+            bits = 0
+            for k in range(K):                           # one step-local mask for every step: the union
+                bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
+        else:
+            bits = int(ckpt)
+        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+        em = (C.c_uint64 * 2)(ebits & _M64, ebits >> 64)
+        ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
+        g = g.to(u.dtype).contiguous()                   # slots 0..K'-2 are the states' gradients, the last slice is gy
+        gu = torch.empty_like(u)
+        gp = [torch.empty_like(t) for t in p]
+        gM = torch.empty_like(Mf)
+        with torch.cuda.device(u.device):
+            L.check(lib.pde_adi_small_backward_states(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(g[Ke - 1]), _ptr(g), em,
+                                                      _ptr(u), _ptr(states), _ptr(Mf), mask, _ptr(gu), *[_ptr(t) for t in p],
+                                                      *[_ptr(t) for t in gp], _ptr(gM), _ptr(ctx.sws), _ptr(ws), ws.numel(),
+                                                      _stream()), "pde_adi_small_backward_states")
+        gp = [t.reshape(sh) for t, sh in zip(gp, ctx.param_shapes)]
+        return (gu, *gp, gM.to(ctx.M_dtype), None, None, None, None, None, None, None, None)
+
+
+def adi_diffuse_small_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode: str, emit,
+                             smooth3: bool = False, clamp_max: Optional[float] = None, eps: float = 1e-6, checkpoints="auto",
+                             kmax_sink: Optional[list] = None):
+    """``adi_diffuse_small`` (no skip blend) that returns the trajectory: the state after every time step listed in
+    ``emit`` (strictly increasing 0-based step indices; the last step is always included) as ONE tensor
+    (K', B, C, N, N), out of the same single launch per pass.  The state after a step is what the reference's loop holds
+    at the end of that iteration: "pre" the step's sweep output, "post" the sweep output after the operator.  With 16-bit
+    tensors the time loop goes on from the rounded sweep output of every step in grad mode and under ``no_grad`` alike,
+    and a "post" state is the fp32 value rounded once.  Differentiable: ``u``, the four coefficient tensors and ``M``
+    receive the gradient of a loss on any of the returned states.  Check ``adi_small_supported`` first; always the
+    ctypes path.  ``checkpoints`` / ``kmax_sink`` as in ``adi_diffuse_small``."""
+    if mode not in ("pre", "post"):
+        raise ValueError(mode)
+    steps = _as_schedule(steps)
+    K = len(steps)
+    emit = [int(k) for k in emit]
+    if any(k < 0 or k >= K for k in emit) or any(b <= a for a, b in zip(emit, emit[1:])):
+        raise ValueError(f"emit must be strictly increasing step indices in 0..{K - 1}, got {emit}")
+    if K == 0:
+        raise ValueError("no steps")
+    if not emit or emit[-1] != K - 1:
+        emit.append(K - 1)
+    emit = tuple(emit)
+    if u.shape[0] == 0:
+        y = _empty_passthrough(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
+        return torch.stack([y] * len(emit))
+    u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
+    return _AdiSmallStatesFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, emit, mode,
+                                   bool(smooth3), clamp_max, float(eps), checkpoints, kmax_sink)
 
 
 # --------------------------------------------------------------------------- channel mixing

@@ -231,8 +231,14 @@ class _AdiBase(nn.Module):
         tensors and the channel operator.
 
         A layer without a channel operator returns all states out of the launches ``forward`` makes (one sweep launch
-        per pass and launch group).  A layer with an operator runs step by step (functional.adi_diffuse_mixed_per_step,
-        at every C): the one-launch C <= 4 and wide kernels do not emit states; "lagged" plans there as "auto"."""
+        per pass and launch group).  So does a layer with an operator wherever ``forward`` runs on the one-launch C <= 4
+        kernels (``small_channel_kernels`` and functional.adi_small_supported: C <= 4, N in {16, 28, 32}, Strang or Lie
+        steps, fp32 / bf16 / fp16 tensors): functional.adi_diffuse_small_states, one launch per pass and launch group,
+        every checkpoint policy as in ``forward``.  There, with 16-bit tensors, the time loop goes on from the rounded
+        sweep output of every step, as the training forward of such a layer does, in grad mode and under ``no_grad``
+        alike, so the two return the same tensor.  Every other layer with an operator (C > 4, other N, rectangles,
+        float64, ``small_channel_kernels = False``) runs step by step (functional.adi_diffuse_mixed_per_step): the wide
+        kernels do not emit states; "lagged" plans there as "auto"."""
         K = int(self.num_steps)
         if steps is None:
             sel = list(range(1, K + 1))
@@ -264,8 +270,20 @@ class _AdiBase(nn.Module):
             kw = dict(smooth3=self._smooth3, clamp_max=self._clamp_max, eps=self.stability_eps)
             live = (M,) + args
             grad = torch.is_grad_enabled() and (u.requires_grad or any(p.requires_grad for p in live))
+            groups = self._step_groups(sched)
+            if self.small_channel_kernels and all(F_.adi_small_supported(u, grp, **kw) for grp in groups):
+                pieces = []
+                for gi, grp in enumerate(groups):
+                    first = gi * per                           # steps first+1 .. first+len(grp) are this group's
+                    mine = [k - first for k in sel if first < k <= first + len(grp)]
+                    out = self._diffuse_small_states(u, grp, M, mode, [k - 1 for k in mine], gi, grad)
+                    u = out[-1]
+                    if len(groups) == 1 and len(mine) == out.shape[0]:
+                        return out                             # one group, its last step wanted: the launch's own tensor
+                    pieces.append(out if mine and mine[-1] == len(grp) else out[:-1])
+                return torch.cat(pieces)
             states = []
-            for gi, grp in enumerate(self._step_groups(sched)):
+            for gi, grp in enumerate(groups):
                 ck = self._policy_of_group(gi) if grad else 0
                 u = F_.adi_diffuse_mixed_per_step(u, *args, M, grp, mode, checkpoints="auto" if ck == "lagged" else ck,
                                                   states=states, **kw)
@@ -283,6 +301,28 @@ class _AdiBase(nn.Module):
 
     #: False forces the per-step launch path (pde_adi_mixed_*) where the single-launch C <= 4 kernels would apply
     small_channel_kernels = True
+
+    def _diffuse_small_states(self, u, steps, M, mode, emit, gi, grad):
+        """One launch group of ``trajectory`` on the one-launch C <= 4 kernels (functional.adi_diffuse_small_states): the
+        states after the 0-based steps in ``emit`` and after the last one; checkpoints as in ``_diffuse_mixed``."""
+        args = (self.alpha_base, self.beta_base, self.alpha_time_coeff, self.beta_time_coeff)
+        kw = dict(smooth3=self._smooth3, clamp_max=self._clamp_max, eps=self.stability_eps)
+        ck = self._policy_of_group(gi) if grad else 0
+        if ck != "lagged":
+            return F_.adi_diffuse_small_states(u, *args, M, steps, mode, emit, checkpoints=ck, **kw)
+        sps = len(steps[0])
+
+        def plan(km):
+            bits = 0
+            for k in range(len(steps)):
+                bits |= F_.plan_checkpoints(km[k * sps:(k + 1) * sps], F_.CKPT_AMAX / 2)
+            return bits
+        old, cache, key = self._lagged_plan(("mixed", len(steps), sps, steps[0][0].t), u, args, kw,
+                                            [s for st in steps for s in st], plan)
+        sink = []
+        y = F_.adi_diffuse_small_states(u, *args, M, steps, mode, emit, checkpoints=old[1], kmax_sink=sink, **kw)
+        cache[key] = (sink[0], old[1]) if sink else old
+        return y
 
     def _diffuse_mixed(self, u, steps, M, mode, skip_weight=None, gi=0):
         """All steps of a layer with a channel operator between them; checkpoints as in ``_diffuse`` (one step-local

@@ -267,6 +267,39 @@ int pde_adi_small_backward(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t
                            float* gM, float* g_skip_weight, const void* steps_workspace,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* The trajectory of such a layer out of the SAME launches: pde_adi_small_forward / _backward without the skip blend
+ * (no skip_weight / g_skip_weight) that also return the state after chosen time steps, and take an upstream gradient
+ * for every one of them.  emit_mask is indexed by time step: bit k (0-based) = the state after step k, what the
+ * reference's loop holds at the end of iteration k — mode 1 the step's sweep output, mode 2 the sweep output after the
+ * coupling.  Only bits 0 .. K-2 may be set, K = num_sweeps / sweeps_per_step (the state after the last step is y).
+ * forward_states: the emitted states go to traj[slot(k)][B][C][N][N] in io_dtype, slots in the order of the set bits; a
+ * caller that wants one stacked tensor points y at the slice behind the last slot.  `states` as in the plain call (NULL:
+ * inference).  With 16-bit tensors the emitting forward always goes on from the rounded sweep output of every step,
+ * whether `states` is kept or not (the plain call does so only when it keeps them), so traj and y do not depend on
+ * `states`, and the backward reads what the forward went on from; an emitted mode-2 state is the fp32 value rounded once.
+ * backward_states: gtraj has the layout of traj and holds dL/d(state); at the top of the reverse iteration of step k the
+ * adjoint gets += gtraj[slot(k)] (mode 2: before the adjoint of the coupling, mode 1: before the step's adjoint sweeps).
+ * State rebuild, step-local checkpoints, masked channels, gM and the coefficient sums are those of the plain call.
+ * Workspaces are those of the plain calls.  Checked on the host before any launch: traj / gtraj NULL with a non-empty
+ * mask, a bit at or above K-1, or a descriptor pde_adi_small_supported refuses: PDE_E_BADARG.  An empty (or NULL) mask
+ * is the plain call exactly, traj / gtraj are then not read. */
+int pde_adi_small_forward_states(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode,
+                                 const void* u, void* y, void* states, void* traj, const uint64_t emit_mask[2],
+                                 const float* M,
+                                 const float* alpha_base, const float* beta_base,
+                                 const float* alpha_slope, const float* beta_slope,
+                                 float* kappa_max, float* kappa_max_host, void* kappa_event,
+                                 void* steps_workspace, size_t workspace_bytes, void* stream);
+int pde_adi_small_backward_states(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode,
+                                  const void* gy, const void* gtraj, const uint64_t emit_mask[2],
+                                  const void* u, const void* states, const float* M,
+                                  const uint64_t ckpt_mask[2], void* gu,
+                                  const float* alpha_base, const float* beta_base,
+                                  const float* alpha_slope, const float* beta_slope,
+                                  float* g_alpha_base, float* g_beta_base, float* g_alpha_slope, float* g_beta_slope,
+                                  float* gM, const void* steps_workspace,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- K1, layers that share an input, in ONE launch per pass ------------------------
  * cifar10.py:272-274 runs three EnhancedDiffusionLayers (5, 8 and 4 steps with their own dt/dx and their own
  * parameters) on the same x and combines them with softmax weights (:277-280); cifar_2version.py:287-288 two.
