@@ -160,6 +160,15 @@ SIGNATURES = {
     "pde_jacobi_io_forward": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _vp, _vp]),
     "pde_jacobi_io_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "pde_jacobi_io_backward": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _fp, _fp, _vp, _fp, _fp, _vp, _sz, _vp]),
+    # the trajectory of the explicit layers: the plain call's arguments plus the states tensor and the emission mask
+    "pde_jacobi_io_forward_states": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _vp, _vp, C.POINTER(C.c_uint64),
+                                               _vp, _sz, _vp]),
+    "pde_jacobi_io_backward_states": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, C.POINTER(C.c_uint64), _fp, _fp,
+                                                _vp, _fp, _fp, _vp, _sz, _vp]),
+    "pde_explicit5_forward_states": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _f32, _f32, _f32, _f32, _i32, _vp,
+                                               _vp, _vp, C.POINTER(C.c_uint64), _vp]),
+    "pde_explicit5_backward_states": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _fp,
+                                                _fp, _f32, _f32, _f32, _f32, _i32, _vp, _fp, _fp, _vp, _sz, _vp]),
     "pde_sym_layer_supported": (C.c_int, [_i32, _i32]),
     "pde_sym_layer_workspace_bytes": (_sz, [_i32, _i32]),
     "pde_sym_layer_forward": (C.c_int, [_i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _f32, _f32, _fp, _f32,
@@ -206,6 +215,13 @@ SIGNATURES = {
     "pde_jacobi_f64_forward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pde_jacobi_f64_backward_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "pde_jacobi_f64_backward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_explicit5_f64_forward_states": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _vp,
+                                                   _vp, _vp, C.POINTER(C.c_uint64), _vp]),
+    "pde_explicit5_f64_backward_states": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp,
+                                                    _vp, _f64, _f64, _f64, _f64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_jacobi_f64_forward_states": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp]),
+    "pde_jacobi_f64_backward_states": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _sz, _vp]),
     "pde_adi_rect_supported": (C.c_int, [_i32, _i32]),
     "pde_adi_rect_forward_workspace_bytes": (_sz, [_DR]),
     "pde_adi_rect_backward_workspace_bytes": (_sz, [_DR, _i32]),

@@ -82,6 +82,37 @@ __device__ __forceinline__ unsigned short f32_to_bf16_hw(float f) { return __bui
 __device__ __forceinline__ unsigned short f32_to_f16_hw(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
 __device__ __forceinline__ float f16_to_f32(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
 
+// ---- trajectory emission of the explicit layers (pde_jacobi_*_states, pde_explicit5_*_states) --------------------------
+// emit_mask[2] of the C ABI by value: bit k-1 = the state after time step k is emitted; slots in bit order
+struct EmitMask {
+    unsigned long long lo, hi;
+    __host__ __device__ bool any() const { return (lo | hi) != 0; }
+};
+// slot of the state after (1-based) time step `step`, -1 when it is not emitted
+__host__ __device__ inline int emit_slot(const EmitMask& m, int step) {
+    const int bit = step - 1;
+    if (bit < 0 || bit > 127) return -1;
+    const unsigned long long w = bit < 64 ? m.lo : m.hi;
+    const int b = bit & 63;
+    if (!((w >> b) & 1ull)) return -1;
+    return __builtin_popcountll(w & ((1ull << b) - 1ull)) + (bit < 64 ? 0 : __builtin_popcountll(m.lo));
+}
+// The host-side checks every *_states entry point makes before any launch: a non-empty mask needs nt <= 128, bits
+// 0 .. nt-2 only (the state after the last step is `out`), and the tensor the states go to / their gradients come from.
+inline int emit_check(const uint64_t* mask, int nt, const void* tensor, EmitMask& m) {
+    m.lo = mask ? mask[0] : 0;
+    m.hi = mask ? mask[1] : 0;
+    if (!m.any()) return PDE_OK;
+    if (nt > 128) return PDE_E_TOO_MANY_SWEEPS;
+    const int top = nt - 1;                                // the first bit that may not be set
+    bool bad;
+    if (top <= 0) bad = true;
+    else if (top < 64) bad = (m.lo >> top) != 0 || m.hi != 0;
+    else if (top == 64) bad = m.hi != 0;
+    else bad = (m.hi >> (top - 64)) != 0;
+    return (bad || !tensor) ? PDE_E_BADARG : PDE_OK;
+}
+
 struct Timing {
     bool on = false;
     double fwd_ms = 0, bwd_ms = 0;

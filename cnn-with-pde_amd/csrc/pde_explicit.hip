@@ -23,6 +23,17 @@
 //   Backward recomputes the forward, parking each state in the workspace, then walks the
 //   adjoint back, accumulating dA_i, dB_j per sample; a second kernel sums over samples.
 //   Larger planes (up to PDE_JACOBI_MAX_HW): the tiled kernels of pde_jacobi_tiled.h.
+//
+// trajectory (pde_explicit5_*_states, pde_jacobi_io_*_states): every forward / backward kernel above has an emitting
+//   variant — a template flag (EMIT; TE for the generic explicit kernels): the plain instantiations run the instructions
+//   they ran, with two more (unread) kernel arguments.
+//   Forward: after a time step whose bit is set in the 128-bit mask (EmitMask, pde_common.h) the state is also written to
+//   its slot of the trajectory tensor in the tensors' own type, rounded once, while the time loop goes on in fp32.
+//   Backward: once the walk holds the adjoint of an emitted state, that state's upstream gradient is added to it (interior
+//   cells only for Jacobi).  No launch is added: an empty mask runs the plain instantiations, and the plain entry points
+//   are the *_states ones with a NULL mask.
+#include <type_traits>
+
 #include "pde_common.h"
 
 namespace pde {
@@ -110,12 +121,17 @@ __device__ __forceinline__ float4 lap0_4(const IO* plane, int H, int W, int h, i
 }
 
 // (TI / TO: the step's input and output types — a call with bf16 tensors reads bf16 in its first step and writes bf16 in
-//  its last; what passes between the steps is fp32)
-template <typename TI, typename TO>
+//  its last; what passes between the steps is fp32.  TE: void, or the type of the trajectory tensor `emit`, which then
+//  receives this step's output too, rounded once — the emitting variants of pde_explicit5_forward_states)
+struct NoEmit {};
+template <typename TE> struct EmitPtr { typedef TE* type; };
+template <> struct EmitPtr<void> { typedef NoEmit type; };
+template <> struct EmitPtr<const void> { typedef NoEmit type; };
+template <typename TI, typename TO, typename TE = void>
 __global__ __launch_bounds__(256) void explicit5_fwd_kernel(const TI* __restrict__ u, const float* __restrict__ alpha,
                                                             const float* __restrict__ scale, TO* __restrict__ out,
                                                             int C, int H, int W, float dt, float eps, float maxc,
-                                                            float relax) {
+                                                            float relax, typename EmitPtr<TE>::type emit) {
     const int pc = blockIdx.x;                         // plane index b*C + c
     const int c = pc % C;
     const float a = fminf(fmaxf(alpha[c], eps), maxc) * dt;
@@ -134,6 +150,7 @@ __global__ __launch_bounds__(256) void explicit5_fwd_kernel(const TI* __restrict
         { const float v = s * cu.z; const float nw = v + a * (s * lp.z); o.z = cu.z + relax * (nw - cu.z); }
         { const float v = s * cu.w; const float nw = v + a * (s * lp.w); o.w = cu.w + relax * (nw - cu.w); }
         V4<TO>::st(oplane + (size_t)h * W + w0, o);
+        if constexpr (!std::is_void<TE>::value) V4<TE>::st(emit + (size_t)pc * H * W + (size_t)h * W + w0, o);
     }
 }
 
@@ -146,12 +163,14 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-template <typename TU, typename TG, typename TO>
+// (TE: void, or the type of `ginj`, the gradient of the emitted state this step's output is the adjoint of: added to gu)
+template <typename TU, typename TG, typename TO, typename TE = void>
 __global__ __launch_bounds__(256) void explicit5_bwd_kernel(const TU* __restrict__ u, const TG* __restrict__ g,
                                                             const float* __restrict__ alpha,
                                                             const float* __restrict__ scale, TO* __restrict__ gu,
                                                             float* __restrict__ part, int C, int H, int W, float dt,
-                                                            float eps, float maxc, float relax, int accumulate) {
+                                                            float eps, float maxc, float relax, int accumulate,
+                                                            typename EmitPtr<const TE>::type ginj) {
     __shared__ float sh[4];
     const int pc = blockIdx.x;
     const int c = pc % C;
@@ -172,6 +191,10 @@ __global__ __launch_bounds__(256) void explicit5_bwd_kernel(const TU* __restrict
         o.y = (1.f - relax) * cg.y + relax * s * (cg.y + a * lg.y);
         o.z = (1.f - relax) * cg.z + relax * s * (cg.z + a * lg.z);
         o.w = (1.f - relax) * cg.w + relax * s * (cg.w + a * lg.w);
+        if constexpr (!std::is_void<TE>::value) {
+            const float4 gi = V4<TE>::ld_once(ginj + (size_t)pc * H * W + (size_t)h * W + w0);
+            o.x += gi.x; o.y += gi.y; o.z += gi.z; o.w += gi.w;
+        }
         V4<TO>::st(op + (size_t)h * W + w0, o);
         p1 += cg.x * cu.x + cg.y * cu.y + cg.z * cu.z + cg.w * cu.w;
         p2 += lg.x * cu.x + lg.y * cu.y + lg.z * cu.z + lg.w * cu.w;
@@ -196,11 +219,11 @@ __device__ __forceinline__ float lap0_1(const IO* plane, int H, int W, int h, in
     return n + s + l + r - 4.f * c;
 }
 
-template <typename TI, typename TO>
+template <typename TI, typename TO, typename TE = void>
 __global__ __launch_bounds__(256) void explicit5_fwd_col_kernel(const TI* __restrict__ u, const float* __restrict__ alpha,
                                                                 const float* __restrict__ scale, TO* __restrict__ out,
                                                                 int C, int H, int W, float dt, float eps, float maxc,
-                                                                float relax) {
+                                                                float relax, typename EmitPtr<TE>::type emit) {
     const int pc = blockIdx.x;
     const int c = pc % C;
     const float a = fminf(fmaxf(alpha[c], eps), maxc) * dt;
@@ -213,16 +236,19 @@ __global__ __launch_bounds__(256) void explicit5_fwd_col_kernel(const TI* __rest
         const float lp = lap0_1<TI>(plane, H, W, h, w, cu);
         const float v = s * cu;
         const float nw = v + a * (s * lp);
-        S1<TO>::st(oplane + f, cu + relax * (nw - cu));
+        const float o = cu + relax * (nw - cu);
+        S1<TO>::st(oplane + f, o);
+        if constexpr (!std::is_void<TE>::value) S1<TE>::st(emit + (size_t)pc * H * W + f, o);
     }
 }
 
-template <typename TU, typename TG, typename TO>
+template <typename TU, typename TG, typename TO, typename TE = void>
 __global__ __launch_bounds__(256) void explicit5_bwd_col_kernel(const TU* __restrict__ u, const TG* __restrict__ g,
                                                                 const float* __restrict__ alpha,
                                                                 const float* __restrict__ scale, TO* __restrict__ gu,
                                                                 float* __restrict__ part, int C, int H, int W, float dt,
-                                                                float eps, float maxc, float relax, int accumulate) {
+                                                                float eps, float maxc, float relax, int accumulate,
+                                                                typename EmitPtr<const TE>::type ginj) {
     __shared__ float sh[4];
     const int pc = blockIdx.x;
     const int c = pc % C;
@@ -237,7 +263,9 @@ __global__ __launch_bounds__(256) void explicit5_bwd_col_kernel(const TU* __rest
         const float cg = S1<TG>::ld(gp + f);
         const float cu = S1<TU>::ld(up + f);
         const float lg = lap0_1<TG>(gp, H, W, h, w, cg);
-        S1<TO>::st(op + f, (1.f - relax) * cg + relax * s * (cg + a * lg));
+        float o = (1.f - relax) * cg + relax * s * (cg + a * lg);
+        if constexpr (!std::is_void<TE>::value) o += S1<TE>::ld(ginj + (size_t)pc * H * W + f);
+        S1<TO>::st(op + f, o);
         p1 += cg * cu;
         p2 += lg * cu;
     }
@@ -312,11 +340,13 @@ __device__ __forceinline__ void lap0_rows(const float4 (&c)[R], float4 (&lp)[R],
     }
 }
 
-template <typename IO, int R, int W4>
+// EMIT: the state after every step of `em` also goes to traj[slot] in the tensors' type (pde_explicit5_forward_states)
+template <typename IO, int R, int W4, bool EMIT = false>
 __global__ __launch_bounds__(256) void explicit5_fwd_wave(const IO* __restrict__ u, const float* __restrict__ alpha,
                                                           const float* __restrict__ scale, IO* __restrict__ out,
                                                           float* __restrict__ states, int nplanes, int C, int num_steps,
-                                                          float dt, float eps, float maxc, float relax) {
+                                                          float dt, float eps, float maxc, float relax,
+                                                          IO* __restrict__ traj, EmitMask em) {
     constexpr int W = 4 * W4, H = R * (64 / W4);
     const int lane = threadIdx.x & 63;
     const int pc = blockIdx.x * 4 + (threadIdx.x >> 6);          // one wave per plane
@@ -346,6 +376,14 @@ __global__ __launch_bounds__(256) void explicit5_fwd_wave(const IO* __restrict__
 #pragma unroll
             for (int i = 0; i < R; ++i) V4<float>::st(sp + off + (size_t)i * W, cur[i]);
         }
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, step + 1);
+            if (slot >= 0) {
+                IO* tp = traj + (size_t)slot * nplanes * H * W;
+#pragma unroll
+                for (int i = 0; i < R; ++i) V4<IO>::st(tp + off + (size_t)i * W, cur[i]);
+            }
+        }
     }
 #pragma unroll
     for (int i = 0; i < R; ++i) V4<IO>::st(out + off + (size_t)i * W, cur[i]);
@@ -358,12 +396,14 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // backward of num_steps steps: g walks back through the steps in registers; u_{k-1} (the input of step k) is the
 // layer input for k = 1 and states[k-2] otherwise
-template <typename IO, int R, int W4>
+// EMIT: once g is the adjoint of an emitted state it gets += gtraj[slot] (pde_explicit5_backward_states)
+template <typename IO, int R, int W4, bool EMIT = false>
 __global__ __launch_bounds__(256) void explicit5_bwd_wave(const IO* __restrict__ u, const float* __restrict__ states,
                                                           const IO* __restrict__ g, const float* __restrict__ alpha,
                                                           const float* __restrict__ scale, IO* __restrict__ gu,
                                                           float* __restrict__ part, int nplanes, int C, int num_steps,
-                                                          float dt, float eps, float maxc, float relax) {
+                                                          float dt, float eps, float maxc, float relax,
+                                                          const IO* __restrict__ gtraj, EmitMask em) {
     constexpr int W = 4 * W4, H = R * (64 / W4);
     const int lane = threadIdx.x & 63;
     const int pc = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -390,6 +430,17 @@ __global__ __launch_bounds__(256) void explicit5_bwd_wave(const IO* __restrict__
             cg4[i].z = (1.f - relax) * cg4[i].z + relax * s * (cg4[i].z + a * lg[i].z);
             cg4[i].w = (1.f - relax) * cg4[i].w + relax * s * (cg4[i].w + a * lg[i].w);
         }
+        if constexpr (EMIT) {                                     // g is now the adjoint of the state after step - 1
+            const int slot = emit_slot(em, step - 1);
+            if (slot >= 0) {
+                const IO* tp = gtraj + (size_t)slot * nplanes * H * W;
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    const float4 gi = V4<IO>::ld_once(tp + off + (size_t)i * W);
+                    cg4[i].x += gi.x; cg4[i].y += gi.y; cg4[i].z += gi.z; cg4[i].w += gi.w;
+                }
+            }
+        }
     }
 #pragma unroll
     for (int i = 0; i < R; ++i) V4<IO>::st(gu + off + (size_t)i * W, cg4[i]);
@@ -401,22 +452,36 @@ __global__ __launch_bounds__(256) void explicit5_bwd_wave(const IO* __restrict__
 // which plane sizes the wave-per-plane kernels cover
 bool wave_plane_ok(int H, int W) { return (H == 64 && W == 64) || (H == 32 && W == 32) || (H == 16 && W == 16); }
 
-template <typename IO>
+template <typename IO, bool EMIT>
 void launch_fwd_wave(int H, const IO* u, const float* alpha, const float* scale, IO* out, float* states, int nplanes, int C,
-                     int num_steps, float dt, float eps, float maxc, float relax, hipStream_t st) {
+                     int num_steps, float dt, float eps, float maxc, float relax, IO* traj, EmitMask em, hipStream_t st) {
     const dim3 grid((nplanes + 3) / 4), block(256);
-    if (H == 64) hipLaunchKernelGGL((explicit5_fwd_wave<IO, 16, 16>), grid, block, 0, st, u, alpha, scale, out, states, nplanes, C, num_steps, dt, eps, maxc, relax);
-    else if (H == 32) hipLaunchKernelGGL((explicit5_fwd_wave<IO, 4, 8>), grid, block, 0, st, u, alpha, scale, out, states, nplanes, C, num_steps, dt, eps, maxc, relax);
-    else hipLaunchKernelGGL((explicit5_fwd_wave<IO, 1, 4>), grid, block, 0, st, u, alpha, scale, out, states, nplanes, C, num_steps, dt, eps, maxc, relax);
+    if (H == 64) hipLaunchKernelGGL((explicit5_fwd_wave<IO, 16, 16, EMIT>), grid, block, 0, st, u, alpha, scale, out, states, nplanes, C, num_steps, dt, eps, maxc, relax, traj, em);
+    else if (H == 32) hipLaunchKernelGGL((explicit5_fwd_wave<IO, 4, 8, EMIT>), grid, block, 0, st, u, alpha, scale, out, states, nplanes, C, num_steps, dt, eps, maxc, relax, traj, em);
+    else hipLaunchKernelGGL((explicit5_fwd_wave<IO, 1, 4, EMIT>), grid, block, 0, st, u, alpha, scale, out, states, nplanes, C, num_steps, dt, eps, maxc, relax, traj, em);
 }
-template <typename IO>
+template <typename IO, bool EMIT>
 void launch_bwd_wave(int H, const IO* u, const float* states, const IO* g, const float* alpha, const float* scale, IO* gu,
                      float* part, int nplanes, int C, int num_steps, float dt, float eps, float maxc, float relax,
-                     hipStream_t st) {
+                     const IO* gtraj, EmitMask em, hipStream_t st) {
     const dim3 grid((nplanes + 3) / 4), block(256);
-    if (H == 64) hipLaunchKernelGGL((explicit5_bwd_wave<IO, 16, 16>), grid, block, 0, st, u, states, g, alpha, scale, gu, part, nplanes, C, num_steps, dt, eps, maxc, relax);
-    else if (H == 32) hipLaunchKernelGGL((explicit5_bwd_wave<IO, 4, 8>), grid, block, 0, st, u, states, g, alpha, scale, gu, part, nplanes, C, num_steps, dt, eps, maxc, relax);
-    else hipLaunchKernelGGL((explicit5_bwd_wave<IO, 1, 4>), grid, block, 0, st, u, states, g, alpha, scale, gu, part, nplanes, C, num_steps, dt, eps, maxc, relax);
+    if (H == 64) hipLaunchKernelGGL((explicit5_bwd_wave<IO, 16, 16, EMIT>), grid, block, 0, st, u, states, g, alpha, scale, gu, part, nplanes, C, num_steps, dt, eps, maxc, relax, gtraj, em);
+    else if (H == 32) hipLaunchKernelGGL((explicit5_bwd_wave<IO, 4, 8, EMIT>), grid, block, 0, st, u, states, g, alpha, scale, gu, part, nplanes, C, num_steps, dt, eps, maxc, relax, gtraj, em);
+    else hipLaunchKernelGGL((explicit5_bwd_wave<IO, 1, 4, EMIT>), grid, block, 0, st, u, states, g, alpha, scale, gu, part, nplanes, C, num_steps, dt, eps, maxc, relax, gtraj, em);
+}
+// the wave-per-plane call of one tensor type: the plain instantiations for an empty mask
+template <typename IO>
+void fwd_wave_io(int H, const void* u, const float* alpha, const float* scale, void* out, float* states, int nplanes, int C,
+                 int num_steps, float dt, float eps, float maxc, float relax, void* traj, EmitMask em, hipStream_t st) {
+    if (em.any()) launch_fwd_wave<IO, true>(H, (const IO*)u, alpha, scale, (IO*)out, states, nplanes, C, num_steps, dt, eps, maxc, relax, (IO*)traj, em, st);
+    else launch_fwd_wave<IO, false>(H, (const IO*)u, alpha, scale, (IO*)out, states, nplanes, C, num_steps, dt, eps, maxc, relax, (IO*)nullptr, em, st);
+}
+template <typename IO>
+void bwd_wave_io(int H, const void* u, const float* states, const void* g, const float* alpha, const float* scale, void* gu,
+                 float* part, int nplanes, int C, int num_steps, float dt, float eps, float maxc, float relax,
+                 const void* gtraj, EmitMask em, hipStream_t st) {
+    if (em.any()) launch_bwd_wave<IO, true>(H, (const IO*)u, states, (const IO*)g, alpha, scale, (IO*)gu, part, nplanes, C, num_steps, dt, eps, maxc, relax, (const IO*)gtraj, em, st);
+    else launch_bwd_wave<IO, false>(H, (const IO*)u, states, (const IO*)g, alpha, scale, (IO*)gu, part, nplanes, C, num_steps, dt, eps, maxc, relax, (const IO*)nullptr, em, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -444,10 +509,11 @@ __device__ __forceinline__ void jacobi_step(const float* P, float* Q, const floa
     }
 }
 
-template <typename IO>
+// EMIT: the interior of the state after every step of `em` also goes to traj[slot][B][H][W] (pde_jacobi_io_forward_states)
+template <typename IO, bool EMIT = false>
 __global__ __launch_bounds__(256) void jacobi_fwd_kernel(const IO* __restrict__ u, const float* __restrict__ a_row,
                                                          const float* __restrict__ b_col, IO* __restrict__ out,
-                                                         int H, int W, int nt) {
+                                                         int H, int W, int nt, IO* __restrict__ traj, EmitMask em) {
     extern __shared__ float sm[];
     const int Wp = W + 2, PN = (H + 2) * Wp;
     float* P = sm;
@@ -466,18 +532,26 @@ __global__ __launch_bounds__(256) void jacobi_fwd_kernel(const IO* __restrict__ 
         jacobi_step(P, Q, a, b, H, W);
         __syncthreads();
         float* t = P; P = Q; Q = t;
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, n + 1);
+            if (slot >= 0) {
+                IO* tb = traj + ((size_t)slot * gridDim.x + blockIdx.x) * H * W;
+                for (int e = threadIdx.x; e < H * W; e += blockDim.x) S1<IO>::st(tb + e, P[(e / W + 1) * Wp + (e % W) + 1]);
+            }
+        }
     }
     IO* ob = out + (size_t)blockIdx.x * H * W;
     for (int e = threadIdx.x; e < H * W; e += blockDim.x) S1<IO>::st(ob + e, P[(e / W + 1) * Wp + (e % W) + 1]);
 }
 
 // workspace per sample: nt states of PN floats, then H+W partial sums
-template <typename IO>
+// EMIT: once G is the adjoint of an emitted state its interior gets += gtraj[slot] (pde_jacobi_io_backward_states)
+template <typename IO, bool EMIT = false>
 __global__ __launch_bounds__(256) void jacobi_bwd_kernel(const IO* __restrict__ u, const IO* __restrict__ gout,
                                                          const float* __restrict__ a_row,
                                                          const float* __restrict__ b_col, IO* __restrict__ gu,
                                                          float* __restrict__ states, float* __restrict__ part,
-                                                         int H, int W, int nt) {
+                                                         int H, int W, int nt, const IO* __restrict__ gtraj, EmitMask em) {
     extern __shared__ float sm[];
     const int Wp = W + 2, PN = (H + 2) * Wp;
     float* P = sm;
@@ -535,6 +609,11 @@ __global__ __launch_bounds__(256) void jacobi_bwd_kernel(const IO* __restrict__ 
             }
         }
         // dL/dP_n from dL/dP_{n+1}
+        const IO* gt = nullptr;                                // dL/d(state after step n), where that state was emitted
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, n);
+            if (slot >= 0) gt = gtraj + ((size_t)slot * gridDim.x + s) * H * W;
+        }
         for (int e = threadIdx.x; e < PN; e += blockDim.x) {
             const int i = e / Wp, j = e % Wp;
             const bool in = (i >= 1 && i <= H && j >= 1 && j <= W);
@@ -546,6 +625,9 @@ __global__ __launch_bounds__(256) void jacobi_bwd_kernel(const IO* __restrict__ 
             if (i >= 1 && i <= H) {
                 if (j - 1 >= 1 && j - 1 <= W) v += b[j - 2] * G[e - 1];
                 if (j + 1 >= 1 && j + 1 <= W) v += b[j] * G[e + 1];
+            }
+            if constexpr (EMIT) {
+                if (gt && in) v += S1<IO>::ld(gt + (i - 1) * W + (j - 1));
             }
             Gn[e] = v;
         }
@@ -613,9 +695,9 @@ JTiledWs jacobi_tiled_ws(int B, int H, int W, int nt) {
     return w;
 }
 
-template <typename IO>
+template <typename IO, bool EMIT>
 int jacobi_tiled_forward(int B, int H, int W, int nt, const void* u, const float* a_row, const float* b_col, void* out,
-                         void* workspace, hipStream_t st) {
+                         void* workspace, void* traj, EmitMask em, hipStream_t st) {
     const int nTy = jtiles(H), nTx = jtiles(W);
     const dim3 grid((unsigned)((size_t)B * nTy * nTx));
     float* img[2] = {static_cast<float*>(workspace),
@@ -625,21 +707,23 @@ int jacobi_tiled_forward(int B, int H, int W, int nt, const void* u, const float
     do {                                                    // nt = 0: one launch of no steps copies
         const int k = nt - n0 < kJK ? nt - n0 : kJK;
         const bool last = n0 + k == nt;
-        hipLaunchKernelGGL(jacobi_tiled_fwd_kernel<IO>, grid, dim3(256), 0, st, (const IO*)u,
+        hipLaunchKernelGGL((jacobi_tiled_fwd_kernel<IO, EMIT>), grid, dim3(256), 0, st, (const IO*)u,
                            l == 0 ? (const float*)nullptr : (const float*)img[(l - 1) & 1], a_row, b_col,
-                           last ? out : (void*)img[l & 1], last ? 0 : 1, (float*)nullptr, (size_t)0, H, W, nTy, nTx, k);
+                           last ? out : (void*)img[l & 1], last ? 0 : 1, (float*)nullptr, (size_t)0, H, W, nTy, nTx, k,
+                           (IO*)traj, (size_t)B * H * W, em, n0);
         n0 += k;
         ++l;
     } while (n0 < nt);
     return check_launch();
 }
 
-template <typename IO>
+template <typename IO, bool EMIT>
 int jacobi_tiled_backward(int B, int H, int W, int nt, const void* u, const void* gout, const float* a_row,
-                          const float* b_col, void* gu, float* g_a_row, float* g_b_col, void* workspace, hipStream_t st) {
+                          const float* b_col, void* gu, float* g_a_row, float* g_b_col, void* workspace, const void* gtraj,
+                          EmitMask em, hipStream_t st) {
     static unsigned long long configured = 0;
     const size_t lds = kJBwdFloats * sizeof(float);
-    if (ensure_dynamic_lds(reinterpret_cast<const void*>(jacobi_tiled_bwd_kernel<IO>), (int)lds, configured) != PDE_OK)
+    if (ensure_dynamic_lds(reinterpret_cast<const void*>(jacobi_tiled_bwd_kernel<IO, EMIT>), (int)lds, configured) != PDE_OK)
         return PDE_E_LAUNCH;
     const int nTy = jtiles(H), nTx = jtiles(W);
     const dim3 grid((unsigned)((size_t)B * nTy * nTx));
@@ -652,16 +736,17 @@ int jacobi_tiled_backward(int B, int H, int W, int nt, const void* u, const void
     // forward again, parking P_1 .. P_{nt-1}; every launch continues from the last state the one before parked
     for (int n0 = 0; n0 < nt - 1; n0 += kJK) {
         const int k = nt - 1 - n0 < kJK ? nt - 1 - n0 : kJK;
-        hipLaunchKernelGGL(jacobi_tiled_fwd_kernel<IO>, grid, dim3(256), 0, st, (const IO*)u,
+        hipLaunchKernelGGL((jacobi_tiled_fwd_kernel<IO, false>), grid, dim3(256), 0, st, (const IO*)u,
                            n0 == 0 ? (const float*)nullptr : (const float*)(states + (size_t)(n0 - 1) * stride), a_row, b_col,
-                           (void*)nullptr, 0, states + (size_t)n0 * stride, stride, H, W, nTy, nTx, k);
+                           (void*)nullptr, 0, states + (size_t)n0 * stride, stride, H, W, nTy, nTx, k, (IO*)nullptr, (size_t)0,
+                           EmitMask{0, 0}, 0);
     }
     int n_hi = nt, l = 0;
     do {                                                    // nt = 0: one launch of no steps pads gout
         const int k = n_hi < kJK ? n_hi : kJK;
-        hipLaunchKernelGGL(jacobi_tiled_bwd_kernel<IO>, grid, dim3(256), lds, st, (const IO*)u, (const float*)states, stride,
-                           l == 0 ? (const IO*)gout : (const IO*)nullptr, (const float*)gimg[(l + 1) & 1], gimg[l & 1], a_row,
-                           b_col, part, l == 0 ? 0 : 1, H, W, nTy, nTx, n_hi, k);
+        hipLaunchKernelGGL((jacobi_tiled_bwd_kernel<IO, EMIT>), grid, dim3(256), lds, st, (const IO*)u, (const float*)states,
+                           stride, l == 0 ? (const IO*)gout : (const IO*)nullptr, (const float*)gimg[(l + 1) & 1], gimg[l & 1],
+                           a_row, b_col, part, l == 0 ? 0 : 1, H, W, nTy, nTx, n_hi, k, (const IO*)gtraj, em);
         n_hi -= k;
         ++l;
     } while (n_hi > 0);
@@ -680,40 +765,49 @@ struct ExArgs {
     int nplanes, C, H, W;
     float dt, eps, maxc, relax;
 };
-template <typename TI, typename TO>
-void ex_fwd(const ExArgs& a, const void* src, void* dst, hipStream_t st) {
+template <typename TI, typename TO, typename TE = void>
+void ex_fwd(const ExArgs& a, const void* src, void* dst, typename EmitPtr<TE>::type emit, hipStream_t st) {
     if (a.W % 4)                                           // rows not 16-byte aligned: the scalar-column variant
-        hipLaunchKernelGGL((explicit5_fwd_col_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha,
-                           a.scale, (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax);
+        hipLaunchKernelGGL((explicit5_fwd_col_kernel<TI, TO, TE>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha,
+                           a.scale, (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, emit);
     else
-        hipLaunchKernelGGL((explicit5_fwd_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha, a.scale,
-                           (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax);
+        hipLaunchKernelGGL((explicit5_fwd_kernel<TI, TO, TE>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src, a.alpha,
+                           a.scale, (TO*)dst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, emit);
 }
+// emit: NULL, or the slot of the trajectory tensor (type T) this step's output goes to as well; never at the last step
 template <typename T>
-void ex_fwd_step(const ExArgs& a, bool first, bool last, const void* src, void* dst, hipStream_t st) {
-    if (first && last) ex_fwd<T, T>(a, src, dst, st);
-    else if (first) ex_fwd<T, float>(a, src, dst, st);
-    else if (last) ex_fwd<float, T>(a, src, dst, st);
-    else ex_fwd<float, float>(a, src, dst, st);
+void ex_fwd_step(const ExArgs& a, bool first, bool last, const void* src, void* dst, void* emit, hipStream_t st) {
+    if (emit && first) ex_fwd<T, float, T>(a, src, dst, (T*)emit, st);
+    else if (emit) ex_fwd<float, float, T>(a, src, dst, (T*)emit, st);
+    else if (first && last) ex_fwd<T, T>(a, src, dst, NoEmit{}, st);
+    else if (first) ex_fwd<T, float>(a, src, dst, NoEmit{}, st);
+    else if (last) ex_fwd<float, T>(a, src, dst, NoEmit{}, st);
+    else ex_fwd<float, float>(a, src, dst, NoEmit{}, st);
 }
 // backward step k: u is the caller's (type T) for the first step, a parked fp32 state otherwise; the incoming gradient
 // is the caller's for the last step; gu is written to the caller's tensor at the first step
-template <typename TU, typename TG, typename TO>
-void ex_bwd(const ExArgs& a, const void* up, const void* gin, void* gdst, float* part, int acc, hipStream_t st) {
+template <typename TU, typename TG, typename TO, typename TE = void>
+void ex_bwd(const ExArgs& a, const void* up, const void* gin, void* gdst, float* part, int acc,
+            typename EmitPtr<const TE>::type ginj, hipStream_t st) {
     if (a.W % 4)
-        hipLaunchKernelGGL((explicit5_bwd_col_kernel<TU, TG, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up,
-                           (const TG*)gin, a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc);
+        hipLaunchKernelGGL((explicit5_bwd_col_kernel<TU, TG, TO, TE>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up,
+                           (const TG*)gin, a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc,
+                           ginj);
     else
-        hipLaunchKernelGGL((explicit5_bwd_kernel<TU, TG, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up, (const TG*)gin,
-                           a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc);
+        hipLaunchKernelGGL((explicit5_bwd_kernel<TU, TG, TO, TE>), dim3(a.nplanes), dim3(256), 0, st, (const TU*)up,
+                           (const TG*)gin, a.alpha, a.scale, (TO*)gdst, part, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, acc,
+                           ginj);
 }
+// ginj: NULL, or the slot of the trajectory's gradient (type T) that is added to this step's output; never at step 1
 template <typename T>
 void ex_bwd_step(const ExArgs& a, bool ufirst, bool gfirst, const void* up, const void* gin, void* gdst, float* part, int acc,
-                 hipStream_t st) {
-    if (ufirst && gfirst) ex_bwd<T, T, T>(a, up, gin, gdst, part, acc, st);
-    else if (ufirst) ex_bwd<T, float, T>(a, up, gin, gdst, part, acc, st);
-    else if (gfirst) ex_bwd<float, T, float>(a, up, gin, gdst, part, acc, st);
-    else ex_bwd<float, float, float>(a, up, gin, gdst, part, acc, st);
+                 const void* ginj, hipStream_t st) {
+    if (ginj && gfirst) ex_bwd<float, T, float, T>(a, up, gin, gdst, part, acc, (const T*)ginj, st);
+    else if (ginj) ex_bwd<float, float, float, T>(a, up, gin, gdst, part, acc, (const T*)ginj, st);
+    else if (ufirst && gfirst) ex_bwd<T, T, T>(a, up, gin, gdst, part, acc, NoEmit{}, st);
+    else if (ufirst) ex_bwd<T, float, T>(a, up, gin, gdst, part, acc, NoEmit{}, st);
+    else if (gfirst) ex_bwd<float, T, float>(a, up, gin, gdst, part, acc, NoEmit{}, st);
+    else ex_bwd<float, float, float>(a, up, gin, gdst, part, acc, NoEmit{}, st);
 }
 
 }  // namespace
@@ -726,34 +820,48 @@ extern "C" {
 int pde_explicit5_forward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype, const void* u,
                           const float* alpha_base, const float* channel_scaling, float dt, float eps, float max_coeff,
                           float relax, int32_t num_steps, void* states, void* out, void* stream) {
+    return pde_explicit5_forward_states(B, C, H, W, io_dtype, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax,
+                                        num_steps, states, out, nullptr, nullptr, stream);
+}
+
+int pde_explicit5_forward_states(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype, const void* u,
+                                 const float* alpha_base, const float* channel_scaling, float dt, float eps, float max_coeff,
+                                 float relax, int32_t num_steps, void* states, void* out, void* traj,
+                                 const uint64_t emit_mask[2], void* stream) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !alpha_base || !channel_scaling || !out)
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, num_steps, traj, em);
+    if (erc != PDE_OK) return erc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nplanes = B * C;
     if (wave_plane_ok(H, W)) {                             // the plane stays in registers over all steps
         if (io_dtype == PDE_IO_F32)
-            launch_fwd_wave<float>(H, (const float*)u, alpha_base, channel_scaling, (float*)out, (float*)states, nplanes, C,
-                                   num_steps, dt, eps, max_coeff, relax, st);
+            fwd_wave_io<float>(H, u, alpha_base, channel_scaling, out, (float*)states, nplanes, C, num_steps, dt, eps,
+                               max_coeff, relax, traj, em, st);
         else if (io_dtype == PDE_IO_F16)
-            launch_fwd_wave<f16e>(H, (const f16e*)u, alpha_base, channel_scaling, (f16e*)out, (float*)states, nplanes, C,
-                                  num_steps, dt, eps, max_coeff, relax, st);
+            fwd_wave_io<f16e>(H, u, alpha_base, channel_scaling, out, (float*)states, nplanes, C, num_steps, dt, eps,
+                              max_coeff, relax, traj, em, st);
         else
-            launch_fwd_wave<bf16e>(H, (const bf16e*)u, alpha_base, channel_scaling, (bf16e*)out, (float*)states, nplanes, C,
-                                   num_steps, dt, eps, max_coeff, relax, st);
+            fwd_wave_io<bf16e>(H, u, alpha_base, channel_scaling, out, (float*)states, nplanes, C, num_steps, dt, eps,
+                               max_coeff, relax, traj, em, st);
         return check_launch();
     }
     if (num_steps > 1 && !states) return PDE_E_BADARG;     // generic sizes: one launch per step through `states` (fp32)
     const size_t tf = (size_t)nplanes * H * W;
+    const size_t esz = io_dtype == PDE_IO_F32 ? 4 : 2;
     float* sf = static_cast<float*>(states);
     const ExArgs ea{alpha_base, channel_scaling, nplanes, C, H, W, dt, eps, max_coeff, relax};
     for (int k = 0; k < num_steps; ++k) {
         const bool first = k == 0, last = k == num_steps - 1;
         const void* src = first ? u : static_cast<const void*>(sf + (size_t)(k - 1) * tf);
         void* dst = last ? out : static_cast<void*>(sf + (size_t)k * tf);
-        if (io_dtype == PDE_IO_F32) ex_fwd_step<float>(ea, first, last, src, dst, st);
-        else if (io_dtype == PDE_IO_F16) ex_fwd_step<f16e>(ea, first, last, src, dst, st);
-        else ex_fwd_step<bf16e>(ea, first, last, src, dst, st);
+        const int slot = emit_slot(em, k + 1);             // the step's own launch writes the emitted state too
+        void* emit = slot >= 0 ? static_cast<void*>(static_cast<char*>(traj) + (size_t)slot * tf * esz) : nullptr;
+        if (io_dtype == PDE_IO_F32) ex_fwd_step<float>(ea, first, last, src, dst, emit, st);
+        else if (io_dtype == PDE_IO_F16) ex_fwd_step<f16e>(ea, first, last, src, dst, emit, st);
+        else ex_fwd_step<bf16e>(ea, first, last, src, dst, emit, st);
     }
     return check_launch();
 }
@@ -772,30 +880,44 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
                            float dt, float eps, float max_coeff, float relax, int32_t num_steps, void* gu,
                            float* g_alpha_base, float* g_channel_scaling, void* workspace, size_t workspace_bytes,
                            void* stream) {
+    return pde_explicit5_backward_states(B, C, H, W, io_dtype, u, states, gout, nullptr, nullptr, alpha_base, channel_scaling,
+                                         dt, eps, max_coeff, relax, num_steps, gu, g_alpha_base, g_channel_scaling, workspace,
+                                         workspace_bytes, stream);
+}
+
+int pde_explicit5_backward_states(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype, const void* u,
+                                  const void* states, const void* gout, const void* gtraj, const uint64_t emit_mask[2],
+                                  const float* alpha_base, const float* channel_scaling, float dt, float eps,
+                                  float max_coeff, float relax, int32_t num_steps, void* gu, float* g_alpha_base,
+                                  float* g_channel_scaling, void* workspace, size_t workspace_bytes, void* stream) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !gout || !alpha_base ||
         !channel_scaling || !gu || !g_alpha_base || !g_channel_scaling || !workspace || (num_steps > 1 && !states))
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, num_steps, gtraj, em);
+    if (erc != PDE_OK) return erc;
     if (workspace_bytes < pde_explicit5_backward_workspace_bytes(B, C, H, W, io_dtype, num_steps)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(workspace);
     const int nplanes = B * C;
     if (wave_plane_ok(H, W)) {
         if (io_dtype == PDE_IO_F32)
-            launch_bwd_wave<float>(H, (const float*)u, (const float*)states, (const float*)gout, alpha_base, channel_scaling,
-                                   (float*)gu, part, nplanes, C, num_steps, dt, eps, max_coeff, relax, st);
+            bwd_wave_io<float>(H, u, (const float*)states, gout, alpha_base, channel_scaling, gu, part, nplanes, C, num_steps,
+                               dt, eps, max_coeff, relax, gtraj, em, st);
         else if (io_dtype == PDE_IO_F16)
-            launch_bwd_wave<f16e>(H, (const f16e*)u, (const float*)states, (const f16e*)gout, alpha_base, channel_scaling,
-                                  (f16e*)gu, part, nplanes, C, num_steps, dt, eps, max_coeff, relax, st);
+            bwd_wave_io<f16e>(H, u, (const float*)states, gout, alpha_base, channel_scaling, gu, part, nplanes, C, num_steps,
+                              dt, eps, max_coeff, relax, gtraj, em, st);
         else
-            launch_bwd_wave<bf16e>(H, (const bf16e*)u, (const float*)states, (const bf16e*)gout, alpha_base, channel_scaling,
-                                   (bf16e*)gu, part, nplanes, C, num_steps, dt, eps, max_coeff, relax, st);
+            bwd_wave_io<bf16e>(H, u, (const float*)states, gout, alpha_base, channel_scaling, gu, part, nplanes, C, num_steps,
+                               dt, eps, max_coeff, relax, gtraj, em, st);
     } else {
         // what passes between the steps is fp32 (the states the forward left, the gradient buffers here), whatever io_dtype
         const size_t tf = (size_t)nplanes * H * W;
         float* buf0 = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)nplanes * 2 * sizeof(float)));
         float* buf1 = reinterpret_cast<float*>(reinterpret_cast<char*>(buf0) + align256(tf * sizeof(float)));
         const float* sf = static_cast<const float*>(states);
+        const size_t esz = io_dtype == PDE_IO_F32 ? 4 : 2;
         const ExArgs ea{alpha_base, channel_scaling, nplanes, C, H, W, dt, eps, max_coeff, relax};
         const void* gin = gout;
         for (int k = num_steps; k >= 1; --k) {
@@ -803,9 +925,12 @@ int pde_explicit5_backward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t i
             const void* up = ufirst ? u : static_cast<const void*>(sf + (size_t)(k - 2) * tf);
             void* gdst = ufirst ? gu : static_cast<void*>(gin == buf0 ? buf1 : buf0);
             const int acc = gfirst ? 0 : 1;
-            if (io_dtype == PDE_IO_F32) ex_bwd_step<float>(ea, ufirst, gfirst, up, gin, gdst, part, acc, st);
-            else if (io_dtype == PDE_IO_F16) ex_bwd_step<f16e>(ea, ufirst, gfirst, up, gin, gdst, part, acc, st);
-            else ex_bwd_step<bf16e>(ea, ufirst, gfirst, up, gin, gdst, part, acc, st);
+            const int slot = emit_slot(em, k - 1);         // gdst is the adjoint of the state after step k-1
+            const void* ginj = slot >= 0 ? static_cast<const void*>(static_cast<const char*>(gtraj) + (size_t)slot * tf * esz)
+                                         : nullptr;
+            if (io_dtype == PDE_IO_F32) ex_bwd_step<float>(ea, ufirst, gfirst, up, gin, gdst, part, acc, ginj, st);
+            else if (io_dtype == PDE_IO_F16) ex_bwd_step<f16e>(ea, ufirst, gfirst, up, gin, gdst, part, acc, ginj, st);
+            else ex_bwd_step<bf16e>(ea, ufirst, gfirst, up, gin, gdst, part, acc, ginj, st);
             gin = gdst;
         }
     }
@@ -836,31 +961,52 @@ size_t pde_jacobi_forward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32
     return 2 * align256((size_t)B * H * W * sizeof(float));     // two fp32 images for the launches to alternate between
 }
 
+}  // extern "C"
+
+// one tensor type of the Jacobi calls: the plain instantiations for an empty mask, the emitting ones otherwise
+template <typename IO>
+static int jacobi_forward_io(int path, int B, int H, int W, int nt, const void* u, const float* a_row, const float* b_col,
+                             void* out, void* workspace, void* traj, EmitMask em, hipStream_t st) {
+    if (path == 2)
+        return em.any() ? jacobi_tiled_forward<IO, true>(B, H, W, nt, u, a_row, b_col, out, workspace, traj, em, st)
+                        : jacobi_tiled_forward<IO, false>(B, H, W, nt, u, a_row, b_col, out, workspace, nullptr, em, st);
+    const size_t lds = jacobi_lds(H, W, false);
+    if (em.any())
+        hipLaunchKernelGGL((jacobi_fwd_kernel<IO, true>), dim3(B), dim3(256), lds, st, (const IO*)u, a_row, b_col, (IO*)out, H, W,
+                           nt, (IO*)traj, em);
+    else
+        hipLaunchKernelGGL((jacobi_fwd_kernel<IO, false>), dim3(B), dim3(256), lds, st, (const IO*)u, a_row, b_col, (IO*)out, H,
+                           W, nt, (IO*)nullptr, em);
+    return check_launch();
+}
+
+extern "C" {
+
 int pde_jacobi_io_forward_ws(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u,
                              const float* a_row, const float* b_col, void* out, void* workspace, size_t workspace_bytes,
                              void* stream) {
+    return pde_jacobi_io_forward_states(B, H, W, nt, io_dtype, u, a_row, b_col, out, nullptr, nullptr, workspace,
+                                        workspace_bytes, stream);
+}
+
+int pde_jacobi_io_forward_states(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u,
+                                 const float* a_row, const float* b_col, void* out, void* states,
+                                 const uint64_t emit_mask[2], void* workspace, size_t workspace_bytes, void* stream) {
     const int path = jacobi_path(H, W);
     if (B <= 0 || path == 0 || nt < 0 || !u || !a_row || !b_col || !out) return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, nt, states, em);
+    if (erc != PDE_OK) return erc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (path == 2) {
-        if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
         if (!jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
         const size_t need = pde_jacobi_forward_workspace_bytes(B, H, W, nt);
         if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))) return PDE_E_WORKSPACE;
-        if (io_dtype == PDE_IO_F32) return jacobi_tiled_forward<float>(B, H, W, nt, u, a_row, b_col, out, workspace, st);
-        if (io_dtype == PDE_IO_BF16) return jacobi_tiled_forward<bf16e>(B, H, W, nt, u, a_row, b_col, out, workspace, st);
-        return jacobi_tiled_forward<f16e>(B, H, W, nt, u, a_row, b_col, out, workspace, st);
     }
-    const size_t lds = jacobi_lds(H, W, false);
-    if (io_dtype == PDE_IO_F32)
-        hipLaunchKernelGGL(jacobi_fwd_kernel<float>, dim3(B), dim3(256), lds, st, (const float*)u, a_row, b_col, (float*)out, H, W, nt);
-    else if (io_dtype == PDE_IO_BF16)
-        hipLaunchKernelGGL(jacobi_fwd_kernel<bf16e>, dim3(B), dim3(256), lds, st, (const bf16e*)u, a_row, b_col, (bf16e*)out, H, W, nt);
-    else if (io_dtype == PDE_IO_F16)
-        hipLaunchKernelGGL(jacobi_fwd_kernel<f16e>, dim3(B), dim3(256), lds, st, (const f16e*)u, a_row, b_col, (f16e*)out, H, W, nt);
-    else
-        return PDE_E_BADARG;
-    return check_launch();
+    if (io_dtype == PDE_IO_F32) return jacobi_forward_io<float>(path, B, H, W, nt, u, a_row, b_col, out, workspace, states, em, st);
+    if (io_dtype == PDE_IO_BF16) return jacobi_forward_io<bf16e>(path, B, H, W, nt, u, a_row, b_col, out, workspace, states, em, st);
+    return jacobi_forward_io<f16e>(path, B, H, W, nt, u, a_row, b_col, out, workspace, states, em, st);
 }
 
 size_t pde_jacobi_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt) {
@@ -882,39 +1028,62 @@ int pde_jacobi_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const float
                                   workspace_bytes, stream);
 }
 
+}  // extern "C"
+
+template <typename IO>
+static int jacobi_backward_io(int path, int B, int H, int W, int nt, const void* u, const void* gout, const float* a_row,
+                              const float* b_col, void* gu, float* g_a_row, float* g_b_col, void* workspace,
+                              const void* gtraj, EmitMask em, hipStream_t st) {
+    if (path == 2)
+        return em.any() ? jacobi_tiled_backward<IO, true>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace,
+                                                          gtraj, em, st)
+                        : jacobi_tiled_backward<IO, false>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace,
+                                                           nullptr, em, st);
+    const size_t PN = (size_t)(H + 2) * (W + 2);
+    float* states = static_cast<float*>(workspace);
+    float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)B * nt * PN * sizeof(float)));
+    const size_t lds = jacobi_lds(H, W, true);
+    if (em.any())
+        hipLaunchKernelGGL((jacobi_bwd_kernel<IO, true>), dim3(B), dim3(256), lds, st, (const IO*)u, (const IO*)gout, a_row,
+                           b_col, (IO*)gu, states, part, H, W, nt, (const IO*)gtraj, em);
+    else
+        hipLaunchKernelGGL((jacobi_bwd_kernel<IO, false>), dim3(B), dim3(256), lds, st, (const IO*)u, (const IO*)gout, a_row,
+                           b_col, (IO*)gu, states, part, H, W, nt, (const IO*)nullptr, em);
+    hipLaunchKernelGGL(jacobi_pgrad_kernel, dim3((H + W + 63) / 64), dim3(64), 0, st, part, g_a_row, g_b_col, B, H, W);
+    return check_launch();
+}
+
+extern "C" {
+
 int pde_jacobi_io_backward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u, const void* gout,
                            const float* a_row, const float* b_col, void* gu, float* g_a_row, float* g_b_col,
                            void* workspace, size_t workspace_bytes, void* stream) {
+    return pde_jacobi_io_backward_states(B, H, W, nt, io_dtype, u, gout, nullptr, nullptr, a_row, b_col, gu, g_a_row, g_b_col,
+                                         workspace, workspace_bytes, stream);
+}
+
+int pde_jacobi_io_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u,
+                                  const void* gout, const void* gstates, const uint64_t emit_mask[2], const float* a_row,
+                                  const float* b_col, void* gu, float* g_a_row, float* g_b_col, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
     const int path = jacobi_path(H, W);
     if (B <= 0 || path == 0 || nt < 0 || !u || !gout || !a_row || !b_col || !gu || !g_a_row || !g_b_col || !workspace)
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, nt, gstates, em);
+    if (erc != PDE_OK) return erc;
     if (workspace_bytes < pde_jacobi_backward_workspace_bytes(B, H, W, nt)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (path == 2) {
         if (!jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
         if ((uintptr_t)workspace & 3) return PDE_E_WORKSPACE;
-        if (io_dtype == PDE_IO_F32)
-            return jacobi_tiled_backward<float>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, st);
-        if (io_dtype == PDE_IO_BF16)
-            return jacobi_tiled_backward<bf16e>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, st);
-        return jacobi_tiled_backward<f16e>(B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, st);
     }
-    const size_t PN = (size_t)(H + 2) * (W + 2);
-    float* states = static_cast<float*>(workspace);
-    float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256((size_t)B * nt * PN * sizeof(float)));
-    const size_t lds = jacobi_lds(H, W, true);
     if (io_dtype == PDE_IO_F32)
-        hipLaunchKernelGGL(jacobi_bwd_kernel<float>, dim3(B), dim3(256), lds, st, (const float*)u, (const float*)gout, a_row,
-                           b_col, (float*)gu, states, part, H, W, nt);
-    else if (io_dtype == PDE_IO_BF16)
-        hipLaunchKernelGGL(jacobi_bwd_kernel<bf16e>, dim3(B), dim3(256), lds, st, (const bf16e*)u, (const bf16e*)gout, a_row,
-                           b_col, (bf16e*)gu, states, part, H, W, nt);
-    else
-        hipLaunchKernelGGL(jacobi_bwd_kernel<f16e>, dim3(B), dim3(256), lds, st, (const f16e*)u, (const f16e*)gout, a_row,
-                           b_col, (f16e*)gu, states, part, H, W, nt);
-    hipLaunchKernelGGL(jacobi_pgrad_kernel, dim3((H + W + 63) / 64), dim3(64), 0, st, part, g_a_row, g_b_col, B, H, W);
-    return check_launch();
+        return jacobi_backward_io<float>(path, B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, gstates, em, st);
+    if (io_dtype == PDE_IO_BF16)
+        return jacobi_backward_io<bf16e>(path, B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, gstates, em, st);
+    return jacobi_backward_io<f16e>(path, B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, gstates, em, st);
 }
 
 }  // extern "C"

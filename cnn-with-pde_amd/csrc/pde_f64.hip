@@ -2,7 +2,9 @@
 // the SVHN skip blend (SVHN.py:73-74), the explicit 5-point layer (tiny_imagenet.py:34-72) and the Jacobi layer
 // (emotion_recognition.py:82-97).  Plain double arithmetic (v_fma_f64 and friends), one simple kernel per pass; every sum
 // that feeds a parameter gradient runs in a fixed order, so two calls give the same bits.  The implicit sweeps themselves
-// are the any-size family of pde_adi_gen.hip instantiated for double.
+// are the any-size family of pde_adi_gen.hip instantiated for double.  The explicit and the Jacobi kernels have an emitting
+// variant each (template flag EMIT: pde_explicit5_f64_*_states, pde_jacobi_f64_*_states — the trajectory, as in
+// pde_explicit.hip); the plain entry points are those calls with a NULL mask and run the plain instantiations.
 #include "pde_common.h"
 
 namespace pde {
@@ -130,10 +132,12 @@ __global__ __launch_bounds__(256) void blend64_reduce_kernel(int nparts, const d
 // v = s_c u;  out = u + relax*((v + a_c dt Lap0(v)) - u),  a_c = clamp(alpha_base_c, eps, max_coeff)
 __device__ __forceinline__ double clamp64(double a, double lo, double hi) { return fmin(fmax(a, lo), hi); }
 
+// EMIT: the step's output goes to `emit` (a slot of the trajectory tensor) too
+template <bool EMIT = false>
 __global__ __launch_bounds__(256) void expl64_fwd_kernel(int C, int H, int W, const double* __restrict__ x,
                                                          const double* __restrict__ ab, const double* __restrict__ sc,
                                                          double dt, double eps, double maxc, double relax,
-                                                         double* __restrict__ out) {
+                                                         double* __restrict__ out, double* __restrict__ emit) {
     const int HW = H * W, p = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
     if (p >= HW) return;
     const int i = p / W, j = p % W;
@@ -144,16 +148,20 @@ __global__ __launch_bounds__(256) void expl64_fwd_kernel(int C, int H, int W, co
     const double lf = j > 0 ? s * xp[p - 1] : 0.0, rt = j + 1 < W ? s * xp[p + 1] : 0.0;
     const double lap = (((up + dn) + lf) + rt) - 4.0 * v;
     const double nw = v + k * lap;
-    out[((size_t)b * C + c) * HW + p] = xp[p] + relax * (nw - xp[p]);
+    const double o = xp[p] + relax * (nw - xp[p]);
+    out[((size_t)b * C + c) * HW + p] = o;
+    if constexpr (EMIT) emit[((size_t)b * C + c) * HW + p] = o;
 }
 
 // adjoint of one step for plane (b, c): gx = (1-relax) g + s (r + k Lap0(r)), r = relax g; partial sums of the two
 // parameter gradients, added to part[b][c][0..1] (the steps in reverse order: a fixed order)
+// EMIT: gx, the adjoint of an emitted state, gets += ginj (that state's upstream gradient)
+template <bool EMIT = false>
 __global__ __launch_bounds__(256) void expl64_bwd_kernel(int C, int H, int W, const double* __restrict__ x,
                                                          const double* __restrict__ g, const double* __restrict__ ab,
                                                          const double* __restrict__ sc, double dt, double eps, double maxc,
                                                          double relax, double* __restrict__ gx, double* __restrict__ part,
-                                                         int accumulate) {
+                                                         int accumulate, const double* __restrict__ ginj) {
     __shared__ double red[256];
     const int HW = H * W, c = blockIdx.x % C, b = blockIdx.x / C;
     const size_t off = ((size_t)b * C + c) * HW;
@@ -171,7 +179,9 @@ __global__ __launch_bounds__(256) void expl64_bwd_kernel(int C, int H, int W, co
         const double up = i > 0 ? s * xp[p - W] : 0.0, dn = i + 1 < H ? s * xp[p + W] : 0.0;
         const double lf = j > 0 ? s * xp[p - 1] : 0.0, rt = j + 1 < W ? s * xp[p + 1] : 0.0;
         const double lap = (((up + dn) + lf) + rt) - 4.0 * v;
-        gx[off + p] = (1.0 - relax) * gp[p] + s * gv;
+        double o = (1.0 - relax) * gp[p] + s * gv;
+        if constexpr (EMIT) o += ginj[off + p];
+        gx[off + p] = o;
         acc_s = fma(gv, xp[p], acc_s);
         acc_k = fma(r, lap, acc_k);
     }
@@ -202,9 +212,12 @@ __global__ void expl64_reduce_kernel(int B, int C, const double* __restrict__ pa
 // replaced by inner + a_i d1 + b_j d2.  states: nullptr | nt padded planes per sample (P_0 .. P_{nt-1}, the backward's)
 __device__ __forceinline__ int refl(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
+// EMIT: the interior of the state after every step of `em` also goes to traj[slot][B][H][W]
+template <bool EMIT = false>
 __global__ __launch_bounds__(256) void jac64_fwd_kernel(int H, int W, int nt, const double* __restrict__ u,
                                                         const double* __restrict__ a, const double* __restrict__ bc,
-                                                        double* __restrict__ out, double* __restrict__ states) {
+                                                        double* __restrict__ out, double* __restrict__ states,
+                                                        double* __restrict__ traj, EmitMask em) {
     extern __shared__ double jsm[];
     const int Hp = H + 2, Wp = W + 2, PP = Hp * Wp, b = blockIdx.x;
     double* P = jsm;
@@ -229,16 +242,26 @@ __global__ __launch_bounds__(256) void jac64_fwd_kernel(int H, int W, int nt, co
         }
         __syncthreads();
         double* t = P; P = Q; Q = t;        // the ring is the same in both
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, k + 1);
+            if (slot >= 0) {
+                double* tb = traj + ((size_t)slot * gridDim.x + b) * H * W;
+                for (int e = threadIdx.x; e < H * W; e += blockDim.x) tb[e] = P[(e / W + 1) * Wp + e % W + 1];
+            }
+        }
     }
     for (int e = threadIdx.x; e < H * W; e += blockDim.x) out[(size_t)b * H * W + e] = P[(e / W + 1) * Wp + e % W + 1];
 }
 
 // adjoint, one workgroup per sample: G over the padded plane (ring entries accumulate, interior entries are replaced);
 // per-sample partial sums of the coefficient gradients: threads < H own a row, threads 64..64+W-1 a column
+// EMIT: once G is the adjoint of an emitted state its interior gets += gtraj[slot]
+template <bool EMIT = false>
 __global__ __launch_bounds__(256) void jac64_bwd_kernel(int H, int W, int nt, const double* __restrict__ gout,
                                                         const double* __restrict__ a, const double* __restrict__ bc,
                                                         const double* __restrict__ states, double* __restrict__ gu,
-                                                        double* __restrict__ pa, double* __restrict__ pb) {
+                                                        double* __restrict__ pa, double* __restrict__ pb,
+                                                        const double* __restrict__ gtraj, EmitMask em) {
     extern __shared__ double jsm[];
     const int Hp = H + 2, Wp = W + 2, PP = Hp * Wp, b = blockIdx.x, tid = threadIdx.x;
     double* G = jsm;
@@ -264,6 +287,11 @@ __global__ __launch_bounds__(256) void jac64_bwd_kernel(int H, int W, int nt, co
                 acc = fma(G[q], (P[q + 1] - 2.0 * P[q]) + P[q - 1], acc);
             }
         }
+        const double* gt = nullptr;                           // dL/d(state after step k), where that state was emitted
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, k);
+            if (slot >= 0) gt = gtraj + ((size_t)slot * gridDim.x + b) * H * W;
+        }
         for (int e = tid; e < PP; e += blockDim.x) {
             const int i = e / Wp, j = e % Wp;
             const bool inner = i >= 1 && i <= H && j >= 1 && j <= W;
@@ -272,6 +300,9 @@ __global__ __launch_bounds__(256) void jac64_bwd_kernel(int H, int W, int nt, co
             if (i + 1 >= 1 && i + 1 <= H && j >= 1 && j <= W) v += a[i] * G[e + Wp];
             if (j - 1 >= 1 && j - 1 <= W && i >= 1 && i <= H) v += bc[j - 2] * G[e - 1];
             if (j + 1 >= 1 && j + 1 <= W && i >= 1 && i <= H) v += bc[j] * G[e + 1];
+            if constexpr (EMIT) {
+                if (gt && inner) v += gt[(i - 1) * W + (j - 1)];
+            }
             G2[e] = v;
         }
         __syncthreads();
@@ -387,18 +418,34 @@ int pde_skip_blend_f64_backward(int64_t n, const double* g, const double* u0, co
 int pde_explicit5_f64_forward(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* alpha_base,
                               const double* channel_scaling, double dt, double eps, double max_coeff, double relax,
                               int32_t num_steps, double* states, double* out, void* stream) {
+    return pde_explicit5_f64_forward_states(B, C, H, W, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, num_steps,
+                                            states, out, nullptr, nullptr, stream);
+}
+
+int pde_explicit5_f64_forward_states(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* alpha_base,
+                                     const double* channel_scaling, double dt, double eps, double max_coeff, double relax,
+                                     int32_t num_steps, double* states, double* out, double* traj,
+                                     const uint64_t emit_mask[2], void* stream) {
     if (B <= 0 || B > 65535 || C <= 0 || C > 65535 || H <= 0 || W <= 0 || num_steps < 1 || !u || !alpha_base ||
         !channel_scaling || !out ||
         (num_steps > 1 && !states))
         return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, num_steps, traj, em);
+    if (erc != PDE_OK) return erc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t n = (size_t)B * C * H * W;
     const dim3 grid((H * W + 255) / 256, C, B);
     for (int k = 0; k < num_steps; ++k) {
         const double* x = k == 0 ? u : states + (k - 1) * n;
         double* y = k == num_steps - 1 ? out : states + k * n;
-        hipLaunchKernelGGL(expl64_fwd_kernel, grid, dim3(256), 0, st, C, H, W, x, alpha_base, channel_scaling, dt, eps,
-                           max_coeff, relax, y);
+        const int slot = emit_slot(em, k + 1);
+        if (slot >= 0)
+            hipLaunchKernelGGL(expl64_fwd_kernel<true>, grid, dim3(256), 0, st, C, H, W, x, alpha_base, channel_scaling, dt,
+                               eps, max_coeff, relax, y, traj + (size_t)slot * n);
+        else
+            hipLaunchKernelGGL(expl64_fwd_kernel<false>, grid, dim3(256), 0, st, C, H, W, x, alpha_base, channel_scaling, dt,
+                               eps, max_coeff, relax, y, (double*)nullptr);
     }
     return check_launch();
 }
@@ -414,9 +461,22 @@ int pde_explicit5_f64_backward(int32_t B, int32_t C, int32_t H, int32_t W, const
                                double eps, double max_coeff, double relax, int32_t num_steps, double* gu,
                                double* g_alpha_base, double* g_channel_scaling, void* workspace, size_t workspace_bytes,
                                void* stream) {
+    return pde_explicit5_f64_backward_states(B, C, H, W, u, states, gout, nullptr, nullptr, alpha_base, channel_scaling, dt,
+                                             eps, max_coeff, relax, num_steps, gu, g_alpha_base, g_channel_scaling, workspace,
+                                             workspace_bytes, stream);
+}
+
+int pde_explicit5_f64_backward_states(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* states,
+                                      const double* gout, const double* gtraj, const uint64_t emit_mask[2],
+                                      const double* alpha_base, const double* channel_scaling, double dt, double eps,
+                                      double max_coeff, double relax, int32_t num_steps, double* gu, double* g_alpha_base,
+                                      double* g_channel_scaling, void* workspace, size_t workspace_bytes, void* stream) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !gout || !alpha_base || !channel_scaling || !gu ||
         !g_alpha_base || !g_channel_scaling || !workspace || (num_steps > 1 && !states))
         return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, num_steps, gtraj, em);
+    if (erc != PDE_OK) return erc;
     if (workspace_bytes < pde_explicit5_f64_backward_workspace_bytes(B, C, H, W, num_steps) || ((uintptr_t)workspace & 15))
         return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -429,8 +489,15 @@ int pde_explicit5_f64_backward(int32_t B, int32_t C, int32_t H, int32_t W, const
     for (int k = num_steps - 1; k >= 0; --k) {
         const double* x = k == 0 ? u : states + (size_t)(k - 1) * n;
         double* gx = k == 0 ? gu : buf[k & 1];
-        hipLaunchKernelGGL(expl64_bwd_kernel, dim3(B * C), dim3(256), 0, st, C, H, W, x, g, alpha_base, channel_scaling, dt,
-                           eps, max_coeff, relax, gx, part, (int)(k != num_steps - 1));
+        const int slot = emit_slot(em, k);                 // gx is the adjoint of the state after step k
+        if (slot >= 0)
+            hipLaunchKernelGGL(expl64_bwd_kernel<true>, dim3(B * C), dim3(256), 0, st, C, H, W, x, g, alpha_base,
+                               channel_scaling, dt, eps, max_coeff, relax, gx, part, (int)(k != num_steps - 1),
+                               gtraj + (size_t)slot * n);
+        else
+            hipLaunchKernelGGL(expl64_bwd_kernel<false>, dim3(B * C), dim3(256), 0, st, C, H, W, x, g, alpha_base,
+                               channel_scaling, dt, eps, max_coeff, relax, gx, part, (int)(k != num_steps - 1),
+                               (const double*)nullptr);
         g = gx;
     }
     hipLaunchKernelGGL(expl64_reduce_kernel, dim3((C + 63) / 64), dim3(64), 0, st, B, C, part, alpha_base, dt, eps, max_coeff,
@@ -440,12 +507,28 @@ int pde_explicit5_f64_backward(int32_t B, int32_t C, int32_t H, int32_t W, const
 
 int pde_jacobi_f64_forward(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* a_row,
                            const double* b_col, double* out, void* stream) {
+    return pde_jacobi_f64_forward_states(B, H, W, nt, u, a_row, b_col, out, nullptr, nullptr, stream);
+}
+
+int pde_jacobi_f64_forward_states(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* a_row,
+                                  const double* b_col, double* out, double* states, const uint64_t emit_mask[2],
+                                  void* stream) {
     if (!jac64_ok(B, H, W, nt) || !u || !a_row || !b_col || !out) return PDE_E_BADARG;
-    static unsigned long long done = 0;
-    int rc = ensure_dynamic_lds((const void*)jac64_fwd_kernel, (int)jac64_lds(kJacMax, kJacMax), done);
+    EmitMask em;
+    int rc = emit_check(emit_mask, nt, states, em);
     if (rc != PDE_OK) return rc;
-    hipLaunchKernelGGL(jac64_fwd_kernel, dim3(B), dim3(256), jac64_lds(H, W), static_cast<hipStream_t>(stream), H, W, nt, u,
-                       a_row, b_col, out, (double*)nullptr);
+    static unsigned long long done = 0, done_e = 0;
+    if (em.any()) {
+        rc = ensure_dynamic_lds((const void*)jac64_fwd_kernel<true>, (int)jac64_lds(kJacMax, kJacMax), done_e);
+        if (rc != PDE_OK) return rc;
+        hipLaunchKernelGGL(jac64_fwd_kernel<true>, dim3(B), dim3(256), jac64_lds(H, W), static_cast<hipStream_t>(stream), H, W,
+                           nt, u, a_row, b_col, out, (double*)nullptr, states, em);
+        return check_launch();
+    }
+    rc = ensure_dynamic_lds((const void*)jac64_fwd_kernel<false>, (int)jac64_lds(kJacMax, kJacMax), done);
+    if (rc != PDE_OK) return rc;
+    hipLaunchKernelGGL(jac64_fwd_kernel<false>, dim3(B), dim3(256), jac64_lds(H, W), static_cast<hipStream_t>(stream), H, W, nt,
+                       u, a_row, b_col, out, (double*)nullptr, (double*)nullptr, em);
     return check_launch();
 }
 
@@ -458,14 +541,26 @@ size_t pde_jacobi_f64_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, 
 int pde_jacobi_f64_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* gout,
                             const double* a_row, const double* b_col, double* gu, double* g_a_row, double* g_b_col,
                             void* workspace, size_t workspace_bytes, void* stream) {
+    return pde_jacobi_f64_backward_states(B, H, W, nt, u, gout, nullptr, nullptr, a_row, b_col, gu, g_a_row, g_b_col, workspace,
+                                          workspace_bytes, stream);
+}
+
+int pde_jacobi_f64_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* gout,
+                                   const double* gstates, const uint64_t emit_mask[2], const double* a_row,
+                                   const double* b_col, double* gu, double* g_a_row, double* g_b_col, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
     if (!jac64_ok(B, H, W, nt) || !u || !gout || !a_row || !b_col || !gu || !g_a_row || !g_b_col || !workspace)
         return PDE_E_BADARG;
+    EmitMask em;
+    int rc = emit_check(emit_mask, nt, gstates, em);
+    if (rc != PDE_OK) return rc;
     if (workspace_bytes < pde_jacobi_f64_backward_workspace_bytes(B, H, W, nt) || ((uintptr_t)workspace & 15))
         return PDE_E_WORKSPACE;
-    static unsigned long long done_f = 0, done_b = 0;
-    int rc = ensure_dynamic_lds((const void*)jac64_fwd_kernel, (int)jac64_lds(kJacMax, kJacMax), done_f);
+    static unsigned long long done_f = 0, done_b = 0, done_e = 0;
+    rc = ensure_dynamic_lds((const void*)jac64_fwd_kernel<false>, (int)jac64_lds(kJacMax, kJacMax), done_f);
     if (rc != PDE_OK) return rc;
-    rc = ensure_dynamic_lds((const void*)jac64_bwd_kernel, (int)jac64_lds(kJacMax, kJacMax), done_b);
+    rc = em.any() ? ensure_dynamic_lds((const void*)jac64_bwd_kernel<true>, (int)jac64_lds(kJacMax, kJacMax), done_e)
+                  : ensure_dynamic_lds((const void*)jac64_bwd_kernel<false>, (int)jac64_lds(kJacMax, kJacMax), done_b);
     if (rc != PDE_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
@@ -475,9 +570,14 @@ int pde_jacobi_f64_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const d
     double* pb = pa + (size_t)B * H;
     ws += up256((size_t)B * (H + W) * sizeof(double));
     double* scratch = reinterpret_cast<double*>(ws);          // the forward's output, not needed
-    hipLaunchKernelGGL(jac64_fwd_kernel, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, u, a_row, b_col, scratch, states);
-    hipLaunchKernelGGL(jac64_bwd_kernel, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, gout, a_row, b_col, states, gu,
-                       pa, pb);
+    hipLaunchKernelGGL(jac64_fwd_kernel<false>, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, u, a_row, b_col, scratch,
+                       states, (double*)nullptr, EmitMask{0, 0});
+    if (em.any())
+        hipLaunchKernelGGL(jac64_bwd_kernel<true>, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, gout, a_row, b_col,
+                           states, gu, pa, pb, gstates, em);
+    else
+        hipLaunchKernelGGL(jac64_bwd_kernel<false>, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, gout, a_row, b_col,
+                           states, gu, pa, pb, (const double*)nullptr, em);
     hipLaunchKernelGGL(jac64_reduce_kernel, dim3((H + W + 127) / 128), dim3(128), 0, st, B, H, W, pa, pb, g_a_row, g_b_col);
     return check_launch();
 }

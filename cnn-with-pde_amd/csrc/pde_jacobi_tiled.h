@@ -23,6 +23,10 @@
 // fold      gu = interior of G_0 + the ring folded back onto rows / columns 1 and H-2 / W-2 (a pass of its own: the
 //           ring cell and the row it folds onto can lie in different tiles, e.g. H = 65).
 // pgrad     g_a_row / g_b_col = sum of the tiles' slots over samples and tiles, in a fixed order.  No float atomics.
+// trajectory (EMIT variants, pde_jacobi_io_*_states): the forward writes the tile's own cells of an emitted state to
+//           traj[slot] in the tensors' type right after the step, where `park` writes; the adjoint adds gtraj[slot(n)] to
+//           G_n as it computes it, on every interior cell of the region still valid at that step (ring cells get nothing),
+//           so tiles agree on their shared halo cells exactly as they do without it and no launch is cut.
 
 constexpr int kJT = 64;                     // tile edge, interior cells
 constexpr int kJK = PDE_JACOBI_TILED_K;     // time steps per launch
@@ -47,12 +51,14 @@ __device__ __forceinline__ JSpan jspan(int t, int nT, int n, int halo) {
     return s;
 }
 
-template <typename IO>
+// (EMIT: n0 = the time steps taken before this launch; traj_stride = B*H*W)
+template <typename IO, bool EMIT = false>
 __global__ __launch_bounds__(256) void jacobi_tiled_fwd_kernel(const IO* __restrict__ u, const float* __restrict__ fsrc,
                                                                const float* __restrict__ a_row,
                                                                const float* __restrict__ b_col, void* __restrict__ dst,
                                                                int dst_f32, float* __restrict__ park, size_t park_stride,
-                                                               int H, int W, int nTy, int nTx, int k) {
+                                                               int H, int W, int nTy, int nTx, int k,
+                                                               IO* __restrict__ traj, size_t traj_stride, EmitMask em, int n0) {
     __shared__ float sm[kJFwdFloats];
     float* P = sm;
     float* Q = sm + kJR * kJS;
@@ -111,6 +117,15 @@ __global__ __launch_bounds__(256) void jacobi_tiled_fwd_kernel(const IO* __restr
                 for (int j = oj0 + tx; j < oj1; j += 32)
                     pk[(size_t)(i - 1) * W + (j - 1)] = P[(i - rs.lo) * kJS + (j - cs.lo)];
         }
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, n0 + st);
+            if (slot >= 0) {
+                IO* tp = traj + (size_t)slot * traj_stride + s * plane;
+                for (int i = oi0 + ty; i < oi1; i += 8)
+                    for (int j = oj0 + tx; j < oj1; j += 32)
+                        S1<IO>::st(tp + (size_t)(i - 1) * W + (j - 1), P[(i - rs.lo) * kJS + (j - cs.lo)]);
+            }
+        }
     }
     if (!dst) return;
     for (int i = oi0 + ty; i < oi1; i += 8)
@@ -123,13 +138,14 @@ __global__ __launch_bounds__(256) void jacobi_tiled_fwd_kernel(const IO* __restr
 }
 
 // states: slot n-1 holds P_n (n >= 1), interior only; P_0 is u.  gout != nullptr: the launch that starts from G_nt.
-template <typename IO>
+template <typename IO, bool EMIT = false>
 __global__ __launch_bounds__(256) void jacobi_tiled_bwd_kernel(const IO* __restrict__ u, const float* __restrict__ states,
                                                                size_t state_stride, const IO* __restrict__ gout,
                                                                const float* __restrict__ gsrc, float* __restrict__ gdst,
                                                                const float* __restrict__ a_row,
                                                                const float* __restrict__ b_col, float* __restrict__ part,
-                                                               int acc, int H, int W, int nTy, int nTx, int n_hi, int k) {
+                                                               int acc, int H, int W, int nTy, int nTx, int n_hi, int k,
+                                                               const IO* __restrict__ gtraj, EmitMask em) {
     extern __shared__ float smd[];
     float* G = smd;
     float* Gn = G + kJR * kJS;
@@ -201,6 +217,11 @@ __global__ __launch_bounds__(256) void jacobi_tiled_bwd_kernel(const IO* __restr
         // dL/dP_n from dL/dP_{n+1}; ring cells (clipped sides) are cells like any other here
         const int r0 = rs.lo == 0 ? 0 : rs.lo + st, r1 = rs.hi == H + 2 ? H + 2 : rs.hi - st;
         const int c0 = cs.lo == 0 ? 0 : cs.lo + st, c1 = cs.hi == W + 2 ? W + 2 : cs.hi - st;
+        const IO* gt = nullptr;                            // dL/d(state after step n), where that state was emitted
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, n);
+            if (slot >= 0) gt = gtraj + (size_t)slot * state_stride + s * plane;
+        }
         for (int i = r0 + ty; i < r1; i += 8) {
             const bool ri = i >= 1 && i <= H;
             const bool up = i - 1 >= 1 && i - 1 <= H, dn = i + 1 >= 1 && i + 1 <= H;   // vertical neighbour is interior
@@ -219,6 +240,9 @@ __global__ __launch_bounds__(256) void jacobi_tiled_bwd_kernel(const IO* __restr
                 if (ri) {
                     if (j - 1 >= 1 && j - 1 <= W) v += sb[j - 1 - cs.lo] * g[-1];
                     if (j + 1 >= 1 && j + 1 <= W) v += sb[j + 1 - cs.lo] * g[1];
+                }
+                if constexpr (EMIT) {
+                    if (gt && ri && cj) v += S1<IO>::ld(gt + (size_t)(i - 1) * W + (j - 1));
                 }
                 qrow[j] = v;
             }

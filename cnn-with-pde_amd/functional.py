@@ -17,7 +17,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small", "adi_diffuse_small_states", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse",
+__all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small", "adi_diffuse_small_states", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse", "explicit5_states", "jacobi_diffuse_states",
            "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
            "sym_layer_f16_supported", "sym_layer_bf16_supported", "sym_k16"]
 
@@ -1855,6 +1855,207 @@ def jacobi_diffuse(u, a_row, b_col, nt: int):
     if _is_f64(u, a_row, b_col):
         return _JacobiF64Fn.apply(u, a_row, b_col, int(nt))
     return _JacobiFn.apply(_io_in(u, a_row, b_col), a_row, b_col, int(nt))
+
+
+# --------------------------------------------------------------------------- trajectories of the explicit layers
+MAX_EMIT_STEPS = 128        # the emission mask of the C ABI is 128 bits
+
+
+def check_steps(steps, last: int, what: str = "steps"):
+    """The step selection of every ``trajectory`` / ``*_states`` call: None (every step of 1..last) or whole, strictly
+    increasing 1-based step numbers within 1..last (None: no upper end).  Returns them as a list; ValueError otherwise."""
+    if steps is None:
+        if last is None:
+            raise ValueError(f"{what} must be a sequence of step numbers")
+        sel = list(range(1, int(last) + 1))
+    else:
+        try:
+            raw = list(steps)
+            sel = [int(k) for k in raw]
+            exact = all(float(k) == int(k) for k in raw)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be None or a sequence of step numbers, got {steps!r}") from None
+        if not exact:
+            raise ValueError(f"{what} must be whole step numbers, got {steps!r}")
+    if not sel or sel[0] < 1 or (last is not None and sel[-1] > last) or any(b <= a for a, b in zip(sel, sel[1:])):
+        end = "" if last is None else f" in 1..{last}"
+        raise ValueError(f"{what} must be strictly increasing step numbers{end}, got {steps!r}")
+    return sel
+
+
+def _emit_steps(steps):
+    """(steps as a tuple, the C ABI's emission mask without the last step) of a ``*_states`` call."""
+    sel = tuple(check_steps(steps, None))
+    if sel[-1] > MAX_EMIT_STEPS:
+        raise ValueError(f"a trajectory call takes at most {MAX_EMIT_STEPS} time steps, got {sel[-1]}")
+    return sel, sum(1 << (k - 1) for k in sel[:-1])
+
+
+def _emit_mask(bits: int):
+    return (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+
+
+class _JacobiStatesFn(torch.autograd.Function):
+    """``_JacobiFn`` / ``_JacobiF64Fn`` that also return the state after chosen time steps, out of the plain call's launches
+    (pde_jacobi_io_*_states, pde_jacobi_f64_*_states).  The result is ONE tensor (K', B, H, W); the library's ``out`` is
+    its last slice."""
+
+    @staticmethod
+    def forward(ctx, u, a_row, b_col, steps, bits, f64):
+        lib = L.load()
+        _require_cuda(u, a_row, b_col)
+        nt, K = steps[-1], len(steps)
+        if f64:
+            u = u.to(torch.float64).contiguous()
+            a, b = _d64(a_row), _d64(b_col)
+        else:
+            u = (u if u.dtype == torch.float16 else u.float()).contiguous()
+            a = a_row.detach().float().contiguous()
+            b = b_col.detach().float().contiguous()
+        B, H, W = u.shape
+        out = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
+        with torch.cuda.device(u.device):
+            if f64:
+                L.check(lib.pde_jacobi_f64_forward_states(B, H, W, nt, _ptr(u), _ptr(a), _ptr(b), _ptr(out[K - 1]), _ptr(out),
+                                                          _emit_mask(bits), _stream()), "pde_jacobi_f64_forward_states")
+            else:
+                # a tiled plane with more steps than one launch takes: the launches chain through a workspace
+                fws = lib.pde_jacobi_forward_workspace_bytes(B, H, W, nt)
+                ws = _workspace(fws, u.device) if fws else None
+                L.check(lib.pde_jacobi_io_forward_states(B, H, W, nt, _io_dtype(u), _ptr(u), _ptr(a), _ptr(b), _ptr(out[K - 1]),
+                                                         _ptr(out), _emit_mask(bits), _ptr(ws), ws.numel() if fws else 0,
+                                                         _stream()), "pde_jacobi_io_forward_states")
+        ctx.save_for_backward(u, a, b)
+        ctx.cfg = (nt, K, bits, f64)
+        ctx.p_dtypes = (a_row.dtype, b_col.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        u, a, b = ctx.saved_tensors
+        nt, K, bits, f64 = ctx.cfg
+        B, H, W = u.shape
+        g = g.to(u.dtype).contiguous()                   # slots 0..K-2 are gstates, the last slice is gout
+        gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
+        with torch.cuda.device(u.device):
+            if f64:
+                ws = _workspace(lib.pde_jacobi_f64_backward_workspace_bytes(B, H, W, nt), u.device)
+                L.check(lib.pde_jacobi_f64_backward_states(B, H, W, nt, _ptr(u), _ptr(g[K - 1]), _ptr(g), _emit_mask(bits),
+                                                           _ptr(a), _ptr(b), _ptr(gu), _ptr(ga), _ptr(gb), _ptr(ws), ws.numel(),
+                                                           _stream()), "pde_jacobi_f64_backward_states")
+            else:
+                io = _io_dtype(u)
+                ws = _workspace(lib.pde_jacobi_io_backward_workspace_bytes(B, H, W, nt, io), u.device)
+                L.check(lib.pde_jacobi_io_backward_states(B, H, W, nt, io, _ptr(u), _ptr(g[K - 1]), _ptr(g), _emit_mask(bits),
+                                                          _ptr(a), _ptr(b), _ptr(gu), _ptr(ga), _ptr(gb), _ptr(ws), ws.numel(),
+                                                          _stream()), "pde_jacobi_io_backward_states")
+        return gu, ga.to(ctx.p_dtypes[0]), gb.to(ctx.p_dtypes[1]), None, None, None
+
+
+def jacobi_diffuse_states(u, a_row, b_col, steps):
+    """``jacobi_diffuse`` that returns the trajectory: the state after every time step listed in ``steps`` (strictly
+    increasing 1-based step numbers; ``max(steps)`` steps are run, at most 128) as ONE tensor ``(len(steps),) + u.shape``,
+    out of the launches the plain call of ``max(steps)`` steps makes.  Slice ``i`` is bit for bit
+    ``jacobi_diffuse(u, a_row, b_col, steps[i])`` — the reflect-padded ring keeps the input's values over the whole time
+    loop, which chained one-step calls would not; with fp16 tensors it is the fp32 state rounded once while the time loop
+    goes on unrounded.  Differentiable in ``u`` and both coefficient vectors for a loss on any of the returned states.
+    fp32, the float16 route and float64 by the rules of ``jacobi_diffuse``."""
+    sel, bits = _emit_steps(steps)
+    if u.dim() != 3:
+        raise L.PdeError(f"expected (B,H,W), got {tuple(u.shape)}")
+    if u.shape[0] == 0:
+        return torch.stack([_empty_passthrough(u, a_row, b_col)] * len(sel))
+    f64 = _is_f64(u, a_row, b_col)
+    if not f64:
+        u = _io_in(u, a_row, b_col)
+    return _JacobiStatesFn.apply(u, a_row, b_col, sel, bits, f64)
+
+
+class _Explicit5StatesFn(torch.autograd.Function):
+    """``_Explicit5Fn`` / ``_Explicit5F64Fn`` that also return the state after chosen steps, out of the plain call's
+    launches (pde_explicit5_*_states, pde_explicit5_f64_*_states).  The result is ONE tensor (K', B, C, H, W); the
+    library's ``out`` is its last slice."""
+
+    @staticmethod
+    def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, steps, bits, f64):
+        lib = L.load()
+        _require_cuda(u, alpha_base, channel_scaling)
+        num_steps, K = steps[-1], len(steps)
+        need_grad = any(ctx.needs_input_grad[:3])
+        if f64:
+            u = u.to(torch.float64).contiguous()
+            a, s = _d64(alpha_base), _d64(channel_scaling)
+            fused = False
+        else:
+            if u.dtype not in _IO_TYPES:
+                u = u.float()
+            u = u.contiguous()
+            a = alpha_base.detach().to(torch.float32).contiguous()
+            s = channel_scaling.detach().to(torch.float32).contiguous()
+            fused = tuple(u.shape[2:]) in ((64, 64), (32, 32), (16, 16))
+        B, Cc, H, W = u.shape
+        out = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
+        # the inputs of steps 2..num_steps, as the plain call keeps them (fp32, or doubles): what the backward reads
+        states = torch.empty((num_steps - 1,) + tuple(u.shape), dtype=torch.float64 if f64 else torch.float32,
+                             device=u.device) if num_steps > 1 and (need_grad or not fused) else None
+        with torch.cuda.device(u.device):
+            if f64:
+                L.check(lib.pde_explicit5_f64_forward_states(B, Cc, H, W, _ptr(u), _ptr(a), _ptr(s), dt, eps, max_coeff, relax,
+                                                             num_steps, _ptr(states), _ptr(out[K - 1]), _ptr(out),
+                                                             _emit_mask(bits), _stream()), "pde_explicit5_f64_forward_states")
+            else:
+                L.check(lib.pde_explicit5_forward_states(B, Cc, H, W, _io_dtype(u), _ptr(u), _ptr(a), _ptr(s), dt, eps,
+                                                         max_coeff, relax, num_steps, _ptr(states), _ptr(out[K - 1]),
+                                                         _ptr(out), _emit_mask(bits), _stream()),
+                        "pde_explicit5_forward_states")
+        ctx.save_for_backward(u, states if need_grad else None, a, s)
+        ctx.cfg = (dt, eps, max_coeff, relax, num_steps, K, bits, f64)
+        ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        u, states, a, s = ctx.saved_tensors
+        dt, eps, max_coeff, relax, num_steps, K, bits, f64 = ctx.cfg
+        B, Cc, H, W = u.shape
+        g = g.to(u.dtype).contiguous()                   # slots 0..K-2 are gtraj, the last slice is gout
+        gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
+        with torch.cuda.device(u.device):
+            if f64:
+                ws = _workspace(lib.pde_explicit5_f64_backward_workspace_bytes(B, Cc, H, W, num_steps), u.device)
+                L.check(lib.pde_explicit5_f64_backward_states(B, Cc, H, W, _ptr(u), _ptr(states), _ptr(g[K - 1]), _ptr(g),
+                                                              _emit_mask(bits), _ptr(a), _ptr(s), dt, eps, max_coeff, relax,
+                                                              num_steps, _ptr(gu), _ptr(ga), _ptr(gs), _ptr(ws), ws.numel(),
+                                                              _stream()), "pde_explicit5_f64_backward_states")
+            else:
+                io = _io_dtype(u)
+                ws = _workspace(lib.pde_explicit5_backward_workspace_bytes(B, Cc, H, W, io, num_steps), u.device)
+                L.check(lib.pde_explicit5_backward_states(B, Cc, H, W, io, _ptr(u), _ptr(states), _ptr(g[K - 1]), _ptr(g),
+                                                          _emit_mask(bits), _ptr(a), _ptr(s), dt, eps, max_coeff, relax,
+                                                          num_steps, _ptr(gu), _ptr(ga), _ptr(gs), _ptr(ws), ws.numel(),
+                                                          _stream()), "pde_explicit5_backward_states")
+        return gu, ga.to(ctx.p_dtypes[0]), gs.to(ctx.p_dtypes[1]), None, None, None, None, None, None, None
+
+
+def explicit5_states(u, alpha_base, channel_scaling, dt=0.01, eps=1e-6, max_coeff=0.15, relax=0.1, steps=(1,)):
+    """``explicit5_step`` that returns the trajectory: the state after every step listed in ``steps`` (strictly increasing
+    1-based step numbers; ``max(steps)`` steps are run, at most 128) as ONE tensor ``(len(steps),) + u.shape``, out of the
+    launches the plain call of ``max(steps)`` steps makes (one for 64x64, 32x32 and 16x16 planes).  Slice ``i`` is bit for
+    bit ``explicit5_step(..., num_steps=steps[i])``; with 16-bit tensors it is the fp32 state rounded once while the time
+    loop goes on unrounded.  Differentiable in ``u``, ``alpha_base`` and ``channel_scaling`` for a loss on any of the
+    returned states.  fp32, bf16, the float16 route and float64 by the rules of ``explicit5_step``."""
+    sel, bits = _emit_steps(steps)
+    if u.dim() != 4:
+        raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
+    if u.shape[0] == 0:
+        return torch.stack([_empty_passthrough(u, alpha_base, channel_scaling)] * len(sel))
+    f64 = _is_f64(u, alpha_base, channel_scaling)
+    if not f64:
+        u = _io_in(u, alpha_base, channel_scaling)
+    return _Explicit5StatesFn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
+                                    sel, bits, f64)
 
 
 # --------------------------------------------------------------------------- SVHN skip connection

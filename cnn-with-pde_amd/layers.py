@@ -240,19 +240,7 @@ class _AdiBase(nn.Module):
         float64, ``small_channel_kernels = False``) runs step by step (functional.adi_diffuse_mixed_per_step): the wide
         kernels do not emit states; "lagged" plans there as "auto"."""
         K = int(self.num_steps)
-        if steps is None:
-            sel = list(range(1, K + 1))
-        else:
-            try:
-                raw = list(steps)
-                sel = [int(k) for k in raw]
-                exact = all(float(k) == int(k) for k in raw)
-            except (TypeError, ValueError):
-                raise ValueError(f"steps must be None or a sequence of step numbers, got {steps!r}") from None
-            if not exact:
-                raise ValueError(f"steps must be whole step numbers, got {steps!r}")
-        if not sel or sel[0] < 1 or sel[-1] > K or any(b <= a for a, b in zip(sel, sel[1:])):
-            raise ValueError(f"steps must be strictly increasing step numbers in 1..{K}, got {steps!r}")
+        sel = F_.check_steps(steps, K)
         if self._single_channel and (u.dim() != 4 or u.shape[1] != 1):
             raise ValueError("expected (B,1,%d,%d), got %s" % (*_plane(self.size), tuple(u.shape)))
         sched = self._schedule()
@@ -513,10 +501,13 @@ class ImprovedDiffusionLayer(nn.Module):
         self.stability_eps = 1e-6
         self.max_coeff = 0.15
 
+    #: the relaxation of tiny_imagenet.py:49
+    _relax = 0.1
+
     def forward(self, u):
         # all num_steps steps in one call (64x64 / 32x32 / 16x16 planes: one launch, the plane stays in registers)
         return F_.explicit5_step(u, self.alpha_base, self.channel_scaling, self.dt, self.stability_eps,
-                                 self.max_coeff, 0.1, self.num_steps)
+                                 self.max_coeff, self._relax, self.num_steps)
 
 
 class PDELayer(nn.Module):
@@ -553,3 +544,36 @@ class PDELayer(nn.Module):
         # coefficient vectors: alpha varies along dim 1 (rows), beta along dim 2 (columns)
         out = F_.jacobi_diffuse(u0.squeeze(1), self.alpha(self.y), self.beta(self.x), self.Nt)
         return out.unsqueeze(1)
+
+
+def layer_trajectory(layer, u, steps=None):
+    """The trajectory of any PDE layer's time loop: a tensor whose slice ``i`` is the state after time step ``steps[i]``,
+    out of the launches ``layer(u)`` makes, differentiable in ``u`` and the layer's parameters.
+
+    ``steps``: None (every step) or a strictly increasing sequence of whole 1-based step numbers within the layer's own
+    time loop (``1..num_steps``; ``1..Nt`` for ``PDELayer``), ValueError otherwise; the loop ends after ``max(steps)``.
+
+    * an implicit layer (every class with a ``trajectory`` method): ``layer.trajectory(u, steps)``, (K', B, C, H, W);
+    * ``ImprovedDiffusionLayer``: (K', B, C, H, W) from functional.explicit5_states with the layer's dt, eps, max_coeff
+      and relaxation — one launch per pass for 64x64, 32x32 and 16x16 planes, one per step otherwise;
+    * ``PDELayer``: (K', B, 1, H, W) from functional.jacobi_diffuse_states; an input that is not (B,1,H,W) is refused as
+      ``forward`` refuses it.  The plane is reflect-padded once and the ring keeps the input's values, so this is not what
+      chained one-step layers give.
+
+    For the two explicit layers at most 128 steps per call; slice ``i`` is bit for bit the output of the same layer with
+    ``num_steps`` / ``Nt`` = ``steps[i]``, so ``layer_trajectory(layer, u)[-1]`` is ``layer(u)``; inputs are routed as in
+    ``forward`` (fp32, bf16 where it takes it, ``model.half()``, float64).  The two explicit classes themselves carry no
+    ``trajectory`` method; this function is their layer-level entry, and the classes of ``compat/`` are the same classes."""
+    if isinstance(layer, ImprovedDiffusionLayer):
+        sel = F_.check_steps(steps, int(layer.num_steps))
+        return F_.explicit5_states(u, layer.alpha_base, layer.channel_scaling, layer.dt, layer.stability_eps,
+                                   layer.max_coeff, layer._relax, sel)
+    if isinstance(layer, PDELayer):
+        sel = F_.check_steps(steps, layer.Nt)
+        if u.dim() != 4 or u.shape[1] != 1:
+            raise ValueError(f"expected (B,1,H,W), got {tuple(u.shape)}")
+        out = F_.jacobi_diffuse_states(u.squeeze(1), layer.alpha(layer.y), layer.beta(layer.x), sel)
+        return out.unsqueeze(2)
+    if isinstance(layer, _AdiBase):
+        return layer.trajectory(u, steps)
+    raise TypeError(f"{type(layer).__name__} has no time loop to return the trajectory of")

@@ -502,6 +502,53 @@ int pde_jacobi_io_backward(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t 
                            void* gu, float* g_a_row, float* g_b_col,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the trajectory of the explicit layers: intermediate states of the time loop out of the plain call's launches ----
+ * pde_jacobi_io_forward_ws / pde_explicit5_forward that also return the state after chosen time steps, and the backwards
+ * that take an upstream gradient for every one of them.  The contract is that of pde_adi_forward_states, indexed by time
+ * step: emit_mask[2] is 128 bits, bit k-1 (bit (k-1)%64 of emit_mask[(k-1)/64]) set = the state after time step k is
+ * emitted, slots in the order of the set bits.  Only bits 0 .. nt-2 (num_steps-2) may be set: the state after the last
+ * step is `out` itself, and a caller that wants one stacked tensor points `out` at the slice behind the last slot.
+ * forward_states: the Jacobi calls write states[slot][B][H][W] (the interior of the padded plane), the explicit calls
+ * traj[slot][B][C][H][W] (their `states` stays the fp32 workspace of the plain call), both in io_dtype; with 16-bit
+ * tensors an emitted state is the fp32 state rounded once — the time loop goes on unrounded, so `out` and every emitted
+ * state are bit for bit what the plain call of that many steps returns.
+ * backward_states: gstates / gtraj has the layout of states / traj and holds dL/d(state); when the reverse walk holds the
+ * adjoint of the state after step k it gets += gstates[slot(k)] on the interior cells (the frozen Jacobi ring gets
+ * nothing).  Parked states, the order of the partial sums, the pgrad kernels and the fold of the reflect padding are those
+ * of the plain backward; no float atomics.
+ * Checked on the host before any launch, after the plain call's own argument checks: a non-empty mask with nt
+ * (num_steps) > 128: PDE_E_TOO_MANY_SWEEPS; a bit at or above nt-1, or states / traj / gstates / gtraj NULL with a
+ * non-empty mask: PDE_E_BADARG; then the workspace.  An empty (or NULL) mask is the plain call exactly — the same kernel
+ * instantiations, states / traj / gstates / gtraj are not read; the plain entry points are these calls with a NULL mask.
+ * Workspaces are those of the plain calls (the forward takes the workspace of pde_jacobi_io_forward_ws).
+ * Launches are the plain call's; emission and injection add global writes and reads to them, never a launch: the
+ * one-workgroup Jacobi kernels and the wave-per-plane explicit kernels (64x64, 32x32, 16x16) emit from LDS / registers
+ * after the step; the tiled Jacobi forward writes the tile's own cells after the step (ceil(nt / K) launches), its
+ * adjoint adds gstates[slot(n)] to G_n on every interior cell of the region still valid at that step, so neighbouring
+ * tiles keep agreeing on their shared halo and no launch is cut at an emitted step; the generic explicit planes run one
+ * launch per step as the plain call, the step's own launch writing traj / adding gtraj. */
+int pde_jacobi_io_forward_states(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype,
+                                 const void* u, const float* a_row, const float* b_col, void* out,
+                                 void* states, const uint64_t emit_mask[2],
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int pde_jacobi_io_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype,
+                                  const void* u, const void* gout, const void* gstates, const uint64_t emit_mask[2],
+                                  const float* a_row, const float* b_col,
+                                  void* gu, float* g_a_row, float* g_b_col,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int pde_explicit5_forward_states(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype,
+                                 const void* u, const float* alpha_base, const float* channel_scaling,
+                                 float dt, float eps, float max_coeff, float relax,
+                                 int32_t num_steps, void* states, void* out,
+                                 void* traj, const uint64_t emit_mask[2], void* stream);
+int pde_explicit5_backward_states(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype,
+                                  const void* u, const void* states, const void* gout,
+                                  const void* gtraj, const uint64_t emit_mask[2],
+                                  const float* alpha_base, const float* channel_scaling,
+                                  float dt, float eps, float max_coeff, float relax, int32_t num_steps,
+                                  void* gu, float* g_alpha_base, float* g_channel_scaling,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Ruthotto-Haber symmetric layer on the fp32 matrix cores ------------- */
 
 /* cifar_2version.py:190-220 SymmetricLayer.forward and the residual steps built on it (ParabolicBlock :223-236,
@@ -706,6 +753,27 @@ size_t pde_jacobi_f64_backward_workspace_bytes(int32_t B, int32_t H, int32_t W, 
 int pde_jacobi_f64_backward(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* gout,
                             const double* a_row, const double* b_col, double* gu, double* g_a_row, double* g_b_col,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* pde_jacobi_io_*_states / pde_explicit5_*_states in float64: states, gstates (slots, B, H, W) and traj, gtraj (slots, B,
+ * C, H, W) doubles; the same contract, checks and launches (one per step for the explicit layer, the step's own launch
+ * writing traj / adding gtraj; one forward launch, then recompute, adjoint and reduction for the Jacobi layer). */
+int pde_explicit5_f64_forward_states(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* alpha_base,
+                                     const double* channel_scaling, double dt, double eps, double max_coeff, double relax,
+                                     int32_t num_steps, double* states, double* out,
+                                     double* traj, const uint64_t emit_mask[2], void* stream);
+int pde_explicit5_f64_backward_states(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* states,
+                                      const double* gout, const double* gtraj, const uint64_t emit_mask[2],
+                                      const double* alpha_base, const double* channel_scaling,
+                                      double dt, double eps, double max_coeff, double relax, int32_t num_steps,
+                                      double* gu, double* g_alpha_base, double* g_channel_scaling,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int pde_jacobi_f64_forward_states(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* a_row,
+                                  const double* b_col, double* out, double* states, const uint64_t emit_mask[2],
+                                  void* stream);
+int pde_jacobi_f64_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* gout,
+                                   const double* gstates, const uint64_t emit_mask[2],
+                                   const double* a_row, const double* b_col, double* gu, double* g_a_row, double* g_b_col,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- K1 on rectangular planes (H != W) -------------------------------------------------------------------
  * The reference's sweep functions read B, C, H, W = u.shape and transpose for the y direction (mnist_test.py:45,72,105;
