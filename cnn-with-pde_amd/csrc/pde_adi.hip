@@ -47,6 +47,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -719,6 +720,53 @@ bool fwd_ho_eligible(const PdeAdiDesc* d) {
     return fwd_ho_enabled() && d->N == 32 && d->io_dtype == PDE_IO_F32 && split_of(d) == kSplitStrang && d->num_sweeps > kRing;
 }
 
+// The stagger of the hand-over schedule (SweepArgs::stagger, see adi_fwd_kernel): the two workgroups of a CU take turns in
+// priority, chunk by chunk, and one of them can be held back at the head.  PDE_FWD_STAGGER (read once per process):
+// 0 = off, the schedule as it was; 1 or unset = the default; for sizing: "t" = turns alone, "<n>" = the second workgroup
+// naps n times 512 cycles before its first plane loads (n < 0: the first one does), "t<n>" = both, "t/<p>" or "t<n>/<p>"
+// = the turn passes from the first workgroup to the second after p percent of their time steps.
+// Only launches that put two workgroups on every CU are staggered: on a half-empty chip there is nobody to take turns
+// with, and a hold-back would only be added to the launch.
+// The default, sized on the headline launch (512 x 64 x 32 x 32, 30 sweeps; tools/fwd_timeline.py and
+// tools/perf_fwd_stagger.py, profiles/fwd_stagger_*): the head — every workgroup loading its first chunk — takes 17 us, and
+// a hold-back of a third of it (24 naps = 12288 cycles = 5.9 us at the 2.08 GHz measured) is what pays; 48 naps and more
+// cost what they hide.  The turn passes after 30 % of the time steps: at 50 % the second workgroup still ends 21 us
+// after the first, at 25 % both end together but the first one's late steps crawl, at 10 % the launch is slower than
+// without turns.  Forward launch 161.8 -> 153.9 us (means of three alternated processes), 64.4 -> 58.5 us at two time steps.
+constexpr int kFwdStaggerShare = 30;
+constexpr int kFwdStaggerNaps = 24;
+constexpr int kFwdStaggerDefault = kStaggerTurn | (kFwdStaggerShare << 17) | kFwdStaggerNaps;
+constexpr int kFwdStaggerMaxNaps = 256;
+constexpr int kFwdStaggerMinGrid = 256;     // the CUs of the chip, as groups_per_channel() counts them
+int fwd_stagger() {
+    static const int mode = [] {
+        const char* e = getenv("PDE_FWD_STAGGER");
+        if (!e || !e[0] || (e[0] == '1' && !e[1])) return kFwdStaggerDefault;
+        const int turn = (e[0] == 't') ? kStaggerTurn : 0;
+        int n = atoi(turn ? e + 1 : e);
+        n = n > kFwdStaggerMaxNaps ? kFwdStaggerMaxNaps : (n < -kFwdStaggerMaxNaps ? -kFwdStaggerMaxNaps : n);
+        const char* sl = strchr(e, '/');
+        int share = sl ? atoi(sl + 1) : kFwdStaggerShare;
+        share = share < 0 ? 0 : (share > 100 ? 100 : share);
+        return turn | (turn ? share << 17 : 0) | (n & 0xffff);
+    }();
+    return mode;
+}
+
+#ifdef PDE_STAMP
+// diagnostic builds only (tools/fwd_timeline.py): the timeline slots of the last hand-over launch
+constexpr size_t kFwdStampBytes = (size_t)1024 * kWaves * kFwdStamps * sizeof(unsigned long long);
+void* fwd_stamp_buffer() {
+    static void* buf = [] () -> void* {
+        void* p = nullptr;
+        if (hipMalloc(&p, kFwdStampBytes) != hipSuccess) return nullptr;
+        (void)hipMemset(p, 0, kFwdStampBytes);
+        return p;
+    }();
+    return buf;
+}
+#endif
+
 // ---- launch helpers shared by the whole-schedule entry points and the per-step ones -----------------
 // forward sweeps of `d` (a whole schedule or one step of it) with records/table already in place
 // `states` / `emit` (pde_adi_forward_states, a non-empty mask): the emitting variant of the HIP kernel on the
@@ -752,6 +800,10 @@ int launch_fwd_sweeps(const PdeAdiDesc* d, const void* u, void* y, const float* 
     }
     if (fwd_ho_eligible(d)) {
         const size_t lds = (size_t)(kRingHo * kRecFwdPad + kWaves * kImage + kRingHo) * sizeof(float);
+        sa.stagger = (sa.G * d->C > kFwdStaggerMinGrid) ? fwd_stagger() : 0;
+#ifdef PDE_STAMP
+        sa.dbg = (sa.G * d->C <= 1024) ? fwd_stamp_buffer() : nullptr;
+#endif
         return dispatch_fwd(d, split_of(d), sa, sa.G * d->C, lds, st, true, 1);
     }
     const size_t lds = (size_t)(kRing * kRecFwdPad + kWaves * kImage) * sizeof(float);
@@ -942,6 +994,16 @@ int pde_adi_forward_kernel(const PdeAdiDesc* d) {
     if (!fused_n(d->N)) return 2;
     return asm_fwd_eligible(d) ? 1 : (fwd_ho_eligible(d) ? 3 : 0);
 }
+
+#ifdef PDE_STAMP
+// diagnostic builds only (tools/fwd_timeline.py): copy out n 64-bit timeline slots of the last hand-over forward
+int pde_fwd_stamps(unsigned long long* out, int n) {
+    void* b = fwd_stamp_buffer();
+    if (!b || n < 0 || (size_t)n * 8 > kFwdStampBytes) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpy(out, b, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+#endif
 
 int pde_adi_backward_kernel(const PdeAdiDesc* d, int32_t num_checkpoints) {
     if (check_desc(d, true) != PDE_OK) return PDE_E_BADARG;

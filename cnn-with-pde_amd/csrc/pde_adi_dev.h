@@ -72,6 +72,8 @@ struct SweepArgs {
                             // (same time, same increment): its rows are loaded from LDS once for the two sweeps
     void* dbg;              // diagnostic builds only
     int only_masked;        // bwd: the grid is C*G blocks of the MASKED body alone (the fast body ran as the assembly kernel)
+    int stagger;            // fwd, hand-over schedule: how the two workgroups of a CU are kept out of phase (kStaggerTurn,
+                            // stagger_naps; 0: not at all); sits in what was padding
     // emitting variants only (EMIT = true; nothing else reads these): bit s of em = the state after sweep s leaves the
     // launch.  fwd: the true state, to states[slot][B][C][N][N] of the I/O type; bwd: the same layout holds dL/d(state)
     void* states;
@@ -155,9 +157,44 @@ __device__ __forceinline__ unsigned long long stamp() {
     return t;
 }
 #define PDE_STAMP_AT(i) do { if (stamp_on) stamps[i] = stamp(); } while (0)
+// The forward's timeline (tools/fwd_timeline.py): lane 0 of every wave of every workgroup of a hand-over launch keeps
+// kFwdStamps 64-bit slots at dbg[(block * kWaves + wave) * kFwdStamps]: 0 kernel top; per chunk k = 0, 1 at 1 + 5k: plane
+// loads begin, planes in registers, first sweep done, last sweep done, stores issued; 11 last stores drained; 12, 13 the
+// 100 MHz counter at the top and at the end; 14 HW_ID | XCC_ID << 32; 15 the LDS_ALLOC register
+constexpr int kFwdStamps = 16;
+__device__ __forceinline__ unsigned long long stamp_real() {
+    unsigned long long t;
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    return t;
+}
+#define PDE_FWD_STAMP(i) do { if (fst) fst[i] = stamp(); } while (0)
 #else
 #define PDE_STAMP_AT(i) do { } while (0)
+#define PDE_FWD_STAMP(i) do { } while (0)
 #endif
+
+// Which of the (at most two) workgroups resident on a CU am I?  The LDS allocation of the first starts at 0, that of the
+// second behind it: LDS_BASE of the wave's LDS_ALLOC register (in allocation granules) says so without any traffic
+// between the two.  A workgroup alone on its CU reads 0.  Used for scheduling only, never for results.
+__device__ __forceinline__ unsigned lds_alloc_reg() {
+    unsigned r;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_LDS_ALLOC)" : "=s"(r));
+    return r;
+}
+__device__ __forceinline__ bool second_on_cu() { return (lds_alloc_reg() & 0xfffu) != 0u; }   // (LDS_SIZE starts at bit 12)
+// SweepArgs::stagger: bits 0-15 = hold-back naps (signed: > 0 the second workgroup of a CU naps before its first plane
+// loads, < 0 the first), one nap = s_sleep 8 = 512 cycles; bit 16 = the two workgroups of a CU take turns in priority,
+// bits 17-23 = the share of its time steps (percent) after which the turn passes from the first to the second
+constexpr int kStaggerSleep = 8;
+constexpr int kStaggerTurn = 1 << 16;
+__device__ __forceinline__ int stagger_naps(int st) { return (int)(short)(st & 0xffff); }
+__device__ __forceinline__ int stagger_share(int st) { return (st >> 17) & 127; }   // A's part of the time steps, percent
+// a workgroup's priority class (0: as young_half_priority left it, 1: one above) on top of the younger half's
+__device__ __forceinline__ void chunk_priority(bool high, int wave) {
+    const bool young = PDE_PRIO && wave >= kWaves / 2;
+    if (high) { if (young) __builtin_amdgcn_s_setprio(PDE_PRIO + 1); else __builtin_amdgcn_s_setprio(1); }
+    else { if (young) __builtin_amdgcn_s_setprio(PDE_PRIO); else __builtin_amdgcn_s_setprio(0); }
+}
 
 // value held by lane ^ 32 (the other half of my line).  v_permlane32_swap (new on gfx950) does it in
 // the VALU; __shfl_xor becomes ds_bpermute_b32, which queues behind the re-layout traffic of the
@@ -651,6 +688,21 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
     const bool resident = !HO && a.S <= kRing;
     const int lag = (resident || HO) ? 0 : wave_lag(wave);
     young_half_priority(wave);
+#ifdef PDE_STAMP
+    unsigned long long* fst = nullptr;                   // my timeline slots (lane 0 of the waves of a hand-over launch)
+    int fchunk = 0;                                       // chunks I have begun
+    if (HO && a.dbg != nullptr && lane == 0) fst = static_cast<unsigned long long*>(a.dbg) + ((size_t)blockIdx.x * kWaves + wave) * kFwdStamps;
+    unsigned long long* const fend = fst;
+    PDE_FWD_STAMP(0);
+    if (fst) {
+        unsigned id, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(id));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        fst[12] = stamp_real();
+        fst[14] = id | ((unsigned long long)xcc << 32);
+        fst[15] = lds_alloc_reg();
+    }
+#endif
 
     // rows >= N of the wave images are never written: zero them once so idle lanes read zeros
     for (int e = tid; e < kWaves * kImage; e += kThreads) tbuf[e] = 0.f;
@@ -726,8 +778,35 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
     // one (same record, see SweepArgs::pair_x) instead of reading them from LDS again
     float ce[M], cinv[M], cjn = 0.f;
     bool abl_loaded = false;
+    // The stagger (a.stagger != 0: launches that fill every CU with two workgroups; HO only).  The two workgroups of a CU
+    // start together with equal work, but not at equal speed: the first-dispatched one (phase A) wins the issue
+    // arbitration and sweeps a chunk in 48 us where the second (phase B) takes 62 (tools/fwd_timeline.py), so
+    // A is done 20 us before B, which then runs its last 20 us alone on a CU that two workgroups keep busy.  With
+    // kStaggerTurn the two take turns instead: A runs one priority class above B until a set share of its time steps is
+    // done, B above A after the same share of its own.  A still leads B at the exchange of chunks in the middle — their
+    // memory bursts fall into each other's sweeps — and B no longer trails at the end.  The naps hold B back at the head,
+    // where everybody loads at once.  Nobody waits for anybody: a static priority, changed once, a bounded number of
+    // naps, no flag, no memory polled; a workgroup that is wrong about its phase is merely not staggered.
+    [[maybe_unused]] bool second = false;
+    [[maybe_unused]] int ks = 0, kflip = -1;              // time steps I have begun; the one at which the turn passes to B
+    if constexpr (HO) {
+        if (a.stagger != 0) {
+            second = second_on_cu();
+            if (a.stagger & kStaggerTurn) {
+                kflip = ((nchunk - g + a.G - 1) / a.G) * (a.S / 3) * stagger_share(a.stagger) / 100;
+                chunk_priority(!second, wave);
+            }
+            const int naps = second ? stagger_naps(a.stagger) : -stagger_naps(a.stagger);
+#pragma unroll 1
+            for (int i = 0; i < naps; ++i) __builtin_amdgcn_s_sleep(kStaggerSleep);
+        }
+    }
     for (int q = g; q < nchunk; q += a.G) {
         typename Pack<J>::P v[M];
+#ifdef PDE_STAMP
+        if (fchunk >= 2) fst = nullptr;                   // the timeline covers the first two chunks
+        PDE_FWD_STAMP(1 + 5 * fchunk);
+#endif
         if (!((PDE_ABL & 4) && abl_loaded)) {
 #ifndef PDE_FWD_PAR_LOAD
 #define PDE_FWD_PAR_LOAD 0
@@ -736,6 +815,7 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
         else if constexpr (J > 2 && !PDE_FWD_PAR_LOAD) load_planes_seq<N, J, IO>(u, q, wave, lane, l, hf, a.B, a.C, c, T, v);   // 16, not 16*J, registers in flight
         else load_planes<N, J, IO>(u, q, wave, lane, l, hf, a.B, a.C, c, T, v);
         }
+        PDE_FWD_STAMP(2 + 5 * fchunk);
         auto sweep = [&](auto AXC, int s, auto TWINC) {
             constexpr int AX = decltype(AXC)::value;
             if constexpr (HO) {                           // (never with checkpoints: the pre-pass runs kSplitAny)
@@ -784,7 +864,14 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
         };
         if constexpr (SPLIT == kSplitStrang) {
             for (int s = 0; s < a.S; s += 3) {
+                if constexpr (HO) {
+                    if (ks == kflip) chunk_priority(second, wave);
+                    ++ks;
+                }
                 sweep(std::integral_constant<int, PDE_AXIS_X>{}, s, std::true_type{});       // twin of the sweep before it
+#ifdef PDE_STAMP
+                if (s == 0) PDE_FWD_STAMP(3 + 5 * fchunk);
+#endif
                 sweep(std::integral_constant<int, PDE_AXIS_Y>{}, s + 1, std::false_type{});
                 sweep(std::integral_constant<int, PDE_AXIS_X>{}, s + 2, std::false_type{});
             }
@@ -796,8 +883,20 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
         } else {
             for (int s = 0; s < a.S; ++s) sweep(std::integral_constant<int, -1>{}, s, std::false_type{});
         }
+        PDE_FWD_STAMP(4 + 5 * fchunk);
         if (y != nullptr && !((PDE_ABL & 4) && q + a.G < nchunk)) store_planes<N, J, IO>(y, q, wave, lane, l, hf, a.B, a.C, c, T, v);
+#ifdef PDE_STAMP
+        PDE_FWD_STAMP(5 + 5 * fchunk);
+        ++fchunk;
+#endif
     }
+#ifdef PDE_STAMP
+    if (fend) {
+        dma_wait_all();                                   // my last stores have left
+        fend[11] = stamp();
+        fend[13] = stamp_real();
+    }
+#endif
     if (!HO && !lag) __syncthreads();                     // the interval in which the upper waves finish
 }
 

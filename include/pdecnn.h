@@ -81,7 +81,8 @@ int pde_adi_line_length_path(int32_t N);
 /* Which kernel pde_adi_forward runs for this schedule: 0 = the HIP kernel with a barrier per sweep (adi_fwd_kernel), 1 = the
  * hand-scheduled assembly kernel (opt-in, PDE_ASM_FWD=1), 2 = the any-size kernels, 3 = the HIP kernel's hand-over schedule
  * (N = 32, fp32 tensors, Strang steps, more sweeps than stay resident: counters in LDS instead of the barrier per sweep).
- * Same arithmetic in the same order for 0, 1 and 3; PDE_FWD_SCHED=0 in the environment turns 3 into 0. */
+ * Same arithmetic in the same order for 0, 1 and 3; PDE_FWD_SCHED=0 in the environment turns 3 into 0;
+ * PDE_FWD_STAGGER=0 runs 3 without the stagger of the two workgroups of a CU (scheduling only). */
 int pde_adi_forward_kernel(const PdeAdiDesc* d);
 
 /* Which kernel pde_adi_backward runs for this schedule's unmasked channels: 0 = the HIP kernel (adi_bwd_kernel), 1 = the
