@@ -249,16 +249,16 @@ __global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_fwd_kernel(SmallArg
                     for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
                     if (lane == 0) psum[(size_t)b * nC + c] = t;
                 }
-                if (a.L > 1) {                                            // out = sum_i w_i y_i: my own earlier store, re-read
-                    if (li > 0 && lsel < 0) {
-                        float o[M];
-                        small_load<N, 0, IO>(y, b, nC, c, lane, l, hf, T, o);
+                // out = sum_i w_i y_i, a single layer included (the one-layer entry points pass the weight 1, and 1 * v is v
+                // bit for bit): one after the other the running sum is my own earlier store, re-read
+                if (li > 0 && lsel < 0) {
+                    float o[M];
+                    small_load<N, 0, IO>(y, b, nC, c, lane, l, hf, T, o);
 #pragma unroll
-                        for (int q = 0; q < M; ++q) v[q] = fmaf(wl, v[q], o[q]);
-                    } else {
+                    for (int q = 0; q < M; ++q) v[q] = fmaf(wl, v[q], o[q]);
+                } else {
 #pragma unroll
-                        for (int q = 0; q < M; ++q) v[q] = wl * v[q];
-                    }
+                    for (int q = 0; q < M; ++q) v[q] = wl * v[q];
                 }
                 small_store<N, 0, IO>(yl, b, nC, c, lane, l, hf, T, v);
             }

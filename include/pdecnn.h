@@ -308,7 +308,16 @@ int pde_adi_small_backward_states(const PdeAdiDesc* d, int32_t sweeps_per_step, 
  * samples through layer after layer, or, while the batch alone does not fill the chip (B < 1024), the layers run side
  * by side (one layer per workgroup; the terms of `out` / `gu` meet in a small second launch, in a fixed order) — and
  * writes out = sum_i weight_i * y_i; the y_i themselves are the last of each layer's `states`.  One layer with
- * weight 1 is pde_adi_small_forward.
+ * weight 1 is pde_adi_small_forward; one layer with another weight gives out = r(weight_0 * y_0) like any term.
+ * How `out` is rounded (r: one rounding to io_dtype; the arithmetic is fp32; with 16-bit tensors and kept `states`
+ * y_i is the rounded value the layer's last state holds):
+ *   side by side (num_layers > 1, B < 1024)   t_i = r(weight_i * y_i) per layer, then out = r(((t_0 + t_1) + t_2) + t_3),
+ *                                             the sum in fp32 in layer order: one rounding per term plus one of the sum
+ *                                             (fp32 tensors: the L-1 fp32 additions are the roundings of the sum);
+ *   one after the other (B >= 1024)           out_0 = r(weight_0 * y_0), out_i = r(fma(weight_i, y_i, out_{i-1})) with
+ *                                             out_{i-1} re-read in io_dtype: L roundings of the running sum.
+ * Either way |out - sum_i weight_i y_i| <= (L+1) eps sum_i |weight_i y_i| elementwise, eps = 2^-24 / 2^-8 / 2^-11 for
+ * fp32 / bf16 / fp16 (plus (L+1) 2^-25 where fp16 results are subnormal).  gu = sum_i gu_i is built the same two ways.
  * The backward takes gy = dL/dout and/or per layer gys = dL/dy_i, and gives gu = sum_i gu_i, every layer's
  * parameter gradients, and g_weight = <gy, y_i>. */
 typedef struct PdeSmallLayer {
