@@ -134,29 +134,28 @@ def route_input(u: torch.Tensor, *params) -> torch.Tensor:
     return _io_in(u, *params)
 
 
-_desc_cache = {}
 _M64 = (1 << 64) - 1
 
 
-def _make_desc(B, Cc, N, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) -> L.PdeAdiDesc:
-    """The launch descriptor (read-only for the library).  Cached: filling ~100 ctypes fields costs more
-    host time than the kernels of a small layer take on the device."""
-    if not isinstance(sweeps, tuple):
-        sweeps = tuple(sweeps)
-    key = (B, Cc, N, io, sweeps, bool(smooth3), clamp_max, float(eps))
-    d = _desc_cache.get(key)
-    if d is None:
-        if len(_desc_cache) > 256:
-            _desc_cache.clear()
-        d = _desc_cache[key] = _build_desc(B, Cc, N, io, sweeps, smooth3, clamp_max, eps)
-    return d
+def _mask128(bits: int):
+    """A 128-bit mask of the C ABI (the backward's checkpoints, a trajectory call's emitted sweeps or steps)."""
+    return (C.c_uint64 * 2)(bits & _M64, bits >> 64)
 
 
-def _build_desc(B, Cc, N, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) -> L.PdeAdiDesc:
+_desc_cache = {}
+
+
+def _fill_desc(cls, B, Cc, H, W, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps):
+    """A new launch descriptor of type ``cls``: PdeAdiDesc / PdeAdiDescF64 for a square plane (N = H), PdeAdiRectDesc /
+    PdeAdiRectDescF64 for (H, W)."""
     if len(sweeps) > L.PDE_MAX_SWEEPS:
         raise L.PdeError(f"{len(sweeps)} sweeps in one launch exceed PDE_MAX_SWEEPS={L.PDE_MAX_SWEEPS}")
-    d = L.PdeAdiDesc()
-    d.B, d.C, d.N, d.io_dtype, d.num_sweeps = B, Cc, N, io, len(sweeps)
+    d = cls()
+    if hasattr(cls, "N"):
+        d.N = H
+    else:
+        d.H, d.W = H, W
+    d.B, d.C, d.io_dtype, d.num_sweeps = B, Cc, io, len(sweeps)
     d.smooth3 = int(bool(smooth3))
     d.has_clamp_max = int(clamp_max is not None)
     d.clamp_max = float(clamp_max) if clamp_max is not None else 0.0
@@ -166,31 +165,28 @@ def _build_desc(B, Cc, N, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) 
     return d
 
 
-_rect_desc_cache = {}
-
-
-def _make_rect_desc(B, Cc, H, W, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps):
-    """The launch descriptor of a rectangular plane: PdeAdiRectDesc, or PdeAdiRectDescF64 for ``io == PDE_IO_F64``.
-    Cached like ``_make_desc``, keyed on (H, W)."""
+def _desc(cls, B, Cc, H, W, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps):
+    """The launch descriptor (read-only for the library).  Cached: filling ~100 ctypes fields costs more host time than
+    the kernels of a small layer take on the device."""
     if not isinstance(sweeps, tuple):
         sweeps = tuple(sweeps)
-    key = (B, Cc, H, W, io, sweeps, bool(smooth3), clamp_max, float(eps))
-    d = _rect_desc_cache.get(key)
+    key = (cls, B, Cc, H, W, io, sweeps, bool(smooth3), clamp_max, float(eps))
+    d = _desc_cache.get(key)
     if d is None:
-        if len(sweeps) > L.PDE_MAX_SWEEPS:
-            raise L.PdeError(f"{len(sweeps)} sweeps in one launch exceed PDE_MAX_SWEEPS={L.PDE_MAX_SWEEPS}")
-        if len(_rect_desc_cache) > 256:
-            _rect_desc_cache.clear()
-        d = L.PdeAdiRectDescF64() if io == L.PDE_IO_F64 else L.PdeAdiRectDesc()
-        d.B, d.C, d.H, d.W, d.io_dtype, d.num_sweeps = B, Cc, H, W, io, len(sweeps)
-        d.smooth3 = int(bool(smooth3))
-        d.has_clamp_max = int(clamp_max is not None)
-        d.clamp_max = float(clamp_max) if clamp_max is not None else 0.0
-        d.eps = float(eps)
-        for i, s in enumerate(sweeps):
-            d.sweep[i].axis, d.sweep[i].delta, d.sweep[i].h2, d.sweep[i].t = int(s.axis), s.delta, s.h2, s.t
-        _rect_desc_cache[key] = d
+        d = _fill_desc(cls, B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps)
+        if len(_desc_cache) > 256:
+            _desc_cache.clear()
+        _desc_cache[key] = d
     return d
+
+
+def _make_desc(B, Cc, N, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) -> L.PdeAdiDesc:
+    return _desc(L.PdeAdiDesc, B, Cc, N, N, io, sweeps, smooth3, clamp_max, eps)
+
+
+def _build_desc(B, Cc, N, io, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) -> L.PdeAdiDesc:
+    """A square descriptor of the caller's own, not cached (bench.py asks the library about one)."""
+    return _fill_desc(L.PdeAdiDesc, B, Cc, N, N, io, sweeps, smooth3, clamp_max, eps)
 
 
 def _is_rect(u) -> bool:
@@ -215,6 +211,46 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+# What the one node of a layer family (_AdiFn, _Explicit5Fn, _JacobiFn) needs to serve the plain call and the trajectory
+# call alike.  ``sel`` None is the plain call; otherwise it lists what the call emits, the last sweep / step included.
+def _kernel_input(u: torch.Tensor, f64: bool, io_types=_IO_TYPES) -> torch.Tensor:
+    """``u`` as a family's kernels take it, contiguous: double on the float64 route, otherwise as it is when ``io_types``
+    holds its type and widened to fp32 when not."""
+    if f64:
+        return u.to(torch.float64).contiguous()
+    return (u if u.dtype in io_types else u.float()).contiguous()
+
+
+def _kernel_param(p: torch.Tensor, dtype) -> torch.Tensor:
+    """A parameter cut from the graph, contiguous and in the kernels' type (no torch call for a type it has already)."""
+    p = p.detach()
+    return (p if p.dtype == dtype else p.to(dtype)).contiguous()
+
+
+def _out_and_traj(u, sel):
+    """(what the node returns, the library's output, its trajectory tensor or None): a plain call returns the output, a
+    tensor of its own; a trajectory call ONE tensor (K', ...) whose last slice is the library's output."""
+    if sel is None:
+        out = torch.empty_like(u)
+        return out, out, None
+    res = torch.empty((len(sel),) + tuple(u.shape), dtype=u.dtype, device=u.device)
+    return res, res[-1], res
+
+
+def _grad_as(g, dtype, shape=None):
+    """A gradient in the type (and shape) of the tensor it belongs to; no torch call where it has them already (each costs
+    the host more than a microsecond, and fp32 gradients of fp32 tensors are the common case)."""
+    if shape is not None and g.shape != shape:
+        g = g.reshape(shape)
+    return g if g.dtype == dtype else g.to(dtype)
+
+
+def _cotangents(g, like, sel):
+    """(gradient of the library's output, gradient of the trajectory tensor or None) from the node's cotangent."""
+    g = _grad_as(g, like.dtype).contiguous()
+    return (g, None) if sel is None else (g[-1], g)       # slots 0..K'-2 are the states' gradients, the last slice is gy
+
+
 def _as_chw(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.Tensor:
     """The parameter as a contiguous fp32 (C, N, N) tensor — (C, N, W) on a rectangle."""
     W = N if W is None else W
@@ -227,6 +263,24 @@ def _as_chw(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.
     if tuple(q.shape) != (Cc, N, W):
         raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{W})")
     return q.to(torch.float32).contiguous()
+
+
+def _as_chw64(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.Tensor:
+    W = N if W is None else W
+    q = p.detach()
+    if q.dim() == 2:
+        q = q.unsqueeze(0)
+    if tuple(q.shape) != (Cc, N, W):
+        raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{W})")
+    return q.to(torch.float64).contiguous()
+
+
+#: (rect, f64) -> what tells the four sub-families of the implicit sweeps apart on the host: the prefix of their symbols,
+#: their descriptor and the view their kernels take of a parameter.  Everything else is one body (``_AdiFn``).
+_ADI_FAMILY = {(False, False): ("pde_adi_", L.PdeAdiDesc, _as_chw),
+               (True, False): ("pde_adi_rect_", L.PdeAdiRectDesc, _as_chw),
+               (False, True): ("pde_adi_f64_", L.PdeAdiDescF64, _as_chw64),
+               (True, True): ("pde_adi_rect_f64_", L.PdeAdiRectDescF64, _as_chw64)}
 
 
 #: amplification of rounding error tolerated when a state is rebuilt backwards from a later one
@@ -261,7 +315,7 @@ def kappa_max_async(u_like, alpha_base, beta_base, alpha_time_coeff, beta_time_c
     kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u_like.device)
     with torch.cuda.device(u_like.device):
         if N != W:                                         # a rectangle: the pde_adi_rect_* entry points
-            d = _make_rect_desc(max(B, 1), Cc, N, W, L.PDE_IO_F32, sweeps, smooth3, clamp_max, eps)
+            d = _desc(L.PdeAdiRectDesc, max(B, 1), Cc, N, W, L.PDE_IO_F32, sweeps, smooth3, clamp_max, eps)
             L.check(lib.pde_adi_rect_kappa_max(C.byref(d), *[_ptr(t) for t in p], _ptr(kdev), _stream()),
                     "pde_adi_rect_kappa_max")
         else:
@@ -416,137 +470,83 @@ class _KmaxConcat:
 
 
 class _AdiFn(torch.autograd.Function):
+    """The implicit sweeps through ctypes, the general path: ``adi_diffuse`` and ``adi_diffuse_states`` of the four
+    sub-families ``_ADI_FAMILY`` tells apart — squares and rectangles, fp32 / bf16 / fp16 tensors and float64 (every
+    tensor in double, the checkpoint plan of ``_f64_ckpt_bits``, no coefficient maxima).
+
+    One body, because the library has one: a plain call is the family's ``*_states`` call without a mask.  ``emit`` None is
+    the plain call and returns ``y``, a tensor of its own.  Otherwise ``emit`` lists the sweeps whose state is returned
+    (the last one included) and the result is ONE tensor (K', B, C, H, W) whose last slice is the library's ``y``."""
+
     @staticmethod
-    def forward(ctx, u, ab, bb, asl, bsl, sweeps, smooth3, clamp_max, eps, ckpt, kmax_sink):
+    def forward(ctx, u, ab, bb, asl, bsl, sweeps, smooth3, clamp_max, eps, ckpt, kmax_sink, emit=None, rect=False,
+                f64=False):
+        # the defaults are the plain square call below float64: what ``apply`` with the first eleven arguments has always
+        # been (the backward's surplus trailing Nones are dropped by autograd)
         lib = L.load()
-        _require_cuda(u, ab, bb, asl, bsl)
-        if u.dim() != 4 or u.shape[2] != u.shape[3]:
-            raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
-        B, Cc, N, _ = u.shape
-        if u.dtype not in _IO_TYPES:
-            u = u.float()
-        u = u.contiguous()
-        p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-        y = torch.empty_like(u)
-        nbytes = lib.pde_adi_forward_workspace_bytes(C.byref(d))
-        ws = _workspace(nbytes, u.device)
+        if rect:
+            _check_rect(u, ab, bb, asl, bsl)
+        else:
+            _require_cuda(u, ab, bb, asl, bsl)
+            if u.dim() != 4 or u.shape[2] != u.shape[3]:
+                raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
+        B, Cc, H, W = u.shape
+        fam, desc_cls, as_chw = _ADI_FAMILY[rect, f64]
+        u = _kernel_input(u, f64)
+        if f64:
+            ckpt = _f64_ckpt_bits(ckpt, len(sweeps))
+        p = [as_chw(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
+        d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(u), sweeps, smooth3, clamp_max, eps)
+        out, y, traj = _out_and_traj(u, emit)
+        ebits = None if emit is None else sum(1 << s for s in emit[:-1])
+        ws = _workspace(getattr(lib, fam + "forward_workspace_bytes")(C.byref(d)), u.device)
         need_grad = any(ctx.needs_input_grad[:5])
-        want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
+        want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
         kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
         with torch.cuda.device(u.device):
             # per-sweep maximum coefficient (a by-product of the factorisation kernel): copied to pinned host
             # memory right behind that kernel, before the sweep launch, so whoever plans checkpoints from it
-            # waits for the factorisation only
+            # waits for the factorisation only.  The float64 entry points take the device pointer alone (never set)
             tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            L.check(lib.pde_adi_forward(C.byref(d), _ptr(u), _ptr(y), *[_ptr(t) for t in p], _ptr(kdev),
-                                        _ptr(tk.host if tk else None), C.c_void_p(tk.event.cuda_event if tk else 0),
-                                        _ptr(ws), ws.numel(), _stream()), "pde_adi_forward")
-            ctx.kmax = tk
-            if want_kmax and kmax_sink is not None:
-                kmax_sink.append(tk)
-        ctx.fwd_ws = ws if need_grad else None       # factorisation reused by the backward
-        ctx.save_for_backward(y, u if (need_grad and ckpt != 0) else None, *p)
-        ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt)
-        ctx.param_shapes = [t.shape for t in (ab, bb, asl, bsl)]
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        lib = L.load()
-        y, u, *p = ctx.saved_tensors
-        sweeps, smooth3, clamp_max, eps, ckpt = ctx.cfg
-        B, Cc, N, _ = y.shape
-        gy = gy.to(y.dtype).contiguous()
-        d = _make_desc(B, Cc, N, _io_dtype(y), sweeps, smooth3, clamp_max, eps)
-        gu = torch.empty_like(y)
-        gp = [torch.empty_like(t) for t in p]
-        if ckpt == "auto":
-            bits = plan_checkpoints(ctx.kmax.wait())
-        else:
-            bits = int(ckpt)
-        mask = (C.c_uint64 * 2)(bits & (2 ** 64 - 1), bits >> 64)
-        nbytes = lib.pde_adi_backward_workspace_bytes(C.byref(d), bin(bits).count("1"))
-        ws = _workspace(nbytes, y.device)
-        with torch.cuda.device(y.device):          # autograd thread: set device, fetch the stream here
-            L.check(lib.pde_adi_backward(C.byref(d), _ptr(gy), _ptr(y), _ptr(u if bits else None), mask, _ptr(gu),
-                                         *[_ptr(t) for t in p], *[_ptr(t) for t in gp], _ptr(ctx.fwd_ws),
-                                         _ptr(ws), ws.numel(), _stream()), "pde_adi_backward")
-        ctx.fwd_ws = None
-        gp = [g.reshape(s) for g, s in zip(gp, ctx.param_shapes)]
-        return (gu, *gp, None, None, None, None, None, None)
-
-
-class _AdiRectFn(torch.autograd.Function):
-    """adi_diffuse on a rectangular plane (pde_adi_rect_* / pde_adi_rect_f64_*): ``_AdiFn`` and ``_AdiF64Fn`` for
-    H != W.  ``f64``: every tensor in double, the checkpoint plan of ``_f64_ckpt_bits`` (no coefficient maxima)."""
-
-    @staticmethod
-    def forward(ctx, u, ab, bb, asl, bsl, sweeps, smooth3, clamp_max, eps, ckpt, kmax_sink, f64):
-        lib = L.load()
-        if u.dim() != 4:
-            raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
-        _check_rect(u, ab, bb, asl, bsl)
-        B, Cc, H, W = u.shape
-        if f64:
-            u = u.to(torch.float64).contiguous()
-            p = [_as_chw64(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
-            io, kt, fam = L.PDE_IO_F64, torch.float64, "pde_adi_rect_f64_"
-        else:
-            if u.dtype not in _IO_TYPES:
-                u = u.float()
-            u = u.contiguous()
-            p = [_as_chw(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
-            io, kt, fam = _io_dtype(u), torch.float32, "pde_adi_rect_"
-        d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps)
-        y = torch.empty_like(u)
-        ws = _workspace(getattr(lib, fam + "forward_workspace_bytes")(C.byref(d)), u.device)
-        need_grad = any(ctx.needs_input_grad[:5])
-        if f64:
-            ckpt = _f64_ckpt_bits(ckpt, len(sweeps))
-        want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
-        kdev = torch.empty(len(sweeps), dtype=kt, device=u.device) if want_kmax else None
-        with torch.cuda.device(u.device):
-            if f64:
-                L.check(lib.pde_adi_rect_f64_forward(C.byref(d), _ptr(u), _ptr(y), *[_ptr(t) for t in p], None, _ptr(ws),
-                                                     ws.numel(), _stream()), "pde_adi_rect_f64_forward")
-                tk = None
-            else:
-                # the coefficient maxima reach the host through the same pinned ring as a square call's
-                tk = _kmax_channel(len(sweeps)) if want_kmax else None
-                L.check(lib.pde_adi_rect_forward(C.byref(d), _ptr(u), _ptr(y), *[_ptr(t) for t in p], _ptr(kdev),
-                                                 _ptr(tk.host if tk else None), C.c_void_p(tk.event.cuda_event if tk else 0),
-                                                 _ptr(ws), ws.numel(), _stream()), "pde_adi_rect_forward")
+            kmax = (None,) if f64 else (_ptr(kdev), _ptr(tk.host if tk else None),
+                                        C.c_void_p(tk.event.cuda_event if tk else 0))
+            L.check(getattr(lib, fam + "forward_states")(C.byref(d), _ptr(u), _ptr(y), _ptr(traj),
+                                                         None if emit is None else _mask128(ebits),
+                                                         *[_ptr(t) for t in p], *kmax, _ptr(ws), ws.numel(), _stream()),
+                    fam + "forward_states")
             ctx.kmax = tk
             if tk is not None and kmax_sink is not None:
                 kmax_sink.append(tk)
         ctx.fwd_ws = ws if need_grad else None       # factorisation reused by the backward
-        ctx.save_for_backward(y, u if (need_grad and ckpt != 0) else None, *p)
-        ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt, f64)
+        ctx.save_for_backward(out, u if (need_grad and ckpt != 0) else None, *p)
+        ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt, rect, f64, ebits)
         ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
-        return y
+        return out
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, g):
         lib = L.load()
-        y, u, *p = ctx.saved_tensors
-        sweeps, smooth3, clamp_max, eps, ckpt, f64 = ctx.cfg
-        B, Cc, H, W = y.shape
-        gy = gy.to(y.dtype).contiguous()
-        d = _make_rect_desc(B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(y), sweeps, smooth3, clamp_max, eps)
+        out, u, *p = ctx.saved_tensors
+        sweeps, smooth3, clamp_max, eps, ckpt, rect, f64, ebits = ctx.cfg
+        B, Cc, H, W = out.shape[-4:]
+        fam, desc_cls, _ = _ADI_FAMILY[rect, f64]
+        y = out if ebits is None else out[-1]
+        gy, gtraj = _cotangents(g, out, ebits)
+        d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(out), sweeps, smooth3, clamp_max, eps)
         gu = torch.empty_like(y)
         gp = [torch.empty_like(t) for t in p]
         bits = plan_checkpoints(ctx.kmax.wait()) if ckpt == "auto" else int(ckpt)
-        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
-        fam = "pde_adi_rect_f64_" if f64 else "pde_adi_rect_"
-        ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(C.byref(d), bin(bits).count("1")), y.device)
-        with torch.cuda.device(y.device):          # autograd thread: set device, fetch the stream here
-            L.check(getattr(lib, fam + "backward")(C.byref(d), _ptr(gy), _ptr(y), _ptr(u if bits else None), mask, _ptr(gu),
-                                                   *[_ptr(t) for t in p], *[_ptr(t) for t in gp], _ptr(ctx.fwd_ws),
-                                                   _ptr(ws), ws.numel(), _stream()), fam + "backward")
+        ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(C.byref(d), bin(bits).count("1")), out.device)
+        with torch.cuda.device(out.device):          # autograd thread: set device, fetch the stream here
+            L.check(getattr(lib, fam + "backward_states")(C.byref(d), _ptr(gy), _ptr(gtraj),
+                                                          None if ebits is None else _mask128(ebits), _ptr(y),
+                                                          _ptr(u if bits else None), _mask128(bits), _ptr(gu),
+                                                          *[_ptr(t) for t in p], *[_ptr(t) for t in gp],
+                                                          _ptr(ctx.fwd_ws), _ptr(ws), ws.numel(), _stream()),
+                    fam + "backward_states")
         ctx.fwd_ws = None
-        gp = [g.reshape(s).to(dt) for g, (s, dt) in zip(gp, ctx.param_meta)]
-        return (gu, *gp, None, None, None, None, None, None, None)
+        gp = [_grad_as(t, dt, s) for t, (s, dt) in zip(gp, ctx.param_meta)]
+        return (gu, *gp) + (None,) * 9
 
 
 class _AdiMixedFn(torch.autograd.Function):
@@ -616,7 +616,7 @@ class _AdiMixedFn(torch.autograd.Function):
         else:
             bits = int(ckpt)
         nck = bin(bits).count("1")
-        mask = (C.c_uint64 * 2)(bits & (2 ** 64 - 1), bits >> 64)
+        mask = _mask128(bits)
         ws = _workspace(lib.pde_adi_mixed_backward_workspace_bytes(C.byref(d), sps, nck), u.device)
         g_in = gy.to(u.dtype).contiguous()
         g_a = torch.empty_like(g_in)
@@ -690,7 +690,7 @@ class _AdiSmallFn(torch.autograd.Function):
                 bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
         else:
             bits = int(ckpt)
-        mask = (C.c_uint64 * 2)(bits & (2 ** 64 - 1), bits >> 64)
+        mask = _mask128(bits)
         ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
         g_in = gy.to(u.dtype).contiguous()
         gu = torch.empty_like(g_in)
@@ -806,7 +806,7 @@ class _AdiMultiFn(torch.autograd.Function):
                     bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
             else:
                 bits = int(ctx.ckpt[i])
-            mask = (C.c_uint64 * 2)(bits & (2 ** 64 - 1), bits >> 64)
+            mask = _mask128(bits)
             ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
             gp = [torch.empty_like(t) for t in p]
             gM = torch.empty_like(Mf)
@@ -1041,20 +1041,13 @@ def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, swe
         return _empty_passthrough(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
     if not isinstance(sweeps, tuple):
         sweeps = tuple(sweeps)
-    if _is_rect(u):
-        # H != W: the rectangle entry points through the ctypes autograd function (no host-extension path); float64 and
-        # float16 by the same rules as a square call
-        f64 = _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
-        if not f64:
-            u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
-        return _AdiRectFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3),
-                                clamp_max, float(eps), checkpoints, kmax_sink, f64)
-    if _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff):
-        return _AdiF64Fn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3), clamp_max,
-                               float(eps), checkpoints)
-    u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
-    if (kmax_sink is None and (checkpoints == "auto" or isinstance(checkpoints, int))) or \
-            (kmax_sink is not None and isinstance(checkpoints, int)):
+    # the sub-family, decided here once: a rectangle (H != W) and float64 run through the ctypes node only (no
+    # host-extension path); float64 and float16 by the same rules on a rectangle as on a square
+    rect = _is_rect(u)
+    f64 = _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+    if not f64:
+        u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+    if not (rect or f64) and (isinstance(checkpoints, int) or (kmax_sink is None and checkpoints == "auto")):
         H = L.host_ext()
         if H is not None and u.dim() == 4 and u.is_cuda and u.dtype in _IO_TYPES:
             # the native host path (csrc/host_ext.cpp): the same two calls of the C ABI from a C++ autograd node
@@ -1073,97 +1066,7 @@ def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, swe
                 return y
             return H.adi(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, C.addressof(d), mode, lo, hi, CKPT_AMAX)
     return _AdiFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff,
-                        sweeps, bool(smooth3), clamp_max, float(eps), checkpoints, kmax_sink)
-
-
-class _AdiStatesFn(torch.autograd.Function):
-    """adi_diffuse that also returns the state after chosen sweeps, out of the same launch (pde_adi*_forward_states /
-    pde_adi*_backward_states): one node for the four families — squares and rectangles, fp32 / bf16 / fp16 tensors
-    and float64.  The result is ONE tensor (K', B, C, H, W); the library's ``y`` is its last slice."""
-
-    @staticmethod
-    def forward(ctx, u, ab, bb, asl, bsl, sweeps, emit, smooth3, clamp_max, eps, ckpt, kmax_sink, f64):
-        lib = L.load()
-        if u.dim() != 4:
-            raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
-        rect = u.shape[2] != u.shape[3]
-        if rect:
-            _check_rect(u, ab, bb, asl, bsl)
-        else:
-            _require_cuda(u, ab, bb, asl, bsl)
-        B, Cc, H, W = u.shape
-        if f64:
-            u = u.to(torch.float64).contiguous()
-            p = [_as_chw64(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
-            io = L.PDE_IO_F64
-            d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps) if rect else \
-                _make_desc64(B, Cc, H, sweeps, smooth3, clamp_max, eps)
-            ckpt = _f64_ckpt_bits(ckpt, len(sweeps))
-        else:
-            if u.dtype not in _IO_TYPES:
-                u = u.float()
-            u = u.contiguous()
-            p = [_as_chw(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
-            io = _io_dtype(u)
-            d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps) if rect else \
-                _make_desc(B, Cc, H, io, sweeps, smooth3, clamp_max, eps)
-        fam = "pde_adi_" + ("rect_" if rect else "") + ("f64_" if f64 else "")
-        K = len(emit)
-        out = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
-        bits = sum(1 << s for s in emit[:-1])
-        em = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
-        ws = _workspace(getattr(lib, fam + "forward_workspace_bytes")(C.byref(d)), u.device)
-        need_grad = any(ctx.needs_input_grad[:5])
-        want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
-        kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
-        with torch.cuda.device(u.device):
-            tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            head = (C.byref(d), _ptr(u), _ptr(out[K - 1]), _ptr(out), em, *[_ptr(t) for t in p])
-            if f64:
-                rc = getattr(lib, fam + "forward_states")(*head, None, _ptr(ws), ws.numel(), _stream())
-            else:
-                rc = getattr(lib, fam + "forward_states")(*head, _ptr(kdev), _ptr(tk.host if tk else None),
-                                                          C.c_void_p(tk.event.cuda_event if tk else 0), _ptr(ws),
-                                                          ws.numel(), _stream())
-            L.check(rc, fam + "forward_states")
-            ctx.kmax = tk
-            if tk is not None and kmax_sink is not None:
-                kmax_sink.append(tk)
-        ctx.fwd_ws = ws if need_grad else None       # factorisation reused by the backward
-        ctx.save_for_backward(out, u if (need_grad and ckpt != 0) else None, *p)
-        ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt, f64, rect, bits)
-        ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = L.load()
-        out, u, *p = ctx.saved_tensors
-        sweeps, smooth3, clamp_max, eps, ckpt, f64, rect, ebits = ctx.cfg
-        K, B, Cc, H, W = out.shape
-        g = g.to(out.dtype).contiguous()             # slots 0..K-2 are gstates, the last slice is gy
-        io = L.PDE_IO_F64 if f64 else _io_dtype(out)
-        if rect:
-            d = _make_rect_desc(B, Cc, H, W, io, sweeps, smooth3, clamp_max, eps)
-        else:
-            d = _make_desc64(B, Cc, H, sweeps, smooth3, clamp_max, eps) if f64 else \
-                _make_desc(B, Cc, H, io, sweeps, smooth3, clamp_max, eps)
-        fam = "pde_adi_" + ("rect_" if rect else "") + ("f64_" if f64 else "")
-        gu = torch.empty_like(out[0])
-        gp = [torch.empty_like(t) for t in p]
-        bits = plan_checkpoints(ctx.kmax.wait()) if ckpt == "auto" else int(ckpt)
-        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
-        em = (C.c_uint64 * 2)(ebits & _M64, ebits >> 64)
-        ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(C.byref(d), bin(bits).count("1")), out.device)
-        with torch.cuda.device(out.device):          # autograd thread: set device, fetch the stream here
-            L.check(getattr(lib, fam + "backward_states")(C.byref(d), _ptr(g[K - 1]), _ptr(g), em, _ptr(out[K - 1]),
-                                                          _ptr(u if bits else None), mask, _ptr(gu),
-                                                          *[_ptr(t) for t in p], *[_ptr(t) for t in gp],
-                                                          _ptr(ctx.fwd_ws), _ptr(ws), ws.numel(), _stream()),
-                    fam + "backward_states")
-        ctx.fwd_ws = None
-        gp = [t.reshape(s).to(dt) for t, (s, dt) in zip(gp, ctx.param_meta)]
-        return (gu, *gp, None, None, None, None, None, None, None, None)
+                        sweeps, bool(smooth3), clamp_max, float(eps), checkpoints, kmax_sink, None, rect, f64)
 
 
 def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps: Sequence[Sweep], emit,
@@ -1193,10 +1096,13 @@ def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coe
         return torch.stack([y] * len(emit))
     if not f64:
         u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
-    return _AdiStatesFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, emit, bool(smooth3),
-                              clamp_max, float(eps), checkpoints, kmax_sink, f64)
+    if u.dim() != 4:
+        raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
+    return _AdiFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3), clamp_max,
+                        float(eps), checkpoints, kmax_sink, emit, _is_rect(u), f64)
 
 
+# not folded into _AdiSmallFn: the two C entries differ in more than the mask (skip weight, DESIGN "Rounding points")
 class _AdiSmallStatesFn(torch.autograd.Function):
     """``_AdiSmallFn`` without the skip blend that also returns the state after chosen time steps, out of the same launch
     per pass (pde_adi_small_forward_states / pde_adi_small_backward_states).  The result is ONE tensor (K', B, C, N, N);
@@ -1226,7 +1132,7 @@ class _AdiSmallStatesFn(torch.autograd.Function):
         # keeps them: keep them then, so that the result is the same tensor in grad mode and without
         keep = need_grad or (bits == 0 and u.element_size() < 4)
         states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if keep else None
-        em = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
+        em = _mask128(bits)
         with torch.cuda.device(u.device):
             tk = _kmax_channel(len(sweeps)) if want_kmax else None
             L.check(lib.pde_adi_small_forward_states(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(out[Ke - 1]),
@@ -1261,8 +1167,8 @@ class _AdiSmallStatesFn(torch.autograd.Function):
                 bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
         else:
             bits = int(ckpt)
-        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
-        em = (C.c_uint64 * 2)(ebits & _M64, ebits >> 64)
+        mask = _mask128(bits)
+        em = _mask128(ebits)
         ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
         g = g.to(u.dtype).contiguous()                   # slots 0..K'-2 are the states' gradients, the last slice is gy
         gu = torch.empty_like(u)
@@ -1746,115 +1652,124 @@ def gate_combine(ys, gates, weights):
 
 
 # --------------------------------------------------------------------------- explicit layers
+# One node per family, as for the implicit sweeps: a plain call is the family's ``*_states`` call without a mask.  ``steps``
+# None is the plain call of ``num_steps`` / ``nt`` steps (any count the library takes) and returns ``out``, a tensor of its
+# own; otherwise ``steps`` are the emitted step numbers (the last one is the step count), ``bits`` their mask without the
+# last, and the result is ONE tensor (K', ...) whose last slice is the library's ``out``.  ``f64`` picks the
+# pde_*_f64_* entry points: every tensor in double, no tensor-type argument.
 class _Explicit5Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, num_steps):
+    def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, num_steps, steps, bits, f64):
         lib = L.load()
         _require_cuda(u, alpha_base, channel_scaling)
-        if u.dtype not in _IO_TYPES:
-            u = u.float()
-        u = u.contiguous()
+        fam, kt = ("pde_explicit5_f64_", torch.float64) if f64 else ("pde_explicit5_", torch.float32)
+        u = _kernel_input(u, f64)
         B, Cc, H, W = u.shape
-        a = alpha_base.detach().to(torch.float32).contiguous()
-        s = channel_scaling.detach().to(torch.float32).contiguous()
-        out = torch.empty_like(u)
+        a, s = _kernel_param(alpha_base, kt), _kernel_param(channel_scaling, kt)
+        res, out, traj = _out_and_traj(u, steps)
         need_grad = any(ctx.needs_input_grad[:3])
-        fused = (H, W) in ((64, 64), (32, 32), (16, 16))         # planes that stay in registers over all steps
+        fused = not f64 and (H, W) in ((64, 64), (32, 32), (16, 16))     # planes that stay in registers over all steps
         # inputs of steps 2..num_steps: what the backward reads (and what chains the steps for generic plane sizes): fp32
-        # whatever the tensors' type
-        states = torch.empty((num_steps - 1,) + tuple(u.shape), dtype=torch.float32, device=u.device) \
+        # whatever the tensors' type, or doubles
+        states = torch.empty((num_steps - 1,) + tuple(u.shape), dtype=kt, device=u.device) \
             if num_steps > 1 and (need_grad or not fused) else None
+        io = () if f64 else (_io_dtype(u),)
         with torch.cuda.device(u.device):
-            L.check(lib.pde_explicit5_forward(B, Cc, H, W, _io_dtype(u), _ptr(u), _ptr(a), _ptr(s), dt, eps, max_coeff,
-                                              relax, num_steps, _ptr(states), _ptr(out), _stream()), "pde_explicit5_forward")
+            L.check(getattr(lib, fam + "forward_states")(B, Cc, H, W, *io, _ptr(u), _ptr(a), _ptr(s), dt, eps, max_coeff,
+                                                         relax, num_steps, _ptr(states), _ptr(out), _ptr(traj),
+                                                         None if steps is None else _mask128(bits), _stream()),
+                    fam + "forward_states")
         ctx.save_for_backward(u, states if need_grad else None, a, s)
-        ctx.cfg = (dt, eps, max_coeff, relax, num_steps)
-        return out
+        ctx.cfg = (dt, eps, max_coeff, relax, num_steps, steps, bits, f64)
+        ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
+        return res
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, g):
         lib = L.load()
         u, states, a, s = ctx.saved_tensors
-        dt, eps, max_coeff, relax, num_steps = ctx.cfg
+        dt, eps, max_coeff, relax, num_steps, steps, bits, f64 = ctx.cfg
+        fam = "pde_explicit5_f64_" if f64 else "pde_explicit5_"
         B, Cc, H, W = u.shape
-        gout = gout.to(u.dtype).contiguous()
-        gu = torch.empty_like(u)
-        ga, gs = torch.empty_like(a), torch.empty_like(s)
-        ws = _workspace(lib.pde_explicit5_backward_workspace_bytes(B, Cc, H, W, _io_dtype(u), num_steps), u.device)
+        gout, gtraj = _cotangents(g, u, steps)
+        gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
+        io = () if f64 else (_io_dtype(u),)
+        ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(B, Cc, H, W, *io, num_steps), u.device)
         with torch.cuda.device(u.device):
-            L.check(lib.pde_explicit5_backward(B, Cc, H, W, _io_dtype(u), _ptr(u), _ptr(states), _ptr(gout), _ptr(a), _ptr(s),
-                                               dt, eps, max_coeff, relax, num_steps, _ptr(gu), _ptr(ga), _ptr(gs), _ptr(ws),
-                                               ws.numel(), _stream()), "pde_explicit5_backward")
-        return gu, ga, gs, None, None, None, None, None
+            L.check(getattr(lib, fam + "backward_states")(B, Cc, H, W, *io, _ptr(u), _ptr(states), _ptr(gout), _ptr(gtraj),
+                                                          None if steps is None else _mask128(bits), _ptr(a), _ptr(s), dt,
+                                                          eps, max_coeff, relax, num_steps, _ptr(gu), _ptr(ga), _ptr(gs),
+                                                          _ptr(ws), ws.numel(), _stream()), fam + "backward_states")
+        return (gu, _grad_as(ga, ctx.p_dtypes[0]), _grad_as(gs, ctx.p_dtypes[1])) + (None,) * 8
 
 
 def explicit5_step(u, alpha_base, channel_scaling, dt=0.01, eps=1e-6, max_coeff=0.15, relax=0.1, num_steps=1):
     """``num_steps`` relaxed explicit 5-point steps in one call — tiny_imagenet.py:38-49,53-72."""
     if u.shape[0] == 0 or num_steps < 1:
         return _empty_passthrough(u, alpha_base, channel_scaling)
-    if _is_f64(u, alpha_base, channel_scaling):
-        return _Explicit5F64Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
-                                     int(num_steps))
-    return _Explicit5Fn.apply(_io_in(u, alpha_base, channel_scaling), alpha_base, channel_scaling, float(dt), float(eps),
-                              float(max_coeff), float(relax), int(num_steps))
+    f64 = _is_f64(u, alpha_base, channel_scaling)
+    if not f64:
+        u = _io_in(u, alpha_base, channel_scaling)
+    return _Explicit5Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
+                              int(num_steps), None, None, f64)
 
 
 class _JacobiFn(torch.autograd.Function):
-    """fp32 tensors (pde_jacobi_*), or fp16 ones on the float16 route (pde_jacobi_io_*: the same kernels with fp16 I/O)."""
+    """fp32 tensors, fp16 ones on the float16 route (pde_jacobi_io_*: the same kernels with fp16 I/O; anything else is
+    widened to fp32), or float64 (pde_jacobi_f64_*)."""
 
     @staticmethod
-    def forward(ctx, u, a_row, b_col, nt):
+    def forward(ctx, u, a_row, b_col, nt, steps, bits, f64):
         lib = L.load()
         _require_cuda(u, a_row, b_col)
-        u = (u if u.dtype == torch.float16 else u.float()).contiguous()
+        fam, kt = ("pde_jacobi_f64_", torch.float64) if f64 else ("pde_jacobi_io_", torch.float32)
+        u = _kernel_input(u, f64, (torch.float32, torch.float16))
         B, H, W = u.shape
-        a = a_row.detach().float().contiguous()
-        b = b_col.detach().float().contiguous()
-        out = torch.empty_like(u)
+        a, b = _kernel_param(a_row, kt), _kernel_param(b_col, kt)
+        res, out, traj = _out_and_traj(u, steps)
         with torch.cuda.device(u.device):
-            fws = lib.pde_jacobi_forward_workspace_bytes(B, H, W, nt)
-            if fws:     # a tiled plane with more steps than one launch takes: the launches chain through a workspace
-                ws = _workspace(fws, u.device)
-                L.check(lib.pde_jacobi_io_forward_ws(B, H, W, nt, L.PDE_IO_F16 if u.dtype == torch.float16 else L.PDE_IO_F32,
-                                                     _ptr(u), _ptr(a), _ptr(b), _ptr(out), _ptr(ws), ws.numel(), _stream()),
-                        "pde_jacobi_io_forward_ws")
-            elif u.dtype == torch.float16:
-                L.check(lib.pde_jacobi_io_forward(B, H, W, nt, L.PDE_IO_F16, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
-                        "pde_jacobi_io_forward")
+            if f64:
+                io, fws = (), ()
             else:
-                L.check(lib.pde_jacobi_forward(B, H, W, nt, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
-                        "pde_jacobi_forward")
+                # a tiled plane with more steps than one launch takes: the launches chain through a workspace
+                n = lib.pde_jacobi_forward_workspace_bytes(B, H, W, nt)
+                ws = _workspace(n, u.device) if n else None
+                io, fws = (_io_dtype(u),), (_ptr(ws), ws.numel() if n else 0)
+            L.check(getattr(lib, fam + "forward_states")(B, H, W, nt, *io, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _ptr(traj),
+                                                         None if steps is None else _mask128(bits), *fws, _stream()),
+                    fam + "forward_states")
         ctx.save_for_backward(u, a, b)
-        ctx.nt = nt
-        return out
+        ctx.cfg = (nt, steps, bits, f64)
+        ctx.p_dtypes = (a_row.dtype, b_col.dtype)
+        return res
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, g):
         lib = L.load()
         u, a, b = ctx.saved_tensors
+        nt, steps, bits, f64 = ctx.cfg
+        fam = "pde_jacobi_f64_" if f64 else "pde_jacobi_io_"
         B, H, W = u.shape
-        gout = gout.to(u.dtype).contiguous()
+        gout, gtraj = _cotangents(g, u, steps)
         gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
+        io = () if f64 else (_io_dtype(u),)
         with torch.cuda.device(u.device):
-            if u.dtype == torch.float16:
-                ws = _workspace(lib.pde_jacobi_io_backward_workspace_bytes(B, H, W, ctx.nt, L.PDE_IO_F16), u.device)
-                L.check(lib.pde_jacobi_io_backward(B, H, W, ctx.nt, L.PDE_IO_F16, _ptr(u), _ptr(gout), _ptr(a), _ptr(b),
-                                                   _ptr(gu), _ptr(ga), _ptr(gb), _ptr(ws), ws.numel(), _stream()),
-                        "pde_jacobi_io_backward")
-            else:
-                ws = _workspace(lib.pde_jacobi_backward_workspace_bytes(B, H, W, ctx.nt), u.device)
-                L.check(lib.pde_jacobi_backward(B, H, W, ctx.nt, _ptr(u), _ptr(gout), _ptr(a), _ptr(b), _ptr(gu), _ptr(ga),
-                                                _ptr(gb), _ptr(ws), ws.numel(), _stream()), "pde_jacobi_backward")
-        return gu, ga, gb, None
+            ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(B, H, W, nt, *io), u.device)
+            L.check(getattr(lib, fam + "backward_states")(B, H, W, nt, *io, _ptr(u), _ptr(gout), _ptr(gtraj),
+                                                          None if steps is None else _mask128(bits), _ptr(a), _ptr(b),
+                                                          _ptr(gu), _ptr(ga), _ptr(gb), _ptr(ws), ws.numel(), _stream()),
+                    fam + "backward_states")
+        return gu, _grad_as(ga, ctx.p_dtypes[0]), _grad_as(gb, ctx.p_dtypes[1]), None, None, None, None
 
 
 def jacobi_diffuse(u, a_row, b_col, nt: int):
     """emotion_recognition.py:82-97 on (B,H,W): reflect-pad once, ``nt`` Jacobi updates."""
     if u.shape[0] == 0:
         return _empty_passthrough(u, a_row, b_col)
-    if _is_f64(u, a_row, b_col):
-        return _JacobiF64Fn.apply(u, a_row, b_col, int(nt))
-    return _JacobiFn.apply(_io_in(u, a_row, b_col), a_row, b_col, int(nt))
+    f64 = _is_f64(u, a_row, b_col)
+    if not f64:
+        u = _io_in(u, a_row, b_col)
+    return _JacobiFn.apply(u, a_row, b_col, int(nt), None, None, f64)
 
 
 # --------------------------------------------------------------------------- trajectories of the explicit layers
@@ -1891,68 +1806,6 @@ def _emit_steps(steps):
     return sel, sum(1 << (k - 1) for k in sel[:-1])
 
 
-def _emit_mask(bits: int):
-    return (C.c_uint64 * 2)(bits & _M64, bits >> 64)
-
-
-class _JacobiStatesFn(torch.autograd.Function):
-    """``_JacobiFn`` / ``_JacobiF64Fn`` that also return the state after chosen time steps, out of the plain call's launches
-    (pde_jacobi_io_*_states, pde_jacobi_f64_*_states).  The result is ONE tensor (K', B, H, W); the library's ``out`` is
-    its last slice."""
-
-    @staticmethod
-    def forward(ctx, u, a_row, b_col, steps, bits, f64):
-        lib = L.load()
-        _require_cuda(u, a_row, b_col)
-        nt, K = steps[-1], len(steps)
-        if f64:
-            u = u.to(torch.float64).contiguous()
-            a, b = _d64(a_row), _d64(b_col)
-        else:
-            u = (u if u.dtype == torch.float16 else u.float()).contiguous()
-            a = a_row.detach().float().contiguous()
-            b = b_col.detach().float().contiguous()
-        B, H, W = u.shape
-        out = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
-        with torch.cuda.device(u.device):
-            if f64:
-                L.check(lib.pde_jacobi_f64_forward_states(B, H, W, nt, _ptr(u), _ptr(a), _ptr(b), _ptr(out[K - 1]), _ptr(out),
-                                                          _emit_mask(bits), _stream()), "pde_jacobi_f64_forward_states")
-            else:
-                # a tiled plane with more steps than one launch takes: the launches chain through a workspace
-                fws = lib.pde_jacobi_forward_workspace_bytes(B, H, W, nt)
-                ws = _workspace(fws, u.device) if fws else None
-                L.check(lib.pde_jacobi_io_forward_states(B, H, W, nt, _io_dtype(u), _ptr(u), _ptr(a), _ptr(b), _ptr(out[K - 1]),
-                                                         _ptr(out), _emit_mask(bits), _ptr(ws), ws.numel() if fws else 0,
-                                                         _stream()), "pde_jacobi_io_forward_states")
-        ctx.save_for_backward(u, a, b)
-        ctx.cfg = (nt, K, bits, f64)
-        ctx.p_dtypes = (a_row.dtype, b_col.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = L.load()
-        u, a, b = ctx.saved_tensors
-        nt, K, bits, f64 = ctx.cfg
-        B, H, W = u.shape
-        g = g.to(u.dtype).contiguous()                   # slots 0..K-2 are gstates, the last slice is gout
-        gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
-        with torch.cuda.device(u.device):
-            if f64:
-                ws = _workspace(lib.pde_jacobi_f64_backward_workspace_bytes(B, H, W, nt), u.device)
-                L.check(lib.pde_jacobi_f64_backward_states(B, H, W, nt, _ptr(u), _ptr(g[K - 1]), _ptr(g), _emit_mask(bits),
-                                                           _ptr(a), _ptr(b), _ptr(gu), _ptr(ga), _ptr(gb), _ptr(ws), ws.numel(),
-                                                           _stream()), "pde_jacobi_f64_backward_states")
-            else:
-                io = _io_dtype(u)
-                ws = _workspace(lib.pde_jacobi_io_backward_workspace_bytes(B, H, W, nt, io), u.device)
-                L.check(lib.pde_jacobi_io_backward_states(B, H, W, nt, io, _ptr(u), _ptr(g[K - 1]), _ptr(g), _emit_mask(bits),
-                                                          _ptr(a), _ptr(b), _ptr(gu), _ptr(ga), _ptr(gb), _ptr(ws), ws.numel(),
-                                                          _stream()), "pde_jacobi_io_backward_states")
-        return gu, ga.to(ctx.p_dtypes[0]), gb.to(ctx.p_dtypes[1]), None, None, None
-
-
 def jacobi_diffuse_states(u, a_row, b_col, steps):
     """``jacobi_diffuse`` that returns the trajectory: the state after every time step listed in ``steps`` (strictly
     increasing 1-based step numbers; ``max(steps)`` steps are run, at most 128) as ONE tensor ``(len(steps),) + u.shape``,
@@ -1969,74 +1822,7 @@ def jacobi_diffuse_states(u, a_row, b_col, steps):
     f64 = _is_f64(u, a_row, b_col)
     if not f64:
         u = _io_in(u, a_row, b_col)
-    return _JacobiStatesFn.apply(u, a_row, b_col, sel, bits, f64)
-
-
-class _Explicit5StatesFn(torch.autograd.Function):
-    """``_Explicit5Fn`` / ``_Explicit5F64Fn`` that also return the state after chosen steps, out of the plain call's
-    launches (pde_explicit5_*_states, pde_explicit5_f64_*_states).  The result is ONE tensor (K', B, C, H, W); the
-    library's ``out`` is its last slice."""
-
-    @staticmethod
-    def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, steps, bits, f64):
-        lib = L.load()
-        _require_cuda(u, alpha_base, channel_scaling)
-        num_steps, K = steps[-1], len(steps)
-        need_grad = any(ctx.needs_input_grad[:3])
-        if f64:
-            u = u.to(torch.float64).contiguous()
-            a, s = _d64(alpha_base), _d64(channel_scaling)
-            fused = False
-        else:
-            if u.dtype not in _IO_TYPES:
-                u = u.float()
-            u = u.contiguous()
-            a = alpha_base.detach().to(torch.float32).contiguous()
-            s = channel_scaling.detach().to(torch.float32).contiguous()
-            fused = tuple(u.shape[2:]) in ((64, 64), (32, 32), (16, 16))
-        B, Cc, H, W = u.shape
-        out = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
-        # the inputs of steps 2..num_steps, as the plain call keeps them (fp32, or doubles): what the backward reads
-        states = torch.empty((num_steps - 1,) + tuple(u.shape), dtype=torch.float64 if f64 else torch.float32,
-                             device=u.device) if num_steps > 1 and (need_grad or not fused) else None
-        with torch.cuda.device(u.device):
-            if f64:
-                L.check(lib.pde_explicit5_f64_forward_states(B, Cc, H, W, _ptr(u), _ptr(a), _ptr(s), dt, eps, max_coeff, relax,
-                                                             num_steps, _ptr(states), _ptr(out[K - 1]), _ptr(out),
-                                                             _emit_mask(bits), _stream()), "pde_explicit5_f64_forward_states")
-            else:
-                L.check(lib.pde_explicit5_forward_states(B, Cc, H, W, _io_dtype(u), _ptr(u), _ptr(a), _ptr(s), dt, eps,
-                                                         max_coeff, relax, num_steps, _ptr(states), _ptr(out[K - 1]),
-                                                         _ptr(out), _emit_mask(bits), _stream()),
-                        "pde_explicit5_forward_states")
-        ctx.save_for_backward(u, states if need_grad else None, a, s)
-        ctx.cfg = (dt, eps, max_coeff, relax, num_steps, K, bits, f64)
-        ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = L.load()
-        u, states, a, s = ctx.saved_tensors
-        dt, eps, max_coeff, relax, num_steps, K, bits, f64 = ctx.cfg
-        B, Cc, H, W = u.shape
-        g = g.to(u.dtype).contiguous()                   # slots 0..K-2 are gtraj, the last slice is gout
-        gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
-        with torch.cuda.device(u.device):
-            if f64:
-                ws = _workspace(lib.pde_explicit5_f64_backward_workspace_bytes(B, Cc, H, W, num_steps), u.device)
-                L.check(lib.pde_explicit5_f64_backward_states(B, Cc, H, W, _ptr(u), _ptr(states), _ptr(g[K - 1]), _ptr(g),
-                                                              _emit_mask(bits), _ptr(a), _ptr(s), dt, eps, max_coeff, relax,
-                                                              num_steps, _ptr(gu), _ptr(ga), _ptr(gs), _ptr(ws), ws.numel(),
-                                                              _stream()), "pde_explicit5_f64_backward_states")
-            else:
-                io = _io_dtype(u)
-                ws = _workspace(lib.pde_explicit5_backward_workspace_bytes(B, Cc, H, W, io, num_steps), u.device)
-                L.check(lib.pde_explicit5_backward_states(B, Cc, H, W, io, _ptr(u), _ptr(states), _ptr(g[K - 1]), _ptr(g),
-                                                          _emit_mask(bits), _ptr(a), _ptr(s), dt, eps, max_coeff, relax,
-                                                          num_steps, _ptr(gu), _ptr(ga), _ptr(gs), _ptr(ws), ws.numel(),
-                                                          _stream()), "pde_explicit5_backward_states")
-        return gu, ga.to(ctx.p_dtypes[0]), gs.to(ctx.p_dtypes[1]), None, None, None, None, None, None, None
+    return _JacobiFn.apply(u, a_row, b_col, sel[-1], sel, bits, f64)
 
 
 def explicit5_states(u, alpha_base, channel_scaling, dt=0.01, eps=1e-6, max_coeff=0.15, relax=0.1, steps=(1,)):
@@ -2054,8 +1840,8 @@ def explicit5_states(u, alpha_base, channel_scaling, dt=0.01, eps=1e-6, max_coef
     f64 = _is_f64(u, alpha_base, channel_scaling)
     if not f64:
         u = _io_in(u, alpha_base, channel_scaling)
-    return _Explicit5StatesFn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
-                                    sel, bits, f64)
+    return _Explicit5Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
+                              sel[-1], sel, bits, f64)
 
 
 # --------------------------------------------------------------------------- SVHN skip connection
@@ -2107,8 +1893,9 @@ def skip_blend(u0, u, skip_weight):
 
 # --------------------------------------------------------------------------- float64
 # A call takes the float64 path when its input or any floating parameter is float64 (torch's type promotion, which the
-# reference's ops follow): the output is float64 and every gradient comes back in its own tensor's dtype.  The functions
-# below run the pde_*_f64_* entry points (double arithmetic throughout); there is no float64 host-extension path.
+# reference's ops follow): the output is float64 and every gradient comes back in its own tensor's dtype.  The layer
+# families' nodes (_AdiFn, _Explicit5Fn, _JacobiFn) take it as their ``f64`` switch; the functions below run the other
+# pde_*_f64_* entry points (double arithmetic throughout).  There is no float64 host-extension path.
 def _is_f64(*ts) -> bool:
     return any(isinstance(t, torch.Tensor) and t.dtype == torch.float64 for t in ts)
 
@@ -2117,92 +1904,12 @@ def _d64(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float64).contiguous()
 
 
-_desc64_cache = {}
-
-
-def _make_desc64(B, Cc, N, sweeps: Sequence[Sweep], smooth3, clamp_max, eps) -> L.PdeAdiDescF64:
-    key = (B, Cc, N, sweeps, bool(smooth3), clamp_max, float(eps))
-    d = _desc64_cache.get(key)
-    if d is None:
-        if len(sweeps) > L.PDE_MAX_SWEEPS:
-            raise L.PdeError(f"{len(sweeps)} sweeps in one launch exceed PDE_MAX_SWEEPS={L.PDE_MAX_SWEEPS}")
-        if len(_desc64_cache) > 256:
-            _desc64_cache.clear()
-        d = L.PdeAdiDescF64()
-        d.B, d.C, d.N, d.io_dtype, d.num_sweeps = B, Cc, N, L.PDE_IO_F64, len(sweeps)
-        d.smooth3 = int(bool(smooth3))
-        d.has_clamp_max = int(clamp_max is not None)
-        d.clamp_max = float(clamp_max) if clamp_max is not None else 0.0
-        d.eps = float(eps)
-        for i, sw in enumerate(sweeps):
-            d.sweep[i].axis, d.sweep[i].delta, d.sweep[i].h2, d.sweep[i].t = int(sw.axis), sw.delta, sw.h2, sw.t
-        _desc64_cache[key] = d
-    return d
-
-
-def _as_chw64(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.Tensor:
-    W = N if W is None else W
-    q = p.detach()
-    if q.dim() == 2:
-        q = q.unsqueeze(0)
-    if tuple(q.shape) != (Cc, N, W):
-        raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{W})")
-    return q.to(torch.float64).contiguous()
-
-
 def _f64_ckpt_bits(ckpt, num_sweeps: int) -> int:
     """The backward's checkpoint mask in float64: an int is honoured; "auto" / "lagged" keep the state after every sweep
     (nothing is rebuilt, so no rounding is amplified: the plan needs no coefficient maxima)."""
     if isinstance(ckpt, int) and not isinstance(ckpt, bool):
         return int(ckpt)
     return (1 << max(num_sweeps - 1, 0)) - 1
-
-
-class _AdiF64Fn(torch.autograd.Function):
-    """adi_diffuse in float64 (pde_adi_f64_*)."""
-
-    @staticmethod
-    def forward(ctx, u, ab, bb, asl, bsl, sweeps, smooth3, clamp_max, eps, ckpt):
-        lib = L.load()
-        _require_cuda(u, ab, bb, asl, bsl)
-        if u.dim() != 4 or u.shape[2] != u.shape[3]:
-            raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
-        B, Cc, N, _ = u.shape
-        u = u.to(torch.float64).contiguous()
-        p = [_as_chw64(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        d = _make_desc64(B, Cc, N, sweeps, smooth3, clamp_max, eps)
-        y = torch.empty_like(u)
-        ws = _workspace(lib.pde_adi_f64_forward_workspace_bytes(C.byref(d)), u.device)
-        need_grad = any(ctx.needs_input_grad[:5])
-        bits = _f64_ckpt_bits(ckpt, len(sweeps))
-        with torch.cuda.device(u.device):
-            L.check(lib.pde_adi_f64_forward(C.byref(d), _ptr(u), _ptr(y), *[_ptr(t) for t in p], None, _ptr(ws), ws.numel(),
-                                            _stream()), "pde_adi_f64_forward")
-        ctx.fwd_ws = ws if need_grad else None
-        ctx.save_for_backward(y, u if (need_grad and bits) else None, *p)
-        ctx.cfg = (sweeps, smooth3, clamp_max, eps, bits)
-        ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        lib = L.load()
-        y, u, *p = ctx.saved_tensors
-        sweeps, smooth3, clamp_max, eps, bits = ctx.cfg
-        B, Cc, N, _ = y.shape
-        gy = gy.to(torch.float64).contiguous()
-        d = _make_desc64(B, Cc, N, sweeps, smooth3, clamp_max, eps)
-        gu = torch.empty_like(y)
-        gp = [torch.empty_like(t) for t in p]
-        mask = (C.c_uint64 * 2)(bits & _M64, bits >> 64)
-        ws = _workspace(lib.pde_adi_f64_backward_workspace_bytes(C.byref(d), bin(bits).count("1")), y.device)
-        with torch.cuda.device(y.device):
-            L.check(lib.pde_adi_f64_backward(C.byref(d), _ptr(gy), _ptr(y), _ptr(u if bits else None), mask, _ptr(gu),
-                                             *[_ptr(t) for t in p], *[_ptr(t) for t in gp], _ptr(ctx.fwd_ws), _ptr(ws),
-                                             ws.numel(), _stream()), "pde_adi_f64_backward")
-        ctx.fwd_ws = None
-        gp = [g.reshape(s).to(dt) for g, (s, dt) in zip(gp, ctx.param_meta)]
-        return (gu, *gp, None, None, None, None, None)
 
 
 class _MixF64Fn(torch.autograd.Function):
@@ -2267,71 +1974,6 @@ class _SkipBlendF64Fn(torch.autograd.Function):
                                                     _ptr(g_w), _ptr(ws), ws.numel(), _stream()), "pde_skip_blend_f64_backward")
         d0, d1, dw, shw = ctx.in_meta
         return g_a.to(d0), g_b.to(d1), g_w.to(dw).reshape(shw)
-
-
-class _Explicit5F64Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, num_steps):
-        lib = L.load()
-        _require_cuda(u, alpha_base, channel_scaling)
-        u = u.to(torch.float64).contiguous()
-        B, Cc, H, W = u.shape
-        a, s = _d64(alpha_base), _d64(channel_scaling)
-        out = torch.empty_like(u)
-        states = torch.empty((num_steps - 1,) + tuple(u.shape), dtype=torch.float64, device=u.device) if num_steps > 1 else None
-        with torch.cuda.device(u.device):
-            L.check(lib.pde_explicit5_f64_forward(B, Cc, H, W, _ptr(u), _ptr(a), _ptr(s), dt, eps, max_coeff, relax, num_steps,
-                                                  _ptr(states), _ptr(out), _stream()), "pde_explicit5_f64_forward")
-        ctx.save_for_backward(u, states, a, s)
-        ctx.cfg = (dt, eps, max_coeff, relax, num_steps)
-        ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = L.load()
-        u, states, a, s = ctx.saved_tensors
-        dt, eps, max_coeff, relax, num_steps = ctx.cfg
-        B, Cc, H, W = u.shape
-        gout = gout.to(torch.float64).contiguous()
-        gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
-        ws = _workspace(lib.pde_explicit5_f64_backward_workspace_bytes(B, Cc, H, W, num_steps), u.device)
-        with torch.cuda.device(u.device):
-            L.check(lib.pde_explicit5_f64_backward(B, Cc, H, W, _ptr(u), _ptr(states), _ptr(gout), _ptr(a), _ptr(s), dt, eps,
-                                                   max_coeff, relax, num_steps, _ptr(gu), _ptr(ga), _ptr(gs), _ptr(ws),
-                                                   ws.numel(), _stream()), "pde_explicit5_f64_backward")
-        return gu, ga.to(ctx.p_dtypes[0]), gs.to(ctx.p_dtypes[1]), None, None, None, None, None
-
-
-class _JacobiF64Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, a_row, b_col, nt):
-        lib = L.load()
-        _require_cuda(u, a_row, b_col)
-        u = u.to(torch.float64).contiguous()
-        B, H, W = u.shape
-        a, b = _d64(a_row), _d64(b_col)
-        out = torch.empty_like(u)
-        with torch.cuda.device(u.device):
-            L.check(lib.pde_jacobi_f64_forward(B, H, W, nt, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _stream()),
-                    "pde_jacobi_f64_forward")
-        ctx.save_for_backward(u, a, b)
-        ctx.nt = nt
-        ctx.p_dtypes = (a_row.dtype, b_col.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = L.load()
-        u, a, b = ctx.saved_tensors
-        B, H, W = u.shape
-        gout = gout.to(torch.float64).contiguous()
-        gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
-        ws = _workspace(lib.pde_jacobi_f64_backward_workspace_bytes(B, H, W, ctx.nt), u.device)
-        with torch.cuda.device(u.device):
-            L.check(lib.pde_jacobi_f64_backward(B, H, W, ctx.nt, _ptr(u), _ptr(gout), _ptr(a), _ptr(b), _ptr(gu), _ptr(ga),
-                                                _ptr(gb), _ptr(ws), ws.numel(), _stream()), "pde_jacobi_f64_backward")
-        return gu, ga.to(ctx.p_dtypes[0]), gb.to(ctx.p_dtypes[1]), None
 
 
 # --------------------------------------------------------------------------- timing

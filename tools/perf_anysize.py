@@ -36,7 +36,7 @@ def run(B, C, H, W, entry="old", n=10):
             p.grad = None
         u.grad = None
         if entry == "rect" and H == W:          # the layer sends squares to the square entry points: call the function itself
-            y = F_._AdiRectFn.apply(u, *args, sweeps, False, ly._clamp_max, ly.stability_eps, "auto", None, False)
+            y = F_._AdiFn.apply(u, *args, sweeps, False, ly._clamp_max, ly.stability_eps, "auto", None, None, True, False)
         else:
             y = ly(u)
         y.backward(gy)
