@@ -1,7 +1,8 @@
 """Case generators and fp64 references for the coefficient stage of the implicit (ADI) layers: theta = clamp(base +
 slope*t, eps[, max]) (mnist_test.py:33-42, cifar10.py:53-63), the optional 3-tap smoothing (mnist_test.py:135-149), the
 clamp's pass-through mask in the backward, the per-channel "mask moves in time" flag and the per-sweep coefficient maxima.
-tests/test_adi_edge_cases.py checks what is built here on the CPU; tests/test_gpu_adi_edges.py holds every kernel path to it.
+tests/test_adi_edge_cases.py checks what is built here on the CPU; tests/test_gpu_adi_edges.py holds every kernel path to it
+(families A .. G; G is the one-launch wide forward at C = 32 / 64 with its lane-major copy of the coefficient records).
 
 Exact inputs.  Everything that decides a mask is dyadic — eps = 2**-20, clamp_max = 8, dt = 2**-4, bases multiples of 2**-6,
 slopes multiples of 2**-3, sweep times multiples of dt/2 — so base + slope*t has at most 24 significant bits: a tie with a
@@ -69,7 +70,7 @@ def schedule(kind: str, steps: int = 0) -> Tuple[Tuple[int, float, float], ...]:
 @dataclass(frozen=True)
 class Case:
     name: str
-    family: str                       # "A" .. "F"
+    family: str                       # "A" .. "G"
     N: int
     C: int
     B: int
@@ -391,7 +392,15 @@ def _cases() -> List[Case]:
         Case("F-n16-emitted-only", "F", 16, 2, 3, "strang", 3, smooth3=True, ckpt="auto", cstar=0, rot=5, emit=(7,),
              gy_last_zero=True),
     ]
-    return A + Bf + Cf + D + E + Ff
+    # the one-launch wide forward (C = 32 / 64, pde_adi_wide.h): its own lane-major copy of the coefficient records, and —
+    # with a step-local checkpoint mask — the backward that first recomputes the operator outputs the forward did not keep
+    Gf = [
+        Case("G-c32-n28-strang-pre-smooth", "G", 28, 32, 2, "strang", 3, smooth3=True, ckpt=0, cstar=30, rot=1, mix="pre"),
+        Case("G-c64-n32-lie-post", "G", 32, 64, 2, "lie", 3, ckpt=0, cstar=63, rot=2, mix="post"),
+        Case("G-c32-n32-strang-post-smooth", "G", 32, 32, 2, "strang", 3, smooth3=True, ckpt=0, cstar=7, rot=4, mix="post"),
+    ]
+    Gf += [dataclasses.replace(c, name=c.name + "-ckpt", ckpt=m) for c, m in zip(Gf, (0b10, 0b01, 0b01))]
+    return A + Bf + Cf + D + E + Ff + Gf
 
 
 #: seeds the CPU conditions accepted (test_adi_edge_cases.py::test_noise_and_separation): the case's index, plus 100 for

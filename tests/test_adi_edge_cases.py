@@ -17,7 +17,8 @@ def _oracle_spec(case):
 
 
 @pytest.mark.parametrize("name", ["A-n8-c3-strang", "A-n12-c2-smooth-all", "A-n20-c3-lie-auto", "A-n32-c3-lie-dx2",
-                                  "C-c5-pre", "C-c8-post-smooth", "D-c4-n16-post"])
+                                  "C-c5-pre", "C-c8-post-smooth", "D-c4-n16-post",
+                                  "G-c32-n28-strang-pre-smooth", "G-c64-n32-lie-post", "G-c32-n32-strang-post-smooth"])
 def test_reference_is_the_oracles_autograd(name):
     """Strang and Lie schedules, with and without a channel operator: 1e-13 of ``O.adi_forward`` under autograd."""
     case = E.BY_NAME[name]

@@ -2,7 +2,9 @@
 adi_pgrad_kernel of csrc/pde_adi.hip and gen_factor / gen_bwd_kernel of csrc/pde_adi_gen.hip — held to fp64 at its clamp
 and smoothing edges, through every backward body that consumes the pass-through mask and the per-channel flag: the two
 halves of the HIP backward's grid (A), the assembly backward with its masked-only launch (B), the per-step launches of a
-layer with a channel operator (C), the one-launch C <= 4 kernel (D), the any-size kernel (E) and the emitting variant (F).
+layer with a channel operator (C), the one-launch C <= 4 kernel (D), the any-size kernel (E), the emitting variant (F), and
+the one-launch wide forward at C = 32 / 64, which reads its own lane-major copy of the records, with the per-step backward
+behind it — without checkpoints and with a step-local mask, which first recomputes the operator outputs in place (G).
 
 Cases, scenarios S1-S8 and the fp64 reference: tests/adi_edge_cases.py (checked on the CPU by tests/test_adi_edge_cases.py,
 which also shows that a wrong comparison operator, a mask taken from the wrong sweep or time, or a wrong end weight of the
@@ -71,6 +73,11 @@ def assert_path(case, p, ud):
         assert (path, fwd, bwd) == (2, 2, 2)
         return
     assert path == 1
+    if case.family == "G":                                           # the one-launch wide forward (pde_adi_wide.h)
+        assert lib.pde_adi_mixed_one_launch(ctypes.byref(d), {"strang": 3, "lie": 2}[case.sched]) == 1
+        assert not F.adi_small_supported(ud, _steps(case), case.smooth3, case.clamp_max, E.EPS)
+        assert (_nck(case, p) > 0) == case.name.endswith("-ckpt")    # the twin reaches the backward's recompute branch
+        return
     if case.family == "B":
         assert fwd == FWD_KERNEL_B
         assert bwd == (0 if case.name.endswith("-ckpt") else 1)     # 1: assembly kernel, then the masked-only launch
@@ -94,7 +101,7 @@ def run(case):
     assert_path(case, p, ud)
     kw = dict(smooth3=case.smooth3, clamp_max=case.clamp_max, eps=E.EPS, checkpoints=case.ckpt_bits())
     four = [ps[k] for k in E.NAMES]
-    if case.family == "C":
+    if case.family in ("C", "G"):
         y = F.adi_diffuse_mixed(ud, *four, ps["M"], _steps(case), case.mix, **kw)
     elif case.family == "D":
         y = F.adi_diffuse_small(ud, *four, ps["M"], _steps(case), case.mix, **kw)

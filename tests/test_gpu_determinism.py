@@ -1,6 +1,7 @@
 """GPU: repeated calls give bitwise identical, finite results whatever other kernels left in LDS in between — for
 every supported line length (lanes beyond the plane exist for N < 32), the plain layers, the layers with a channel
-operator on the per-step, one-launch (C <= 4) and shared-input paths, masked (time-varying clamp) channels included.
+operator on the per-step, one-launch (C <= 4), one-launch wide (C = 32 / 64) and shared-input paths, masked (time-varying
+clamp) channels included.
 A sum that multiplies by a 0/1 lane factor, or an idle lane that reads LDS nobody wrote, shows up here as a NaN or as a
 difference between repetitions."""
 import contextlib
@@ -104,6 +105,38 @@ def test_shared_input_group_and_svhn_layer_are_deterministic_and_finite(N):
         sv.alpha_base.mul_(15.0)
         sv.beta_base.mul_(15.0)
     _repeat(_fwd_bwd(sv, u, gy))
+
+
+@pytest.mark.parametrize("kind", ["enhanced", "svhn"])
+@pytest.mark.parametrize("N,C", [(28, 32), (28, 64), (32, 64)])
+def test_wide_one_launch_layers_are_deterministic_and_finite(N, C, kind):
+    """The one-launch forward at C = 32 / 64 (pde_adi_wide.h): a wave's private re-layout image lies inside its slice of
+    the exchange image, which the matrix-core phase of every operator overwrites with products, and at N = 28 idle lanes
+    read it.  The SVHN layer's coefficients are large enough that the backward parks states inside the steps and
+    recomputes, in place, the operator outputs the forward did not keep."""
+    import ctypes
+
+    import cnn_with_pde_amd as P
+    from cnn_with_pde_amd import _lib as L
+    from cnn_with_pde_amd import functional as F_
+    g = torch.Generator().manual_seed(3000 + 10 * N + C)
+    if kind == "enhanced":
+        layer = quiet(P.EnhancedDiffusionLayer, N, C, dt=0.05, num_steps=3).cuda()
+        _perturb(layer, g, 25.0)             # slopes large enough to cross the clamp bounds: masked channels
+    else:
+        layer = P.SvhnDiffusionLayer(N, C, dt=0.3, num_steps=3).cuda()
+        _perturb(layer, g, 0.2)
+        with torch.no_grad():
+            layer.alpha_base.mul_(15.0)
+            layer.beta_base.mul_(15.0)
+        layer.checkpoint_policy = 0b01       # park the state after every step's first sweep, whatever the plan would say
+    B = 37
+    sched = layer._schedule()
+    d = F_._make_desc(B, C, N, L.PDE_IO_F32, sched.flat, layer._smooth3, layer._clamp_max, layer.stability_eps)
+    assert L.load().pde_adi_mixed_one_launch(ctypes.byref(d), len(sched[0])) == 1
+    u = torch.randn(B, C, N, N, generator=g).cuda()
+    gy = torch.randn(B, C, N, N, generator=g).cuda()
+    _repeat(_fwd_bwd(layer, u, gy))
 
 
 @pytest.mark.parametrize("size,steps,dtype", [(16, 2, torch.float32), (32, 1, torch.bfloat16), (64, 3, torch.float32),
