@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Write code objects as C byte arrays plus a table: blob_to_inc.py out.inc spec=file [spec=file ...]
-(spec = "<waves>[b|c]" or "<waves>[b|c]a<bits>", see gen_adi_bwd_asm.py)."""
+(spec = "<waves>[b|c|d]" or "<waves>[b|c|d]a<bits>", see gen_adi_bwd_asm.py)."""
 import sys
 
 if "--fwd" in sys.argv:                      # the forward kernels' table: out.inc --fwd <waves>[t]=file ...
@@ -23,7 +23,7 @@ with open(sys.argv[1], "w") as out:
     for spec in sys.argv[2:]:
         name, path = spec.split("=", 1)
         data = open(path, "rb").read()
-        nw = int(name.split("a")[0].rstrip("bc"))
+        nw = int(name.split("a")[0].rstrip("bcd"))
         out.write(f"alignas(4096) static const unsigned char kAsmBlob_{name}[{len(data)}] = {{\n")
         for i in range(0, len(data), 32):
             out.write(",".join(str(b) for b in data[i:i + 32]) + ",\n")

@@ -18,7 +18,7 @@ The file is a tiny macro assembler: `Emit` tracks the outstanding LDS / vector-m
 and puts the exact `s_waitcnt lgkmcnt(n)` / `vmcnt(n)` in front of the first instruction that touches a register an
 outstanding load returns into.
 
-usage: gen_adi_bwd_asm.py NW out.s        (NW = waves per workgroup: 8 or 12)
+usage: gen_adi_bwd_asm.py SPEC out.s      (SPEC = "<waves>[b|c|d][a<bits>]", waves per workgroup 8 or 12: see parse_spec)
 """
 import sys
 
@@ -206,10 +206,19 @@ def gen(NW, ABL=0, MODE="A"):
     latency shadow of the next sweep's junction exchange.  MODE "C": MODE B's arithmetic in the same order per element, with
     the scalar work taken out of the time step (bases per chunk, running record / table pointers, the counter targets
     carried from step to step, one poll for both counters, the rare paths out of line) and the wait states of the lane
-    exchanges counted by `Emit` instead of fixed `s_nop`s."""
-    assert NW in (8, 12, 16) and MODE in ("A", "B", "C")
-    BM = MODE in ("B", "C")
-    SC = MODE == "C"
+    exchanges counted by `Emit` instead of fixed `s_nop`s.  MODE "D": MODE C with the two round trips of the step's top
+    issued one step ahead, inside the step's last sweep (which reads no LDS): the next step's time increments go straight
+    into the S_DTS quad once the sweep's junction has used this step's (the one still needed moves to S_D0), and the next
+    step's counter pair is read there too, so that the top only looks at two registers and falls into MODE C's poll (out
+    of line) when a target was not yet met; no static wave priority."""
+    assert NW in (8, 12, 16) and MODE in ("A", "B", "C", "D")
+    BM = MODE in ("B", "C", "D")
+    SC = MODE in ("C", "D")
+    SD = MODE == "D"
+    # MODE D, one candidate at a time (correct results; built only to time each by itself): bit 18 = the counters are not
+    # read ahead, bit 19 = the time increments are not loaded ahead
+    P_AHEAD = SD and not (ABL & 262144)
+    D_AHEAD = SD and not (ABL & 524288)
     NT = NW * 64
     PPI = 2 * NW
     NPI = (3 * PIECES + NW - 1) // NW          # DMA pieces per wave and time step
@@ -230,8 +239,8 @@ def gen(NW, ABL=0, MODE="A"):
     e = Emit()
     e.vop2_only = bool(ABL & 64)
     e.count_haz = SC
-    name = f"adi_bwd_asm_n32_w{NW}" + {"A": "", "B": "b", "C": "c"}[MODE] + (f"a{ABL}" if ABL else "")
-    assert not (SC and ABL & (4 | 8 | 2048 | 8192 | 16384 | 65536)), "diagnostic bits of MODE B only"
+    name = f"adi_bwd_asm_n32_w{NW}" + {"A": "", "B": "b", "C": "c", "D": "d"}[MODE] + (f"a{ABL}" if ABL else "")
+    assert not (SC and ABL & (4 | 8 | 2048 | 16384 | 65536)), "diagnostic bits of MODE B only"
 
     NMARK = 16
 
@@ -354,6 +363,8 @@ def gen(NW, ABL=0, MODE="A"):
         S_RNKK = 31                             # kk >= S_RNKK: load the newest x record's rows (K-1 with twins, else 0)
         S_PFKK = 91                             # kk at which the next chunk's planes are prefetched (per chunk; -1: none)
         NSGPR = 102
+        S_D0 = S_COEF                           # MODE D: the step's x0 increment while the next step's load into S_DTS
+                                                # (the record pointer's argument is dead once S_SRC0 is formed)
 
     # =============================================================================================================
     e.out.append('\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
@@ -644,6 +655,63 @@ def gen(NW, ABL=0, MODE="A"):
             e.salu("s_branch L_poll")
         OOL.append(e.ool(tail))
 
+    def poll_ahead():
+        """MODE D, inside the step's last sweep: the pair the NEXT step's top asks for — ready[other set] and, 8 bytes
+        above it, done[this set] — into the first two prefetch registers, read through VADDRN (free in this sweep; JN is
+        not: with twin records the next step's first sweep holds it like the rows).  Not in a chunk's last step: the next
+        chunk's planes are on their way into those registers, and a chunk's first step polls for itself anyway.  (The
+        skipped read stays in Emit's queue: nothing waits on a count between here and the step's closing drain.)"""
+        assert PF % 2 == 0
+        e.salu(f"s_cmp_eq_u32 s{S_KK}, 0")
+        e.salu("s_cbranch_scc1 L_nopoll")
+        e.valu(f"v_mov_b32 {v(VADDRN)}, s{S_CNTO}", dst=[VADDRN])
+        e.ds_read(f"ds_read2_b32 {vp(PF)}, {v(VADDRN)} offset1:2", [PF, PF + 1], VADDRN)
+        e.label("L_nopoll")
+
+    def flag_poll_sd():
+        """MODE D: the counters were read during the previous step's last sweep (poll_ahead; a chunk's first step finds
+        a zero there).  Both targets met: go on — the counters only grow.  Else MODE C's bounded spin, all of it out of
+        line, through the address VADDRN still holds."""
+        a, b = NQ[0][0], NQ[0][1]
+        e.assert_idle()
+        e.raw(f"v_readfirstlane_b32 s{S_T2}, {v(PF)}")
+        e.raw(f"v_readfirstlane_b32 s{S_T3}, {v(PF + 1)}")
+        e.salu(f"s_cmp_lt_u32 s{S_T2}, s{S_RT}")
+        e.salu("s_cbranch_scc1 L_poll_slow")
+        e.salu(f"s_cmp_lt_u32 s{S_T3}, s{S_DT}")
+        e.salu("s_cbranch_scc1 L_poll_slow")
+        e.label("L_polled")
+
+        def tail():
+            e.label("L_poll_slow")
+            e.salu(f"s_mov_b32 s{S_T1}, 0")
+            e.label("L_poll")
+            e.raw(f"ds_read2_b32 {vp(a)}, {v(VADDRN)} offset1:2")
+            e.raw("s_waitcnt lgkmcnt(0)")
+            e.raw(f"v_readfirstlane_b32 s{S_T2}, {v(a)}")
+            e.raw(f"v_readfirstlane_b32 s{S_T3}, {v(b)}")
+            e.salu(f"s_cmp_lt_u32 s{S_T2}, s{S_RT}")
+            e.salu("s_cbranch_scc1 L_poll_wait")
+            e.salu(f"s_cmp_ge_u32 s{S_T3}, s{S_DT}")
+            e.salu("s_cbranch_scc1 L_polled")
+            e.label("L_poll_wait")
+            e.salu(f"s_add_u32 s{S_T1}, s{S_T1}, 1")
+            e.salu(f"s_cmp_lt_u32 s{S_T1}, 0x100000")             # (never reached unless a count is wrong)
+            e.salu("s_cbranch_scc0 L_polled")
+            e.raw("s_sleep 1")
+            e.salu("s_branch L_poll")
+        OOL.append(e.ool(tail))
+
+    def dts_ahead():
+        """MODE D, inside the step's last sweep, behind its junction (the y increment has been used): the next step's
+        time increments into S_DTS; this step's x0 increment, still to be used by the sweep's own update, moves to S_D0.
+        S_DTSB lies one step (12 bytes) low, so that the offset 12 kk addresses step kk - 1; in a chunk's last step
+        that is the three words in front of the table's increments (inside the table, never used: the chunk's first step
+        loads its own where the chunk starts)."""
+        e.salu(f"s_mul_i32 s{S_T0}, s{S_KK}, 12")
+        e.salu(f"s_mov_b32 s{S_D0}, s{S_DTS[0]}")
+        e.s_load(f"s_load_dwordx4 s[{S_DTS[0]}:{S_DTS[0] + 3}], s[{S_DTSB}:{S_DTSB + 1}], s{S_T0}")   # (+ one spare)
+
     OOL = []                                    # MODE C: rare paths, placed behind the time-step loop
     if FLAGS:
         for i in range(4):
@@ -657,9 +725,11 @@ def gen(NW, ABL=0, MODE="A"):
             e.salu(f"s_mov_b32 s{S_DT}, 0")
         else:
             e.salu(f"s_mov_b32 s{S_TSTEP}, 0")
-    if bool(ABL & 8192) != BM:
+    if bool(ABL & 8192) != (BM and not SD):
         # the second-dispatched half of the waves loses the SIMD's arbitration against its older partner on every
         # instruction and reaches each step barrier ~2k cycles late (tools/asm_timeline.py): one static priority evens it
+        # (MODE D: none — with the step top's waits gone the favoured half only runs further into its wait for the other
+        #  half's `done`, and the launch measured 0.5-0.7 % shorter without it; bit 13 puts it back)
         e.salu(f"s_cmp_lt_u32 s{S_WAVE}, {NW // 2}")
         e.salu("s_cbranch_scc1 L_noprio")
         e.raw("s_setprio 1")
@@ -673,6 +743,10 @@ def gen(NW, ABL=0, MODE="A"):
     stage(32)
     load_dts(S_KK)
     e.drain(vm=False)
+    if D_AHEAD:
+        assert TAB_DTS >= 12
+        e.salu(f"s_sub_u32 s{S_DTSB}, s{S_DTSB}, 12")                # one step low from here on (dts_ahead)
+        e.salu(f"s_subb_u32 s{S_DTSB + 1}, s{S_DTSB + 1}, 0")
     stage(33)
     e.salu(f"s_mov_b32 s{S_Q}, s{S_g}")
     e.drain()
@@ -1221,7 +1295,8 @@ def gen(NW, ABL=0, MODE="A"):
                 e.nvalu += 1
         e.raw("s_mov_b32 exec_lo, -1")
 
-    def sweep_x_b(rec_index, next_rec, relayout_after, deferred, own_t):
+    def sweep_x_b(rec_index, next_rec, relayout_after, deferred, own_t, hooks=None):
+        """hooks: {k: fn} run at the end of element k of the fused pass (MODE D: the next step's loads, issued ahead)"""
         e.comment(f"==== x sweep (held rows), record {rec_index} of the set")
         if next_rec is not None and not SC:
             rec_addr(VADDRN, next_rec)
@@ -1294,6 +1369,8 @@ def gen(NW, ABL=0, MODE="A"):
             for p in (0, 1):
                 e.valu(f"v_fmac_f32 {v(AX + k)}, {v(R[p] + k)}, {v(nqreg(p, k))}", dst=[AX + k], src=[AX + k, R[p] + k, nqreg(p, k)])
             pend = k
+            if hooks and k in hooks:
+                hooks[k]()
         if relayout_after:
             relayout_reads()                    # the adjoint comes back in column layout while the tail below runs
         for p in (0, 1):
@@ -1370,7 +1447,7 @@ def gen(NW, ABL=0, MODE="A"):
         """MODE C time step: the sweeps of MODE B in the same order; the scalar work is one add per use of a base kept
         per chunk or carried from step to step, the rare paths (spin, adjusting update, plane prefetch) out of line."""
         e.salu(f"s_mul_i32 s{S_SS}, s{S_KK}, 3")
-        flag_poll_sc()                           # my step's records have landed, nobody still reads the other set
+        (flag_poll_sd if P_AHEAD else flag_poll_sc)() # my step's records have landed, nobody still reads the other set
         e.salu(f"s_add_u32 s{S_REC}, s{S_SET}, {RING0}")
         e.valu(f"v_add_u32 {v(VADDRN)}, s{S_REC}, {v(V_CROW)}", dst=[VADDRN], src=[V_CROW])   # the set's rows
         # next step of my job: kk-1 of this chunk (records SWB3 lower), or K-1 of the next one
@@ -1380,15 +1457,17 @@ def gen(NW, ABL=0, MODE="A"):
         e.salu(f"s_cselect_b32 s{S_HASNEXT}, 1, s{S_MORE}")
         e.salu(f"s_cselect_b64 s[{S_SRC}:{S_SRC + 1}], s[{S_SRC}:{S_SRC + 1}], s[{S_SRCTOP}:{S_SRCTOP + 1}]")
         e.salu(f"s_cselect_b32 s{S_T3}, s{S_PVH}, s{S_PV}")        # a chunk's first item holds no rows
-        e.salu(f"s_mul_i32 s{S_T0}, s{S_KK}, 12")
-        e.s_load(f"s_load_dwordx4 s[{S_DTS[0]}:{S_DTS[0] + 3}], s[{S_DTSB}:{S_DTSB + 1}], s{S_T0}")   # (+ one spare)
+        if not D_AHEAD:
+            e.salu(f"s_mul_i32 s{S_T0}, s{S_KK}, 12")
+            e.s_load(f"s_load_dwordx4 s[{S_DTS[0]}:{S_DTS[0] + 3}], s[{S_DTSB}:{S_DTSB + 1}], s{S_T0}")   # (+ one spare)
         e.salu(f"s_cmp_eq_u32 s{S_HASNEXT}, 0")
         e.salu("s_cbranch_scc1 L_nonext")
         if not (ABL & 4) and not (ABL & 2048):
             e.salu(f"s_xor_b32 s{S_T2}, s{S_SET}, {3 * RECP_B}")
             dma_step_sc(S_T2, S_T3)
         e.label("L_nonext")
-        e.drain(vm=False)                        # (the time increments)
+        if not D_AHEAD:
+            e.drain(vm=False)                    # (the time increments)
         mark(1)
         e.salu(f"s_cmp_ge_u32 s{S_KK}, s{S_RNKK}")
         e.salu("s_cbranch_scc0 L_rows_held")
@@ -1416,7 +1495,19 @@ def gen(NW, ABL=0, MODE="A"):
         sweep_y_b(1, 2, (AX, TX, S_DTS[2], S_AJ[0], S_TLX, "x2"))
         flag_add_sc(S_CNTO, 8)                   # done[this set] += 1: the last sweep's rows are in registers
         mark(3)
-        sweep_x_b(2, None, False, (AY, TY, S_DTS[1], S_AJ[1], S_TLY, "y"), (AX, TX, S_DTS[0], S_AJ[2], S_TLX, "x0"))
+        if SD:
+            def ahead():
+                # every row read of this sweep has returned (the kap quad waited for above was the last one issued), so
+                # the scalar load turns no counted LDS wait into lgkmcnt(0); the step's closing drain collects both
+                assert not any(e.lgkm) and not e.smem, e.lgkm
+                if P_AHEAD:
+                    poll_ahead()
+                if D_AHEAD:
+                    dts_ahead()
+            sweep_x_b(2, None, False, (AY, TY, S_DTS[1], S_AJ[1], S_TLY, "y"),
+                      (AX, TX, S_D0 if D_AHEAD else S_DTS[0], S_AJ[2], S_TLX, "x0"), {14: ahead})
+        else:
+            sweep_x_b(2, None, False, (AY, TY, S_DTS[1], S_AJ[1], S_TLY, "y"), (AX, TX, S_DTS[0], S_AJ[2], S_TLX, "x0"))
         mark(4)
         e.drain(vm=False)
         e.salu(f"s_add_u32 s{S_T0}, s{S_DT}, {NW}")
@@ -1465,6 +1556,16 @@ def gen(NW, ABL=0, MODE="A"):
         e.salu(f"s_cselect_b32 s{S_AJ[1]}, s{S_AJ[1]}, -1")
         e.salu(f"s_cselect_b32 s{S_AJ[2]}, s{S_FIRSTX}, -1")        # x0: sweep 3kk
         e.salu(f"s_cselect_b32 s{S_PFKK}, 0, -1")
+        if SD:
+            # the chunk's first step: its time increments (step K-1; S_DTSB lies one step low), and a zero where the top
+            # looks for the `ready` count read ahead, so that it polls for itself (through VADDRN)
+            if D_AHEAD:
+                e.salu(f"s_mul_i32 s{S_T0}, s{S_K}, 12")
+                e.s_load(f"s_load_dwordx4 s[{S_DTS[0]}:{S_DTS[0] + 3}], s[{S_DTSB}:{S_DTSB + 1}], s{S_T0}")
+            if P_AHEAD:
+                e.valu(f"v_mov_b32 {v(PF)}, 0", dst=[PF])
+                e.valu(f"v_mov_b32 {v(VADDRN)}, s{S_CNTC}", dst=[VADDRN])
+            e.drain(vm=False)                    # (also the wait state v_readfirstlane_b32 needs behind a VALU write)
     e.salu(f"s_sub_u32 s{S_KK}, s{S_K}, 1")
     e.label("L_step")
     e.assert_idle()
@@ -1740,10 +1841,10 @@ amdhsa.version:
 
 
 def parse_spec(spec):
-    """"<waves>[b|c][a<bits>]" -> (waves, ABL bits, MODE)"""
+    """"<waves>[b|c|d][a<bits>]" -> (waves, ABL bits, MODE)"""
     head, _, abl = spec.partition("a")
-    mode = {"b": "B", "c": "C"}.get(head[-1], "A")
-    return int(head.rstrip("bc")), int(abl or 0), mode
+    mode = {"b": "B", "c": "C", "d": "D"}.get(head[-1], "A")
+    return int(head.rstrip("bcd")), int(abl or 0), mode
 
 
 def step_loop_counts(text):
@@ -1777,7 +1878,7 @@ def step_loop_counts(text):
 
 
 if __name__ == "__main__":
-    spec = sys.argv[1]                       # "<waves>[b|c][a<bits>]": "12", "8b", "8c", "8ca4096" (a...: diagnostic build, see gen())
+    spec = sys.argv[1]                       # "<waves>[b|c|d][a<bits>]": "12", "8b", "8c", "8d", "8da4096" (a...: diagnostic build, see gen())
     text, info = gen(*parse_spec(spec))
     with open(sys.argv[2], "w") as f:
         f.write(text)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostic: cycle stamps of the assembly backward kernel (a build with ABL bit 12, e.g. PDE_ASM_VARIANT=8ba4096): every
-wave of workgroup (0,0,0) during time step kk = 5 of its second chunk.  usage: asm_timeline.py <variant>"""
+"""Diagnostic: cycle stamps of the assembly backward kernel (a build with ABL bit 12, e.g. PDE_ASM_VARIANT=8ba4096, 8ca4096,
+8da4096; the library must have been built with that spec in ASMW): every wave of workgroup (0,0,0) during time step kk = 5 of its second chunk.  usage: asm_timeline.py <variant>"""
 import ctypes as C
 import os
 import sys

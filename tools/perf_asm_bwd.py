@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: launch times (HIP events inside the library) of the cfg2 backward with the HIP kernel and with the
-hand-scheduled assembly kernels, one child process per variant.  usage: perf_asm_bwd.py [tag=ENV=VAL,ENV=VAL ...]"""
+hand-scheduled assembly kernels, one child process per variant (any spec built into the library: 8b, 8c, 8d, 12, ...; repeat
+the list to alternate).  usage: perf_asm_bwd.py [tag=ENV=VAL,ENV=VAL ...]"""
 import os
 import subprocess
 import sys
@@ -40,7 +41,8 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "child":
         child()
         sys.exit(0)
-    specs = sys.argv[1:] or ["hip=PDE_ASM_BWD=0,PDE_ASM_FWD=0", "asm8=PDE_ASM_VARIANT=8", "asm12=PDE_ASM_VARIANT=12"]
+    specs = sys.argv[1:] or ["hip=PDE_ASM_BWD=0,PDE_ASM_FWD=0", "8b=PDE_ASM_VARIANT=8b", "8c=PDE_ASM_VARIANT=8c", "8d=PDE_ASM_VARIANT=8d",
+                             "asm12=PDE_ASM_VARIANT=12"]
     for spec in specs:
         tag, _, envs = spec.partition("=")
         env = dict(os.environ)
