@@ -753,6 +753,28 @@ int fwd_stagger() {
     return mode;
 }
 
+// The round trips the hand-over schedule issues ahead of their use (SweepArgs::ahead, kAhead* in pde_adi_dev.h; when a
+// round trip is asked for changes, never what is computed).  PDE_FWD_AHEAD (read once per process): a bit mask, 0 = the
+// schedule as it was, unset = the default set.  Sizing: tools/perf_fwd_ahead.py, profiles/fwd_ahead_*, DESIGN.md §4.
+// A set is an instantiation of the kernel (PDE_FWD_AHEAD_LIST); a value that names none of them is the default.
+// The default is the one candidate of five that paid alone, the counters polled a solve ahead (bit 2): headline forward
+// 0.1305 -> 0.1252 ms (bench.py, parent's build and this one alternated three times), 148.6-150.7 -> 145.8-147.0 us by the
+// library's events on a slower box.
+constexpr int kFwdAheadDefault = kAheadPoll;
+int fwd_ahead() {
+    static const int mask = [] {
+        const char* e = getenv("PDE_FWD_AHEAD");
+        if (!e || !e[0]) return kFwdAheadDefault;
+        switch (atoi(e)) {
+#define PDE_CASE(AH) case AH: return AH;
+            PDE_FWD_AHEAD_LIST
+#undef PDE_CASE
+        }
+        return kFwdAheadDefault;
+    }();
+    return mask;
+}
+
 #ifdef PDE_STAMP
 // diagnostic builds only (tools/fwd_timeline.py): the timeline slots of the last hand-over launch
 constexpr size_t kFwdStampBytes = (size_t)1024 * kWaves * kFwdStamps * sizeof(unsigned long long);
@@ -801,6 +823,7 @@ int launch_fwd_sweeps(const PdeAdiDesc* d, const void* u, void* y, const float* 
     if (fwd_ho_eligible(d)) {
         const size_t lds = (size_t)(kRingHo * kRecFwdPad + kWaves * kImage + kRingHo) * sizeof(float);
         sa.stagger = (sa.G * d->C > kFwdStaggerMinGrid) ? fwd_stagger() : 0;
+        sa.ahead = fwd_ahead();
 #ifdef PDE_STAMP
         sa.dbg = (sa.G * d->C <= 1024) ? fwd_stamp_buffer() : nullptr;
 #endif

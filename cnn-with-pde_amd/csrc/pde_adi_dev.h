@@ -70,6 +70,8 @@ struct SweepArgs {
     int acc_part;           // bwd: add the partial gradient sums to what `part` holds (per-step launches)
     int pair_x;             // Strang schedules: the last x sweep of a step and the first of the next have the SAME record
                             // (same time, same increment): its rows are loaded from LDS once for the two sweeps
+    int ahead;              // fwd, hand-over schedule: which round trips are issued ahead of their use (kAhead* bits; 0: none);
+                            // sits in what was padding
     void* dbg;              // diagnostic builds only
     int only_masked;        // bwd: the grid is C*G blocks of the MASKED body alone (the fast body ran as the assembly kernel)
     int stagger;            // fwd, hand-over schedule: how the two workgroups of a CU are kept out of phase (kStaggerTurn,
@@ -160,8 +162,11 @@ __device__ __forceinline__ unsigned long long stamp() {
 // The forward's timeline (tools/fwd_timeline.py): lane 0 of every wave of every workgroup of a hand-over launch keeps
 // kFwdStamps 64-bit slots at dbg[(block * kWaves + wave) * kFwdStamps]: 0 kernel top; per chunk k = 0, 1 at 1 + 5k: plane
 // loads begin, planes in registers, first sweep done, last sweep done, stores issued; 11 last stores drained; 12, 13 the
-// 100 MHz counter at the top and at the end; 14 HW_ID | XCC_ID << 32; 15 the LDS_ALLOC register
-constexpr int kFwdStamps = 16;
+// 100 MHz counter at the top and at the end; 14 HW_ID | XCC_ID << 32; 15 the LDS_ALLOC register; sums over the wave's whole
+// job: 16 cycles from a hand-over poll's first look to its being met, 17 cycles from the request of an x sweep's rows to
+// their arrival where nothing stands between the two, 18 cycles from the prologue's first record DMA to the first plane
+// fetch; 19 polls, 20 polls not met at the first look, 21 such row requests
+constexpr int kFwdStamps = 24;
 __device__ __forceinline__ unsigned long long stamp_real() {
     unsigned long long t;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
@@ -189,6 +194,10 @@ constexpr int kStaggerSleep = 8;
 constexpr int kStaggerTurn = 1 << 16;
 __device__ __forceinline__ int stagger_naps(int st) { return (int)(short)(st & 0xffff); }
 __device__ __forceinline__ int stagger_share(int st) { return (st >> 17) & 127; }   // A's part of the time steps, percent
+// SweepArgs::ahead: round trips of the hand-over schedule issued ahead of their use (see adi_fwd_kernel)
+// (bits 1, 4 and 8 were candidates that did not pay — rows of the x sweep in front of the y sweep's trailing re-layout,
+// the first plane fetched in the prologue, rows in front of the exchange of planes — and are gone: DESIGN.md §4)
+constexpr int kAheadPoll = 2;       // the counter of the next hand-over is read where the current record's solve begins
 // a workgroup's priority class (0: as young_half_priority left it, 1: one above) on top of the younger half's
 __device__ __forceinline__ void chunk_priority(bool high, int wave) {
     const bool young = PDE_PRIO && wave >= kWaves / 2;
@@ -657,12 +666,13 @@ __device__ __forceinline__ void add_planes(const IO* base, int q, int wave, int 
 // the I/O type once; the time loop goes on in fp32 registers.  A variant of its own so that the plain kernels compile
 // to what they were; it runs on the barrier-per-sweep (or resident) schedule.
 constexpr int kRingHo = 4;
-template <int N, int J, typename IO, int SPLIT, bool HO = false, bool EMIT = false>
+template <int N, int J, typename IO, int SPLIT, bool HO = false, bool EMIT = false, int AHEAD = 0>
 __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kernel(SweepArgs a) {
     constexpr int M = Geo<N>::M;
     constexpr int RING = HO ? kRingHo : kRing;
     static_assert(!HO || SPLIT == kSplitStrang, "the hand-over schedule is written for the Strang pattern");
     static_assert(!(HO && EMIT), "emission runs on the barrier schedule");
+    static_assert(HO || AHEAD == 0, "round trips are issued ahead on the hand-over schedule only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* cbuf = smem;                                   // [RING][kRecFwdPad]
     float* tbuf = smem + RING * kRecFwdPad;              // [kWaves][kImage]
@@ -693,6 +703,7 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
     int fchunk = 0;                                       // chunks I have begun
     if (HO && a.dbg != nullptr && lane == 0) fst = static_cast<unsigned long long*>(a.dbg) + ((size_t)blockIdx.x * kWaves + wave) * kFwdStamps;
     unsigned long long* const fend = fst;
+    unsigned long long f_poll = 0, f_rows = 0, f_head = 0, f_npoll = 0, f_nslow = 0, f_nrows = 0;
     PDE_FWD_STAMP(0);
     if (fst) {
         unsigned id, xcc;
@@ -735,6 +746,9 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
     if (resident) {
         for (int s = 0; s < a.S; ++s) dma_rec(s, s);
     } else {
+#ifdef PDE_STAMP
+        if (fend) f_head = stamp();
+#endif
         dma_rec(0, 0);
         if (HO) dma_rec(1, 1);                            // (HO is only launched for a.S > kRing)
     }
@@ -747,14 +761,37 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
     const int rpc = a.pair_x ? 1 + 2 * (a.S / 3) : a.S;   // records per chunk
     const int ntot = ((nchunk - g + a.G - 1) / a.G) * rpc;
     int dsw = 2;                                          // sweep of record n + 2, the next one to stage
+    // kAheadPoll: the wait for record n+1 looks at the counter of record n-1.  ho_poll() reads it where record n's solve
+    // begins, ho_wait() takes the value a solve later: the counters only grow, so a value that meets `want` is final and
+    // the LDS round trip of the look has passed behind the solve; anything less falls into the spin.
+    [[maybe_unused]] unsigned polled = 0u;
+    auto ho_poll = [&]() __attribute__((always_inline)) {
+        if ((AHEAD & kAheadPoll) && n >= 1)
+            polled = __hip_atomic_load(passed + ((n - 1) & (kRingHo - 1)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
     // wait until every wave has passed the hand-over point of record n-2 (see the kernel's head comment)
     auto ho_wait = [&]() __attribute__((always_inline)) {
         if (n < 2) return;
         const unsigned want = (unsigned)kWaves * (unsigned)(((n - 2) >> 2) + 1);
         const unsigned* ctr = passed + ((n - 2) & (kRingHo - 1));
-        while ((unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < want)
-            __builtin_amdgcn_s_sleep(1);
+#ifdef PDE_STAMP
+        const unsigned long long t0 = fend ? stamp() : 0ull;
+        bool slow = false;
+#endif
+        // (every wait with n >= 2 follows a solve of record n-1 >= 1, so `polled` is the counter of record n-2)
+        const bool met = (AHEAD & kAheadPoll) && (unsigned)__builtin_amdgcn_readfirstlane((int)polled) >= want;
+        if (!met) {
+            while ((unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < want) {
+                __builtin_amdgcn_s_sleep(1);
+#ifdef PDE_STAMP
+                slow = true;
+#endif
+            }
+        }
         asm volatile("" ::: "memory");                    // no LDS access of this record moves above the poll
+#ifdef PDE_STAMP
+        if (fend) { f_poll += stamp() - t0; ++f_npoll; f_nslow += slow ? 1 : 0; }
+#endif
     };
     auto ho_stage = [&]() __attribute__((always_inline)) {
         if (n + 2 < ntot) dma_rec((n + 2) & (kRingHo - 1), dsw);
@@ -806,6 +843,7 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
 #ifdef PDE_STAMP
         if (fchunk >= 2) fst = nullptr;                   // the timeline covers the first two chunks
         PDE_FWD_STAMP(1 + 5 * fchunk);
+        if (HO && fend && fchunk == 0) f_head = stamp() - f_head;
 #endif
         if (!((PDE_ABL & 4) && abl_loaded)) {
 #ifndef PDE_FWD_PAR_LOAD
@@ -826,8 +864,17 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
                 }
                 const float* rec = cbuf + (n & (kRingHo - 1)) * kRecFwdPad;
                 // the y sweep's rows are requested before its re-layout, not after it
-                if (staged) load_fwd_rows<M>(rec, l, hf, ce, cinv, cjn);
+                if (staged) {
+#ifdef PDE_STAMP
+                    const unsigned long long t0 = (fend && AX != PDE_AXIS_Y) ? stamp() : 0ull;
+#endif
+                    load_fwd_rows<M>(rec, l, hf, ce, cinv, cjn);
+#ifdef PDE_STAMP
+                    if (fend && AX != PDE_AXIS_Y) { f_rows += stamp() - t0; ++f_nrows; }
+#endif
+                }
                 if (AX == PDE_AXIS_Y) relayout_all<N, J>(v, T, l, hf);
+                if (staged) ho_poll();
                 solve_fwd_rows<M, J>(v, ce, cinv, cjn, hf);
                 if (staged) ho_pass();
                 if (AX == PDE_AXIS_Y) relayout_all<N, J>(v, T, l, hf);
@@ -895,6 +942,8 @@ __global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_fwd_kerne
         dma_wait_all();                                   // my last stores have left
         fend[11] = stamp();
         fend[13] = stamp_real();
+        fend[16] = f_poll; fend[17] = f_rows; fend[18] = f_head;
+        fend[19] = f_npoll; fend[20] = f_nslow; fend[21] = f_nrows;
     }
 #endif
     if (!HO && !lag) __syncthreads();                     // the interval in which the upper waves finish

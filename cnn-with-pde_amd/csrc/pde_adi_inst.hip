@@ -32,7 +32,16 @@ template <typename IO>
 int fwd_io(int split, int ho, const SweepArgs& sa, int grid, size_t lds, hipStream_t st) {
     constexpr int N = PDE_INST_N;
     if constexpr (N == 32 && std::is_same<IO, float>::value) {
-        if (ho && split == kSplitStrang) return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitStrang, true>, sa, grid, lds, st);
+        if (ho && split == kSplitStrang) {
+            // one instantiation per set of round trips issued ahead (SweepArgs::ahead, PDE_FWD_AHEAD): a set decided at
+            // run time costs the sweep loop registers it does not have
+            switch (sa.ahead) {
+#define PDE_CASE(AH) case AH: return launch(adi_fwd_kernel<N, kJFwd, IO, kSplitStrang, true, false, AH>, sa, grid, lds, st);
+                PDE_FWD_AHEAD_LIST
+#undef PDE_CASE
+            }
+            return PDE_E_LAUNCH;
+        }
     }
     if (ho) return PDE_E_LAUNCH;
     switch (split) {

@@ -16,6 +16,12 @@ struct SweepArgsOpaque;          // = SweepArgs of pde_adi_dev.h, passed by poin
 constexpr int kJFwd = PDE_JF;    // planes per lane in the forward kernel
 constexpr int kJBwd = PDE_JB;    // planes per lane in the backward kernel
 
+// the sets of round trips the hand-over forward can issue ahead of their use (SweepArgs::ahead, kAhead* bits), one kernel
+// instantiation each: PDE_FWD_AHEAD picks among these
+#ifndef PDE_FWD_AHEAD_LIST
+#define PDE_FWD_AHEAD_LIST PDE_CASE(0) PDE_CASE(2)
+#endif
+
 // return 0 on success, PDE_E_LAUNCH otherwise.  ho: the forward's hand-over schedule (N = 32, fp32, Strang only; the
 // caller checks that and sizes `lds` for it).  _emit: the variants that write / read the emitted states (SweepArgs::states,
 // SweepArgs::em), forward on the barrier-per-sweep schedule

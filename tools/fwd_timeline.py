@@ -4,8 +4,11 @@ the s_memtime stamps of a stamped build (tools/variant.sh fstamp -DPDE_STAMP=1):
 top of the kernel and, for its two chunks, plane loads begun / planes in registers / first sweep done / last sweep done /
 stores issued, then the last stores drained.  HW_ID / XCC_ID say which workgroups share a CU and LDS_ALLOC which of the two
 came second, so the tool prints how long head, exchange and tail are and how far apart the two workgroups of a CU run.
-usage: fwd_timeline.py [stagger [tag]]      (stagger: PDE_FWD_STAGGER for this run — 0, 1, <naps>, t<naps>/<share> —
-default 0; tag: default fstamp)"""
+Every wave also sums, over its whole job, the cycles it spends between a hand-over poll's first look and its being met,
+between the request of an x sweep's rows and their arrival where nothing stands between the two, and between the prologue's
+first record DMA and the first plane fetch: the round trips PDE_FWD_AHEAD issues ahead of their use.
+usage: fwd_timeline.py [stagger [tag [ahead]]]      (stagger: PDE_FWD_STAGGER for this run — 0, 1, <naps>,
+t<naps>/<share> — default 0; tag: default fstamp; ahead: PDE_FWD_AHEAD for this run, default: the library's)"""
 import ctypes as C
 import os
 import statistics as S
@@ -15,12 +18,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["PDE_FWD_STAGGER"] = sys.argv[1] if len(sys.argv) > 1 else "0"
 tag = sys.argv[2] if len(sys.argv) > 2 else "fstamp"
+if len(sys.argv) > 3:
+    os.environ["PDE_FWD_AHEAD"] = sys.argv[3]
 os.environ.setdefault("PDECNN_LIB", os.path.join(ROOT, "cnn-with-pde_amd", "lib", f"libpdecnn_{tag}.so"))
 import torch  # noqa: E402
 import cnn_with_pde_amd.functional as F  # noqa: E402
 import cnn_with_pde_amd._lib as L  # noqa: E402
 
-B, Cc, N, steps, NW, NS = 512, 64, 32, 10, 8, 16
+B, Cc, N, steps, NW, NS = 512, 64, 32, 10, 8, 24
 g = torch.Generator().manual_seed(3)
 ab = (2.0 * (1 + 0.1 * torch.randn(Cc, N, N, generator=g))).cuda()
 bb = (1.8 * (1 + 0.1 * torch.randn(Cc, N, N, generator=g))).cuda()
@@ -47,7 +52,7 @@ med = S.median
 # shader clock: s_memtime ticks per 100 MHz tick over the whole wave
 mhz = med([(w[11] - w[0]) / max(1, (w[13] - w[12])) * 100.0 for b in st for w in b])
 us = lambda cyc: cyc / mhz
-print(f"stagger {os.environ['PDE_FWD_STAGGER']}: shader clock {mhz:.0f} MHz (s_memtime against the 100 MHz counter, median over waves)")
+print(f"stagger {os.environ['PDE_FWD_STAGGER']}, ahead {os.environ.get('PDE_FWD_AHEAD', 'default')}: shader clock {mhz:.0f} MHz (s_memtime against the 100 MHz counter, median over waves)")
 
 
 def where(b):
@@ -111,3 +116,17 @@ if pairs:
     for i in range(12):
         print(f"  {NAMES[i]:18s} " + " ".join(f"{us(st[a][w][i] - t0):6.1f}" for w in range(NW)) + "  | " +
               " ".join(f"{us(st[b][w][i] - t0):6.1f}" for w in range(NW)))
+
+# the round trips a wave waits out in the open, summed over its job (slots 16-21)
+print("waits per wave over its whole job, us, median [min .. max] over the waves of phase A | phase B")
+for name, i, j in (("hand-over polls: first look -> met", 16, 19), ("x sweep rows: request -> arrival, bare", 17, 21),
+                   ("prologue: record DMA -> first plane fetch", 18, None)):
+    row = []
+    for p in (0, 1):
+        d = [us(st[b][w][i]) for b in range(G) if ph[b] == p for w in range(NW)]
+        k = [st[b][w][j] for b in range(G) if ph[b] == p for w in range(NW)] if j is not None else None
+        row.append((f"{med(d):6.2f} [{min(d):6.2f} .. {max(d):6.2f}]" + (f" in {med(k):.0f}" if k else "")) if d else "-")
+    print(f"  {name:42s} {row[0]}  |  {row[1]}")
+slow = [st[b][w][20] for b in range(G) for w in range(NW)]
+npoll = [st[b][w][19] for b in range(G) for w in range(NW)]
+print(f"polls not met at the first look: {sum(slow)} of {sum(npoll)} ({100.0 * sum(slow) / max(1, sum(npoll)):.1f} %)")
