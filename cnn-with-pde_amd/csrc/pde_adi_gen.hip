@@ -224,6 +224,8 @@ __global__ void gen_fwd_kernel(GenArgs<TT, EMIT> a) {
         if (a.ckpt && gen_ck_bit(a.ck, s)) {
             TT* dst = a.ckpt + (size_t)gen_ck_slot(a.ck, s) * a.B * a.C * plane + pb;
             for (int e = tid; e < NN; e += T) dst[e] = X[(e / W) * ld + (e % W)];
+            __syncthreads();                 // as below: a wave that is done copying must not start the next sweep on lines
+                                             // another wave is still reading
         }
         if constexpr (EMIT) {
             if (gen_ck_bit(a.em, s)) {

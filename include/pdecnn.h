@@ -13,6 +13,26 @@
  *     bookkeeping that never changes a result: one "dynamic-LDS attribute set" bit per (kernel,
  *     device) behind a mutex, and the optional timing recorder of pde_timing_*;
  *   - return value: 0 on success, a negative PDE_E_* code otherwise (never throws).
+ *
+ * Contents on entry, and what a call may touch (tests/test_gpu_bounds.py holds every entry point to this).  A call writes
+ * inside the buffers it is given and nowhere else: an output of n elements gets exactly n elements, a workspace exactly the
+ * bytes its *_workspace_bytes() query returned.  Unless a function's own comment says otherwise:
+ *   - OUTPUT (every pointer to non-const tensor memory: y, out, gu, states, traj, the parameter gradients, gM, g_weight,
+ *     g_skip_weight, plane_sums, kappa_max, P, H, dP, mean, invstd, argmax, K16, ...): overwritten in full — every element
+ *     is stored, none is read or added to — so its contents on entry do not matter;
+ *   - WORKSPACE (`workspace`, and `steps_workspace` in the call that fills it): scratch whose contents on entry do not
+ *     matter: nothing in it is read before the call itself has written it;
+ *   - CARRIED between the calls of a sequence — contents do not matter before the FIRST call, must stay intact until the last:
+ *       `steps_workspace`  filled by pde_adi_factor_steps or by the forward of pde_adi_mixed_* / pde_adi_small_* /
+ *                          pde_adi_multi_*, read by every later call of that layer call;
+ *       `workspace` of pde_adi_backward_step        accumulate = 0 starts the partial sums in it (the first call of a
+ *                          sequence), accumulate = 1 adds to them, pde_adi_param_grads reads them;
+ *       `workspace` of pde_channel_mix[_f64]_backward_steps   likewise: accumulate = 0 starts, 1 adds, finalize = 1 reduces;
+ *       `fwd_workspace`    the forward's workspace, read only;
+ *       `states` of pde_adi_mixed_forward in the one-launch case: written in part (see there); the rest is left as it was,
+ *                          and the backward recomputes what it needs of it instead of reading it;
+ *   - UPDATED in place (read, then written): running_mean / running_var, in training mode only.
+ * Inputs (pointers to const) are never written.
  */
 #ifndef PDECNN_H
 #define PDECNN_H
@@ -181,7 +201,8 @@ int pde_adi_kappa_max(const PdeAdiDesc* d,
  * backward accumulating the parameter-gradient partial sums across its per-step launches so that
  * pde_adi_param_grads runs once.  `d` is always the descriptor of the WHOLE schedule. */
 size_t pde_adi_steps_workspace_bytes(const PdeAdiDesc* d, int32_t sweeps_per_step);
-/* zero + factorise every sweep, one sweep table per step; kappa_max as in pde_adi_forward */
+/* zero + factorise every sweep, one sweep table per step; kappa_max as in pde_adi_forward.  steps_workspace: contents on
+ * entry do not matter; every later call of the sequence reads it */
 int pde_adi_factor_steps(const PdeAdiDesc* d, int32_t sweeps_per_step,
                          const float* alpha_base, const float* beta_base,
                          const float* alpha_slope, const float* beta_slope,
@@ -191,8 +212,8 @@ int pde_adi_forward_step(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t s
                          const void* u, void* y, const void* steps_workspace, void* stream);
 size_t pde_adi_backward_step_workspace_bytes(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t num_checkpoints);
 /* gu = adjoint of step `step`; ckpt_mask bits are relative to the step (bit 0 = state after its first
- * sweep).  accumulate = 0 starts the partial sums held in `workspace`, 1 adds to them: use the same
- * workspace for every step of a call. */
+ * sweep).  accumulate = 0 starts the partial sums held in `workspace` (whose contents then do not matter), 1 adds to
+ * them: use the same workspace for every step of a call and keep it intact up to pde_adi_param_grads. */
 int pde_adi_backward_step(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t step,
                           const void* gy, const void* y, const void* u, const uint64_t ckpt_mask[2], void* gu,
                           const void* steps_workspace, void* workspace, size_t workspace_bytes,
@@ -365,7 +386,8 @@ int pde_channel_mix_backward(int32_t B, int32_t C, int32_t HW, int32_t io_dtype,
                              void* workspace, size_t workspace_bytes, void* stream);
 /* The same with gM spread over several calls that share `workspace` (one per time step of a layer):
  * accumulate = 0 starts the partial sums, 1 adds to them; finalize = 1 reduces them into gM
- * (gM may be NULL otherwise). */
+ * (gM may be NULL otherwise).  The workspace's contents do not matter before the accumulate = 0 call and must stay
+ * intact from there to the finalising one; gu is overwritten by every call. */
 int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_dtype,
                                    const void* u, const void* gout, const float* M,
                                    void* gu, float* gM,
@@ -455,7 +477,7 @@ int pde_bn_pool_backward(int32_t B, int32_t C, int32_t N, const float* x, const 
  * variant is a correctness path and has not been timed).  states: NULL, or room for (num_steps-1) FP32 tensors of u's shape (whatever io_dtype:
  * with bf16 tensors only the layer's own input, output and gradients are bf16) that receive the inputs of steps
  * 2..num_steps (what pde_explicit5_backward needs); required for num_steps > 1 unless the plane is 64x64, 32x32 or 16x16
- * (those stay in registers over all steps, one launch). */
+ * (those stay in registers over all steps, one launch); when given, all of it is written at every plane size. */
 int pde_explicit5_forward(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype,
                           const void* u, const float* alpha_base, const float* channel_scaling,
                           float dt, float eps, float max_coeff, float relax,
