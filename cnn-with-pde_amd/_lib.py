@@ -243,6 +243,25 @@ SIGNATURES = {
                                                   _sz, _vp]),
     "pde_adi_rect_f64_backward_states": (C.c_int, [_DR64, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(C.c_uint64),
                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the backward for the input alone (frozen coefficients): gy, [gstates, emit_mask,] gu, the four coefficient tensors, the
+    # forward's workspace or NULL, a workspace of the queried size, the stream
+    "pde_adi_backward_input_kernel": (C.c_int, [_D]),
+    "pde_adi_backward_input_workspace_bytes": (_sz, [_D]),
+    "pde_adi_backward_input": (C.c_int, [_D, _vp, _vp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_backward_input_states": (C.c_int, [_D, _vp, _vp, C.POINTER(C.c_uint64), _vp, _fp, _fp, _fp, _fp, _vp, _vp, _sz,
+                                                _vp]),
+    "pde_adi_rect_backward_input_workspace_bytes": (_sz, [_DR]),
+    "pde_adi_rect_backward_input": (C.c_int, [_DR, _vp, _vp, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_backward_input_states": (C.c_int, [_DR, _vp, _vp, C.POINTER(C.c_uint64), _vp, _fp, _fp, _fp, _fp, _vp, _vp,
+                                                     _sz, _vp]),
+    "pde_adi_f64_backward_input_workspace_bytes": (_sz, [_D64]),
+    "pde_adi_f64_backward_input": (C.c_int, [_D64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_f64_backward_input_states": (C.c_int, [_D64, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _sz, _vp]),
+    "pde_adi_rect_f64_backward_input_workspace_bytes": (_sz, [_DR64]),
+    "pde_adi_rect_f64_backward_input": (C.c_int, [_DR64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_f64_backward_input_states": (C.c_int, [_DR64, _vp, _vp, C.POINTER(C.c_uint64), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                         _vp, _sz, _vp]),
     "pde_timing_enable": (C.c_int, [_i32]),
     "pde_timing_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int64)]),
@@ -296,6 +315,18 @@ def host_ext():
             mod.set_error_class(PdeError)
             _host = mod
     return _host or None
+
+
+_bwd_input = None
+
+
+def bwd_input_enabled() -> bool:
+    """Whether a call whose coefficients take no gradient runs the backward for the input alone (*_backward_input).
+    PDE_BWD_INPUT=0 restores the full backward for such calls, so that both can be compared in one build."""
+    global _bwd_input
+    if _bwd_input is None:
+        _bwd_input = os.environ.get("PDE_BWD_INPUT", "1") != "0"
+    return _bwd_input
 
 
 def check(rc, what):

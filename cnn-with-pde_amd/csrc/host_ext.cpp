@@ -17,6 +17,7 @@
 #include <chrono>
 #include <map>
 #include <tuple>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -196,13 +197,31 @@ Tensor bytes(size_t n, const Tensor& like) {
     return at::empty({(int64_t)std::max<size_t>(n, 256)}, like.options().dtype(at::kByte));
 }
 
+// _lib.bwd_input_enabled: PDE_BWD_INPUT=0 keeps the full backward for calls whose coefficients take no gradient
+bool bwd_input_enabled() {
+    static const bool on = [] { const char* e = std::getenv("PDE_BWD_INPUT"); return !(e && e[0] == '0' && e[1] == 0); }();
+    return on;
+}
+
+// what a call keeps for its backward: nothing, everything the full backward reads, or — coefficients frozen, gradient
+// for the input alone — the coefficient views and the factorisation only (pde_adi_backward_input reads neither y nor u)
+constexpr int64_t kGradNone = 0, kGradFull = 1, kGradInput = 2;
+int64_t adi_grad_mode(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& asl, const Tensor& bsl) {
+    if (!at::GradMode::is_enabled()) return kGradNone;
+    const bool params = ab.requires_grad() || bb.requires_grad() || asl.requires_grad() || bsl.requires_grad();
+    if (params) return kGradFull;
+    if (!u.requires_grad()) return kGradNone;
+    return bwd_input_enabled() ? kGradInput : kGradFull;
+}
+
 struct AdiFn : public torch::autograd::Function<AdiFn> {
     // ckpt_mode: 0 = explicit mask (ckpt_lo/hi), 1 = "auto" (planned in the backward from this call's coefficients),
     // 2 = explicit mask, and this call's coefficient maxima go to a slot the CALLER owns (slot_out: where to leave it) —
     // the "lagged" policy of layers.py: the next call plans from them, nobody waits
     static Tensor forward(AutogradContext* ctx, const Tensor& u_in, const Tensor& ab, const Tensor& bb, const Tensor& asl,
                           const Tensor& bsl, int64_t desc_addr, int64_t ckpt_mode, int64_t ckpt_lo, int64_t ckpt_hi,
-                          double amax, bool need_grad, int64_t slot_out) {
+                          double amax, int64_t grad_mode, int64_t slot_out) {
+        const bool need_grad = grad_mode != kGradNone, input_only = grad_mode == kGradInput;
         PDE_REQUIRE(u_in.is_cuda() && ab.is_cuda() && bb.is_cuda() && asl.is_cuda() && bsl.is_cuda(),
                     "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
         PDE_REQUIRE(u_in.dim() == 4 && u_in.size(2) == u_in.size(3), "expected (B,C,N,N), got ", u_in.sizes());
@@ -215,7 +234,8 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
         PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                     "descriptor does not match the tensor");
         Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
-        const bool want_kmax = need_grad && (ckpt_mode == 1 || ckpt_mode == 2);
+        // (the input-only backward plans no checkpoints: maxima only for the lagged call, which hands the ticket out)
+        const bool want_kmax = need_grad && (ckpt_mode == 2 || (ckpt_mode == 1 && !input_only));
         c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
         Tensor y = at::empty_like(u);
@@ -233,7 +253,13 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
                               slot ? slot->host : nullptr, slot ? (void*)slot->ev : nullptr, ws.data_ptr(), (size_t)ws.numel(),
                               (void*)st),
               "pde_adi_forward");
-        if (need_grad) {
+        if (input_only) {
+            ctx->save_for_backward({p[0], p[1], p[2], p[3]});
+            ctx->saved_data["ws"] = ws;
+            if (kdev.defined()) ctx->saved_data["kdev"] = kdev;
+            ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(&d), sizeof(d));
+            ctx->saved_data["input_only"] = (int64_t)u.scalar_type();
+        } else if (need_grad) {
             const bool explicit_none = ckpt_mode == 0 && ckpt_lo == 0 && ckpt_hi == 0;
             ctx->save_for_backward({y, explicit_none ? Tensor() : u, p[0], p[1], p[2], p[3]});
             ctx->saved_data["ws"] = ws;                      // the factorisation, reused by the backward
@@ -253,7 +279,29 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
         return y;
     }
 
+    // gu = F^T gy alone: the coefficient views, the forward's factorisation, one launch
+    static variable_list backward_input(AutogradContext* ctx, variable_list& grads) {
+        auto saved = ctx->get_saved_variables();
+        PdeAdiDesc d;
+        std::memcpy(&d, ctx->saved_data["desc"].toStringRef().data(), sizeof(d));
+        const auto dtype = static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
+        Tensor gy = grads[0];
+        if (gy.scalar_type() != dtype) gy = gy.to(dtype);
+        gy = gy.contiguous();
+        c10::hip::HIPGuardMasqueradingAsCUDA guard(gy.device());
+        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(gy.device().index()).stream();
+        Tensor gu = at::empty_like(gy);
+        Tensor ws = bytes(pde_adi_backward_input_workspace_bytes(&d), gy);
+        Tensor fws = ctx->saved_data["ws"].toTensor();
+        check(pde_adi_backward_input(&d, gy.data_ptr(), gu.data_ptr(), saved[0].data_ptr<float>(), saved[1].data_ptr<float>(),
+                                     saved[2].data_ptr<float>(), saved[3].data_ptr<float>(), fws.data_ptr(), ws.data_ptr(),
+                                     (size_t)ws.numel(), (void*)st),
+              "pde_adi_backward_input");
+        return {gu, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (ctx->saved_data.count("input_only")) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &y = saved[0], &u = saved[1];
         PdeAdiDesc d;
@@ -290,10 +338,9 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
 
 Tensor adi(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& asl, const Tensor& bsl, int64_t desc_addr,
            int64_t ckpt_mode, int64_t ckpt_lo, int64_t ckpt_hi, double amax) {
-    // forward() runs with grad mode off: whether anything is kept for a backward is decided out here
-    const bool need_grad = at::GradMode::is_enabled() && (u.requires_grad() || ab.requires_grad() || bb.requires_grad() ||
-                                                          asl.requires_grad() || bsl.requires_grad());
-    return AdiFn::apply(u, ab, bb, asl, bsl, desc_addr, ckpt_mode, ckpt_lo, ckpt_hi, amax, need_grad, (int64_t)0);
+    // forward() runs with grad mode off: whether anything is kept for a backward, and what, is decided out here
+    return AdiFn::apply(u, ab, bb, asl, bsl, desc_addr, ckpt_mode, ckpt_lo, ckpt_hi, amax, adi_grad_mode(u, ab, bb, asl, bsl),
+                        (int64_t)0);
 }
 
 // The coefficient maxima of one call, for whoever plans a LATER call from them (layers.py, "lagged" policy): `event`
@@ -311,11 +358,9 @@ struct Ticket {
 
 std::pair<Tensor, std::shared_ptr<Ticket>> adi_lagged(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& asl,
                                                       const Tensor& bsl, int64_t desc_addr, int64_t ckpt_lo, int64_t ckpt_hi) {
-    const bool need_grad = at::GradMode::is_enabled() && (u.requires_grad() || ab.requires_grad() || bb.requires_grad() ||
-                                                          asl.requires_grad() || bsl.requires_grad());
     Slot* slot = nullptr;
-    Tensor y = AdiFn::apply(u, ab, bb, asl, bsl, desc_addr, (int64_t)2, ckpt_lo, ckpt_hi, 0.0, need_grad,
-                            (int64_t) reinterpret_cast<intptr_t>(&slot));
+    Tensor y = AdiFn::apply(u, ab, bb, asl, bsl, desc_addr, (int64_t)2, ckpt_lo, ckpt_hi, 0.0,
+                            adi_grad_mode(u, ab, bb, asl, bsl), (int64_t) reinterpret_cast<intptr_t>(&slot));
     PdeAdiDesc d;
     std::memcpy(&d, reinterpret_cast<const void*>(desc_addr), sizeof(d));
     return {y, slot ? std::make_shared<Ticket>(slot, d.num_sweeps) : std::shared_ptr<Ticket>()};

@@ -703,6 +703,17 @@ int dispatch_bwd_emit(const PdeAdiDesc* d, int split, const SweepArgs& sa, int g
     }, st, false, true);
 }
 
+int dispatch_bwd_input(const PdeAdiDesc* d, int split, const SweepArgs& sa, int grid, size_t lds, hipStream_t st, bool emit) {
+    return timed_launch([&]() -> int {
+        switch (d->N) {
+#define PDE_CASE(NN) case NN: return adi_launch_bwd_input_##NN(d->io_dtype, split, emit ? 1 : 0, &sa, grid, lds, st);
+            PDE_N_LIST
+#undef PDE_CASE
+        }
+        return PDE_E_UNSUPPORTED_N;
+    }, st, false, true);
+}
+
 int count_ckpt(const uint64_t m[2]) { return m ? __builtin_popcountll(m[0]) + __builtin_popcountll(m[1]) : 0; }
 
 bool asm_fwd_eligible(const PdeAdiDesc* d) {
@@ -938,6 +949,23 @@ int launch_bwd_sweeps(const PdeAdiDesc* d, const void* gy, const void* y, const 
     return dispatch_bwd(d, split, sa, 2 * G * d->C, st);
 }
 
+// the adjoint sweeps alone (pde_adi_backward_input*): gu = F^T gy with records and table already in place.  The launch
+// has the forward's shape — its groups, its LDS, the barrier-per-sweep schedule (resident records for one time step)
+int launch_bwd_input_sweeps(const PdeAdiDesc* d, const void* gy, void* gu, const float* coef, const SweepTab* tab,
+                            hipStream_t st, const void* gstates, const uint64_t* emit) {
+    SweepArgs sa{};
+    sa.in0 = gy; sa.out = gu; sa.coef = coef; sa.tab = tab;
+    sa.B = d->B; sa.C = d->C; sa.S = d->num_sweeps;
+    sa.G = groups_per_channel(d, kWaves * kJFwd, 16 / kWaves);
+    sa.one_eps = 1.0f + d->eps;
+    sa.gu_scale = (float)pow(1.0 + (double)d->eps, -(double)d->num_sweeps);
+    sa.xcd_map = use_xcd_map(d);
+    sa.pair_x = (split_of(d) == kSplitStrang && strang_pairs_identical(d)) ? 1 : 0;
+    if (emit) { sa.states = const_cast<void*>(gstates); sa.em[0] = emit[0]; sa.em[1] = emit[1]; }
+    const size_t lds = (size_t)(kRing * kRecFwdPad + kWaves * kImage) * sizeof(float);
+    return dispatch_bwd_input(d, split_of(d), sa, sa.G * d->C, lds, st, emit != nullptr);
+}
+
 // parameter gradients from the partial sums; `d` is the WHOLE schedule the sums were taken over
 int launch_pgrad(const PdeAdiDesc* d, const AxisWeights& w, const float* alpha_base, const float* beta_base,
                  const float* alpha_slope, const float* beta_slope, float* g_alpha_base, float* g_beta_base,
@@ -1169,6 +1197,52 @@ int pde_adi_backward_states(const PdeAdiDesc* d, const void* gy, const void* gst
     return adi_backward_impl(d, gy, gstates, emit_mask, y, u, ckpt_mask, gu, alpha_base, beta_base, alpha_slope, beta_slope,
                              g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope, fwd_workspace, workspace,
                              workspace_bytes, stream);
+}
+
+// ---- the backward of a layer whose coefficients take no gradient: gu = F^T gy, nothing else ----
+int pde_adi_backward_input_kernel(const PdeAdiDesc* d) {
+    if (check_desc(d, true) != PDE_OK) return PDE_E_BADARG;
+    return fused_n(d->N) ? 0 : 2;
+}
+
+size_t pde_adi_backward_input_workspace_bytes(const PdeAdiDesc* d) {
+    if (check_desc(d, true) != PDE_OK) return 0;
+    if (!fused_n(d->N)) return gen_forward_workspace_bytes(d);
+    return coef_bytes(d) + tab_bytes();
+}
+
+int pde_adi_backward_input_states(const PdeAdiDesc* d, const void* gy, const void* gstates, const uint64_t emit_mask[2],
+                                  void* gu, const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                                  const float* beta_slope, const void* fwd_workspace, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    int rc = check_desc(d, true);
+    if (rc != PDE_OK) return rc;
+    if (!gy || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    int nem;
+    rc = emit_plan(d->num_sweeps, emit_mask, gstates, nem);
+    if (rc != PDE_OK) return rc;
+    const uint64_t* emit = nem ? emit_mask : nullptr;
+    if (workspace_bytes < pde_adi_backward_input_workspace_bytes(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!fused_n(d->N))
+        return gen_backward_input(d, gy, gu, alpha_base, beta_base, alpha_slope, beta_slope, fwd_workspace, workspace, st,
+                                  gstates, emit);
+    const char* ws = static_cast<const char*>(fwd_workspace ? fwd_workspace : workspace);
+    const float* coef = reinterpret_cast<const float*>(ws);
+    const SweepTab* tab = reinterpret_cast<const SweepTab*>(ws + coef_bytes(d));
+    if (!fwd_workspace) {                                 // the factorisation alone: nobody reads channel flags here
+        rc = launch_factor(d, alpha_base, beta_base, alpha_slope, beta_slope, const_cast<float*>(coef),
+                           const_cast<SweepTab*>(tab), nullptr, nullptr, st);
+        if (rc != PDE_OK) return rc;
+    }
+    return launch_bwd_input_sweeps(d, gy, gu, coef, tab, st, gstates, emit);
+}
+
+int pde_adi_backward_input(const PdeAdiDesc* d, const void* gy, void* gu, const float* alpha_base, const float* beta_base,
+                           const float* alpha_slope, const float* beta_slope, const void* fwd_workspace, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    return pde_adi_backward_input_states(d, gy, nullptr, nullptr, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                                         fwd_workspace, workspace, workspace_bytes, stream);
 }
 
 // ---- one layer call as a sequence of per-step launches (layers with a channel operator between the steps) ----

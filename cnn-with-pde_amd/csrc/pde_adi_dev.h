@@ -616,7 +616,9 @@ __device__ __forceinline__ void store_planes(IO* base, int q, int wave, int lane
 // r += sc * (the J planes of a lane at `base`), one plane at a time through the wave's image (plane_to_rows with the
 // half row consumed four values at a time): 16 registers of raw data, then 4, in flight beside the caller's state — the
 // backward adds the upstream gradient of an emitted state while both its adjoint and its state are live
-template <int N, int J, typename IO>
+// FENCE (J = 4, adi_bwd_input_kernel): a plane is done before the next one is requested.  Left alone hipcc requests plane
+// j+1 in front of the row reads of plane j, 16 more registers in flight, and the N = 32 kernels spill.
+template <int N, int J, typename IO, bool FENCE = false>
 __device__ __forceinline__ void add_planes(const IO* base, int q, int wave, int lane, int l, int hf, int B, int C, int c,
                                            float* T, float sc, typename Pack<J>::P (&r)[N / 2]) {
     constexpr int PPI = kWaves * J, M = N / 2;
@@ -645,8 +647,13 @@ __device__ __forceinline__ void add_planes(const IO* base, int q, int wave, int 
             if constexpr (4 * i + 1 < M) pk_set<j>(r[4 * i + 1], fmaf(sc, x.y, pk_get<j>(r[4 * i + 1])));
             if constexpr (4 * i + 2 < M) pk_set<j>(r[4 * i + 2], fmaf(sc, x.z, pk_get<j>(r[4 * i + 2])));
             if constexpr (4 * i + 3 < M) pk_set<j>(r[4 * i + 3], fmaf(sc, x.w, pk_get<j>(r[4 * i + 3])));
+            // (the sums are formed here, not held back as sixteen row values until after the next plane's loads)
+            if constexpr (FENCE)
+                asm volatile("" ::"v"(pk_get<j>(r[4 * i])), "v"(pk_get<j>(r[4 * i + (4 * i + 1 < M ? 1 : 0)])),
+                             "v"(pk_get<j>(r[4 * i + (4 * i + 2 < M ? 2 : 0)])), "v"(pk_get<j>(r[4 * i + (4 * i + 3 < M ? 3 : 0)])));
         });
         __builtin_amdgcn_wave_barrier();
+        if constexpr (FENCE) asm volatile("s_nop 0" ::: "memory");
     });
 }
 
@@ -1495,6 +1502,153 @@ __global__ __launch_bounds__(kThreads, PDE_BWD_MINW) void adi_bwd_kernel(SweepAr
 #ifndef PDE_BWD_NO_MASKED        // diagnostic builds: the fast body alone (its own register allocation)
     else adi_bwd_body<N, 1, IO, true, kSplitAny, EMIT>(a, (int)blockIdx.x - nb);
 #endif
+}
+
+// ---- backward for the input alone (pde_adi_*_backward_input) ---------------------------------------
+// gu = F^T gy and nothing else: the layer is linear in its input, so with frozen coefficients the backward is the
+// transposed two-sided solves walked from sweep S-1 down to 0.  No y, no u, no rebuilt state, no gradient sums, no
+// clamp-mask flags: the kernel has the shape of adi_fwd_kernel — J = 4 planes per lane, the 128-register class, the
+// barrier-per-sweep ring with the phase skew (a launch of at most kRing sweeps keeps its records resident) — and stages
+// the window JN | E | INVB of a record, which is as long as the forward's INV | JN | E.
+// Per plane the operations on the adjoint are those of adi_bwd_body in its order (solve_adj per sweep, the emitted
+// states' gradients through add_planes, one multiply by gu_scale at the end), so gu is the full backward's bit for bit;
+// re-layouts are permutations, and the adjoint changes layout only where the axis does.
+// EMIT: as in adi_bwd_body — dL/d(state after sweep s-1) joins once sweep s is undone, times 1/ysc[s-1].
+template <int N, int J, typename IO, int SPLIT, bool EMIT = false>
+__global__ __launch_bounds__(kThreads, (kWaves == 8 ? 4 : 1)) void adi_bwd_input_kernel(SweepArgs a) {
+    constexpr int M = Geo<N>::M;
+    using P = typename Pack<J>::P;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* cbuf = smem;                                   // [kRing][kRecFwdPad]
+    float* tbuf = smem + kRing * kRecFwdPad;             // [kWaves][kImage]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hf = lane >> 5, l = lane & 31;
+    int c, g;
+    block_to_work(blockIdx.x, a.C, a.G, a.xcd_map, c, g);
+    float* T = tbuf + wave * kImage;
+    const IO* gy = static_cast<const IO*>(a.in0);
+    IO* gu = static_cast<IO*>(a.out);
+    const ConstTab tab = as_const(a.tab);
+    constexpr int PPI = kWaves * J;
+    const int nchunk = (a.B + PPI - 1) / PPI;
+    const size_t plane = (size_t)N * N;
+    const bool resident = a.S <= kRing;
+    const int lag = resident ? 0 : wave_lag(wave);
+    young_half_priority(wave);
+
+    for (int e = tid; e < kWaves * kImage; e += kThreads) tbuf[e] = 0.f;
+    // Items are numbered along the whole job of this workgroup in processing order (item i = sweep S-1 - i % S of my
+    // chunk i / S); the ring works as in adi_fwd_kernel: in barrier interval t the lower waves run item t from slot
+    // t % kRing, the upper waves item t-1, and every wave brings its pieces of item t+1
+    constexpr int PPR = kRecFwdPad / 256;                 // 1-KB pieces per record window
+    static_assert(kRecFwd == kB_Inv + kImage, "JN | E | INVB is as long as the forward's window");
+    static_assert(kBwdOff + kRecFwdPad <= kRecStride, "the padded window must stay inside the record");
+    const float* dma_src0 = uniform_ptr(a.coef + (size_t)c * kRecStride + kBwdOff + wave * 256);
+    const unsigned dma_step = (unsigned)a.C * kRecStride;
+    const unsigned dma_lds0 = lds_byte_address(cbuf) + wave * 1024u;
+    const unsigned dma_voff = 16u * lane;
+    auto dma_rec = [&](int slot, int s) __attribute__((always_inline)) {
+        const float* src = dma_src0 + (size_t)((unsigned)s * dma_step);
+        const unsigned dst = dma_lds0 + (unsigned)slot * (kRecFwdPad * 4u);
+#pragma unroll
+        for (int i = 0; i < (PPR + kWaves - 1) / kWaves; ++i) {
+            if ((i + 1) * kWaves <= PPR || wave + i * kWaves < PPR)
+                lds_dma16_a(src + i * kWaves * 256, dma_voff, dst + i * kWaves * 1024u);
+        }
+    };
+    if (resident) {
+        for (int s = 0; s < a.S; ++s) dma_rec(s, s);
+    } else {
+        dma_rec(0, a.S - 1);
+    }
+    dma_wait_all();
+    __syncthreads();
+    if (lag) {                                            // interval 0 of the upper waves: staging only
+        dma_rec(1, a.S > 1 ? a.S - 2 : 0);
+        dma_wait_all();
+        __syncthreads();
+    }
+    int cur = 0;                                          // ring slot of my current item
+    // coefficient rows of the current sweep: the newest x sweep of a Strang step keeps those of the sweep undone just
+    // before it, the first x sweep of the next step (same record, see SweepArgs::pair_x)
+    float ce[M], cinv[M], cjn = 0.f;
+    for (int q = g; q < nchunk; q += a.G) {
+        P r[M];
+        // (the lane's addresses in the plane image are worked out where a plane comes in or leaves, from a copy of the lane
+        //  number the compiler cannot see through: hoisted out of the loops they sit in registers beside the adjoint
+        //  through every sweep — some twenty of them — and the N = 32 kernels spill)
+        auto fresh_lane = [&]() __attribute__((always_inline)) -> int {
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            return ln;
+        };
+        {
+            const int ln = fresh_lane();
+            load_planes_seq<N, J, IO>(gy, q, wave, ln, ln & 31, ln >> 5, a.B, a.C, c, T, r);
+        }
+        bool incol = false;                               // the adjoint is in column layout
+        auto sweep = [&](auto AXC, int s, auto TWINC) __attribute__((always_inline)) {
+            constexpr int AX = decltype(AXC)::value;
+            int sp = s - lag - 1;                         // sweep of the item staged in this interval
+            if (sp < 0) sp += a.S;
+            if (sp < 0) sp += a.S;
+            int ps = cur + lag + 1;
+            if (ps >= kRing) ps -= kRing;
+            if (!resident) dma_rec(ps, sp);
+            const float* rec = cbuf + (resident ? s : cur) * kRecFwdPad;
+            const int axs = (AX >= 0) ? AX : tab->axis[s];
+            if ((axs == PDE_AXIS_Y) != incol) {
+                relayout_all<N, J>(r, T, l, hf);
+                incol = !incol;
+            }
+            const bool twin = decltype(TWINC)::value && !EMIT && a.pair_x != 0 && s != a.S - 1;
+            if (!twin) {
+                const float* crow = rec + l * kLineStride + hf * kHalfPad;
+                cjn = rec[kB_Jn + l];
+                load_half<M>(crow + kB_E, ce);
+                load_half<M>(crow + kB_Inv, cinv);
+            }
+            solve_adj<M, J>(r, ce, cinv, cjn, hf);
+            if constexpr (EMIT) {
+                if (s > 0 && ck_bit(a.em, s - 1)) {
+                    if (incol) {
+                        relayout_all<N, J>(r, T, l, hf);
+                        incol = false;
+                    }
+                    const IO* slot = static_cast<const IO*>(a.states) + (size_t)ck_slot(a.em, s - 1) * a.B * a.C * plane;
+                    const int ln = fresh_lane();
+                    add_planes<N, J, IO, true>(slot, q, wave, ln, ln & 31, ln >> 5, a.B, a.C, c, T, 1.0f / tab->ysc[s - 1], r);
+                }
+            }
+            if (!resident) {
+                dma_wait_all();                           // my pieces of the next record have landed
+                __syncthreads();
+                cur = (cur == kRing - 1) ? 0 : cur + 1;
+            }
+        };
+        if constexpr (SPLIT == kSplitStrang) {
+            for (int s = a.S - 3; s >= 0; s -= 3) {
+                sweep(std::integral_constant<int, PDE_AXIS_X>{}, s + 2, std::true_type{});   // twin of the sweep before it
+                sweep(std::integral_constant<int, PDE_AXIS_Y>{}, s + 1, std::false_type{});
+                sweep(std::integral_constant<int, PDE_AXIS_X>{}, s, std::false_type{});
+            }
+        } else if constexpr (SPLIT == kSplitLie) {
+            for (int s = a.S - 2; s >= 0; s -= 2) {
+                sweep(std::integral_constant<int, PDE_AXIS_Y>{}, s + 1, std::false_type{});
+                sweep(std::integral_constant<int, PDE_AXIS_X>{}, s, std::false_type{});
+            }
+        } else {
+            for (int s = a.S - 1; s >= 0; --s) sweep(std::integral_constant<int, -1>{}, s, std::false_type{});
+        }
+        if (incol) relayout_all<N, J>(r, T, l, hf);
+#pragma unroll
+        for (int k = 0; k < M; ++k) r[k] = r[k] * pk_bc<P>(a.gu_scale);      // undo the (1+eps) carried per sweep
+        {
+            const int ln = fresh_lane();
+            store_planes<N, J, IO>(gu, q, wave, ln, ln & 31, ln >> 5, a.B, a.C, c, T, r);
+        }
+    }
+    if (!lag) __syncthreads();                            // the interval in which the upper waves finish
 }
 
 }  // namespace

@@ -23,4 +23,10 @@ int gen_backward(const PdeAdiDesc* d, const void* gy, const void* y, const void*
                  float* g_bb, float* g_as, float* g_bs, const void* fwd_workspace, void* workspace, hipStream_t st,
                  const void* gstates = nullptr, const uint64_t* emit = nullptr);
 
+// the adjoint alone (gu = F^T gy) for frozen coefficients: the factorisation from `fwd_workspace`, or made in `workspace`
+// (laid out as the forward's) when that is null
+int gen_backward_input(const PdeAdiDesc* d, const void* gy, void* gu, const float* ab, const float* bb, const float* as,
+                       const float* bs, const void* fwd_workspace, void* workspace, hipStream_t st,
+                       const void* gstates = nullptr, const uint64_t* emit = nullptr);
+
 }  // namespace pde

@@ -408,6 +408,86 @@ __global__ void gen_bwd_kernel(GenArgs<TT, EMIT> a, int smooth3) {
     }
 }
 
+// backward for the input alone (the *_backward_input entry points): gu = F^T gy.  One workgroup per plane like
+// gen_fwd_kernel, the adjoint plane in LDS, sweeps S-1 .. 0 with the transposed recurrences of gen_bwd_kernel — the same
+// operations in the same order on every plane, so gu is that kernel's bit for bit — and nothing of what the parameter
+// gradients need: no y, no rebuilt state, no sums.  Adjoints are the true ones (no scale), as there.
+// EMIT: a.states holds dL/d(state after sweep s) for every bit s of a.em; the plane joins once sweep s+1 has been undone.
+template <typename T>
+struct GenInputArgs {
+    const void* gy;
+    void* gu;
+    const void* states;                      // EMIT only
+    const T* fac;
+    const GenSweep<T>* tab;
+    unsigned long long em[2];
+    int B, C, H, W, S;
+};
+template <typename TT, typename IO, bool EMIT>
+__global__ void gen_bwd_input_kernel(GenInputArgs<TT> a) {
+    extern __shared__ float gen_ismem[];
+    TT* R = reinterpret_cast<TT*>(gen_ismem);
+    const int W = a.W, ld = W + 1, tid = threadIdx.x, T = blockDim.x, NN = a.H * W;
+    const size_t plane = (size_t)NN, pb = (size_t)blockIdx.x * plane;         // blockIdx = b*C + c
+    const int c = blockIdx.x % a.C;
+    for (int e = tid; e < NN; e += T) R[(e / W) * ld + (e % W)] = GenIo<IO>::ld(a.gy, pb + e);
+    __syncthreads();
+    for (int s = a.S - 1; s >= 0; --s) {
+        const GenSweep<TT> sw = a.tab[s];
+        const bool xs = sw.axis == PDE_AXIS_X;
+        const int N = xs ? W : a.H, L = xs ? a.H : W;                         // unknowns per line, lines
+        if (tid < L) {
+            const TT* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
+            TT* r = R + (xs ? tid * ld : tid);
+            const int st = xs ? 1 : ld;
+            // transposed recurrences: U^T w = r (unit lower, sub-diagonal c*), L^T lam = w (diagonal den, super-diagonal a)
+            TT prev = r[0];
+            for (int k0 = 1; k0 < N; k0 += kGenBatch) {
+                TT t[kGenBatch], cs[kGenBatch];
+#pragma unroll
+                for (int j = 0; j < kGenBatch; ++j) {
+                    const int k = k0 + j < N ? k0 + j : N - 1;
+                    t[j] = r[k * st];
+                    cs[j] = f[plane + (size_t)(k - 1) * L];
+                }
+#pragma unroll
+                for (int j = 0; j < kGenBatch; ++j)
+                    if (k0 + j < N) { prev = t[j] - cs[j] * prev; t[j] = prev; }
+#pragma unroll
+                for (int j = 0; j < kGenBatch; ++j)
+                    if (k0 + j < N) r[(k0 + j) * st] = t[j];
+            }
+            prev = prev * f[2 * plane + (size_t)(N - 1) * L];
+            r[(N - 1) * st] = prev;
+            for (int k0 = N - 2; k0 >= 0; k0 -= kGenBatch) {
+                TT t[kGenBatch], co[kGenBatch], iv[kGenBatch];
+#pragma unroll
+                for (int j = 0; j < kGenBatch; ++j) {
+                    const int k = k0 - j >= 0 ? k0 - j : 0;
+                    t[j] = r[k * st];
+                    co[j] = f[(size_t)(k + 1) * L];
+                    iv[j] = f[2 * plane + (size_t)k * L];
+                }
+#pragma unroll
+                for (int j = 0; j < kGenBatch; ++j)
+                    if (k0 - j >= 0) { prev = (t[j] + co[j] * prev) * iv[j]; t[j] = prev; }
+#pragma unroll
+                for (int j = 0; j < kGenBatch; ++j)
+                    if (k0 - j >= 0) r[(k0 - j) * st] = t[j];
+            }
+        }
+        __syncthreads();                     // the next sweep (or the copy below) reads lines other threads wrote
+        if constexpr (EMIT) {
+            if (s > 0 && gen_ck_bit(a.em, s - 1)) {
+                const size_t o = (size_t)gen_ck_slot(a.em, s - 1) * a.B * a.C * plane + pb;
+                for (int e = tid; e < NN; e += T) R[(e / W) * ld + (e % W)] += GenIo<IO>::ld(a.states, o + e);
+                __syncthreads();
+            }
+        }
+    }
+    for (int e = tid; e < NN; e += T) GenIo<IO>::st(a.gu, pb + e, R[(e / W) * ld + (e % W)]);
+}
+
 // the four parameter gradients: partial sums added over the groups in a fixed order
 template <typename T>
 __global__ void gen_reduce_kernel(const T* part, int G, int C, int H, int W, T* g_ab, T* g_as, T* g_bb, T* g_bs) {
@@ -616,6 +696,44 @@ int backward_impl(const D* d, const void* gy, const void* y, const void* u, cons
     return check_launch();
 }
 
+// the input backward: the factorisation of the forward call, or one made here, then one launch
+template <typename T, typename D>
+int backward_input_impl(const D* d, const void* gy, void* gu, const T* ab, const T* bb, const T* as, const T* bs,
+                        const void* fwd_workspace, void* workspace, hipStream_t st, const void* gstates,
+                        const uint64_t* emit) {
+    const char* ws = static_cast<const char*>(fwd_workspace ? fwd_workspace : workspace);
+    const T* fac = reinterpret_cast<const T*>(ws);
+    const GenSweep<T>* tab = reinterpret_cast<const GenSweep<T>*>(ws + fac_bytes<T>(d));
+    int rc;
+    if (!fwd_workspace) {
+        rc = launch_gen_factor<T>(d, ab, bb, as, bs, const_cast<T*>(fac), const_cast<GenSweep<T>*>(tab), (T*)nullptr, st);
+        if (rc != PDE_OK) return rc;
+    }
+    GenInputArgs<T> ia{};
+    ia.gy = gy; ia.gu = gu; ia.states = emit ? gstates : nullptr; ia.fac = fac; ia.tab = tab;
+    ia.em[0] = emit ? emit[0] : 0ull; ia.em[1] = emit ? emit[1] : 0ull;
+    ia.B = d->B; ia.C = d->C; ia.H = rows_of(d); ia.W = cols_of(d); ia.S = d->num_sweeps;
+    const size_t lds = gen_img<T>(d);
+    const dim3 grid(d->B * d->C), block(gen_threads(d));
+    static unsigned long long done[4] = {0, 0, 0, 0}, done_e[4] = {0, 0, 0, 0};
+#define PDE_GEN_BWD_INPUT(TY, IO, SLOT)                                                                    \
+    do {                                                                                                   \
+        if (emit) {                                                                                        \
+            if ((rc = gen_lds(gen_bwd_input_kernel<TY, IO, true>, done_e[SLOT])) != PDE_OK) return rc;     \
+            hipLaunchKernelGGL((gen_bwd_input_kernel<TY, IO, true>), grid, block, lds, st, ia);            \
+        } else {                                                                                           \
+            if ((rc = gen_lds(gen_bwd_input_kernel<TY, IO, false>, done[SLOT])) != PDE_OK) return rc;      \
+            hipLaunchKernelGGL((gen_bwd_input_kernel<TY, IO, false>), grid, block, lds, st, ia);           \
+        }                                                                                                  \
+    } while (0)
+    if constexpr (std::is_same<T, double>::value) PDE_GEN_BWD_INPUT(double, double, 0);
+    else if (d->io_dtype == PDE_IO_F32) PDE_GEN_BWD_INPUT(float, float, 1);
+    else if (d->io_dtype == PDE_IO_F16) PDE_GEN_BWD_INPUT(float, gen_f16, 2);
+    else PDE_GEN_BWD_INPUT(float, gen_bf16, 3);
+#undef PDE_GEN_BWD_INPUT
+    return check_launch();
+}
+
 }  // namespace
 
 bool gen_n_ok(int N) { return N >= 2 && N <= PDE_MAX_N_GENERIC; }
@@ -645,6 +763,12 @@ int gen_backward(const PdeAdiDesc* d, const void* gy, const void* y, const void*
                  const void* gstates, const uint64_t* emit) {
     return backward_impl<float>(d, gy, y, u, ckpt_mask, nck, Sf, gu, ab, bb, as, bs, g_ab, g_bb, g_as, g_bs, fwd_workspace,
                                 workspace, st, gstates, emit);
+}
+
+int gen_backward_input(const PdeAdiDesc* d, const void* gy, void* gu, const float* ab, const float* bb, const float* as,
+                       const float* bs, const void* fwd_workspace, void* workspace, hipStream_t st, const void* gstates,
+                       const uint64_t* emit) {
+    return backward_input_impl<float>(d, gy, gu, ab, bb, as, bs, fwd_workspace, workspace, st, gstates, emit);
 }
 
 }  // namespace pde
@@ -766,9 +890,71 @@ int rect_backward(const D* d, const void* gy, const void* y, const void* u, cons
                             workspace, static_cast<hipStream_t>(stream), gstates, emit);
 }
 
+// the input backward of the rectangle families and of float64 squares (CHECK: the family's descriptor check)
+template <typename T, typename D, typename CHECK>
+int any_backward_input(const D* d, CHECK&& check, const void* gy, const void* gstates, const uint64_t* emit_mask, void* gu,
+                       const T* ab, const T* bb, const T* as, const T* bs, const void* fwd_workspace, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    int rc = check(d);
+    if (rc != PDE_OK) return rc;
+    if (!gy || !gu || !ab || !bb || !as || !bs || !workspace) return PDE_E_BADARG;
+    const uint64_t* emit;
+    if ((rc = emit_plan(d->num_sweeps, emit_mask, gstates, emit)) != PDE_OK) return rc;
+    if (workspace_bytes < fwd_ws_bytes<T>(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    return backward_input_impl<T>(d, gy, gu, ab, bb, as, bs, fwd_workspace, workspace, static_cast<hipStream_t>(stream),
+                                  gstates, emit);
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- the backward of a layer whose coefficients take no gradient (gu = F^T gy): float64 squares and rectangles ----
+size_t pde_adi_f64_backward_input_workspace_bytes(const PdeAdiDescF64* d) {
+    return check_desc_f64(d) != PDE_OK ? 0 : fwd_ws_bytes<double>(d);
+}
+int pde_adi_f64_backward_input_states(const PdeAdiDescF64* d, const double* gy, const double* gstates,
+                                      const uint64_t emit_mask[2], double* gu, const double* alpha_base,
+                                      const double* beta_base, const double* alpha_slope, const double* beta_slope,
+                                      const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    return any_backward_input<double>(d, check_desc_f64, gy, gstates, emit_mask, gu, alpha_base, beta_base, alpha_slope,
+                                      beta_slope, fwd_workspace, workspace, workspace_bytes, stream);
+}
+int pde_adi_f64_backward_input(const PdeAdiDescF64* d, const double* gy, double* gu, const double* alpha_base,
+                               const double* beta_base, const double* alpha_slope, const double* beta_slope,
+                               const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    return pde_adi_f64_backward_input_states(d, gy, nullptr, nullptr, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                                             fwd_workspace, workspace, workspace_bytes, stream);
+}
+size_t pde_adi_rect_backward_input_workspace_bytes(const PdeAdiRectDesc* d) { return rect_fwd_bytes<float>(d); }
+int pde_adi_rect_backward_input_states(const PdeAdiRectDesc* d, const void* gy, const void* gstates,
+                                       const uint64_t emit_mask[2], void* gu, const float* alpha_base,
+                                       const float* beta_base, const float* alpha_slope, const float* beta_slope,
+                                       const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    return any_backward_input<float>(d, check_desc_rect<float, PdeAdiRectDesc>, gy, gstates, emit_mask, gu, alpha_base,
+                                     beta_base, alpha_slope, beta_slope, fwd_workspace, workspace, workspace_bytes, stream);
+}
+int pde_adi_rect_backward_input(const PdeAdiRectDesc* d, const void* gy, void* gu, const float* alpha_base,
+                                const float* beta_base, const float* alpha_slope, const float* beta_slope,
+                                const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    return pde_adi_rect_backward_input_states(d, gy, nullptr, nullptr, gu, alpha_base, beta_base, alpha_slope, beta_slope,
+                                              fwd_workspace, workspace, workspace_bytes, stream);
+}
+size_t pde_adi_rect_f64_backward_input_workspace_bytes(const PdeAdiRectDescF64* d) { return rect_fwd_bytes<double>(d); }
+int pde_adi_rect_f64_backward_input_states(const PdeAdiRectDescF64* d, const double* gy, const double* gstates,
+                                           const uint64_t emit_mask[2], double* gu, const double* alpha_base,
+                                           const double* beta_base, const double* alpha_slope, const double* beta_slope,
+                                           const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+    return any_backward_input<double>(d, check_desc_rect<double, PdeAdiRectDescF64>, gy, gstates, emit_mask, gu, alpha_base,
+                                      beta_base, alpha_slope, beta_slope, fwd_workspace, workspace, workspace_bytes, stream);
+}
+int pde_adi_rect_f64_backward_input(const PdeAdiRectDescF64* d, const double* gy, double* gu, const double* alpha_base,
+                                    const double* beta_base, const double* alpha_slope, const double* beta_slope,
+                                    const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    return pde_adi_rect_f64_backward_input_states(d, gy, nullptr, nullptr, gu, alpha_base, beta_base, alpha_slope,
+                                                  beta_slope, fwd_workspace, workspace, workspace_bytes, stream);
+}
 
 size_t pde_adi_f64_forward_workspace_bytes(const PdeAdiDescF64* d) {
     if (check_desc_f64(d) != PDE_OK) return 0;

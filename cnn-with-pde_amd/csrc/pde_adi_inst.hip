@@ -93,7 +93,31 @@ int bwd_emit_io(int split, const SweepArgs& sa, int grid, hipStream_t st) {
     }
 }
 
+// the backward for the input alone (pde_adi_backward_input*): the forward's launch shape
+template <typename IO, bool EMIT>
+int bwd_input_io(int split, const SweepArgs& sa, int grid, size_t lds, hipStream_t st) {
+    constexpr int N = PDE_INST_N;
+    switch (split) {
+        case kSplitStrang: return launch(adi_bwd_input_kernel<N, kJFwd, IO, kSplitStrang, EMIT>, sa, grid, lds, st);
+        case kSplitLie: return launch(adi_bwd_input_kernel<N, kJFwd, IO, kSplitLie, EMIT>, sa, grid, lds, st);
+        default: return launch(adi_bwd_input_kernel<N, kJFwd, IO, kSplitAny, EMIT>, sa, grid, lds, st);
+    }
+}
+
 }  // namespace
+
+int PDE_CAT(adi_launch_bwd_input_, PDE_INST_N)(int io, int split, int emit, const void* args, int grid, size_t lds,
+                                               hipStream_t st) {
+    const SweepArgs& sa = *static_cast<const SweepArgs*>(args);
+    if (emit) {
+        if (io == PDE_IO_F16) return bwd_input_io<half_t, true>(split, sa, grid, lds, st);
+        return io == PDE_IO_F32 ? bwd_input_io<float, true>(split, sa, grid, lds, st)
+                                : bwd_input_io<bf16_t, true>(split, sa, grid, lds, st);
+    }
+    if (io == PDE_IO_F16) return bwd_input_io<half_t, false>(split, sa, grid, lds, st);
+    return io == PDE_IO_F32 ? bwd_input_io<float, false>(split, sa, grid, lds, st)
+                            : bwd_input_io<bf16_t, false>(split, sa, grid, lds, st);
+}
 
 int PDE_CAT(adi_launch_fwd_emit_, PDE_INST_N)(int io, int split, const void* args, int grid, size_t lds, hipStream_t st) {
     const SweepArgs& sa = *static_cast<const SweepArgs*>(args);

@@ -24,12 +24,14 @@ constexpr int kJBwd = PDE_JB;    // planes per lane in the backward kernel
 
 // return 0 on success, PDE_E_LAUNCH otherwise.  ho: the forward's hand-over schedule (N = 32, fp32, Strang only; the
 // caller checks that and sizes `lds` for it).  _emit: the variants that write / read the emitted states (SweepArgs::states,
-// SweepArgs::em), forward on the barrier-per-sweep schedule
+// SweepArgs::em), forward on the barrier-per-sweep schedule.  _bwd_input: the backward for the input alone (gu = F^T gy;
+// emit != 0: with the emitted states' gradients), launched like the forward
 #define PDE_DECLARE_N(NN)                                                                              \
     int adi_launch_fwd_##NN(int io, int split, int ho, const void* args, int grid, size_t lds, hipStream_t st); \
     int adi_launch_bwd_##NN(int io, int split, const void* args, int grid, hipStream_t st);                      \
     int adi_launch_fwd_emit_##NN(int io, int split, const void* args, int grid, size_t lds, hipStream_t st);    \
-    int adi_launch_bwd_emit_##NN(int io, int split, const void* args, int grid, hipStream_t st);
+    int adi_launch_bwd_emit_##NN(int io, int split, const void* args, int grid, hipStream_t st);                 \
+    int adi_launch_bwd_input_##NN(int io, int split, int emit, const void* args, int grid, size_t lds, hipStream_t st);
 PDE_DECLARE_N(8) PDE_DECLARE_N(12) PDE_DECLARE_N(16) PDE_DECLARE_N(20) PDE_DECLARE_N(24) PDE_DECLARE_N(28) PDE_DECLARE_N(32)
 #undef PDE_DECLARE_N
 

@@ -476,7 +476,12 @@ class _AdiFn(torch.autograd.Function):
 
     One body, because the library has one: a plain call is the family's ``*_states`` call without a mask.  ``emit`` None is
     the plain call and returns ``y``, a tensor of its own.  Otherwise ``emit`` lists the sweeps whose state is returned
-    (the last one included) and the result is ONE tensor (K', B, C, H, W) whose last slice is the library's ``y``."""
+    (the last one included) and the result is ONE tensor (K', B, C, H, W) whose last slice is the library's ``y``.
+
+    When the input needs a gradient and none of the four coefficient tensors does (a frozen layer, an attack, a saliency
+    map), the backward is the family's ``*_backward_input_states``: gu = F^T gy alone, bitwise the full backward's gu.
+    The node then keeps the coefficient views and the forward's workspace only — neither ``y`` nor ``u`` — and asks for no
+    coefficient maxima unless a ``kmax_sink`` was handed in.  ``PDE_BWD_INPUT=0`` keeps the full backward for such calls."""
 
     @staticmethod
     def forward(ctx, u, ab, bb, asl, bsl, sweeps, smooth3, clamp_max, eps, ckpt, kmax_sink, emit=None, rect=False,
@@ -501,7 +506,14 @@ class _AdiFn(torch.autograd.Function):
         ebits = None if emit is None else sum(1 << s for s in emit[:-1])
         ws = _workspace(getattr(lib, fam + "forward_workspace_bytes")(C.byref(d)), u.device)
         need_grad = any(ctx.needs_input_grad[:5])
-        want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
+        # frozen coefficients: the backward is gu = F^T gy alone (*_backward_input_states).  It reads neither y nor u and
+        # plans no checkpoints, so nothing of u's shape is kept and no coefficient maxima are asked for — unless the
+        # caller handed in a sink for them
+        input_only = need_grad and not any(ctx.needs_input_grad[1:5]) and L.bwd_input_enabled()
+        if input_only:
+            want_kmax = not f64 and kmax_sink is not None
+        else:
+            want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
         kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
         with torch.cuda.device(u.device):
             # per-sweep maximum coefficient (a by-product of the factorisation kernel): copied to pinned host
@@ -518,7 +530,11 @@ class _AdiFn(torch.autograd.Function):
             if tk is not None and kmax_sink is not None:
                 kmax_sink.append(tk)
         ctx.fwd_ws = ws if need_grad else None       # factorisation reused by the backward
-        ctx.save_for_backward(out, u if (need_grad and ckpt != 0) else None, *p)
+        ctx.input_only = (out.shape, out.dtype, out.device) if input_only else None
+        if input_only:
+            ctx.save_for_backward(*p)
+        else:
+            ctx.save_for_backward(out, u if (need_grad and ckpt != 0) else None, *p)
         ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt, rect, f64, ebits)
         ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
         return out
@@ -526,6 +542,8 @@ class _AdiFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         lib = L.load()
+        if ctx.input_only is not None:
+            return _AdiFn._backward_input(ctx, g)
         out, u, *p = ctx.saved_tensors
         sweeps, smooth3, clamp_max, eps, ckpt, rect, f64, ebits = ctx.cfg
         B, Cc, H, W = out.shape[-4:]
@@ -547,6 +565,29 @@ class _AdiFn(torch.autograd.Function):
         ctx.fwd_ws = None
         gp = [_grad_as(t, dt, s) for t, (s, dt) in zip(gp, ctx.param_meta)]
         return (gu, *gp) + (None,) * 9
+
+    @staticmethod
+    def _backward_input(ctx, g):
+        """The backward of a call whose coefficients take no gradient: the family's ``*_backward_input_states``."""
+        lib = L.load()
+        p = ctx.saved_tensors
+        sweeps, smooth3, clamp_max, eps, _, rect, f64, ebits = ctx.cfg
+        shape, dtype, device = ctx.input_only
+        B, Cc, H, W = shape[-4:]
+        fam, desc_cls, _ = _ADI_FAMILY[rect, f64]
+        g = _grad_as(g, dtype).contiguous()
+        gy, gtraj = (g, None) if ebits is None else (g[-1], g)
+        d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(g), sweeps, smooth3, clamp_max, eps)
+        gu = torch.empty((B, Cc, H, W), dtype=dtype, device=device)
+        ws = _workspace(getattr(lib, fam + "backward_input_workspace_bytes")(C.byref(d)), device)
+        with torch.cuda.device(device):              # autograd thread: set device, fetch the stream here
+            L.check(getattr(lib, fam + "backward_input_states")(C.byref(d), _ptr(gy), _ptr(gtraj),
+                                                                None if ebits is None else _mask128(ebits), _ptr(gu),
+                                                                *[_ptr(t) for t in p], _ptr(ctx.fwd_ws), _ptr(ws),
+                                                                ws.numel(), _stream()),
+                    fam + "backward_input_states")
+        ctx.fwd_ws = None
+        return (gu,) + (None,) * 13
 
 
 class _AdiMixedFn(torch.autograd.Function):

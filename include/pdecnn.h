@@ -916,6 +916,72 @@ int pde_adi_rect_f64_backward_states(const PdeAdiRectDescF64* d, const double* g
                                      double* g_alpha_base, double* g_beta_base, double* g_alpha_slope, double* g_beta_slope,
                                      const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the backward of a layer whose coefficients take no gradient -----------------------------------------
+ * Every implicit layer is linear in its input: gu = F^T gy, the transposed two-sided solves walked from the last sweep to
+ * the first.  These entry points compute that and nothing else — for frozen coefficients, adversarial attacks, saliency
+ * maps, a frozen feature extractor under a trainable head.  They read neither y nor u, rebuild no state, keep no
+ * checkpoints, form no parameter-gradient sums and need no coefficient maxima: 8 bytes per element (gy in, gu out) where
+ * pde_adi_backward moves 12, in a launch shaped like the forward's.  gu is bit for bit the gu of the family's
+ * *_backward_states call on the same arguments (the same operations per plane in the same order).
+ * The plain call is the _states call with a NULL mask.  gstates / emit_mask as in *_backward_states: dL/d(state after
+ * sweep s) joins the adjoint when the reverse walk is about to enter sweep s; a non-empty mask with gstates NULL, or a
+ * bit at or above num_sweeps-1: PDE_E_BADARG.  fwd_workspace: the workspace the forward call of the same descriptor and
+ * coefficients left behind (its factorisation is read, not written), or NULL — the call then factorises into
+ * `workspace` itself.  workspace: at least *_backward_input_workspace_bytes(d) bytes, 16-byte aligned, required either
+ * way (PDE_E_WORKSPACE); the query is 0 for a descriptor the call refuses.  Descriptors, error codes and "checked on
+ * the host before any launch" are those of the family's other calls, except that sweeps of one axis need not share
+ * delta / h2 (that restriction of pde_adi_backward belongs to its time-weighted sums).  Nothing is allocated,
+ * synchronised or waited for inside the calls.
+ * pde_adi_backward_input_kernel: which kernel the square fp32 / bf16 / fp16 call runs — 0 the fused HIP kernel
+ * (N = 8, 12, ..., 32; barrier-per-sweep schedule, records resident for a launch of at most three sweeps), 2 the
+ * any-size kernel (one workgroup per plane); PDE_E_BADARG for a descriptor the call refuses.  The rectangle and
+ * float64 families always run the any-size kernel. */
+int pde_adi_backward_input_kernel(const PdeAdiDesc* d);
+size_t pde_adi_backward_input_workspace_bytes(const PdeAdiDesc* d);
+int pde_adi_backward_input(const PdeAdiDesc* d, const void* gy, void* gu,
+                           const float* alpha_base, const float* beta_base,
+                           const float* alpha_slope, const float* beta_slope,
+                           const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_backward_input_states(const PdeAdiDesc* d, const void* gy, const void* gstates, const uint64_t emit_mask[2],
+                                  void* gu,
+                                  const float* alpha_base, const float* beta_base,
+                                  const float* alpha_slope, const float* beta_slope,
+                                  const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
+size_t pde_adi_rect_backward_input_workspace_bytes(const PdeAdiRectDesc* d);
+int pde_adi_rect_backward_input(const PdeAdiRectDesc* d, const void* gy, void* gu,
+                                const float* alpha_base, const float* beta_base,
+                                const float* alpha_slope, const float* beta_slope,
+                                const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_rect_backward_input_states(const PdeAdiRectDesc* d, const void* gy, const void* gstates,
+                                       const uint64_t emit_mask[2], void* gu,
+                                       const float* alpha_base, const float* beta_base,
+                                       const float* alpha_slope, const float* beta_slope,
+                                       const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
+size_t pde_adi_f64_backward_input_workspace_bytes(const PdeAdiDescF64* d);
+int pde_adi_f64_backward_input(const PdeAdiDescF64* d, const double* gy, double* gu,
+                               const double* alpha_base, const double* beta_base,
+                               const double* alpha_slope, const double* beta_slope,
+                               const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_f64_backward_input_states(const PdeAdiDescF64* d, const double* gy, const double* gstates,
+                                      const uint64_t emit_mask[2], double* gu,
+                                      const double* alpha_base, const double* beta_base,
+                                      const double* alpha_slope, const double* beta_slope,
+                                      const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+
+size_t pde_adi_rect_f64_backward_input_workspace_bytes(const PdeAdiRectDescF64* d);
+int pde_adi_rect_f64_backward_input(const PdeAdiRectDescF64* d, const double* gy, double* gu,
+                                    const double* alpha_base, const double* beta_base,
+                                    const double* alpha_slope, const double* beta_slope,
+                                    const void* fwd_workspace, void* workspace, size_t workspace_bytes, void* stream);
+int pde_adi_rect_f64_backward_input_states(const PdeAdiRectDescF64* d, const double* gy, const double* gstates,
+                                           const uint64_t emit_mask[2], double* gu,
+                                           const double* alpha_base, const double* beta_base,
+                                           const double* alpha_slope, const double* beta_slope,
+                                           const void* fwd_workspace, void* workspace, size_t workspace_bytes,
+                                           void* stream);
+
 /* ---- utilities ------------------------------------------------------------------------- */
 
 /* Average device time (ms) per launch of the dominant kernel of the most recent
