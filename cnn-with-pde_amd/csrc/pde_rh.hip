@@ -978,6 +978,15 @@ typedef _Float16 rh_h8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned short rh_f2h(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
 __device__ __forceinline__ float rh_h2f(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
 __device__ __forceinline__ float rh_r16(float f) { return (float)(_Float16)f; }
+// scale x as autocast's element-wise kernels compute it: an fp32 product, rounded to fp32, that r() then rounds again.  The
+// empty asm keeps the product in a register as fp32: without it the compiler folds the multiplication into the conversion
+// (v_fma_mixlo_f16), which rounds the exact product once and differs from autocast by one fp16 step wherever the fp32
+// rounding lands on an fp16 tie — one element in forty at scale = 0.7 (tests/test_gpu_rh16_stages.py).
+__device__ __forceinline__ float rh_scaled(float scale, float x) {
+    float p = scale * x;
+    asm volatile("" : "+v"(p));
+    return p;
+}
 
 // The 16-bit element of the layer: every kernel below is written once over E.  RhF16 is fp16 autocast; RhBf16 is bf16
 // autocast — the same contract with r() = round to nearest even to bf16 (v_cvt_pk_bf16_f32; fp32's exponent range, so
@@ -1055,7 +1064,7 @@ __global__ __launch_bounds__(WV * 64) void rh_part16_kernel(RhPart16Args a) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float x = E::r(v[j]);
-                    if (a.dbl) x = a.ascale * x;
+                    if (a.dbl) x = rh_scaled(a.ascale, x);
                     h[j] = row < a.B ? E::bits(x) : (unsigned short)0;
                 }
                 *reinterpret_cast<uint2*>(As + row * kH16Pitch + 8 * c) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
@@ -1160,7 +1169,7 @@ __global__ __launch_bounds__(256) void rh_out16_epi_kernel(Rh16OutArgs a, const 
         const int row = e.row0 + r;
         if (row < a.B) {
             const size_t o = (size_t)row * a.D + e.col;
-            const float v = E::r(a.scale * E::r(acc[r]));
+            const float v = E::r(rh_scaled(a.scale, E::r(acc[r])));
             if (a.base != nullptr) static_cast<float*>(a.out)[o] = a.base[o] + v;
             else static_cast<unsigned short*>(a.out)[o] = E::bits(v);
         }
@@ -1276,7 +1285,7 @@ __global__ __launch_bounds__(kRhThreads) void rh_outer16_kernel(RhOuter16Args a)
             const float v[4] = {pb[m].x, pb[m].y, pb[m].z, pb[m].w};
             unsigned short h[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) h[j] = E::bits(second ? a.s2 * E::r(v[j]) : v[j]);
+            for (int j = 0; j < 4; ++j) h[j] = E::bits(second ? rh_scaled(a.s2, E::r(v[j])) : v[j]);
             *reinterpret_cast<uint2*>(base + IA + row * PB + 8 * c) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
         }
     };

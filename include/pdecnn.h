@@ -642,6 +642,9 @@ int pde_sym_layer_dk_path(int32_t B, int32_t D);
 /* The rounding points of torch.autocast("cuda", torch.float16) for the layer above, r() = round to fp16 (overflow to
  * +-inf), accumulation in fp32:
  *     P = r(r(X) K16^T);  N = r(BatchNorm1d(P));  H = r(act(N));  Q = r(H K16);  out = base + r(scale Q)
+ * The products by `scale` (scale Q here, scale r(g_out) in the backward) are fp32 multiplications rounded to fp32 before
+ * r() rounds them again, as autocast's element-wise kernels do — not one rounding of the exact product: at scale = 0.7
+ * the two differ by a 16-bit step for one element in forty.  The sign of a zero is not specified.
  * K16: (D, D) fp16 = r(K) (pde_sym_k_to_f16, once per autocast region).  X, base: (B, D) fp32.  P, H: (B, D) fp16,
  * written for the backward.  out: fp16 (B, D) = r(scale Q) when base is NULL (F_sym(Y) is scale = -1), fp32 (B, D)
  * otherwise.  Statistics, running statistics, mean and invstd as in pde_sym_layer_forward.  1 <= B <= 128 and D a
