@@ -22,7 +22,7 @@ PDE_JACOBI_MAX_HW = 1024
 PDE_JACOBI_TILED_K = 10
 
 ERRORS = {
-    -1: "PDE_E_BADARG (null pointer, bad dimension or enum)",
+    -1: "PDE_E_BADARG (null or misaligned pointer, bad dimension or enum)",
     -2: "PDE_E_UNSUPPORTED_N (line length — either side of a rectangle — outside [2, 128], or a per-step / one-launch "
         "entry point at a line length without fused kernels: those exist for multiples of 4 in [8, 32])",
     -3: "PDE_E_TOO_MANY_SWEEPS",

@@ -35,7 +35,7 @@ using torch::autograd::variable_list;
 
 const char* err_text(int rc) {
     switch (rc) {
-        case -1: return "PDE_E_BADARG (null pointer, bad dimension or enum)";
+        case -1: return "PDE_E_BADARG (null or misaligned pointer, bad dimension or enum)";
         case -2:
             return "PDE_E_UNSUPPORTED_N (line length outside [2, 128], or a per-step / one-launch entry point at a line length "
                    "without fused kernels: those exist for multiples of 4 in [8, 32])";
@@ -175,6 +175,15 @@ void plan_checkpoints(const float* kmax, int n, double amax, uint64_t mask[2]) {
 
 int popcount2(const uint64_t m[2]) { return __builtin_popcountll(m[0]) + __builtin_popcountll(m[1]); }
 
+// functional._aligned: the tensor as the library may be handed it (pdecnn.h, "Alignment": tensors, coefficient planes and
+// matrices begin on 16 bytes) — itself when it does, as every fresh allocation, else a contiguous copy of its own.
+// contiguous() leaves a contiguous view where its storage offset puts it: u[1:], a parameter cut from one flat buffer.
+// Running statistics are updated in place one element at a time and are passed as they are.
+Tensor aligned(Tensor t) {
+    if (!t.defined() || (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0) return t;
+    return t.clone(at::MemoryFormat::Contiguous);
+}
+
 // functional._as_chw: (C,N,N) fp32 contiguous view of a coefficient tensor given as (N,N), (1,N,N) or (C,N,N)
 Tensor as_chw(const Tensor& p, int64_t C, int64_t N) {
     Tensor q = p.detach();
@@ -182,7 +191,7 @@ Tensor as_chw(const Tensor& p, int64_t C, int64_t N) {
     PDE_REQUIRE(q.dim() == 3 && q.size(0) == C && q.size(1) == N && q.size(2) == N, "coefficient of shape ", p.sizes(),
                 " does not match (", C, ",", N, ",", N, ")");
     if (q.scalar_type() != at::kFloat) q = q.to(at::kFloat);
-    return q.contiguous();
+    return aligned(q.contiguous());
 }
 
 // tensor types the kernels take as they are (functional._IO_TYPES; the caller widens an fp16 input off the float16 route)
@@ -230,7 +239,7 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
         if (!io_type(u)) u = u.to(at::kFloat);
-        u = u.contiguous();
+        u = aligned(u.contiguous());
         PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                     "descriptor does not match the tensor");
         Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
@@ -287,7 +296,7 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
         const auto dtype = static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
         Tensor gy = grads[0];
         if (gy.scalar_type() != dtype) gy = gy.to(dtype);
-        gy = gy.contiguous();
+        gy = aligned(gy.contiguous());
         c10::hip::HIPGuardMasqueradingAsCUDA guard(gy.device());
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(gy.device().index()).stream();
         Tensor gu = at::empty_like(gy);
@@ -319,7 +328,7 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(y.device().index()).stream();
         Tensor gy = grads[0];
         if (gy.scalar_type() != y.scalar_type()) gy = gy.to(y.scalar_type());
-        gy = gy.contiguous();
+        gy = aligned(gy.contiguous());
         Tensor gu = at::empty_like(y);
         static const char* const kShape[4] = {"sh0", "sh1", "sh2", "sh3"};
         Tensor gp[4];
@@ -378,10 +387,12 @@ void plan_steps(const float* kmax, int K, int sps, double amax, uint64_t mask[2]
     }
 }
 
-Tensor as_f32(const Tensor& t) {
+// wide: a tensor or matrix the kernels read 16 bytes wide; otherwise one of the header's ELEMENT-ALIGNED parameters
+// (skip_weight, weights, gamma / beta, bn_weight / bn_bias), which may begin wherever its elements do: no copy
+Tensor as_f32(const Tensor& t, bool wide = true) {
     Tensor q = t.detach();
     if (q.scalar_type() != at::kFloat) q = q.to(at::kFloat);
-    return q.contiguous();
+    return wide ? aligned(q.contiguous()) : q.contiguous();
 }
 
 std::vector<int64_t> states_shape(int64_t K, const Tensor& u) {
@@ -405,13 +416,13 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
         if (!io_type(u)) u = u.to(at::kFloat);
-        u = u.contiguous();
+        u = aligned(u.contiguous());
         PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                     "descriptor does not match the tensor");
         const int64_t K = d.num_sweeps / sps;
         Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
         Tensor Mf = as_f32(M);
-        Tensor sw = skip.defined() ? as_f32(skip).reshape({1}) : Tensor();
+        Tensor sw = skip.defined() ? as_f32(skip, false).reshape({1}) : Tensor();
         const bool want_kmax = need_grad && ckpt_mode == 1;
         c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
@@ -470,7 +481,7 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
         Tensor gy = grads[0];
         if (gy.scalar_type() != u.scalar_type()) gy = gy.to(u.scalar_type());
-        gy = gy.contiguous();
+        gy = aligned(gy.contiguous());
         Tensor gu = at::empty_like(gy);
         static const char* const kShape[4] = {"sh0", "sh1", "sh2", "sh3"};
         Tensor gp[4];
@@ -522,7 +533,7 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
         if (!io_type(u)) u = u.to(at::kFloat);
-        u = u.contiguous();
+        u = aligned(u.contiguous());
         PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
                     "descriptor does not match the tensor");
         const int64_t K = d.num_sweeps / sps;
@@ -583,7 +594,7 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
         Tensor gy = grads[0];
         if (gy.scalar_type() != u.scalar_type()) gy = gy.to(u.scalar_type());
-        gy = gy.contiguous();
+        gy = aligned(gy.contiguous());
         Tensor gu = at::empty_like(gy);
         static const char* const kShape[4] = {"sh0", "sh1", "sh2", "sh3"};
         Tensor gp[4];
@@ -625,10 +636,10 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
         Tensor u = u_in.detach();
         if (!io_type(u)) u = u.to(at::kFloat);
-        u = u.contiguous();
+        u = aligned(u.contiguous());
         const bool want_kmax = need_grad && ckpt_mode == 1;
         ctx->set_materialize_grads(false);
-        Tensor wdev = weights.defined() ? as_f32(weights) : Tensor();
+        Tensor wdev = weights.defined() ? as_f32(weights, false) : Tensor();
         c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
 
@@ -730,7 +741,7 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         Tensor gout = grads[0];
         if (gout.defined()) {
             if (gout.scalar_type() != u.scalar_type()) gout = gout.to(u.scalar_type());
-            gout = gout.contiguous();
+            gout = aligned(gout.contiguous());
         }
         std::vector<PdeSmallLayer> arr(nl);
         std::vector<uint64_t> mk(2 * nl);
@@ -756,11 +767,11 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
             Tensor gyi = grads[1 + i], gsi = want_sums ? grads[1 + nl + i] : Tensor();
             if (gyi.defined()) {
                 if (gyi.scalar_type() != u.scalar_type()) gyi = gyi.to(u.scalar_type());
-                gyi = gyi.contiguous();
+                gyi = aligned(gyi.contiguous());
             }
             if (gsi.defined()) {
                 if (gsi.scalar_type() != at::kFloat) gsi = gsi.to(at::kFloat);
-                gsi = gsi.contiguous();
+                gsi = aligned(gsi.contiguous());
             }
             any_in = any_in || gyi.defined() || gsi.defined();
             const Tensor& sws = hold[kmax_stride * i + (kmax_stride - 1)];
@@ -850,7 +861,7 @@ struct SymFn : public torch::autograd::Function<SymFn> {
                     "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
         PDE_REQUIRE(X.dim() == 2 && K.dim() == 2 && K.size(0) == X.size(1) && K.size(1) == X.size(1), "expected X (B, D), K (D, D)");
         const int64_t B = X.size(0), D = X.size(1);
-        Tensor Xf = as_f32(X), Kf = as_f32(K), gm = as_f32(gamma), bt = as_f32(beta);
+        Tensor Xf = as_f32(X), Kf = as_f32(K), gm = as_f32(gamma, false), bt = as_f32(beta, false);
         Tensor bs = base.has_value() ? as_f32(*base) : Tensor();
         c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(X.device().index()).stream();
@@ -883,7 +894,7 @@ struct SymFn : public torch::autograd::Function<SymFn> {
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Xf.device().index()).stream();
         Tensor g = grads[0];
         if (g.scalar_type() != at::kFloat) g = g.to(at::kFloat);
-        g = g.contiguous();
+        g = aligned(g.contiguous());
         Tensor dP = at::empty_like(Xf), gX = at::empty_like(Xf), gK = at::empty_like(Kf);
         Tensor gg = at::empty({D}, Xf.options()), gb = at::empty({D}, Xf.options());
         Tensor ws = sym_workspace(B, D, Xf, st);
@@ -966,8 +977,9 @@ struct Sym16Node : public torch::autograd::Function<Fn> {
         PDE_REQUIRE(X.dim() == 2 && K16.dim() == 2 && K16.size(0) == X.size(1) && K16.size(1) == X.size(1) &&
                     K16.scalar_type() == Api::dtype && K16.is_contiguous(), Api::k16_msg);
         const int64_t B = X.size(0), D = X.size(1);
-        Tensor Xf = as_f32(X), gm = as_f32(gamma), bt = as_f32(beta);
+        Tensor Xf = as_f32(X), gm = as_f32(gamma, false), bt = as_f32(beta, false);
         Tensor bs = base.has_value() ? as_f32(*base) : Tensor();
+        const Tensor K16a = aligned(K16);
         c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(X.device().index()).stream();
         const auto h = Xf.options().dtype(Api::dtype);
@@ -977,14 +989,14 @@ struct Sym16Node : public torch::autograd::Function<Fn> {
         Tensor ws = sym16_workspace<Api>(B, D, Xf);
         float* rm = run_mean.has_value() ? run_mean->data_ptr<float>() : nullptr;
         float* rv = run_var.has_value() ? run_var->data_ptr<float>() : nullptr;
-        check(Api::forward((int32_t)B, (int32_t)D, (int32_t)act, training ? 1 : 0, Xf.data_ptr<float>(), h16(K16),
+        check(Api::forward((int32_t)B, (int32_t)D, (int32_t)act, training ? 1 : 0, Xf.data_ptr<float>(), h16(K16a),
                            gm.data_ptr<float>(), bt.data_ptr<float>(), rm, rv, (float)momentum, (float)eps,
                            bs.defined() ? bs.data_ptr<float>() : nullptr, (float)scale, h16(P), h16(H),
                            mean.data_ptr<float>(), invstd.data_ptr<float>(), out.data_ptr(), ws.data_ptr(),
                            (size_t)ws.numel(), (void*)st),
               Api::forward_name);
         if (need_grad) {
-            ctx->save_for_backward({Xf, K16, gm, P, H, mean, invstd});
+            ctx->save_for_backward({Xf, K16a, gm, P, H, mean, invstd});
             ctx->saved_data["cfg"] = std::vector<int64_t>{training ? 1 : 0, act, base.has_value() ? 1 : 0};
             ctx->saved_data["scale"] = scale;
         }
@@ -1001,7 +1013,7 @@ struct Sym16Node : public torch::autograd::Function<Fn> {
         hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Xf.device().index()).stream();
         Tensor g = grads[0];
         if (g.scalar_type() != at::kFloat) g = g.to(at::kFloat);
-        g = g.contiguous();
+        g = aligned(g.contiguous());
         Tensor dP = at::empty({B, D}, P.options()), gX = at::empty_like(Xf), gK = at::empty({D, D}, Xf.options());
         Tensor gg = at::empty({D}, Xf.options()), gb = at::empty({D}, Xf.options());
         Tensor ws = sym16_workspace<Api>(B, D, Xf);

@@ -1078,6 +1078,11 @@ size_t pde_adi_backward_workspace_bytes(const PdeAdiDesc* d, int32_t num_checkpo
     return b;
 }
 
+// Where the buffers of a whole-schedule call may begin (pdecnn.h, "Alignment"): the fused kernels move tensors and
+// coefficient planes 16 bytes wide; the any-size kernels (pde_adi_gen.hip) one element at a time.
+static unsigned tensor_align(const PdeAdiDesc* d) { return fused_n(d->N) ? kVecAlign : io_elem_bytes(d->io_dtype); }
+static unsigned param_align(const PdeAdiDesc* d) { return fused_n(d->N) ? kVecAlign : 4u; }
+
 // pde_adi_forward and pde_adi_forward_states (states / emit_mask null or empty: the plain call, launch for launch)
 static int adi_forward_impl(const PdeAdiDesc* d, const void* u, void* y, void* states, const uint64_t* emit_mask,
                             const float* alpha_base, const float* beta_base, const float* alpha_slope,
@@ -1086,6 +1091,9 @@ static int adi_forward_impl(const PdeAdiDesc* d, const void* u, void* y, void* s
     int rc = check_desc(d, true);
     if (rc != PDE_OK) return rc;
     if (!u || !y || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    if (misaligned(tensor_align(d), u, y, states) || misaligned(param_align(d), alpha_base, beta_base, alpha_slope, beta_slope) ||
+        misaligned(4, kappa_max, kappa_max_host))
+        return PDE_E_BADARG;
     int nem;
     rc = emit_plan(d->num_sweeps, emit_mask, states, nem);
     if (rc != PDE_OK) return rc;
@@ -1138,6 +1146,11 @@ static int adi_backward_impl(const PdeAdiDesc* d, const void* gy, const void* gs
     if (!gy || !y || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !g_alpha_base ||
         !g_beta_base || !g_alpha_slope || !g_beta_slope || !workspace)
         return PDE_E_BADARG;
+    if (misaligned(tensor_align(d), gy, gstates, y, u, gu) ||
+        misaligned(param_align(d), alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base, g_beta_base, g_alpha_slope,
+                   g_beta_slope))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, fwd_workspace)) return PDE_E_WORKSPACE;
     int nem;
     rc = emit_plan(d->num_sweeps, emit_mask, gstates, nem);
     if (rc != PDE_OK) return rc;
@@ -1218,6 +1231,9 @@ int pde_adi_backward_input_states(const PdeAdiDesc* d, const void* gy, const voi
     int rc = check_desc(d, true);
     if (rc != PDE_OK) return rc;
     if (!gy || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    if (misaligned(tensor_align(d), gy, gstates, gu) || misaligned(param_align(d), alpha_base, beta_base, alpha_slope, beta_slope))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, fwd_workspace)) return PDE_E_WORKSPACE;
     int nem;
     rc = emit_plan(d->num_sweeps, emit_mask, gstates, nem);
     if (rc != PDE_OK) return rc;
@@ -1264,6 +1280,8 @@ static int factor_steps_impl(const PdeAdiDesc* d, int32_t sweeps_per_step, const
     int rc = check_desc(d);
     if (rc != PDE_OK) return rc;
     if (!alpha_base || !beta_base || !alpha_slope || !beta_slope || !steps_workspace) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, alpha_base, beta_base, alpha_slope, beta_slope) || misaligned(4, kappa_max, kappa_max_host))
+        return PDE_E_BADARG;
     const size_t need = pde_adi_steps_workspace_bytes(d, sweeps_per_step);
     if (need == 0) return PDE_E_BADARG;
     if (workspace_bytes < need || ((uintptr_t)steps_workspace & 15)) return PDE_E_WORKSPACE;
@@ -1291,7 +1309,8 @@ int pde_adi_forward_step(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t s
     PdeAdiDesc ds;
     int rc = step_desc(d, sweeps_per_step, step, ds);
     if (rc != PDE_OK) return rc;
-    if (!u || !y || !steps_workspace) return PDE_E_BADARG;
+    if (!u || !y || !steps_workspace || misaligned(kVecAlign, u, y)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, steps_workspace)) return PDE_E_WORKSPACE;
     const char* ws = static_cast<const char*>(steps_workspace);
     const float* coef = reinterpret_cast<const float*>(ws) + (size_t)step * sweeps_per_step * d->C * kRecStride;
     const SweepTab* tab = reinterpret_cast<const SweepTab*>(ws + steps_tab_offset(d)) + step;
@@ -1312,7 +1331,8 @@ int pde_adi_backward_step(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t 
     PdeAdiDesc ds;
     int rc = step_desc(d, sweeps_per_step, step, ds);
     if (rc != PDE_OK) return rc;
-    if (!gy || !y || !gu || !steps_workspace || !workspace) return PDE_E_BADARG;
+    if (!gy || !y || !gu || !steps_workspace || !workspace || misaligned(kVecAlign, gy, y, u, gu)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, steps_workspace)) return PDE_E_WORKSPACE;
     int nck, Sf;
     rc = ckpt_plan(&ds, ckpt_mask, u, nck, Sf);
     if (rc != PDE_OK) return rc;
@@ -1341,6 +1361,9 @@ int pde_adi_param_grads(const PdeAdiDesc* d, int32_t sweeps_per_step, const floa
     if (!alpha_base || !beta_base || !alpha_slope || !beta_slope || !g_alpha_base || !g_beta_base || !g_alpha_slope ||
         !g_beta_slope || !steps_workspace || !workspace)
         return PDE_E_BADARG;
+    if (misaligned(kVecAlign, alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base, g_beta_base, g_alpha_slope, g_beta_slope))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, steps_workspace, workspace)) return PDE_E_WORKSPACE;
     AxisWeights w;
     rc = axis_weights(d, w);                               // over the whole schedule
     if (rc != PDE_OK) return rc;
@@ -1381,6 +1404,7 @@ int pde_adi_mixed_forward(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t 
                           const float* beta_slope, float* kappa_max, float* kappa_max_host, void* kappa_event,
                           void* steps_workspace, size_t workspace_bytes, void* stream) {
     if (!u || !states || !M || (mode != 1 && mode != 2)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, u, states, y, M)) return PDE_E_BADARG;      // the rest: factor_steps_impl, before its launch
     bool wrote = false;
     int rc = factor_steps_impl(d, sweeps_per_step, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, kappa_max_host,
                                &wrote, steps_workspace, workspace_bytes, stream);
@@ -1423,6 +1447,10 @@ int pde_adi_mixed_backward(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t
                            float* g_beta_slope, float* gM, const void* steps_workspace, void* workspace,
                            size_t workspace_bytes, void* stream) {
     if (!gy || !u || !states || !M || !gu || !gM || !workspace || (mode != 1 && mode != 2)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, gy, u, states, y, M, gu, gM, alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base, g_beta_base,
+                   g_alpha_slope, g_beta_slope))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, steps_workspace)) return PDE_E_WORKSPACE;
     const int nck = count_ckpt(ckpt_mask);
     const size_t need = pde_adi_mixed_backward_workspace_bytes(d, sweeps_per_step, nck);
     if (need == 0) return PDE_E_BADARG;
@@ -1557,6 +1585,12 @@ static int multi_check(int32_t L, const PdeSmallLayer* layers) {
             return PDE_E_BADARG;
         if (L > 1 && y.mode != 1) return PDE_E_BADARG;     // shared-input groups exist for the mixing-first layers only
         if (!y.alpha_base || !y.beta_base || !y.alpha_slope || !y.beta_slope || !y.steps_workspace) return PDE_E_BADARG;
+        // every device pointer of the layer, the backward's too (NULL in a forward call), before the first launch of the call
+        if (misaligned(kVecAlign, y.M, y.alpha_base, y.beta_base, y.alpha_slope, y.beta_slope, y.states, y.gys, y.g_plane_sums,
+                       y.g_alpha_base, y.g_beta_base, y.g_alpha_slope, y.g_beta_slope, y.gM) ||
+            misaligned(4, y.skip_weight, y.weight_ptr, y.plane_sums, y.kappa_max, y.kappa_max_host, y.g_skip_weight, y.g_weight))
+            return PDE_E_BADARG;
+        if (misaligned(kVecAlign, y.steps_workspace, y.workspace)) return PDE_E_WORKSPACE;
     }
     return PDE_OK;
 }
@@ -1578,7 +1612,7 @@ static int small_forward_impl(int32_t num_layers, const PdeSmallLayer* layers, c
                               void* stream, void* traj, const uint64_t* em) {
     int rc = multi_check(num_layers, layers);
     if (rc != PDE_OK) return rc;
-    if (!u || !out) return PDE_E_BADARG;
+    if (!u || !out || misaligned(kVecAlign, u, out, traj)) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const PdeAdiDesc* d0 = layers[0].desc;
     SmallArgs sa{};
@@ -1625,7 +1659,7 @@ static int small_backward_impl(int32_t num_layers, const PdeSmallLayer* layers, 
                                void* stream, const void* gtraj, const uint64_t* em) {
     int rc = multi_check(num_layers, layers);
     if (rc != PDE_OK) return rc;
-    if (!u || !gu) return PDE_E_BADARG;
+    if (!u || !gu || misaligned(kVecAlign, gy, u, gu, gtraj)) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const PdeAdiDesc* d0 = layers[0].desc;
     const int sps = layers[0].sweeps_per_step, G = small_grid(d0), split = small_split(d0, sps);
@@ -1762,6 +1796,7 @@ int pde_adi_kappa_max(const PdeAdiDesc* d, const float* alpha_base, const float*
     int rc = check_desc(d, true);
     if (rc != PDE_OK) return rc;
     if (!alpha_base || !beta_base || !alpha_slope || !beta_slope || !kappa_max) return PDE_E_BADARG;
+    if (misaligned(param_align(d), alpha_base, beta_base, alpha_slope, beta_slope) || misaligned(4, kappa_max)) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!fused_n(d->N)) return gen_kappa_max(d, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, st);
     if (hipMemsetAsync(kappa_max, 0, (size_t)d->num_sweeps * sizeof(float), st) != hipSuccess) return PDE_E_LAUNCH;

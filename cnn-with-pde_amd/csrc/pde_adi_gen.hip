@@ -846,7 +846,7 @@ template <typename T, typename D>
 int rect_kappa_max(const D* d, const T* ab, const T* bb, const T* as, const T* bs, T* kmax, void* stream) {
     const int rc = check_desc_rect<T>(d);
     if (rc != PDE_OK) return rc;
-    if (!ab || !bb || !as || !bs || !kmax) return PDE_E_BADARG;
+    if (!ab || !bb || !as || !bs || !kmax || misaligned(sizeof(T), ab, bb, as, bs, kmax)) return PDE_E_BADARG;
     return launch_gen_factor<T>(d, ab, bb, as, bs, (T*)nullptr, (GenSweep<T>*)nullptr, kmax, static_cast<hipStream_t>(stream));
 }
 
@@ -858,6 +858,9 @@ int rect_forward(const D* d, const void* u, void* y, const T* ab, const T* bb, c
     int rc = check_desc_rect<T>(d);
     if (rc != PDE_OK) return rc;
     if (!u || !y || !ab || !bb || !as || !bs || !workspace) return PDE_E_BADARG;
+    // one element at a time in every kernel of this path (pdecnn.h, "Alignment"): the element's own alignment is all it asks
+    if (misaligned(io_elem_bytes(d->io_dtype), u, y, states) || misaligned(sizeof(T), ab, bb, as, bs, kmax, kmax_host))
+        return PDE_E_BADARG;
     const uint64_t* emit;
     if ((rc = emit_plan(d->num_sweeps, emit_mask, states, emit)) != PDE_OK) return rc;
     if (kmax_host && !kmax) return PDE_E_BADARG;
@@ -880,6 +883,9 @@ int rect_backward(const D* d, const void* gy, const void* y, const void* u, cons
     int rc = check_desc_rect<T>(d);
     if (rc != PDE_OK) return rc;
     if (!gy || !y || !gu || !ab || !bb || !as || !bs || !g_ab || !g_bb || !g_as || !g_bs || !workspace) return PDE_E_BADARG;
+    if (misaligned(io_elem_bytes(d->io_dtype), gy, gstates, y, u, gu) || misaligned(sizeof(T), ab, bb, as, bs, g_ab, g_bb, g_as, g_bs))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, fwd_workspace)) return PDE_E_WORKSPACE;
     const uint64_t* emit;
     if ((rc = emit_plan(d->num_sweeps, emit_mask, gstates, emit)) != PDE_OK) return rc;
     int nck, Sf;
@@ -898,6 +904,8 @@ int any_backward_input(const D* d, CHECK&& check, const void* gy, const void* gs
     int rc = check(d);
     if (rc != PDE_OK) return rc;
     if (!gy || !gu || !ab || !bb || !as || !bs || !workspace) return PDE_E_BADARG;
+    if (misaligned(io_elem_bytes(d->io_dtype), gy, gstates, gu) || misaligned(sizeof(T), ab, bb, as, bs)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, fwd_workspace)) return PDE_E_WORKSPACE;
     const uint64_t* emit;
     if ((rc = emit_plan(d->num_sweeps, emit_mask, gstates, emit)) != PDE_OK) return rc;
     if (workspace_bytes < fwd_ws_bytes<T>(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
@@ -973,6 +981,7 @@ int pde_adi_f64_forward_states(const PdeAdiDescF64* d, const double* u, double* 
     int rc = check_desc_f64(d);
     if (rc != PDE_OK) return rc;
     if (!u || !y || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    if (misaligned(8, u, y, states, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max)) return PDE_E_BADARG;
     const uint64_t* emit;
     if ((rc = emit_plan(d->num_sweeps, emit_mask, states, emit)) != PDE_OK) return rc;
     if (workspace_bytes < pde_adi_f64_forward_workspace_bytes(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
@@ -1000,6 +1009,10 @@ int pde_adi_f64_backward_states(const PdeAdiDescF64* d, const double* gy, const 
     if (!gy || !y || !gu || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !g_alpha_base || !g_beta_base ||
         !g_alpha_slope || !g_beta_slope || !workspace)
         return PDE_E_BADARG;
+    if (misaligned(8, gy, gstates, y, u, gu, alpha_base, beta_base, alpha_slope, beta_slope, g_alpha_base, g_beta_base, g_alpha_slope,
+                   g_beta_slope))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, fwd_workspace)) return PDE_E_WORKSPACE;
     const uint64_t* emit;
     if ((rc = emit_plan(d->num_sweeps, emit_mask, gstates, emit)) != PDE_OK) return rc;
     int nck, Sf;

@@ -145,6 +145,7 @@ extern "C" {
 int pde_skip_blend_forward(int64_t n, int32_t io_dtype, const void* u0, const void* u, const float* skip_weight, void* out,
                            void* stream) {
     if (n <= 0 || !u0 || !u || !skip_weight || !out) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, u0, u, out) || misaligned(4, skip_weight)) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int grid = blend_grid((size_t)n);
     if (io_dtype == PDE_IO_F32)
@@ -163,10 +164,11 @@ size_t pde_skip_blend_backward_workspace_bytes(int64_t n) { return n > 0 ? (size
 int pde_skip_blend_backward(int64_t n, int32_t io_dtype, const void* g, const void* u0, const void* u, const float* skip_weight,
                             void* g_u0, void* g_u, float* g_skip_weight, void* workspace, size_t workspace_bytes, void* stream) {
     if (n <= 0 || !g || !u0 || !u || !skip_weight || !g_u0 || !g_u || !g_skip_weight || !workspace) return PDE_E_BADARG;
-    if (workspace_bytes < pde_skip_blend_backward_workspace_bytes(n)) return PDE_E_WORKSPACE;
+    if (misaligned(kVecAlign, g, u0, u, g_u0, g_u) || misaligned(4, skip_weight, g_skip_weight)) return PDE_E_BADARG;
+    // the partial sums are doubles read one at a time: 8 bytes would do, the header asks 16 of every workspace
+    if (workspace_bytes < pde_skip_blend_backward_workspace_bytes(n) || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int grid = blend_grid((size_t)n);
-    if ((uintptr_t)workspace & 7) return PDE_E_WORKSPACE;
     double* part = static_cast<double*>(workspace);
     if (io_dtype == PDE_IO_F32)
         hipLaunchKernelGGL(blend_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)g, (const float*)u0, (const float*)u, skip_weight, (float*)g_u0, (float*)g_u, part, (size_t)n);

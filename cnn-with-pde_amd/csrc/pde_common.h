@@ -113,6 +113,18 @@ inline int emit_check(const uint64_t* mask, int nt, const void* tensor, EmitMask
     return (bad || !tensor) ? PDE_E_BADARG : PDE_OK;
 }
 
+// ---- where a buffer may begin (pdecnn.h, "Alignment") ------------------------------------------------------------------
+// Checked on the host with the NULL and shape checks, before anything touches the runtime: the OR of the addresses has a
+// low bit set as soon as one of them has (NULL has none, so optional pointers go in as they are).  `align`: a power of two.
+inline uintptr_t addr_bits() { return 0; }
+template <typename... R>
+inline uintptr_t addr_bits(const void* p, R... rest) { return reinterpret_cast<uintptr_t>(p) | addr_bits(rest...); }
+template <typename... P>
+inline bool misaligned(unsigned align, P... ptrs) { return (addr_bits(ptrs...) & (uintptr_t)(align - 1)) != 0; }
+constexpr unsigned kVecAlign = 16;                      // tensors the kernels read and write 16 bytes wide, and every workspace
+// bytes of one element of a PDE_IO_* tensor: all that the element-wise kernels (any-size sweeps, Jacobi, odd-width explicit) ask
+inline unsigned io_elem_bytes(int io_dtype) { return io_dtype == PDE_IO_F32 ? 4u : (io_dtype == PDE_IO_F64 ? 8u : 2u); }
+
 struct Timing {
     bool on = false;
     double fwd_ms = 0, bwd_ms = 0;

@@ -810,6 +810,11 @@ void ex_bwd_step(const ExArgs& a, bool ufirst, bool gfirst, const void* up, cons
     else ex_bwd<float, float, float>(a, up, gin, gdst, part, acc, NoEmit{}, st);
 }
 
+// Where the call's own tensors may begin (pdecnn.h, "Alignment"): planes whose rows are whole groups of four columns move
+// four elements wide (float4, or four 16-bit values in 8 bytes), every other plane one element at a time.  alpha_base and
+// channel_scaling (C values each) are read one at a time whatever the plane.
+unsigned ex_tensor_align(int W, int io_dtype) { return (W % 4 ? 1u : 4u) * io_elem_bytes(io_dtype); }
+
 }  // namespace
 }  // namespace pde
 
@@ -831,6 +836,9 @@ int pde_explicit5_forward_states(int32_t B, int32_t C, int32_t H, int32_t W, int
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !alpha_base || !channel_scaling || !out)
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    if (misaligned(ex_tensor_align(W, io_dtype), u, out, traj) || misaligned(ex_tensor_align(W, PDE_IO_F32), states) ||
+        misaligned(4, alpha_base, channel_scaling))
+        return PDE_E_BADARG;
     EmitMask em;
     const int erc = emit_check(emit_mask, num_steps, traj, em);
     if (erc != PDE_OK) return erc;
@@ -894,10 +902,16 @@ int pde_explicit5_backward_states(int32_t B, int32_t C, int32_t H, int32_t W, in
         !channel_scaling || !gu || !g_alpha_base || !g_channel_scaling || !workspace || (num_steps > 1 && !states))
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    if (misaligned(ex_tensor_align(W, io_dtype), u, gout, gtraj, gu) || misaligned(ex_tensor_align(W, PDE_IO_F32), states) ||
+        misaligned(4, alpha_base, channel_scaling, g_alpha_base, g_channel_scaling))
+        return PDE_E_BADARG;
     EmitMask em;
     const int erc = emit_check(emit_mask, num_steps, gtraj, em);
     if (erc != PDE_OK) return erc;
-    if (workspace_bytes < pde_explicit5_backward_workspace_bytes(B, C, H, W, io_dtype, num_steps)) return PDE_E_WORKSPACE;
+    // the two gradient buffers behind the partial sums are read and written as float4 on the generic float4 path
+    if (workspace_bytes < pde_explicit5_backward_workspace_bytes(B, C, H, W, io_dtype, num_steps) ||
+        misaligned(kVecAlign, workspace))
+        return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* part = static_cast<float*>(workspace);
     const int nplanes = B * C;
@@ -995,6 +1009,9 @@ int pde_jacobi_io_forward_states(int32_t B, int32_t H, int32_t W, int32_t nt, in
     const int path = jacobi_path(H, W);
     if (B <= 0 || path == 0 || nt < 0 || !u || !a_row || !b_col || !out) return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    // the Jacobi kernels move one element at a time, tensors and workspace alike; the header asks 16 bytes of every workspace
+    if (misaligned(io_elem_bytes(io_dtype), u, out, states) || misaligned(4, a_row, b_col)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
     EmitMask em;
     const int erc = emit_check(emit_mask, nt, states, em);
     if (erc != PDE_OK) return erc;
@@ -1002,7 +1019,7 @@ int pde_jacobi_io_forward_states(int32_t B, int32_t H, int32_t W, int32_t nt, in
     if (path == 2) {
         if (!jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
         const size_t need = pde_jacobi_forward_workspace_bytes(B, H, W, nt);
-        if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 3))) return PDE_E_WORKSPACE;
+        if (need && (!workspace || workspace_bytes < need)) return PDE_E_WORKSPACE;
     }
     if (io_dtype == PDE_IO_F32) return jacobi_forward_io<float>(path, B, H, W, nt, u, a_row, b_col, out, workspace, states, em, st);
     if (io_dtype == PDE_IO_BF16) return jacobi_forward_io<bf16e>(path, B, H, W, nt, u, a_row, b_col, out, workspace, states, em, st);
@@ -1070,15 +1087,13 @@ int pde_jacobi_io_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, i
     if (B <= 0 || path == 0 || nt < 0 || !u || !gout || !a_row || !b_col || !gu || !g_a_row || !g_b_col || !workspace)
         return PDE_E_BADARG;
     if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    if (misaligned(io_elem_bytes(io_dtype), u, gout, gstates, gu) || misaligned(4, a_row, b_col, g_a_row, g_b_col)) return PDE_E_BADARG;
     EmitMask em;
     const int erc = emit_check(emit_mask, nt, gstates, em);
     if (erc != PDE_OK) return erc;
-    if (workspace_bytes < pde_jacobi_backward_workspace_bytes(B, H, W, nt)) return PDE_E_WORKSPACE;
+    if (workspace_bytes < pde_jacobi_backward_workspace_bytes(B, H, W, nt) || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (path == 2) {
-        if (!jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
-        if ((uintptr_t)workspace & 3) return PDE_E_WORKSPACE;
-    }
+    if (path == 2 && !jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
     if (io_dtype == PDE_IO_F32)
         return jacobi_backward_io<float>(path, B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, gstates, em, st);
     if (io_dtype == PDE_IO_BF16)

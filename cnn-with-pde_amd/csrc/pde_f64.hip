@@ -354,7 +354,7 @@ using namespace pde;
 extern "C" {
 
 int pde_channel_mix_f64_forward(int32_t B, int32_t C, int32_t HW, const double* u, const double* M, double* out, void* stream) {
-    if (!mix64_ok(B, C, HW) || !u || !M || !out) return PDE_E_BADARG;
+    if (!mix64_ok(B, C, HW) || !u || !M || !out || misaligned(8, u, M, out)) return PDE_E_BADARG;
     hipLaunchKernelGGL(mix64_apply_kernel, dim3((HW + 255) / 256, C, B), dim3(256), 0, static_cast<hipStream_t>(stream), C, HW,
                        u, M, out, 0);
     return check_launch();
@@ -369,6 +369,7 @@ int pde_channel_mix_f64_backward_steps(int32_t B, int32_t C, int32_t HW, const d
                                        double* gu, double* gM, void* workspace, size_t workspace_bytes, int32_t accumulate,
                                        int32_t finalize, void* stream) {
     if (!mix64_ok(B, C, HW) || !u || !gout || !M || !gu || !workspace || (finalize && !gM)) return PDE_E_BADARG;
+    if (misaligned(8, u, gout, M, gu, gM)) return PDE_E_BADARG;
     if (workspace_bytes < pde_channel_mix_f64_backward_workspace_bytes(B, C, HW) || ((uintptr_t)workspace & 15))
         return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -390,7 +391,7 @@ int pde_channel_mix_f64_backward(int32_t B, int32_t C, int32_t HW, const double*
 
 int pde_skip_blend_f64_forward(int64_t n, const double* u0, const double* u, const double* skip_weight, double* out,
                                void* stream) {
-    if (n <= 0 || !u0 || !u || !skip_weight || !out) return PDE_E_BADARG;
+    if (n <= 0 || !u0 || !u || !skip_weight || !out || misaligned(8, u0, u, skip_weight, out)) return PDE_E_BADARG;
     const long long blocks = (n + 255) / 256;
     hipLaunchKernelGGL(blend64_fwd_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), (long long)n, u0, u, skip_weight, out);
@@ -406,6 +407,7 @@ int pde_skip_blend_f64_backward(int64_t n, const double* g, const double* u0, co
                                 double* g_u0, double* g_u, double* g_skip_weight, void* workspace, size_t workspace_bytes,
                                 void* stream) {
     if (n <= 0 || !g || !u0 || !u || !skip_weight || !g_u0 || !g_u || !g_skip_weight || !workspace) return PDE_E_BADARG;
+    if (misaligned(8, g, u0, u, skip_weight, g_u0, g_u, g_skip_weight)) return PDE_E_BADARG;
     if (workspace_bytes < pde_skip_blend_f64_backward_workspace_bytes(n) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int np = blend64_parts(n);
@@ -430,6 +432,7 @@ int pde_explicit5_f64_forward_states(int32_t B, int32_t C, int32_t H, int32_t W,
         !channel_scaling || !out ||
         (num_steps > 1 && !states))
         return PDE_E_BADARG;
+    if (misaligned(8, u, alpha_base, channel_scaling, states, out, traj)) return PDE_E_BADARG;
     EmitMask em;
     const int erc = emit_check(emit_mask, num_steps, traj, em);
     if (erc != PDE_OK) return erc;
@@ -474,6 +477,7 @@ int pde_explicit5_f64_backward_states(int32_t B, int32_t C, int32_t H, int32_t W
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !gout || !alpha_base || !channel_scaling || !gu ||
         !g_alpha_base || !g_channel_scaling || !workspace || (num_steps > 1 && !states))
         return PDE_E_BADARG;
+    if (misaligned(8, u, states, gout, gtraj, alpha_base, channel_scaling, gu, g_alpha_base, g_channel_scaling)) return PDE_E_BADARG;
     EmitMask em;
     const int erc = emit_check(emit_mask, num_steps, gtraj, em);
     if (erc != PDE_OK) return erc;
@@ -514,6 +518,7 @@ int pde_jacobi_f64_forward_states(int32_t B, int32_t H, int32_t W, int32_t nt, c
                                   const double* b_col, double* out, double* states, const uint64_t emit_mask[2],
                                   void* stream) {
     if (!jac64_ok(B, H, W, nt) || !u || !a_row || !b_col || !out) return PDE_E_BADARG;
+    if (misaligned(8, u, a_row, b_col, out, states)) return PDE_E_BADARG;
     EmitMask em;
     int rc = emit_check(emit_mask, nt, states, em);
     if (rc != PDE_OK) return rc;
@@ -551,6 +556,7 @@ int pde_jacobi_f64_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, 
                                    size_t workspace_bytes, void* stream) {
     if (!jac64_ok(B, H, W, nt) || !u || !gout || !a_row || !b_col || !gu || !g_a_row || !g_b_col || !workspace)
         return PDE_E_BADARG;
+    if (misaligned(8, u, gout, gstates, a_row, b_col, gu, g_a_row, g_b_col)) return PDE_E_BADARG;
     EmitMask em;
     int rc = emit_check(emit_mask, nt, gstates, em);
     if (rc != PDE_OK) return rc;

@@ -125,10 +125,10 @@ int pde_gate_combine_forward(int32_t L, int32_t B, int32_t C, int32_t HW, int32_
                              const float* const* gates, const float* weights, void* out, void* stream) {
     int rc = gate_check(L, B, C, HW, io_dtype);
     if (rc != PDE_OK) return rc;
-    if (!ys || !gates || !weights || !out) return PDE_E_BADARG;
+    if (!ys || !gates || !weights || !out || misaligned(kVecAlign, out) || misaligned(4, weights)) return PDE_E_BADARG;
     GateArgs a{};
     for (int i = 0; i < L; ++i) {
-        if (!ys[i] || !gates[i]) return PDE_E_BADARG;
+        if (!ys[i] || !gates[i] || misaligned(kVecAlign, ys[i]) || misaligned(4, gates[i])) return PDE_E_BADARG;
         a.y[i] = ys[i]; a.gate[i] = gates[i];
     }
     a.w = weights; a.out = out; a.L = L; a.planes = B * C; a.HW = HW;
@@ -145,10 +145,11 @@ int pde_gate_combine_backward(int32_t L, int32_t B, int32_t C, int32_t HW, int32
                               float* const* dots, void* stream) {
     int rc = gate_check(L, B, C, HW, io_dtype);
     if (rc != PDE_OK) return rc;
-    if (!g || !ys || !gates || !weights || !gys || !dots) return PDE_E_BADARG;
+    if (!g || !ys || !gates || !weights || !gys || !dots || misaligned(kVecAlign, g) || misaligned(4, weights)) return PDE_E_BADARG;
     GateArgs a{};
     for (int i = 0; i < L; ++i) {
         if (!ys[i] || !gates[i] || !gys[i] || !dots[i]) return PDE_E_BADARG;
+        if (misaligned(kVecAlign, ys[i], gys[i]) || misaligned(4, gates[i], dots[i])) return PDE_E_BADARG;
         a.y[i] = ys[i]; a.gate[i] = gates[i]; a.gy[i] = gys[i]; a.dot[i] = dots[i];
     }
     a.w = weights; a.g = g; a.L = L; a.planes = B * C; a.HW = HW;

@@ -550,7 +550,7 @@ extern "C" {
 
 int pde_channel_mix_forward(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, const void* u, const float* M,
                             void* out, void* stream) {
-    if (B <= 0 || C <= 0 || HW <= 0 || !u || !M || !out) return PDE_E_BADARG;
+    if (B <= 0 || C <= 0 || HW <= 0 || !u || !M || !out || misaligned(kVecAlign, u, M, out)) return PDE_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const MixPlan plan = mix_plan(B, C, HW, io_dtype, false);
     if (plan.path < 0) return plan.path;
@@ -602,7 +602,10 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
                                    const float* M, void* gu, float* gM, void* workspace, size_t workspace_bytes,
                                    int32_t accumulate, int32_t finalize, void* stream) {
     if (B <= 0 || C <= 0 || HW <= 0 || !u || !gout || !M || !gu || !workspace || (finalize && !gM)) return PDE_E_BADARG;
-    if (workspace_bytes < pde_channel_mix_backward_workspace_bytes(B, C, HW)) return PDE_E_WORKSPACE;
+    if (misaligned(kVecAlign, u, gout, M, gu, gM)) return PDE_E_BADARG;
+    // partial matrices and the fragment table are floats read one at a time: 4 bytes would do, the header asks 16 of every workspace
+    if (workspace_bytes < pde_channel_mix_backward_workspace_bytes(B, C, HW) || misaligned(kVecAlign, workspace))
+        return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const MixPlan plan = mix_plan(B, C, HW, io_dtype, true);
     if (plan.path < 0) return plan.path;

@@ -1356,7 +1356,7 @@ int launch_part16(const void* A, const unsigned short* W, int B, int D, float as
 // host side of the 16-bit layer, once over E: argument checks, then the launches in a fixed order
 template <class E>
 int sym16_k_to(int32_t D, const float* K, uint16_t* K16, void* stream) {
-    if (D < 64 || (D % 64) != 0 || !K || !K16) return PDE_E_BADARG;
+    if (D < 64 || (D % 64) != 0 || !K || !K16 || misaligned(kVecAlign, K, K16)) return PDE_E_BADARG;
     const size_t n4 = (size_t)D * D / 4;
     const int blocks = (int)(n4 / 256 < 2048 ? (n4 + 255) / 256 : 2048);
     hipLaunchKernelGGL(rh_k_to_f16_kernel<E>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), K, K16, n4);
@@ -1372,6 +1372,9 @@ int sym16_forward(int32_t B, int32_t D, int32_t act, int32_t training, const flo
     if (!X || !K16 || !bn_weight || !bn_bias || !P || !H || !mean || !invstd || !out) return PDE_E_BADARG;
     if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
     if (!training && (!running_mean || !running_var)) return PDE_E_BADARG;
+    // the (B, D) and (D, D) matrices go 16 bytes wide; what is per feature (D values) one element at a time
+    if (misaligned(kVecAlign, X, K16, base, P, H, out) || misaligned(4, bn_weight, bn_bias, running_mean, running_var, mean, invstd))
+        return PDE_E_BADARG;
     if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
         return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1399,6 +1402,8 @@ int sym16_backward(int32_t B, int32_t D, int32_t act, int32_t training, const fl
     if (!g_out || !X || !K16 || !bn_weight || !P || !H || !mean || !invstd || !dP || !gX || !gK || !g_bn_weight || !g_bn_bias)
         return PDE_E_BADARG;
     if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, g_out, X, K16, P, H, dP, gX, gK) || misaligned(4, bn_weight, mean, invstd, g_bn_weight, g_bn_bias))
+        return PDE_E_BADARG;
     if (!workspace || workspace_bytes < rh_split16_bytes(B, D) || (reinterpret_cast<uintptr_t>(workspace) & 15))
         return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1457,6 +1462,9 @@ int pde_sym_layer_forward(int32_t B, int32_t D, int32_t act, int32_t training, c
     if (!X || !K || !bn_weight || !bn_bias || !P || !H || !mean || !invstd || !out) return PDE_E_BADARG;
     if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
     if (!training && (!running_mean || !running_var)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, X, K, base, P, H, out) || misaligned(4, bn_weight, bn_bias, running_mean, running_var, mean, invstd))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;         // whichever family runs: a workspace that is given
     hipStream_t st = static_cast<hipStream_t>(stream);
     RhFwdArgs f{X, K, bn_weight, bn_bias, running_mean, running_var, P, H, mean, invstd, B, D, act, training ? 1 : 0, momentum, eps};
     int rc;
@@ -1496,6 +1504,9 @@ int pde_sym_layer_backward(int32_t B, int32_t D, int32_t act, int32_t training, 
     if (!g_out || !X || !K || !bn_weight || !P || !H || !mean || !invstd || !dP || !gX || !gK || !g_bn_weight || !g_bn_bias)
         return PDE_E_BADARG;
     if (act < kActIdentity || act > kActTanh) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, g_out, X, K, P, H, dP, gX, gK) || misaligned(4, bn_weight, mean, invstd, g_bn_weight, g_bn_bias))
+        return PDE_E_BADARG;
+    if (misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     RhBwdArgs b{g_out, K, bn_weight, P, H, mean, invstd, dP, g_bn_weight, g_bn_bias, B, D, act, training ? 1 : 0, scale};
     int rc;

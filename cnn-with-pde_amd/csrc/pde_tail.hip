@@ -244,7 +244,9 @@ int pde_bn_pool_forward(int32_t B, int32_t C, int32_t N, const float* x, const f
     if (rc != PDE_OK) return rc;
     if (!x || !mean || !invstd || !out || !argmax || !workspace) return PDE_E_BADARG;
     if (!training && (!running_mean || !running_var)) return PDE_E_BADARG;
-    if (workspace_bytes < pde_bn_pool_workspace_bytes(B, C)) return PDE_E_WORKSPACE;
+    // whole planes of x go 16 bytes wide; what is per channel or per pooled cell (out, argmax, gout) one element at a time
+    if (misaligned(kVecAlign, x) || misaligned(4, gamma, beta, running_mean, running_var, mean, invstd, out, argmax)) return PDE_E_BADARG;
+    if (workspace_bytes < pde_bn_pool_workspace_bytes(B, C) || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
     TailArgs a{};
     a.x = x; a.gamma = gamma; a.beta = beta; a.mean = mean; a.invstd = invstd; a.run_mean = running_mean; a.run_var = running_var;
     a.part = static_cast<float*>(workspace); a.out = out; a.argmax = argmax;
@@ -267,7 +269,8 @@ int pde_bn_pool_backward(int32_t B, int32_t C, int32_t N, const float* x, const 
     int rc = tail_check(B, C, N);
     if (rc != PDE_OK) return rc;
     if (!x || !mean || !invstd || !argmax || !gout || !gx || !ggamma || !gbeta || !workspace) return PDE_E_BADARG;
-    if (workspace_bytes < pde_bn_pool_workspace_bytes(B, C)) return PDE_E_WORKSPACE;
+    if (misaligned(kVecAlign, x, gx) || misaligned(4, gamma, mean, invstd, argmax, gout, ggamma, gbeta)) return PDE_E_BADARG;
+    if (workspace_bytes < pde_bn_pool_workspace_bytes(B, C) || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
     TailArgs a{};
     a.x = x; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.invstd = const_cast<float*>(invstd);
     a.argmax = const_cast<int*>(argmax); a.gout = gout; a.gx = gx; a.ggamma = ggamma; a.gbeta = gbeta;

@@ -89,6 +89,25 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+#: bytes the library asks of where a tensor, a coefficient plane or a matrix begins (include/pdecnn.h, "Alignment")
+ALIGN = 16
+
+
+def _aligned(t: Optional[torch.Tensor], align: int = ALIGN) -> Optional[torch.Tensor]:
+    """``t`` as the library may be handed it: the SAME object when its storage begins on ``align`` bytes (no copy, no launch:
+    every fresh allocation does), otherwise a contiguous copy in an allocation of its own.  ``align`` is what the header asks
+    of the parameter in THIS call: 16 by default, 1 (never a copy: a tensor begins on its element's boundary) for a call
+    served by element-wise kernels; the header's ELEMENT-ALIGNED parameters (skip_weight, weights, gates, gamma / beta,
+    a_row / b_col, channel_scaling ...) do not come through here at all.  ``.contiguous()`` leaves a
+    contiguous view where it is — a batch slice ``u[1:]``, a parameter cut from one flat buffer, a tensor that arrived
+    through DLPack — and such a view begins wherever its storage offset puts it.  For read-only arguments; running
+    statistics, which the kernels update in place one element at a time, need their element's alignment only and are
+    passed as they are."""
+    if t is None or align <= 1 or t.data_ptr() % align == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def _require_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -213,18 +232,18 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
 
 # What the one node of a layer family (_AdiFn, _Explicit5Fn, _JacobiFn) needs to serve the plain call and the trajectory
 # call alike.  ``sel`` None is the plain call; otherwise it lists what the call emits, the last sweep / step included.
-def _kernel_input(u: torch.Tensor, f64: bool, io_types=_IO_TYPES) -> torch.Tensor:
+def _kernel_input(u: torch.Tensor, f64: bool, io_types=_IO_TYPES, align: int = ALIGN) -> torch.Tensor:
     """``u`` as a family's kernels take it, contiguous: double on the float64 route, otherwise as it is when ``io_types``
     holds its type and widened to fp32 when not."""
     if f64:
-        return u.to(torch.float64).contiguous()
-    return (u if u.dtype in io_types else u.float()).contiguous()
+        return u.to(torch.float64).contiguous()                 # every float64 entry point is element-wise: no requirement
+    return _aligned((u if u.dtype in io_types else u.float()).contiguous(), align)
 
 
 def _kernel_param(p: torch.Tensor, dtype) -> torch.Tensor:
     """A parameter cut from the graph, contiguous and in the kernels' type (no torch call for a type it has already)."""
     p = p.detach()
-    return (p if p.dtype == dtype else p.to(dtype)).contiguous()
+    return (p if p.dtype == dtype else p.to(dtype)).contiguous()     # per-channel / per-line vectors: ELEMENT-ALIGNED
 
 
 def _out_and_traj(u, sel):
@@ -245,27 +264,27 @@ def _grad_as(g, dtype, shape=None):
     return g if g.dtype == dtype else g.to(dtype)
 
 
-def _cotangents(g, like, sel):
+def _cotangents(g, like, sel, align: int = ALIGN):
     """(gradient of the library's output, gradient of the trajectory tensor or None) from the node's cotangent."""
-    g = _grad_as(g, like.dtype).contiguous()
+    g = _aligned(_grad_as(g, like.dtype).contiguous(), align)
     return (g, None) if sel is None else (g[-1], g)       # slots 0..K'-2 are the states' gradients, the last slice is gy
 
 
-def _as_chw(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.Tensor:
+def _as_chw(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None, align: int = ALIGN) -> torch.Tensor:
     """The parameter as a contiguous fp32 (C, N, N) tensor — (C, N, W) on a rectangle."""
     W = N if W is None else W
     if p.dtype == torch.float32 and p.dim() == 3 and p.shape[0] == Cc and p.shape[1] == N and p.shape[2] == W \
             and p.is_contiguous():
-        return p.detach()
+        return _aligned(p.detach(), align)
     q = p.detach()
     if q.dim() == 2:
         q = q.unsqueeze(0)
     if tuple(q.shape) != (Cc, N, W):
         raise L.PdeError(f"coefficient of shape {tuple(p.shape)} does not match ({Cc},{N},{W})")
-    return q.to(torch.float32).contiguous()
+    return _aligned(q.to(torch.float32).contiguous(), align)
 
 
-def _as_chw64(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None) -> torch.Tensor:
+def _as_chw64(p: torch.Tensor, Cc: int, N: int, W: Optional[int] = None, align: int = 1) -> torch.Tensor:
     W = N if W is None else W
     q = p.detach()
     if q.dim() == 2:
@@ -497,10 +516,13 @@ class _AdiFn(torch.autograd.Function):
                 raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
         B, Cc, H, W = u.shape
         fam, desc_cls, as_chw = _ADI_FAMILY[rect, f64]
-        u = _kernel_input(u, f64)
+        # the fused kernels move tensors and coefficient planes 16 bytes wide; rectangles, float64 and the any-size path
+        # one element at a time (include/pdecnn.h, "Alignment"): nothing to copy there
+        ctx.align = al = ALIGN if not (rect or f64) and H % 4 == 0 and 8 <= H <= 32 else 1
+        u = _kernel_input(u, f64, align=al)
         if f64:
             ckpt = _f64_ckpt_bits(ckpt, len(sweeps))
-        p = [as_chw(t, Cc, H, W) for t in (ab, bb, asl, bsl)]
+        p = [as_chw(t, Cc, H, W, al) for t in (ab, bb, asl, bsl)]
         d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(u), sweeps, smooth3, clamp_max, eps)
         out, y, traj = _out_and_traj(u, emit)
         ebits = None if emit is None else sum(1 << s for s in emit[:-1])
@@ -549,7 +571,7 @@ class _AdiFn(torch.autograd.Function):
         B, Cc, H, W = out.shape[-4:]
         fam, desc_cls, _ = _ADI_FAMILY[rect, f64]
         y = out if ebits is None else out[-1]
-        gy, gtraj = _cotangents(g, out, ebits)
+        gy, gtraj = _cotangents(g, out, ebits, ctx.align)
         d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(out), sweeps, smooth3, clamp_max, eps)
         gu = torch.empty_like(y)
         gp = [torch.empty_like(t) for t in p]
@@ -575,7 +597,7 @@ class _AdiFn(torch.autograd.Function):
         shape, dtype, device = ctx.input_only
         B, Cc, H, W = shape[-4:]
         fam, desc_cls, _ = _ADI_FAMILY[rect, f64]
-        g = _grad_as(g, dtype).contiguous()
+        g = _aligned(_grad_as(g, dtype).contiguous(), ctx.align)
         gy, gtraj = (g, None) if ebits is None else (g[-1], g)
         d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(g), sweeps, smooth3, clamp_max, eps)
         gu = torch.empty((B, Cc, H, W), dtype=dtype, device=device)
@@ -608,11 +630,11 @@ class _AdiMixedFn(torch.autograd.Function):
         B, Cc, N, _ = u.shape
         if u.dtype not in _IO_TYPES:
             u = u.float()
-        u = u.contiguous()
+        u = _aligned(u.contiguous())
         sps, K = len(steps[0]), len(steps)
         sweeps = tuple(s for st in steps for s in st)
         p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        Mf = M.detach().to(torch.float32).contiguous()
+        Mf = _aligned(M.detach().to(torch.float32).contiguous())
         d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
         sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
         need_grad = any(ctx.needs_input_grad[:6])
@@ -659,7 +681,7 @@ class _AdiMixedFn(torch.autograd.Function):
         nck = bin(bits).count("1")
         mask = _mask128(bits)
         ws = _workspace(lib.pde_adi_mixed_backward_workspace_bytes(C.byref(d), sps, nck), u.device)
-        g_in = gy.to(u.dtype).contiguous()
+        g_in = _aligned(gy.to(u.dtype).contiguous())
         g_a = torch.empty_like(g_in)
         gp = [torch.empty_like(t) for t in p]
         gM = torch.empty_like(Mf)
@@ -684,11 +706,11 @@ class _AdiSmallFn(torch.autograd.Function):
         B, Cc, N, _ = u.shape
         if u.dtype not in _IO_TYPES:
             u = u.float()
-        u = u.contiguous()
+        u = _aligned(u.contiguous())
         sps, K = len(steps[0]), len(steps)
         sweeps = steps.flat
         p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        Mf = M.detach().to(torch.float32).contiguous()
+        Mf = _aligned(M.detach().to(torch.float32).contiguous())
         sw = None if skip_weight is None else skip_weight.detach().to(torch.float32).reshape(1).contiguous()
         d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
         sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
@@ -733,7 +755,7 @@ class _AdiSmallFn(torch.autograd.Function):
             bits = int(ckpt)
         mask = _mask128(bits)
         ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
-        g_in = gy.to(u.dtype).contiguous()
+        g_in = _aligned(gy.to(u.dtype).contiguous())
         gu = torch.empty_like(g_in)
         gp = [torch.empty_like(t) for t in p]
         gM = torch.empty_like(Mf)
@@ -761,7 +783,7 @@ class _AdiMultiFn(torch.autograd.Function):
         B, Cc, N, _ = u.shape
         if u.dtype not in _IO_TYPES:
             u = u.float()
-        u = u.contiguous()
+        u = _aligned(u.contiguous())
         need_grad = any(ctx.needs_input_grad)
         want_kmax = need_grad and ckpt == "auto"
         if ckpt != "auto" and not isinstance(ckpt, (tuple, list)):
@@ -778,7 +800,7 @@ class _AdiMultiFn(torch.autograd.Function):
             sps, K = len(steps[0]), len(steps)
             sweeps = steps.flat
             p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-            Mf = M.detach().to(torch.float32).contiguous()
+            Mf = _aligned(M.detach().to(torch.float32).contiguous())
             d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
             sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
             states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
@@ -834,7 +856,7 @@ class _AdiMultiFn(torch.autograd.Function):
         if ctx.ckpt == "auto":
             _wait_event(ctx.keep[-1][3].event)
         outs, hold = [], []
-        gout_c = None if gout is None else gout.to(u.dtype).contiguous()
+        gout_c = None if gout is None else _aligned(gout.to(u.dtype).contiguous())
         for i in range(nl):
             sws, states, kdev, tk = ctx.keep[i]
             p, Mf = pm[5 * i:5 * i + 4], pm[5 * i + 4]
@@ -852,8 +874,8 @@ class _AdiMultiFn(torch.autograd.Function):
             gp = [torch.empty_like(t) for t in p]
             gM = torch.empty_like(Mf)
             gw = torch.empty(1, dtype=torch.float32, device=u.device)
-            gyi = None if gys[i] is None else gys[i].to(u.dtype).contiguous()
-            gsi = None if gsums[i] is None else gsums[i].to(torch.float32).contiguous()
+            gyi = None if gys[i] is None else _aligned(gys[i].to(u.dtype).contiguous())
+            gsi = None if gsums[i] is None else _aligned(gsums[i].to(torch.float32).contiguous())
             a = arr[i]
             a.desc, a.sweeps_per_step, a.mode = C.pointer(d), sps, 1
             a.M = Mf.data_ptr()
@@ -1156,11 +1178,11 @@ class _AdiSmallStatesFn(torch.autograd.Function):
         B, Cc, N, _ = u.shape
         if u.dtype not in _IO_TYPES:
             u = u.float()
-        u = u.contiguous()
+        u = _aligned(u.contiguous())
         sps, K = len(steps[0]), len(steps)
         sweeps = steps.flat
         p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        Mf = M.detach().to(torch.float32).contiguous()
+        Mf = _aligned(M.detach().to(torch.float32).contiguous())
         d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
         sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
         need_grad = any(ctx.needs_input_grad[:6])
@@ -1211,7 +1233,7 @@ class _AdiSmallStatesFn(torch.autograd.Function):
         mask = _mask128(bits)
         em = _mask128(ebits)
         ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
-        g = g.to(u.dtype).contiguous()                   # slots 0..K'-2 are the states' gradients, the last slice is gy
+        g = _aligned(g.to(u.dtype).contiguous())                   # slots 0..K'-2 are the states' gradients, the last slice is gy
         gu = torch.empty_like(u)
         gp = [torch.empty_like(t) for t in p]
         gM = torch.empty_like(Mf)
@@ -1265,8 +1287,8 @@ class _MixFn(torch.autograd.Function):
         HW = u[0, 0].numel()
         if u.dtype not in _IO_TYPES:
             u = u.float()
-        u = u.contiguous()
-        Mf = M.detach().to(torch.float32).contiguous()
+        u = _aligned(u.contiguous())
+        Mf = _aligned(M.detach().to(torch.float32).contiguous())
         out = torch.empty_like(u)
         with torch.cuda.device(u.device):
             L.check(lib.pde_channel_mix_forward(B, Cc, HW, _io_dtype(u), _ptr(u), _ptr(Mf), _ptr(out), _stream()),
@@ -1280,7 +1302,7 @@ class _MixFn(torch.autograd.Function):
         u, Mf = ctx.saved_tensors
         B, Cc = u.shape[0], u.shape[1]
         HW = u[0, 0].numel()
-        gout = gout.to(u.dtype).contiguous()
+        gout = _aligned(gout.to(u.dtype).contiguous())
         gu = torch.empty_like(u)
         gM = torch.empty_like(Mf)
         ws = _workspace(lib.pde_channel_mix_backward_workspace_bytes(B, Cc, HW), u.device)
@@ -1309,7 +1331,7 @@ class _BnPoolFn(torch.autograd.Function):
         lib = L.load()
         _require_cuda(x, gamma, beta)
         B, Cc, N, _ = x.shape
-        xf = x.contiguous()
+        xf = _aligned(x.contiguous())
         gm = None if gamma is None else gamma.detach().to(torch.float32).contiguous()
         bt = None if beta is None else beta.detach().to(torch.float32).contiguous()
         mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
@@ -1331,7 +1353,7 @@ class _BnPoolFn(torch.autograd.Function):
         lib = L.load()
         xf, gm, mean, invstd, amax = ctx.saved_tensors
         B, Cc, N, _ = xf.shape
-        g = gout.to(torch.float32).contiguous()
+        g = _aligned(gout.to(torch.float32).contiguous())
         gx = torch.empty_like(xf)
         gg = torch.empty(Cc, dtype=torch.float32, device=xf.device)
         gb = torch.empty_like(gg)
@@ -1395,11 +1417,11 @@ class _SymLayerFn(torch.autograd.Function):
         lib = L.load()
         _require_cuda(X, K, gamma, beta, base)
         B, D = X.shape
-        Xf = X.to(torch.float32).contiguous()
-        Kf = K.detach().to(torch.float32).contiguous()
+        Xf = _aligned(X.to(torch.float32).contiguous())
+        Kf = _aligned(K.detach().to(torch.float32).contiguous())
         gm = gamma.detach().to(torch.float32).contiguous()
         bt = beta.detach().to(torch.float32).contiguous()
-        bs = None if base is None else base.to(torch.float32).contiguous()
+        bs = None if base is None else _aligned(base.to(torch.float32).contiguous())
         dev = X.device
         P = torch.empty((B, D), dtype=torch.float32, device=dev)
         H = torch.empty_like(P)
@@ -1423,7 +1445,7 @@ class _SymLayerFn(torch.autograd.Function):
         Xf, Kf, gm, P, H, mean, invstd = ctx.saved_tensors
         training, scale, act, has_base = ctx.cfg
         B, D = Xf.shape
-        g = gout.to(torch.float32).contiguous()
+        g = _aligned(gout.to(torch.float32).contiguous())
         dev = Xf.device
         dP = torch.empty_like(Xf)
         gX = torch.empty_like(Xf)
@@ -1472,7 +1494,7 @@ def sym_k16(K, dtype=torch.float16):
     if H_ is not None and K.is_cuda:
         return H_.sym_kbf16(K) if bf else H_.sym_k16(K)
     _require_cuda(K)
-    Kf = K.detach().to(torch.float32).contiguous()
+    Kf = _aligned(K.detach().to(torch.float32).contiguous())
     K16 = torch.empty(K.shape, dtype=dtype, device=K.device)
     with torch.cuda.device(K.device):
         if bf:
@@ -1520,10 +1542,11 @@ def _sym16_forward(ctx, tag, dtype, X, K16, gamma, beta, base, running_mean, run
     lib = L.load()
     _require_cuda(X, K16, gamma, beta, base)
     B, D = X.shape
-    Xf = X.to(torch.float32).contiguous()
+    Xf = _aligned(X.to(torch.float32).contiguous())
     gm = gamma.detach().to(torch.float32).contiguous()
     bt = beta.detach().to(torch.float32).contiguous()
-    bs = None if base is None else base.to(torch.float32).contiguous()
+    bs = None if base is None else _aligned(base.to(torch.float32).contiguous())
+    K16 = _aligned(K16)
     dev = X.device
     P = torch.empty((B, D), dtype=dtype, device=dev)
     H = torch.empty_like(P)
@@ -1547,7 +1570,7 @@ def _sym16_backward(ctx, tag, gout):
     Xf, K16, gm, P, H, mean, invstd = ctx.saved_tensors
     training, scale, act, has_base = ctx.cfg
     B, D = Xf.shape
-    g = gout.to(torch.float32).contiguous()
+    g = _aligned(gout.to(torch.float32).contiguous())
     dev = Xf.device
     dP = torch.empty_like(P)
     gX = torch.empty_like(Xf)
@@ -1647,7 +1670,7 @@ class _GateCombineFn(torch.autograd.Function):
         _require_cuda(weights, *rest)
         y0 = ys[0]
         dt = y0.dtype if y0.dtype in (torch.float32, torch.bfloat16) or _is_f16(*ys, *gates, weights) else torch.float32
-        ys_c = [y.to(dt).contiguous() for y in ys]
+        ys_c = [_aligned(y.to(dt).contiguous()) for y in ys]
         B, Cc = y0.shape[:2]
         HW = y0[0, 0].numel()
         g_c = [g.detach().to(torch.float32).reshape(B, Cc).contiguous() for g in gates]
@@ -1671,7 +1694,7 @@ class _GateCombineFn(torch.autograd.Function):
         ys_c, g_c = rest[:nl], rest[nl:]
         B, Cc = ys_c[0].shape[:2]
         HW = ys_c[0][0, 0].numel()
-        g = g.to(ys_c[0].dtype).contiguous()
+        g = _aligned(g.to(ys_c[0].dtype).contiguous())
         gys = [torch.empty_like(y) for y in ys_c]
         dots = [torch.empty((B, Cc), dtype=torch.float32, device=g.device) for _ in range(nl)]
         yp = (C.c_void_p * nl)(*[y.data_ptr() for y in ys_c])
@@ -1704,8 +1727,12 @@ class _Explicit5Fn(torch.autograd.Function):
         lib = L.load()
         _require_cuda(u, alpha_base, channel_scaling)
         fam, kt = ("pde_explicit5_f64_", torch.float64) if f64 else ("pde_explicit5_", torch.float32)
-        u = _kernel_input(u, f64)
+        u = _kernel_input(u, f64, align=1)
         B, Cc, H, W = u.shape
+        # rows of whole groups of four columns move four elements wide (16 bytes of fp32, 8 of 16-bit values); every other
+        # plane, and float64, one element at a time
+        ctx.align = 1 if (f64 or W % 4) else 4 * u.element_size()
+        u = _aligned(u, ctx.align)
         a, s = _kernel_param(alpha_base, kt), _kernel_param(channel_scaling, kt)
         res, out, traj = _out_and_traj(u, steps)
         need_grad = any(ctx.needs_input_grad[:3])
@@ -1732,7 +1759,7 @@ class _Explicit5Fn(torch.autograd.Function):
         dt, eps, max_coeff, relax, num_steps, steps, bits, f64 = ctx.cfg
         fam = "pde_explicit5_f64_" if f64 else "pde_explicit5_"
         B, Cc, H, W = u.shape
-        gout, gtraj = _cotangents(g, u, steps)
+        gout, gtraj = _cotangents(g, u, steps, ctx.align)
         gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
         io = () if f64 else (_io_dtype(u),)
         ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(B, Cc, H, W, *io, num_steps), u.device)
@@ -1764,7 +1791,8 @@ class _JacobiFn(torch.autograd.Function):
         lib = L.load()
         _require_cuda(u, a_row, b_col)
         fam, kt = ("pde_jacobi_f64_", torch.float64) if f64 else ("pde_jacobi_io_", torch.float32)
-        u = _kernel_input(u, f64, (torch.float32, torch.float16))
+        ctx.align = 1                                            # the Jacobi kernels move one element at a time
+        u = _kernel_input(u, f64, (torch.float32, torch.float16), align=1)
         B, H, W = u.shape
         a, b = _kernel_param(a_row, kt), _kernel_param(b_col, kt)
         res, out, traj = _out_and_traj(u, steps)
@@ -1791,7 +1819,7 @@ class _JacobiFn(torch.autograd.Function):
         nt, steps, bits, f64 = ctx.cfg
         fam = "pde_jacobi_f64_" if f64 else "pde_jacobi_io_"
         B, H, W = u.shape
-        gout, gtraj = _cotangents(g, u, steps)
+        gout, gtraj = _cotangents(g, u, steps, ctx.align)
         gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
         io = () if f64 else (_io_dtype(u),)
         with torch.cuda.device(u.device):
@@ -1894,7 +1922,7 @@ class _SkipBlendFn(torch.autograd.Function):
         if u0.shape != u.shape:
             raise L.PdeError(f"shapes differ: {tuple(u0.shape)} vs {tuple(u.shape)}")
         dt = u.dtype if u.dtype in (torch.float32, torch.bfloat16) or _is_f16(u, u0, skip_weight) else torch.float32
-        a, b = u0.to(dt).contiguous(), u.to(dt).contiguous()
+        a, b = _aligned(u0.to(dt).contiguous()), _aligned(u.to(dt).contiguous())
         w = skip_weight.detach().to(torch.float32).reshape(1).contiguous()
         out = torch.empty_like(b)
         with torch.cuda.device(b.device):
@@ -1908,7 +1936,7 @@ class _SkipBlendFn(torch.autograd.Function):
     def backward(ctx, g):
         lib = L.load()
         a, b, w = ctx.saved_tensors
-        g = g.to(b.dtype).contiguous()
+        g = _aligned(g.to(b.dtype).contiguous())
         g_a, g_b = torch.empty_like(a), torch.empty_like(b)
         g_w = torch.empty(1, dtype=torch.float32, device=b.device)
         ws = _workspace(lib.pde_skip_blend_backward_workspace_bytes(b.numel()), b.device)

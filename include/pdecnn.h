@@ -33,6 +33,33 @@
  *                          and the backward recomputes what it needs of it instead of reading it;
  *   - UPDATED in place (read, then written): running_mean / running_var, in training mode only.
  * Inputs (pointers to const) are never written.
+ *
+ * Alignment.  Where a buffer may begin: the width of the widest access any kernel behind the parameter makes through it,
+ * in every dispatch variant and under every environment switch (DESIGN.md section 5 has the evidence per family).  A
+ * non-NULL device pointer below its requirement is refused on the host, with the NULL and shape checks and before anything
+ * touches the runtime: PDE_E_BADARG, for a workspace PDE_E_WORKSPACE.  A pointer that is given is checked, also where the
+ * call would not read it (states with an empty mask).  Only the base address is constrained, never a buffer's length.
+ *   - DEFAULT, 16 bytes: every tensor, coefficient plane and matrix (u, y, gy, gu, states, traj, out, gout, x, X, K, K16, P, H,
+ *     M, alpha_base ..., their gradients, the tensors ys[i] / gys[i] point to, ...) and EVERY workspace (`workspace`,
+ *     `steps_workspace`, `fwd_workspace`).  The kernels move these as float4 / uint4 (uint2 for four 16-bit values).
+ *   - ELEMENT, the alignment of one element (4 bytes for float and int32_t, 8 for double, 2 for 16-bit values): what
+ *     the kernels read and write one element at a time, by parameter name, struct fields of PdeSmallLayer included:
+ *     ELEMENT-ALIGNED: kappa_max, kappa_max_host, skip_weight, g_skip_weight, weight_ptr, g_weight, plane_sums, weights,
+ *                      gates, dots, gamma, beta, mean, invstd, running_mean, running_var, ggamma, gbeta, argmax,
+ *                      bn_weight, bn_bias, g_bn_weight, g_bn_bias, a_row, b_col, g_a_row, g_b_col, channel_scaling,
+ *                      g_channel_scaling
+ *     (gates and dots: the arrays their entries point to; so weight_ptr = weights + i of a shared-input group is legal).
+ *     Two families read a parameter one element at a time whose NAME is a 16-byte tensor everywhere else:
+ *     ELEMENT-ALIGNED IN pde_explicit5_: alpha_base, g_alpha_base    (C values, not the implicit layers' (C,N,N) planes)
+ *     ELEMENT-ALIGNED IN pde_bn_pool_: out, gout                      (the pooled cells, stored and read one at a time)
+ *   - ELEMENT-WISE CALLS: a call whose kernels all move one element at a time asks the element's alignment of every tensor
+ *     and coefficient pointer (its workspaces stay at 16): every pde_*_f64_* function; every pde_adi_rect_* function;
+ *     pde_adi_forward / _backward / _backward_input[_states] / _forward_states / _backward_states / _kappa_max when N is not
+ *     one of the fused line lengths (pde_adi_line_length_path(N) == 2); every pde_jacobi_* function; pde_explicit5_* when W
+ *     is no multiple of 4.  This is what lets `y` (`out`) be the last slice of a stacked trajectory tensor at any plane size.
+ *   - FOUR ELEMENTS: pde_explicit5_* with W a multiple of 4 and 16-bit tensors asks 8 bytes of u, out, gout, gu, traj,
+ *     gtraj (four 16-bit values per access; a slice of a (slots, B, C, H, W) tensor begins on such a boundary); its fp32
+ *     `states` and everything else follow the default.
  */
 #ifndef PDECNN_H
 #define PDECNN_H
@@ -49,7 +76,7 @@ extern "C" {
 #define PDE_MAX_N_GENERIC 128      /* longest line of the any-size path (one thread per line, plane in LDS)              */
 
 #define PDE_OK 0
-#define PDE_E_BADARG (-1)          /* null pointer, non-positive dim, bad enum */
+#define PDE_E_BADARG (-1)          /* null or misaligned pointer (see Alignment above), non-positive dim, bad enum */
 #define PDE_E_UNSUPPORTED_N (-2)   /* whole-schedule calls: N < 2 or > PDE_MAX_N_GENERIC; per-step / one-launch
                                       families: N not one of the fused line lengths */
 #define PDE_E_TOO_MANY_SWEEPS (-3)
@@ -112,7 +139,7 @@ int pde_adi_forward_kernel(const PdeAdiDesc* d);
  * environment keeps the library on 0. */
 int pde_adi_backward_kernel(const PdeAdiDesc* d, int32_t num_checkpoints);
 
-/* Bytes of scratch the forward/backward calls need (256-byte aligned base expected). */
+/* Bytes of scratch the forward/backward calls need (the base 16-byte aligned, as every workspace: Alignment above). */
 size_t pde_adi_forward_workspace_bytes(const PdeAdiDesc* d);
 size_t pde_adi_backward_workspace_bytes(const PdeAdiDesc* d, int32_t num_checkpoints);
 

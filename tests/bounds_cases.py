@@ -17,6 +17,12 @@ Roles of a buffer:
             one-launch wide forward: ``written_slots`` names the slices that are, and those are held like an output)
     ws      scratch of exactly the queried size, 0xFF on entry
 
+Every buffer also carries the alignment the header's "Alignment" section asks of the pointer it is bound to (``ctx.aligns``,
+bytes): 16 by default and for every workspace, the element's own for the names of ``ELEMENT_ALIGNED`` and, when the builder
+says that its calls are served by element-wise kernels (``ctx.vec_elems = 1``), for every other tensor too; ``vec_elems = 4``
+is the explicit layer on float4 rows (16-bit tensors then begin on 8 bytes).  tests/test_bounds_cases.py holds the table to
+the header; tests/test_alignment_refusal.py and tests/test_gpu_alignment.py run it.
+
 Arguments of a call are looked up by the parameter NAMES the header declares, so a builder only says where a name differs
 from the buffer it is bound to ({"workspace": "bws"}); kappa_max_host and kappa_event are NULL in every case."""
 import ctypes as C
@@ -30,6 +36,39 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IO = {"f32": (0, torch.float32), "bf16": (1, torch.bfloat16), "f16": (3, torch.float16), "f64": (2, torch.float64)}
 IO3 = ("f32", "bf16", "f16")
 NULL_BY_DEFAULT = ("kappa_max_host", "kappa_event")
+
+DEFAULT_ALIGN = 16
+#: parameters (and PdeSmallLayer fields) the kernels read and write one element at a time: the ELEMENT-ALIGNED list of pdecnn.h
+ELEMENT_ALIGNED = frozenset((
+    "kappa_max", "kappa_max_host", "skip_weight", "g_skip_weight", "weight_ptr", "g_weight", "plane_sums", "weights", "gates", "dots",
+    "gamma", "beta", "mean", "invstd", "running_mean", "running_var", "ggamma", "gbeta", "argmax", "bn_weight", "bn_bias",
+    "g_bn_weight", "g_bn_bias", "a_row", "b_col", "g_a_row", "g_b_col", "channel_scaling", "g_channel_scaling"))
+
+
+def header_element_aligned():
+    """The names behind ``ELEMENT-ALIGNED:`` in the Alignment section of pdecnn.h."""
+    src = open(os.path.join(ROOT, "include", "pdecnn.h")).read()
+    m = re.search(r"ELEMENT-ALIGNED:(.*?)\n \*\s+\(", src, flags=re.S)
+    return frozenset(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", m.group(1).replace("*", " ")))
+
+
+#: function prefix -> names that are element-aligned in those functions only (the ELEMENT-ALIGNED IN lines of pdecnn.h)
+ELEMENT_ALIGNED_IN = {"pde_explicit5_": frozenset(("alpha_base", "g_alpha_base")), "pde_bn_pool_": frozenset(("out", "gout"))}
+
+
+def header_element_aligned_in():
+    src = open(os.path.join(ROOT, "include", "pdecnn.h")).read()
+    return {m.group(1): frozenset(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", m.group(2).split("(")[0]))
+            for m in re.finditer(r"ELEMENT-ALIGNED IN (pde_[a-z0-9_]+): ([^\n]*)", src)}
+
+
+def param_of(buffer):
+    """The parameter (or struct field) a buffer is named after: per-layer and per-slot suffixes dropped (gates_0, kappa_max_2)."""
+    return re.sub(r"_\d+$", "", buffer)
+
+
+def fused_line_length(n):
+    return 8 <= n <= 32 and n % 4 == 0
 
 
 # ---------------------------------------------------------------------------------------------------- the header
@@ -76,10 +115,22 @@ class SpecCtx:
     def __init__(self):
         self.roles, self.shapes, self.dtypes, self.values, self.t = {}, {}, {}, {}, {}
         self.written_slots = {}                  # carry buffer written in part -> the slices (first axis) the header says are written
+        self.aligns = {}                         # buffer -> bytes its base must be a multiple of (pdecnn.h, "Alignment")
+        self.vec_elems = None                    # None: the default rule; k: tensors of this case begin on k elements (at most 16 bytes)
+        self.also_element = frozenset()          # names that are element-aligned in this case's functions only
 
-    def _add(self, name, role, shape, dtype, fill=None):
+    def _align_of(self, name, role, dtype, param):
+        item = torch.empty((), dtype=dtype).element_size()
+        if dtype == torch.uint8 and role in ("ws", "carry"):
+            return DEFAULT_ALIGN                                     # every workspace
+        if (param or param_of(name)) in ELEMENT_ALIGNED or (param or param_of(name)) in self.also_element:
+            return item
+        return DEFAULT_ALIGN if self.vec_elems is None else min(DEFAULT_ALIGN, self.vec_elems * item)
+
+    def _add(self, name, role, shape, dtype, fill=None, param=None):
         assert name not in self.roles and name not in self.values, f"{name} declared twice"
         self.roles[name], self.shapes[name], self.dtypes[name] = role, tuple(int(s) for s in shape), dtype
+        self.aligns[name] = self._align_of(name, role, dtype, param)
         self.t[name] = self._alloc(name, role, self.shapes[name], dtype, fill)
         return self.t[name]
 
@@ -93,8 +144,9 @@ class SpecCtx:
     def inout(self, name, t):
         return self._add(name, "inout", t.shape, t.dtype, t)
 
-    def out(self, name, shape, dtype):
-        return self._add(name, "out", shape, dtype)
+    def out(self, name, shape, dtype, param=None):
+        """``param``: the parameter whose alignment rule applies, where the buffer is not named after it."""
+        return self._add(name, "out", shape, dtype, param=param)
 
     def carry(self, name, shape, dtype):
         return self._add(name, "carry", shape, dtype)
@@ -216,6 +268,8 @@ def build_adi(ctx, p):
     d = ctx.val("d", _adi_desc(p))
     shape = (p["B"], p["C"], p["H"], p["W"])
     S, fam = d.num_sweeps, _adi_fam(p)
+    if fam != "pde_adi_" or not fused_line_length(p["H"]):       # rectangles, float64, the any-size path: element-wise kernels
+        ctx.vec_elems = 1
     ckpt, emit = p.get("ckpt", 0), p.get("emit", 0)
     ctx.inp("u", torch.randn(shape, generator=g), dt)
     ctx.inp("gy", torch.randn(shape, generator=g), dt)
@@ -238,7 +292,7 @@ def build_adi(ctx, p):
              (fam + "backward" + st, {"fwd_workspace": "fws" if p.get("reuse", True) else None, "workspace": "bws",
                                       "workspace_bytes": nb})]
     if fam != "pde_adi_f64_":                          # the square float64 family has no kappa_max entry point
-        ctx.out("kappa2", (S,), kt)
+        ctx.out("kappa2", (S,), kt, param="kappa_max")
         calls.append((fam + "kappa_max", {"kappa_max": "kappa2"}))
     expect = []
     if "fwd_kernel" in p:
@@ -426,6 +480,8 @@ def build_mix(ctx, p):
     B, Cc, HW, f64 = p["B"], p["C"], p["HW"], p["io"] == "f64"
     code, dt = IO[p["io"]]
     pt = torch.float64 if f64 else torch.float32
+    if f64:
+        ctx.vec_elems = 1
     for k in ("B", "C", "HW"):
         ctx.val(k, p[k])
     ctx.val("io_dtype", code)
@@ -463,6 +519,8 @@ def build_blend(ctx, p):
     n, f64 = p["n"], p["io"] == "f64"
     code, dt = IO[p["io"]]
     pt = torch.float64 if f64 else torch.float32
+    if f64:
+        ctx.vec_elems = 1
     ctx.val("n", n)
     ctx.val("io_dtype", code)
     ctx.inp("u0", torch.randn(n, generator=g), dt)
@@ -505,6 +563,7 @@ def build_bn_pool(ctx, p):
     l = lib()
     g = _gen(p)
     B, Cc, N = p["B"], p["C"], p["N"]
+    ctx.also_element = ELEMENT_ALIGNED_IN["pde_bn_pool_"]
     for k in ("B", "C", "N"):
         ctx.val(k, p[k])
     ctx.val("eps", 1e-5)
@@ -539,6 +598,8 @@ def build_explicit(ctx, p):
     code, dt = IO[p["io"]]
     pt = torch.float64 if f64 else torch.float32
     emit = p.get("emit", 0)
+    ctx.vec_elems = 1 if (f64 or W % 4) else 4                   # float4 rows: four elements per access, 8 bytes of 16-bit ones
+    ctx.also_element = ELEMENT_ALIGNED_IN["pde_explicit5_"]
     for k, v in (("B", B), ("C", Cc), ("H", H), ("W", W), ("io_dtype", code), ("num_steps", nt), ("dt", 0.01), ("eps", 1e-6),
                  ("max_coeff", 0.15), ("relax", 0.1)):
         ctx.val(k, v)
@@ -577,6 +638,7 @@ def build_jacobi(ctx, p):
     code, dt = IO["f64" if f64 else p["io"]]
     pt = torch.float64 if f64 else torch.float32
     emit = p.get("emit", 0)
+    ctx.vec_elems = 1                                            # the Jacobi kernels move one element at a time
     for k, v in (("B", B), ("H", H), ("W", W), ("nt", nt), ("io_dtype", code)):
         ctx.val(k, v)
     ctx.inp("u", torch.randn(B, H, W, generator=g), dt)

@@ -256,3 +256,64 @@ def test_the_cases_are_small(built):
     for cid, (ctx, _, _) in built.items():
         total = sum(ctx.nbytes(n) for n in ctx.roles)
         assert total < 96 << 20, (cid, total)
+
+
+# ---------------------------------------------------------------------------------------------------- alignment
+_WHOLE_SCHEDULE = ("forward", "backward", "forward_states", "backward_states", "backward_input", "backward_input_states",
+                   "kappa_max")
+_EXPLICIT_IO = ("u", "out", "gout", "gu", "traj", "gtraj")
+
+
+def _header_align(case, fn, pname, dtype):
+    """Bytes the Alignment section of pdecnn.h asks of parameter ``pname`` of ``fn`` in this case — written out from the
+    header's text, independently of the builders."""
+    item = torch.empty((), dtype=dtype).element_size()
+    p = case.p
+    if "workspace" in pname:
+        return 16
+    if pname in BC.header_element_aligned():
+        return item
+    for prefix, names in BC.header_element_aligned_in().items():
+        if fn.startswith(prefix) and pname in names:
+            return item
+    elementwise = ("_f64_" in fn or fn.startswith(("pde_adi_rect_", "pde_jacobi_")) or
+                   (fn.startswith("pde_explicit5_") and p["W"] % 4 != 0) or
+                   (fn in tuple("pde_adi_" + s for s in _WHOLE_SCHEDULE) and BC.lib().pde_adi_line_length_path(p["H"]) == 2))
+    if elementwise:
+        return item
+    if fn.startswith("pde_explicit5_") and pname in _EXPLICIT_IO and item == 2:
+        return 8
+    return 16
+
+
+def test_the_alignment_table_is_the_headers(built):
+    """Every exception the header names is in the table and vice versa; every buffer a call is handed carries the alignment
+    the header asks of that parameter (a buffer bound to several parameters: of each of them)."""
+    assert BC.header_element_aligned() == BC.ELEMENT_ALIGNED
+    assert BC.header_element_aligned_in() == BC.ELEMENT_ALIGNED_IN
+    declared = {n for ps in HDR.values() for n, ptr, _ in ps if ptr}
+    from cnn_with_pde_amd import _lib
+    declared |= {f for f, _ in _lib.PdeSmallLayer._fields_}
+    assert not BC.ELEMENT_ALIGNED - declared, BC.ELEMENT_ALIGNED - declared
+    seen, less = 0, set()
+    for c in BC.CASES:
+        ctx, calls, _ = built[c.id]
+        assert set(ctx.aligns) == set(ctx.roles)
+        for fn, amap in calls:
+            for pname, buf, _ in BC.bound_buffers(ctx, HDR[fn], amap):
+                want = _header_align(c, fn, pname, ctx.dtypes[buf])
+                assert ctx.aligns[buf] == want, (c.id, fn, pname, buf, ctx.aligns[buf], want)
+                seen += 1
+                if want < 16:
+                    less.add(pname)
+        if c.family in ("multi", "gate"):                        # pointers that travel inside a struct or an array
+            for buf in ctx.roles:
+                field = BC.param_of(buf)
+                if buf != field or buf == "weights":
+                    item = torch.empty((), dtype=ctx.dtypes[buf]).element_size()
+                    want = 16 if (ctx.dtypes[buf] == torch.uint8) else (item if field in BC.ELEMENT_ALIGNED else 16)
+                    assert ctx.aligns[buf] == want, (c.id, buf, ctx.aligns[buf], want)
+                    seen += 1
+    assert seen > 5000 and BC.ELEMENT_ALIGNED - {"kappa_max_host", "weight_ptr", "gates", "dots", "plane_sums", "g_weight"} <= less, \
+        BC.ELEMENT_ALIGNED - less
+    print(f"{seen} (call, parameter) bindings carry the header's alignment; below 16 bytes: {sorted(less)}")

@@ -68,11 +68,15 @@ class PlainCtx(BC.SpecCtx):
 
 
 class ArenaCtx(PlainCtx):
+    skew = False                                 # tests/test_gpu_alignment.py: every buffer at exactly the alignment the header asks
+
     def __init__(self):
         super().__init__()
-        self.arena = GU.Arena("cuda")
+        self.arena = GU.Arena("cuda", skew=self.skew)
 
     def _alloc(self, name, role, shape, dtype, fill):
+        if self.skew:
+            return self.arena.tensor(shape, dtype, fill=fill, name=name, align=self.aligns[name])
         return self.arena.tensor(shape, dtype, fill=fill, name=name)
 
     def ptr(self, name, byte_offset=0):
@@ -113,11 +117,12 @@ def _finite(t):
     return torch.isfinite(t) if t.is_floating_point() else torch.ones_like(t, dtype=torch.bool)
 
 
-def check_case(case, lib=None, hdr=None):
-    """Both runs of one case and the assertions; returns the line it prints."""
+def check_case(case, lib=None, hdr=None, guarded_ctx=None):
+    """Both runs of one case and the assertions; returns the line it prints.  ``guarded_ctx``: the context of the guarded run
+    (``ArenaCtx``, or a subclass that places its buffers differently)."""
     lib = lib or BC.lib()
     hdr = hdr or BC.header_functions()
-    guarded = ArenaCtx()
+    guarded = (guarded_ctx or ArenaCtx)()
     _run(case, guarded, lib, hdr)
     guarded.arena.check()                                        # 1. every guard byte of every buffer
     outs = [n for n, r in guarded.roles.items() if r == "out"]

@@ -106,3 +106,58 @@ def test_unwritten_on_integer_outputs():
     assert a.unwritten(t) == 6
     t[0] = 0
     assert a.unwritten(t) == 3
+
+
+@pytest.mark.parametrize("align", [2, 4, 8, 16, 256])
+def test_a_skewed_arena_places_buffers_at_exactly_their_alignment(align):
+    """address = align (mod 2 * align): a multiple of the alignment asked for and of nothing larger — 16 mod 32 for a
+    tensor of the C ABI, 4 mod 8 for one of its fp32 scalars — for odd sizes and for the empty buffer too."""
+    a = GU.Arena(skew=True)
+    for nbytes in (0, 1, 24, 1001):
+        v = a.raw(nbytes, align=align)
+        assert a.ptr(v) % (2 * align) == align and v.numel() == nbytes
+        if nbytes:
+            assert v.data_ptr() == a.ptr(v)
+    for dtype in (torch.float16, torch.float32, torch.float64, torch.int32):
+        item = torch.empty((), dtype=dtype).element_size()
+        if align < item:
+            with pytest.raises(ValueError):
+                a.tensor((3, 5), dtype, align=align)
+            continue
+        t = a.tensor((3, 5), dtype, fill=torch.arange(15).reshape(3, 5), align=align)
+        assert t.data_ptr() % (2 * align) == align and t.is_contiguous() and t.dtype == dtype
+        assert torch.equal(t, torch.arange(15).reshape(3, 5).to(dtype)) and a.unwritten(t) == 0
+    a.check()
+    with pytest.raises(ValueError):
+        a.raw(8, align=24)
+
+
+def test_an_arena_without_skew_keeps_its_default_and_honours_a_smaller_alignment():
+    a = GU.Arena()
+    assert a.ptr(a.raw(40)) % GU.ALIGN == 0                          # what every test before the skew relied on
+    assert a.tensor((7,), torch.float32, align=16).data_ptr() % 16 == 0
+
+
+def test_the_guards_of_a_skewed_buffer_start_at_its_exact_first_and_last_byte():
+    """The placement moves the view, never the guards' edges: a byte just before the first element and a byte just behind
+    the last one of an odd-sized tensor are both reported at offsets -1 and 0."""
+    a = GU.Arena(skew=True)
+    t = a.tensor((37, 3), torch.bfloat16, fill=torch.zeros(37, 3), name="t", align=16)
+    s = a.tensor((1,), torch.float32, fill=torch.zeros(1), name="s", align=4)
+    assert t.data_ptr() % 32 == 16 and s.data_ptr() % 8 == 4
+    a.check()
+    r = a.bufs[0]
+    assert r.nbytes == 37 * 3 * 2 and r.buf.data_ptr() + r.off == t.data_ptr()
+    end = r.off + r.nbytes
+    r.buf[r.off - 1] = 0
+    r.buf[end] = 0
+    assert a.damage() == [("t", "head", -1, -1, 1), ("t", "tail", 0, 0, 1)]
+    r.buf[r.off - 1] = GU.POISON
+    r.buf[end] = GU.POISON
+    t[0, 0] = 1.0                                                    # the first and the last element are inside, not guard
+    t[-1, -1] = 1.0
+    a.check()
+    q = a.bufs[1]
+    q.buf[q.off + 4] = 0
+    assert a.damage() == [("s", "tail", 0, 0, 1)]
+    assert r.off >= GU.GUARD and r.buf.numel() - end >= GU.GUARD     # 1 MiB on both sides still
