@@ -268,6 +268,19 @@ SIGNATURES = {
     "pde_version": (C.c_char_p, []),
 }
 
+#: include/pdecnn_small_input.h (included by pdecnn.h): the input-only backward of the one-launch C <= 4 layers — the forward
+#: that parks nothing, and gu = F^T gy from the factorisation the forward left (steps_workspace), with a workspace that
+#: holds the slab of a side-by-side group only
+SIGNATURES_SMALL_INPUT = {
+    "pde_adi_small_backward_input_workspace_bytes": (_sz, [_D, _i32]),
+    "pde_adi_small_forward_input": (C.c_int, [_D, _i32, _i32, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz,
+                                              _vp]),
+    "pde_adi_small_backward_input": (C.c_int, [_D, _i32, _i32, _vp, _fp, _fp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_small_backward_input_states": (C.c_int, [_D, _i32, _i32, _vp, _vp, C.POINTER(C.c_uint64), _fp, _vp, _vp, _vp,
+                                                      _sz, _vp]),
+    "pde_adi_multi_backward_input": (C.c_int, [_i32, C.POINTER(PdeSmallLayer), _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -281,7 +294,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C cnn-with-pde_amd/csrc`). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SMALL_INPUT.items()):
         fn = getattr(lib, name)         # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     _lib = lib

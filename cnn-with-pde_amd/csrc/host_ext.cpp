@@ -215,12 +215,14 @@ bool bwd_input_enabled() {
 // what a call keeps for its backward: nothing, everything the full backward reads, or — coefficients frozen, gradient
 // for the input alone — the coefficient views and the factorisation only (pde_adi_backward_input reads neither y nor u)
 constexpr int64_t kGradNone = 0, kGradFull = 1, kGradInput = 2;
-int64_t adi_grad_mode(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& asl, const Tensor& bsl) {
+int64_t grad_mode_of(const Tensor& u, bool params) {
     if (!at::GradMode::is_enabled()) return kGradNone;
-    const bool params = ab.requires_grad() || bb.requires_grad() || asl.requires_grad() || bsl.requires_grad();
     if (params) return kGradFull;
     if (!u.requires_grad()) return kGradNone;
     return bwd_input_enabled() ? kGradInput : kGradFull;
+}
+int64_t adi_grad_mode(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& asl, const Tensor& bsl) {
+    return grad_mode_of(u, ab.requires_grad() || bb.requires_grad() || asl.requires_grad() || bsl.requires_grad());
 }
 
 struct AdiFn : public torch::autograd::Function<AdiFn> {
@@ -406,7 +408,10 @@ std::vector<int64_t> states_shape(int64_t K, const Tensor& u) {
 struct SmallFn : public torch::autograd::Function<SmallFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& u_in, const Tensor& ab, const Tensor& bb, const Tensor& asl,
                           const Tensor& bsl, const Tensor& M, const std::optional<Tensor>& skip_opt, int64_t desc_addr, int64_t sps,
-                          int64_t mode, int64_t ckpt_mode, int64_t ckpt_lo, double amax, bool need_grad) {
+                          int64_t mode, int64_t ckpt_mode, int64_t ckpt_lo, double amax, int64_t grad_mode) {
+        // kGradInput: frozen parameters — pde_adi_small_forward_input parks nothing, and the backward is
+        // pde_adi_small_backward_input (M, skip_weight and the steps workspace are all it keeps)
+        const bool need_grad = grad_mode == kGradFull, input_only = grad_mode == kGradInput;
         const Tensor skip = skip_opt.has_value() ? *skip_opt : Tensor();
         PDE_REQUIRE(u_in.is_cuda() && ab.is_cuda() && bb.is_cuda() && asl.is_cuda() && bsl.is_cuda() && M.is_cuda() &&
                         (!skip.defined() || skip.is_cuda()),
@@ -436,6 +441,19 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         }
         if (need_grad) states = at::empty(states_shape(K, u), u.options());
         Tensor y = at::empty_like(u);
+        if (input_only) {
+            check(pde_adi_small_forward_input(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), y.data_ptr(), Mf.data_ptr<float>(),
+                                              sw.defined() ? sw.data_ptr<float>() : nullptr, p[0].data_ptr<float>(),
+                                              p[1].data_ptr<float>(), p[2].data_ptr<float>(), p[3].data_ptr<float>(), nullptr,
+                                              nullptr, nullptr, sws.data_ptr(), (size_t)sws.numel(), (void*)st),
+                  "pde_adi_small_forward_input");
+            ctx->save_for_backward({Mf, sw});
+            ctx->saved_data["sws"] = sws;
+            ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(&d), sizeof(d));
+            ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode};
+            ctx->saved_data["input_only"] = (int64_t)u.scalar_type();
+            return y;
+        }
         check(pde_adi_small_forward(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), y.data_ptr(),
                                     need_grad ? states.data_ptr() : nullptr, Mf.data_ptr<float>(),
                                     sw.defined() ? sw.data_ptr<float>() : nullptr, p[0].data_ptr<float>(), p[1].data_ptr<float>(),
@@ -464,7 +482,31 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         return y;
     }
 
+    // gu = F^T gy alone: the operator, the skip weight, the forward's factorisation, one launch
+    static variable_list backward_input(AutogradContext* ctx, variable_list& grads) {
+        auto saved = ctx->get_saved_variables();
+        const Tensor &Mf = saved[0], &sw = saved[1];
+        PdeAdiDesc d;
+        std::memcpy(&d, ctx->saved_data["desc"].toStringRef().data(), sizeof(d));
+        auto cfg = ctx->saved_data["cfg"].toIntVector();
+        const auto dtype = static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
+        Tensor gy = grads[0];
+        if (gy.scalar_type() != dtype) gy = gy.to(dtype);
+        gy = aligned(gy.contiguous());
+        c10::hip::HIPGuardMasqueradingAsCUDA guard(gy.device());
+        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(gy.device().index()).stream();
+        Tensor gu = at::empty_like(gy);
+        Tensor sws = ctx->saved_data["sws"].toTensor();
+        check(pde_adi_small_backward_input(&d, (int32_t)cfg[0], (int32_t)cfg[1], gy.data_ptr(), Mf.data_ptr<float>(),
+                                           sw.defined() ? sw.data_ptr<float>() : nullptr, gu.data_ptr(), sws.data_ptr(), nullptr,
+                                           0, (void*)st),
+              "pde_adi_small_backward_input");
+        return {gu, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                Tensor(), Tensor()};
+    }
+
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (ctx->saved_data.count("input_only")) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &u = saved[0], &Mf = saved[1], &sw = saved[2];
         PdeAdiDesc d;
@@ -512,10 +554,9 @@ Tensor small(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& 
              double amax) {
     const Tensor sk = (skip.has_value() && skip->defined()) ? *skip : Tensor();
     const std::optional<Tensor> sko = sk.defined() ? std::optional<Tensor>(sk) : std::nullopt;
-    const bool need_grad = at::GradMode::is_enabled() &&
-                           (u.requires_grad() || ab.requires_grad() || bb.requires_grad() || asl.requires_grad() ||
-                            bsl.requires_grad() || M.requires_grad() || (sk.defined() && sk.requires_grad()));
-    return SmallFn::apply(u, ab, bb, asl, bsl, M, sko, desc_addr, sps, mode, ckpt_mode, ckpt_lo, amax, need_grad);
+    const bool params = ab.requires_grad() || bb.requires_grad() || asl.requires_grad() || bsl.requires_grad() ||
+                        M.requires_grad() || (sk.defined() && sk.requires_grad());
+    return SmallFn::apply(u, ab, bb, asl, bsl, M, sko, desc_addr, sps, mode, ckpt_mode, ckpt_lo, amax, grad_mode_of(u, params));
 }
 
 // ---- one layer with a channel operator between its steps at any width: one factorisation, then per step one mixing and
@@ -626,7 +667,10 @@ Tensor mixed(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& 
 struct MultiFn : public torch::autograd::Function<MultiFn> {
     static variable_list forward(AutogradContext* ctx, const Tensor& u_in, const std::optional<Tensor>& w_opt, at::TensorList flat,
                                  std::vector<int64_t> desc_addrs, int64_t sps, bool want_sums, int64_t ckpt_mode,
-                                 std::vector<int64_t> masks, double amax, bool need_grad) {
+                                 std::vector<int64_t> masks, double amax, int64_t grad_mode) {
+        // kGradInput: frozen parameters — the forward is the same call (the y_i are the last kept states), but no
+        // coefficient maxima are asked for and the node keeps the operators, the weights and the factorisations only
+        const bool need_grad = grad_mode != kGradNone, input_only = grad_mode == kGradInput;
         const int nl = (int)desc_addrs.size();
         const Tensor weights = w_opt.has_value() ? *w_opt : Tensor();
         PDE_REQUIRE(nl >= 1 && (int)flat.size() == 5 * nl, "adi_diffuse_multi: five tensors per layer");
@@ -637,7 +681,7 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         Tensor u = u_in.detach();
         if (!io_type(u)) u = u.to(at::kFloat);
         u = aligned(u.contiguous());
-        const bool want_kmax = need_grad && ckpt_mode == 1;
+        const bool want_kmax = need_grad && ckpt_mode == 1 && !input_only;
         ctx->set_materialize_grads(false);
         Tensor wdev = weights.defined() ? as_f32(weights, false) : Tensor();
         c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
@@ -698,7 +742,16 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         Slot* last = want_kmax ? reinterpret_cast<Slot*>((intptr_t)slots.back()) : nullptr;   // recorded behind the last layer's copy
         check(pde_adi_multi_forward(nl, arr.data(), u.data_ptr(), out.data_ptr(), last ? (void*)last->ev : nullptr, (void*)st),
               "pde_adi_multi_forward");
-        if (need_grad) {
+        if (input_only) {
+            std::vector<Tensor> keep{wdev};
+            for (int i = 0; i < nl; ++i) keep.push_back(save[2 + 5 * i + 4]);
+            ctx->save_for_backward(keep);
+            ctx->saved_data["hold"] = hold;                   // the steps workspaces, one per layer
+            ctx->saved_data["descs"] = std::string(reinterpret_cast<const char*>(descs.data()), sizeof(PdeAdiDesc) * nl);
+            ctx->saved_data["cfg"] = std::vector<int64_t>{nl, sps, want_sums ? 1 : 0, ckpt_mode, weights.defined() ? 1 : 0};
+            ctx->saved_data["input_only"] = (int64_t)u.scalar_type();
+            ctx->saved_data["ushape"] = u.sizes().vec();
+        } else if (need_grad) {
             ctx->save_for_backward(save);
             ctx->saved_data["hold"] = hold;
             ctx->saved_data["states"] = states_v;
@@ -720,7 +773,73 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         return res;
     }
 
+    // gu = sum_i F_i^T (w_i gy + gys_i + g_plane_sums_i) alone: pde_adi_multi_backward_input, one launch (two side by side)
+    static variable_list backward_input(AutogradContext* ctx, variable_list& grads) {
+        auto saved = ctx->get_saved_variables();
+        auto cfg = ctx->saved_data["cfg"].toIntVector();
+        const int nl = (int)cfg[0], sps = (int)cfg[1];
+        const bool want_sums = cfg[2] != 0;
+        const Tensor& wdev = saved[0];
+        const auto dtype = static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
+        std::vector<PdeAdiDesc> descs(nl);
+        std::memcpy(descs.data(), ctx->saved_data["descs"].toStringRef().data(), sizeof(PdeAdiDesc) * nl);
+        auto hold = ctx->saved_data["hold"].toTensorVector();
+        const Tensor& like = saved[1];
+        c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
+        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(like.device().index()).stream();
+        Tensor gout = grads[0];
+        if (gout.defined()) {
+            if (gout.scalar_type() != dtype) gout = gout.to(dtype);
+            gout = aligned(gout.contiguous());
+        }
+        std::vector<PdeSmallLayer> arr(nl);
+        std::vector<Tensor> keep;
+        bool any_in = gout.defined();
+        for (int i = 0; i < nl; ++i) {
+            PdeAdiDesc& d = descs[i];
+            Tensor gyi = grads[1 + i], gsi = want_sums ? grads[1 + nl + i] : Tensor();
+            if (gyi.defined()) {
+                if (gyi.scalar_type() != dtype) gyi = gyi.to(dtype);
+                gyi = aligned(gyi.contiguous());
+            }
+            if (gsi.defined()) {
+                if (gsi.scalar_type() != at::kFloat) gsi = gsi.to(at::kFloat);
+                gsi = aligned(gsi.contiguous());
+            }
+            any_in = any_in || gyi.defined() || gsi.defined();
+            // (the slab of a side-by-side group; the query is what the library checks against, used or not)
+            Tensor ws = nl > 1 ? bytes(pde_adi_small_backward_input_workspace_bytes(&d, sps), like) : Tensor();
+            PdeSmallLayer& a = arr[i];
+            std::memset(&a, 0, sizeof(a));
+            a.desc = &d;
+            a.sweeps_per_step = sps;
+            a.mode = 1;
+            a.M = saved[1 + i].data_ptr<float>();
+            a.weight = 0.f;
+            a.weight_ptr = wdev.defined() ? wdev.data_ptr<float>() + i : nullptr;
+            a.steps_workspace = hold[i].data_ptr();
+            a.steps_workspace_bytes = (size_t)hold[i].numel();
+            a.gys = gyi.defined() ? gyi.data_ptr() : nullptr;
+            a.g_plane_sums = gsi.defined() ? gsi.data_ptr<float>() : nullptr;
+            if (ws.defined()) {
+                a.workspace = ws.data_ptr();
+                a.workspace_bytes = (size_t)ws.numel();
+            }
+            keep.push_back(ws);
+            keep.push_back(gyi);
+            keep.push_back(gsi);
+        }
+        PDE_REQUIRE(any_in, "adi_diffuse_multi: no incoming gradient");
+        Tensor gu = at::empty(ctx->saved_data["ushape"].toIntVector(), like.options().dtype(dtype));
+        check(pde_adi_multi_backward_input(nl, arr.data(), gout.defined() ? gout.data_ptr() : nullptr, gu.data_ptr(), (void*)st),
+              "pde_adi_multi_backward_input");
+        variable_list res(2 + 5 * nl + 7);
+        res[0] = gu;
+        return res;
+    }
+
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (ctx->saved_data.count("input_only")) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         auto cfg = ctx->saved_data["cfg"].toIntVector();
         const int nl = (int)cfg[0], sps = (int)cfg[1];
@@ -826,10 +945,10 @@ variable_list multi(const Tensor& u, const std::optional<Tensor>& weights, std::
                     double amax) {
     const Tensor w = (weights.has_value() && weights->defined()) ? *weights : Tensor();
     const std::optional<Tensor> wo = w.defined() ? std::optional<Tensor>(w) : std::nullopt;
-    bool need_grad = u.requires_grad() || (w.defined() && w.requires_grad());
-    for (const auto& t : flat) need_grad = need_grad || t.requires_grad();
-    need_grad = need_grad && at::GradMode::is_enabled();
-    return MultiFn::apply(u, wo, at::TensorList(flat), desc_addrs, sps, want_sums, ckpt_mode, masks, amax, need_grad);
+    bool params = w.defined() && w.requires_grad();
+    for (const auto& t : flat) params = params || t.requires_grad();
+    return MultiFn::apply(u, wo, at::TensorList(flat), desc_addrs, sps, want_sums, ckpt_mode, masks, amax,
+                          grad_mode_of(u, params));
 }
 
 

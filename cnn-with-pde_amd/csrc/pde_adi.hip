@@ -1791,6 +1791,123 @@ int pde_adi_small_backward_states(const PdeAdiDesc* d, int32_t sweeps_per_step, 
     return small_backward_impl(1, &l, gy, u, gu, stream, gtraj, any ? emit_mask : nullptr);
 }
 
+// ---- the one-launch layers with frozen parameters: gu = F^T gy alone (adi_small_bwd_input_kernel) ----
+size_t pde_adi_small_backward_input_workspace_bytes(const PdeAdiDesc* d, int32_t sweeps_per_step) {
+    if (!pde_adi_small_supported(d, sweeps_per_step)) return 0;
+    return align_up(state_bytes(d), 256);                  // this layer's term of a side-by-side group's input gradient
+}
+
+// multi_check for a call that reads no coefficient: what the launch depends on, every non-NULL device pointer of the
+// struct at its alignment, the factorisation, and — side by side — a slab per layer.  All of it before the launch
+static int multi_check_input(int32_t L, const PdeSmallLayer* layers) {
+    if (L < 1 || L > kSmallMaxL || !layers) return PDE_E_BADARG;
+    const PdeAdiDesc* d0 = layers[0].desc;
+    for (int i = 0; i < L; ++i) {
+        const PdeSmallLayer& y = layers[i];
+        if (!y.desc || !pde_adi_small_supported(y.desc, y.sweeps_per_step)) return PDE_E_BADARG;
+        if (!y.M || (y.mode != 1 && y.mode != 2) || (y.skip_weight && y.mode != 2)) return PDE_E_BADARG;
+        if (y.desc->B != d0->B || y.desc->C != d0->C || y.desc->N != d0->N || y.desc->io_dtype != d0->io_dtype ||
+            y.sweeps_per_step != layers[0].sweeps_per_step)
+            return PDE_E_BADARG;
+        if (L > 1 && y.mode != 1) return PDE_E_BADARG;
+        if (misaligned(kVecAlign, y.M, y.alpha_base, y.beta_base, y.alpha_slope, y.beta_slope, y.states, y.gys, y.g_plane_sums,
+                       y.g_alpha_base, y.g_beta_base, y.g_alpha_slope, y.g_beta_slope, y.gM) ||
+            misaligned(4, y.skip_weight, y.weight_ptr, y.plane_sums, y.kappa_max, y.kappa_max_host, y.g_skip_weight, y.g_weight))
+            return PDE_E_BADARG;
+    }
+    const bool par = multi_parallel(L, d0) != 0;
+    for (int i = 0; i < L; ++i) {
+        const PdeSmallLayer& y = layers[i];
+        if (!y.steps_workspace || misaligned(kVecAlign, y.steps_workspace, y.workspace)) return PDE_E_WORKSPACE;
+        if (par && (!y.workspace ||
+                    y.workspace_bytes < pde_adi_small_backward_input_workspace_bytes(y.desc, y.sweeps_per_step)))
+            return PDE_E_WORKSPACE;
+    }
+    return PDE_OK;
+}
+
+static int dispatch_small_bwd_input(const PdeAdiDesc* d, int split, const SmallArgs& sa, size_t lds, hipStream_t st, bool emit) {
+    const int grid = small_grid(d) * (sa.par ? sa.L : 1);
+    switch (d->N) {
+#define PDE_SMALL_CASE(NN) case NN: return adi_launch_small_bwd_input_##NN(d->io_dtype, split, emit ? 1 : 0, &sa, grid, lds, st);
+        PDE_SMALL_N_LIST
+#undef PDE_SMALL_CASE
+    }
+    return PDE_E_UNSUPPORTED_N;
+}
+
+// gtraj / em as in small_backward_impl.  One launch, plus the combine launch when the layers ran side by side
+static int small_backward_input_impl(int32_t num_layers, const PdeSmallLayer* layers, const void* gy, void* gu, void* stream,
+                                     const void* gtraj, const uint64_t* em) {
+    int rc = multi_check_input(num_layers, layers);
+    if (rc != PDE_OK) return rc;
+    if (!gu || misaligned(kVecAlign, gy, gu, gtraj)) return PDE_E_BADARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const PdeAdiDesc* d0 = layers[0].desc;
+    const int sps = layers[0].sweeps_per_step;
+    SmallArgs sa{};
+    sa.gy = gy; sa.out = gu; sa.B = d0->B; sa.C = d0->C; sa.L = num_layers;
+    sa.par = multi_parallel(num_layers, d0);
+    if (em) { sa.traj = const_cast<void*>(gtraj); sa.em[0] = em[0]; sa.em[1] = em[1]; }
+    for (int i = 0; i < num_layers; ++i) {
+        const PdeSmallLayer& y = layers[i];
+        SmallLayer& sl = sa.layer[i];
+        small_fill(sl, y.desc, sps, y.mode, y.steps_workspace, y.M, y.skip_weight, y.weight, y.weight_ptr);
+        sl.gys = y.gys;
+        sl.roff = y.g_plane_sums;
+        sl.slab = sa.par ? y.workspace : nullptr;
+    }
+    rc = dispatch_small_bwd_input(d0, small_split(d0, sps), sa, small_lds_fwd(d0->C), st, em != nullptr);
+    if (rc == PDE_OK && sa.par) rc = combine_slabs(d0, sa, gu, st);
+    return rc;
+}
+
+int pde_adi_multi_backward_input(int32_t num_layers, const PdeSmallLayer* layers, const void* gy, void* gu, void* stream) {
+    return small_backward_input_impl(num_layers, layers, gy, gu, stream, nullptr, nullptr);
+}
+
+int pde_adi_small_backward_input(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode, const void* gy, const float* M,
+                                 const float* skip_weight, void* gu, const void* steps_workspace, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (!gy) return PDE_E_BADARG;
+    PdeSmallLayer l{};
+    l.desc = d; l.sweeps_per_step = sweeps_per_step; l.mode = mode; l.M = M; l.skip_weight = skip_weight;
+    l.weight = 1.0f; l.steps_workspace = const_cast<void*>(steps_workspace);
+    l.workspace = workspace; l.workspace_bytes = workspace_bytes;
+    return small_backward_input_impl(1, &l, gy, gu, stream, nullptr, nullptr);
+}
+
+int pde_adi_small_backward_input_states(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode, const void* gy,
+                                        const void* gtraj, const uint64_t emit_mask[2], const float* M, void* gu,
+                                        const void* steps_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    bool any;
+    const int rc = small_emit_check(d, sweeps_per_step, gtraj, emit_mask, any);
+    if (rc != PDE_OK) return rc;
+    if (!gy) return PDE_E_BADARG;
+    PdeSmallLayer l{};
+    l.desc = d; l.sweeps_per_step = sweeps_per_step; l.mode = mode; l.M = M;
+    l.weight = 1.0f; l.steps_workspace = const_cast<void*>(steps_workspace);
+    l.workspace = workspace; l.workspace_bytes = workspace_bytes;
+    return small_backward_input_impl(1, &l, gy, gu, stream, gtraj, any ? emit_mask : nullptr);
+}
+
+// The forward of a call whose backward will be the input one: nothing is parked, and y is the y of pde_adi_small_forward
+// WITH states.  fp32: the launch without states.  16-bit tensors: the kept-states forward goes on from the rounded sweep
+// output of every step, which the emitting kernel does with or without states — run it with an empty mask
+int pde_adi_small_forward_input(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode, const void* u, void* y,
+                                const float* M, const float* skip_weight, const float* alpha_base, const float* beta_base,
+                                const float* alpha_slope, const float* beta_slope, float* kappa_max, float* kappa_max_host,
+                                void* kappa_event, void* steps_workspace, size_t workspace_bytes, void* stream) {
+    static const uint64_t none[2] = {0, 0};
+    PdeSmallLayer l{};
+    l.desc = d; l.sweeps_per_step = sweeps_per_step; l.mode = mode; l.M = M; l.skip_weight = skip_weight;
+    l.alpha_base = alpha_base; l.beta_base = beta_base; l.alpha_slope = alpha_slope; l.beta_slope = beta_slope;
+    l.weight = 1.0f; l.steps_workspace = steps_workspace; l.steps_workspace_bytes = workspace_bytes;
+    l.kappa_max = kappa_max; l.kappa_max_host = kappa_max_host;
+    const bool round16 = d && d->io_dtype != PDE_IO_F32;
+    return small_forward_impl(1, &l, u, y, kappa_event, stream, nullptr, round16 ? none : nullptr);
+}
+
 int pde_adi_kappa_max(const PdeAdiDesc* d, const float* alpha_base, const float* beta_base, const float* alpha_slope,
                       const float* beta_slope, float* kappa_max, void* stream) {
     int rc = check_desc(d, true);

@@ -169,6 +169,20 @@ int PDE_CAT(adi_launch_small_bwd_emit_, PDE_INST_N)(int io, int split, const voi
     return io == PDE_IO_F32 ? small_bwd_io<PDE_INST_N, float, true>(split, sa, grid, lds, st)
                             : small_bwd_io<PDE_INST_N, bf16_t, true>(split, sa, grid, lds, st);
 }
+// the backward for the input alone (pde_adi_small_backward_input*, pde_adi_multi_backward_input); emit != 0: with the
+// emitted states' gradients
+int PDE_CAT(adi_launch_small_bwd_input_, PDE_INST_N)(int io, int split, int emit, const void* args, int grid, size_t lds,
+                                                     hipStream_t st) {
+    const SmallArgs& sa = *static_cast<const SmallArgs*>(args);
+    if (emit) {
+        if (io == PDE_IO_F16) return small_bwd_input_io<PDE_INST_N, half_t, true>(split, sa, grid, lds, st);
+        return io == PDE_IO_F32 ? small_bwd_input_io<PDE_INST_N, float, true>(split, sa, grid, lds, st)
+                                : small_bwd_input_io<PDE_INST_N, bf16_t, true>(split, sa, grid, lds, st);
+    }
+    if (io == PDE_IO_F16) return small_bwd_input_io<PDE_INST_N, half_t>(split, sa, grid, lds, st);
+    return io == PDE_IO_F32 ? small_bwd_input_io<PDE_INST_N, float>(split, sa, grid, lds, st)
+                            : small_bwd_input_io<PDE_INST_N, bf16_t>(split, sa, grid, lds, st);
+}
 #endif
 
 #ifdef PDE_INST_WIDE

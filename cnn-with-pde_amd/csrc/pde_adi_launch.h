@@ -36,13 +36,15 @@ PDE_DECLARE_N(8) PDE_DECLARE_N(12) PDE_DECLARE_N(16) PDE_DECLARE_N(20) PDE_DECLA
 #undef PDE_DECLARE_N
 
 // whole-layer kernels for C <= 4 (pde_adi_small.h), instantiated for the line lengths below.  _emit: the variants that
-// write / read the states after chosen time steps (SmallArgs::traj, SmallArgs::em)
+// write / read the states after chosen time steps (SmallArgs::traj, SmallArgs::em).  _bwd_input: the backward for the
+// input alone (emit != 0: with the emitted states' gradients), with the forward's LDS
 #define PDE_SMALL_N_LIST PDE_SMALL_CASE(16) PDE_SMALL_CASE(28) PDE_SMALL_CASE(32)
 #define PDE_SMALL_CASE(NN)                                                                                \
     int adi_launch_small_fwd_##NN(int io, int split, const void* args, int grid, size_t lds, hipStream_t st); \
     int adi_launch_small_bwd_##NN(int io, int split, const void* args, int grid, size_t lds, hipStream_t st); \
     int adi_launch_small_fwd_emit_##NN(int io, int split, const void* args, int grid, size_t lds, hipStream_t st); \
-    int adi_launch_small_bwd_emit_##NN(int io, int split, const void* args, int grid, size_t lds, hipStream_t st);
+    int adi_launch_small_bwd_emit_##NN(int io, int split, const void* args, int grid, size_t lds, hipStream_t st); \
+    int adi_launch_small_bwd_input_##NN(int io, int split, int emit, const void* args, int grid, size_t lds, hipStream_t st);
 PDE_SMALL_N_LIST
 #undef PDE_SMALL_CASE
 

@@ -544,6 +544,186 @@ __global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_bwd_kernel(SmallArg
     dma_wait_all();
 }
 
+// ---- backward for the input alone (pde_adi_small_backward_input*, pde_adi_multi_backward_input) ----------------
+// gu = F^T gy of a layer (or a shared-input group) whose parameters take no gradient: the reverse walk of
+// adi_small_bwd_kernel with everything but the adjoint removed.  The launch shape, the layer loop, par, the weights, gys,
+// the plane-sum cotangents, the skip split and the running sum of gu over the layers are the full kernel's.  A sweep
+// stages the window JN | E | INVB of its record (as long as the forward's INV | JN | E: the ring has the forward's
+// slots) and runs solve_adj, with the re-layout where the axis is y; at a step boundary ONE image per wave carries the
+// adjoints and every lane applies its column of the operator.  Neither u, states nor ckpt is read, neither part nor
+// gm_part written, and no clamp-mask flag is looked at.
+// Per plane the operations on the adjoint are those of adi_small_bwd_kernel in its order, so gu is the full kernel's bit
+// for bit.  EMIT: a.traj[slot(k)] joins the adjoint at the top of reverse step k, as there.
+template <int N, typename IO, int SPLIT, bool EMIT = false>
+__global__ __launch_bounds__(64 * kSmallMaxC) void adi_small_bwd_input_kernel(SmallArgs a) {
+    constexpr int M = Geo<N>::M;
+    constexpr int SPS = SPLIT == kSplitStrang ? 3 : 2;
+    constexpr int RECP = kRecFwdPad;
+    static_assert(SPLIT == kSplitStrang || SPLIT == kSplitLie, "step pattern must be known");
+    static_assert(kRecFwd == kB_Inv + kImage, "JN | E | INVB is as long as the forward's window");
+    static_assert(kBwdOff + kRecFwdPad <= kRecStride, "the padded window must stay inside the record");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, c = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hf = lane >> 5, l = lane & 31;
+    const int nC = a.C;
+    float* ring = smem + (size_t)c * 2 * RECP;                            // wave-private [2][RECP]
+    const unsigned ring_lds = lds_byte_address(smem) + (unsigned)c * 2u * RECP * 4u;
+    float* imgs = smem + (size_t)nC * 2 * RECP;                           // [C][kImage]: plane I/O, re-layout, exchange
+    float* T = imgs + (size_t)c * kImage;
+    for (int e = lane; e < kImage; e += 64) T[e] = 0.f;
+    const IO* gy = static_cast<const IO*>(a.gy);
+    IO* gu = static_cast<IO*>(a.out);
+    const size_t tens = (size_t)a.B * nC * N * N;
+    const bool live = l < N;
+
+    auto dma_rec = [&](int slot, const float* coef, int s) __attribute__((always_inline)) {
+        const float* rec = coef + ((size_t)s * nC + c) * kRecStride + kBwdOff;
+#pragma unroll
+        for (int p = 0; p < RECP / 256; ++p) {
+            const int f = p * 64 + lane;
+            if (f < kRecFwd / 4) lds_dma16_a(rec + p * 256, 16u * lane, ring_lds + ((unsigned)slot * RECP + p * 256u) * 4u);
+        }
+    };
+
+    const int lsel = a.par ? (int)(blockIdx.x % (unsigned)a.L) : -1;
+    const int b0 = a.par ? (int)(blockIdx.x / (unsigned)a.L) : (int)blockIdx.x;
+    const int bstep = a.par ? (int)(gridDim.x / (unsigned)a.L) : (int)gridDim.x;
+    int cur = 0;
+    dma_rec(0, small_layer(lsel < 0 ? 0 : lsel)->coef, small_layer(lsel < 0 ? 0 : lsel)->K * SPS - 1);
+    for (int li = 0; li < a.L; ++li) {
+        if (lsel >= 0 && li != lsel) continue;
+        const ConstLayer Lp = small_layer(li);
+        const float* coef = Lp->coef;
+        const float* Mp = Lp->M;
+        const float* skp = Lp->skip_w;
+        const IO* gys = static_cast<const IO*>(Lp->gys);
+        const float* roff = Lp->roff;
+        const int K = Lp->K, mode = Lp->mode, S = K * SPS;
+        const float* wpp = Lp->wp;
+        const float wl = wpp ? *wpp : Lp->w, step_scale = Lp->step_scale;
+        const bool last_layer = li + 1 == a.L || lsel >= 0;
+        const ConstLayer Ln = small_layer(last_layer ? 0 : li + 1);
+        IO* gul = lsel >= 0 ? static_cast<IO*>(Lp->slab) : gu;             // where my term of the input gradient goes
+        const float* coef_next = Ln->coef;
+        const int s_next = Ln->K * SPS - 1;
+        float mcol[kSmallMaxC];                                           // my column of the operator
+#pragma unroll
+        for (int j = 0; j < kSmallMaxC; ++j) mcol[j] = (j < nC) ? Mp[j * nC + c] : 0.f;
+        const float sk = skp ? sigmoid_f(*skp) : 0.f;
+
+        // adjoint of v = M w at a step boundary: r <- sum_i M[i][c] r_i, the adjoints through the waves' images
+        auto mix_adjoint = [&](float (&r)[M]) __attribute__((always_inline)) {
+            image_put<M>(T, l, hf, r);
+            __syncthreads();
+            float racc[M];
+#pragma unroll
+            for (int k = 0; k < M; ++k) racc[k] = 0.f;
+#pragma unroll
+            for (int j = 0; j < kSmallMaxC; ++j) {
+                if (j < nC) {
+                    float o[M];
+                    image_get<M>(imgs + (size_t)j * kImage, l, hf, o);
+#pragma unroll
+                    for (int k = 0; k < M; ++k) racc[k] = fmaf(mcol[j], o[k], racc[k]);
+                }
+            }
+            __syncthreads();                                              // everyone has read: the images are free again
+#pragma unroll
+            for (int k = 0; k < M; ++k) r[k] = racc[k];
+        };
+
+        for (int b = b0; b < a.B; b += bstep) {
+            const bool last_sample = b + bstep >= a.B;
+            float r[M], gsk[M], g0[M];
+            if (gy != nullptr) small_load<N, 0, IO>(gy, b, nC, c, lane, l, hf, T, g0);
+            else {
+#pragma unroll
+                for (int k = 0; k < M; ++k) g0[k] = 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k < M; ++k) r[k] = wl * g0[k];                // out = sum_i w_i y_i
+            if (gys != nullptr) {                                         // ... plus what arrives at y_i itself
+                float gi[M];
+                small_load<N, 0, IO>(gys, b, nC, c, lane, l, hf, T, gi);
+#pragma unroll
+                for (int k = 0; k < M; ++k) r[k] += gi[k];
+            }
+            if (roff != nullptr) {                                        // ... and at its spatial sum (the average pool)
+                const float ro = live ? roff[(size_t)b * nC + c] : 0.f;
+#pragma unroll
+                for (int k = 0; k < M; ++k) r[k] += ro;
+            }
+#pragma unroll
+            for (int k = 0; k < M; ++k) { gsk[k] = sk * r[k]; r[k] = (1.0f - sk) * r[k]; }     // sk = 0 without a skip blend
+            // The full kernel also reads gsk inside the time loop (the skip-weight term), so it forms the products here and
+            // adds them behind the loop.  Here nothing else reads them: left alone hipcc moves the multiply down to the add
+            // and contracts the two into one fma, which rounds once where the full kernel rounds twice.  Pin the products.
+#pragma unroll
+            for (int k = 0; k < M; ++k) asm volatile("" : "+v"(gsk[k]));
+            int eslot = EMIT ? ck_slot(a.em, K) : 0;                      // EMIT: one behind the newest slot of a.traj
+            for (int k = K - 1; k >= 0; --k) {
+                if constexpr (EMIT) {
+                    if (ck_bit(a.em, k)) {                                // dL/d(state after step k); T is free here
+                        float gi[M];
+                        --eslot;
+                        small_load<N, 0, IO>(static_cast<const IO*>(a.traj) + (size_t)eslot * tens, b, nC, c, lane, l, hf, T, gi);
+#pragma unroll
+                        for (int q = 0; q < M; ++q) r[q] += gi[q];
+                    }
+                }
+                if (mode == 2) mix_adjoint(r);                            // SVHN: the coupling came after the sweeps
+                sfor<0, SPS>([&](auto SI) __attribute__((always_inline)) {
+                    constexpr int si = SPS - 1 - decltype(SI)::value;     // newest sweep of the step first
+                    constexpr int AX = (si == 1) ? PDE_AXIS_Y : PDE_AXIS_X;
+                    const int s = k * SPS + si;
+                    dma_wait_all();
+                    __builtin_amdgcn_wave_barrier();
+                    // The DMA below overwrites the slot the previous sweep read its rows from: every LDS read of this wave
+                    // has to be served before it is issued (nothing else orders an LDS-DMA behind a pending ds_read).
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    // next record: of this sample, of my next sample, or of the next layer's first sample
+                    if (s > 0) dma_rec(cur ^ 1, coef, s - 1);
+                    else if (!last_sample) dma_rec(cur ^ 1, coef, S - 1);
+                    else if (!last_layer) dma_rec(cur ^ 1, coef_next, s_next);
+                    const float* rec = ring + (size_t)cur * RECP;
+                    const float* crow = rec + l * kLineStride + hf * kHalfPad;
+                    const float cjn = rec[kB_Jn + l];
+                    float ce[M], cinv[M];
+                    if (AX == PDE_AXIS_Y) relayout<N, 0>(r, T, l, hf);
+                    load_half<M>(crow + kB_E, ce);
+                    load_half<M>(crow + kB_Inv, cinv);
+                    solve_adj<M, 1>(r, ce, cinv, cjn, hf);
+                    if (AX == PDE_AXIS_Y) relayout<N, 0>(r, T, l, hf);
+                    // The next sweep's first act is a DMA into the slot just read, and nothing orders an LDS-DMA behind a
+                    // ds_read that has been issued but not served.  The solve above consumes every row read from the slot,
+                    // so it has to stay above that DMA: left alone hipcc lifts the five row reads to the top of the sweep and
+                    // lets the arithmetic sink below the next wait and DMA issue, and with two workgroups on a CU (the second
+                    // finds the records in the L1 the first has just filled) the DMA then lands before the reads are served.
+                    // The full kernel and the forward do not meet this: their sweeps read rows all the way through.
+                    // The wait at the top of a sweep states the requirement; keeping the solve up here is what makes that
+                    // wait find the reads already served instead of stalling on them.
+#pragma unroll
+                    for (int q = 0; q < M; ++q) asm volatile("" : "+v"(r[q]));
+                    cur ^= 1;
+                });
+#pragma unroll
+                for (int q = 0; q < M; ++q) r[q] *= step_scale;          // the (1+eps) carried by every adjoint solve
+                if (mode == 1) mix_adjoint(r);                            // cifar10: the mixing came before the sweeps
+            }
+#pragma unroll
+            for (int q = 0; q < M; ++q) r[q] += gsk[q];                  // the skip branch's share of dL/du
+            if (li > 0 && lsel < 0) {                                     // gu = sum over the layers: my own earlier store
+                float o[M];
+                small_load<N, 0, IO>(gu, b, nC, c, lane, l, hf, T, o);
+#pragma unroll
+                for (int q = 0; q < M; ++q) r[q] += o[q];
+            }
+            small_store<N, 0, IO>(gul, b, nC, c, lane, l, hf, T, r);
+        }
+    }
+    dma_wait_all();
+}
+
 template <typename IO>
 int small_combine_io(const CombineArgs& ca, hipStream_t st) {
     hipLaunchKernelGGL(small_combine_kernel<IO>, dim3((unsigned)((ca.n4 + 255) / 256)), dim3(256), 0, st, ca);
@@ -571,6 +751,18 @@ int small_bwd_io(int split, const SmallArgs& sa, int grid, size_t lds, hipStream
     } else {
         if (ensure_dynamic_lds((const void*)adi_small_bwd_kernel<N, IO, kSplitLie, EMIT>, (int)lds, cfg[1]) != PDE_OK) return PDE_E_LAUNCH;
         hipLaunchKernelGGL((adi_small_bwd_kernel<N, IO, kSplitLie, EMIT>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
+    }
+    return check_launch();
+}
+template <int N, typename IO, bool EMIT = false>
+int small_bwd_input_io(int split, const SmallArgs& sa, int grid, size_t lds, hipStream_t st) {
+    static unsigned long long cfg[2] = {0, 0};
+    if (split == kSplitStrang) {
+        if (ensure_dynamic_lds((const void*)adi_small_bwd_input_kernel<N, IO, kSplitStrang, EMIT>, (int)lds, cfg[0]) != PDE_OK) return PDE_E_LAUNCH;
+        hipLaunchKernelGGL((adi_small_bwd_input_kernel<N, IO, kSplitStrang, EMIT>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
+    } else {
+        if (ensure_dynamic_lds((const void*)adi_small_bwd_input_kernel<N, IO, kSplitLie, EMIT>, (int)lds, cfg[1]) != PDE_OK) return PDE_E_LAUNCH;
+        hipLaunchKernelGGL((adi_small_bwd_input_kernel<N, IO, kSplitLie, EMIT>), dim3(grid), dim3(64 * sa.C), lds, st, sa);
     }
     return check_launch();
 }

@@ -697,7 +697,13 @@ class _AdiMixedFn(torch.autograd.Function):
 class _AdiSmallFn(torch.autograd.Function):
     """A layer with a channel operator between its time steps at C <= 4, whole time loop in ONE launch per pass
     (pde_adi_small_*): cifar10.py:84-112 ("pre"), SVHN.py:55-76 ("post", with the skip blend when ``skip_weight``
-    is given).  The sweep output of every step is kept for the backward, as autograd keeps it in the reference."""
+    is given).  The sweep output of every step is kept for the backward, as autograd keeps it in the reference.
+
+    When ``u`` needs a gradient and neither a coefficient tensor, ``M`` nor ``skip_weight`` does, the forward is
+    ``pde_adi_small_forward_input`` and the backward ``pde_adi_small_backward_input``: gu = F^T gy alone, bitwise the full
+    backward's gu.  No (K, B, C, N, N) tensor is allocated, ``u`` is not saved, ``checkpoints`` is ignored and no
+    coefficient maxima are asked for unless a ``kmax_sink`` was handed in; ``M``, ``skip_weight`` and the steps workspace
+    stay alive.  ``PDE_BWD_INPUT=0`` keeps the full backward for such calls."""
 
     @staticmethod
     def forward(ctx, u, ab, bb, asl, bsl, M, skip_weight, steps, mode, smooth3, clamp_max, eps, ckpt, kmax_sink):
@@ -715,20 +721,32 @@ class _AdiSmallFn(torch.autograd.Function):
         d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
         sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
         need_grad = any(ctx.needs_input_grad[:7])
-        want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
+        input_only = ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:7]) and L.bwd_input_enabled()
+        if input_only:
+            want_kmax = kmax_sink is not None
+        else:
+            want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
         kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
-        states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if need_grad else None
+        states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if need_grad and not input_only else None
         y = torch.empty_like(u)
         with torch.cuda.device(u.device):
             tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            L.check(lib.pde_adi_small_forward(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(y), _ptr(states),
-                                              _ptr(Mf), _ptr(sw), *[_ptr(t) for t in p], _ptr(kdev),
-                                              _ptr(tk.host if tk else None), C.c_void_p(tk.event.cuda_event if tk else 0),
-                                              _ptr(sws), sws.numel(), _stream()), "pde_adi_small_forward")
+            tail = (*[_ptr(t) for t in p], _ptr(kdev), _ptr(tk.host if tk else None),
+                    C.c_void_p(tk.event.cuda_event if tk else 0), _ptr(sws), sws.numel(), _stream())
+            if input_only:                               # parks nothing, y as with states kept
+                L.check(lib.pde_adi_small_forward_input(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(y), _ptr(Mf),
+                                                        _ptr(sw), *tail), "pde_adi_small_forward_input")
+            else:
+                L.check(lib.pde_adi_small_forward(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(y), _ptr(states),
+                                                  _ptr(Mf), _ptr(sw), *tail), "pde_adi_small_forward")
             ctx.kmax = tk
             if want_kmax and kmax_sink is not None:
                 kmax_sink.append(tk)
-        if need_grad:
+        ctx.input_only = (u.shape, u.dtype, u.device) if input_only else None
+        if input_only:
+            ctx.save_for_backward(Mf, sw)
+            ctx.sws = sws
+        elif need_grad:
             ctx.save_for_backward(u, states, Mf, sw, *p)
             ctx.sws = sws
         ctx.cfg = (steps, mode, smooth3, clamp_max, eps, ckpt)
@@ -738,8 +756,27 @@ class _AdiSmallFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    def _backward_input(ctx, gy):
+        """The backward of a call whose parameters take no gradient: ``pde_adi_small_backward_input``."""
+        lib = L.load()
+        Mf, sw = ctx.saved_tensors
+        steps, mode, smooth3, clamp_max, eps, _ = ctx.cfg
+        shape, dtype, device = ctx.input_only
+        B, Cc, N, _ = shape
+        g_in = _aligned(gy.to(dtype).contiguous())
+        d = _make_desc(B, Cc, N, _io_dtype(g_in), steps.flat, smooth3, clamp_max, eps)
+        gu = torch.empty_like(g_in)
+        with torch.cuda.device(device):
+            L.check(lib.pde_adi_small_backward_input(C.byref(d), len(steps[0]), 1 if mode == "pre" else 2, _ptr(g_in), _ptr(Mf),
+                                                     _ptr(sw), _ptr(gu), _ptr(ctx.sws), None, 0, _stream()),
+                    "pde_adi_small_backward_input")
+        return (gu,) + (None,) * 13
+
+    @staticmethod
     def backward(ctx, gy):
         lib = L.load()
+        if ctx.input_only is not None:
+            return _AdiSmallFn._backward_input(ctx, gy)
         u, states, Mf, sw, *p = ctx.saved_tensors
         steps, mode, smooth3, clamp_max, eps, ckpt = ctx.cfg
         B, Cc, N, _ = u.shape
@@ -773,7 +810,13 @@ class _AdiSmallFn(torch.autograd.Function):
 class _AdiMultiFn(torch.autograd.Function):
     """Several mixing-first layers (cifar10.EnhancedDiffusionLayer / cifar_2version.LearnableDiffusionLayer, C <= 4)
     on the SAME input in one launch per pass (pde_adi_multi_*): cifar10.py:272-280, cifar_2version.py:287-288.
-    Returns (sum_i w_i y_i, y_1, ..., y_L); the y_i are the last sweep outputs the kernel keeps anyway."""
+    Returns (sum_i w_i y_i, y_1, ..., y_L); the y_i are the last sweep outputs the kernel keeps anyway.
+
+    With frozen parameters (``u`` needs a gradient; no coefficient tensor, ``M`` or ``weights`` does) the backward is
+    ``pde_adi_multi_backward_input``: one launch, plus the combine launch side by side — no pre-pass, no parameter-gradient
+    epilogue, no wait for the coefficient maxima, which are not asked for.  The forward is unchanged: the ``y_i`` are the
+    last kept states, so the states are written as before (the node just does not hold them).
+    ``PDE_BWD_INPUT=0`` keeps the full backward."""
 
     @staticmethod
     def forward(ctx, u, weights, specs, want_sums, ckpt, *flat):
@@ -785,7 +828,9 @@ class _AdiMultiFn(torch.autograd.Function):
             u = u.float()
         u = _aligned(u.contiguous())
         need_grad = any(ctx.needs_input_grad)
-        want_kmax = need_grad and ckpt == "auto"
+        input_only = (ctx.needs_input_grad[0] and not ctx.needs_input_grad[1] and not any(ctx.needs_input_grad[5:])
+                      and L.bwd_input_enabled())
+        want_kmax = need_grad and ckpt == "auto" and not input_only
         if ckpt != "auto" and not isinstance(ckpt, (tuple, list)):
             ckpt = (int(ckpt),) * nl                      # one step-local mask for every layer
         if ckpt != "auto" and len(ckpt) != nl:
@@ -832,21 +877,66 @@ class _AdiMultiFn(torch.autograd.Function):
         # the input, the parameter views and the operators go through save_for_backward (an in-place change of any of them
         # between forward and backward then raises torch's version-counter error instead of giving gradients that mix the
         # forward's factorisation with new parameter values); workspaces, states and tickets stay on ctx
-        saved = [u] + ([wdev] if wdev is not None else [])
-        for k in keep:
-            saved += list(k[0]) + [k[1]]
-        ctx.save_for_backward(*saved)
-        ctx.keep, ctx.descs, ctx.per = [k[2:] for k in keep], descs, per
+        ctx.input_only = (u.shape, u.dtype, u.device) if input_only else None
+        if input_only:                                     # the operators, the weights and the factorisations only
+            ctx.save_for_backward(*([wdev] if wdev is not None else []), *[k[1] for k in keep])
+            ctx.keep, ctx.descs, ctx.per = [(k[2],) for k in keep], descs, per
+        else:
+            saved = [u] + ([wdev] if wdev is not None else [])
+            for k in keep:
+                saved += list(k[0]) + [k[1]]
+            ctx.save_for_backward(*saved)
+            ctx.keep, ctx.descs, ctx.per = [k[2:] for k in keep], descs, per
         ctx.has_w = weights is not None
         ctx.want_sums = want_sums
         ys = [k[3][-1] for k in keep]                      # the last sweep output of every layer
         return (out, *ys, *sums) if want_sums else (out, *ys)
 
     @staticmethod
+    def _backward_input(ctx, gout, gys, gsums):
+        """The backward of a group whose parameters take no gradient: ``pde_adi_multi_backward_input``."""
+        lib = L.load()
+        nl = len(ctx.per)
+        shape, dtype, device = ctx.input_only
+        saved = ctx.saved_tensors
+        wdev = saved[0] if ctx.has_w else None
+        Ms = saved[1 if ctx.has_w else 0:]
+        arr = (L.PdeSmallLayer * nl)()
+        hold = []
+        gout_c = None if gout is None else _aligned(gout.to(dtype).contiguous())
+        for i in range(nl):
+            (sws,) = ctx.keep[i]
+            d, sps = ctx.descs[i], ctx.per[i][0]
+            # (the slab of a side-by-side group; the query is what the library checks against, used or not)
+            ws = _workspace(lib.pde_adi_small_backward_input_workspace_bytes(C.byref(d), sps), device) if nl > 1 else None
+            gyi = None if gys[i] is None else _aligned(gys[i].to(dtype).contiguous())
+            gsi = None if gsums[i] is None else _aligned(gsums[i].to(torch.float32).contiguous())
+            a = arr[i]
+            a.desc, a.sweeps_per_step, a.mode = C.pointer(d), sps, 1
+            a.M = Ms[i].data_ptr()
+            a.weight = 0.0
+            a.weight_ptr = None if wdev is None else wdev.data_ptr() + 4 * i
+            a.steps_workspace, a.steps_workspace_bytes = sws.data_ptr(), sws.numel()
+            a.gys = gyi.data_ptr() if gyi is not None else None
+            a.g_plane_sums = gsi.data_ptr() if gsi is not None else None
+            if ws is not None:
+                a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+            hold.append((ws, gyi, gsi))
+        if gout_c is None and all(h[1] is None and h[2] is None for h in hold):
+            raise L.PdeError("adi_diffuse_multi: no incoming gradient")
+        gu = torch.empty(shape, dtype=dtype, device=device)
+        with torch.cuda.device(device):
+            L.check(lib.pde_adi_multi_backward_input(nl, arr, _ptr(gout_c), _ptr(gu), _stream()),
+                    "pde_adi_multi_backward_input")
+        return (gu,) + (None,) * (4 + 5 * nl)
+
+    @staticmethod
     def backward(ctx, gout, *gall):
         lib = L.load()
         nl = len(ctx.per)
         gys, gsums = gall[:nl], (gall[nl:] if ctx.want_sums else (None,) * nl)
+        if ctx.input_only is not None:
+            return _AdiMultiFn._backward_input(ctx, gout, gys, gsums)
         saved = ctx.saved_tensors
         u = saved[0]
         wdev = saved[1] if ctx.has_w else None
@@ -1169,7 +1259,10 @@ def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coe
 class _AdiSmallStatesFn(torch.autograd.Function):
     """``_AdiSmallFn`` without the skip blend that also returns the state after chosen time steps, out of the same launch
     per pass (pde_adi_small_forward_states / pde_adi_small_backward_states).  The result is ONE tensor (K', B, C, N, N);
-    the library's ``y`` is its last slice."""
+    the library's ``y`` is its last slice.
+
+    With frozen parameters (see ``_AdiSmallFn``) the forward keeps no states — the emitting forward with ``states`` NULL,
+    or ``pde_adi_small_forward_input`` for an empty mask — and the backward is ``pde_adi_small_backward_input_states``."""
 
     @staticmethod
     def forward(ctx, u, ab, bb, asl, bsl, M, steps, emit, mode, smooth3, clamp_max, eps, ckpt, kmax_sink):
@@ -1186,27 +1279,39 @@ class _AdiSmallStatesFn(torch.autograd.Function):
         d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
         sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
         need_grad = any(ctx.needs_input_grad[:6])
-        want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
+        input_only = ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:6]) and L.bwd_input_enabled()
+        if input_only:
+            want_kmax = kmax_sink is not None
+        else:
+            want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
         kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
         Ke = len(emit)
         out = torch.empty((Ke,) + tuple(u.shape), dtype=u.dtype, device=u.device)
         bits = sum(1 << k for k in emit[:-1])
         # an empty mask is the plain call, which goes on from the rounded sweep outputs of 16-bit tensors only when it
         # keeps them: keep them then, so that the result is the same tensor in grad mode and without
-        keep = need_grad or (bits == 0 and u.element_size() < 4)
+        keep = not input_only and (need_grad or (bits == 0 and u.element_size() < 4))
         states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if keep else None
         em = _mask128(bits)
         with torch.cuda.device(u.device):
             tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            L.check(lib.pde_adi_small_forward_states(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(out[Ke - 1]),
-                                                     _ptr(states), _ptr(out), em, _ptr(Mf), *[_ptr(t) for t in p], _ptr(kdev),
-                                                     _ptr(tk.host if tk else None),
-                                                     C.c_void_p(tk.event.cuda_event if tk else 0),
-                                                     _ptr(sws), sws.numel(), _stream()), "pde_adi_small_forward_states")
+            tail = (*[_ptr(t) for t in p], _ptr(kdev), _ptr(tk.host if tk else None),
+                    C.c_void_p(tk.event.cuda_event if tk else 0), _ptr(sws), sws.numel(), _stream())
+            if input_only and bits == 0:                 # the plain call that rounds as if it kept its states
+                L.check(lib.pde_adi_small_forward_input(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(out[Ke - 1]),
+                                                        _ptr(Mf), None, *tail), "pde_adi_small_forward_input")
+            else:
+                L.check(lib.pde_adi_small_forward_states(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u),
+                                                         _ptr(out[Ke - 1]), _ptr(states), _ptr(out), em, _ptr(Mf), *tail),
+                        "pde_adi_small_forward_states")
             ctx.kmax = tk
             if want_kmax and kmax_sink is not None:
                 kmax_sink.append(tk)
-        if need_grad:
+        ctx.input_only = (u.shape, u.dtype, u.device) if input_only else None
+        if input_only:
+            ctx.save_for_backward(Mf)
+            ctx.sws = sws
+        elif need_grad:
             ctx.save_for_backward(u, states, Mf, *p)
             ctx.sws = sws
         ctx.cfg = (steps, mode, smooth3, clamp_max, eps, ckpt, bits, Ke)
@@ -1215,8 +1320,28 @@ class _AdiSmallStatesFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    def _backward_input(ctx, g):
+        """The backward of a call whose parameters take no gradient: ``pde_adi_small_backward_input_states``."""
+        lib = L.load()
+        (Mf,) = ctx.saved_tensors
+        steps, mode, smooth3, clamp_max, eps, _, ebits, Ke = ctx.cfg
+        shape, dtype, device = ctx.input_only
+        B, Cc, N, _ = shape
+        g = _aligned(g.to(dtype).contiguous())
+        d = _make_desc(B, Cc, N, _io_dtype(g), steps.flat, smooth3, clamp_max, eps)
+        gu = torch.empty(shape, dtype=dtype, device=device)
+        with torch.cuda.device(device):
+            L.check(lib.pde_adi_small_backward_input_states(C.byref(d), len(steps[0]), 1 if mode == "pre" else 2,
+                                                            _ptr(g[Ke - 1]), _ptr(g), _mask128(ebits), _ptr(Mf), _ptr(gu),
+                                                            _ptr(ctx.sws), None, 0, _stream()),
+                    "pde_adi_small_backward_input_states")
+        return (gu,) + (None,) * 13
+
+    @staticmethod
     def backward(ctx, g):
         lib = L.load()
+        if ctx.input_only is not None:
+            return _AdiSmallStatesFn._backward_input(ctx, g)
         u, states, Mf, *p = ctx.saved_tensors
         steps, mode, smooth3, clamp_max, eps, ckpt, ebits, Ke = ctx.cfg
         B, Cc, N, _ = u.shape

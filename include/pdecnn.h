@@ -1012,6 +1012,9 @@ int pde_adi_rect_f64_backward_input_states(const PdeAdiRectDescF64* d, const dou
                                            const void* fwd_workspace, void* workspace, size_t workspace_bytes,
                                            void* stream);
 
+/* The same for the one-launch C <= 4 layers (the K1 calls above and their shared-input groups): declared in
+ * pdecnn_small_input.h, which this header includes below. */
+
 /* ---- utilities ------------------------------------------------------------------------- */
 
 /* Average device time (ms) per launch of the dominant kernel of the most recent
@@ -1021,6 +1024,8 @@ int pde_timing_enable(int32_t on);
 int pde_timing_read(double* fwd_ms_sum, int64_t* fwd_launches, double* bwd_ms_sum, int64_t* bwd_launches);
 
 const char* pde_version(void);
+
+#include "pdecnn_small_input.h"
 
 #ifdef __cplusplus
 }
