@@ -1,7 +1,9 @@
 // Native host path of the launch-bound layer calls: the autograd node of one implicit diffusion layer
 // (functional.adi_diffuse: mnist_test.py:44-198, fashion_mnist.py:18-196, the C = 1 shapes the reference trains on) written
 // against torch's C++ autograd and the C ABI of include/pdecnn.h.  Same calls, same arguments and the same order of
-// launches as functional._AdiFn (which stays the general path: coefficient-maxima sinks, lagged plans); what goes is the
+// launches as functional._AdiFn (which stays the general path: coefficient-maxima sinks, lagged plans), and likewise for
+// the layers with a channel operator (SmallFn, MixedFn, MultiFn against functional._AdiSmallFn, _AdiMixedFn, _AdiMultiFn:
+// the helpers ahead of the nodes mirror functional.py's, decision by decision); what goes is the
 // interpreter between them — at (64,1,28,28) the kernels of a forward + backward take 0.1 ms on the device and the Python
 // around them 0.17 ms on the host.
 //
@@ -225,6 +227,164 @@ int64_t adi_grad_mode(const Tensor& u, const Tensor& ab, const Tensor& bb, const
     return grad_mode_of(u, ab.requires_grad() || bb.requires_grad() || asl.requires_grad() || bsl.requires_grad());
 }
 
+// ---- what the four nodes below share: each decision is taken in one place (functional.py cuts its nodes the same way;
+// tests/test_gpu_node_calls.py holds the two mirrors to the same bits) ---------------------------------------------------
+void require_cuda(std::initializer_list<const Tensor*> ts) {
+    for (const Tensor* t : ts)
+        PDE_REQUIRE(!t->defined() || t->is_cuda(), "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
+}
+
+float* fptr(const Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+void* vptr(const Tensor& t) { return t.defined() ? t.data_ptr() : nullptr; }
+// the four coefficient views (or their gradients) as the C ABI takes them, one argument each
+#define PDE_F4(p) (p)[0].data_ptr<float>(), (p)[1].data_ptr<float>(), (p)[2].data_ptr<float>(), (p)[3].data_ptr<float>()
+
+// The tensor's device made current and torch's current stream on it.  A backward runs on autograd's worker thread: it
+// sets the device and fetches the stream again.
+struct OnDevice {
+    c10::hip::HIPGuardMasqueradingAsCUDA guard;
+    hipStream_t st;
+    explicit OnDevice(const Tensor& t)
+        : guard(t.device()), st(c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream()) {}
+};
+
+// The head of every forward: the input as the kernels take it (cut from the graph, widened when it is no I/O type,
+// contiguous, aligned), its device and stream, and per layer the caller's descriptor held to the tensor and the four
+// coefficient views.  MultiFn has several layers on one input and calls layer() for each.
+struct Prologue {
+    Tensor u;
+    OnDevice dev;
+    PdeAdiDesc d;
+    Tensor p[4];
+    static Tensor input(const Tensor& u_in) {
+        Tensor u = u_in.detach();
+        if (!io_type(u)) u = u.to(at::kFloat);
+        return aligned(u.contiguous());
+    }
+    explicit Prologue(const Tensor& u_in) : u(input(u_in)), dev(u) {}
+    Prologue(const Tensor& u_in, const Tensor& ab, const Tensor& bb, const Tensor& asl, const Tensor& bsl, int64_t desc_addr)
+        : Prologue(u_in) {
+        layer(desc_addr, ab, bb, asl, bsl, &d, p);
+    }
+    void layer(int64_t desc_addr, const Tensor& ab, const Tensor& bb, const Tensor& asl, const Tensor& bsl, PdeAdiDesc* dd,
+               Tensor* pp) const {
+        std::memcpy(dd, reinterpret_cast<const void*>(desc_addr), sizeof(*dd));
+        const int64_t C = u.size(1), N = u.size(2);
+        PDE_REQUIRE(dd->B == u.size(0) && dd->C == C && dd->N == N && dd->io_dtype == io_of(u),
+                    "descriptor does not match the tensor");
+        pp[0] = as_chw(ab, C, N);
+        pp[1] = as_chw(bb, C, N);
+        pp[2] = as_chw(asl, C, N);
+        pp[3] = as_chw(bsl, C, N);
+    }
+};
+
+// A forward's request for its per-sweep coefficient maxima: the device buffer, a pinned slot with its event, and (unless
+// the caller owns the slot: adi_lagged) the ticket that hands the slot back when the node dies.  All NULL when not wanted.
+struct Kmax {
+    Tensor kdev, ticket;
+    Slot* slot = nullptr;
+    Kmax(bool want, int n, const Tensor& u, bool own_ticket = true) {
+        if (!want) return;
+        kdev = at::empty({(int64_t)n}, u.options().dtype(at::kFloat));
+        slot = acquire_slot(u.device().index());
+        if (own_ticket) ticket = slot_ticket(slot, n);
+    }
+    float* dev() const { return fptr(kdev); }
+    float* host() const { return slot ? slot->host : nullptr; }
+    void* event() const { return slot ? (void*)slot->ev : nullptr; }
+    void save(AutogradContext* ctx) const {
+        if (ticket.defined()) {
+            ctx->saved_data["ticket"] = ticket;
+            ctx->saved_data["slot"] = (int64_t) reinterpret_cast<intptr_t>(slot);
+        }
+        if (kdev.defined()) ctx->saved_data["kdev"] = kdev;       // (the device copy lives as long as the node)
+    }
+};
+
+// the union over the steps of the step-local plans (functional._plan_steps); one step of all sweeps is plan_checkpoints
+void plan_steps(const float* kmax, int K, int sps, double amax, uint64_t mask[2]) {
+    mask[0] = mask[1] = 0;
+    for (int k = 0; k < K; ++k) {
+        uint64_t m[2];
+        plan_checkpoints(kmax + (size_t)k * sps, sps, amax, m);
+        mask[0] |= m[0];
+        mask[1] |= m[1];
+    }
+}
+
+// ckpt_mode 1 = "auto": the backward plans from this call's coefficients; otherwise the mask is explicit
+void save_plan(AutogradContext* ctx, int64_t ckpt_mode, int64_t lo, int64_t hi, double amax) {
+    ctx->saved_data["ckpt"] = std::vector<int64_t>{ckpt_mode, lo, hi};
+    ctx->saved_data["amax"] = amax;
+}
+
+// The backward's checkpoint mask: the explicit one, or under "auto" the plan — per step of `sps` sweeps — from the maxima
+// in the node's slot, once the event behind the forward's factorisation kernel has completed.
+void mask_from_ctx(AutogradContext* ctx, const PdeAdiDesc& d, int sps, uint64_t mask[2]) {
+    auto ck = ctx->saved_data["ckpt"].toIntVector();
+    mask[0] = (uint64_t)ck[1];
+    mask[1] = (uint64_t)ck[2];
+    if (ck[0] != 1) return;
+    Slot* slot = reinterpret_cast<Slot*>((intptr_t)ctx->saved_data["slot"].toInt());
+    wait_event(slot->ev);
+    plan_steps(slot->host, d.num_sweeps / sps, sps, ctx->saved_data["amax"].toDouble(), mask);
+}
+
+void save_desc(AutogradContext* ctx, const PdeAdiDesc* d, int n = 1) {
+    ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(d), sizeof(PdeAdiDesc) * n);
+}
+void load_desc(AutogradContext* ctx, PdeAdiDesc* d, int n = 1) {
+    std::memcpy(d, ctx->saved_data["desc"].toStringRef().data(), sizeof(PdeAdiDesc) * n);
+}
+
+// the callers' shapes of the four coefficient tensors of layer `i` — (N,N) at C = 1 — in which their gradients go back
+void save_shapes(AutogradContext* ctx, std::initializer_list<const Tensor*> params, int i = 0) {
+    int j = 4 * i;
+    for (const Tensor* t : params) ctx->saved_data["sh" + std::to_string(j++)] = t->sizes().vec();
+}
+void param_grads(AutogradContext* ctx, const Tensor* p, Tensor* gp, int i = 0) {
+    for (int j = 0; j < 4; ++j) gp[j] = at::empty(ctx->saved_data["sh" + std::to_string(4 * i + j)].toIntVector(), p[j].options());
+}
+
+// a cotangent as the library takes it: in the tensors' type, contiguous, aligned; an undefined one stays undefined
+Tensor cotangent(Tensor g, at::ScalarType dtype) {
+    if (!g.defined()) return g;
+    if (g.scalar_type() != dtype) g = g.to(dtype);
+    return aligned(g.contiguous());
+}
+Tensor as_dtype(const Tensor& g, int64_t dtype) {
+    return (int64_t)g.scalar_type() == dtype ? g : g.to((at::ScalarType)dtype);
+}
+
+// the frozen route marks its node with the tensors' type (the node keeps no tensor of that type)
+void save_input_only(AutogradContext* ctx, const Tensor& u) { ctx->saved_data["input_only"] = (int64_t)u.scalar_type(); }
+bool is_input_only(AutogradContext* ctx) { return ctx->saved_data.count("input_only") != 0; }
+at::ScalarType input_only_dtype(AutogradContext* ctx) {
+    return static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
+}
+
+// a backward's result: the gradients it has, then undefined tensors up to the forward's `n` arguments
+variable_list grads_out(size_t n, std::initializer_list<Tensor> head) {
+    variable_list res(head);
+    res.resize(n);
+    return res;
+}
+
+// wide: a tensor or matrix the kernels read 16 bytes wide; otherwise one of the header's ELEMENT-ALIGNED parameters
+// (skip_weight, weights, gamma / beta, bn_weight / bn_bias), which may begin wherever its elements do: no copy
+Tensor as_f32(const Tensor& t, bool wide = true) {
+    Tensor q = t.detach();
+    if (q.scalar_type() != at::kFloat) q = q.to(at::kFloat);
+    return wide ? aligned(q.contiguous()) : q.contiguous();
+}
+
+std::vector<int64_t> states_shape(int64_t K, const Tensor& u) {
+    std::vector<int64_t> sh{K};
+    for (auto v : u.sizes()) sh.push_back(v);
+    return sh;
+}
+
 struct AdiFn : public torch::autograd::Function<AdiFn> {
     // ckpt_mode: 0 = explicit mask (ckpt_lo/hi), 1 = "auto" (planned in the backward from this call's coefficients),
     // 2 = explicit mask, and this call's coefficient maxima go to a slot the CALLER owns (slot_out: where to leave it) —
@@ -233,60 +393,32 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
                           const Tensor& bsl, int64_t desc_addr, int64_t ckpt_mode, int64_t ckpt_lo, int64_t ckpt_hi,
                           double amax, int64_t grad_mode, int64_t slot_out) {
         const bool need_grad = grad_mode != kGradNone, input_only = grad_mode == kGradInput;
-        PDE_REQUIRE(u_in.is_cuda() && ab.is_cuda() && bb.is_cuda() && asl.is_cuda() && bsl.is_cuda(),
-                    "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
+        require_cuda({&u_in, &ab, &bb, &asl, &bsl});
         PDE_REQUIRE(u_in.dim() == 4 && u_in.size(2) == u_in.size(3), "expected (B,C,N,N), got ", u_in.sizes());
-        PdeAdiDesc d;
-        std::memcpy(&d, reinterpret_cast<const void*>(desc_addr), sizeof(d));
-        const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
-        Tensor u = u_in.detach();
-        if (!io_type(u)) u = u.to(at::kFloat);
-        u = aligned(u.contiguous());
-        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
-                    "descriptor does not match the tensor");
-        Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
-        // (the input-only backward plans no checkpoints: maxima only for the lagged call, which hands the ticket out)
-        const bool want_kmax = need_grad && (ckpt_mode == 2 || (ckpt_mode == 1 && !input_only));
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
+        Prologue pr(u_in, ab, bb, asl, bsl, desc_addr);
+        const Tensor& u = pr.u;
+        const PdeAdiDesc& d = pr.d;
         Tensor y = at::empty_like(u);
         Tensor ws = bytes(pde_adi_forward_workspace_bytes(&d), u);
-        Tensor kdev, ticket;
-        Slot* slot = nullptr;
-        if (want_kmax) {
-            kdev = at::empty({(int64_t)d.num_sweeps}, u.options().dtype(at::kFloat));
-            slot = acquire_slot(u.device().index());
-            if (ckpt_mode == 1) ticket = slot_ticket(slot, d.num_sweeps);
-            else *reinterpret_cast<Slot**>(slot_out) = slot;           // the caller's ticket holds it
-        }
-        check(pde_adi_forward(&d, u.data_ptr(), y.data_ptr(), p[0].data_ptr<float>(), p[1].data_ptr<float>(),
-                              p[2].data_ptr<float>(), p[3].data_ptr<float>(), want_kmax ? kdev.data_ptr<float>() : nullptr,
-                              slot ? slot->host : nullptr, slot ? (void*)slot->ev : nullptr, ws.data_ptr(), (size_t)ws.numel(),
-                              (void*)st),
+        // (the input-only backward plans no checkpoints: maxima only for the lagged call, which hands the ticket out)
+        Kmax km(need_grad && (ckpt_mode == 2 || (ckpt_mode == 1 && !input_only)), d.num_sweeps, u, ckpt_mode == 1);
+        if (km.slot && ckpt_mode != 1) *reinterpret_cast<Slot**>(slot_out) = km.slot;   // the caller's ticket holds it
+        check(pde_adi_forward(&d, u.data_ptr(), y.data_ptr(), PDE_F4(pr.p), km.dev(), km.host(), km.event(), ws.data_ptr(),
+                              (size_t)ws.numel(), (void*)pr.dev.st),
               "pde_adi_forward");
+        if (!need_grad) return y;
         if (input_only) {
-            ctx->save_for_backward({p[0], p[1], p[2], p[3]});
-            ctx->saved_data["ws"] = ws;
-            if (kdev.defined()) ctx->saved_data["kdev"] = kdev;
-            ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(&d), sizeof(d));
-            ctx->saved_data["input_only"] = (int64_t)u.scalar_type();
-        } else if (need_grad) {
+            ctx->save_for_backward({pr.p[0], pr.p[1], pr.p[2], pr.p[3]});
+            save_input_only(ctx, u);
+        } else {
             const bool explicit_none = ckpt_mode == 0 && ckpt_lo == 0 && ckpt_hi == 0;
-            ctx->save_for_backward({y, explicit_none ? Tensor() : u, p[0], p[1], p[2], p[3]});
-            ctx->saved_data["ws"] = ws;                      // the factorisation, reused by the backward
-            if (slot && ckpt_mode == 1) {
-                ctx->saved_data["ticket"] = ticket;
-                ctx->saved_data["slot"] = (int64_t) reinterpret_cast<intptr_t>(slot);
-            }
-            if (kdev.defined()) ctx->saved_data["kdev"] = kdev;       // (the device copy lives as long as the node)
-            ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(&d), sizeof(d));
-            ctx->saved_data["ckpt"] = std::vector<int64_t>{ckpt_mode, ckpt_lo, ckpt_hi};
-            ctx->saved_data["amax"] = amax;
-            ctx->saved_data["sh0"] = ab.sizes().vec();
-            ctx->saved_data["sh1"] = bb.sizes().vec();
-            ctx->saved_data["sh2"] = asl.sizes().vec();
-            ctx->saved_data["sh3"] = bsl.sizes().vec();
+            ctx->save_for_backward({y, explicit_none ? Tensor() : u, pr.p[0], pr.p[1], pr.p[2], pr.p[3]});
+            save_plan(ctx, ckpt_mode, ckpt_lo, ckpt_hi, amax);
+            save_shapes(ctx, {&ab, &bb, &asl, &bsl});
         }
+        ctx->saved_data["ws"] = ws;                          // the factorisation, reused by the backward
+        km.save(ctx);
+        save_desc(ctx, &d);
         return y;
     }
 
@@ -294,56 +426,39 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
     static variable_list backward_input(AutogradContext* ctx, variable_list& grads) {
         auto saved = ctx->get_saved_variables();
         PdeAdiDesc d;
-        std::memcpy(&d, ctx->saved_data["desc"].toStringRef().data(), sizeof(d));
-        const auto dtype = static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
-        Tensor gy = grads[0];
-        if (gy.scalar_type() != dtype) gy = gy.to(dtype);
-        gy = aligned(gy.contiguous());
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(gy.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(gy.device().index()).stream();
+        load_desc(ctx, &d);
+        Tensor gy = cotangent(grads[0], input_only_dtype(ctx));
+        OnDevice dev(gy);
         Tensor gu = at::empty_like(gy);
         Tensor ws = bytes(pde_adi_backward_input_workspace_bytes(&d), gy);
         Tensor fws = ctx->saved_data["ws"].toTensor();
-        check(pde_adi_backward_input(&d, gy.data_ptr(), gu.data_ptr(), saved[0].data_ptr<float>(), saved[1].data_ptr<float>(),
-                                     saved[2].data_ptr<float>(), saved[3].data_ptr<float>(), fws.data_ptr(), ws.data_ptr(),
-                                     (size_t)ws.numel(), (void*)st),
+        check(pde_adi_backward_input(&d, gy.data_ptr(), gu.data_ptr(), PDE_F4(&saved[0]), fws.data_ptr(), ws.data_ptr(),
+                                     (size_t)ws.numel(), (void*)dev.st),
               "pde_adi_backward_input");
-        return {gu, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        return grads_out(12, {gu});
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
-        if (ctx->saved_data.count("input_only")) return backward_input(ctx, grads);
+        if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &y = saved[0], &u = saved[1];
         PdeAdiDesc d;
-        std::memcpy(&d, ctx->saved_data["desc"].toStringRef().data(), sizeof(d));
-        auto ck = ctx->saved_data["ckpt"].toIntVector();
-        uint64_t mask[2] = {(uint64_t)ck[1], (uint64_t)ck[2]};
-        if (ck[0] == 1) {
-            Slot* slot = reinterpret_cast<Slot*>((intptr_t)ctx->saved_data["slot"].toInt());
-            wait_event(slot->ev);
-            plan_checkpoints(slot->host, d.num_sweeps, ctx->saved_data["amax"].toDouble(), mask);
-        }
+        load_desc(ctx, &d);
+        uint64_t mask[2];
+        mask_from_ctx(ctx, d, d.num_sweeps, mask);
         const bool any = (mask[0] | mask[1]) != 0;
         PDE_REQUIRE(!any || u.defined(), "a checkpoint plan needs the layer input, which was not kept");
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(y.device());                 // autograd's worker thread: set the device, fetch the stream here
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(y.device().index()).stream();
-        Tensor gy = grads[0];
-        if (gy.scalar_type() != y.scalar_type()) gy = gy.to(y.scalar_type());
-        gy = aligned(gy.contiguous());
+        OnDevice dev(y);
+        Tensor gy = cotangent(grads[0], y.scalar_type());
         Tensor gu = at::empty_like(y);
-        static const char* const kShape[4] = {"sh0", "sh1", "sh2", "sh3"};
         Tensor gp[4];
-        for (int i = 0; i < 4; ++i) gp[i] = at::empty(ctx->saved_data[kShape[i]].toIntVector(), saved[2 + i].options());
+        param_grads(ctx, &saved[2], gp);
         Tensor ws = bytes(pde_adi_backward_workspace_bytes(&d, popcount2(mask)), y);
         Tensor fws = ctx->saved_data["ws"].toTensor();
         check(pde_adi_backward(&d, gy.data_ptr(), y.data_ptr(), any ? u.data_ptr() : nullptr, mask, gu.data_ptr(),
-                               saved[2].data_ptr<float>(), saved[3].data_ptr<float>(), saved[4].data_ptr<float>(),
-                               saved[5].data_ptr<float>(), gp[0].data_ptr<float>(), gp[1].data_ptr<float>(),
-                               gp[2].data_ptr<float>(), gp[3].data_ptr<float>(), fws.data_ptr(), ws.data_ptr(),
-                               (size_t)ws.numel(), (void*)st),
+                               PDE_F4(&saved[2]), PDE_F4(gp), fws.data_ptr(), ws.data_ptr(), (size_t)ws.numel(), (void*)dev.st),
               "pde_adi_backward");
-        return {gu, gp[0], gp[1], gp[2], gp[3], Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        return grads_out(12, {gu, gp[0], gp[1], gp[2], gp[3]});
     }
 };
 
@@ -377,34 +492,8 @@ std::pair<Tensor, std::shared_ptr<Ticket>> adi_lagged(const Tensor& u, const Ten
     return {y, slot ? std::make_shared<Ticket>(slot, d.num_sweeps) : std::shared_ptr<Ticket>()};
 }
 
-
-// the union over the steps of the step-local plans (functional._AdiSmallFn.backward)
-void plan_steps(const float* kmax, int K, int sps, double amax, uint64_t mask[2]) {
-    mask[0] = mask[1] = 0;
-    for (int k = 0; k < K; ++k) {
-        uint64_t m[2];
-        plan_checkpoints(kmax + (size_t)k * sps, sps, amax, m);
-        mask[0] |= m[0];
-        mask[1] |= m[1];
-    }
-}
-
-// wide: a tensor or matrix the kernels read 16 bytes wide; otherwise one of the header's ELEMENT-ALIGNED parameters
-// (skip_weight, weights, gamma / beta, bn_weight / bn_bias), which may begin wherever its elements do: no copy
-Tensor as_f32(const Tensor& t, bool wide = true) {
-    Tensor q = t.detach();
-    if (q.scalar_type() != at::kFloat) q = q.to(at::kFloat);
-    return wide ? aligned(q.contiguous()) : q.contiguous();
-}
-
-std::vector<int64_t> states_shape(int64_t K, const Tensor& u) {
-    std::vector<int64_t> sh{K};
-    for (auto v : u.sizes()) sh.push_back(v);
-    return sh;
-}
-
-// ---- one layer with a channel operator between its steps, C <= 4, one launch per pass (functional._AdiSmallFn:
-// cifar10.py:84-112 "pre", SVHN.py:55-76 "post" with the skip blend) -----------------------------------------------
+// ---- one layer with a channel operator between its steps, C <= 4, one launch per pass (functional._AdiSmallFn without
+// ``emit``: cifar10.py:84-112 "pre", SVHN.py:55-76 "post" with the skip blend) ---------------------------------------
 struct SmallFn : public torch::autograd::Function<SmallFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& u_in, const Tensor& ab, const Tensor& bb, const Tensor& asl,
                           const Tensor& bsl, const Tensor& M, const std::optional<Tensor>& skip_opt, int64_t desc_addr, int64_t sps,
@@ -413,72 +502,43 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         // pde_adi_small_backward_input (M, skip_weight and the steps workspace are all it keeps)
         const bool need_grad = grad_mode == kGradFull, input_only = grad_mode == kGradInput;
         const Tensor skip = skip_opt.has_value() ? *skip_opt : Tensor();
-        PDE_REQUIRE(u_in.is_cuda() && ab.is_cuda() && bb.is_cuda() && asl.is_cuda() && bsl.is_cuda() && M.is_cuda() &&
-                        (!skip.defined() || skip.is_cuda()),
-                    "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
-        PdeAdiDesc d;
-        std::memcpy(&d, reinterpret_cast<const void*>(desc_addr), sizeof(d));
-        const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
-        Tensor u = u_in.detach();
-        if (!io_type(u)) u = u.to(at::kFloat);
-        u = aligned(u.contiguous());
-        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
-                    "descriptor does not match the tensor");
-        const int64_t K = d.num_sweeps / sps;
-        Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
+        require_cuda({&u_in, &ab, &bb, &asl, &bsl, &M, &skip});
+        Prologue pr(u_in, ab, bb, asl, bsl, desc_addr);
+        const Tensor& u = pr.u;
+        const PdeAdiDesc& d = pr.d;
         Tensor Mf = as_f32(M);
         Tensor sw = skip.defined() ? as_f32(skip, false).reshape({1}) : Tensor();
-        const bool want_kmax = need_grad && ckpt_mode == 1;
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
         Tensor sws = bytes(pde_adi_steps_workspace_bytes(&d, (int32_t)sps), u);
-        Tensor kdev, ticket, states;
-        Slot* slot = nullptr;
-        if (want_kmax) {
-            kdev = at::empty({(int64_t)d.num_sweeps}, u.options().dtype(at::kFloat));
-            slot = acquire_slot(u.device().index());
-            ticket = slot_ticket(slot, d.num_sweeps);
-        }
-        if (need_grad) states = at::empty(states_shape(K, u), u.options());
+        Kmax km(need_grad && ckpt_mode == 1, d.num_sweeps, u);
+        Tensor states = need_grad ? at::empty(states_shape(d.num_sweeps / sps, u), u.options()) : Tensor();
         Tensor y = at::empty_like(u);
-        if (input_only) {
+        if (input_only)
             check(pde_adi_small_forward_input(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), y.data_ptr(), Mf.data_ptr<float>(),
-                                              sw.defined() ? sw.data_ptr<float>() : nullptr, p[0].data_ptr<float>(),
-                                              p[1].data_ptr<float>(), p[2].data_ptr<float>(), p[3].data_ptr<float>(), nullptr,
-                                              nullptr, nullptr, sws.data_ptr(), (size_t)sws.numel(), (void*)st),
+                                              fptr(sw), PDE_F4(pr.p), nullptr, nullptr, nullptr, sws.data_ptr(),
+                                              (size_t)sws.numel(), (void*)pr.dev.st),
                   "pde_adi_small_forward_input");
+        else
+            check(pde_adi_small_forward(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), y.data_ptr(), vptr(states),
+                                        Mf.data_ptr<float>(), fptr(sw), PDE_F4(pr.p), km.dev(), km.host(), km.event(),
+                                        sws.data_ptr(), (size_t)sws.numel(), (void*)pr.dev.st),
+                  "pde_adi_small_forward");
+        if (grad_mode == kGradNone) return y;
+        if (input_only) {
             ctx->save_for_backward({Mf, sw});
-            ctx->saved_data["sws"] = sws;
-            ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(&d), sizeof(d));
-            ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode};
-            ctx->saved_data["input_only"] = (int64_t)u.scalar_type();
-            return y;
-        }
-        check(pde_adi_small_forward(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), y.data_ptr(),
-                                    need_grad ? states.data_ptr() : nullptr, Mf.data_ptr<float>(),
-                                    sw.defined() ? sw.data_ptr<float>() : nullptr, p[0].data_ptr<float>(), p[1].data_ptr<float>(),
-                                    p[2].data_ptr<float>(), p[3].data_ptr<float>(), want_kmax ? kdev.data_ptr<float>() : nullptr,
-                                    slot ? slot->host : nullptr, slot ? (void*)slot->ev : nullptr, sws.data_ptr(),
-                                    (size_t)sws.numel(), (void*)st),
-              "pde_adi_small_forward");
-        if (need_grad) {
-            ctx->save_for_backward({u, Mf, sw, p[0], p[1], p[2], p[3]});
+            save_input_only(ctx, u);
+        } else {
+            ctx->save_for_backward({u, Mf, sw, pr.p[0], pr.p[1], pr.p[2], pr.p[3]});
             ctx->saved_data["states"] = states;
-            ctx->saved_data["sws"] = sws;
-            if (slot) {
-                ctx->saved_data["ticket"] = ticket;
-                ctx->saved_data["slot"] = (int64_t) reinterpret_cast<intptr_t>(slot);
-            }
-            ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(&d), sizeof(d));
-            ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode, ckpt_mode, ckpt_lo, (int64_t)M.scalar_type(),
-                                                          skip.defined() ? (int64_t)skip.scalar_type() : -1};
-            ctx->saved_data["amax"] = amax;
-            ctx->saved_data["sh0"] = ab.sizes().vec();
-            ctx->saved_data["sh1"] = bb.sizes().vec();
-            ctx->saved_data["sh2"] = asl.sizes().vec();
-            ctx->saved_data["sh3"] = bsl.sizes().vec();
+            km.save(ctx);
+            save_plan(ctx, ckpt_mode, ckpt_lo, 0, amax);
+            save_shapes(ctx, {&ab, &bb, &asl, &bsl});
+            ctx->saved_data["types"] = std::vector<int64_t>{(int64_t)M.scalar_type(),
+                                                            skip.defined() ? (int64_t)skip.scalar_type() : -1};
             if (skip.defined()) ctx->saved_data["shs"] = skip.sizes().vec();
         }
+        ctx->saved_data["sws"] = sws;
+        save_desc(ctx, &d);
+        ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode};
         return y;
     }
 
@@ -487,65 +547,44 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         auto saved = ctx->get_saved_variables();
         const Tensor &Mf = saved[0], &sw = saved[1];
         PdeAdiDesc d;
-        std::memcpy(&d, ctx->saved_data["desc"].toStringRef().data(), sizeof(d));
+        load_desc(ctx, &d);
         auto cfg = ctx->saved_data["cfg"].toIntVector();
-        const auto dtype = static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
-        Tensor gy = grads[0];
-        if (gy.scalar_type() != dtype) gy = gy.to(dtype);
-        gy = aligned(gy.contiguous());
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(gy.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(gy.device().index()).stream();
+        Tensor gy = cotangent(grads[0], input_only_dtype(ctx));
+        OnDevice dev(gy);
         Tensor gu = at::empty_like(gy);
         Tensor sws = ctx->saved_data["sws"].toTensor();
-        check(pde_adi_small_backward_input(&d, (int32_t)cfg[0], (int32_t)cfg[1], gy.data_ptr(), Mf.data_ptr<float>(),
-                                           sw.defined() ? sw.data_ptr<float>() : nullptr, gu.data_ptr(), sws.data_ptr(), nullptr,
-                                           0, (void*)st),
+        check(pde_adi_small_backward_input(&d, (int32_t)cfg[0], (int32_t)cfg[1], gy.data_ptr(), Mf.data_ptr<float>(), fptr(sw),
+                                           gu.data_ptr(), sws.data_ptr(), nullptr, 0, (void*)dev.st),
               "pde_adi_small_backward_input");
-        return {gu, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor(), Tensor()};
+        return grads_out(14, {gu});
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
-        if (ctx->saved_data.count("input_only")) return backward_input(ctx, grads);
+        if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &u = saved[0], &Mf = saved[1], &sw = saved[2];
         PdeAdiDesc d;
-        std::memcpy(&d, ctx->saved_data["desc"].toStringRef().data(), sizeof(d));
+        load_desc(ctx, &d);
         auto cfg = ctx->saved_data["cfg"].toIntVector();
-        const int sps = (int)cfg[0], mode = (int)cfg[1], K = d.num_sweeps / sps;
-        uint64_t mask[2] = {(uint64_t)cfg[3], 0};
-        if (cfg[2] == 1) {
-            Slot* slot = reinterpret_cast<Slot*>((intptr_t)ctx->saved_data["slot"].toInt());
-            wait_event(slot->ev);
-            plan_steps(slot->host, K, sps, ctx->saved_data["amax"].toDouble(), mask);
-        }
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
-        Tensor gy = grads[0];
-        if (gy.scalar_type() != u.scalar_type()) gy = gy.to(u.scalar_type());
-        gy = aligned(gy.contiguous());
+        auto types = ctx->saved_data["types"].toIntVector();
+        const int sps = (int)cfg[0], mode = (int)cfg[1];
+        uint64_t mask[2];
+        mask_from_ctx(ctx, d, sps, mask);
+        OnDevice dev(u);
+        Tensor gy = cotangent(grads[0], u.scalar_type());
         Tensor gu = at::empty_like(gy);
-        static const char* const kShape[4] = {"sh0", "sh1", "sh2", "sh3"};
         Tensor gp[4];
-        for (int i = 0; i < 4; ++i) gp[i] = at::empty(ctx->saved_data[kShape[i]].toIntVector(), saved[3 + i].options());
+        param_grads(ctx, &saved[3], gp);
         Tensor gM = at::empty_like(Mf);
         Tensor gsw = sw.defined() ? at::empty({1}, Mf.options()) : Tensor();
         Tensor ws = bytes(pde_adi_small_backward_workspace_bytes(&d, sps, popcount2(mask)), u);
         Tensor states = ctx->saved_data["states"].toTensor(), sws = ctx->saved_data["sws"].toTensor();
-        check(pde_adi_small_backward(&d, sps, mode, gy.data_ptr(), u.data_ptr(), states.data_ptr(), Mf.data_ptr<float>(),
-                                     sw.defined() ? sw.data_ptr<float>() : nullptr, mask, gu.data_ptr(),
-                                     saved[3].data_ptr<float>(), saved[4].data_ptr<float>(), saved[5].data_ptr<float>(),
-                                     saved[6].data_ptr<float>(), gp[0].data_ptr<float>(), gp[1].data_ptr<float>(),
-                                     gp[2].data_ptr<float>(), gp[3].data_ptr<float>(), gM.data_ptr<float>(),
-                                     gsw.defined() ? gsw.data_ptr<float>() : nullptr, sws.data_ptr(), ws.data_ptr(),
-                                     (size_t)ws.numel(), (void*)st),
+        check(pde_adi_small_backward(&d, sps, mode, gy.data_ptr(), u.data_ptr(), states.data_ptr(), Mf.data_ptr<float>(), fptr(sw),
+                                     mask, gu.data_ptr(), PDE_F4(&saved[3]), PDE_F4(gp), gM.data_ptr<float>(), fptr(gsw),
+                                     sws.data_ptr(), ws.data_ptr(), (size_t)ws.numel(), (void*)dev.st),
               "pde_adi_small_backward");
-        if ((int64_t)gM.scalar_type() != cfg[4]) gM = gM.to((at::ScalarType)cfg[4]);
-        if (gsw.defined()) {
-            if ((int64_t)gsw.scalar_type() != cfg[5]) gsw = gsw.to((at::ScalarType)cfg[5]);
-            gsw = gsw.reshape(ctx->saved_data["shs"].toIntVector());
-        }
-        return {gu, gp[0], gp[1], gp[2], gp[3], gM, gsw, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        if (gsw.defined()) gsw = as_dtype(gsw, types[1]).reshape(ctx->saved_data["shs"].toIntVector());
+        return grads_out(14, {gu, gp[0], gp[1], gp[2], gp[3], as_dtype(gM, types[0]), gsw});
     }
 };
 
@@ -566,55 +605,30 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& u_in, const Tensor& ab, const Tensor& bb, const Tensor& asl,
                           const Tensor& bsl, const Tensor& M, int64_t desc_addr, int64_t sps, int64_t mode, int64_t ckpt_mode,
                           int64_t ckpt_lo, double amax, bool need_grad) {
-        PDE_REQUIRE(u_in.is_cuda() && ab.is_cuda() && bb.is_cuda() && asl.is_cuda() && bsl.is_cuda() && M.is_cuda(),
-                    "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
+        require_cuda({&u_in, &ab, &bb, &asl, &bsl, &M});
         PDE_REQUIRE(u_in.dim() == 4 && u_in.size(2) == u_in.size(3), "expected (B,C,N,N), got ", u_in.sizes());
-        PdeAdiDesc d;
-        std::memcpy(&d, reinterpret_cast<const void*>(desc_addr), sizeof(d));
-        const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
-        Tensor u = u_in.detach();
-        if (!io_type(u)) u = u.to(at::kFloat);
-        u = aligned(u.contiguous());
-        PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
-                    "descriptor does not match the tensor");
-        const int64_t K = d.num_sweeps / sps;
-        Tensor p[4] = {as_chw(ab, C, N), as_chw(bb, C, N), as_chw(asl, C, N), as_chw(bsl, C, N)};
+        Prologue pr(u_in, ab, bb, asl, bsl, desc_addr);
+        const Tensor& u = pr.u;
+        const PdeAdiDesc& d = pr.d;
         Tensor Mf = as_f32(M);
-        const bool want_kmax = need_grad && ckpt_mode == 1;
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
         Tensor sws = bytes(pde_adi_steps_workspace_bytes(&d, (int32_t)sps), u);
-        Tensor kdev, ticket;
-        Slot* slot = nullptr;
-        if (want_kmax) {
-            kdev = at::empty({(int64_t)d.num_sweeps}, u.options().dtype(at::kFloat));
-            slot = acquire_slot(u.device().index());
-            ticket = slot_ticket(slot, d.num_sweeps);
-        }
+        Kmax km(need_grad && ckpt_mode == 1, d.num_sweeps, u);
         // states[2k]: output of step k's first operator, states[2k+1]: of its second (= input of step k + 1); the last of
         // them is the layer output and lives in a tensor of its own
-        Tensor states = at::empty(states_shape(2 * K - 1, u), u.options());
+        Tensor states = at::empty(states_shape(2 * (d.num_sweeps / sps) - 1, u), u.options());
         Tensor y = at::empty_like(u);
-        check(pde_adi_mixed_forward(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), states.data_ptr(), y.data_ptr(), Mf.data_ptr<float>(),
-                                    p[0].data_ptr<float>(), p[1].data_ptr<float>(), p[2].data_ptr<float>(), p[3].data_ptr<float>(),
-                                    want_kmax ? kdev.data_ptr<float>() : nullptr, slot ? slot->host : nullptr,
-                                    slot ? (void*)slot->ev : nullptr, sws.data_ptr(), (size_t)sws.numel(), (void*)st),
+        check(pde_adi_mixed_forward(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), states.data_ptr(), y.data_ptr(),
+                                    Mf.data_ptr<float>(), PDE_F4(pr.p), km.dev(), km.host(), km.event(), sws.data_ptr(),
+                                    (size_t)sws.numel(), (void*)pr.dev.st),
               "pde_adi_mixed_forward");
-        if (need_grad) {
-            ctx->save_for_backward({u, states, Mf, p[0], p[1], p[2], p[3], y});
-            ctx->saved_data["sws"] = sws;
-            if (slot) {
-                ctx->saved_data["ticket"] = ticket;
-                ctx->saved_data["slot"] = (int64_t) reinterpret_cast<intptr_t>(slot);
-            }
-            ctx->saved_data["desc"] = std::string(reinterpret_cast<const char*>(&d), sizeof(d));
-            ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode, ckpt_mode, ckpt_lo, (int64_t)M.scalar_type()};
-            ctx->saved_data["amax"] = amax;
-            ctx->saved_data["sh0"] = ab.sizes().vec();
-            ctx->saved_data["sh1"] = bb.sizes().vec();
-            ctx->saved_data["sh2"] = asl.sizes().vec();
-            ctx->saved_data["sh3"] = bsl.sizes().vec();
-        }
+        if (!need_grad) return y;
+        ctx->save_for_backward({u, states, Mf, pr.p[0], pr.p[1], pr.p[2], pr.p[3], y});
+        ctx->saved_data["sws"] = sws;
+        km.save(ctx);
+        save_desc(ctx, &d);
+        save_plan(ctx, ckpt_mode, ckpt_lo, 0, amax);
+        save_shapes(ctx, {&ab, &bb, &asl, &bsl});
+        ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode, (int64_t)M.scalar_type()};
         return y;
     }
 
@@ -622,36 +636,24 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
         auto saved = ctx->get_saved_variables();
         const Tensor &u = saved[0], &states = saved[1], &Mf = saved[2];
         PdeAdiDesc d;
-        std::memcpy(&d, ctx->saved_data["desc"].toStringRef().data(), sizeof(d));
+        load_desc(ctx, &d);
         auto cfg = ctx->saved_data["cfg"].toIntVector();
-        const int sps = (int)cfg[0], mode = (int)cfg[1], K = d.num_sweeps / sps;
-        uint64_t mask[2] = {(uint64_t)cfg[3], 0};
-        if (cfg[2] == 1) {
-            Slot* slot = reinterpret_cast<Slot*>((intptr_t)ctx->saved_data["slot"].toInt());
-            wait_event(slot->ev);
-            plan_steps(slot->host, K, sps, ctx->saved_data["amax"].toDouble(), mask);
-        }
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
-        Tensor gy = grads[0];
-        if (gy.scalar_type() != u.scalar_type()) gy = gy.to(u.scalar_type());
-        gy = aligned(gy.contiguous());
+        const int sps = (int)cfg[0], mode = (int)cfg[1];
+        uint64_t mask[2];
+        mask_from_ctx(ctx, d, sps, mask);
+        OnDevice dev(u);
+        Tensor gy = cotangent(grads[0], u.scalar_type());
         Tensor gu = at::empty_like(gy);
-        static const char* const kShape[4] = {"sh0", "sh1", "sh2", "sh3"};
         Tensor gp[4];
-        for (int i = 0; i < 4; ++i) gp[i] = at::empty(ctx->saved_data[kShape[i]].toIntVector(), saved[3 + i].options());
+        param_grads(ctx, &saved[3], gp);
         Tensor gM = at::empty_like(Mf);
         Tensor ws = bytes(pde_adi_mixed_backward_workspace_bytes(&d, sps, popcount2(mask)), u);
         Tensor sws = ctx->saved_data["sws"].toTensor();
         check(pde_adi_mixed_backward(&d, sps, mode, gy.data_ptr(), u.data_ptr(), states.data_ptr(), saved[7].data_ptr(),
-                                     Mf.data_ptr<float>(), mask,
-                                     gu.data_ptr(), saved[3].data_ptr<float>(), saved[4].data_ptr<float>(),
-                                     saved[5].data_ptr<float>(), saved[6].data_ptr<float>(), gp[0].data_ptr<float>(),
-                                     gp[1].data_ptr<float>(), gp[2].data_ptr<float>(), gp[3].data_ptr<float>(),
-                                     gM.data_ptr<float>(), sws.data_ptr(), ws.data_ptr(), (size_t)ws.numel(), (void*)st),
+                                     Mf.data_ptr<float>(), mask, gu.data_ptr(), PDE_F4(&saved[3]), PDE_F4(gp),
+                                     gM.data_ptr<float>(), sws.data_ptr(), ws.data_ptr(), (size_t)ws.numel(), (void*)dev.st),
               "pde_adi_mixed_backward");
-        if ((int64_t)gM.scalar_type() != cfg[4]) gM = gM.to((at::ScalarType)cfg[4]);
-        return {gu, gp[0], gp[1], gp[2], gp[3], gM, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        return grads_out(13, {gu, gp[0], gp[1], gp[2], gp[3], as_dtype(gM, cfg[2])});
     }
 };
 
@@ -665,6 +667,39 @@ Tensor mixed(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& 
 // ---- several mixing-first layers on the SAME input, one launch per pass (functional._AdiMultiFn: cifar10.py:272-280,
 // cifar_2version.py:287-288).  Returns (sum_i w_i y_i, y_1 .. y_L[, s_1 .. s_L]) ----------------------------------------
 struct MultiFn : public torch::autograd::Function<MultiFn> {
+    // what every pass sets of a layer's record (functional._small_layer); the caller adds what its pass has
+    static PdeSmallLayer layer_record(const PdeAdiDesc* d, int64_t sps, const Tensor& Mf, const Tensor& wdev, int i,
+                                      const Tensor& sws) {
+        PdeSmallLayer a;
+        std::memset(&a, 0, sizeof(a));
+        a.desc = d;
+        a.sweeps_per_step = (int32_t)sps;
+        a.mode = 1;
+        a.M = Mf.data_ptr<float>();
+        a.weight = 0.f;
+        a.weight_ptr = wdev.defined() ? wdev.data_ptr<float>() + i : nullptr;
+        a.steps_workspace = sws.data_ptr();
+        a.steps_workspace_bytes = (size_t)sws.numel();
+        return a;
+    }
+    static void set_coeffs(PdeSmallLayer& a, const Tensor* p) {
+        a.alpha_base = p[0].data_ptr<float>();
+        a.beta_base = p[1].data_ptr<float>();
+        a.alpha_slope = p[2].data_ptr<float>();
+        a.beta_slope = p[3].data_ptr<float>();
+    }
+    // the cotangents of layer `i` (its y_i and, with plane sums, its s_i) into its record; false when it has neither
+    static bool set_cotangents(PdeSmallLayer& a, const variable_list& grads, int i, int nl, bool want_sums,
+                               at::ScalarType dtype, std::vector<Tensor>& keep) {
+        Tensor gyi = cotangent(grads[1 + i], dtype);
+        Tensor gsi = want_sums ? cotangent(grads[1 + nl + i], at::kFloat) : Tensor();
+        a.gys = vptr(gyi);
+        a.g_plane_sums = fptr(gsi);
+        keep.push_back(gyi);
+        keep.push_back(gsi);
+        return gyi.defined() || gsi.defined();
+    }
+
     static variable_list forward(AutogradContext* ctx, const Tensor& u_in, const std::optional<Tensor>& w_opt, at::TensorList flat,
                                  std::vector<int64_t> desc_addrs, int64_t sps, bool want_sums, int64_t ckpt_mode,
                                  std::vector<int64_t> masks, double amax, int64_t grad_mode) {
@@ -674,97 +709,71 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         const int nl = (int)desc_addrs.size();
         const Tensor weights = w_opt.has_value() ? *w_opt : Tensor();
         PDE_REQUIRE(nl >= 1 && (int)flat.size() == 5 * nl, "adi_diffuse_multi: five tensors per layer");
-        PDE_REQUIRE(u_in.is_cuda() && (!weights.defined() || weights.is_cuda()),
-                    "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
-        for (const auto& t : flat) PDE_REQUIRE(t.is_cuda(), "libpdecnn_hip operators need CUDA/HIP tensors (there is no CPU fallback)");
-        const int64_t B = u_in.size(0), C = u_in.size(1), N = u_in.size(2);
-        Tensor u = u_in.detach();
-        if (!io_type(u)) u = u.to(at::kFloat);
-        u = aligned(u.contiguous());
+        require_cuda({&u_in, &weights});
+        for (const auto& t : flat) require_cuda({&t});
+        Prologue pr(u_in);
+        const Tensor& u = pr.u;
         const bool want_kmax = need_grad && ckpt_mode == 1 && !input_only;
         ctx->set_materialize_grads(false);
         Tensor wdev = weights.defined() ? as_f32(weights, false) : Tensor();
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
 
         std::vector<PdeAdiDesc> descs(nl);
         std::vector<PdeSmallLayer> arr(nl);
-        std::vector<Tensor> save{u, wdev}, hold, states_v, sums_v, tickets;
-        std::vector<int64_t> slots, meta;
-        std::string shapes;                                   // the parameter shapes, for the gradients
+        std::vector<Tensor> save, views, hold, states_v, sums_v, tickets;
+        if (!input_only) save.push_back(u);
+        save.push_back(wdev);
+        std::vector<int64_t> slots, mdt;
         for (int i = 0; i < nl; ++i) {
             PdeAdiDesc& d = descs[i];
-            std::memcpy(&d, reinterpret_cast<const void*>(desc_addrs[i]), sizeof(d));
-            PDE_REQUIRE(d.B == B && d.C == C && d.N == N && d.io_dtype == io_of(u),
-                        "descriptor does not match the tensor");
-            const int64_t K = d.num_sweeps / sps;
             Tensor p[4];
-            for (int j = 0; j < 4; ++j) p[j] = as_chw(flat[5 * i + j], C, N);
+            pr.layer(desc_addrs[i], flat[5 * i], flat[5 * i + 1], flat[5 * i + 2], flat[5 * i + 3], &d, p);
             Tensor Mf = as_f32(flat[5 * i + 4]);
             Tensor sws = bytes(pde_adi_steps_workspace_bytes(&d, (int32_t)sps), u);
-            Tensor states = at::empty(states_shape(K, u), u.options());
-            Tensor kdev;
-            Slot* slot = nullptr;
+            Tensor states = at::empty(states_shape(d.num_sweeps / sps, u), u.options());
+            Kmax km(want_kmax, d.num_sweeps, u);
             if (want_kmax) {
-                kdev = at::empty({(int64_t)d.num_sweeps}, u.options().dtype(at::kFloat));
-                slot = acquire_slot(u.device().index());
-                tickets.push_back(slot_ticket(slot, d.num_sweeps));
-                hold.push_back(kdev);
+                tickets.push_back(km.ticket);
+                hold.push_back(km.kdev);
             }
-            slots.push_back((int64_t) reinterpret_cast<intptr_t>(slot));
-            Tensor psum = want_sums ? at::empty({B, C}, u.options().dtype(at::kFloat)) : Tensor();
-            PdeSmallLayer& a = arr[i];
-            std::memset(&a, 0, sizeof(a));
-            a.desc = &d;
-            a.sweeps_per_step = (int32_t)sps;
-            a.mode = 1;
-            a.M = Mf.data_ptr<float>();
-            a.alpha_base = p[0].data_ptr<float>();
-            a.beta_base = p[1].data_ptr<float>();
-            a.alpha_slope = p[2].data_ptr<float>();
-            a.beta_slope = p[3].data_ptr<float>();
-            a.weight = 0.f;
-            a.weight_ptr = wdev.defined() ? wdev.data_ptr<float>() + i : nullptr;
+            slots.push_back((int64_t) reinterpret_cast<intptr_t>(km.slot));
+            Tensor psum = want_sums ? at::empty({u.size(0), u.size(1)}, u.options().dtype(at::kFloat)) : Tensor();
+            PdeSmallLayer& a = arr[i] = layer_record(&d, sps, Mf, wdev, i, sws);
+            set_coeffs(a, p);
             a.states = states.data_ptr();
-            a.steps_workspace = sws.data_ptr();
-            a.steps_workspace_bytes = (size_t)sws.numel();
-            a.kappa_max = want_kmax ? kdev.data_ptr<float>() : nullptr;
-            a.kappa_max_host = slot ? slot->host : nullptr;
-            a.plane_sums = psum.defined() ? psum.data_ptr<float>() : nullptr;
-            for (int j = 0; j < 4; ++j) save.push_back(p[j]);
+            a.kappa_max = km.dev();
+            a.kappa_max_host = km.host();
+            a.plane_sums = fptr(psum);
+            // (the views may be fp32 copies of 16-bit parameters: alive until the launch on every route)
+            for (int j = 0; j < 4; ++j) (input_only ? views : save).push_back(p[j]);
             save.push_back(Mf);
             hold.push_back(sws);
             states_v.push_back(states);
             sums_v.push_back(psum);
-            meta.push_back((int64_t)flat[5 * i + 4].scalar_type());
+            mdt.push_back((int64_t)flat[5 * i + 4].scalar_type());
+            if (need_grad && !input_only) save_shapes(ctx, {&flat[5 * i], &flat[5 * i + 1], &flat[5 * i + 2], &flat[5 * i + 3]}, i);
         }
         Tensor out = at::empty_like(u);
         Slot* last = want_kmax ? reinterpret_cast<Slot*>((intptr_t)slots.back()) : nullptr;   // recorded behind the last layer's copy
-        check(pde_adi_multi_forward(nl, arr.data(), u.data_ptr(), out.data_ptr(), last ? (void*)last->ev : nullptr, (void*)st),
+        check(pde_adi_multi_forward(nl, arr.data(), u.data_ptr(), out.data_ptr(), last ? (void*)last->ev : nullptr,
+                                    (void*)pr.dev.st),
               "pde_adi_multi_forward");
-        if (input_only) {
-            std::vector<Tensor> keep{wdev};
-            for (int i = 0; i < nl; ++i) keep.push_back(save[2 + 5 * i + 4]);
-            ctx->save_for_backward(keep);
-            ctx->saved_data["hold"] = hold;                   // the steps workspaces, one per layer
-            ctx->saved_data["descs"] = std::string(reinterpret_cast<const char*>(descs.data()), sizeof(PdeAdiDesc) * nl);
-            ctx->saved_data["cfg"] = std::vector<int64_t>{nl, sps, want_sums ? 1 : 0, ckpt_mode, weights.defined() ? 1 : 0};
-            ctx->saved_data["input_only"] = (int64_t)u.scalar_type();
-            ctx->saved_data["ushape"] = u.sizes().vec();
-        } else if (need_grad) {
+        if (need_grad) {
+            // frozen: the weights and the operators; else the input, the weights, per layer four views and the operator
             ctx->save_for_backward(save);
-            ctx->saved_data["hold"] = hold;
-            ctx->saved_data["states"] = states_v;
-            if (want_kmax) ctx->saved_data["tickets"] = tickets;
-            ctx->saved_data["slots"] = slots;
-            ctx->saved_data["descs"] = std::string(reinterpret_cast<const char*>(descs.data()), sizeof(PdeAdiDesc) * nl);
-            ctx->saved_data["cfg"] = std::vector<int64_t>{nl, sps, want_sums ? 1 : 0, ckpt_mode,
-                                                          weights.defined() ? 1 : 0};
-            ctx->saved_data["masks"] = masks;
-            ctx->saved_data["mdt"] = meta;
-            ctx->saved_data["amax"] = amax;
-            for (int i = 0; i < 4 * nl; ++i)
-                ctx->saved_data["sh" + std::to_string(i)] = flat[5 * (i / 4) + (i % 4)].sizes().vec();
+            ctx->saved_data["hold"] = hold;                   // per layer [kdev with coefficient maxima,] the steps workspace
+            save_desc(ctx, descs.data(), nl);
+            ctx->saved_data["cfg"] = std::vector<int64_t>{nl, sps, want_sums ? 1 : 0, ckpt_mode, weights.defined() ? 1 : 0};
+            if (input_only) {
+                save_input_only(ctx, u);
+                ctx->saved_data["ushape"] = u.sizes().vec();
+            } else {
+                ctx->saved_data["states"] = states_v;
+                if (want_kmax) ctx->saved_data["tickets"] = tickets;
+                ctx->saved_data["slots"] = slots;
+                ctx->saved_data["masks"] = masks;
+                ctx->saved_data["mdt"] = mdt;
+                ctx->saved_data["amax"] = amax;
+            }
         }
         variable_list res{out};
         for (int i = 0; i < nl; ++i) res.push_back(states_v[i].select(0, states_v[i].size(0) - 1));   // the last sweep output of every layer
@@ -778,139 +787,74 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
         auto saved = ctx->get_saved_variables();
         auto cfg = ctx->saved_data["cfg"].toIntVector();
         const int nl = (int)cfg[0], sps = (int)cfg[1];
-        const bool want_sums = cfg[2] != 0;
         const Tensor& wdev = saved[0];
-        const auto dtype = static_cast<at::ScalarType>(ctx->saved_data["input_only"].toInt());
+        const auto dtype = input_only_dtype(ctx);
         std::vector<PdeAdiDesc> descs(nl);
-        std::memcpy(descs.data(), ctx->saved_data["descs"].toStringRef().data(), sizeof(PdeAdiDesc) * nl);
+        load_desc(ctx, descs.data(), nl);
         auto hold = ctx->saved_data["hold"].toTensorVector();
         const Tensor& like = saved[1];
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(like.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(like.device().index()).stream();
-        Tensor gout = grads[0];
-        if (gout.defined()) {
-            if (gout.scalar_type() != dtype) gout = gout.to(dtype);
-            gout = aligned(gout.contiguous());
-        }
+        OnDevice dev(like);
+        Tensor gout = cotangent(grads[0], dtype);
         std::vector<PdeSmallLayer> arr(nl);
         std::vector<Tensor> keep;
         bool any_in = gout.defined();
         for (int i = 0; i < nl; ++i) {
-            PdeAdiDesc& d = descs[i];
-            Tensor gyi = grads[1 + i], gsi = want_sums ? grads[1 + nl + i] : Tensor();
-            if (gyi.defined()) {
-                if (gyi.scalar_type() != dtype) gyi = gyi.to(dtype);
-                gyi = aligned(gyi.contiguous());
-            }
-            if (gsi.defined()) {
-                if (gsi.scalar_type() != at::kFloat) gsi = gsi.to(at::kFloat);
-                gsi = aligned(gsi.contiguous());
-            }
-            any_in = any_in || gyi.defined() || gsi.defined();
+            PdeSmallLayer& a = arr[i] = layer_record(&descs[i], sps, saved[1 + i], wdev, i, hold[i]);
+            any_in = set_cotangents(a, grads, i, nl, cfg[2] != 0, dtype, keep) || any_in;
             // (the slab of a side-by-side group; the query is what the library checks against, used or not)
-            Tensor ws = nl > 1 ? bytes(pde_adi_small_backward_input_workspace_bytes(&d, sps), like) : Tensor();
-            PdeSmallLayer& a = arr[i];
-            std::memset(&a, 0, sizeof(a));
-            a.desc = &d;
-            a.sweeps_per_step = sps;
-            a.mode = 1;
-            a.M = saved[1 + i].data_ptr<float>();
-            a.weight = 0.f;
-            a.weight_ptr = wdev.defined() ? wdev.data_ptr<float>() + i : nullptr;
-            a.steps_workspace = hold[i].data_ptr();
-            a.steps_workspace_bytes = (size_t)hold[i].numel();
-            a.gys = gyi.defined() ? gyi.data_ptr() : nullptr;
-            a.g_plane_sums = gsi.defined() ? gsi.data_ptr<float>() : nullptr;
-            if (ws.defined()) {
-                a.workspace = ws.data_ptr();
-                a.workspace_bytes = (size_t)ws.numel();
-            }
+            Tensor ws = nl > 1 ? bytes(pde_adi_small_backward_input_workspace_bytes(&descs[i], sps), like) : Tensor();
+            a.workspace = vptr(ws);
+            a.workspace_bytes = ws.defined() ? (size_t)ws.numel() : 0;
             keep.push_back(ws);
-            keep.push_back(gyi);
-            keep.push_back(gsi);
         }
         PDE_REQUIRE(any_in, "adi_diffuse_multi: no incoming gradient");
         Tensor gu = at::empty(ctx->saved_data["ushape"].toIntVector(), like.options().dtype(dtype));
-        check(pde_adi_multi_backward_input(nl, arr.data(), gout.defined() ? gout.data_ptr() : nullptr, gu.data_ptr(), (void*)st),
+        check(pde_adi_multi_backward_input(nl, arr.data(), vptr(gout), gu.data_ptr(), (void*)dev.st),
               "pde_adi_multi_backward_input");
-        variable_list res(2 + 5 * nl + 7);
-        res[0] = gu;
-        return res;
+        return grads_out(2 + 5 * nl + 7, {gu});
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
-        if (ctx->saved_data.count("input_only")) return backward_input(ctx, grads);
+        if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         auto cfg = ctx->saved_data["cfg"].toIntVector();
         const int nl = (int)cfg[0], sps = (int)cfg[1];
-        const bool want_sums = cfg[2] != 0, has_w = cfg[4] != 0;
+        const bool has_w = cfg[4] != 0, planned = cfg[3] == 1;
         const Tensor &u = saved[0], &wdev = saved[1];
         std::vector<PdeAdiDesc> descs(nl);
-        std::memcpy(descs.data(), ctx->saved_data["descs"].toStringRef().data(), sizeof(PdeAdiDesc) * nl);
+        load_desc(ctx, descs.data(), nl);
         auto slots = ctx->saved_data["slots"].toIntVector();
         auto masks = ctx->saved_data["masks"].toIntVector();
         auto mdt = ctx->saved_data["mdt"].toIntVector();
         auto states_v = ctx->saved_data["states"].toTensorVector();
         auto hold = ctx->saved_data["hold"].toTensorVector();
         const double amax = ctx->saved_data["amax"].toDouble();
-        if (cfg[3] == 1) wait_event(reinterpret_cast<Slot*>((intptr_t)slots.back())->ev);
-        c10::hip::HIPGuardMasqueradingAsCUDA guard(u.device());
-        hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(u.device().index()).stream();
-
-        Tensor gout = grads[0];
-        if (gout.defined()) {
-            if (gout.scalar_type() != u.scalar_type()) gout = gout.to(u.scalar_type());
-            gout = aligned(gout.contiguous());
-        }
+        if (planned) wait_event(reinterpret_cast<Slot*>((intptr_t)slots.back())->ev);
+        OnDevice dev(u);
+        Tensor gout = cotangent(grads[0], u.scalar_type());
         std::vector<PdeSmallLayer> arr(nl);
         std::vector<uint64_t> mk(2 * nl);
-        std::vector<Tensor> keep;
+        std::vector<Tensor> keep, gws;
         variable_list res(2 + 5 * nl + 7);                    // u, weights, five per layer, the seven non-tensor arguments
-        std::vector<Tensor> gws;
         bool any_in = gout.defined();
-        const int kmax_stride = cfg[3] == 1 ? 2 : 1;          // hold: [kdev, sws] per layer with coefficient maxima, else [sws]
         for (int i = 0; i < nl; ++i) {
             PdeAdiDesc& d = descs[i];
-            const int K = d.num_sweeps / sps;
             uint64_t* m = &mk[2 * i];
             m[0] = m[1] = 0;
-            if (cfg[3] == 1) plan_steps(reinterpret_cast<Slot*>((intptr_t)slots[i])->host, K, sps, amax, m);
+            if (planned) plan_steps(reinterpret_cast<Slot*>((intptr_t)slots[i])->host, d.num_sweeps / sps, sps, amax, m);
             else m[0] = (uint64_t)masks[i];
             const Tensor* p = &saved[2 + 5 * i];
             const Tensor& Mf = saved[2 + 5 * i + 4];
             Tensor ws = bytes(pde_adi_small_backward_workspace_bytes(&d, sps, popcount2(m)), u);
             Tensor gp[4];
-            for (int j = 0; j < 4; ++j) gp[j] = at::empty(ctx->saved_data["sh" + std::to_string(4 * i + j)].toIntVector(), p[j].options());
+            param_grads(ctx, p, gp, i);
             Tensor gM = at::empty_like(Mf);
             Tensor gw = at::empty({1}, Mf.options());
-            Tensor gyi = grads[1 + i], gsi = want_sums ? grads[1 + nl + i] : Tensor();
-            if (gyi.defined()) {
-                if (gyi.scalar_type() != u.scalar_type()) gyi = gyi.to(u.scalar_type());
-                gyi = aligned(gyi.contiguous());
-            }
-            if (gsi.defined()) {
-                if (gsi.scalar_type() != at::kFloat) gsi = gsi.to(at::kFloat);
-                gsi = aligned(gsi.contiguous());
-            }
-            any_in = any_in || gyi.defined() || gsi.defined();
-            const Tensor& sws = hold[kmax_stride * i + (kmax_stride - 1)];
-            PdeSmallLayer& a = arr[i];
-            std::memset(&a, 0, sizeof(a));
-            a.desc = &d;
-            a.sweeps_per_step = sps;
-            a.mode = 1;
-            a.M = Mf.data_ptr<float>();
-            a.alpha_base = p[0].data_ptr<float>();
-            a.beta_base = p[1].data_ptr<float>();
-            a.alpha_slope = p[2].data_ptr<float>();
-            a.beta_slope = p[3].data_ptr<float>();
-            a.weight = 0.f;
-            a.weight_ptr = wdev.defined() ? wdev.data_ptr<float>() + i : nullptr;
+            // hold: [kdev, sws] per layer with coefficient maxima, else [sws]
+            PdeSmallLayer& a = arr[i] = layer_record(&d, sps, Mf, wdev, i, hold[planned ? 2 * i + 1 : i]);
+            set_coeffs(a, p);
+            any_in = set_cotangents(a, grads, i, nl, cfg[2] != 0, u.scalar_type(), keep) || any_in;
             a.states = states_v[i].data_ptr();
-            a.steps_workspace = sws.data_ptr();
-            a.steps_workspace_bytes = (size_t)sws.numel();
-            a.gys = gyi.defined() ? gyi.data_ptr() : nullptr;
-            a.g_plane_sums = gsi.defined() ? gsi.data_ptr<float>() : nullptr;
             a.ckpt_mask = m;
             a.g_alpha_base = gp[0].data_ptr<float>();
             a.g_beta_base = gp[1].data_ptr<float>();
@@ -921,19 +865,15 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
             a.workspace = ws.data_ptr();
             a.workspace_bytes = (size_t)ws.numel();
             keep.push_back(ws);
-            keep.push_back(gyi);
-            keep.push_back(gsi);
             for (int j = 0; j < 4; ++j) res[2 + 5 * i + j] = gp[j];
             res[2 + 5 * i + 4] = gM;                                        // converted to the operator's type behind the launch
             gws.push_back(gw);
         }
         PDE_REQUIRE(any_in, "adi_diffuse_multi: no incoming gradient");
         Tensor gu = at::empty_like(u);
-        check(pde_adi_multi_backward(nl, arr.data(), gout.defined() ? gout.data_ptr() : nullptr, u.data_ptr(), gu.data_ptr(),
-                                     (void*)st),
+        check(pde_adi_multi_backward(nl, arr.data(), vptr(gout), u.data_ptr(), gu.data_ptr(), (void*)dev.st),
               "pde_adi_multi_backward");
-        for (int i = 0; i < nl; ++i)
-            if ((int64_t)res[2 + 5 * i + 4].scalar_type() != mdt[i]) res[2 + 5 * i + 4] = res[2 + 5 * i + 4].to((at::ScalarType)mdt[i]);
+        for (int i = 0; i < nl; ++i) res[2 + 5 * i + 4] = as_dtype(res[2 + 5 * i + 4], mdt[i]);
         res[0] = gu;
         if (has_w) res[1] = at::cat(gws);
         return res;
@@ -950,6 +890,7 @@ variable_list multi(const Tensor& u, const std::optional<Tensor>& weights, std::
     return MultiFn::apply(u, wo, at::TensorList(flat), desc_addrs, sps, want_sums, ckpt_mode, masks, amax,
                           grad_mode_of(u, params));
 }
+
 
 
 // ---- the Ruthotto-Haber symmetric layer (functional._SymLayerFn: cifar_2version.py:190-258) ----------------------------

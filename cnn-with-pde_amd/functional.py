@@ -264,9 +264,14 @@ def _grad_as(g, dtype, shape=None):
     return g if g.dtype == dtype else g.to(dtype)
 
 
-def _cotangents(g, like, sel, align: int = ALIGN):
+def _cotangent(g, dtype, align: int = ALIGN):
+    """A cotangent as the library takes it: in the type of the tensor it belongs to, contiguous, aligned; None stays None."""
+    return None if g is None else _aligned(_grad_as(g, dtype).contiguous(), align)
+
+
+def _cotangents(g, dtype, sel, align: int = ALIGN):
     """(gradient of the library's output, gradient of the trajectory tensor or None) from the node's cotangent."""
-    g = _aligned(_grad_as(g, like.dtype).contiguous(), align)
+    g = _cotangent(g, dtype, align)
     return (g, None) if sel is None else (g[-1], g)       # slots 0..K'-2 are the states' gradients, the last slice is gy
 
 
@@ -488,6 +493,104 @@ class _KmaxConcat:
         return [v for p in self.parts for v in p.wait()]
 
 
+# ---- what the implicit-layer nodes below share: each decision is taken in one place (csrc/host_ext.cpp cuts its nodes the
+# same way, and the two mirrors stay bitwise alike: tests/test_gpu_node_calls.py) --------------------------------------
+def _grad_route(need_u, need_params, input_route: bool = True) -> str:
+    """"none" / "full" / "input_only" from what needs a gradient (``grad_mode_of`` in csrc/host_ext.cpp).  "input_only":
+    the input does and no parameter does, so the backward is gu = F^T gy alone — unless the family has no such backward
+    (``input_route`` False) or ``PDE_BWD_INPUT=0`` keeps the full one."""
+    if need_params:
+        return "full"
+    if not need_u:
+        return "none"
+    return "input_only" if input_route and L.bwd_input_enabled() else "full"
+
+
+def _want_kmax(route: str, ckpt, kmax_sink) -> bool:
+    """Whether the forward asks for its per-sweep coefficient maxima.  The full backward plans its checkpoints from them
+    under "auto"; the input-only backward plans nothing, so there — as wherever an explicit mask was given — only a caller
+    who handed in a sink gets them (``_AdiMultiFn`` has no sink: it never asks on the frozen route)."""
+    if route == "none":
+        return False
+    return kmax_sink is not None or (route == "full" and ckpt == "auto")
+
+
+def _kmax_request(want: bool, n: int, device, kmax_sink=None):
+    """(device buffer, ticket, the entry points' three maxima arguments) of a forward that asks for ``n`` coefficient maxima
+    — all NULL when it does not.  The maxima are a by-product of the factorisation kernel, copied to pinned host memory
+    right behind it, so whoever plans checkpoints from them waits for the factorisation only.  The ticket goes to
+    ``kmax_sink`` when there is one.  Call with the input's device current."""
+    if not want:
+        return None, None, (_ptr(None), _ptr(None), C.c_void_p(0))
+    kdev = torch.empty(n, dtype=torch.float32, device=device)
+    tk = _kmax_channel(n)
+    if kmax_sink is not None:
+        kmax_sink.append(tk)
+    return kdev, tk, (_ptr(kdev), _ptr(tk.host), C.c_void_p(tk.event.cuda_event))
+
+
+def _plan_steps(km: Sequence[float], K: int, sps: int) -> int:
+    """One step-local checkpoint mask for all ``K`` steps of ``sps`` sweeps: the union of the steps' own plans
+    (``plan_steps`` in csrc/host_ext.cpp)."""
+    bits = 0
+    for k in range(K):
+        bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
+    return bits
+
+
+def _steps_prologue(lib, u, ab, bb, asl, bsl, M, steps, smooth3, clamp_max, eps):
+    """What the forward of a layer with a channel operator between its steps builds from the kernel input ``u``: the four
+    coefficient views, the operator in fp32, the descriptor, sweeps per step, steps, and the steps workspace (the
+    factorisation, which the backward reuses)."""
+    B, Cc, N, _ = u.shape
+    sps, K = len(steps[0]), len(steps)
+    sweeps = steps.flat if isinstance(steps, Schedule) else tuple(s for st in steps for s in st)
+    p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
+    Mf = _aligned(M.detach().to(torch.float32).contiguous())
+    d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
+    sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
+    return p, Mf, d, sps, K, sws
+
+
+def _param_meta(*params):
+    return [(t.shape, t.dtype) for t in params]
+
+
+def _grads_like(p):
+    """The library's parameter gradients: one fp32 (double on the float64 route) tensor per coefficient view."""
+    return [torch.empty_like(t) for t in p]
+
+
+def _grads_as(gp, meta):
+    """... handed back in the callers' shapes — (N, N) at C = 1 — and types."""
+    return [_grad_as(g, dt, s) for g, (s, dt) in zip(gp, meta)]
+
+
+_SMALL_COEFFS = ("alpha_base", "beta_base", "alpha_slope", "beta_slope")
+
+
+def _small_layer(a, i, d, sps, Mf, wdev, sws, p=None, gp=None, ws=None, mask=None, **tensors):
+    """Fill ``a``, the PdeSmallLayer record of layer ``i`` of a shared-input group: what every pass sets, then what this
+    pass has — coefficient views ``p``, their gradients ``gp``, the backward's workspace and checkpoint mask, and any
+    other pointer field by name (a None stays NULL, as a fresh record has it)."""
+    a.desc, a.sweeps_per_step, a.mode = C.pointer(d), sps, 1
+    a.M = Mf.data_ptr()
+    a.weight = 0.0
+    a.weight_ptr = None if wdev is None else wdev.data_ptr() + 4 * i
+    a.steps_workspace, a.steps_workspace_bytes = sws.data_ptr(), sws.numel()
+    if p is not None:
+        a.alpha_base, a.beta_base, a.alpha_slope, a.beta_slope = (t.data_ptr() for t in p)
+    if gp is not None:
+        a.g_alpha_base, a.g_beta_base, a.g_alpha_slope, a.g_beta_slope = (t.data_ptr() for t in gp)
+    if ws is not None:
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if mask is not None:
+        a.ckpt_mask = mask
+    for name, t in tensors.items():
+        if t is not None:
+            setattr(a, name, t.data_ptr())
+
+
 class _AdiFn(torch.autograd.Function):
     """The implicit sweeps through ctypes, the general path: ``adi_diffuse`` and ``adi_diffuse_states`` of the four
     sub-families ``_ADI_FAMILY`` tells apart — squares and rectangles, fp32 / bf16 / fp16 tensors and float64 (every
@@ -527,38 +630,26 @@ class _AdiFn(torch.autograd.Function):
         out, y, traj = _out_and_traj(u, emit)
         ebits = None if emit is None else sum(1 << s for s in emit[:-1])
         ws = _workspace(getattr(lib, fam + "forward_workspace_bytes")(C.byref(d)), u.device)
-        need_grad = any(ctx.needs_input_grad[:5])
-        # frozen coefficients: the backward is gu = F^T gy alone (*_backward_input_states).  It reads neither y nor u and
-        # plans no checkpoints, so nothing of u's shape is kept and no coefficient maxima are asked for — unless the
-        # caller handed in a sink for them
-        input_only = need_grad and not any(ctx.needs_input_grad[1:5]) and L.bwd_input_enabled()
-        if input_only:
-            want_kmax = not f64 and kmax_sink is not None
-        else:
-            want_kmax = not f64 and need_grad and (ckpt == "auto" or kmax_sink is not None)
-        kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
+        # frozen coefficients: the backward (*_backward_input_states) reads neither y nor u and plans no checkpoints, so
+        # nothing of u's shape is kept
+        route = _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5]))
         with torch.cuda.device(u.device):
-            # per-sweep maximum coefficient (a by-product of the factorisation kernel): copied to pinned host
-            # memory right behind that kernel, before the sweep launch, so whoever plans checkpoints from it
-            # waits for the factorisation only.  The float64 entry points take the device pointer alone (never set)
-            tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            kmax = (None,) if f64 else (_ptr(kdev), _ptr(tk.host if tk else None),
-                                        C.c_void_p(tk.event.cuda_event if tk else 0))
+            kdev, ctx.kmax, kargs = _kmax_request(not f64 and _want_kmax(route, ckpt, kmax_sink), len(sweeps), u.device,
+                                                  kmax_sink)
+            if f64:
+                kargs = (None,)                      # the float64 entry points take the device pointer alone (never set)
             L.check(getattr(lib, fam + "forward_states")(C.byref(d), _ptr(u), _ptr(y), _ptr(traj),
                                                          None if emit is None else _mask128(ebits),
-                                                         *[_ptr(t) for t in p], *kmax, _ptr(ws), ws.numel(), _stream()),
+                                                         *[_ptr(t) for t in p], *kargs, _ptr(ws), ws.numel(), _stream()),
                     fam + "forward_states")
-            ctx.kmax = tk
-            if tk is not None and kmax_sink is not None:
-                kmax_sink.append(tk)
-        ctx.fwd_ws = ws if need_grad else None       # factorisation reused by the backward
-        ctx.input_only = (out.shape, out.dtype, out.device) if input_only else None
-        if input_only:
+        ctx.fwd_ws = ws if route != "none" else None     # factorisation reused by the backward
+        ctx.input_only = (out.shape, out.dtype, out.device) if route == "input_only" else None
+        if route == "input_only":
             ctx.save_for_backward(*p)
         else:
-            ctx.save_for_backward(out, u if (need_grad and ckpt != 0) else None, *p)
-        ctx.cfg = (sweeps, smooth3, clamp_max, eps, ckpt, rect, f64, ebits)
-        ctx.param_meta = [(t.shape, t.dtype) for t in (ab, bb, asl, bsl)]
+            ctx.save_for_backward(out, u if (route == "full" and ckpt != 0) else None, *p)
+        ctx.cfg = (d, fam, ckpt, ebits)
+        ctx.param_meta = _param_meta(ab, bb, asl, bsl)
         return out
 
     @staticmethod
@@ -567,14 +658,11 @@ class _AdiFn(torch.autograd.Function):
         if ctx.input_only is not None:
             return _AdiFn._backward_input(ctx, g)
         out, u, *p = ctx.saved_tensors
-        sweeps, smooth3, clamp_max, eps, ckpt, rect, f64, ebits = ctx.cfg
-        B, Cc, H, W = out.shape[-4:]
-        fam, desc_cls, _ = _ADI_FAMILY[rect, f64]
+        d, fam, ckpt, ebits = ctx.cfg
         y = out if ebits is None else out[-1]
-        gy, gtraj = _cotangents(g, out, ebits, ctx.align)
-        d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(out), sweeps, smooth3, clamp_max, eps)
+        gy, gtraj = _cotangents(g, out.dtype, ebits, ctx.align)
         gu = torch.empty_like(y)
-        gp = [torch.empty_like(t) for t in p]
+        gp = _grads_like(p)
         bits = plan_checkpoints(ctx.kmax.wait()) if ckpt == "auto" else int(ckpt)
         ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(C.byref(d), bin(bits).count("1")), out.device)
         with torch.cuda.device(out.device):          # autograd thread: set device, fetch the stream here
@@ -585,22 +673,17 @@ class _AdiFn(torch.autograd.Function):
                                                           _ptr(ctx.fwd_ws), _ptr(ws), ws.numel(), _stream()),
                     fam + "backward_states")
         ctx.fwd_ws = None
-        gp = [_grad_as(t, dt, s) for t, (s, dt) in zip(gp, ctx.param_meta)]
-        return (gu, *gp) + (None,) * 9
+        return (gu, *_grads_as(gp, ctx.param_meta)) + (None,) * 9
 
     @staticmethod
     def _backward_input(ctx, g):
         """The backward of a call whose coefficients take no gradient: the family's ``*_backward_input_states``."""
         lib = L.load()
         p = ctx.saved_tensors
-        sweeps, smooth3, clamp_max, eps, _, rect, f64, ebits = ctx.cfg
+        d, fam, _, ebits = ctx.cfg
         shape, dtype, device = ctx.input_only
-        B, Cc, H, W = shape[-4:]
-        fam, desc_cls, _ = _ADI_FAMILY[rect, f64]
-        g = _aligned(_grad_as(g, dtype).contiguous(), ctx.align)
-        gy, gtraj = (g, None) if ebits is None else (g[-1], g)
-        d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(g), sweeps, smooth3, clamp_max, eps)
-        gu = torch.empty((B, Cc, H, W), dtype=dtype, device=device)
+        gy, gtraj = _cotangents(g, dtype, ebits, ctx.align)
+        gu = torch.empty(shape[-4:], dtype=dtype, device=device)
         ws = _workspace(getattr(lib, fam + "backward_input_workspace_bytes")(C.byref(d)), device)
         with torch.cuda.device(device):              # autograd thread: set device, fetch the stream here
             L.check(getattr(lib, fam + "backward_input_states")(C.byref(d), _ptr(gy), _ptr(gtraj),
@@ -627,38 +710,24 @@ class _AdiMixedFn(torch.autograd.Function):
         _require_cuda(u, ab, bb, asl, bsl, M)
         if u.dim() != 4 or u.shape[2] != u.shape[3]:
             raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
-        B, Cc, N, _ = u.shape
-        if u.dtype not in _IO_TYPES:
-            u = u.float()
-        u = _aligned(u.contiguous())
-        sps, K = len(steps[0]), len(steps)
-        sweeps = tuple(s for st in steps for s in st)
-        p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        Mf = _aligned(M.detach().to(torch.float32).contiguous())
-        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-        sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
-        need_grad = any(ctx.needs_input_grad[:6])
-        want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
-        kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
+        u = _kernel_input(u, False)
+        p, Mf, d, sps, K, sws = _steps_prologue(lib, u, ab, bb, asl, bsl, M, steps, smooth3, clamp_max, eps)
+        route = _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:6]), input_route=False)
         # states[2k]: output of step k's first operator, states[2k+1]: of its second (= input of step k+1); the last of them
         # is the layer output and lives in a tensor of its own (no copy, and nobody can reach the kept states through it)
         states = torch.empty((2 * K - 1,) + tuple(u.shape), dtype=u.dtype, device=u.device)
         y = torch.empty_like(u)
+        m = 1 if mode == "pre" else 2
         with torch.cuda.device(u.device):
-            tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            L.check(lib.pde_adi_mixed_forward(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(states), _ptr(y), _ptr(Mf),
-                                              *[_ptr(t) for t in p], _ptr(kdev), _ptr(tk.host if tk else None),
-                                              C.c_void_p(tk.event.cuda_event if tk else 0),
-                                              _ptr(sws), sws.numel(), _stream()),
+            kdev, ctx.kmax, kargs = _kmax_request(_want_kmax(route, ckpt, kmax_sink), d.num_sweeps, u.device, kmax_sink)
+            L.check(lib.pde_adi_mixed_forward(C.byref(d), sps, m, _ptr(u), _ptr(states), _ptr(y), _ptr(Mf),
+                                              *[_ptr(t) for t in p], *kargs, _ptr(sws), sws.numel(), _stream()),
                     "pde_adi_mixed_forward")
-            ctx.kmax = tk
-            if want_kmax and kmax_sink is not None:
-                kmax_sink.append(tk)
-        if need_grad:
+        if route != "none":
             ctx.save_for_backward(u, states, y, Mf, *p)
             ctx.sws = sws
-        ctx.cfg = (steps, mode, smooth3, clamp_max, eps, ckpt)
-        ctx.param_shapes = [t.shape for t in (ab, bb, asl, bsl)]
+        ctx.cfg = (d, sps, K, m, ckpt)
+        ctx.param_meta = _param_meta(ab, bb, asl, bsl)
         ctx.M_dtype = M.dtype
         return y
 
@@ -666,32 +735,18 @@ class _AdiMixedFn(torch.autograd.Function):
     def backward(ctx, gy):
         lib = L.load()
         u, states, y, Mf, *p = ctx.saved_tensors
-        steps, mode, smooth3, clamp_max, eps, ckpt = ctx.cfg
-        B, Cc, N, _ = u.shape
-        sps, K, HW = len(steps[0]), len(steps), N * N
-        sweeps = tuple(s for st in steps for s in st)
-        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-        if ckpt == "auto":
-            km = ctx.kmax.wait()
-            bits = 0
-            for k in range(K):                           # one step-local mask for every step: the union
-                bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
-        else:
-            bits = int(ckpt)
-        nck = bin(bits).count("1")
-        mask = _mask128(bits)
-        ws = _workspace(lib.pde_adi_mixed_backward_workspace_bytes(C.byref(d), sps, nck), u.device)
-        g_in = _aligned(gy.to(u.dtype).contiguous())
+        d, sps, K, m, ckpt = ctx.cfg
+        bits = _plan_steps(ctx.kmax.wait(), K, sps) if ckpt == "auto" else int(ckpt)
+        ws = _workspace(lib.pde_adi_mixed_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
+        g_in = _cotangent(gy, u.dtype)
         g_a = torch.empty_like(g_in)
-        gp = [torch.empty_like(t) for t in p]
-        gM = torch.empty_like(Mf)
+        gp, gM = _grads_like(p), torch.empty_like(Mf)
         with torch.cuda.device(u.device):
-            L.check(lib.pde_adi_mixed_backward(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(g_in), _ptr(u), _ptr(states),
-                                               _ptr(y), _ptr(Mf), mask, _ptr(g_a), *[_ptr(t) for t in p], *[_ptr(t) for t in gp],
+            L.check(lib.pde_adi_mixed_backward(C.byref(d), sps, m, _ptr(g_in), _ptr(u), _ptr(states), _ptr(y), _ptr(Mf),
+                                               _mask128(bits), _ptr(g_a), *[_ptr(t) for t in p], *[_ptr(t) for t in gp],
                                                _ptr(gM), _ptr(ctx.sws), _ptr(ws), ws.numel(), _stream()),
                     "pde_adi_mixed_backward")
-        gp = [g.reshape(s) for g, s in zip(gp, ctx.param_shapes)]
-        return (g_a, *gp, gM.to(ctx.M_dtype), None, None, None, None, None, None, None)
+        return (g_a, *_grads_as(gp, ctx.param_meta), _grad_as(gM, ctx.M_dtype)) + (None,) * 7
 
 
 class _AdiSmallFn(torch.autograd.Function):
@@ -699,112 +754,109 @@ class _AdiSmallFn(torch.autograd.Function):
     (pde_adi_small_*): cifar10.py:84-112 ("pre"), SVHN.py:55-76 ("post", with the skip blend when ``skip_weight``
     is given).  The sweep output of every step is kept for the backward, as autograd keeps it in the reference.
 
-    When ``u`` needs a gradient and neither a coefficient tensor, ``M`` nor ``skip_weight`` does, the forward is
-    ``pde_adi_small_forward_input`` and the backward ``pde_adi_small_backward_input``: gu = F^T gy alone, bitwise the full
+    ``emit`` None is the plain call (``adi_diffuse_small``) and returns ``y``.  Otherwise (``adi_diffuse_small_states``:
+    no skip blend) ``emit`` lists the time steps whose state is returned too, the last one included, out of the same
+    launch per pass (pde_adi_small_forward_states / pde_adi_small_backward_states), and the result is ONE tensor
+    (K', B, C, N, N) whose last slice is the library's ``y``.
+
+    When ``u`` needs a gradient and neither a coefficient tensor, ``M`` nor ``skip_weight`` does, the forward keeps no
+    states — ``pde_adi_small_forward_input``, or for a trajectory with a non-empty mask the emitting forward with ``states``
+    NULL — and the backward is ``pde_adi_small_backward_input`` / ``_input_states``: gu = F^T gy alone, bitwise the full
     backward's gu.  No (K, B, C, N, N) tensor is allocated, ``u`` is not saved, ``checkpoints`` is ignored and no
     coefficient maxima are asked for unless a ``kmax_sink`` was handed in; ``M``, ``skip_weight`` and the steps workspace
     stay alive.  ``PDE_BWD_INPUT=0`` keeps the full backward for such calls."""
 
     @staticmethod
-    def forward(ctx, u, ab, bb, asl, bsl, M, skip_weight, steps, mode, smooth3, clamp_max, eps, ckpt, kmax_sink):
+    def forward(ctx, u, ab, bb, asl, bsl, M, skip_weight, steps, mode, smooth3, clamp_max, eps, ckpt, kmax_sink, emit=None):
         lib = L.load()
         _require_cuda(u, ab, bb, asl, bsl, M, skip_weight)
-        B, Cc, N, _ = u.shape
-        if u.dtype not in _IO_TYPES:
-            u = u.float()
-        u = _aligned(u.contiguous())
-        sps, K = len(steps[0]), len(steps)
-        sweeps = steps.flat
-        p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        Mf = _aligned(M.detach().to(torch.float32).contiguous())
+        u = _kernel_input(u, False)
+        p, Mf, d, sps, K, sws = _steps_prologue(lib, u, ab, bb, asl, bsl, M, steps, smooth3, clamp_max, eps)
         sw = None if skip_weight is None else skip_weight.detach().to(torch.float32).reshape(1).contiguous()
-        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-        sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
-        need_grad = any(ctx.needs_input_grad[:7])
-        input_only = ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:7]) and L.bwd_input_enabled()
-        if input_only:
-            want_kmax = kmax_sink is not None
+        route = _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:7]))
+        out, y, traj = _out_and_traj(u, emit)
+        ebits = None if emit is None else sum(1 << k for k in emit[:-1])
+        # where the two public calls differ beyond the mask: an empty mask is the plain call, which goes on from the rounded
+        # sweep outputs of 16-bit tensors only when it keeps them; a trajectory call keeps them under no_grad too, so that
+        # its result is the same tensor in both grad modes — adi_diffuse_small under no_grad keeps none
+        keep = route == "full" or (route == "none" and ebits == 0 and u.element_size() < 4)
+        states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if keep else None
+        m = 1 if mode == "pre" else 2
+        if route == "input_only" and not ebits:          # parks nothing, y as with states kept
+            name, args = "pde_adi_small_forward_input", (_ptr(u), _ptr(y), _ptr(Mf), _ptr(sw))
+        elif emit is None:
+            name, args = "pde_adi_small_forward", (_ptr(u), _ptr(y), _ptr(states), _ptr(Mf), _ptr(sw))
         else:
-            want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
-        kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
-        states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if need_grad and not input_only else None
-        y = torch.empty_like(u)
+            name, args = "pde_adi_small_forward_states", (_ptr(u), _ptr(y), _ptr(states), _ptr(traj), _mask128(ebits), _ptr(Mf))
         with torch.cuda.device(u.device):
-            tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            tail = (*[_ptr(t) for t in p], _ptr(kdev), _ptr(tk.host if tk else None),
-                    C.c_void_p(tk.event.cuda_event if tk else 0), _ptr(sws), sws.numel(), _stream())
-            if input_only:                               # parks nothing, y as with states kept
-                L.check(lib.pde_adi_small_forward_input(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(y), _ptr(Mf),
-                                                        _ptr(sw), *tail), "pde_adi_small_forward_input")
-            else:
-                L.check(lib.pde_adi_small_forward(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(y), _ptr(states),
-                                                  _ptr(Mf), _ptr(sw), *tail), "pde_adi_small_forward")
-            ctx.kmax = tk
-            if want_kmax and kmax_sink is not None:
-                kmax_sink.append(tk)
-        ctx.input_only = (u.shape, u.dtype, u.device) if input_only else None
-        if input_only:
-            ctx.save_for_backward(Mf, sw)
-            ctx.sws = sws
-        elif need_grad:
-            ctx.save_for_backward(u, states, Mf, sw, *p)
-            ctx.sws = sws
-        ctx.cfg = (steps, mode, smooth3, clamp_max, eps, ckpt)
-        ctx.param_shapes = [t.shape for t in (ab, bb, asl, bsl)]
+            kdev, ctx.kmax, kargs = _kmax_request(_want_kmax(route, ckpt, kmax_sink), d.num_sweeps, u.device, kmax_sink)
+            L.check(getattr(lib, name)(C.byref(d), sps, m, *args, *[_ptr(t) for t in p], *kargs, _ptr(sws), sws.numel(),
+                                       _stream()), name)
+        ctx.input_only = (u.shape, u.dtype, u.device) if route == "input_only" else None
+        skip = (sw,) if emit is None else ()
+        if route == "input_only":
+            ctx.save_for_backward(Mf, *skip)
+        elif route == "full":
+            ctx.save_for_backward(u, states, Mf, *skip, *p)
+        ctx.sws = sws if route != "none" else None
+        ctx.cfg = (d, sps, K, m, ckpt, ebits)
+        ctx.param_meta = _param_meta(ab, bb, asl, bsl)
         ctx.M_dtype = M.dtype
-        ctx.skip_meta = None if skip_weight is None else (skip_weight.dtype, skip_weight.shape)
-        return y
+        ctx.skip_meta = None if skip_weight is None else (skip_weight.shape, skip_weight.dtype)
+        return out
 
     @staticmethod
-    def _backward_input(ctx, gy):
-        """The backward of a call whose parameters take no gradient: ``pde_adi_small_backward_input``."""
+    def _backward_input(ctx, g):
+        """The backward of a call whose parameters take no gradient: ``pde_adi_small_backward_input`` / ``_input_states``."""
         lib = L.load()
-        Mf, sw = ctx.saved_tensors
-        steps, mode, smooth3, clamp_max, eps, _ = ctx.cfg
+        Mf, *skip = ctx.saved_tensors
+        d, sps, _, m, _, ebits = ctx.cfg
         shape, dtype, device = ctx.input_only
-        B, Cc, N, _ = shape
-        g_in = _aligned(gy.to(dtype).contiguous())
-        d = _make_desc(B, Cc, N, _io_dtype(g_in), steps.flat, smooth3, clamp_max, eps)
-        gu = torch.empty_like(g_in)
+        gy, gtraj = _cotangents(g, dtype, ebits)
+        gu = torch.empty(shape, dtype=dtype, device=device)
+        if ebits is None:
+            name, args = "pde_adi_small_backward_input", (_ptr(gy), _ptr(Mf), _ptr(skip[0]), _ptr(gu))
+        else:
+            name, args = "pde_adi_small_backward_input_states", (_ptr(gy), _ptr(gtraj), _mask128(ebits), _ptr(Mf), _ptr(gu))
         with torch.cuda.device(device):
-            L.check(lib.pde_adi_small_backward_input(C.byref(d), len(steps[0]), 1 if mode == "pre" else 2, _ptr(g_in), _ptr(Mf),
-                                                     _ptr(sw), _ptr(gu), _ptr(ctx.sws), None, 0, _stream()),
-                    "pde_adi_small_backward_input")
-        return (gu,) + (None,) * 13
+            L.check(getattr(lib, name)(C.byref(d), sps, m, *args, _ptr(ctx.sws), None, 0, _stream()), name)
+        return (gu,) + (None,) * 14
 
     @staticmethod
-    def backward(ctx, gy):
+    def backward(ctx, g):
         lib = L.load()
         if ctx.input_only is not None:
-            return _AdiSmallFn._backward_input(ctx, gy)
-        u, states, Mf, sw, *p = ctx.saved_tensors
-        steps, mode, smooth3, clamp_max, eps, ckpt = ctx.cfg
-        B, Cc, N, _ = u.shape
-        sps, K = len(steps[0]), len(steps)
-        sweeps = steps.flat
-        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-        if ckpt == "auto":
-            km = ctx.kmax.wait()
-            bits = 0
-            for k in range(K):                           # one step-local mask for every step: the union
-                bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
-        else:
-            bits = int(ckpt)
-        mask = _mask128(bits)
+            return _AdiSmallFn._backward_input(ctx, g)
+        d, sps, K, m, ckpt, ebits = ctx.cfg
+        u, states, Mf, *rest = ctx.saved_tensors
+        sw, p = (rest[0] if ebits is None else None), rest[-4:]
+        bits = _plan_steps(ctx.kmax.wait(), K, sps) if ckpt == "auto" else int(ckpt)
         ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
-        g_in = _aligned(gy.to(u.dtype).contiguous())
-        gu = torch.empty_like(g_in)
-        gp = [torch.empty_like(t) for t in p]
-        gM = torch.empty_like(Mf)
+        gy, gtraj = _cotangents(g, u.dtype, ebits)
+        gu = torch.empty_like(u)
+        gp, gM = _grads_like(p), torch.empty_like(Mf)
         gsw = torch.empty(1, dtype=torch.float32, device=u.device) if sw is not None else None
+        pp = (*[_ptr(t) for t in p], *[_ptr(t) for t in gp], _ptr(gM))
+        if ebits is None:
+            name = "pde_adi_small_backward"
+            args = (_ptr(gy), _ptr(u), _ptr(states), _ptr(Mf), _ptr(sw), _mask128(bits), _ptr(gu), *pp, _ptr(gsw))
+        else:
+            name = "pde_adi_small_backward_states"
+            args = (_ptr(gy), _ptr(gtraj), _mask128(ebits), _ptr(u), _ptr(states), _ptr(Mf), _mask128(bits), _ptr(gu), *pp)
         with torch.cuda.device(u.device):
-            L.check(lib.pde_adi_small_backward(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(g_in), _ptr(u), _ptr(states),
-                                               _ptr(Mf), _ptr(sw), mask, _ptr(gu), *[_ptr(t) for t in p],
-                                               *[_ptr(t) for t in gp], _ptr(gM), _ptr(gsw), _ptr(ctx.sws), _ptr(ws),
-                                               ws.numel(), _stream()), "pde_adi_small_backward")
-        gp = [g.reshape(s) for g, s in zip(gp, ctx.param_shapes)]
-        gskip = None if sw is None else gsw.to(ctx.skip_meta[0]).reshape(ctx.skip_meta[1])
-        return (gu, *gp, gM.to(ctx.M_dtype), gskip, None, None, None, None, None, None, None)
+            L.check(getattr(lib, name)(C.byref(d), sps, m, *args, _ptr(ctx.sws), _ptr(ws), ws.numel(), _stream()), name)
+        gskip = None if sw is None else _grad_as(gsw, ctx.skip_meta[1], ctx.skip_meta[0])
+        return (gu, *_grads_as(gp, ctx.param_meta), _grad_as(gM, ctx.M_dtype), gskip) + (None,) * 8
+
+
+def _multi_cotangents(gout, gys, gsums, dtype):
+    """The cotangents of a shared-input group as the library takes them; any of them may be missing, but not all."""
+    gout = _cotangent(gout, dtype)
+    gys = [_cotangent(g, dtype) for g in gys]
+    gsums = [_cotangent(g, torch.float32) for g in gsums]
+    if gout is None and all(g is None for g in gys) and all(g is None for g in gsums):
+        raise L.PdeError("adi_diffuse_multi: no incoming gradient")
+    return gout, gys, gsums
 
 
 class _AdiMultiFn(torch.autograd.Function):
@@ -823,14 +875,10 @@ class _AdiMultiFn(torch.autograd.Function):
         lib = L.load()
         nl = len(specs)
         _require_cuda(u, weights, *flat)
-        B, Cc, N, _ = u.shape
-        if u.dtype not in _IO_TYPES:
-            u = u.float()
-        u = _aligned(u.contiguous())
-        need_grad = any(ctx.needs_input_grad)
-        input_only = (ctx.needs_input_grad[0] and not ctx.needs_input_grad[1] and not any(ctx.needs_input_grad[5:])
-                      and L.bwd_input_enabled())
-        want_kmax = need_grad and ckpt == "auto" and not input_only
+        B, Cc = u.shape[:2]
+        u = _kernel_input(u, False)
+        route = _grad_route(ctx.needs_input_grad[0], ctx.needs_input_grad[1] or any(ctx.needs_input_grad[5:]))
+        want_kmax = _want_kmax(route, ckpt, None)
         if ckpt != "auto" and not isinstance(ckpt, (tuple, list)):
             ckpt = (int(ckpt),) * nl                      # one step-local mask for every layer
         if ckpt != "auto" and len(ckpt) != nl:
@@ -839,101 +887,65 @@ class _AdiMultiFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         wdev = None if weights is None else weights.detach().to(torch.float32).contiguous()   # read by the kernels on the device
         arr = (L.PdeSmallLayer * nl)()
-        keep, descs, per, sums = [], [], [], []
+        layers, saved, views, ys, sums = [], [], [], [], []
         for i, (steps, smooth3, clamp_max, eps) in enumerate(specs):
             ab, bb, asl, bsl, M = flat[5 * i:5 * i + 5]
-            sps, K = len(steps[0]), len(steps)
-            sweeps = steps.flat
-            p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-            Mf = _aligned(M.detach().to(torch.float32).contiguous())
-            d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-            sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
+            p, Mf, d, sps, K, sws = _steps_prologue(lib, u, ab, bb, asl, bsl, M, steps, smooth3, clamp_max, eps)
             states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device)
-            kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
             with torch.cuda.device(u.device):
-                tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            host = tk.host if tk else None
-            a = arr[i]
-            a.desc, a.sweeps_per_step, a.mode = C.pointer(d), sps, 1
-            a.M = Mf.data_ptr()
-            a.alpha_base, a.beta_base, a.alpha_slope, a.beta_slope = (t.data_ptr() for t in p)
-            a.weight = 0.0
-            a.weight_ptr = None if wdev is None else wdev.data_ptr() + 4 * i
-            a.states = states.data_ptr()
-            a.steps_workspace, a.steps_workspace_bytes = sws.data_ptr(), sws.numel()
-            a.kappa_max = kdev.data_ptr() if kdev is not None else None
-            a.kappa_max_host = host.data_ptr() if host is not None else None
+                kdev, tk, _ = _kmax_request(want_kmax, d.num_sweeps, u.device)
             psum = torch.empty((B, Cc), dtype=torch.float32, device=u.device) if want_sums else None
-            a.plane_sums = psum.data_ptr() if psum is not None else None
+            _small_layer(arr[i], i, d, sps, Mf, wdev, sws, p=p, states=states, kappa_max=kdev,
+                         kappa_max_host=tk.host if tk else None, plane_sums=psum)
+            # workspaces, states and tickets stay on ctx — on the frozen route the factorisations alone
+            layers.append((d, sps, K, sws, *((None,) * 3 if route == "input_only" else (states, kdev, tk)),
+                           _param_meta(ab, bb, asl, bsl), M.dtype))
+            saved += [Mf] if route == "input_only" else [*p, Mf]
+            views.append(p)                                # (fp32 copies of 16-bit parameters: alive until the launch)
+            ys.append(states[-1])                          # the last sweep output of every layer
             sums.append(psum)
-            keep.append((p, Mf, sws, states, kdev, tk))
-            descs.append(d)
-            per.append((sps, K, [t.shape for t in (ab, bb, asl, bsl)], M.dtype))
         out = torch.empty_like(u)
         with torch.cuda.device(u.device):
-            ev = keep[-1][5].event if want_kmax else None      # recorded behind the last layer's copy
+            ev = tk.event if want_kmax else None               # recorded behind the last layer's copy
             L.check(lib.pde_adi_multi_forward(nl, arr, _ptr(u), _ptr(out), C.c_void_p(ev.cuda_event if ev is not None else 0),
                                               _stream()), "pde_adi_multi_forward")
         # the input, the parameter views and the operators go through save_for_backward (an in-place change of any of them
         # between forward and backward then raises torch's version-counter error instead of giving gradients that mix the
-        # forward's factorisation with new parameter values); workspaces, states and tickets stay on ctx
-        ctx.input_only = (u.shape, u.dtype, u.device) if input_only else None
-        if input_only:                                     # the operators, the weights and the factorisations only
-            ctx.save_for_backward(*([wdev] if wdev is not None else []), *[k[1] for k in keep])
-            ctx.keep, ctx.descs, ctx.per = [(k[2],) for k in keep], descs, per
-        else:
-            saved = [u] + ([wdev] if wdev is not None else [])
-            for k in keep:
-                saved += list(k[0]) + [k[1]]
-            ctx.save_for_backward(*saved)
-            ctx.keep, ctx.descs, ctx.per = [k[2:] for k in keep], descs, per
+        # forward's factorisation with new parameter values); frozen: the operators and the weights only
+        ctx.input_only = (u.shape, u.dtype, u.device) if route == "input_only" else None
+        ctx.save_for_backward(*([] if route == "input_only" else [u]), *([wdev] if wdev is not None else []), *saved)
+        ctx.layers = layers
         ctx.has_w = weights is not None
         ctx.want_sums = want_sums
-        ys = [k[3][-1] for k in keep]                      # the last sweep output of every layer
         return (out, *ys, *sums) if want_sums else (out, *ys)
 
     @staticmethod
     def _backward_input(ctx, gout, gys, gsums):
         """The backward of a group whose parameters take no gradient: ``pde_adi_multi_backward_input``."""
         lib = L.load()
-        nl = len(ctx.per)
+        nl = len(ctx.layers)
         shape, dtype, device = ctx.input_only
         saved = ctx.saved_tensors
         wdev = saved[0] if ctx.has_w else None
         Ms = saved[1 if ctx.has_w else 0:]
+        gout, gys, gsums = _multi_cotangents(gout, gys, gsums, dtype)
         arr = (L.PdeSmallLayer * nl)()
         hold = []
-        gout_c = None if gout is None else _aligned(gout.to(dtype).contiguous())
-        for i in range(nl):
-            (sws,) = ctx.keep[i]
-            d, sps = ctx.descs[i], ctx.per[i][0]
+        for i, (d, sps, _, sws, *_rest) in enumerate(ctx.layers):
             # (the slab of a side-by-side group; the query is what the library checks against, used or not)
             ws = _workspace(lib.pde_adi_small_backward_input_workspace_bytes(C.byref(d), sps), device) if nl > 1 else None
-            gyi = None if gys[i] is None else _aligned(gys[i].to(dtype).contiguous())
-            gsi = None if gsums[i] is None else _aligned(gsums[i].to(torch.float32).contiguous())
-            a = arr[i]
-            a.desc, a.sweeps_per_step, a.mode = C.pointer(d), sps, 1
-            a.M = Ms[i].data_ptr()
-            a.weight = 0.0
-            a.weight_ptr = None if wdev is None else wdev.data_ptr() + 4 * i
-            a.steps_workspace, a.steps_workspace_bytes = sws.data_ptr(), sws.numel()
-            a.gys = gyi.data_ptr() if gyi is not None else None
-            a.g_plane_sums = gsi.data_ptr() if gsi is not None else None
-            if ws is not None:
-                a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            hold.append((ws, gyi, gsi))
-        if gout_c is None and all(h[1] is None and h[2] is None for h in hold):
-            raise L.PdeError("adi_diffuse_multi: no incoming gradient")
+            _small_layer(arr[i], i, d, sps, Ms[i], wdev, sws, ws=ws, gys=gys[i], g_plane_sums=gsums[i])
+            hold.append(ws)
         gu = torch.empty(shape, dtype=dtype, device=device)
         with torch.cuda.device(device):
-            L.check(lib.pde_adi_multi_backward_input(nl, arr, _ptr(gout_c), _ptr(gu), _stream()),
+            L.check(lib.pde_adi_multi_backward_input(nl, arr, _ptr(gout), _ptr(gu), _stream()),
                     "pde_adi_multi_backward_input")
         return (gu,) + (None,) * (4 + 5 * nl)
 
     @staticmethod
     def backward(ctx, gout, *gall):
         lib = L.load()
-        nl = len(ctx.per)
+        nl = len(ctx.layers)
         gys, gsums = gall[:nl], (gall[nl:] if ctx.want_sums else (None,) * nl)
         if ctx.input_only is not None:
             return _AdiMultiFn._backward_input(ctx, gout, gys, gsums)
@@ -941,58 +953,30 @@ class _AdiMultiFn(torch.autograd.Function):
         u = saved[0]
         wdev = saved[1] if ctx.has_w else None
         pm = saved[2 if ctx.has_w else 1:]                 # per layer: four parameter views and the operator
-        B, Cc, N, _ = u.shape
-        arr = (L.PdeSmallLayer * nl)()
         if ctx.ckpt == "auto":
-            _wait_event(ctx.keep[-1][3].event)
+            _wait_event(ctx.layers[-1][6].event)
+        gout, gys, gsums = _multi_cotangents(gout, gys, gsums, u.dtype)
+        arr = (L.PdeSmallLayer * nl)()
         outs, hold = [], []
-        gout_c = None if gout is None else _aligned(gout.to(u.dtype).contiguous())
-        for i in range(nl):
-            sws, states, kdev, tk = ctx.keep[i]
+        for i, (d, sps, K, sws, states, _, tk, meta, Mdt) in enumerate(ctx.layers):
             p, Mf = pm[5 * i:5 * i + 4], pm[5 * i + 4]
-            sps, K, shapes, Mdt = ctx.per[i]
-            d = ctx.descs[i]
-            bits = 0
-            if ctx.ckpt == "auto":
-                km = tk.host.tolist()
-                for k in range(K):
-                    bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
-            else:
-                bits = int(ctx.ckpt[i])
+            bits = _plan_steps(tk.host.tolist(), K, sps) if ctx.ckpt == "auto" else int(ctx.ckpt[i])
             mask = _mask128(bits)
             ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
-            gp = [torch.empty_like(t) for t in p]
-            gM = torch.empty_like(Mf)
+            gp, gM = _grads_like(p), torch.empty_like(Mf)
             gw = torch.empty(1, dtype=torch.float32, device=u.device)
-            gyi = None if gys[i] is None else _aligned(gys[i].to(u.dtype).contiguous())
-            gsi = None if gsums[i] is None else _aligned(gsums[i].to(torch.float32).contiguous())
-            a = arr[i]
-            a.desc, a.sweeps_per_step, a.mode = C.pointer(d), sps, 1
-            a.M = Mf.data_ptr()
-            a.alpha_base, a.beta_base, a.alpha_slope, a.beta_slope = (t.data_ptr() for t in p)
-            a.weight = 0.0
-            a.weight_ptr = None if wdev is None else wdev.data_ptr() + 4 * i
-            a.states = states.data_ptr()
-            a.steps_workspace, a.steps_workspace_bytes = sws.data_ptr(), sws.numel()
-            a.gys = gyi.data_ptr() if gyi is not None else None
-            a.g_plane_sums = gsi.data_ptr() if gsi is not None else None
-            a.ckpt_mask = mask
-            a.g_alpha_base, a.g_beta_base, a.g_alpha_slope, a.g_beta_slope = (t.data_ptr() for t in gp)
-            a.gM, a.g_weight = gM.data_ptr(), gw.data_ptr()
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            hold.append((mask, ws, gyi, gsi))
-            outs.append((gp, gM, gw, shapes, Mdt))
-        if gout_c is None and all(h[2] is None and h[3] is None for h in hold):
-            raise L.PdeError("adi_diffuse_multi: no incoming gradient")
+            _small_layer(arr[i], i, d, sps, Mf, wdev, sws, p=p, gp=gp, ws=ws, mask=mask, states=states, gys=gys[i],
+                         g_plane_sums=gsums[i], gM=gM, g_weight=gw)
+            hold.append((mask, ws))
+            outs.append((gp, gM, gw, meta, Mdt))
         gu = torch.empty_like(u)
         with torch.cuda.device(u.device):
-            L.check(lib.pde_adi_multi_backward(nl, arr, _ptr(gout_c), _ptr(u), _ptr(gu), _stream()), "pde_adi_multi_backward")
+            L.check(lib.pde_adi_multi_backward(nl, arr, _ptr(gout), _ptr(u), _ptr(gu), _stream()), "pde_adi_multi_backward")
         flat = []
-        for gp, gM, gw, shapes, Mdt in outs:
-            flat += [g.reshape(s) for g, s in zip(gp, shapes)] + [gM.to(Mdt)]
+        for gp, gM, gw, meta, Mdt in outs:
+            flat += _grads_as(gp, meta) + [_grad_as(gM, Mdt)]
         gweights = torch.cat([o[2] for o in outs]) if ctx.has_w else None
         return (gu, gweights, None, None, None, *flat)
-
 
 def adi_diffuse_multi(u, layers, weights=None, plane_sums=False, checkpoints="auto"):
     """Run several mixing-first layers on the same ``u`` in one launch per pass.
@@ -1255,122 +1239,6 @@ def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coe
                         float(eps), checkpoints, kmax_sink, emit, _is_rect(u), f64)
 
 
-# not folded into _AdiSmallFn: the two C entries differ in more than the mask (skip weight, DESIGN "Rounding points")
-class _AdiSmallStatesFn(torch.autograd.Function):
-    """``_AdiSmallFn`` without the skip blend that also returns the state after chosen time steps, out of the same launch
-    per pass (pde_adi_small_forward_states / pde_adi_small_backward_states).  The result is ONE tensor (K', B, C, N, N);
-    the library's ``y`` is its last slice.
-
-    With frozen parameters (see ``_AdiSmallFn``) the forward keeps no states — the emitting forward with ``states`` NULL,
-    or ``pde_adi_small_forward_input`` for an empty mask — and the backward is ``pde_adi_small_backward_input_states``."""
-
-    @staticmethod
-    def forward(ctx, u, ab, bb, asl, bsl, M, steps, emit, mode, smooth3, clamp_max, eps, ckpt, kmax_sink):
-        lib = L.load()
-        _require_cuda(u, ab, bb, asl, bsl, M)
-        B, Cc, N, _ = u.shape
-        if u.dtype not in _IO_TYPES:
-            u = u.float()
-        u = _aligned(u.contiguous())
-        sps, K = len(steps[0]), len(steps)
-        sweeps = steps.flat
-        p = [_as_chw(t, Cc, N) for t in (ab, bb, asl, bsl)]
-        Mf = _aligned(M.detach().to(torch.float32).contiguous())
-        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-        sws = _workspace(lib.pde_adi_steps_workspace_bytes(C.byref(d), sps), u.device)
-        need_grad = any(ctx.needs_input_grad[:6])
-        input_only = ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:6]) and L.bwd_input_enabled()
-        if input_only:
-            want_kmax = kmax_sink is not None
-        else:
-            want_kmax = need_grad and (ckpt == "auto" or kmax_sink is not None)
-        kdev = torch.empty(len(sweeps), dtype=torch.float32, device=u.device) if want_kmax else None
-        Ke = len(emit)
-        out = torch.empty((Ke,) + tuple(u.shape), dtype=u.dtype, device=u.device)
-        bits = sum(1 << k for k in emit[:-1])
-        # an empty mask is the plain call, which goes on from the rounded sweep outputs of 16-bit tensors only when it
-        # keeps them: keep them then, so that the result is the same tensor in grad mode and without
-        keep = not input_only and (need_grad or (bits == 0 and u.element_size() < 4))
-        states = torch.empty((K,) + tuple(u.shape), dtype=u.dtype, device=u.device) if keep else None
-        em = _mask128(bits)
-        with torch.cuda.device(u.device):
-            tk = _kmax_channel(len(sweeps)) if want_kmax else None
-            tail = (*[_ptr(t) for t in p], _ptr(kdev), _ptr(tk.host if tk else None),
-                    C.c_void_p(tk.event.cuda_event if tk else 0), _ptr(sws), sws.numel(), _stream())
-            if input_only and bits == 0:                 # the plain call that rounds as if it kept its states
-                L.check(lib.pde_adi_small_forward_input(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u), _ptr(out[Ke - 1]),
-                                                        _ptr(Mf), None, *tail), "pde_adi_small_forward_input")
-            else:
-                L.check(lib.pde_adi_small_forward_states(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(u),
-                                                         _ptr(out[Ke - 1]), _ptr(states), _ptr(out), em, _ptr(Mf), *tail),
-                        "pde_adi_small_forward_states")
-            ctx.kmax = tk
-            if want_kmax and kmax_sink is not None:
-                kmax_sink.append(tk)
-        ctx.input_only = (u.shape, u.dtype, u.device) if input_only else None
-        if input_only:
-            ctx.save_for_backward(Mf)
-            ctx.sws = sws
-        elif need_grad:
-            ctx.save_for_backward(u, states, Mf, *p)
-            ctx.sws = sws
-        ctx.cfg = (steps, mode, smooth3, clamp_max, eps, ckpt, bits, Ke)
-        ctx.param_shapes = [t.shape for t in (ab, bb, asl, bsl)]
-        ctx.M_dtype = M.dtype
-        return out
-
-    @staticmethod
-    def _backward_input(ctx, g):
-        """The backward of a call whose parameters take no gradient: ``pde_adi_small_backward_input_states``."""
-        lib = L.load()
-        (Mf,) = ctx.saved_tensors
-        steps, mode, smooth3, clamp_max, eps, _, ebits, Ke = ctx.cfg
-        shape, dtype, device = ctx.input_only
-        B, Cc, N, _ = shape
-        g = _aligned(g.to(dtype).contiguous())
-        d = _make_desc(B, Cc, N, _io_dtype(g), steps.flat, smooth3, clamp_max, eps)
-        gu = torch.empty(shape, dtype=dtype, device=device)
-        with torch.cuda.device(device):
-            L.check(lib.pde_adi_small_backward_input_states(C.byref(d), len(steps[0]), 1 if mode == "pre" else 2,
-                                                            _ptr(g[Ke - 1]), _ptr(g), _mask128(ebits), _ptr(Mf), _ptr(gu),
-                                                            _ptr(ctx.sws), None, 0, _stream()),
-                    "pde_adi_small_backward_input_states")
-        return (gu,) + (None,) * 13
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = L.load()
-        if ctx.input_only is not None:
-            return _AdiSmallStatesFn._backward_input(ctx, g)
-        u, states, Mf, *p = ctx.saved_tensors
-        steps, mode, smooth3, clamp_max, eps, ckpt, ebits, Ke = ctx.cfg
-        B, Cc, N, _ = u.shape
-        sps, K = len(steps[0]), len(steps)
-        sweeps = steps.flat
-        d = _make_desc(B, Cc, N, _io_dtype(u), sweeps, smooth3, clamp_max, eps)
-        if ckpt == "auto":
-            km = ctx.kmax.wait()
-            bits = 0
-            for k in range(K):                           # one step-local mask for every step: the union
-                bits |= plan_checkpoints(km[k * sps:(k + 1) * sps])
-        else:
-            bits = int(ckpt)
-        mask = _mask128(bits)
-        em = _mask128(ebits)
-        ws = _workspace(lib.pde_adi_small_backward_workspace_bytes(C.byref(d), sps, bin(bits).count("1")), u.device)
-        g = _aligned(g.to(u.dtype).contiguous())                   # slots 0..K'-2 are the states' gradients, the last slice is gy
-        gu = torch.empty_like(u)
-        gp = [torch.empty_like(t) for t in p]
-        gM = torch.empty_like(Mf)
-        with torch.cuda.device(u.device):
-            L.check(lib.pde_adi_small_backward_states(C.byref(d), sps, 1 if mode == "pre" else 2, _ptr(g[Ke - 1]), _ptr(g), em,
-                                                      _ptr(u), _ptr(states), _ptr(Mf), mask, _ptr(gu), *[_ptr(t) for t in p],
-                                                      *[_ptr(t) for t in gp], _ptr(gM), _ptr(ctx.sws), _ptr(ws), ws.numel(),
-                                                      _stream()), "pde_adi_small_backward_states")
-        gp = [t.reshape(sh) for t, sh in zip(gp, ctx.param_shapes)]
-        return (gu, *gp, gM.to(ctx.M_dtype), None, None, None, None, None, None, None, None)
-
-
 def adi_diffuse_small_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode: str, emit,
                              smooth3: bool = False, clamp_max: Optional[float] = None, eps: float = 1e-6, checkpoints="auto",
                              kmax_sink: Optional[list] = None):
@@ -1398,8 +1266,8 @@ def adi_diffuse_small_states(u, alpha_base, beta_base, alpha_time_coeff, beta_ti
         y = _empty_passthrough(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
         return torch.stack([y] * len(emit))
     u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
-    return _AdiSmallStatesFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, emit, mode,
-                                   bool(smooth3), clamp_max, float(eps), checkpoints, kmax_sink)
+    return _AdiSmallFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, None, steps, mode,
+                             bool(smooth3), clamp_max, float(eps), checkpoints, kmax_sink, emit)
 
 
 # --------------------------------------------------------------------------- channel mixing
@@ -1884,7 +1752,7 @@ class _Explicit5Fn(torch.autograd.Function):
         dt, eps, max_coeff, relax, num_steps, steps, bits, f64 = ctx.cfg
         fam = "pde_explicit5_f64_" if f64 else "pde_explicit5_"
         B, Cc, H, W = u.shape
-        gout, gtraj = _cotangents(g, u, steps, ctx.align)
+        gout, gtraj = _cotangents(g, u.dtype, steps, ctx.align)
         gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
         io = () if f64 else (_io_dtype(u),)
         ws = _workspace(getattr(lib, fam + "backward_workspace_bytes")(B, Cc, H, W, *io, num_steps), u.device)
@@ -1944,7 +1812,7 @@ class _JacobiFn(torch.autograd.Function):
         nt, steps, bits, f64 = ctx.cfg
         fam = "pde_jacobi_f64_" if f64 else "pde_jacobi_io_"
         B, H, W = u.shape
-        gout, gtraj = _cotangents(g, u, steps, ctx.align)
+        gout, gtraj = _cotangents(g, u.dtype, steps, ctx.align)
         gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
         io = () if f64 else (_io_dtype(u),)
         with torch.cuda.device(u.device):
