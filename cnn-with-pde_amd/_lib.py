@@ -281,6 +281,23 @@ SIGNATURES_SMALL_INPUT = {
     "pde_adi_multi_backward_input": (C.c_int, [_i32, C.POINTER(PdeSmallLayer), _vp, _vp, _vp]),
 }
 
+#: include/pdecnn_mixed_input.h (included by pdecnn.h): the input-only backward of the layers with a channel operator above
+#: C = 4 — M^T g and the skip split alone, one step's adjoint sweeps, and the whole-layer forward / backward built from them
+SIGNATURES_MIXED_INPUT = {
+    "pde_channel_mix_backward_input_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "pde_channel_mix_backward_input": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_channel_mix_f64_backward_input": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pde_skip_blend_backward_input": (C.c_int, [C.c_int64, _i32, _vp, _fp, _vp, _vp, _vp]),
+    "pde_skip_blend_f64_backward_input": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "pde_adi_backward_input_step": (C.c_int, [_D, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pde_adi_mixed_forward_input_workspace_bytes": (_sz, [_D, _i32]),
+    "pde_adi_mixed_forward_input": (C.c_int, [_D, _i32, _i32, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _sz,
+                                              _vp, _sz, _vp]),
+    "pde_adi_mixed_backward_input_workspace_bytes": (_sz, [_D, _i32]),
+    "pde_adi_mixed_backward_input": (C.c_int, [_D, _i32, _i32, _vp, _fp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_mixed_backward_input_one_launch": (C.c_int, [_D, _i32]),
+}
+
 _lib = None
 
 
@@ -294,7 +311,8 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C cnn-with-pde_amd/csrc`). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SMALL_INPUT.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_SMALL_INPUT.items()) +
+                              list(SIGNATURES_MIXED_INPUT.items())):
         fn = getattr(lib, name)         # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     _lib = lib

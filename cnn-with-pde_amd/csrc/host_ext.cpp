@@ -604,7 +604,11 @@ Tensor small(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& 
 struct MixedFn : public torch::autograd::Function<MixedFn> {
     static Tensor forward(AutogradContext* ctx, const Tensor& u_in, const Tensor& ab, const Tensor& bb, const Tensor& asl,
                           const Tensor& bsl, const Tensor& M, int64_t desc_addr, int64_t sps, int64_t mode, int64_t ckpt_mode,
-                          int64_t ckpt_lo, double amax, bool need_grad) {
+                          int64_t ckpt_lo, double amax, int64_t grad_mode) {
+        // kGradInput (frozen parameters) and kGradNone: pde_adi_mixed_forward_input keeps no state at all, and the backward
+        // of the former is pde_adi_mixed_backward_input (M and the steps workspace are all it keeps).  PDE_BWD_INPUT=0
+        // restores pde_adi_mixed_forward for both.
+        const bool need_grad = grad_mode == kGradFull;
         require_cuda({&u_in, &ab, &bb, &asl, &bsl, &M});
         PDE_REQUIRE(u_in.dim() == 4 && u_in.size(2) == u_in.size(3), "expected (B,C,N,N), got ", u_in.sizes());
         Prologue pr(u_in, ab, bb, asl, bsl, desc_addr);
@@ -612,6 +616,21 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
         const PdeAdiDesc& d = pr.d;
         Tensor Mf = as_f32(M);
         Tensor sws = bytes(pde_adi_steps_workspace_bytes(&d, (int32_t)sps), u);
+        if (!need_grad && bwd_input_enabled()) {
+            Tensor y = at::empty_like(u);
+            Tensor ws = bytes(pde_adi_mixed_forward_input_workspace_bytes(&d, (int32_t)sps), u);
+            check(pde_adi_mixed_forward_input(&d, (int32_t)sps, (int32_t)mode, u.data_ptr(), y.data_ptr(), Mf.data_ptr<float>(),
+                                              PDE_F4(pr.p), nullptr, nullptr, nullptr, sws.data_ptr(), (size_t)sws.numel(),
+                                              ws.data_ptr(), (size_t)ws.numel(), (void*)pr.dev.st),
+                  "pde_adi_mixed_forward_input");
+            if (grad_mode == kGradNone) return y;
+            ctx->save_for_backward({Mf});
+            save_input_only(ctx, u);
+            ctx->saved_data["sws"] = sws;
+            save_desc(ctx, &d);
+            ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode, (int64_t)M.scalar_type()};
+            return y;
+        }
         Kmax km(need_grad && ckpt_mode == 1, d.num_sweeps, u);
         // states[2k]: output of step k's first operator, states[2k+1]: of its second (= input of step k + 1); the last of
         // them is the layer output and lives in a tensor of its own
@@ -621,7 +640,7 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
                                     Mf.data_ptr<float>(), PDE_F4(pr.p), km.dev(), km.host(), km.event(), sws.data_ptr(),
                                     (size_t)sws.numel(), (void*)pr.dev.st),
               "pde_adi_mixed_forward");
-        if (!need_grad) return y;
+        if (grad_mode == kGradNone) return y;
         ctx->save_for_backward({u, states, Mf, pr.p[0], pr.p[1], pr.p[2], pr.p[3], y});
         ctx->saved_data["sws"] = sws;
         km.save(ctx);
@@ -632,7 +651,26 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
         return y;
     }
 
+    // gu = F^T gy alone: the operator and the forward's factorisation, per step M^T g and the transposed solves
+    static variable_list backward_input(AutogradContext* ctx, variable_list& grads) {
+        auto saved = ctx->get_saved_variables();
+        const Tensor& Mf = saved[0];
+        PdeAdiDesc d;
+        load_desc(ctx, &d);
+        auto cfg = ctx->saved_data["cfg"].toIntVector();
+        Tensor gy = cotangent(grads[0], input_only_dtype(ctx));
+        OnDevice dev(gy);
+        Tensor gu = at::empty_like(gy);
+        Tensor sws = ctx->saved_data["sws"].toTensor();
+        Tensor ws = bytes(pde_adi_mixed_backward_input_workspace_bytes(&d, (int32_t)cfg[0]), gy);
+        check(pde_adi_mixed_backward_input(&d, (int32_t)cfg[0], (int32_t)cfg[1], gy.data_ptr(), Mf.data_ptr<float>(),
+                                           gu.data_ptr(), sws.data_ptr(), ws.data_ptr(), (size_t)ws.numel(), (void*)dev.st),
+              "pde_adi_mixed_backward_input");
+        return grads_out(13, {gu});
+    }
+
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &u = saved[0], &states = saved[1], &Mf = saved[2];
         PdeAdiDesc d;
@@ -659,9 +697,8 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
 
 Tensor mixed(const Tensor& u, const Tensor& ab, const Tensor& bb, const Tensor& asl, const Tensor& bsl, const Tensor& M,
              int64_t desc_addr, int64_t sps, int64_t mode, int64_t ckpt_mode, int64_t ckpt_lo, double amax) {
-    const bool need_grad = at::GradMode::is_enabled() && (u.requires_grad() || ab.requires_grad() || bb.requires_grad() ||
-                                                          asl.requires_grad() || bsl.requires_grad() || M.requires_grad());
-    return MixedFn::apply(u, ab, bb, asl, bsl, M, desc_addr, sps, mode, ckpt_mode, ckpt_lo, amax, need_grad);
+    const bool params = ab.requires_grad() || bb.requires_grad() || asl.requires_grad() || bsl.requires_grad() || M.requires_grad();
+    return MixedFn::apply(u, ab, bb, asl, bsl, M, desc_addr, sps, mode, ckpt_mode, ckpt_lo, amax, grad_mode_of(u, params));
 }
 
 // ---- several mixing-first layers on the SAME input, one launch per pass (functional._AdiMultiFn: cifar10.py:272-280,

@@ -1506,6 +1506,118 @@ int pde_adi_mixed_backward(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t
                                g_beta_base, g_alpha_slope, g_beta_slope, steps_workspace, aws, stream);
 }
 
+// ---- the same layer when neither the coefficients nor M take a gradient (include/pdecnn_mixed_input.h) ----------
+// The layer is linear in u, so gu is the adjoint alone: per step M^T g and the transposed solves, nothing of the forward
+// but the factorisation.  The forward of such a call keeps no state: two scratch tensors, ping-pong.
+int pde_adi_backward_input_step(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t step, const void* gy, void* gu,
+                                const void* steps_workspace, void* stream) {
+    PdeAdiDesc ds;
+    int rc = step_desc(d, sweeps_per_step, step, ds);
+    if (rc != PDE_OK) return rc;
+    if (!gy || !gu || !steps_workspace || misaligned(kVecAlign, gy, gu)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, steps_workspace)) return PDE_E_WORKSPACE;
+    const char* ws = static_cast<const char*>(steps_workspace);
+    const float* coef = reinterpret_cast<const float*>(ws) + (size_t)step * sweeps_per_step * d->C * kRecStride;
+    const SweepTab* tab = reinterpret_cast<const SweepTab*>(ws + steps_tab_offset(d)) + step;
+    return launch_bwd_input_sweeps(&ds, gy, gu, coef, tab, static_cast<hipStream_t>(stream), nullptr, nullptr);
+}
+
+// the one-launch reverse walk (C = 32 / 64) is not built: every call takes the composed route
+int pde_adi_mixed_backward_input_one_launch(const PdeAdiDesc* d, int32_t sweeps_per_step) {
+    (void)d; (void)sweeps_per_step;
+    return 0;
+}
+
+size_t pde_adi_mixed_forward_input_workspace_bytes(const PdeAdiDesc* d, int32_t sweeps_per_step) {
+    if (check_desc(d) != PDE_OK || sweeps_per_step <= 0 || d->num_sweeps % sweeps_per_step) return 0;
+    if (wide_supported(d, sweeps_per_step)) return 0;      // one launch, nothing in between
+    const int K = d->num_sweeps / sweeps_per_step;
+    const int nbuf = 2 * K - 1 < 2 ? 2 * K - 1 : 2;       // intermediate tensors alive at once
+    return (size_t)nbuf * align_up(state_bytes(d), 256);
+}
+
+int pde_adi_mixed_forward_input(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode, const void* u, void* y,
+                                const float* M, const float* alpha_base, const float* beta_base, const float* alpha_slope,
+                                const float* beta_slope, float* kappa_max, float* kappa_max_host, void* kappa_event,
+                                void* steps_workspace, size_t steps_workspace_bytes, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    if (!u || !y || !M || (mode != 1 && mode != 2)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, u, y, M)) return PDE_E_BADARG;              // the rest: factor_steps_impl, before its launch
+    int rc = check_desc(d);
+    if (rc != PDE_OK) return rc;
+    if (sweeps_per_step <= 0 || d->num_sweeps % sweeps_per_step) return PDE_E_BADARG;
+    const size_t need = pde_adi_mixed_forward_input_workspace_bytes(d, sweeps_per_step);
+    if ((need && !workspace) || workspace_bytes < need || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
+    bool wrote = false;
+    rc = factor_steps_impl(d, sweeps_per_step, alpha_base, beta_base, alpha_slope, beta_slope, kappa_max, kappa_max_host,
+                           &wrote, steps_workspace, steps_workspace_bytes, stream);
+    if (rc != PDE_OK) return rc;
+    rc = publish_kmax(kappa_max, kappa_max_host, kappa_event, d->num_sweeps, static_cast<hipStream_t>(stream), wrote);
+    if (rc != PDE_OK) return rc;
+    const int K = d->num_sweeps / sweeps_per_step, HW = d->N * d->N;
+    if (wide_supported(d, sweeps_per_step))
+        return wide_forward(d, sweeps_per_step, mode, u, nullptr, y, M, steps_workspace, 0, static_cast<hipStream_t>(stream));
+    char* w = static_cast<char*>(workspace);
+    void* buf[2] = {w, w + align_up(state_bytes(d), 256)};
+    const void* cur = u;
+    int nb = 0;                                            // next scratch tensor; never the one `cur` lives in
+    for (int k = 0; k < K; ++k) {
+        void* a_k = buf[nb]; nb ^= 1;
+        void* b_k = (k == K - 1) ? y : buf[nb];
+        if (k != K - 1) nb ^= 1;
+        if (mode == 1) {
+            rc = pde_channel_mix_forward(d->B, d->C, HW, d->io_dtype, cur, M, a_k, stream);
+            if (rc == PDE_OK) rc = pde_adi_forward_step(d, sweeps_per_step, k, a_k, b_k, steps_workspace, stream);
+        } else {
+            rc = pde_adi_forward_step(d, sweeps_per_step, k, cur, a_k, steps_workspace, stream);
+            if (rc == PDE_OK) rc = pde_channel_mix_forward(d->B, d->C, HW, d->io_dtype, a_k, M, b_k, stream);
+        }
+        if (rc != PDE_OK) return rc;
+        cur = b_k;
+    }
+    return PDE_OK;
+}
+
+size_t pde_adi_mixed_backward_input_workspace_bytes(const PdeAdiDesc* d, int32_t sweeps_per_step) {
+    if (check_desc(d) != PDE_OK || sweeps_per_step <= 0 || d->num_sweeps % sweeps_per_step) return 0;
+    return 2 * align_up(state_bytes(d), 256) +
+           align_up(pde_channel_mix_backward_input_workspace_bytes(d->B, d->C, d->N * d->N), 256);
+}
+
+int pde_adi_mixed_backward_input(const PdeAdiDesc* d, int32_t sweeps_per_step, int32_t mode, const void* gy, const float* M,
+                                 void* gu, const void* steps_workspace, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!gy || !M || !gu || !workspace || (mode != 1 && mode != 2)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, gy, M, gu)) return PDE_E_BADARG;
+    if (!steps_workspace || misaligned(kVecAlign, steps_workspace)) return PDE_E_WORKSPACE;
+    const size_t need = pde_adi_mixed_backward_input_workspace_bytes(d, sweeps_per_step);
+    if (need == 0) return PDE_E_BADARG;
+    if (workspace_bytes < need || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
+    const int K = d->num_sweeps / sweeps_per_step, HW = d->N * d->N;
+    const size_t sb = align_up(state_bytes(d), 256);
+    char* w = static_cast<char*>(workspace);
+    void* buf[2] = {w, w + sb};
+    void* mws = w + 2 * sb;
+    const size_t ws_m = pde_channel_mix_backward_input_workspace_bytes(d->B, d->C, HW);
+    const void* g_in = gy;                                 // gradient entering the step (never written)
+    for (int k = K - 1; k >= 0; --k) {
+        void* g_mid = (g_in == buf[0]) ? buf[1] : buf[0];
+        void* g_out = (k == 0) ? gu : ((g_mid == buf[0]) ? buf[1] : buf[0]);
+        int rc;
+        if (mode == 1) {                                   // step = mix, sweeps: the sweeps' adjoint first
+            rc = pde_adi_backward_input_step(d, sweeps_per_step, k, g_in, g_mid, steps_workspace, stream);
+            if (rc == PDE_OK)
+                rc = pde_channel_mix_backward_input(d->B, d->C, HW, d->io_dtype, g_mid, M, g_out, mws, ws_m, stream);
+        } else {                                           // step = sweeps, mix: M^T first
+            rc = pde_channel_mix_backward_input(d->B, d->C, HW, d->io_dtype, g_in, M, g_mid, mws, ws_m, stream);
+            if (rc == PDE_OK)
+                rc = pde_adi_backward_input_step(d, sweeps_per_step, k, g_mid, g_out, steps_workspace, stream);
+        }
+        if (rc != PDE_OK) return rc;
+        g_in = g_out;
+    }
+    return PDE_OK;
+}
+
 // ---- the whole layer in ONE launch per pass: C <= 4 channels with a channel operator between the steps ----------
 // (pde_adi_small.h; the reference's own models: cifar10.py:253-258 C = 3 mixing before every step,
 // SVHN.py:238 C = 3 coupling after every step + skip blend)

@@ -116,6 +116,28 @@ __global__ __launch_bounds__(256) void blend_bwd_kernel(const IO* __restrict__ g
     if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+// the same two products when skip_weight takes no gradient (pde_skip_blend_backward_input): neither u0 nor u is read, no sum
+template <typename IO>
+__global__ __launch_bounds__(256) void blend_bwd_input_kernel(const IO* __restrict__ g, const float* __restrict__ skip_weight,
+                                                              IO* __restrict__ g_u0, IO* __restrict__ g_u, size_t n) {
+    const float s = sigmoidf(*skip_weight), t = sigmoidf(-*skip_weight);      // 1 - s, without its cancellation
+    const size_t stride = (size_t)gridDim.x * 256 * 8;
+    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8; i < n; i += stride) {
+        if (i + 8 <= n) {
+            float gg[8], o0[8], o1[8];
+            Vec<IO>::ld(g + i, gg);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { o0[k] = s * gg[k]; o1[k] = t * gg[k]; }
+            Vec<IO>::st(g_u0 + i, o0); Vec<IO>::st(g_u + i, o1);
+        } else {
+            for (size_t j = i; j < n; ++j) {
+                const float gj = Vec<IO>::ld1(g + j);
+                Vec<IO>::st1(g_u0 + j, s * gj); Vec<IO>::st1(g_u + j, t * gj);
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void blend_reduce_kernel(const double* __restrict__ part, int nparts,
                                                            const float* __restrict__ skip_weight, float* __restrict__ g_w) {
     __shared__ double sh[4];
@@ -179,6 +201,24 @@ int pde_skip_blend_backward(int64_t n, int32_t io_dtype, const void* g, const vo
     else
         return PDE_E_BADARG;
     hipLaunchKernelGGL(blend_reduce_kernel, dim3(1), dim3(256), 0, st, part, grid, skip_weight, g_skip_weight);
+    return check_launch();
+}
+
+// the backward when skip_weight takes no gradient: g_u0 = s g and g_u = (1 - s) g, bit for bit those of pde_skip_blend_backward
+int pde_skip_blend_backward_input(int64_t n, int32_t io_dtype, const void* g, const float* skip_weight, void* g_u0, void* g_u,
+                                  void* stream) {
+    if (n <= 0 || !g || !skip_weight || !g_u0 || !g_u) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, g, g_u0, g_u) || misaligned(4, skip_weight)) return PDE_E_BADARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int grid = blend_grid((size_t)n);
+    if (io_dtype == PDE_IO_F32)
+        hipLaunchKernelGGL(blend_bwd_input_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)g, skip_weight, (float*)g_u0, (float*)g_u, (size_t)n);
+    else if (io_dtype == PDE_IO_BF16)
+        hipLaunchKernelGGL(blend_bwd_input_kernel<bf16v>, dim3(grid), dim3(256), 0, st, (const bf16v*)g, skip_weight, (bf16v*)g_u0, (bf16v*)g_u, (size_t)n);
+    else if (io_dtype == PDE_IO_F16)
+        hipLaunchKernelGGL(blend_bwd_input_kernel<f16v>, dim3(grid), dim3(256), 0, st, (const f16v*)g, skip_weight, (f16v*)g_u0, (f16v*)g_u, (size_t)n);
+    else
+        return PDE_E_BADARG;
     return check_launch();
 }
 

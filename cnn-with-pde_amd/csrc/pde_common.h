@@ -73,6 +73,10 @@ bool mix_split_ok(int C, int HW);
 int mix_split_splits(int B, int C, int HW);
 int mix_split_backward(int B, int C, int HW, const void* u, const void* g, const float* M, void* gu, float* part, int nsplit,
                        int accp, hipStream_t st);
+// the gu halves of the three backward kernels above alone (pde_channel_mix_backward_input): same launch shape, same gu bits
+int mix_bf16_backward_input(int B, int C, int HW, const void* g, const float* M, void* gu, int nsplit, hipStream_t st);
+int mix_f16_backward_input(int B, int C, int HW, const void* g, const float* M, void* gu, int nsplit, hipStream_t st);
+int mix_split_backward_input(int B, int C, int HW, const void* g, const float* M, void* gu, int nsplit, hipStream_t st);
 
 // fp32 -> bf16, round to nearest even: one v_cvt_pk_bf16_f32 per pair on gfx950 (the bit-twiddling form costs
 // five VALU instructions per element, and a VALU instruction is what the sweep kernels run out of)

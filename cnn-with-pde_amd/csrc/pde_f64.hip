@@ -116,6 +116,18 @@ __global__ __launch_bounds__(256) void blend64_bwd_kernel(long long n, const dou
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
+// skip_weight takes no gradient (pde_skip_blend_f64_backward_input): the two products alone
+__global__ __launch_bounds__(256) void blend64_bwd_input_kernel(long long n, const double* __restrict__ g,
+                                                                const double* __restrict__ w, double* __restrict__ g_u0,
+                                                                double* __restrict__ g_u) {
+    const double s = sigmoid64(*w), t = 1.0 - s;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const double ge = g[e];
+        g_u0[e] = s * ge;
+        g_u[e] = t * ge;
+    }
+}
+
 __global__ __launch_bounds__(256) void blend64_reduce_kernel(int nparts, const double* __restrict__ part,
                                                              const double* __restrict__ w, double* __restrict__ gw) {
     __shared__ double red[256];
@@ -389,6 +401,15 @@ int pde_channel_mix_f64_backward(int32_t B, int32_t C, int32_t HW, const double*
     return pde_channel_mix_f64_backward_steps(B, C, HW, u, gout, M, gu, gM, workspace, workspace_bytes, 0, 1, stream);
 }
 
+// gu = M^T gout alone (M takes no gradient): the first launch of pde_channel_mix_f64_backward_steps
+int pde_channel_mix_f64_backward_input(int32_t B, int32_t C, int32_t HW, const double* gout, const double* M, double* gu,
+                                       void* stream) {
+    if (!mix64_ok(B, C, HW) || !gout || !M || !gu || misaligned(8, gout, M, gu)) return PDE_E_BADARG;
+    hipLaunchKernelGGL(mix64_apply_kernel, dim3((HW + 255) / 256, C, B), dim3(256), 0, static_cast<hipStream_t>(stream), C, HW,
+                       gout, M, gu, 1);
+    return check_launch();
+}
+
 int pde_skip_blend_f64_forward(int64_t n, const double* u0, const double* u, const double* skip_weight, double* out,
                                void* stream) {
     if (n <= 0 || !u0 || !u || !skip_weight || !out || misaligned(8, u0, u, skip_weight, out)) return PDE_E_BADARG;
@@ -414,6 +435,15 @@ int pde_skip_blend_f64_backward(int64_t n, const double* g, const double* u0, co
     double* part = static_cast<double*>(workspace);
     hipLaunchKernelGGL(blend64_bwd_kernel, dim3(np), dim3(256), 0, st, (long long)n, g, u0, u, skip_weight, g_u0, g_u, part);
     hipLaunchKernelGGL(blend64_reduce_kernel, dim3(1), dim3(256), 0, st, np, part, skip_weight, g_skip_weight);
+    return check_launch();
+}
+
+// skip_weight takes no gradient: g_u0 = s g, g_u = (1 - s) g, bit for bit those of pde_skip_blend_f64_backward
+int pde_skip_blend_f64_backward_input(int64_t n, const double* g, const double* skip_weight, double* g_u0, double* g_u,
+                                      void* stream) {
+    if (n <= 0 || !g || !skip_weight || !g_u0 || !g_u || misaligned(8, g, skip_weight, g_u0, g_u)) return PDE_E_BADARG;
+    hipLaunchKernelGGL(blend64_bwd_input_kernel, dim3(blend64_parts(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (long long)n, g, skip_weight, g_u0, g_u);
     return check_launch();
 }
 

@@ -330,7 +330,10 @@ __global__ __launch_bounds__(256) void mix_gm_mfma_kernel(const IO* __restrict__
 // WLDS: the M^T fragment table sits in LDS (C = 64: 16 KB); for C = 128 it would take 64 KB and leave
 // room for one workgroup per CU only, so there the fragments are read from the (L2-resident) table
 // `Mfrag` that mix_frag_kernel lays out once per call, and two workgroups overlap staging with MFMAs.
-template <typename IO, int C, int W, bool WLDS>
+// GM false (M takes no gradient, pde_channel_mix_backward_input): the gu half alone — no u loads, no su image, no acc_m,
+// no partial matrix (u and part are NULL); the gu half is the same statements in the same order, so gu is bit for bit the
+// full kernel's.
+template <typename IO, int C, int W, bool WLDS, bool GM = true>
 __global__ __launch_bounds__(64 * W) void mix_bwd_fused_kernel(const IO* __restrict__ u, const IO* __restrict__ g,
                                                                const float* __restrict__ M, const float* __restrict__ Mfrag,
                                                                IO* __restrict__ gu, float* __restrict__ part, int B, int HW,
@@ -377,7 +380,7 @@ __global__ __launch_bounds__(64 * W) void mix_bwd_fused_kernel(const IO* __restr
             const bool pv = p < HW && chn < total;
             const size_t off = ((size_t)fb * C + c) * HW + p;
             gq[i] = pv ? Io4<IO>::ld(g + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-            uq[i] = pv ? Io4<IO>::ld(u + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (GM) uq[i] = pv ? Io4<IO>::ld(u + off) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
     fetch(blockIdx.x);
@@ -392,13 +395,15 @@ __global__ __launch_bounds__(64 * W) void mix_bwd_fused_kernel(const IO* __restr
             float* dg = sg + c * kGmLd + 4 * c4;
             float* du = su + c * kGmLd + 4 * c4;
             *reinterpret_cast<float2*>(dg) = make_float2(gq[i].x, gq[i].y); *reinterpret_cast<float2*>(dg + 2) = make_float2(gq[i].z, gq[i].w);
-            *reinterpret_cast<float2*>(du) = make_float2(uq[i].x, uq[i].y); *reinterpret_cast<float2*>(du + 2) = make_float2(uq[i].z, uq[i].w);
+            if constexpr (GM) {
+                *reinterpret_cast<float2*>(du) = make_float2(uq[i].x, uq[i].y); *reinterpret_cast<float2*>(du + 2) = make_float2(uq[i].z, uq[i].w);
+            }
         }
         __syncthreads();
         fetch(ch + nsplit);                            // in flight under the MFMAs below
         // gM: contraction index = pixel pair ks of the tile
 #pragma unroll 4
-        for (int ks = 0; ks < kGmKP / 2; ++ks) {
+        for (int ks = 0; ks < (GM ? kGmKP / 2 : 0); ++ks) {
 #pragma unroll
             for (int t = 0; t < NTM; ++t) {
                 const int tile = wave + W * t, it = tile / T, jt = tile % T;
@@ -437,6 +442,7 @@ __global__ __launch_bounds__(64 * W) void mix_bwd_fused_kernel(const IO* __restr
             }
         }
     }
+    if constexpr (!GM) return;
     float* dst = part + (size_t)blockIdx.x * C * C;
 #pragma unroll
     for (int t = 0; t < NTM; ++t) {
@@ -474,6 +480,22 @@ void launch_fused(const void* u, const void* g, const float* M, void* gu, float*
     static unsigned long long cfg = 0;
     ensure_lds((const void*)mix_bwd_fused_kernel<IO, C, W, WLDS>, (int)lds, cfg);
     hipLaunchKernelGGL((mix_bwd_fused_kernel<IO, C, W, WLDS>), dim3(nsplit), dim3(64 * W), lds, st, (const IO*)u, (const IO*)g, M, frag, (IO*)gu, part, B, HW, nsplit, accp);
+}
+// the same for gu alone; `frag`: the fragment table of M^T (C = 128 only), the whole workspace of that call
+template <typename IO, int C, int W, bool WLDS>
+void launch_fused_input(const void* g, const float* M, void* gu, float* frag, int B, int HW, int nsplit, hipStream_t st) {
+    const size_t lds = (size_t)((WLDS ? C * C : 0) + C * kGmLd) * sizeof(float);
+    if (!WLDS) hipLaunchKernelGGL(mix_frag_kernel, dim3((C * C + 255) / 256), dim3(256), 0, st, M, frag, C);
+    static unsigned long long cfg = 0;
+    ensure_lds((const void*)mix_bwd_fused_kernel<IO, C, W, WLDS, false>, (int)lds, cfg);
+    hipLaunchKernelGGL((mix_bwd_fused_kernel<IO, C, W, WLDS, false>), dim3(nsplit), dim3(64 * W), lds, st, (const IO*)nullptr, (const IO*)g, M, frag, (IO*)gu, (float*)nullptr, B, HW, nsplit, 0);
+}
+template <typename IO>
+void launch_fused_input_c(int C, const void* g, const float* M, void* gu, float* frag, int B, int HW, int nsplit, hipStream_t st) {
+    if (C == 32) launch_fused_input<IO, 32, 1, true>(g, M, gu, frag, B, HW, nsplit, st);
+    else if (C == 64) launch_fused_input<IO, 64, 4, true>(g, M, gu, frag, B, HW, nsplit, st);
+    else if (C == 96) launch_fused_input<IO, 96, 3, true>(g, M, gu, frag, B, HW, nsplit, st);
+    else launch_fused_input<IO, 128, 8, false>(g, M, gu, frag, B, HW, nsplit, st);
 }
 
 bool mfma_apply_ok(int C, int HW) { return (C % 32) == 0 && C <= 128 && (HW % 4) == 0; }   // W fragments: C*C*4 B of LDS
@@ -685,6 +707,46 @@ int pde_channel_mix_backward_steps(int32_t B, int32_t C, int32_t HW, int32_t io_
                                (const bf16s*)gout, part, B, C, HW, nsplit, accumulate);
     }
     if (finalize) hipLaunchKernelGGL(mix_gm_reduce_kernel, dim3((C * C + 31) / 32), dim3(256), 0, st, part, gM, C * C, nsplit);
+    return check_launch();
+}
+
+// ---- the backward when M takes no gradient: gu = M^T gout alone (include/pdecnn_mixed_input.h) ----
+// Same plan as pde_channel_mix_backward_steps, so every path forms gu with the arithmetic it has there; u is not read, no
+// partial matrix is written and nothing is reduced.  Scratch: the M^T fragment table of the C = 128 fused path only.
+size_t pde_channel_mix_backward_input_workspace_bytes(int32_t B, int32_t C, int32_t HW) {
+    if (B <= 0 || C <= 0 || HW <= 0) return 0;
+    return (C == 128 && mfma_fused_ok(C, HW)) ? (size_t)C * C * sizeof(float) : 0;
+}
+
+int pde_channel_mix_backward_input(int32_t B, int32_t C, int32_t HW, int32_t io_dtype, const void* gout, const float* M,
+                                   void* gu, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B <= 0 || C <= 0 || HW <= 0 || !gout || !M || !gu) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, gout, M, gu)) return PDE_E_BADARG;
+    const size_t need = pde_channel_mix_backward_input_workspace_bytes(B, C, HW);
+    if ((need && !workspace) || workspace_bytes < need || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const MixPlan plan = mix_plan(B, C, HW, io_dtype, true);
+    if (plan.path < 0) return plan.path;
+    const int nsplit = plan.walkers;
+    if (plan.path == PDE_MIX_PATH_MFMA_16)
+        return io_dtype == PDE_IO_BF16 ? mix_bf16_backward_input(B, C, HW, gout, M, gu, nsplit, st)
+                                       : mix_f16_backward_input(B, C, HW, gout, M, gu, nsplit, st);
+    if (plan.path == PDE_MIX_PATH_SPLIT3) return mix_split_backward_input(B, C, HW, gout, M, gu, nsplit, st);
+    if (plan.path == PDE_MIX_PATH_FUSED) {
+        float* frag = static_cast<float*>(workspace);
+        if (io_dtype == PDE_IO_F32) launch_fused_input_c<float>(C, gout, M, gu, frag, B, HW, nsplit, st);
+        else if (io_dtype == PDE_IO_F16) launch_fused_input_c<f16s>(C, gout, M, gu, frag, B, HW, nsplit, st);
+        else launch_fused_input_c<bf16s>(C, gout, M, gu, frag, B, HW, nsplit, st);
+        return check_launch();
+    }
+    if (plan.path == PDE_MIX_PATH_MFMA_F32) return launch_apply_mfma(B, C, HW, io_dtype, gout, M, gu, 1, st);
+    dim3 grid((HW + 255) / 256, B);
+    if (io_dtype == PDE_IO_F32)
+        hipLaunchKernelGGL((mix_apply_kernel<float, true>), grid, dim3(256), 0, st, (const float*)gout, M, (float*)gu, C, HW);
+    else if (io_dtype == PDE_IO_F16)
+        hipLaunchKernelGGL((mix_apply_kernel<f16s, true>), grid, dim3(256), 0, st, (const f16s*)gout, M, (f16s*)gu, C, HW);
+    else
+        hipLaunchKernelGGL((mix_apply_kernel<bf16s, true>), grid, dim3(256), 0, st, (const bf16s*)gout, M, (bf16s*)gu, C, HW);
     return check_launch();
 }
 

@@ -194,7 +194,10 @@ __global__ __launch_bounds__(C * 4) void mix_apply_bf16_kernel(const unsigned sh
 }
 
 // ---- backward: gu = M^T g and the partial sums of gM = g u^T ---------------------------------------------
-template <int C, typename E = MixBf16>
+// GM false (M takes no gradient, pde_channel_mix_backward_input): the gu half alone — no u loads or image, no acc_m, no
+// partial matrix (u and part are NULL); the gu half is the same statements in the same order, so gu is bit for bit the full
+// kernel's.
+template <int C, typename E = MixBf16, bool GM = true>
 __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned short* __restrict__ u, const unsigned short* __restrict__ g,
                                                              const float* __restrict__ M, unsigned short* __restrict__ gu,
                                                              float* __restrict__ part, int B, int HW, int accp) {
@@ -204,7 +207,7 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned shor
     unsigned short* frag = reinterpret_cast<unsigned short*>(smem);
     unsigned char* img_g = smem + frag_bytes<E, C>();
     unsigned char* img_u = img_g + C * kRow;
-    unsigned char* img_o = img_u + C * kRow;
+    unsigned char* img_o = GM ? img_u + C * kRow : img_u;  // without gM there is no image of u
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, r = lane & 31;
     build_frags<C, true, E>(M, frag, tid, NT);
@@ -221,30 +224,32 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned shor
         const size_t o = (size_t)(blockIdx.x / per_sample) * C * HW;
         const int q0 = (int)(blockIdx.x % per_sample) * kPx;
         fetch_tile<C>(g + o, HW, q0, g0, g1, tid);
-        fetch_tile<C>(u + o, HW, q0, u0, u1, tid);
+        if constexpr (GM) fetch_tile<C>(u + o, HW, q0, u0, u1, tid);
     }
     for (long tile = blockIdx.x; tile < total; tile += gridDim.x) {
         const int b = (int)(tile / per_sample), p0 = (int)(tile % per_sample) * kPx;
         __syncthreads();
         deposit_tile<C>(g0, g1, img_g, tid);
-        deposit_tile<C>(u0, u1, img_u, tid);
+        if constexpr (GM) deposit_tile<C>(u0, u1, img_u, tid);
         __syncthreads();
         const long tn = tile + gridDim.x;
         if (tn < total) {
             const size_t o = (size_t)(tn / per_sample) * C * HW;
             const int q0 = (int)(tn % per_sample) * kPx;
             fetch_tile<C>(g + o, HW, q0, g0, g1, tid);
-            fetch_tile<C>(u + o, HW, q0, u0, u1, tid);
+            if constexpr (GM) fetch_tile<C>(u + o, HW, q0, u0, u1, tid);
         }
         // gM: contraction over the 64 pixels of the tile, 16 per MFMA
+        if constexpr (GM) {
 #pragma unroll
-        for (int kp = 0; kp < kPx / 16; ++kp) {
+            for (int kp = 0; kp < kPx / 16; ++kp) {
 #pragma unroll
-            for (int t = 0; t < NTM; ++t) {
-                const int tl = wave + W * t, it = tl / T, jt2 = tl % T;
-                const typename E::v8 a = row_operand<E>(img_g, 32 * it + r, 16 * kp + 8 * h);
-                const typename E::v8 bb = row_operand<E>(img_u, 32 * jt2 + r, 16 * kp + 8 * h);
-                acc_m[t] = E::mfma(a, bb, acc_m[t]);
+                for (int t = 0; t < NTM; ++t) {
+                    const int tl = wave + W * t, it = tl / T, jt2 = tl % T;
+                    const typename E::v8 a = row_operand<E>(img_g, 32 * it + r, 16 * kp + 8 * h);
+                    const typename E::v8 bb = row_operand<E>(img_u, 32 * jt2 + r, 16 * kp + 8 * h);
+                    acc_m[t] = E::mfma(a, bb, acc_m[t]);
+                }
             }
         }
         // gu^T tile = g^T (hi + lo)
@@ -262,6 +267,7 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_bf16_kernel(const unsigned shor
         __syncthreads();
         store_tile<C>(gu + (size_t)b * C * HW, HW, p0, img_o, tid, NT);
     }
+    if constexpr (!GM) return;
     float* dst = part + (size_t)blockIdx.x * C * C;
 #pragma unroll
     for (int t = 0; t < NTM; ++t) {
@@ -309,7 +315,9 @@ __device__ __forceinline__ void build_frags3(const float* __restrict__ M, unsign
     }
 }
 
-template <int C>
+// GM false (M takes no gradient, pde_channel_mix_backward_input): the gu half alone, as in mix_bwd_bf16_kernel; the fp32
+// result image then takes the place of u's images (five piece images of LDS instead of six)
+template <int C, bool GM = true>
 __global__ __launch_bounds__(C * 4) void mix_bwd_split_kernel(const float* __restrict__ u, const float* __restrict__ g,
                                                               const float* __restrict__ M, float* __restrict__ gu,
                                                               float* __restrict__ part, int B, int HW, int accp) {
@@ -327,7 +335,7 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_split_kernel(const float* __res
     unsigned short* frag = reinterpret_cast<unsigned short*>(smem);          // [3][FR][8] bf16 = 6*C*C bytes
     unsigned char* img_g = smem + (size_t)6 * C * C;                          // [3][C][kRow]
     unsigned char* img_u = img_g + 3 * IMG;                                   // [3][C][kRow]
-    unsigned char* img_o = img_u + IMG;                                       // fp32 result over u's mid and lo images
+    unsigned char* img_o = GM ? img_u + IMG : img_u;                          // fp32 result over u's mid and lo images
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, r = lane & 31;
     build_frags3<C>(M, frag, tid, NT);
@@ -349,7 +357,7 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_split_kernel(const float* __res
             const int e = tid + i * NT, row = e >> 4, c4 = e & 15;
             const int cc = 4 * c4 < valid ? 4 * c4 : 0;    // beyond the plane: re-read the tile's first piece, zeroed when deposited
             gq[i] = *reinterpret_cast<const float4*>(g + o + (size_t)row * HW + q0 + cc);
-            uq[i] = *reinterpret_cast<const float4*>(u + o + (size_t)row * HW + q0 + cc);
+            if constexpr (GM) uq[i] = *reinterpret_cast<const float4*>(u + o + (size_t)row * HW + q0 + cc);
         }
     };
     auto deposit = [&](const float4 (&q)[PCS], unsigned char* img, int valid) __attribute__((always_inline)) {
@@ -372,13 +380,13 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_split_kernel(const float* __res
         const int valid = HW - p0 < kPx ? HW - p0 : kPx;
         __syncthreads();                                   // fragments built / previous tile's images consumed and stored
         deposit(gq, img_g, valid);
-        deposit(uq, img_u, valid);
+        if constexpr (GM) deposit(uq, img_u, valid);
         __syncthreads();
         const long tn = tile + gridDim.x;
         if (tn < total) fetch(tn);                         // the next tile's loads fly during this tile's MFMAs
         // gM: contraction over the 64 pixels of the tile (zeros beyond a ragged one), 16 per MFMA, six piece products
 #pragma unroll
-        for (int kq = 0; kq < kPx / 16 / KPARTS; ++kq) {
+        for (int kq = 0; kq < (GM ? kPx / 16 / KPARTS : 0); ++kq) {
             const int kp = KPARTS == 1 ? kq : kq * KPARTS + wave / TT;
 #pragma unroll
             for (int t = 0; t < NTM; ++t) {
@@ -435,6 +443,7 @@ __global__ __launch_bounds__(C * 4) void mix_bwd_split_kernel(const float* __res
                     *reinterpret_cast<const float4*>(img_o + row * kRowF + 16 * c4);
         }
     }
+    if constexpr (!GM) return;
     float* dst = part + (size_t)blockIdx.x * C * C;
     if (KPARTS > 1) {                                      // partial tiles of the same gM tile: added in wave order through LDS
         __syncthreads();
@@ -488,6 +497,15 @@ void launch_bwd(const void* u, const void* g, const float* M, void* gu, float* p
                        (const unsigned short*)g, M, (unsigned short*)gu, part, B, HW, accp);
 }
 
+template <int C, typename E = MixBf16>
+void launch_bwd_input(const void* g, const float* M, void* gu, int B, int HW, int nsplit, hipStream_t st) {
+    const size_t lds = frag_bytes<E, C>() + 2 * (size_t)C * kRow;
+    static unsigned long long cfg = 0;
+    ensure_lds((const void*)mix_bwd_bf16_kernel<C, E, false>, (int)lds, cfg);
+    hipLaunchKernelGGL((mix_bwd_bf16_kernel<C, E, false>), dim3((unsigned)nsplit), dim3(C * 4), lds, st, (const unsigned short*)nullptr,
+                       (const unsigned short*)g, M, (unsigned short*)gu, (float*)nullptr, B, HW, 0);
+}
+
 template <int C>
 void launch_split(const void* u, const void* g, const float* M, void* gu, float* part, int B, int HW, int nsplit, int accp,
                   hipStream_t st) {
@@ -496,6 +514,16 @@ void launch_split(const void* u, const void* g, const float* M, void* gu, float*
     ensure_lds((const void*)mix_bwd_split_kernel<C>, (int)lds, cfg);
     hipLaunchKernelGGL((mix_bwd_split_kernel<C>), dim3((unsigned)nsplit), dim3(C * 4), lds, st, (const float*)u, (const float*)g, M,
                        (float*)gu, part, B, HW, accp);
+}
+
+template <int C>
+void launch_split_input(const void* g, const float* M, void* gu, int B, int HW, int nsplit, hipStream_t st) {
+    // fragments | three piece images of g | the fp32 result image (C * kRowF <= 2 * C * kRow)
+    const size_t lds = (size_t)6 * C * C + 5 * (size_t)C * kRow;
+    static unsigned long long cfg = 0;
+    ensure_lds((const void*)mix_bwd_split_kernel<C, false>, (int)lds, cfg);
+    hipLaunchKernelGGL((mix_bwd_split_kernel<C, false>), dim3((unsigned)nsplit), dim3(C * 4), lds, st, (const float*)nullptr,
+                       (const float*)g, M, (float*)gu, (float*)nullptr, B, HW, 0);
 }
 
 }  // namespace
@@ -516,6 +544,13 @@ int mix_split_backward(int B, int C, int HW, const void* u, const void* g, const
     if (C == 32) launch_split<32>(u, g, M, gu, part, B, HW, nsplit, accp, st);
     else if (C == 64) launch_split<64>(u, g, M, gu, part, B, HW, nsplit, accp, st);
     else launch_split<96>(u, g, M, gu, part, B, HW, nsplit, accp, st);
+    return check_launch();
+}
+
+int mix_split_backward_input(int B, int C, int HW, const void* g, const float* M, void* gu, int nsplit, hipStream_t st) {
+    if (C == 32) launch_split_input<32>(g, M, gu, B, HW, nsplit, st);
+    else if (C == 64) launch_split_input<64>(g, M, gu, B, HW, nsplit, st);
+    else launch_split_input<96>(g, M, gu, B, HW, nsplit, st);
     return check_launch();
 }
 
@@ -554,6 +589,17 @@ int mix_f16_backward(int B, int C, int HW, const void* u, const void* g, const f
                      int accp, hipStream_t st) {
     if (C == 64) launch_bwd<64, MixF16>(u, g, M, gu, part, B, HW, nsplit, accp, st);
     else launch_bwd<128, MixF16>(u, g, M, gu, part, B, HW, nsplit, accp, st);
+    return check_launch();
+}
+
+int mix_bf16_backward_input(int B, int C, int HW, const void* g, const float* M, void* gu, int nsplit, hipStream_t st) {
+    if (C == 64) launch_bwd_input<64>(g, M, gu, B, HW, nsplit, st);
+    else launch_bwd_input<128>(g, M, gu, B, HW, nsplit, st);
+    return check_launch();
+}
+int mix_f16_backward_input(int B, int C, int HW, const void* g, const float* M, void* gu, int nsplit, hipStream_t st) {
+    if (C == 64) launch_bwd_input<64, MixF16>(g, M, gu, B, HW, nsplit, st);
+    else launch_bwd_input<128, MixF16>(g, M, gu, B, HW, nsplit, st);
     return check_launch();
 }
 

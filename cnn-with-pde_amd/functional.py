@@ -495,15 +495,15 @@ class _KmaxConcat:
 
 # ---- what the implicit-layer nodes below share: each decision is taken in one place (csrc/host_ext.cpp cuts its nodes the
 # same way, and the two mirrors stay bitwise alike: tests/test_gpu_node_calls.py) --------------------------------------
-def _grad_route(need_u, need_params, input_route: bool = True) -> str:
+def _grad_route(need_u, need_params) -> str:
     """"none" / "full" / "input_only" from what needs a gradient (``grad_mode_of`` in csrc/host_ext.cpp).  "input_only":
-    the input does and no parameter does, so the backward is gu = F^T gy alone — unless the family has no such backward
-    (``input_route`` False) or ``PDE_BWD_INPUT=0`` keeps the full one."""
+    the input does and no parameter does, so the backward is gu = F^T gy alone — unless ``PDE_BWD_INPUT=0`` keeps the
+    full one."""
     if need_params:
         return "full"
     if not need_u:
         return "none"
-    return "input_only" if input_route and L.bwd_input_enabled() else "full"
+    return "input_only" if L.bwd_input_enabled() else "full"
 
 
 def _want_kmax(route: str, ckpt, kmax_sink) -> bool:
@@ -702,7 +702,14 @@ class _AdiMixedFn(torch.autograd.Function):
     One factorisation for the whole schedule, then per step one mixing launch and one sweep launch; the
     backward walks the steps in reverse, accumulating the partial sums of the parameter gradients and of the
     matrix gradient on the device, and reduces them once at the end (instead of a torch autograd node, a
-    factorisation, a reduction and a gradient-accumulation add per step)."""
+    factorisation, a reduction and a gradient-accumulation add per step).
+
+    When the input needs a gradient and neither a coefficient tensor nor ``M`` does, the forward is
+    ``pde_adi_mixed_forward_input`` — no ``states`` tensor, two scratch tensors at most — and the backward one
+    ``pde_adi_mixed_backward_input``: per step M^T g and the transposed solves, bitwise the full backward's gu.  The node
+    then keeps ``M`` and the steps workspace only, asks for no coefficient maxima unless a ``kmax_sink`` was handed in,
+    ignores ``checkpoints`` and waits for nothing.  A call under ``no_grad`` runs the same forward.  ``PDE_BWD_INPUT=0``
+    restores the full calls for both."""
 
     @staticmethod
     def forward(ctx, u, ab, bb, asl, bsl, M, steps, mode, smooth3, clamp_max, eps, ckpt, kmax_sink):
@@ -712,12 +719,27 @@ class _AdiMixedFn(torch.autograd.Function):
             raise L.PdeError(f"expected (B,C,N,N), got {tuple(u.shape)}")
         u = _kernel_input(u, False)
         p, Mf, d, sps, K, sws = _steps_prologue(lib, u, ab, bb, asl, bsl, M, steps, smooth3, clamp_max, eps)
-        route = _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:6]), input_route=False)
+        route = _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:6]))
+        m = 1 if mode == "pre" else 2
+        ctx.input_only = None
+        if route != "full" and L.bwd_input_enabled():
+            y = torch.empty_like(u)
+            ws = _workspace(lib.pde_adi_mixed_forward_input_workspace_bytes(C.byref(d), sps), u.device)
+            with torch.cuda.device(u.device):
+                kdev, ctx.kmax, kargs = _kmax_request(_want_kmax(route, ckpt, kmax_sink), d.num_sweeps, u.device, kmax_sink)
+                L.check(lib.pde_adi_mixed_forward_input(C.byref(d), sps, m, _ptr(u), _ptr(y), _ptr(Mf), *[_ptr(t) for t in p],
+                                                        *kargs, _ptr(sws), sws.numel(), _ptr(ws), ws.numel(), _stream()),
+                        "pde_adi_mixed_forward_input")
+            if route == "input_only":
+                ctx.save_for_backward(Mf)
+                ctx.sws = sws
+                ctx.input_only = (u.dtype, u.device)
+                ctx.cfg = (d, sps, K, m, ckpt)
+            return y
         # states[2k]: output of step k's first operator, states[2k+1]: of its second (= input of step k+1); the last of them
         # is the layer output and lives in a tensor of its own (no copy, and nobody can reach the kept states through it)
         states = torch.empty((2 * K - 1,) + tuple(u.shape), dtype=u.dtype, device=u.device)
         y = torch.empty_like(u)
-        m = 1 if mode == "pre" else 2
         with torch.cuda.device(u.device):
             kdev, ctx.kmax, kargs = _kmax_request(_want_kmax(route, ckpt, kmax_sink), d.num_sweeps, u.device, kmax_sink)
             L.check(lib.pde_adi_mixed_forward(C.byref(d), sps, m, _ptr(u), _ptr(states), _ptr(y), _ptr(Mf),
@@ -734,6 +756,17 @@ class _AdiMixedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         lib = L.load()
+        if ctx.input_only is not None:
+            (Mf,) = ctx.saved_tensors
+            d, sps, K, m, _ = ctx.cfg
+            dtype, device = ctx.input_only
+            g_in = _cotangent(gy, dtype)
+            g_a = torch.empty_like(g_in)
+            ws = _workspace(lib.pde_adi_mixed_backward_input_workspace_bytes(C.byref(d), sps), device)
+            with torch.cuda.device(device):
+                L.check(lib.pde_adi_mixed_backward_input(C.byref(d), sps, m, _ptr(g_in), _ptr(Mf), _ptr(g_a), _ptr(ctx.sws),
+                                                         _ptr(ws), ws.numel(), _stream()), "pde_adi_mixed_backward_input")
+            return (g_a,) + (None,) * 12
         u, states, y, Mf, *p = ctx.saved_tensors
         d, sps, K, m, ckpt = ctx.cfg
         bits = _plan_steps(ctx.kmax.wait(), K, sps) if ckpt == "auto" else int(ckpt)
@@ -1286,12 +1319,28 @@ class _MixFn(torch.autograd.Function):
         with torch.cuda.device(u.device):
             L.check(lib.pde_channel_mix_forward(B, Cc, HW, _io_dtype(u), _ptr(u), _ptr(Mf), _ptr(out), _stream()),
                     "pde_channel_mix_forward")
-        ctx.save_for_backward(u, Mf)
+        # M frozen (the operator is linear in u): the backward is gu = M^T gout alone and reads no u
+        ctx.input_only = None
+        if _grad_route(ctx.needs_input_grad[0], ctx.needs_input_grad[1]) == "input_only":
+            ctx.input_only = (B, Cc, HW, u.dtype)
+            ctx.save_for_backward(Mf)
+        else:
+            ctx.save_for_backward(u, Mf)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lib = L.load()
+        if ctx.input_only is not None:
+            (Mf,) = ctx.saved_tensors
+            B, Cc, HW, dtype = ctx.input_only
+            gout = _aligned(gout.to(dtype).contiguous())
+            gu = torch.empty_like(gout)
+            ws = _workspace(lib.pde_channel_mix_backward_input_workspace_bytes(B, Cc, HW), gout.device)
+            with torch.cuda.device(gout.device):
+                L.check(lib.pde_channel_mix_backward_input(B, Cc, HW, _io_dtype(gout), _ptr(gout), _ptr(Mf), _ptr(gu), _ptr(ws),
+                                                           ws.numel(), _stream()), "pde_channel_mix_backward_input")
+            return gu, None
         u, Mf = ctx.saved_tensors
         B, Cc = u.shape[0], u.shape[1]
         HW = u[0, 0].numel()
@@ -1921,13 +1970,28 @@ class _SkipBlendFn(torch.autograd.Function):
         with torch.cuda.device(b.device):
             L.check(lib.pde_skip_blend_forward(b.numel(), _io_dtype(b), _ptr(a), _ptr(b), _ptr(w), _ptr(out), _stream()),
                     "pde_skip_blend_forward")
-        ctx.save_for_backward(a, b, w)
+        # skip_weight frozen: the backward is the split g_u0 = s g, g_u = (1 - s) g alone and reads neither u0 nor u
+        ctx.input_only = None
+        if _grad_route(any(ctx.needs_input_grad[:2]), ctx.needs_input_grad[2]) == "input_only":
+            ctx.input_only = b.dtype
+            ctx.save_for_backward(w)
+        else:
+            ctx.save_for_backward(a, b, w)
         ctx.in_dtypes = (u0.dtype, u.dtype, skip_weight.dtype, skip_weight.shape)
         return out
 
     @staticmethod
     def backward(ctx, g):
         lib = L.load()
+        if ctx.input_only is not None:
+            (w,) = ctx.saved_tensors
+            g = _aligned(g.to(ctx.input_only).contiguous())
+            g_a, g_b = torch.empty_like(g), torch.empty_like(g)
+            with torch.cuda.device(g.device):
+                L.check(lib.pde_skip_blend_backward_input(g.numel(), _io_dtype(g), _ptr(g), _ptr(w), _ptr(g_a), _ptr(g_b),
+                                                          _stream()), "pde_skip_blend_backward_input")
+            d0, d1, _, _ = ctx.in_dtypes
+            return g_a.to(d0), g_b.to(d1), None
         a, b, w = ctx.saved_tensors
         g = _aligned(g.to(b.dtype).contiguous())
         g_a, g_b = torch.empty_like(a), torch.empty_like(b)
@@ -1987,13 +2051,27 @@ class _MixF64Fn(torch.autograd.Function):
         with torch.cuda.device(u.device):
             L.check(lib.pde_channel_mix_f64_forward(B, Cc, HW, _ptr(u), _ptr(Md), _ptr(out), _stream()),
                     "pde_channel_mix_f64_forward")
-        ctx.save_for_backward(u, Md)
+        ctx.input_only = None
+        if _grad_route(ctx.needs_input_grad[0], ctx.needs_input_grad[1]) == "input_only":
+            ctx.input_only = (B, Cc, HW)
+            ctx.save_for_backward(Md)
+        else:
+            ctx.save_for_backward(u, Md)
         ctx.m_dtype = M.dtype
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lib = L.load()
+        if ctx.input_only is not None:
+            (Md,) = ctx.saved_tensors
+            B, Cc, HW = ctx.input_only
+            gout = gout.to(torch.float64).contiguous()
+            gu = torch.empty_like(gout)
+            with torch.cuda.device(gout.device):
+                L.check(lib.pde_channel_mix_f64_backward_input(B, Cc, HW, _ptr(gout), _ptr(Md), _ptr(gu), _stream()),
+                        "pde_channel_mix_f64_backward_input")
+            return gu, None
         u, Md = ctx.saved_tensors
         B, Cc = u.shape[0], u.shape[1]
         HW = u[0, 0].numel()
@@ -2019,13 +2097,27 @@ class _SkipBlendF64Fn(torch.autograd.Function):
         with torch.cuda.device(b.device):
             L.check(lib.pde_skip_blend_f64_forward(b.numel(), _ptr(a), _ptr(b), _ptr(w), _ptr(out), _stream()),
                     "pde_skip_blend_f64_forward")
-        ctx.save_for_backward(a, b, w)
+        ctx.input_only = False
+        if _grad_route(any(ctx.needs_input_grad[:2]), ctx.needs_input_grad[2]) == "input_only":
+            ctx.input_only = True
+            ctx.save_for_backward(w)
+        else:
+            ctx.save_for_backward(a, b, w)
         ctx.in_meta = (u0.dtype, u.dtype, skip_weight.dtype, skip_weight.shape)
         return out
 
     @staticmethod
     def backward(ctx, g):
         lib = L.load()
+        if ctx.input_only:
+            (w,) = ctx.saved_tensors
+            g = g.to(torch.float64).contiguous()
+            g_a, g_b = torch.empty_like(g), torch.empty_like(g)
+            with torch.cuda.device(g.device):
+                L.check(lib.pde_skip_blend_f64_backward_input(g.numel(), _ptr(g), _ptr(w), _ptr(g_a), _ptr(g_b), _stream()),
+                        "pde_skip_blend_f64_backward_input")
+            d0, d1, _, _ = ctx.in_meta
+            return g_a.to(d0), g_b.to(d1), None
         a, b, w = ctx.saved_tensors
         g = g.to(torch.float64).contiguous()
         g_a, g_b = torch.empty_like(a), torch.empty_like(b)

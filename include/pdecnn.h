@@ -1013,7 +1013,8 @@ int pde_adi_rect_f64_backward_input_states(const PdeAdiRectDescF64* d, const dou
                                            void* stream);
 
 /* The same for the one-launch C <= 4 layers (the K1 calls above and their shared-input groups): declared in
- * pdecnn_small_input.h, which this header includes below. */
+ * pdecnn_small_input.h, which this header includes below; for the layers with a channel operator above C = 4 (the
+ * pde_adi_mixed_* calls, pde_channel_mix_* and pde_skip_blend_*) in pdecnn_mixed_input.h, included below as well. */
 
 /* ---- utilities ------------------------------------------------------------------------- */
 
@@ -1026,6 +1027,7 @@ int pde_timing_read(double* fwd_ms_sum, int64_t* fwd_launches, double* bwd_ms_su
 const char* pde_version(void);
 
 #include "pdecnn_small_input.h"
+#include "pdecnn_mixed_input.h"
 
 #ifdef __cplusplus
 }
