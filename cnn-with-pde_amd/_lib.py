@@ -298,6 +298,29 @@ SIGNATURES_MIXED_INPUT = {
     "pde_adi_mixed_backward_input_one_launch": (C.c_int, [_D, _i32]),
 }
 
+#: include/pdecnn_explicit_input.h (included by pdecnn.h): the input-only backward of the explicit 5-point and the Jacobi
+#: layers — gout, [the emitted states' cotangents, the emission mask,] the parameters, gu; no u, no states, no parameter
+#: gradients
+_M = C.POINTER(C.c_uint64)
+SIGNATURES_EXPLICIT_INPUT = {
+    "pde_explicit5_backward_input_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "pde_explicit5_backward_input": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _f32, _f32, _f32, _f32, _i32, _vp,
+                                               _vp, _sz, _vp]),
+    "pde_explicit5_backward_input_states": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _M, _fp, _fp, _f32, _f32, _f32,
+                                                      _f32, _i32, _vp, _vp, _sz, _vp]),
+    "pde_explicit5_f64_backward_input_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "pde_explicit5_f64_backward_input": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _i32, _vp,
+                                                   _vp, _sz, _vp]),
+    "pde_explicit5_f64_backward_input_states": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _M, _vp, _vp, _f64, _f64, _f64,
+                                                          _f64, _i32, _vp, _vp, _sz, _vp]),
+    "pde_jacobi_io_backward_input_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "pde_jacobi_io_backward_input": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "pde_jacobi_io_backward_input_states": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _M, _fp, _fp, _vp, _vp, _sz,
+                                                      _vp]),
+    "pde_jacobi_f64_backward_input": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pde_jacobi_f64_backward_input_states": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _M, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -312,7 +335,7 @@ def load():
             "(or `make -C cnn-with-pde_amd/csrc`). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_SMALL_INPUT.items()) +
-                              list(SIGNATURES_MIXED_INPUT.items())):
+                              list(SIGNATURES_MIXED_INPUT.items()) + list(SIGNATURES_EXPLICIT_INPUT.items())):
         fn = getattr(lib, name)         # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -32,6 +32,13 @@
 //   Backward: once the walk holds the adjoint of an emitted state, that state's upstream gradient is added to it (interior
 //   cells only for Jacobi).  No launch is added: an empty mask runs the plain instantiations, and the plain entry points
 //   are the *_states ones with a NULL mask.
+//
+// input-only backward (pdecnn_explicit_input.h: pde_explicit5_backward_input[_states], pde_jacobi_io_backward_input[_states]):
+//   both layers are linear in u, so with frozen parameters gu is the adjoint walk alone.  Every backward kernel above has a
+//   twin of its own (explicit5_bwd_input_wave, explicit5_bwd_input[_col]_kernel, jacobi_bwd_input_kernel,
+//   jacobi_tiled_bwd_input_kernel) that is the reverse walk with everything but the adjoint removed — no u, no states, no
+//   dots, no partial sums, no pgrad launch; the Jacobi twins re-run no forward and park nothing.  What happens to the adjoint
+//   is written as it is in the full kernel, in its order, so gu has the same bits; the full kernels stay as they are.
 #include <type_traits>
 
 #include "pde_common.h"
@@ -277,6 +284,59 @@ __global__ __launch_bounds__(256) void explicit5_bwd_col_kernel(const TU* __rest
     }
 }
 
+// The adjoint of one step alone (pde_explicit5_backward_input[_states]: alpha_base and channel_scaling take no gradient):
+// explicit5_bwd_kernel / explicit5_bwd_col_kernel without the u loads, the two dots and `part`.  What happens to g is
+// written as it is there, in the same order, so gu has the same bits.
+template <typename TG, typename TO, typename TE = void>
+__global__ __launch_bounds__(256) void explicit5_bwd_input_kernel(const TG* __restrict__ g, const float* __restrict__ alpha,
+                                                                  const float* __restrict__ scale, TO* __restrict__ gu,
+                                                                  int C, int H, int W, float dt, float eps, float maxc,
+                                                                  float relax, typename EmitPtr<const TE>::type ginj) {
+    const int pc = blockIdx.x;
+    const int c = pc % C;
+    const float a = fminf(fmaxf(alpha[c], eps), maxc) * dt;
+    const float s = scale[c];
+    const TG* gp = g + (size_t)pc * H * W;
+    TO* op = gu + (size_t)pc * H * W;
+    const int W4 = W / 4;
+    for (int f = threadIdx.x; f < H * W4; f += 256) {
+        const int h = f / W4, w0 = 4 * (f % W4);
+        const float4 cg = V4<TG>::ld(gp + (size_t)h * W + w0);
+        const float4 lg = lap0_4<TG>(gp, H, W, h, w0, cg);
+        float4 o;
+        o.x = (1.f - relax) * cg.x + relax * s * (cg.x + a * lg.x);
+        o.y = (1.f - relax) * cg.y + relax * s * (cg.y + a * lg.y);
+        o.z = (1.f - relax) * cg.z + relax * s * (cg.z + a * lg.z);
+        o.w = (1.f - relax) * cg.w + relax * s * (cg.w + a * lg.w);
+        if constexpr (!std::is_void<TE>::value) {
+            const float4 gi = V4<TE>::ld_once(ginj + (size_t)pc * H * W + (size_t)h * W + w0);
+            o.x += gi.x; o.y += gi.y; o.z += gi.z; o.w += gi.w;
+        }
+        V4<TO>::st(op + (size_t)h * W + w0, o);
+    }
+}
+
+template <typename TG, typename TO, typename TE = void>
+__global__ __launch_bounds__(256) void explicit5_bwd_input_col_kernel(const TG* __restrict__ g, const float* __restrict__ alpha,
+                                                                      const float* __restrict__ scale, TO* __restrict__ gu,
+                                                                      int C, int H, int W, float dt, float eps, float maxc,
+                                                                      float relax, typename EmitPtr<const TE>::type ginj) {
+    const int pc = blockIdx.x;
+    const int c = pc % C;
+    const float a = fminf(fmaxf(alpha[c], eps), maxc) * dt;
+    const float s = scale[c];
+    const TG* gp = g + (size_t)pc * H * W;
+    TO* op = gu + (size_t)pc * H * W;
+    for (int f = threadIdx.x; f < H * W; f += 256) {
+        const int h = f / W, w = f % W;
+        const float cg = S1<TG>::ld(gp + f);
+        const float lg = lap0_1<TG>(gp, H, W, h, w, cg);
+        float o = (1.f - relax) * cg + relax * s * (cg + a * lg);
+        if constexpr (!std::is_void<TE>::value) o += S1<TE>::ld(ginj + (size_t)pc * H * W + f);
+        S1<TO>::st(op + f, o);
+    }
+}
+
 // one workgroup per channel: 256 threads add the per-plane partial sums of their samples, then a
 // fixed-order block reduction (a single 64-thread block looping over all samples took 84 us at B=256)
 __global__ __launch_bounds__(256) void explicit5_pgrad_kernel(const float* __restrict__ part,
@@ -449,6 +509,52 @@ __global__ __launch_bounds__(256) void explicit5_bwd_wave(const IO* __restrict__
     if (lane == 0) { part[2 * (size_t)pc] = p1; part[2 * (size_t)pc + 1] = p2; }
 }
 
+// The same reverse walk for the input alone (alpha_base and channel_scaling take no gradient): explicit5_bwd_wave without
+// the u / states loads, the two dots, the wave sums and `part`; per step g goes through the operations it goes through
+// there, in their order, so gu has the same bits.  Same grid and lane map.
+template <typename IO, int R, int W4, bool EMIT = false>
+__global__ __launch_bounds__(256) void explicit5_bwd_input_wave(const IO* __restrict__ g, const float* __restrict__ alpha,
+                                                                const float* __restrict__ scale, IO* __restrict__ gu,
+                                                                int nplanes, int C, int num_steps, float dt, float eps,
+                                                                float maxc, float relax, const IO* __restrict__ gtraj,
+                                                                EmitMask em) {
+    constexpr int W = 4 * W4, H = R * (64 / W4);
+    const int lane = threadIdx.x & 63;
+    const int pc = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pc >= nplanes) return;
+    const int c = pc % C;
+    const float a = fminf(fmaxf(alpha[c], eps), maxc) * dt;
+    const float s = scale[c];
+    const int cg = lane % W4, rg = lane / W4;
+    const size_t off = (size_t)pc * H * W + (size_t)(rg * R) * W + 4 * cg;
+    float4 cg4[R], lg[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) cg4[i] = V4<IO>::ld_once(g + off + (size_t)i * W);
+    for (int step = num_steps; step >= 1; --step) {
+        lap0_rows<R, W4>(cg4, lg, cg, rg);
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            cg4[i].x = (1.f - relax) * cg4[i].x + relax * s * (cg4[i].x + a * lg[i].x);
+            cg4[i].y = (1.f - relax) * cg4[i].y + relax * s * (cg4[i].y + a * lg[i].y);
+            cg4[i].z = (1.f - relax) * cg4[i].z + relax * s * (cg4[i].z + a * lg[i].z);
+            cg4[i].w = (1.f - relax) * cg4[i].w + relax * s * (cg4[i].w + a * lg[i].w);
+        }
+        if constexpr (EMIT) {                                     // g is now the adjoint of the state after step - 1
+            const int slot = emit_slot(em, step - 1);
+            if (slot >= 0) {
+                const IO* tp = gtraj + (size_t)slot * nplanes * H * W;
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    const float4 gi = V4<IO>::ld_once(tp + off + (size_t)i * W);
+                    cg4[i].x += gi.x; cg4[i].y += gi.y; cg4[i].z += gi.z; cg4[i].w += gi.w;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) V4<IO>::st(gu + off + (size_t)i * W, cg4[i]);
+}
+
 // which plane sizes the wave-per-plane kernels cover
 bool wave_plane_ok(int H, int W) { return (H == 64 && W == 64) || (H == 32 && W == 32) || (H == 16 && W == 16); }
 
@@ -482,6 +588,23 @@ void bwd_wave_io(int H, const void* u, const float* states, const void* g, const
                  const void* gtraj, EmitMask em, hipStream_t st) {
     if (em.any()) launch_bwd_wave<IO, true>(H, (const IO*)u, states, (const IO*)g, alpha, scale, (IO*)gu, part, nplanes, C, num_steps, dt, eps, maxc, relax, (const IO*)gtraj, em, st);
     else launch_bwd_wave<IO, false>(H, (const IO*)u, states, (const IO*)g, alpha, scale, (IO*)gu, part, nplanes, C, num_steps, dt, eps, maxc, relax, (const IO*)nullptr, em, st);
+}
+
+template <typename IO, bool EMIT>
+void launch_bwd_input_wave(int H, const IO* g, const float* alpha, const float* scale, IO* gu, int nplanes, int C,
+                           int num_steps, float dt, float eps, float maxc, float relax, const IO* gtraj, EmitMask em,
+                           hipStream_t st) {
+    const dim3 grid((nplanes + 3) / 4), block(256);
+    if (H == 64) hipLaunchKernelGGL((explicit5_bwd_input_wave<IO, 16, 16, EMIT>), grid, block, 0, st, g, alpha, scale, gu, nplanes, C, num_steps, dt, eps, maxc, relax, gtraj, em);
+    else if (H == 32) hipLaunchKernelGGL((explicit5_bwd_input_wave<IO, 4, 8, EMIT>), grid, block, 0, st, g, alpha, scale, gu, nplanes, C, num_steps, dt, eps, maxc, relax, gtraj, em);
+    else hipLaunchKernelGGL((explicit5_bwd_input_wave<IO, 1, 4, EMIT>), grid, block, 0, st, g, alpha, scale, gu, nplanes, C, num_steps, dt, eps, maxc, relax, gtraj, em);
+}
+template <typename IO>
+void bwd_input_wave_io(int H, const void* g, const float* alpha, const float* scale, void* gu, int nplanes, int C,
+                       int num_steps, float dt, float eps, float maxc, float relax, const void* gtraj, EmitMask em,
+                       hipStream_t st) {
+    if (em.any()) launch_bwd_input_wave<IO, true>(H, (const IO*)g, alpha, scale, (IO*)gu, nplanes, C, num_steps, dt, eps, maxc, relax, (const IO*)gtraj, em, st);
+    else launch_bwd_input_wave<IO, false>(H, (const IO*)g, alpha, scale, (IO*)gu, nplanes, C, num_steps, dt, eps, maxc, relax, (const IO*)nullptr, em, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -671,6 +794,81 @@ __global__ void jacobi_pgrad_kernel(const float* __restrict__ part, float* __res
     if (r < H) ga[r] = s; else gb[r - H] = s;
 }
 
+// The adjoint alone (pde_jacobi_io_backward_input[_states]: a_row and b_col take no gradient): jacobi_bwd_kernel without
+// the forward recompute, the parked states and the row / column dots.  LDS: G, Gn, a, b.  The nt updates and the fold
+// are written as they are there, so gu has the same bits; nt = 0 leaves gu = gout.
+template <typename IO, bool EMIT = false>
+__global__ __launch_bounds__(256) void jacobi_bwd_input_kernel(const IO* __restrict__ gout, const float* __restrict__ a_row,
+                                                               const float* __restrict__ b_col, IO* __restrict__ gu,
+                                                               int H, int W, int nt, const IO* __restrict__ gtraj,
+                                                               EmitMask em) {
+    extern __shared__ float sm[];
+    const int Wp = W + 2, PN = (H + 2) * Wp;
+    float* G = sm;
+    float* Gn = sm + PN;
+    float* a = sm + 2 * PN;
+    float* b = a + H;
+    const int s = blockIdx.x;
+    for (int e = threadIdx.x; e < H; e += blockDim.x) a[e] = a_row[e];
+    for (int e = threadIdx.x; e < W; e += blockDim.x) b[e] = b_col[e];
+    // G = dL/dP_nt (zero ring, gout inside)
+    const IO* gob = gout + (size_t)s * H * W;
+    for (int e = threadIdx.x; e < PN; e += blockDim.x) {
+        const int i = e / Wp, j = e % Wp;
+        G[e] = (i >= 1 && i <= H && j >= 1 && j <= W) ? S1<IO>::ld(gob + (i - 1) * W + (j - 1)) : 0.f;
+    }
+    __syncthreads();
+    for (int n = nt - 1; n >= 0; --n) {
+        // dL/dP_n from dL/dP_{n+1}
+        const IO* gt = nullptr;                                // dL/d(state after step n), where that state was emitted
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, n);
+            if (slot >= 0) gt = gtraj + ((size_t)slot * gridDim.x + s) * H * W;
+        }
+        for (int e = threadIdx.x; e < PN; e += blockDim.x) {
+            const int i = e / Wp, j = e % Wp;
+            const bool in = (i >= 1 && i <= H && j >= 1 && j <= W);
+            float v = in ? (1.f - 2.f * a[i - 1] - 2.f * b[j - 1]) * G[e] : G[e];
+            if (j >= 1 && j <= W) {                                       // vertical neighbours are interior columns
+                if (i - 1 >= 1 && i - 1 <= H) v += a[i - 2] * G[e - Wp];
+                if (i + 1 >= 1 && i + 1 <= H) v += a[i] * G[e + Wp];
+            }
+            if (i >= 1 && i <= H) {
+                if (j - 1 >= 1 && j - 1 <= W) v += b[j - 2] * G[e - 1];
+                if (j + 1 >= 1 && j + 1 <= W) v += b[j] * G[e + 1];
+            }
+            if constexpr (EMIT) {
+                if (gt && in) v += S1<IO>::ld(gt + (i - 1) * W + (j - 1));
+            }
+            Gn[e] = v;
+        }
+        __syncthreads();
+        float* t = G; G = Gn; Gn = t;
+    }
+    // adjoint of the reflect padding: fold the ring back onto rows/cols 1 and H-2 / W-2
+    IO* gub = gu + (size_t)s * H * W;
+    for (int e = threadIdx.x; e < H * W; e += blockDim.x) {
+        const int i = e / W, j = e % W;
+        float v = 0.f;
+        for (int di = 0; di < 2; ++di) {
+            int m;
+            if (di == 0) m = i + 1;
+            else if (i == 1) m = 0;
+            else if (i == H - 2) m = H + 1;
+            else continue;
+            for (int dj = 0; dj < 2; ++dj) {
+                int nn;
+                if (dj == 0) nn = j + 1;
+                else if (j == 1) nn = 0;
+                else if (j == W - 2) nn = W + 1;
+                else continue;
+                v += G[m * Wp + nn];
+            }
+        }
+        S1<IO>::st(gub + e, v);
+    }
+}
+
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 #include "pde_jacobi_tiled.h"
@@ -758,6 +956,30 @@ int jacobi_tiled_backward(int B, int H, int W, int nt, const void* u, const void
     return check_launch();
 }
 
+// the tiled adjoint alone: the adjoint launches without P_n, chained through the two padded fp32 images, then the fold
+size_t jacobi_tiled_gimg_bytes(int B, int H, int W) { return align256((size_t)B * (H + 2) * (W + 2) * sizeof(float)); }
+template <typename IO, bool EMIT>
+int jacobi_tiled_backward_input(int B, int H, int W, int nt, const void* gout, const float* a_row, const float* b_col,
+                                void* gu, void* workspace, const void* gtraj, EmitMask em, hipStream_t st) {
+    const int nTy = jtiles(H), nTx = jtiles(W);
+    const dim3 grid((unsigned)((size_t)B * nTy * nTx));
+    char* base = static_cast<char*>(workspace);
+    float* gimg[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + jacobi_tiled_gimg_bytes(B, H, W))};
+    int n_hi = nt, l = 0;
+    do {                                                    // nt = 0: one launch of no steps pads gout
+        const int k = n_hi < kJK ? n_hi : kJK;
+        hipLaunchKernelGGL((jacobi_tiled_bwd_input_kernel<IO, EMIT>), grid, dim3(256), 0, st,
+                           l == 0 ? (const IO*)gout : (const IO*)nullptr, (const float*)gimg[(l + 1) & 1], gimg[l & 1], a_row,
+                           b_col, (size_t)B * H * W, H, W, nTy, nTx, n_hi, k, (const IO*)gtraj, em);
+        n_hi -= k;
+        ++l;
+    } while (n_hi > 0);
+    const int nRb = (H + 31) / 32, nCb = (W + 31) / 32;
+    hipLaunchKernelGGL(jacobi_tiled_fold_kernel<IO>, dim3((unsigned)((size_t)B * nRb * nCb)), dim3(256), 0, st,
+                       (const float*)gimg[(l - 1) & 1], (IO*)gu, H, W, nRb, nCb);
+    return check_launch();
+}
+
 // One step of the generic-size path: the tensors of the call are of type T (float, bf16e, f16e) — the layer's input is
 // read in the first step, its output written in the last; what passes between the steps is fp32.
 struct ExArgs {
@@ -808,6 +1030,28 @@ void ex_bwd_step(const ExArgs& a, bool ufirst, bool gfirst, const void* up, cons
     else if (ufirst) ex_bwd<T, float, T>(a, up, gin, gdst, part, acc, NoEmit{}, st);
     else if (gfirst) ex_bwd<float, T, float>(a, up, gin, gdst, part, acc, NoEmit{}, st);
     else ex_bwd<float, float, float>(a, up, gin, gdst, part, acc, NoEmit{}, st);
+}
+
+// the same step for the input alone: no u, no partial sums
+template <typename TG, typename TO, typename TE = void>
+void ex_bwd_input(const ExArgs& a, const void* gin, void* gdst, typename EmitPtr<const TE>::type ginj, hipStream_t st) {
+    if (a.W % 4)
+        hipLaunchKernelGGL((explicit5_bwd_input_col_kernel<TG, TO, TE>), dim3(a.nplanes), dim3(256), 0, st, (const TG*)gin,
+                           a.alpha, a.scale, (TO*)gdst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, ginj);
+    else
+        hipLaunchKernelGGL((explicit5_bwd_input_kernel<TG, TO, TE>), dim3(a.nplanes), dim3(256), 0, st, (const TG*)gin,
+                           a.alpha, a.scale, (TO*)gdst, a.C, a.H, a.W, a.dt, a.eps, a.maxc, a.relax, ginj);
+}
+// glast: the step that writes the caller's gu (step 1); gfirst: the step that reads the caller's gout (step num_steps)
+template <typename T>
+void ex_bwd_input_step(const ExArgs& a, bool glast, bool gfirst, const void* gin, void* gdst, const void* ginj,
+                       hipStream_t st) {
+    if (ginj && gfirst) ex_bwd_input<T, float, T>(a, gin, gdst, (const T*)ginj, st);
+    else if (ginj) ex_bwd_input<float, float, T>(a, gin, gdst, (const T*)ginj, st);
+    else if (glast && gfirst) ex_bwd_input<T, T>(a, gin, gdst, NoEmit{}, st);
+    else if (glast) ex_bwd_input<float, T>(a, gin, gdst, NoEmit{}, st);
+    else if (gfirst) ex_bwd_input<T, float>(a, gin, gdst, NoEmit{}, st);
+    else ex_bwd_input<float, float>(a, gin, gdst, NoEmit{}, st);
 }
 
 // Where the call's own tensors may begin (pdecnn.h, "Alignment"): planes whose rows are whole groups of four columns move
@@ -1099,6 +1343,132 @@ int pde_jacobi_io_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, i
     if (io_dtype == PDE_IO_BF16)
         return jacobi_backward_io<bf16e>(path, B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, gstates, em, st);
     return jacobi_backward_io<f16e>(path, B, H, W, nt, u, gout, a_row, b_col, gu, g_a_row, g_b_col, workspace, gstates, em, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// the backward for the input alone (pdecnn_explicit_input.h): the parameters take no gradient
+// ---------------------------------------------------------------------------------------
+extern "C" {
+
+size_t pde_explicit5_backward_input_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype,
+                                                    int32_t num_steps) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 2 || wave_plane_ok(H, W)) return 0;
+    return 2 * align256((size_t)B * C * H * W * sizeof(float));     // generic sizes: two gradient buffers to ping-pong through
+}
+
+int pde_explicit5_backward_input(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype, const void* gout,
+                                 const float* alpha_base, const float* channel_scaling, float dt, float eps, float max_coeff,
+                                 float relax, int32_t num_steps, void* gu, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    return pde_explicit5_backward_input_states(B, C, H, W, io_dtype, gout, nullptr, nullptr, alpha_base, channel_scaling, dt,
+                                               eps, max_coeff, relax, num_steps, gu, workspace, workspace_bytes, stream);
+}
+
+int pde_explicit5_backward_input_states(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype, const void* gout,
+                                        const void* gtraj, const uint64_t emit_mask[2], const float* alpha_base,
+                                        const float* channel_scaling, float dt, float eps, float max_coeff, float relax,
+                                        int32_t num_steps, void* gu, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !gout || !alpha_base || !channel_scaling || !gu)
+        return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    if (misaligned(ex_tensor_align(W, io_dtype), gout, gtraj, gu) || misaligned(4, alpha_base, channel_scaling))
+        return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, num_steps, gtraj, em);
+    if (erc != PDE_OK) return erc;
+    // the two gradient buffers are read and written as float4 on the generic float4 path
+    const size_t need = pde_explicit5_backward_input_workspace_bytes(B, C, H, W, io_dtype, num_steps);
+    if ((need && (!workspace || workspace_bytes < need)) || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nplanes = B * C;
+    if (wave_plane_ok(H, W)) {
+        if (io_dtype == PDE_IO_F32)
+            bwd_input_wave_io<float>(H, gout, alpha_base, channel_scaling, gu, nplanes, C, num_steps, dt, eps, max_coeff, relax,
+                                     gtraj, em, st);
+        else if (io_dtype == PDE_IO_F16)
+            bwd_input_wave_io<f16e>(H, gout, alpha_base, channel_scaling, gu, nplanes, C, num_steps, dt, eps, max_coeff, relax,
+                                    gtraj, em, st);
+        else
+            bwd_input_wave_io<bf16e>(H, gout, alpha_base, channel_scaling, gu, nplanes, C, num_steps, dt, eps, max_coeff, relax,
+                                     gtraj, em, st);
+        return check_launch();
+    }
+    // what passes between the steps is fp32, whatever io_dtype
+    const size_t tf = (size_t)nplanes * H * W;
+    float* buf0 = static_cast<float*>(workspace);
+    float* buf1 = need ? reinterpret_cast<float*>(static_cast<char*>(workspace) + align256(tf * sizeof(float))) : nullptr;
+    const size_t esz = io_dtype == PDE_IO_F32 ? 4 : 2;
+    const ExArgs ea{alpha_base, channel_scaling, nplanes, C, H, W, dt, eps, max_coeff, relax};
+    const void* gin = gout;
+    for (int k = num_steps; k >= 1; --k) {
+        const bool glast = k == 1, gfirst = k == num_steps;            // gu / gout are the caller's tensors
+        void* gdst = glast ? gu : static_cast<void*>(gin == buf0 ? buf1 : buf0);
+        const int slot = emit_slot(em, k - 1);             // gdst is the adjoint of the state after step k-1
+        const void* ginj = slot >= 0 ? static_cast<const void*>(static_cast<const char*>(gtraj) + (size_t)slot * tf * esz)
+                                     : nullptr;
+        if (io_dtype == PDE_IO_F32) ex_bwd_input_step<float>(ea, glast, gfirst, gin, gdst, ginj, st);
+        else if (io_dtype == PDE_IO_F16) ex_bwd_input_step<f16e>(ea, glast, gfirst, gin, gdst, ginj, st);
+        else ex_bwd_input_step<bf16e>(ea, glast, gfirst, gin, gdst, ginj, st);
+        gin = gdst;
+    }
+    return check_launch();
+}
+
+size_t pde_jacobi_io_backward_input_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype) {
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return 0;
+    if (B <= 0 || nt < 0 || jacobi_path(H, W) != 2) return 0;
+    return 2 * jacobi_tiled_gimg_bytes(B, H, W);           // the two padded fp32 images the adjoint launches chain through
+}
+
+}  // extern "C"
+
+template <typename IO>
+static int jacobi_backward_input_io(int path, int B, int H, int W, int nt, const void* gout, const float* a_row,
+                                    const float* b_col, void* gu, void* workspace, const void* gtraj, EmitMask em,
+                                    hipStream_t st) {
+    if (path == 2)
+        return em.any() ? jacobi_tiled_backward_input<IO, true>(B, H, W, nt, gout, a_row, b_col, gu, workspace, gtraj, em, st)
+                        : jacobi_tiled_backward_input<IO, false>(B, H, W, nt, gout, a_row, b_col, gu, workspace, nullptr, em, st);
+    const size_t lds = jacobi_lds(H, W, false);            // G, Gn, a, b
+    if (em.any())
+        hipLaunchKernelGGL((jacobi_bwd_input_kernel<IO, true>), dim3(B), dim3(256), lds, st, (const IO*)gout, a_row, b_col,
+                           (IO*)gu, H, W, nt, (const IO*)gtraj, em);
+    else
+        hipLaunchKernelGGL((jacobi_bwd_input_kernel<IO, false>), dim3(B), dim3(256), lds, st, (const IO*)gout, a_row, b_col,
+                           (IO*)gu, H, W, nt, (const IO*)nullptr, em);
+    return check_launch();
+}
+
+extern "C" {
+
+int pde_jacobi_io_backward_input(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* gout,
+                                 const float* a_row, const float* b_col, void* gu, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    return pde_jacobi_io_backward_input_states(B, H, W, nt, io_dtype, gout, nullptr, nullptr, a_row, b_col, gu, workspace,
+                                               workspace_bytes, stream);
+}
+
+int pde_jacobi_io_backward_input_states(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* gout,
+                                        const void* gstates, const uint64_t emit_mask[2], const float* a_row,
+                                        const float* b_col, void* gu, void* workspace, size_t workspace_bytes, void* stream) {
+    const int path = jacobi_path(H, W);
+    if (B <= 0 || path == 0 || nt < 0 || !gout || !a_row || !b_col || !gu) return PDE_E_BADARG;
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    if (misaligned(io_elem_bytes(io_dtype), gout, gstates, gu) || misaligned(4, a_row, b_col)) return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, nt, gstates, em);
+    if (erc != PDE_OK) return erc;
+    const size_t need = pde_jacobi_io_backward_input_workspace_bytes(B, H, W, nt, io_dtype);
+    if ((need && (!workspace || workspace_bytes < need)) || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (path == 2 && !jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
+    if (io_dtype == PDE_IO_F32)
+        return jacobi_backward_input_io<float>(path, B, H, W, nt, gout, a_row, b_col, gu, workspace, gstates, em, st);
+    if (io_dtype == PDE_IO_BF16)
+        return jacobi_backward_input_io<bf16e>(path, B, H, W, nt, gout, a_row, b_col, gu, workspace, gstates, em, st);
+    return jacobi_backward_input_io<f16e>(path, B, H, W, nt, gout, a_row, b_col, gu, workspace, gstates, em, st);
 }
 
 }  // extern "C"

@@ -206,6 +206,29 @@ __global__ __launch_bounds__(256) void expl64_bwd_kernel(int C, int H, int W, co
     }
 }
 
+// the adjoint of one step alone (pde_explicit5_f64_backward_input[_states]: the parameters take no gradient):
+// expl64_bwd_kernel without x, the two sums and `part`; gx is formed as it is there
+template <bool EMIT = false>
+__global__ __launch_bounds__(256) void expl64_bwd_input_kernel(int C, int H, int W, const double* __restrict__ g,
+                                                               const double* __restrict__ ab, const double* __restrict__ sc,
+                                                               double dt, double eps, double maxc, double relax,
+                                                               double* __restrict__ gx, const double* __restrict__ ginj) {
+    const int HW = H * W, c = blockIdx.x % C, b = blockIdx.x / C;
+    const size_t off = ((size_t)b * C + c) * HW;
+    const double* gp = g + off;
+    const double s = sc[c], k = clamp64(ab[c], eps, maxc) * dt;
+    for (int p = threadIdx.x; p < HW; p += 256) {
+        const int i = p / W, j = p % W;
+        const double r = relax * gp[p];
+        const double rup = i > 0 ? relax * gp[p - W] : 0.0, rdn = i + 1 < H ? relax * gp[p + W] : 0.0;
+        const double rlf = j > 0 ? relax * gp[p - 1] : 0.0, rrt = j + 1 < W ? relax * gp[p + 1] : 0.0;
+        const double gv = r + k * ((((rup + rdn) + rlf) + rrt) - 4.0 * r);
+        double o = (1.0 - relax) * gp[p] + s * gv;
+        if constexpr (EMIT) o += ginj[off + p];
+        gx[off + p] = o;
+    }
+}
+
 __global__ void expl64_reduce_kernel(int B, int C, const double* __restrict__ part, const double* __restrict__ ab,
                                      double dt, double eps, double maxc, double* __restrict__ ga, double* __restrict__ gs) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -323,6 +346,61 @@ __global__ __launch_bounds__(256) void jac64_bwd_kernel(int H, int W, int nt, co
     }
     if (tid < H) pa[(size_t)b * H + tid] = acc;
     else if (tid >= 64 && tid < 64 + W) pb[(size_t)b * W + tid - 64] = acc;
+    // reflect padding transposed: every padded entry goes to the input element it was copied from (fixed order)
+    for (int e = tid; e < H * W; e += blockDim.x) {
+        const int r = e / W, c = e % W;
+        int rows[3], cols[3], nr = 0, nc = 0;
+        rows[nr++] = r + 1;
+        if (r == 1) rows[nr++] = 0;
+        if (r == H - 2) rows[nr++] = H + 1;
+        cols[nc++] = c + 1;
+        if (c == 1) cols[nc++] = 0;
+        if (c == W - 2) cols[nc++] = W + 1;
+        double s = 0.0;
+        for (int x = 0; x < nr; ++x)
+            for (int y = 0; y < nc; ++y) s += G[rows[x] * Wp + cols[y]];
+        gu[(size_t)b * H * W + e] = s;
+    }
+}
+
+// the adjoint alone (pde_jacobi_f64_backward_input[_states]: a_row and b_col take no gradient): jac64_bwd_kernel without
+// the parked states and the row / column sums; G is updated and folded as it is there
+template <bool EMIT = false>
+__global__ __launch_bounds__(256) void jac64_bwd_input_kernel(int H, int W, int nt, const double* __restrict__ gout,
+                                                              const double* __restrict__ a, const double* __restrict__ bc,
+                                                              double* __restrict__ gu, const double* __restrict__ gtraj,
+                                                              EmitMask em) {
+    extern __shared__ double jsm[];
+    const int Hp = H + 2, Wp = W + 2, PP = Hp * Wp, b = blockIdx.x, tid = threadIdx.x;
+    double* G = jsm;
+    double* G2 = jsm + PP;
+    for (int e = tid; e < PP; e += blockDim.x) {
+        const int i = e / Wp, j = e % Wp;
+        G[e] = (i >= 1 && i <= H && j >= 1 && j <= W) ? gout[(size_t)b * H * W + (i - 1) * W + (j - 1)] : 0.0;
+    }
+    __syncthreads();
+    for (int k = nt - 1; k >= 0; --k) {
+        const double* gt = nullptr;                           // dL/d(state after step k), where that state was emitted
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, k);
+            if (slot >= 0) gt = gtraj + ((size_t)slot * gridDim.x + b) * H * W;
+        }
+        for (int e = tid; e < PP; e += blockDim.x) {
+            const int i = e / Wp, j = e % Wp;
+            const bool inner = i >= 1 && i <= H && j >= 1 && j <= W;
+            double v = inner ? G[e] * ((1.0 - 2.0 * a[i - 1]) - 2.0 * bc[j - 1]) : G[e];
+            if (i - 1 >= 1 && i - 1 <= H && j >= 1 && j <= W) v += a[i - 2] * G[e - Wp];
+            if (i + 1 >= 1 && i + 1 <= H && j >= 1 && j <= W) v += a[i] * G[e + Wp];
+            if (j - 1 >= 1 && j - 1 <= W && i >= 1 && i <= H) v += bc[j - 2] * G[e - 1];
+            if (j + 1 >= 1 && j + 1 <= W && i >= 1 && i <= H) v += bc[j] * G[e + 1];
+            if constexpr (EMIT) {
+                if (gt && inner) v += gt[(i - 1) * W + (j - 1)];
+            }
+            G2[e] = v;
+        }
+        __syncthreads();
+        double* t = G; G = G2; G2 = t;
+    }
     // reflect padding transposed: every padded entry goes to the input element it was copied from (fixed order)
     for (int e = tid; e < H * W; e += blockDim.x) {
         const int r = e / W, c = e % W;
@@ -615,6 +693,78 @@ int pde_jacobi_f64_backward_states(int32_t B, int32_t H, int32_t W, int32_t nt, 
         hipLaunchKernelGGL(jac64_bwd_kernel<false>, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, gout, a_row, b_col,
                            states, gu, pa, pb, (const double*)nullptr, em);
     hipLaunchKernelGGL(jac64_reduce_kernel, dim3((H + W + 127) / 128), dim3(128), 0, st, B, H, W, pa, pb, g_a_row, g_b_col);
+    return check_launch();
+}
+
+// ---- the backward for the input alone (pdecnn_explicit_input.h): the parameters take no gradient -----------------------
+size_t pde_explicit5_f64_backward_input_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_steps) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 2) return 0;
+    return 2 * up256((size_t)B * C * H * W * sizeof(double));
+}
+
+int pde_explicit5_f64_backward_input(int32_t B, int32_t C, int32_t H, int32_t W, const double* gout, const double* alpha_base,
+                                     const double* channel_scaling, double dt, double eps, double max_coeff, double relax,
+                                     int32_t num_steps, double* gu, void* workspace, size_t workspace_bytes, void* stream) {
+    return pde_explicit5_f64_backward_input_states(B, C, H, W, gout, nullptr, nullptr, alpha_base, channel_scaling, dt, eps,
+                                                   max_coeff, relax, num_steps, gu, workspace, workspace_bytes, stream);
+}
+
+int pde_explicit5_f64_backward_input_states(int32_t B, int32_t C, int32_t H, int32_t W, const double* gout,
+                                            const double* gtraj, const uint64_t emit_mask[2], const double* alpha_base,
+                                            const double* channel_scaling, double dt, double eps, double max_coeff,
+                                            double relax, int32_t num_steps, double* gu, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !gout || !alpha_base || !channel_scaling || !gu)
+        return PDE_E_BADARG;
+    if (misaligned(8, gout, gtraj, alpha_base, channel_scaling, gu)) return PDE_E_BADARG;
+    EmitMask em;
+    const int erc = emit_check(emit_mask, num_steps, gtraj, em);
+    if (erc != PDE_OK) return erc;
+    const size_t need = pde_explicit5_f64_backward_input_workspace_bytes(B, C, H, W, num_steps);
+    if ((need && (!workspace || workspace_bytes < need)) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)B * C * H * W;
+    char* ws = static_cast<char*>(workspace);
+    double* buf[2] = {reinterpret_cast<double*>(ws), need ? reinterpret_cast<double*>(ws + up256(n * sizeof(double))) : nullptr};
+    const double* g = gout;
+    for (int k = num_steps - 1; k >= 0; --k) {
+        double* gx = k == 0 ? gu : buf[k & 1];
+        const int slot = emit_slot(em, k);                 // gx is the adjoint of the state after step k
+        if (slot >= 0)
+            hipLaunchKernelGGL(expl64_bwd_input_kernel<true>, dim3(B * C), dim3(256), 0, st, C, H, W, g, alpha_base,
+                               channel_scaling, dt, eps, max_coeff, relax, gx, gtraj + (size_t)slot * n);
+        else
+            hipLaunchKernelGGL(expl64_bwd_input_kernel<false>, dim3(B * C), dim3(256), 0, st, C, H, W, g, alpha_base,
+                               channel_scaling, dt, eps, max_coeff, relax, gx, (const double*)nullptr);
+        g = gx;
+    }
+    return check_launch();
+}
+
+int pde_jacobi_f64_backward_input(int32_t B, int32_t H, int32_t W, int32_t nt, const double* gout, const double* a_row,
+                                  const double* b_col, double* gu, void* stream) {
+    return pde_jacobi_f64_backward_input_states(B, H, W, nt, gout, nullptr, nullptr, a_row, b_col, gu, stream);
+}
+
+int pde_jacobi_f64_backward_input_states(int32_t B, int32_t H, int32_t W, int32_t nt, const double* gout,
+                                         const double* gstates, const uint64_t emit_mask[2], const double* a_row,
+                                         const double* b_col, double* gu, void* stream) {
+    if (!jac64_ok(B, H, W, nt) || !gout || !a_row || !b_col || !gu) return PDE_E_BADARG;
+    if (misaligned(8, gout, gstates, a_row, b_col, gu)) return PDE_E_BADARG;
+    EmitMask em;
+    int rc = emit_check(emit_mask, nt, gstates, em);
+    if (rc != PDE_OK) return rc;
+    static unsigned long long done_b = 0, done_e = 0;
+    rc = em.any() ? ensure_dynamic_lds((const void*)jac64_bwd_input_kernel<true>, (int)jac64_lds(kJacMax, kJacMax), done_e)
+                  : ensure_dynamic_lds((const void*)jac64_bwd_input_kernel<false>, (int)jac64_lds(kJacMax, kJacMax), done_b);
+    if (rc != PDE_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (em.any())
+        hipLaunchKernelGGL(jac64_bwd_input_kernel<true>, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, gout, a_row, b_col,
+                           gu, gstates, em);
+    else
+        hipLaunchKernelGGL(jac64_bwd_input_kernel<false>, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, gout, a_row, b_col,
+                           gu, (const double*)nullptr, em);
     return check_launch();
 }
 

@@ -20,6 +20,8 @@
 //           P_n on tile + 1 from the parked states (n = 0: from u) and adds G_{n+1} d1(P_n), G_{n+1} d2(P_n) over the
 //           tile's own cells into per-thread registers; at the end of the launch the registers are summed per row and
 //           per column in a fixed order into the tile's slot of `part`.  Launches chain through padded fp32 images.
+// adjoint for the input alone (jacobi_tiled_bwd_input_kernel): the adjoint above without P_n and without the sums —
+//           no parked state is read, so no forward launch precedes it; the same chain of padded images, the same fold.
 // fold      gu = interior of G_0 + the ring folded back onto rows / columns 1 and H-2 / W-2 (a pass of its own: the
 //           ring cell and the row it folds onto can lie in different tiles, e.g. H = 65).
 // pgrad     g_a_row / g_b_col = sum of the tiles' slots over samples and tiles, in a fixed order.  No float atomics.
@@ -274,6 +276,91 @@ __global__ __launch_bounds__(256) void jacobi_tiled_bwd_kernel(const IO* __restr
         float* pp = part + (size_t)tile * (2 * kJT) + threadIdx.x;
         *pp = acc ? *pp + sum : sum;                       // launches of one call follow each other on the stream
     }
+}
+
+// The adjoint part of jacobi_tiled_bwd_kernel alone (pde_jacobi_io_backward_input[_states]: a_row and b_col take no
+// gradient): no P_n staging, no per-thread row / column sums, no `part`.  G_{n_hi} on tile + k -> G_{n_hi-k} on the tile,
+// every update written as it is there, so the padded G_0 — and the gu folded from it — has the same bits.  LDS: G, Gn,
+// a, b, the forward's static size.
+template <typename IO, bool EMIT = false>
+__global__ __launch_bounds__(256) void jacobi_tiled_bwd_input_kernel(const IO* __restrict__ gout, const float* __restrict__ gsrc,
+                                                                     float* __restrict__ gdst, const float* __restrict__ a_row,
+                                                                     const float* __restrict__ b_col, size_t traj_stride,
+                                                                     int H, int W, int nTy, int nTx, int n_hi, int k,
+                                                                     const IO* __restrict__ gtraj, EmitMask em) {
+    __shared__ float sm[kJFwdFloats];
+    float* G = sm;
+    float* Gn = sm + kJR * kJS;
+    float* sa = sm + 2 * kJR * kJS;
+    float* sb = sa + kJR;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    int bid = blockIdx.x;
+    const int tX = bid % nTx;
+    bid /= nTx;
+    const int tY = bid % nTy;
+    const size_t s = bid / nTy;
+    const JSpan rs = jspan(tY, nTy, H, k), cs = jspan(tX, nTx, W, k);
+    const int Wp = W + 2;
+    const size_t plane = (size_t)H * W, pplane = (size_t)(H + 2) * Wp;
+    for (int e = threadIdx.x; e < rs.hi - rs.lo; e += 256) {
+        const int i = rs.lo + e;
+        sa[e] = (i >= 1 && i <= H) ? a_row[i - 1] : 0.f;
+    }
+    for (int e = threadIdx.x; e < cs.hi - cs.lo; e += 256) {
+        const int j = cs.lo + e;
+        sb[e] = (j >= 1 && j <= W) ? b_col[j - 1] : 0.f;
+    }
+    for (int i = rs.lo + ty; i < rs.hi; i += 8) {
+        const bool ri = i >= 1 && i <= H;
+        for (int j = cs.lo + tx; j < cs.hi; j += 32) {
+            float v;
+            if (gout) v = (ri && j >= 1 && j <= W) ? S1<IO>::ld(gout + s * plane + (size_t)(i - 1) * W + (j - 1)) : 0.f;
+            else v = gsrc[s * pplane + (size_t)i * Wp + j];
+            G[(i - rs.lo) * kJS + (j - cs.lo)] = v;
+        }
+    }
+    __syncthreads();
+    for (int st = 1; st <= k; ++st) {
+        const int n = n_hi - st;                           // this step takes G_{n+1} to G_n
+        // dL/dP_n from dL/dP_{n+1}; ring cells (clipped sides) are cells like any other here
+        const int r0 = rs.lo == 0 ? 0 : rs.lo + st, r1 = rs.hi == H + 2 ? H + 2 : rs.hi - st;
+        const int c0 = cs.lo == 0 ? 0 : cs.lo + st, c1 = cs.hi == W + 2 ? W + 2 : cs.hi - st;
+        const IO* gt = nullptr;                            // dL/d(state after step n), where that state was emitted
+        if constexpr (EMIT) {
+            const int slot = emit_slot(em, n);
+            if (slot >= 0) gt = gtraj + (size_t)slot * traj_stride + s * plane;
+        }
+        for (int i = r0 + ty; i < r1; i += 8) {
+            const bool ri = i >= 1 && i <= H;
+            const bool up = i - 1 >= 1 && i - 1 <= H, dn = i + 1 >= 1 && i + 1 <= H;   // vertical neighbour is interior
+            const float a0 = sa[i - rs.lo];
+            const float aup = up ? sa[i - 1 - rs.lo] : 0.f, adn = dn ? sa[i + 1 - rs.lo] : 0.f;
+            const float* grow = G + (i - rs.lo) * kJS - cs.lo;
+            float* qrow = Gn + (i - rs.lo) * kJS - cs.lo;
+            for (int j = c0 + tx; j < c1; j += 32) {
+                const bool cj = j >= 1 && j <= W;
+                const float* g = grow + j;
+                float v = (ri && cj) ? (1.f - 2.f * a0 - 2.f * sb[j - cs.lo]) * g[0] : g[0];
+                if (cj) {
+                    if (up) v += aup * g[-kJS];
+                    if (dn) v += adn * g[kJS];
+                }
+                if (ri) {
+                    if (j - 1 >= 1 && j - 1 <= W) v += sb[j - 1 - cs.lo] * g[-1];
+                    if (j + 1 >= 1 && j + 1 <= W) v += sb[j + 1 - cs.lo] * g[1];
+                }
+                if constexpr (EMIT) {
+                    if (gt && ri && cj) v += S1<IO>::ld(gt + (size_t)(i - 1) * W + (j - 1));
+                }
+                qrow[j] = v;
+            }
+        }
+        __syncthreads();
+        float* t = G; G = Gn; Gn = t;
+    }
+    float* gd = gdst + s * pplane;
+    for (int i = rs.olo + ty; i < rs.ohi; i += 8)
+        for (int j = cs.olo + tx; j < cs.ohi; j += 32) gd[(size_t)i * Wp + j] = G[(i - rs.lo) * kJS + (j - cs.lo)];
 }
 
 // gu from the padded G_0: the adjoint of the reflect padding

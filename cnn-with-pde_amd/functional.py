@@ -1777,7 +1777,9 @@ class _Explicit5Fn(torch.autograd.Function):
         u = _aligned(u, ctx.align)
         a, s = _kernel_param(alpha_base, kt), _kernel_param(channel_scaling, kt)
         res, out, traj = _out_and_traj(u, steps)
-        need_grad = any(ctx.needs_input_grad[:3])
+        # alpha_base and channel_scaling frozen: the backward is the adjoint walk alone and reads neither u nor a state
+        route = _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:3]))
+        need_grad = route == "full"
         fused = not f64 and (H, W) in ((64, 64), (32, 32), (16, 16))     # planes that stay in registers over all steps
         # inputs of steps 2..num_steps: what the backward reads (and what chains the steps for generic plane sizes): fp32
         # whatever the tensors' type, or doubles
@@ -1789,7 +1791,12 @@ class _Explicit5Fn(torch.autograd.Function):
                                                          relax, num_steps, _ptr(states), _ptr(out), _ptr(traj),
                                                          None if steps is None else _mask128(bits), _stream()),
                     fam + "forward_states")
-        ctx.save_for_backward(u, states if need_grad else None, a, s)
+        ctx.input_only = None
+        if route == "input_only":
+            ctx.input_only = (tuple(u.shape), u.dtype, u.device)
+            ctx.save_for_backward(a, s)
+        else:
+            ctx.save_for_backward(u, states if need_grad else None, a, s)
         ctx.cfg = (dt, eps, max_coeff, relax, num_steps, steps, bits, f64)
         ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
         return res
@@ -1797,9 +1804,24 @@ class _Explicit5Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         lib = L.load()
-        u, states, a, s = ctx.saved_tensors
         dt, eps, max_coeff, relax, num_steps, steps, bits, f64 = ctx.cfg
         fam = "pde_explicit5_f64_" if f64 else "pde_explicit5_"
+        if ctx.input_only is not None:
+            a, s = ctx.saved_tensors
+            shape, dtype, device = ctx.input_only
+            B, Cc, H, W = shape
+            gout, gtraj = _cotangents(g, dtype, steps, ctx.align)
+            gu = torch.empty(shape, dtype=dtype, device=device)
+            io = () if f64 else (_io_dtype(gu),)
+            n = getattr(lib, fam + "backward_input_workspace_bytes")(B, Cc, H, W, *io, num_steps)
+            ws = _workspace(n, device) if n else None
+            with torch.cuda.device(device):
+                L.check(getattr(lib, fam + "backward_input_states")(B, Cc, H, W, *io, _ptr(gout), _ptr(gtraj),
+                                                                    None if steps is None else _mask128(bits), _ptr(a),
+                                                                    _ptr(s), dt, eps, max_coeff, relax, num_steps, _ptr(gu),
+                                                                    _ptr(ws), n, _stream()), fam + "backward_input_states")
+            return (gu,) + (None,) * 10
+        u, states, a, s = ctx.saved_tensors
         B, Cc, H, W = u.shape
         gout, gtraj = _cotangents(g, u.dtype, steps, ctx.align)
         gu, ga, gs = torch.empty_like(u), torch.empty_like(a), torch.empty_like(s)
@@ -1849,7 +1871,13 @@ class _JacobiFn(torch.autograd.Function):
             L.check(getattr(lib, fam + "forward_states")(B, H, W, nt, *io, _ptr(u), _ptr(a), _ptr(b), _ptr(out), _ptr(traj),
                                                          None if steps is None else _mask128(bits), *fws, _stream()),
                     fam + "forward_states")
-        ctx.save_for_backward(u, a, b)
+        # a_row and b_col frozen: the backward is the adjoint walk alone and reads no u
+        ctx.input_only = None
+        if _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:3])) == "input_only":
+            ctx.input_only = (tuple(u.shape), u.dtype, u.device)
+            ctx.save_for_backward(a, b)
+        else:
+            ctx.save_for_backward(u, a, b)
         ctx.cfg = (nt, steps, bits, f64)
         ctx.p_dtypes = (a_row.dtype, b_col.dtype)
         return res
@@ -1857,9 +1885,28 @@ class _JacobiFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         lib = L.load()
-        u, a, b = ctx.saved_tensors
         nt, steps, bits, f64 = ctx.cfg
         fam = "pde_jacobi_f64_" if f64 else "pde_jacobi_io_"
+        if ctx.input_only is not None:
+            a, b = ctx.saved_tensors
+            shape, dtype, device = ctx.input_only
+            B, H, W = shape
+            gout, gtraj = _cotangents(g, dtype, steps, ctx.align)
+            gu = torch.empty(shape, dtype=dtype, device=device)
+            with torch.cuda.device(device):
+                if f64:
+                    io, bws = (), ()
+                else:
+                    io = (_io_dtype(gu),)
+                    n = lib.pde_jacobi_io_backward_input_workspace_bytes(B, H, W, nt, *io)
+                    ws = _workspace(n, device) if n else None
+                    bws = (_ptr(ws), n)
+                L.check(getattr(lib, fam + "backward_input_states")(B, H, W, nt, *io, _ptr(gout), _ptr(gtraj),
+                                                                    None if steps is None else _mask128(bits), _ptr(a),
+                                                                    _ptr(b), _ptr(gu), *bws, _stream()),
+                        fam + "backward_input_states")
+            return gu, None, None, None, None, None, None
+        u, a, b = ctx.saved_tensors
         B, H, W = u.shape
         gout, gtraj = _cotangents(g, u.dtype, steps, ctx.align)
         gu, ga, gb = torch.empty_like(u), torch.empty_like(a), torch.empty_like(b)
