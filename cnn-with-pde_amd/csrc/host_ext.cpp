@@ -14,6 +14,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_runtime_api.h>
+#include <torch/csrc/autograd/functions/basic_ops.h>
 
 #include <atomic>
 #include <chrono>
@@ -385,6 +386,45 @@ std::vector<int64_t> states_shape(int64_t K, const Tensor& u) {
     return sh;
 }
 
+// ---- second order (functional.linear_adjoint): every node below is linear in its input, so its backward output is
+// gu = F(theta)^T g and, for a cotangent v on gu, <v, F^T g> = <F v, g>: the gradient with respect to g is the node's own
+// apply at v, the gradient with respect to theta the parameter gradient of that call with cotangent g.  A backward that runs
+// in grad mode (create_graph=True) goes through AdjointFn (behind the nodes) and otherwise runs as it always has.  For that
+// a node keeps its original parameter tensors — inputs, no copy — next to what it keeps anyway.
+constexpr int64_t kAdi = 0, kSmall = 1, kMixed = 2, kMulti = 3;
+variable_list second_order(int64_t kind, AutogradContext* outer, const variable_list& grads);
+void save_orig(AutogradContext* ctx, std::initializer_list<const Tensor*> params) {
+    std::vector<Tensor> v;
+    for (const Tensor* t : params)
+        if (t->defined()) v.push_back(*t);
+    ctx->saved_data["orig"] = v;
+}
+
+// The nodes that are NOT linear in their input (the symmetric layers) are differentiable once: what
+// torch.autograd.function.once_differentiable does for their ctypes twins — in grad mode, with a cotangent that requires
+// grad, the results carry a node that raises when it is differentiated, instead of passing for constants.
+variable_list once_differentiable(const variable_list& grads, variable_list outs) {
+    bool twice = false;
+    if (at::GradMode::is_enabled())
+        for (const auto& g : grads) twice = twice || (g.defined() && g.requires_grad());
+    if (!twice) return outs;
+    variable_list in;
+    std::vector<size_t> pos;
+    for (size_t i = 0; i < outs.size(); ++i)
+        if (outs[i].defined()) {
+            Tensor t = outs[i].detach();
+            t.set_requires_grad(true);
+            in.push_back(t);
+            pos.push_back(i);
+        }
+    auto err = std::make_shared<torch::autograd::DelayedError>(
+        "trying to differentiate twice a function that is differentiable once (the symmetric layer is not linear in its "
+        "input: second order is not supported)", (int64_t)in.size());
+    variable_list res = (*err)(std::move(in));
+    for (size_t k = 0; k < pos.size(); ++k) outs[pos[k]] = res[k];
+    return outs;
+}
+
 struct AdiFn : public torch::autograd::Function<AdiFn> {
     // ckpt_mode: 0 = explicit mask (ckpt_lo/hi), 1 = "auto" (planned in the backward from this call's coefficients),
     // 2 = explicit mask, and this call's coefficient maxima go to a slot the CALLER owns (slot_out: where to leave it) —
@@ -419,6 +459,7 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
         ctx->saved_data["ws"] = ws;                          // the factorisation, reused by the backward
         km.save(ctx);
         save_desc(ctx, &d);
+        save_orig(ctx, {&ab, &bb, &asl, &bsl});
         return y;
     }
 
@@ -439,6 +480,11 @@ struct AdiFn : public torch::autograd::Function<AdiFn> {
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (at::GradMode::is_enabled()) return second_order(kAdi, ctx, grads);   // create_graph=True
+        return backward_now(ctx, grads);
+    }
+
+    static variable_list backward_now(AutogradContext* ctx, variable_list& grads) {
         if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &y = saved[0], &u = saved[1];
@@ -539,6 +585,7 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
         ctx->saved_data["sws"] = sws;
         save_desc(ctx, &d);
         ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode};
+        save_orig(ctx, {&ab, &bb, &asl, &bsl, &M, &skip});
         return y;
     }
 
@@ -560,6 +607,11 @@ struct SmallFn : public torch::autograd::Function<SmallFn> {
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (at::GradMode::is_enabled()) return second_order(kSmall, ctx, grads);   // create_graph=True
+        return backward_now(ctx, grads);
+    }
+
+    static variable_list backward_now(AutogradContext* ctx, variable_list& grads) {
         if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &u = saved[0], &Mf = saved[1], &sw = saved[2];
@@ -629,6 +681,7 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
             ctx->saved_data["sws"] = sws;
             save_desc(ctx, &d);
             ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode, (int64_t)M.scalar_type()};
+            save_orig(ctx, {&ab, &bb, &asl, &bsl, &M});
             return y;
         }
         Kmax km(need_grad && ckpt_mode == 1, d.num_sweeps, u);
@@ -648,6 +701,7 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
         save_plan(ctx, ckpt_mode, ckpt_lo, 0, amax);
         save_shapes(ctx, {&ab, &bb, &asl, &bsl});
         ctx->saved_data["cfg"] = std::vector<int64_t>{sps, mode, (int64_t)M.scalar_type()};
+        save_orig(ctx, {&ab, &bb, &asl, &bsl, &M});
         return y;
     }
 
@@ -670,6 +724,11 @@ struct MixedFn : public torch::autograd::Function<MixedFn> {
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (at::GradMode::is_enabled()) return second_order(kMixed, ctx, grads);   // create_graph=True
+        return backward_now(ctx, grads);
+    }
+
+    static variable_list backward_now(AutogradContext* ctx, variable_list& grads) {
         if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         const Tensor &u = saved[0], &states = saved[1], &Mf = saved[2];
@@ -800,6 +859,11 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
             ctx->saved_data["hold"] = hold;                   // per layer [kdev with coefficient maxima,] the steps workspace
             save_desc(ctx, descs.data(), nl);
             ctx->saved_data["cfg"] = std::vector<int64_t>{nl, sps, want_sums ? 1 : 0, ckpt_mode, weights.defined() ? 1 : 0};
+            {
+                std::vector<Tensor> orig(flat.begin(), flat.end());             // the five tensors per layer, then the weights
+                if (weights.defined()) orig.push_back(weights);
+                ctx->saved_data["orig"] = orig;
+            }
             if (input_only) {
                 save_input_only(ctx, u);
                 ctx->saved_data["ushape"] = u.sizes().vec();
@@ -852,6 +916,11 @@ struct MultiFn : public torch::autograd::Function<MultiFn> {
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grads) {
+        if (at::GradMode::is_enabled()) return second_order(kMulti, ctx, grads);   // create_graph=True
+        return backward_now(ctx, grads);
+    }
+
+    static variable_list backward_now(AutogradContext* ctx, variable_list& grads) {
         if (is_input_only(ctx)) return backward_input(ctx, grads);
         auto saved = ctx->get_saved_variables();
         auto cfg = ctx->saved_data["cfg"].toIntVector();
@@ -928,6 +997,152 @@ variable_list multi(const Tensor& u, const std::optional<Tensor>& weights, std::
                           grad_mode_of(u, params));
 }
 
+// ---- the adjoint of a node that is linear in its input, differentiable once more (functional._LinearAdjointFn) -----------
+// forward: the node's own backward body, unchanged (backward_now), as a function of the cotangents and of the original
+// parameter tensors.  backward: for the cotangent v of gu, the node's own apply at v — through its public wrapper, with the
+// original parameters, the node's descriptor(s) and its checkpoint plan — whose outputs are the cotangents' gradients, and
+// torch::autograd::grad of them for the parameters'.  The parameter gradients of the first backward are handed through and
+// are NOT differentiable: a cotangent on one raises (NotImplementedError in Python).  It keeps copies of what it needs of
+// the outer node, which may be gone by the time it runs.
+struct AdjointFn : public torch::autograd::Function<AdjointFn> {
+    struct Layout {                       // where the defined results of the body sit among the node's forward arguments
+        size_t n = 0;
+        std::vector<size_t> pos;
+    };
+
+    // cots: the cotangents that came, cot_at: their places among the node's outputs, then the number of those outputs (a
+    // shared-input group may get a cotangent on some of its outputs only, and an undefined tensor is no argument of apply)
+    static variable_list forward(AutogradContext* ctx, at::TensorList cots, at::TensorList params, std::vector<int64_t> cot_at,
+                                 int64_t kind, int64_t outer, int64_t layout_out, std::string descs, std::vector<int64_t> cfg,
+                                 double amax) {
+        ctx->set_materialize_grads(false);
+        AutogradContext* node = reinterpret_cast<AutogradContext*>(outer);
+        variable_list g((size_t)cot_at.back());
+        for (size_t k = 0; k < cots.size(); ++k) g[(size_t)cot_at[k]] = cots[k];
+        variable_list all = kind == kAdi     ? AdiFn::backward_now(node, g)
+                            : kind == kSmall ? SmallFn::backward_now(node, g)
+                            : kind == kMixed ? MixedFn::backward_now(node, g)
+                                             : MultiFn::backward_now(node, g);
+        Layout* lay = reinterpret_cast<Layout*>(layout_out);
+        lay->n = all.size();
+        variable_list res;
+        for (size_t i = 0; i < all.size(); ++i)
+            if (all[i].defined()) {
+                res.push_back(all[i]);
+                lay->pos.push_back(i);
+            }
+        variable_list save(cots.begin(), cots.end());
+        save.insert(save.end(), params.begin(), params.end());
+        ctx->save_for_backward(save);
+        ctx->saved_data["kind"] = kind;
+        ctx->saved_data["cot_at"] = cot_at;
+        ctx->saved_data["n"] = std::vector<int64_t>{(int64_t)cots.size(), (int64_t)params.size()};
+        ctx->saved_data["desc"] = descs;
+        ctx->saved_data["cfg"] = cfg;
+        ctx->saved_data["amax"] = amax;
+        return res;
+    }
+
+    // the node's own apply at v: one output per cotangent of its backward
+    static variable_list primal(int64_t kind, const Tensor& v, const Tensor* p, size_t np, const std::string& descs,
+                                const std::vector<int64_t>& cfg, double amax);
+
+    static variable_list backward(AutogradContext* ctx, variable_list gouts) {
+        for (size_t i = 1; i < gouts.size(); ++i)
+            TORCH_CHECK_NOT_IMPLEMENTED(!gouts[i].defined(),
+                "the parameter gradients of a PDE layer's first backward are not differentiable: they are nonlinear in the "
+                "parameters, and their derivative with respect to the input or the cotangent is a coefficient tangent the "
+                "library has no kernel for (differentiate the input gradient instead, or detach them)");
+        auto saved = ctx->get_saved_variables();
+        auto n = ctx->saved_data["n"].toIntVector();
+        const size_t n_cot = (size_t)n[0], n_par = (size_t)n[1];
+        variable_list res(n_cot + n_par + 7);                 // the cotangents, the parameters, seven non-tensor arguments
+        if (!gouts[0].defined()) return res;
+        auto cot_at = ctx->saved_data["cot_at"].toIntVector();
+        const Tensor* cots = saved.data();
+        const Tensor* params = saved.data() + n_cot;
+        variable_list need;
+        std::vector<size_t> need_at;
+        for (size_t i = 0; i < n_par; ++i)
+            if (params[i].defined() && params[i].requires_grad()) {
+                need.push_back(params[i]);
+                need_at.push_back(i);
+            }
+        const bool create = at::GradMode::is_enabled();
+        at::AutoGradMode mode(create || !need.empty());
+        variable_list outs = primal(ctx->saved_data["kind"].toInt(), gouts[0], params, n_par, ctx->saved_data["desc"].toStringRef(),
+                                    ctx->saved_data["cfg"].toIntVector(), ctx->saved_data["amax"].toDouble());
+        if (!need.empty()) {
+            variable_list o, c;
+            for (size_t k = 0; k < n_cot; ++k)
+                if (outs[(size_t)cot_at[k]].requires_grad()) {
+                    o.push_back(outs[(size_t)cot_at[k]]);
+                    c.push_back(cots[k]);
+                }
+            if (!o.empty()) {
+                variable_list gp = torch::autograd::grad(o, need, c, /*retain_graph=*/create, /*create_graph=*/create,
+                                                         /*allow_unused=*/true);
+                for (size_t k = 0; k < need_at.size(); ++k) res[n_cot + need_at[k]] = gp[k];
+            }
+        }
+        for (size_t k = 0; k < n_cot; ++k) res[k] = create ? outs[(size_t)cot_at[k]] : outs[(size_t)cot_at[k]].detach();
+        return res;
+    }
+};
+
+variable_list AdjointFn::primal(int64_t kind, const Tensor& v, const Tensor* p, size_t np, const std::string& descs,
+                                const std::vector<int64_t>& cfg, double amax) {
+    // cfg: {ckpt_mode, ckpt_lo, ckpt_hi, sweeps_per_step, mode | want_sums, has_weights, layers, their masks ...}; a lagged
+    // call's explicit mask stays explicit, its coefficient maxima go to nobody
+    const int64_t ckpt_mode = cfg[0] == 2 ? 0 : cfg[0];
+    std::vector<PdeAdiDesc> d(descs.size() / sizeof(PdeAdiDesc));
+    std::memcpy(d.data(), descs.data(), d.size() * sizeof(PdeAdiDesc));
+    const int64_t d0 = (int64_t) reinterpret_cast<intptr_t>(d.data());
+    if (kind == kAdi) return {adi(v, p[0], p[1], p[2], p[3], d0, ckpt_mode, cfg[1], cfg[2], amax)};
+    if (kind == kSmall)
+        return {small(v, p[0], p[1], p[2], p[3], p[4], np > 5 ? std::optional<Tensor>(p[5]) : std::nullopt, d0, cfg[3], cfg[4],
+                      ckpt_mode, cfg[1], amax)};
+    if (kind == kMixed) return {mixed(v, p[0], p[1], p[2], p[3], p[4], d0, cfg[3], cfg[4], ckpt_mode, cfg[1], amax)};
+    const size_t nl = (size_t)cfg[6];
+    std::vector<Tensor> flat(p, p + 5 * nl);
+    std::vector<int64_t> addrs, masks(cfg.begin() + 7, cfg.end());
+    for (size_t i = 0; i < nl; ++i) addrs.push_back((int64_t) reinterpret_cast<intptr_t>(&d[i]));
+    return multi(v, cfg[5] ? std::optional<Tensor>(p[5 * nl]) : std::nullopt, flat, addrs, cfg[3], cfg[4] != 0, ckpt_mode, masks,
+                 amax);
+}
+
+variable_list second_order(int64_t kind, AutogradContext* outer, const variable_list& grads) {
+    auto& sd = outer->saved_data;
+    std::vector<Tensor> params = sd["orig"].toTensorVector();
+    std::vector<int64_t> cfg{0, 0, 0};
+    if (sd.count("ckpt")) cfg = sd["ckpt"].toIntVector();
+    if (kind == kSmall || kind == kMixed) {
+        auto c = sd["cfg"].toIntVector();
+        cfg.push_back(c[0]);
+        cfg.push_back(c[1]);
+    } else if (kind == kMulti) {
+        auto c = sd["cfg"].toIntVector();                     // {layers, sweeps per step, plane sums, ckpt_mode, weights}
+        cfg = {c[3], 0, 0, c[1], c[2], c[4], c[0]};
+        std::vector<int64_t> masks = sd.count("masks") ? sd["masks"].toIntVector() : std::vector<int64_t>();
+        masks.resize(c[3] == 1 ? 0 : (size_t)c[0], 0);
+        cfg.insert(cfg.end(), masks.begin(), masks.end());
+    }
+    AdjointFn::Layout lay;
+    variable_list cots;
+    std::vector<int64_t> cot_at;
+    for (size_t i = 0; i < grads.size(); ++i)
+        if (grads[i].defined()) {
+            cots.push_back(grads[i]);
+            cot_at.push_back((int64_t)i);
+        }
+    cot_at.push_back((int64_t)grads.size());
+    variable_list got = AdjointFn::apply(at::TensorList(cots), at::TensorList(params), cot_at, kind,
+                                         (int64_t) reinterpret_cast<intptr_t>(outer), (int64_t) reinterpret_cast<intptr_t>(&lay),
+                                         sd["desc"].toStringRef(), cfg, sd.count("amax") ? sd["amax"].toDouble() : 0.0);
+    variable_list res(lay.n);
+    for (size_t k = 0; k < lay.pos.size(); ++k) res[lay.pos[k]] = got[k];
+    return res;
+}
 
 
 // ---- the Ruthotto-Haber symmetric layer (functional._SymLayerFn: cifar_2version.py:190-258) ----------------------------
@@ -1001,7 +1216,8 @@ struct SymFn : public torch::autograd::Function<SymFn> {
                                      gX.data_ptr<float>(), gK.data_ptr<float>(), gg.data_ptr<float>(), gb.data_ptr<float>(),
                                      ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? (size_t)ws.numel() : 0, (void*)st),
               "pde_sym_layer_backward");
-        return {gX, gK, gg, gb, cfg[2] ? g : Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        return once_differentiable(grads, {gX, gK, gg, gb, cfg[2] ? g : Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+                                           Tensor(), Tensor(), Tensor(), Tensor()});
     }
 };
 
@@ -1120,8 +1336,8 @@ struct Sym16Node : public torch::autograd::Function<Fn> {
                             gK.data_ptr<float>(), gg.data_ptr<float>(), gb.data_ptr<float>(), ws.data_ptr(),
                             (size_t)ws.numel(), (void*)st),
               Api::backward_name);
-        return {gX, gK, Tensor(), gg, gb, cfg[2] ? g : Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-                Tensor(), Tensor()};
+        return once_differentiable(grads, {gX, gK, Tensor(), gg, gb, cfg[2] ? g : Tensor(), Tensor(), Tensor(), Tensor(),
+                                           Tensor(), Tensor(), Tensor(), Tensor(), Tensor()});
     }
 };
 struct SymF16Fn : public Sym16Node<SymF16Fn, F16Api> {};

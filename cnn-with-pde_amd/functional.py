@@ -6,6 +6,7 @@ memory, streams and autograd bookkeeping.  Nothing here has a CPU or eager fallb
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 import time
@@ -14,11 +15,12 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
 __all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small", "adi_diffuse_small_states", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse", "explicit5_states", "jacobi_diffuse_states",
-           "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
+           "linear_adjoint", "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
            "sym_layer_f16_supported", "sym_layer_bf16_supported", "sym_k16"]
 
 
@@ -493,6 +495,72 @@ class _KmaxConcat:
         return [v for p in self.parts for v in p.wait()]
 
 
+# ---- second order: the adjoint of a layer that is linear in its input --------------------------------------------------
+# Every PDE layer family is linear in its input, so a node's backward output is gu = F(theta)^T g, and for a
+# cotangent v on gu  <v, F^T g> = <F v, g>:  the gradient with respect to g is F v — the layer's FORWARD at input v — and the
+# gradient with respect to theta is the parameter gradient of the layer's full backward at input v with cotangent g.  Both
+# are calls the library makes anyway, so differentiating twice needs no kernel of its own: a node whose ``backward`` runs in
+# grad mode (``create_graph=True``) wraps its usual backward body in ``linear_adjoint`` below, and otherwise runs it bare.
+_NO_PARAM_TANGENT = ("the parameter gradients of a PDE layer's first backward are not differentiable: they are nonlinear in "
+                     "the parameters, and their derivative with respect to the input or the cotangent is a coefficient "
+                     "tangent the library has no kernel for (differentiate the input gradient instead, or detach them)")
+
+
+class _LinearAdjointFn(torch.autograd.Function):
+    """``body(*cots)`` — a node's existing backward, run unchanged — as a differentiable function of the cotangents and of
+    the original parameter tensors.  The first ``n_diff`` results are the gradients the layer is linear through (``gu``);
+    every other result is a parameter gradient, handed through and NOT differentiable: a cotangent on one raises.
+    ``primal(*vs)`` is the same layer call at input ``vs`` (one per differentiable result, None where no cotangent came)
+    with the original parameters and the call's own configuration; it returns one output per cotangent of ``body``."""
+
+    @staticmethod
+    def forward(ctx, body, primal, n_cot, n_diff, *tensors):
+        ctx.set_materialize_grads(False)
+        ctx.primal, ctx.n_cot, ctx.n_diff = primal, n_cot, n_diff
+        ctx.save_for_backward(*tensors)                       # the cotangents, then the parameters: inputs, no copy
+        return body(*tensors[:n_cot])
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        n_cot, n_diff = ctx.n_cot, ctx.n_diff
+        if any(g is not None for g in gouts[n_diff:]):
+            raise NotImplementedError(_NO_PARAM_TANGENT)
+        vs = gouts[:n_diff]
+        saved = ctx.saved_tensors
+        none = (None,) * (4 + len(saved))
+        if all(v is None for v in vs):
+            return none
+        cots, params = saved[:n_cot], saved[n_cot:]
+        need = [i for i, n in enumerate(ctx.needs_input_grad[4 + n_cot:]) if n and params[i] is not None]
+        create = torch.is_grad_enabled()
+        with torch.enable_grad() if need else contextlib.nullcontext():
+            outs = ctx.primal(*vs)
+            if not isinstance(outs, (tuple, list)):
+                outs = (outs,)
+            pairs = [(o, c) for o, c in zip(outs, cots) if c is not None and o is not None and o.requires_grad]
+            gp = [None] * len(params)
+            if need and pairs:
+                gs = torch.autograd.grad([o for o, _ in pairs], [params[i] for i in need], [c for _, c in pairs],
+                                         allow_unused=True, create_graph=create)
+                for i, g in zip(need, gs):
+                    gp[i] = g
+        gc = [None if c is None or o is None else (o if create else o.detach()) for o, c in zip(outs, cots)]
+        return (None, None, None, None, *gc, *gp)
+
+
+def linear_adjoint(body, primal, cots, params, n_diff=1):
+    """The results of ``body(*cots)``, differentiable once more (see ``_LinearAdjointFn``).  ``cots``: the cotangents the
+    node's backward received (None where none came); ``params``: the original parameter tensors of the call (None allowed)."""
+    return _LinearAdjointFn.apply(body, primal, len(cots), n_diff, *cots, *params)
+
+
+def _second_order(cls, ctx, cots, n_diff=1):
+    """A node's backward in grad mode: ``cls._backward`` under the core, the primal call ``cls.apply`` at the new input with
+    the arguments the forward left in ``ctx.primal_args`` — (parameter tensors, non-tensor configuration)."""
+    params, cfg = ctx.primal_args
+    return linear_adjoint(lambda *g: cls._backward(ctx, *g), lambda v: cls.apply(v, *params, *cfg), cots, params, n_diff)
+
+
 # ---- what the implicit-layer nodes below share: each decision is taken in one place (csrc/host_ext.cpp cuts its nodes the
 # same way, and the two mirrors stay bitwise alike: tests/test_gpu_node_calls.py) --------------------------------------
 def _grad_route(need_u, need_params) -> str:
@@ -650,10 +718,17 @@ class _AdiFn(torch.autograd.Function):
             ctx.save_for_backward(out, u if (route == "full" and ckpt != 0) else None, *p)
         ctx.cfg = (d, fam, ckpt, ebits)
         ctx.param_meta = _param_meta(ab, bb, asl, bsl)
+        ctx.primal_args = ((ab, bb, asl, bsl), (sweeps, smooth3, clamp_max, eps, ckpt, None, emit, rect, f64))
         return out
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _second_order(_AdiFn, ctx, (g,))
+        return _AdiFn._backward(ctx, g)
+
+    @staticmethod
+    def _backward(ctx, g):
         lib = L.load()
         if ctx.input_only is not None:
             return _AdiFn._backward_input(ctx, g)
@@ -722,6 +797,7 @@ class _AdiMixedFn(torch.autograd.Function):
         route = _grad_route(ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:6]))
         m = 1 if mode == "pre" else 2
         ctx.input_only = None
+        ctx.primal_args = ((ab, bb, asl, bsl, M), (steps, mode, smooth3, clamp_max, eps, ckpt, None))
         if route != "full" and L.bwd_input_enabled():
             y = torch.empty_like(u)
             ws = _workspace(lib.pde_adi_mixed_forward_input_workspace_bytes(C.byref(d), sps), u.device)
@@ -755,6 +831,12 @@ class _AdiMixedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _second_order(_AdiMixedFn, ctx, (gy,))
+        return _AdiMixedFn._backward(ctx, gy)
+
+    @staticmethod
+    def _backward(ctx, gy):
         lib = L.load()
         if ctx.input_only is not None:
             (Mf,) = ctx.saved_tensors
@@ -836,6 +918,7 @@ class _AdiSmallFn(torch.autograd.Function):
         ctx.param_meta = _param_meta(ab, bb, asl, bsl)
         ctx.M_dtype = M.dtype
         ctx.skip_meta = None if skip_weight is None else (skip_weight.shape, skip_weight.dtype)
+        ctx.primal_args = ((ab, bb, asl, bsl, M, skip_weight), (steps, mode, smooth3, clamp_max, eps, ckpt, None, emit))
         return out
 
     @staticmethod
@@ -857,6 +940,12 @@ class _AdiSmallFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _second_order(_AdiSmallFn, ctx, (g,))
+        return _AdiSmallFn._backward(ctx, g)
+
+    @staticmethod
+    def _backward(ctx, g):
         lib = L.load()
         if ctx.input_only is not None:
             return _AdiSmallFn._backward_input(ctx, g)
@@ -950,6 +1039,7 @@ class _AdiMultiFn(torch.autograd.Function):
         ctx.layers = layers
         ctx.has_w = weights is not None
         ctx.want_sums = want_sums
+        ctx.primal_args = ((weights, *flat), (specs, want_sums, ckpt))
         return (out, *ys, *sums) if want_sums else (out, *ys)
 
     @staticmethod
@@ -977,6 +1067,14 @@ class _AdiMultiFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout, *gall):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            params, cfg = ctx.primal_args
+            return linear_adjoint(lambda *g: _AdiMultiFn._backward(ctx, *g),
+                                  lambda v: _AdiMultiFn.apply(v, params[0], *cfg, *params[1:]), (gout, *gall), params)
+        return _AdiMultiFn._backward(ctx, gout, *gall)
+
+    @staticmethod
+    def _backward(ctx, gout, *gall):
         lib = L.load()
         nl = len(ctx.layers)
         gys, gsums = gall[:nl], (gall[nl:] if ctx.want_sums else (None,) * nl)
@@ -1311,6 +1409,7 @@ class _MixFn(torch.autograd.Function):
         _require_cuda(u, M)
         B, Cc = u.shape[0], u.shape[1]
         HW = u[0, 0].numel()
+        u_in = u
         if u.dtype not in _IO_TYPES:
             u = u.float()
         u = _aligned(u.contiguous())
@@ -1326,10 +1425,17 @@ class _MixFn(torch.autograd.Function):
             ctx.save_for_backward(Mf)
         else:
             ctx.save_for_backward(u, Mf)
+        ctx.primal_args = (u_in if ctx.input_only is None else None, M)
         return out
 
     @staticmethod
     def backward(ctx, gout):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _mix_second_order(_MixFn, ctx, gout)
+        return _MixFn._backward(ctx, gout)
+
+    @staticmethod
+    def _backward(ctx, gout):
         lib = L.load()
         if ctx.input_only is not None:
             (Mf,) = ctx.saved_tensors
@@ -1355,6 +1461,20 @@ class _MixFn(torch.autograd.Function):
         return gu, gM
 
 
+def _mix_second_order(cls, ctx, gout):
+    """``y = M u`` is bilinear, so both results of its backward are differentiable:
+    <v, M^T g> + <W, g u^T> = <channel_mix(v, M) + channel_mix(u, W), g>."""
+    u, M = ctx.primal_args
+
+    def primal(v, W):
+        out = None if v is None else cls.apply(v, M)
+        if W is not None:
+            t = cls.apply(u, W)
+            out = t if out is None else out + t
+        return out
+    return linear_adjoint(lambda g: cls._backward(ctx, g), primal, (gout,), (u, M), n_diff=2)
+
+
 def channel_mix(u, M):
     """out[b,i,p] = sum_j M[i,j] u[b,j,p] — cifar10.py:65-72 and SVHN.py:78-86."""
     if u.shape[0] == 0:
@@ -1365,6 +1485,9 @@ def channel_mix(u, M):
 
 
 # --------------------------------------------------------------------------- BatchNorm2d + 4x4 avg/max pooling
+# The nodes that are NOT linear in their input (this one, the symmetric layers, the gate combination) are differentiable
+# once: their backwards are marked ``once_differentiable``, so differentiating through them twice raises instead of
+# treating the first gradient as a constant.
 class _BnPoolFn(torch.autograd.Function):
     """cifar10.py:346-353 in two passes over the activation (pde_tail.hip): statistics, then normalise + pool."""
 
@@ -1391,6 +1514,7 @@ class _BnPoolFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gout):
         lib = L.load()
         xf, gm, mean, invstd, amax = ctx.saved_tensors
@@ -1482,6 +1606,7 @@ class _SymLayerFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gout):
         lib = L.load()
         Xf, Kf, gm, P, H, mean, invstd = ctx.saved_tensors
@@ -1639,6 +1764,7 @@ class _SymLayerF16Fn(torch.autograd.Function):
                               momentum, eps, scale, act)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gout):
         return _sym16_backward(ctx, "f16", gout)
 
@@ -1653,6 +1779,7 @@ class _SymLayerBf16Fn(torch.autograd.Function):
                               momentum, eps, scale, act)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gout):
         return _sym16_backward(ctx, "bf16", gout)
 
@@ -1729,6 +1856,7 @@ class _GateCombineFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         lib = L.load()
         nl = ctx.nl
@@ -1799,10 +1927,17 @@ class _Explicit5Fn(torch.autograd.Function):
             ctx.save_for_backward(u, states if need_grad else None, a, s)
         ctx.cfg = (dt, eps, max_coeff, relax, num_steps, steps, bits, f64)
         ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
+        ctx.primal_args = ((alpha_base, channel_scaling), ctx.cfg)
         return res
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _second_order(_Explicit5Fn, ctx, (g,))
+        return _Explicit5Fn._backward(ctx, g)
+
+    @staticmethod
+    def _backward(ctx, g):
         lib = L.load()
         dt, eps, max_coeff, relax, num_steps, steps, bits, f64 = ctx.cfg
         fam = "pde_explicit5_f64_" if f64 else "pde_explicit5_"
@@ -1880,10 +2015,17 @@ class _JacobiFn(torch.autograd.Function):
             ctx.save_for_backward(u, a, b)
         ctx.cfg = (nt, steps, bits, f64)
         ctx.p_dtypes = (a_row.dtype, b_col.dtype)
+        ctx.primal_args = ((a_row, b_col), ctx.cfg)
         return res
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _second_order(_JacobiFn, ctx, (g,))
+        return _JacobiFn._backward(ctx, g)
+
+    @staticmethod
+    def _backward(ctx, g):
         lib = L.load()
         nt, steps, bits, f64 = ctx.cfg
         fam = "pde_jacobi_f64_" if f64 else "pde_jacobi_io_"
@@ -2025,10 +2167,17 @@ class _SkipBlendFn(torch.autograd.Function):
         else:
             ctx.save_for_backward(a, b, w)
         ctx.in_dtypes = (u0.dtype, u.dtype, skip_weight.dtype, skip_weight.shape)
+        ctx.primal_args = skip_weight
         return out
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _blend_second_order(_SkipBlendFn, ctx, g)
+        return _SkipBlendFn._backward(ctx, g)
+
+    @staticmethod
+    def _backward(ctx, g):
         lib = L.load()
         if ctx.input_only is not None:
             (w,) = ctx.saved_tensors
@@ -2049,6 +2198,16 @@ class _SkipBlendFn(torch.autograd.Function):
                                                 _ptr(g_w), _ptr(ws), ws.numel(), _stream()), "pde_skip_blend_backward")
         d0, d1, dw, shw = ctx.in_dtypes
         return g_a.to(d0), g_b.to(d1), g_w.to(dw).reshape(shw)
+
+
+def _blend_second_order(cls, ctx, g):
+    """The blend is linear in (u0, u): <v0, s g> + <v1, (1 - s) g> = <skip_blend(v0, v1, w), g>.  Its ``skip_weight``
+    gradient is a parameter gradient like any other: not differentiable."""
+    w = ctx.primal_args
+
+    def primal(v0, v1):
+        return cls.apply(torch.zeros_like(v1) if v0 is None else v0, torch.zeros_like(v0) if v1 is None else v1, w)
+    return linear_adjoint(lambda c: cls._backward(ctx, c), primal, (g,), (w,), n_diff=2)
 
 
 def skip_blend(u0, u, skip_weight):
@@ -2092,6 +2251,7 @@ class _MixF64Fn(torch.autograd.Function):
         _require_cuda(u, M)
         B, Cc = u.shape[0], u.shape[1]
         HW = u[0, 0].numel()
+        u_in = u
         u = u.to(torch.float64).contiguous()
         Md = _d64(M)
         out = torch.empty_like(u)
@@ -2105,10 +2265,17 @@ class _MixF64Fn(torch.autograd.Function):
         else:
             ctx.save_for_backward(u, Md)
         ctx.m_dtype = M.dtype
+        ctx.primal_args = (u_in if ctx.input_only is None else None, M)
         return out
 
     @staticmethod
     def backward(ctx, gout):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _mix_second_order(_MixF64Fn, ctx, gout)
+        return _MixF64Fn._backward(ctx, gout)
+
+    @staticmethod
+    def _backward(ctx, gout):
         lib = L.load()
         if ctx.input_only is not None:
             (Md,) = ctx.saved_tensors
@@ -2151,10 +2318,17 @@ class _SkipBlendF64Fn(torch.autograd.Function):
         else:
             ctx.save_for_backward(a, b, w)
         ctx.in_meta = (u0.dtype, u.dtype, skip_weight.dtype, skip_weight.shape)
+        ctx.primal_args = skip_weight
         return out
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():                      # create_graph=True: differentiable once more
+            return _blend_second_order(_SkipBlendF64Fn, ctx, g)
+        return _SkipBlendF64Fn._backward(ctx, g)
+
+    @staticmethod
+    def _backward(ctx, g):
         lib = L.load()
         if ctx.input_only:
             (w,) = ctx.saved_tensors

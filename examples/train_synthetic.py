@@ -7,6 +7,7 @@ with the diffusion layer taken from this package and data parallelism over RCCL:
 
     python examples/train_synthetic.py --variant mnist --steps 200        # single GPU, fp32: the step is ONE hipGraph
     python examples/train_synthetic.py --variant mnist --steps 200 --eager  # the same, one eager autograd step at a time
+    python examples/train_synthetic.py --variant svhn_model --eager --input-grad-penalty 0.01   # + LAMBDA |d loss / d x|^2
     python examples/train_synthetic.py --variant cifar10_noconv --amp          # cifar10.py:318-361 under fp16 autocast
     python examples/train_synthetic.py --variant cifar10_noconv --amp bf16     # the same under bf16 autocast, no GradScaler
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -18,6 +19,11 @@ Variants: ``mnist`` / ``cifar10`` are small stand-ins; ``mnist_model``, ``fashio
 tiny_imagenet.py:237-305, emotion_recognition.py:170-195).  ``--amp`` (or ``--amp fp16``) runs the step under fp16
 autocast with a GradScaler, as cifar10.py:440,458-467 does; ``--amp bf16`` under bf16 autocast, which has fp32's range
 and needs no loss scaling.
+
+``--input-grad-penalty LAMBDA`` adds ``LAMBDA * |d loss / d x|^2`` (mean over the batch) to the loss of the eager fp32 loop:
+the input gradient is taken with ``create_graph=True`` and differentiated again, through the PDE layer too (every PDE layer
+is linear in its input, so its second-order pass is its own forward and backward at another input).  The mnist, fashion,
+svhn, tiny and emotion models support it; ``cifar10_noconv`` (attention gates, BatchNorm pooling) raises.
 
 There is no dataset on the box: every rank draws its shard of a fixed synthetic classification task
 (one smooth random template per class plus noise), so the loss has something to learn and the run is
@@ -157,6 +163,8 @@ def main():
                          "single-GPU fp32 run (the reference's own shapes are bound by the host's launch path when run "
                          "eagerly: 1.8-2.4x fewer samples per second)")
     ap.add_argument("--eager", action="store_true", help="one eager autograd step per iteration (always with --amp or several ranks)")
+    ap.add_argument("--input-grad-penalty", type=float, default=0.0, metavar="LAMBDA",
+                    help="add LAMBDA * |d loss / d x|^2 to the loss (double backward through the PDE layer); eager fp32 loop only")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -188,6 +196,9 @@ def main():
 
     if a.graph and (world > 1 or a.amp):
         raise SystemExit("--graph: single GPU, fp32")
+    if a.input_grad_penalty and (a.graph or a.amp or not (a.eager or world > 1)):
+        raise SystemExit("--input-grad-penalty: the eager fp32 loop only (add --eager): a replayed graph holds one fixed "
+                         "backward, and the penalty's second backward is not part of it")
     if a.graph or not (a.eager or world > 1 or a.amp):
         return train_graphed(a, model, templates, classes, crit, gen, dev)
 
@@ -200,9 +211,14 @@ def main():
         labels = torch.randint(0, classes, (a.batch,), generator=gen, device=dev)
         x = templates[labels] + 1.0 * torch.randn(a.batch, *templates.shape[1:], generator=gen, device=dev)
         opt.zero_grad(set_to_none=True)
+        if a.input_grad_penalty:
+            x.requires_grad_(True)
         with torch.autocast("cuda", dtype=torch.bfloat16 if a.amp == "bf16" else torch.float16, enabled=a.amp is not None):
             out = model(x)
             loss = crit(out, labels)
+        if a.input_grad_penalty:
+            (gx,) = torch.autograd.grad(loss, x, create_graph=True)
+            loss = loss + a.input_grad_penalty * gx.pow(2).sum() * a.batch      # (the loss is a batch mean: gx carries 1/batch)
         scaler.scale(loss).backward()
         if bucket is not None:
             bucket.allreduce(average=True)               # ONE collective per step (of the scaled gradients)
