@@ -321,6 +321,19 @@ SIGNATURES_EXPLICIT_INPUT = {
     "pde_jacobi_f64_backward_input_states": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _M, _vp, _vp, _vp, _vp]),
 }
 
+#: include/pdecnn_tangent.h (included by pdecnn.h): the tangent-linear pass of the four ADI families — u, du, the four
+#: parameters, their four tangents, y, dy, workspace
+SIGNATURES_TANGENT = {
+    "pde_adi_tangent_workspace_bytes": (_sz, [_D]),
+    "pde_adi_tangent": (C.c_int, [_D, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_f64_tangent_workspace_bytes": (_sz, [_D64]),
+    "pde_adi_f64_tangent": (C.c_int, [_D64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_tangent_workspace_bytes": (_sz, [_DR]),
+    "pde_adi_rect_tangent": (C.c_int, [_DR, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_adi_rect_f64_tangent_workspace_bytes": (_sz, [_DR64]),
+    "pde_adi_rect_f64_tangent": (C.c_int, [_DR64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -335,7 +348,8 @@ def load():
             "(or `make -C cnn-with-pde_amd/csrc`). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_SMALL_INPUT.items()) +
-                              list(SIGNATURES_MIXED_INPUT.items()) + list(SIGNATURES_EXPLICIT_INPUT.items())):
+                              list(SIGNATURES_MIXED_INPUT.items()) + list(SIGNATURES_EXPLICIT_INPUT.items()) +
+                              list(SIGNATURES_TANGENT.items())):
         fn = getattr(lib, name)         # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     _lib = lib

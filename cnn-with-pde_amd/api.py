@@ -1,12 +1,12 @@
 """Public surface of cnn_with_pde_amd."""
 from . import _lib
 from ._lib import PdeError, LIB_PATH
-from .functional import (Sweep, adi_schedule, adi_diffuse, adi_diffuse_states, adi_diffuse_mixed, adi_diffuse_small, adi_diffuse_small_states, adi_diffuse_multi, gate_combine, bn_pool,
+from .functional import (Sweep, adi_schedule, adi_diffuse, adi_diffuse_states, adi_diffuse_tangent, adi_diffuse_mixed, adi_diffuse_small, adi_diffuse_small_states, adi_diffuse_multi, gate_combine, bn_pool,
                          plan_checkpoints, channel_mix, explicit5_step, jacobi_diffuse, explicit5_states, jacobi_diffuse_states,
                          timing_enable, timing_read)
 from .dist import shard_range, shard_batch, GradBucket
 from .layers import (MnistDiffusionLayer, FashionDiffusionLayer, SvhnDiffusionLayer, EnhancedDiffusionLayer,
-                     LearnableDiffusionLayer, ImprovedDiffusionLayer, PDELayer, layer_trajectory)
+                     LearnableDiffusionLayer, ImprovedDiffusionLayer, PDELayer, layer_trajectory, layer_jvp)
 from . import models
 from . import graphs
 from .graphs import freeze_checkpoint_plans, make_graphed, GraphedStep
@@ -47,9 +47,9 @@ def library_version() -> str:
     return _lib.load().pde_version().decode()
 
 
-__all__ = ["graphs", "freeze_checkpoint_plans", "make_graphed", "GraphedStep", "PdeError", "LIB_PATH", "Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small",
+__all__ = ["graphs", "freeze_checkpoint_plans", "make_graphed", "GraphedStep", "PdeError", "LIB_PATH", "Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_tangent", "adi_diffuse_mixed", "adi_diffuse_small",
            "adi_diffuse_multi", "gate_combine", "bn_pool", "plan_checkpoints", "channel_mix", "explicit5_step",
-           "jacobi_diffuse", "explicit5_states", "jacobi_diffuse_states", "layer_trajectory", "timing_enable", "timing_read", "MnistDiffusionLayer", "FashionDiffusionLayer",
+           "jacobi_diffuse", "explicit5_states", "jacobi_diffuse_states", "layer_trajectory", "layer_jvp", "timing_enable", "timing_read", "MnistDiffusionLayer", "FashionDiffusionLayer",
            "SvhnDiffusionLayer", "EnhancedDiffusionLayer", "LearnableDiffusionLayer", "ImprovedDiffusionLayer",
            "PDELayer", "models", "MnistPDEClassifier", "FashionPDEClassifier", "SvhnPDEClassifier", "SpatialAttention",
            "MultiScaleExtractor", "EnhancedFC", "CIFAR10PDENoConv", "SymmetricLayer", "ParabolicBlock", "HamiltonianBlock",

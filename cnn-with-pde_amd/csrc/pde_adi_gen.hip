@@ -500,6 +500,168 @@ __global__ void gen_reduce_kernel(const T* part, int G, int C, int H, int W, T* 
     g_ab[e] = s[0]; g_as[e] = s[1]; g_bb[e] = s[2]; g_bs[e] = s[3];
 }
 
+// ---- the tangent-linear pass (include/pdecnn_tangent.h) ---------------------------------------------------------------
+// d(coeff) of every sweep from the four parameter tangents: dco = (delta/h2) * smooth3(pass . (dbase + dslope t)) with the
+// clamp mask gen_factor_kernel stored (fac's fourth array) and its 3-tap association.  Grid and thread mapping are that
+// kernel's: one workgroup per (sweep, channel), one thread per line.  A null tangent is zero.
+template <typename T, typename SW>
+struct GenFactorTangentArgs {
+    const T *dab, *dbb, *das, *dbs;          // each nullptr | [C][H*W]
+    const T* fac;                            // the factorisation of the same call (the pass mask is read)
+    T* dco;                                  // [S][C][H*W], laid out [k][line] like fac's arrays
+    int C, H, W, S, smooth3;
+    SW sweep[PDE_MAX_SWEEPS];
+};
+
+template <typename T, typename SW>
+__global__ void gen_factor_tangent_kernel(GenFactorTangentArgs<T, SW> a) {
+    const int s = blockIdx.x / a.C, c = blockIdx.x % a.C, ln = threadIdx.x;
+    const SW sw = a.sweep[s];
+    const int ax = sw.axis;
+    const int N = (ax == PDE_AXIS_X) ? a.W : a.H, L = (ax == PDE_AXIS_X) ? a.H : a.W;   // unknowns per line, lines
+    if (ln >= L) return;
+    const size_t HW = (size_t)a.H * a.W;
+    const T* db = (ax == PDE_AXIS_X) ? a.dab : a.dbb;
+    const T* ds = (ax == PDE_AXIS_X) ? a.das : a.dbs;
+    if (db) db += (size_t)c * HW;
+    if (ds) ds += (size_t)c * HW;
+    const int lstride = (ax == PDE_AXIS_X) ? a.W : 1, kstride = (ax == PDE_AXIS_X) ? 1 : a.W;
+    const T* pass = a.fac + (((size_t)s * a.C + c) * kGenArr + 3) * HW + ln;             // [k][line = ln]
+    T* out = a.dco + ((size_t)s * a.C + c) * HW + ln;
+    auto p = [&](int k) {
+        const int i = ln * lstride + k * kstride;
+        const T r = (db ? db[i] : T(0)) + (ds ? ds[i] : T(0)) * sw.t;
+        return pass[(size_t)k * L] != T(0) ? r : T(0);
+    };
+    const T third = T(1) / T(3);
+    for (int k = 0; k < N; ++k) {
+        T v = p(k);
+        if (a.smooth3) v = (p(k > 0 ? k - 1 : 0) * third + v * third) + p(k + 1 < N ? k + 1 : N - 1) * third;
+        out[(size_t)k * L] = v * sw.delta / sw.h2;
+    }
+}
+
+template <typename T>
+struct GenTangentArgs {
+    const void *u, *du;                      // du nullptr: a zero input tangent
+    void *y, *dy;                            // y nullptr: not written
+    const T* fac;
+    const T* dco;                            // read only when has_param
+    const GenSweep<T>* tab;
+    T* xg;                                   // XG: [G*C][H][W+1], the primal plane of each workgroup
+    int B, C, H, W, S, G, has_param;
+};
+
+// the two recurrences of one line, operation for operation those of gen_fwd_kernel (v: the line, st: its stride)
+template <typename TT>
+__device__ __forceinline__ void gen_tan_solve(TT* v, int st, const TT* __restrict__ f, size_t plane, int L, int N) {
+    TT prev = v[0] * f[2 * plane];
+    v[0] = prev;
+    for (int k0 = 1; k0 < N; k0 += kGenBatch) {
+        TT t[kGenBatch], co[kGenBatch], iv[kGenBatch];
+#pragma unroll
+        for (int j = 0; j < kGenBatch; ++j) {
+            const int k = k0 + j < N ? k0 + j : N - 1;
+            t[j] = v[k * st];
+            co[j] = f[(size_t)k * L];
+            iv[j] = f[2 * plane + (size_t)k * L];
+        }
+#pragma unroll
+        for (int j = 0; j < kGenBatch; ++j)
+            if (k0 + j < N) { prev = (t[j] + co[j] * prev) * iv[j]; t[j] = prev; }
+#pragma unroll
+        for (int j = 0; j < kGenBatch; ++j)
+            if (k0 + j < N) v[(k0 + j) * st] = t[j];
+    }
+    for (int k0 = N - 2; k0 >= 0; k0 -= kGenBatch) {
+        TT t[kGenBatch], cs[kGenBatch];
+#pragma unroll
+        for (int j = 0; j < kGenBatch; ++j) {
+            const int k = k0 - j >= 0 ? k0 - j : 0;
+            t[j] = v[k * st];
+            cs[j] = f[plane + (size_t)k * L];
+        }
+#pragma unroll
+        for (int j = 0; j < kGenBatch; ++j)
+            if (k0 - j >= 0) { prev = t[j] - cs[j] * prev; t[j] = prev; }
+#pragma unroll
+        for (int j = 0; j < kGenBatch; ++j)
+            if (k0 - j >= 0) v[(k0 - j) * st] = t[j];
+    }
+}
+
+// tangent-linear pass: workgroup (g, c) walks the planes b = g, g+G, ... of channel c (G = B unless XG: one plane per
+// workgroup, blockIdx = b*C + c as in gen_fwd_kernel); the primal plane X and the tangent plane D side by side in LDS, both
+// [row < H][W+1].  Per sweep a thread owns line tid of BOTH planes: it solves the primal line, adds dco_k (x_{k-1} - m_k x_k
+// + x_{k+1}) of the SOLVED line to the tangent line (m = 1 at the two ends, 2 inside, a missing neighbour dropped; skipped
+// when no parameter carries a tangent), then solves the tangent line with the same rows.  Nothing crosses threads inside a
+// sweep, so the barriers are gen_fwd_kernel's: one after every sweep.
+// XG (two planes beyond the LDS limit, as gen_bwd_kernel): X lives in a global scratch slice the workgroup owns.
+template <typename TT, typename IO, bool XG>
+__global__ void gen_tangent_kernel(GenTangentArgs<TT> a) {
+    extern __shared__ float gen_tsmem[];
+    const int H = a.H, W = a.W, ld = W + 1, tid = threadIdx.x, T = blockDim.x, NN = H * W;
+    TT* D = reinterpret_cast<TT*>(gen_tsmem);
+    TT* X = XG ? a.xg + (size_t)blockIdx.x * H * ld : D + (size_t)H * ld;
+    const size_t plane = (size_t)NN;
+    const int c = blockIdx.x % a.C, g = blockIdx.x / a.C;
+    for (int b = g; b < a.B; b += a.G) {
+        const size_t pb = ((size_t)b * a.C + c) * plane;
+        if (b != g) __syncthreads();         // the stores of the previous plane read other threads' lines
+        for (int e = tid; e < NN; e += T) {
+            X[(e / W) * ld + (e % W)] = GenIo<IO>::ld(a.u, pb + e);
+            D[(e / W) * ld + (e % W)] = a.du ? TT(GenIo<IO>::ld(a.du, pb + e)) : TT(0);
+        }
+        __syncthreads();
+        for (int s = 0; s < a.S; ++s) {
+            const GenSweep<TT> sw = a.tab[s];
+            const bool xs = sw.axis == PDE_AXIS_X;
+            const int N = xs ? W : H, L = xs ? H : W;                            // unknowns per line, lines
+            if (tid < L) {
+                const TT* __restrict__ f = a.fac + ((size_t)s * a.C + c) * kGenArr * plane + tid;   // [arr][k][line = tid]
+                TT* x = X + (xs ? tid * ld : tid);
+                TT* dl = D + (xs ? tid * ld : tid);
+                const int st = xs ? 1 : ld;
+                gen_tan_solve<TT>(x, st, f, plane, L, N);
+                if (a.has_param) {
+                    const TT* __restrict__ dc = a.dco + ((size_t)s * a.C + c) * plane + tid;        // [k][line = tid]
+                    TT xm = TT(0), xc = x[0];                                    // x_{k-1}, x_k
+                    for (int k0 = 0; k0 < N; k0 += kGenBatch) {
+                        TT xn[kGenBatch], co[kGenBatch], dv[kGenBatch];
+#pragma unroll
+                        for (int j = 0; j < kGenBatch; ++j) {
+                            const int k = k0 + j < N ? k0 + j : N - 1;
+                            xn[j] = (k0 + j + 1 < N) ? x[(k0 + j + 1) * st] : TT(0);                // x_{k+1}
+                            co[j] = dc[(size_t)k * L];
+                            dv[j] = dl[k * st];
+                        }
+#pragma unroll
+                        for (int j = 0; j < kGenBatch; ++j) {
+                            const int k = k0 + j;
+                            if (k < N) {
+                                const TT xp = xn[j];
+                                const TT lap = (xm + xp) - ((k == 0 || k == N - 1) ? xc : TT(2) * xc);
+                                dv[j] += co[j] * lap;
+                                xm = xc;
+                                xc = xp;
+                            }
+                        }
+#pragma unroll
+                        for (int j = 0; j < kGenBatch; ++j)
+                            if (k0 + j < N) dl[(k0 + j) * st] = dv[j];
+                    }
+                }
+                gen_tan_solve<TT>(dl, st, f, plane, L, N);
+            }
+            __syncthreads();                 // the next sweep (or the stores below) reads lines other threads wrote
+        }
+        for (int e = tid; e < NN; e += T) {
+            if (a.y) GenIo<IO>::st(a.y, pb + e, X[(e / W) * ld + (e % W)]);
+            GenIo<IO>::st(a.dy, pb + e, D[(e / W) * ld + (e % W)]);
+        }
+    }
+}
+
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 // rows and columns of a descriptor's plane: the square descriptors have one N, the rectangle ones H and W
 template <typename D> int rows_of(const D* d) { return d->N; }
@@ -734,6 +896,60 @@ int backward_input_impl(const D* d, const void* gy, void* gu, const T* ab, const
     return check_launch();
 }
 
+// the tangent-linear pass: workspace = factorisation | schedule | dco | (XG) one primal plane per workgroup
+template <typename T, typename D>
+size_t dco_bytes(const D* d) { return up256((size_t)d->num_sweeps * d->C * plane_of(d) * sizeof(T)); }
+template <typename T, typename D>
+int tan_groups(const D* d) { return bwd_xg<T>(d) ? bwd_groups<T>(d) : d->B; }
+template <typename T, typename D>
+size_t tan_ws_bytes(const D* d) {
+    return fwd_ws_bytes<T>(d) + dco_bytes<T>(d) +
+           (bwd_xg<T>(d) ? up256((size_t)tan_groups<T>(d) * d->C * gen_img<T>(d)) : 0);
+}
+
+// factorisation, d(coeff) when a parameter carries a tangent, then one launch for all sweeps
+template <typename T, typename D>
+int tangent_impl(const D* d, const void* u, const void* du, const T* ab, const T* bb, const T* as, const T* bs, const T* dab,
+                 const T* dbb, const T* das, const T* dbs, void* y, void* dy, void* workspace, hipStream_t st) {
+    using SW = typename std::remove_cv<typename std::remove_reference<decltype(d->sweep[0])>::type>::type;
+    char* ws = static_cast<char*>(workspace);
+    T* fac = reinterpret_cast<T*>(ws);
+    GenSweep<T>* tab = reinterpret_cast<GenSweep<T>*>(ws + fac_bytes<T>(d));
+    T* dco = reinterpret_cast<T*>(ws + fwd_ws_bytes<T>(d));
+    const bool xg = bwd_xg<T>(d);
+    T* xplanes = xg ? reinterpret_cast<T*>(ws + fwd_ws_bytes<T>(d) + dco_bytes<T>(d)) : nullptr;
+    const int has_param = (dab || dbb || das || dbs) ? 1 : 0;
+    int rc = launch_gen_factor<T>(d, ab, bb, as, bs, fac, tab, (T*)nullptr, st);
+    if (rc != PDE_OK) return rc;
+    if (has_param) {
+        GenFactorTangentArgs<T, SW> fa;
+        fa.dab = dab; fa.dbb = dbb; fa.das = das; fa.dbs = dbs; fa.fac = fac; fa.dco = dco;
+        fa.C = d->C; fa.H = rows_of(d); fa.W = cols_of(d); fa.S = d->num_sweeps; fa.smooth3 = d->smooth3;
+        for (int s = 0; s < d->num_sweeps; ++s) fa.sweep[s] = d->sweep[s];
+        hipLaunchKernelGGL((gen_factor_tangent_kernel<T, SW>), dim3(d->num_sweeps * d->C), dim3(gen_threads(d)), 0, st, fa);
+        if ((rc = check_launch()) != PDE_OK) return rc;
+    }
+    const int G = tan_groups<T>(d);
+    GenTangentArgs<T> ta{};
+    ta.u = u; ta.du = du; ta.y = y; ta.dy = dy; ta.fac = fac; ta.dco = dco; ta.tab = tab; ta.xg = xplanes;
+    ta.B = d->B; ta.C = d->C; ta.H = rows_of(d); ta.W = cols_of(d); ta.S = d->num_sweeps; ta.G = G; ta.has_param = has_param;
+    const size_t lds = (xg ? 1 : 2) * gen_img<T>(d);
+    const dim3 grid(G * d->C), block(gen_threads(d));
+    static unsigned long long done[5] = {0, 0, 0, 0, 0};
+#define PDE_GEN_TANGENT(TY, IO, XG, SLOT)                                                          \
+    do {                                                                                           \
+        if ((rc = gen_lds(gen_tangent_kernel<TY, IO, XG>, done[SLOT])) != PDE_OK) return rc;       \
+        hipLaunchKernelGGL((gen_tangent_kernel<TY, IO, XG>), grid, block, lds, st, ta);            \
+    } while (0)
+    if constexpr (std::is_same<T, double>::value) {
+        if (xg) PDE_GEN_TANGENT(double, double, true, 0); else PDE_GEN_TANGENT(double, double, false, 1);
+    } else if (d->io_dtype == PDE_IO_F32) PDE_GEN_TANGENT(float, float, false, 2);
+    else if (d->io_dtype == PDE_IO_F16) PDE_GEN_TANGENT(float, gen_f16, false, 3);
+    else PDE_GEN_TANGENT(float, gen_bf16, false, 4);
+#undef PDE_GEN_TANGENT
+    return check_launch();
+}
+
 }  // namespace
 
 bool gen_n_ok(int N) { return N >= 2 && N <= PDE_MAX_N_GENERIC; }
@@ -913,9 +1129,82 @@ int any_backward_input(const D* d, CHECK&& check, const void* gy, const void* gs
                                   gstates, emit);
 }
 
+// fp32-family squares on the any-size kernels: every N in 2 .. PDE_MAX_N_GENERIC (checks and codes of pde_adi_forward)
+int check_desc_sq(const PdeAdiDesc* d) {
+    if (!d) return PDE_E_BADARG;
+    if (d->B <= 0 || d->C <= 0 || d->num_sweeps <= 0) return PDE_E_BADARG;
+    if (!gen_n_ok(d->N)) return PDE_E_UNSUPPORTED_N;
+    if (d->num_sweeps > PDE_MAX_SWEEPS) return PDE_E_TOO_MANY_SWEEPS;
+    if (d->io_dtype != PDE_IO_F32 && d->io_dtype != PDE_IO_BF16 && d->io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    for (int s = 0; s < d->num_sweeps; ++s)
+        if (d->sweep[s].axis != PDE_AXIS_X && d->sweep[s].axis != PDE_AXIS_Y) return PDE_E_BADARG;
+    return PDE_OK;
+}
+
+// the tangent-linear pass of all four families (CHECK: the family's descriptor check)
+template <typename T, typename D, typename CHECK>
+size_t any_tangent_bytes(const D* d, CHECK&& check) { return check(d) != PDE_OK ? 0 : tan_ws_bytes<T>(d); }
+
+template <typename T, typename D, typename CHECK>
+int any_tangent(const D* d, CHECK&& check, const void* u, const void* du, const T* ab, const T* bb, const T* as, const T* bs,
+                const T* dab, const T* dbb, const T* das, const T* dbs, void* y, void* dy, void* workspace,
+                size_t workspace_bytes, void* stream) {
+    const int rc = check(d);
+    if (rc != PDE_OK) return rc;
+    if (!u || !dy || !ab || !bb || !as || !bs || !workspace) return PDE_E_BADARG;
+    if (!du && !dab && !dbb && !das && !dbs) return PDE_E_BADARG;
+    if (misaligned(io_elem_bytes(d->io_dtype), u, du, y, dy) || misaligned(sizeof(T), ab, bb, as, bs, dab, dbb, das, dbs))
+        return PDE_E_BADARG;
+    if (workspace_bytes < tan_ws_bytes<T>(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    return tangent_impl<T>(d, u, du, ab, bb, as, bs, dab, dbb, das, dbs, y, dy, workspace, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- the tangent-linear pass (include/pdecnn_tangent.h): (y, dy) from (u, du) and the four parameter tangents ----------
+size_t pde_adi_tangent_workspace_bytes(const PdeAdiDesc* d) { return any_tangent_bytes<float>(d, check_desc_sq); }
+int pde_adi_tangent(const PdeAdiDesc* d, const void* u, const void* du, const float* alpha_base, const float* beta_base,
+                    const float* alpha_slope, const float* beta_slope, const float* d_alpha_base, const float* d_beta_base,
+                    const float* d_alpha_slope, const float* d_beta_slope, void* y, void* dy, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    return any_tangent<float>(d, check_desc_sq, u, du, alpha_base, beta_base, alpha_slope, beta_slope, d_alpha_base,
+                              d_beta_base, d_alpha_slope, d_beta_slope, y, dy, workspace, workspace_bytes, stream);
+}
+size_t pde_adi_f64_tangent_workspace_bytes(const PdeAdiDescF64* d) { return any_tangent_bytes<double>(d, check_desc_f64); }
+int pde_adi_f64_tangent(const PdeAdiDescF64* d, const double* u, const double* du, const double* alpha_base,
+                        const double* beta_base, const double* alpha_slope, const double* beta_slope,
+                        const double* d_alpha_base, const double* d_beta_base, const double* d_alpha_slope,
+                        const double* d_beta_slope, double* y, double* dy, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    return any_tangent<double>(d, check_desc_f64, u, du, alpha_base, beta_base, alpha_slope, beta_slope, d_alpha_base,
+                               d_beta_base, d_alpha_slope, d_beta_slope, y, dy, workspace, workspace_bytes, stream);
+}
+size_t pde_adi_rect_tangent_workspace_bytes(const PdeAdiRectDesc* d) {
+    return any_tangent_bytes<float>(d, check_desc_rect<float, PdeAdiRectDesc>);
+}
+int pde_adi_rect_tangent(const PdeAdiRectDesc* d, const void* u, const void* du, const float* alpha_base,
+                         const float* beta_base, const float* alpha_slope, const float* beta_slope,
+                         const float* d_alpha_base, const float* d_beta_base, const float* d_alpha_slope,
+                         const float* d_beta_slope, void* y, void* dy, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    return any_tangent<float>(d, check_desc_rect<float, PdeAdiRectDesc>, u, du, alpha_base, beta_base, alpha_slope,
+                              beta_slope, d_alpha_base, d_beta_base, d_alpha_slope, d_beta_slope, y, dy, workspace,
+                              workspace_bytes, stream);
+}
+size_t pde_adi_rect_f64_tangent_workspace_bytes(const PdeAdiRectDescF64* d) {
+    return any_tangent_bytes<double>(d, check_desc_rect<double, PdeAdiRectDescF64>);
+}
+int pde_adi_rect_f64_tangent(const PdeAdiRectDescF64* d, const double* u, const double* du, const double* alpha_base,
+                             const double* beta_base, const double* alpha_slope, const double* beta_slope,
+                             const double* d_alpha_base, const double* d_beta_base, const double* d_alpha_slope,
+                             const double* d_beta_slope, double* y, double* dy, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    return any_tangent<double>(d, check_desc_rect<double, PdeAdiRectDescF64>, u, du, alpha_base, beta_base, alpha_slope,
+                               beta_slope, d_alpha_base, d_beta_base, d_alpha_slope, d_beta_slope, y, dy, workspace,
+                               workspace_bytes, stream);
+}
 
 // ---- the backward of a layer whose coefficients take no gradient (gu = F^T gy): float64 squares and rectangles ----
 size_t pde_adi_f64_backward_input_workspace_bytes(const PdeAdiDescF64* d) {

@@ -15,6 +15,7 @@ from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import torch
+import torch.autograd.forward_ad as _fwad
 from torch.autograd.function import once_differentiable
 
 from . import _lib as L
@@ -506,6 +507,43 @@ _NO_PARAM_TANGENT = ("the parameter gradients of a PDE layer's first backward ar
                      "tangent the library has no kernel for (differentiate the input gradient instead, or detach them)")
 
 
+# ---- forward mode (torch.autograd.forward_ad) -------------------------------------------------------------------------
+# A node's ``jvp`` needs tensors its backward may not keep (the frozen route keeps neither y nor u), and the C++ nodes of
+# csrc/host_ext.cpp cannot carry one.  So the public functions ask ``_has_tangent`` — one module attribute read outside a
+# dual level — and only then go through ``_apply_dual``, which tells the ctypes node's forward to keep what its jvp reads.
+_NO_TRAJ_JVP = ("forward-mode AD through a trajectory call (adi_diffuse_states) is not implemented: the tangent kernel "
+                "emits no intermediate states; differentiate the plain call, or chain one call per emitted state")
+_NO_JVP_ROUTE = ("this node was not called through the library's public functions under forward_ad.dual_level(): it kept "
+                 "nothing for a jvp")
+_dual = threading.local()
+
+
+def _has_tangent(*ts) -> bool:
+    """True inside a ``forward_ad.dual_level()`` when one of the tensors carries a tangent."""
+    if _fwad._current_level < 0:
+        return False
+    return any(isinstance(t, torch.Tensor) and _fwad.unpack_dual(t).tangent is not None for t in ts)
+
+
+def _apply_dual(cls, *args):
+    """``cls.apply`` with the mark that its forward takes (``_take_dual``): keep what the jvp needs."""
+    _dual.on = True
+    try:
+        return cls.apply(*args)
+    finally:
+        _dual.on = False
+
+
+def _take_dual(ctx) -> bool:
+    """Read and clear the mark of ``_apply_dual`` (the calls a jvp makes itself are plain ones).  With the mark, absent
+    tangents arrive as None instead of zeros."""
+    on = getattr(_dual, "on", False)
+    if on:
+        _dual.on = False
+        ctx.set_materialize_grads(False)
+    return on
+
+
 class _LinearAdjointFn(torch.autograd.Function):
     """``body(*cots)`` — a node's existing backward, run unchanged — as a differentiable function of the cotangents and of
     the original parameter tensors.  The first ``n_diff`` results are the gradients the layer is linear through (``gu``);
@@ -719,7 +757,32 @@ class _AdiFn(torch.autograd.Function):
         ctx.cfg = (d, fam, ckpt, ebits)
         ctx.param_meta = _param_meta(ab, bb, asl, bsl)
         ctx.primal_args = ((ab, bb, asl, bsl), (sweeps, smooth3, clamp_max, eps, ckpt, None, emit, rect, f64))
+        ctx.dual = None
+        if _take_dual(ctx):                              # a tangent came in (adi_diffuse decided): what the jvp reads
+            ctx.save_for_forward(u, *p)
+            ctx.dual = (tuple(t.detach() for t in (ab, bb, asl, bsl)), (sweeps, smooth3, clamp_max, eps), as_chw, f64)
         return out
+
+    @staticmethod
+    def jvp(ctx, ut, dab, dbb, das, dbs, *_):
+        """Forward mode.  The layer is linear in ``u``: with no parameter tangent the output tangent is the layer's own
+        forward at ``ut`` (``adi_diffuse``, the fused kernels at N <= 32).  Otherwise one ``*_tangent`` call."""
+        d, fam, _, ebits = ctx.cfg
+        if ebits is not None:
+            raise NotImplementedError(_NO_TRAJ_JVP)
+        if ctx.dual is None:
+            raise NotImplementedError(_NO_JVP_ROUTE)
+        params, cfg, as_chw, f64 = ctx.dual
+        u, *p = ctx.saved_tensors
+        dts = (dab, dbb, das, dbs)
+        if all(t is None for t in dts):
+            if ut is None:
+                return torch.zeros_like(u)
+            return adi_diffuse(ut.to(u.dtype), *params, *cfg).to(u.dtype)
+        Cc, H, W = u.shape[1:]
+        dp = [None if t is None else as_chw(t, Cc, H, W, 1) for t in dts]
+        du = None if ut is None else _kernel_input(ut.to(u.dtype), f64, align=1)
+        return _tangent_call(L.load(), fam, d, u, du, p, dp, False)[1]
 
     @staticmethod
     def backward(ctx, g):
@@ -1196,8 +1259,10 @@ def adi_diffuse_small(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
     if mode not in ("pre", "post"):
         raise ValueError(mode)
     steps = _as_schedule(steps)
-    if _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, skip_weight):
-        # float64: no one-launch kernels; the layer out of its pieces (adi_diffuse_mixed composes it per step)
+    every = (u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, skip_weight)
+    if _is_f64(*every) or (_fwad._current_level >= 0 and _has_tangent(*every)):
+        # float64: no one-launch kernels; the layer out of its pieces (adi_diffuse_mixed composes it per step).  Forward
+        # mode (a tangent on an argument inside a dual level) too: the one-launch node has no jvp, the pieces have one
         y = adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode, smooth3=smooth3,
                               clamp_max=clamp_max, eps=eps, checkpoints=checkpoints)
         return y if skip_weight is None else skip_blend(u, y, skip_weight)
@@ -1234,8 +1299,10 @@ def adi_diffuse_mixed(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coef
         u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
     if _is_rect(u):
         _check_rect(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)   # before the first operator launch
-    if u.dim() == 4 and u.is_cuda and (_is_rect(u) or L.load().pde_adi_line_length_path(int(u.shape[-1])) == 2 or
+    dual = _fwad._current_level >= 0 and _has_tangent(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)
+    if u.dim() == 4 and u.is_cuda and (dual or _is_rect(u) or L.load().pde_adi_line_length_path(int(u.shape[-1])) == 2 or
                                        _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M)):
+        # forward mode (a tangent on an argument inside a dual level: the per-step nodes carry the jvp), or
         # a rectangle (H != W: no per-step entry points either), or
         # a line length without fused kernels (pde_adi_line_length_path: any size up to PDE_MAX_N_GENERIC): the per-step
         # entry points do not exist there; compose the layer from its own pieces — the channel operator and the sweeps of
@@ -1315,6 +1382,10 @@ def adi_diffuse(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, swe
     f64 = _is_f64(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
     if not f64:
         u = _io_in(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+    if _fwad._current_level >= 0 and _has_tangent(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff):
+        # forward mode: the ctypes node carries the jvp (the C++ nodes cannot), and is told to keep what it reads
+        return _apply_dual(_AdiFn, u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff,
+                           sweeps, bool(smooth3), clamp_max, float(eps), checkpoints, kmax_sink, None, rect, f64)
     if not (rect or f64) and (isinstance(checkpoints, int) or (kmax_sink is None and checkpoints == "auto")):
         H = L.host_ext()
         if H is not None and u.dim() == 4 and u.is_cuda and u.dtype in _IO_TYPES:
@@ -1368,6 +1439,58 @@ def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coe
         raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
     return _AdiFn.apply(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps, bool(smooth3), clamp_max,
                         float(eps), checkpoints, kmax_sink, emit, _is_rect(u), f64)
+
+
+def _tangent_call(lib, fam, d, u, du, p, dp, want_y):
+    """One ``*_tangent`` call of family ``fam`` (include/pdecnn_tangent.h) on kernel-ready tensors: (y or None, dy)."""
+    y = torch.empty_like(u) if want_y else None
+    dy = torch.empty_like(u)
+    ws = _workspace(getattr(lib, fam + "tangent_workspace_bytes")(C.byref(d)), u.device)
+    with torch.cuda.device(u.device):
+        L.check(getattr(lib, fam + "tangent")(C.byref(d), _ptr(u), _ptr(du), *[_ptr(t) for t in p], *[_ptr(t) for t in dp],
+                                              _ptr(y), _ptr(dy), _ptr(ws), ws.numel(), _stream()), fam + "tangent")
+    return y, dy
+
+
+def adi_diffuse_tangent(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, sweeps: Sequence[Sweep], *, du=None,
+                        d_alpha_base=None, d_beta_base=None, d_alpha_time_coeff=None, d_beta_time_coeff=None,
+                        smooth3: bool = False, clamp_max: Optional[float] = None, eps: float = 1e-6):
+    """``(y, ydot)``: ``adi_diffuse`` and its directional derivative along the input tangent ``du`` and the four parameter
+    tangents (None: zero; at least one must be given), in one pass of the tangent-linear kernel (pde_adi*_tangent).  Plain
+    tensors, no autograd graph.  Squares and rectangles up to 128, fp32 / bf16 / fp16 tensors and float64 by the rules of
+    ``adi_diffuse``; every size runs on the any-size kernels.  At a kink of the clamp the one-sided derivative of the
+    forward's own mask is taken."""
+    params = (alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
+    dparams = (d_alpha_base, d_beta_base, d_alpha_time_coeff, d_beta_time_coeff)
+    if du is None and all(t is None for t in dparams):
+        raise ValueError("adi_diffuse_tangent needs du or a parameter tangent (use adi_diffuse for the value alone)")
+    if not isinstance(sweeps, tuple):
+        sweeps = tuple(sweeps)
+    if u.dim() != 4:
+        raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
+    if du is not None and du.shape != u.shape:
+        raise L.PdeError(f"du of shape {tuple(du.shape)} does not match u {tuple(u.shape)}")
+    rect = _is_rect(u)
+    f64 = _is_f64(u, *params)
+    with torch.no_grad():
+        if not f64:
+            u = _io_in(u, *params)
+        if rect:
+            _check_rect(u, *params)
+        else:
+            _require_cuda(u, *params)
+        _require_cuda(du, *dparams)
+        if u.shape[0] == 0:
+            y = u.to(torch.float64) if f64 else u.clone()
+            return y, torch.zeros_like(y)
+        B, Cc, H, W = u.shape
+        fam, desc_cls, as_chw = _ADI_FAMILY[rect, f64]
+        u = _kernel_input(u.detach(), f64, align=1)          # the tangent kernels read one element at a time
+        du = None if du is None else _kernel_input(du.detach().to(u.dtype), f64, align=1)
+        p = [as_chw(t, Cc, H, W, 1) for t in params]
+        dp = [None if t is None else as_chw(t, Cc, H, W, 1) for t in dparams]
+        d = _desc(desc_cls, B, Cc, H, W, L.PDE_IO_F64 if f64 else _io_dtype(u), sweeps, smooth3, clamp_max, eps)
+        return _tangent_call(L.load(), fam, d, u, du, p, dp, True)
 
 
 def adi_diffuse_small_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coeff, M, steps, mode: str, emit,
@@ -1426,7 +1549,14 @@ class _MixFn(torch.autograd.Function):
         else:
             ctx.save_for_backward(u, Mf)
         ctx.primal_args = (u_in if ctx.input_only is None else None, M)
+        ctx.dual = _take_dual(ctx)
+        if ctx.dual:
+            ctx.save_for_forward(u, M.detach())
         return out
+
+    @staticmethod
+    def jvp(ctx, ut, Mt):
+        return _mix_jvp(_MixFn, ctx, ut, Mt)
 
     @staticmethod
     def backward(ctx, gout):
@@ -1475,13 +1605,28 @@ def _mix_second_order(cls, ctx, gout):
     return linear_adjoint(lambda g: cls._backward(ctx, g), primal, (gout,), (u, M), n_diff=2)
 
 
+def _mix_jvp(cls, ctx, ut, Mt):
+    """Forward mode of ``y = M u``: ``M ut + Mt u``, each term the node's own forward kernel."""
+    if not ctx.dual:
+        raise NotImplementedError(_NO_JVP_ROUTE)
+    u, M = ctx.saved_tensors
+    out = None if ut is None else cls.apply(ut.to(u.dtype), M)
+    if Mt is not None:
+        t = cls.apply(u, Mt)
+        out = t if out is None else out + t
+    return torch.zeros_like(u) if out is None else out
+
+
 def channel_mix(u, M):
     """out[b,i,p] = sum_j M[i,j] u[b,j,p] — cifar10.py:65-72 and SVHN.py:78-86."""
     if u.shape[0] == 0:
         return _empty_passthrough(u, M)
-    if _is_f64(u, M):
-        return _MixF64Fn.apply(u, M)
-    return _MixFn.apply(_io_in(u, M), M)
+    f64 = _is_f64(u, M)
+    if not f64:
+        u = _io_in(u, M)
+    if _fwad._current_level >= 0 and _has_tangent(u, M):
+        return _apply_dual(_MixF64Fn if f64 else _MixFn, u, M)
+    return _MixF64Fn.apply(u, M) if f64 else _MixFn.apply(u, M)
 
 
 # --------------------------------------------------------------------------- BatchNorm2d + 4x4 avg/max pooling
@@ -2168,7 +2313,14 @@ class _SkipBlendFn(torch.autograd.Function):
             ctx.save_for_backward(a, b, w)
         ctx.in_dtypes = (u0.dtype, u.dtype, skip_weight.dtype, skip_weight.shape)
         ctx.primal_args = skip_weight
+        ctx.dual = _take_dual(ctx)
+        if ctx.dual:
+            ctx.save_for_forward(a, b, w, skip_weight.detach())
         return out
+
+    @staticmethod
+    def jvp(ctx, u0t, ut, wt):
+        return _blend_jvp(_SkipBlendFn, ctx, u0t, ut, wt)
 
     @staticmethod
     def backward(ctx, g):
@@ -2210,6 +2362,23 @@ def _blend_second_order(cls, ctx, g):
     return linear_adjoint(lambda c: cls._backward(ctx, c), primal, (g,), (w,), n_diff=2)
 
 
+def _blend_jvp(cls, ctx, u0t, ut, wt):
+    """Forward mode of ``s u0 + (1 - s) u``, s = sigmoid(w): the blend of the tangents (the node's own forward kernel)
+    plus ``s (1 - s) wt (u0 - u)``."""
+    if not ctx.dual:
+        raise NotImplementedError(_NO_JVP_ROUTE)
+    a, b, w, w_in = ctx.saved_tensors                      # w_in: as the caller gave it (it takes part in the type routing)
+    out = None
+    if u0t is not None or ut is not None:
+        out = cls.apply(torch.zeros_like(a) if u0t is None else u0t.to(a.dtype),
+                        torch.zeros_like(b) if ut is None else ut.to(b.dtype), w_in)
+    if wt is not None:
+        s = torch.sigmoid(w)
+        t = ((s * (1 - s) * wt.reshape(1).to(w.dtype)) * (a.to(w.dtype) - b.to(w.dtype))).to(b.dtype)
+        out = t if out is None else out + t
+    return torch.zeros_like(b) if out is None else out
+
+
 def skip_blend(u0, u, skip_weight):
     """``sigmoid(skip_weight) * u0 + (1 - sigmoid(skip_weight)) * u`` — SVHN.py:73-74, one pass."""
     f64 = _is_f64(u0, u, skip_weight)
@@ -2218,9 +2387,10 @@ def skip_blend(u0, u, skip_weight):
             u0, u, skip_weight = u0.double(), u.double(), skip_weight.double()
         s = torch.sigmoid(skip_weight)
         return s * u0 + (1 - s) * u
-    if f64:
-        return _SkipBlendF64Fn.apply(u0, u, skip_weight)
-    return _SkipBlendFn.apply(u0, u, skip_weight)
+    cls = _SkipBlendF64Fn if f64 else _SkipBlendFn
+    if _fwad._current_level >= 0 and _has_tangent(u0, u, skip_weight):
+        return _apply_dual(cls, u0, u, skip_weight)
+    return cls.apply(u0, u, skip_weight)
 
 
 # --------------------------------------------------------------------------- float64
@@ -2266,7 +2436,14 @@ class _MixF64Fn(torch.autograd.Function):
             ctx.save_for_backward(u, Md)
         ctx.m_dtype = M.dtype
         ctx.primal_args = (u_in if ctx.input_only is None else None, M)
+        ctx.dual = _take_dual(ctx)
+        if ctx.dual:
+            ctx.save_for_forward(u, M.detach())
         return out
+
+    @staticmethod
+    def jvp(ctx, ut, Mt):
+        return _mix_jvp(_MixF64Fn, ctx, ut, Mt)
 
     @staticmethod
     def backward(ctx, gout):
@@ -2319,7 +2496,14 @@ class _SkipBlendF64Fn(torch.autograd.Function):
             ctx.save_for_backward(a, b, w)
         ctx.in_meta = (u0.dtype, u.dtype, skip_weight.dtype, skip_weight.shape)
         ctx.primal_args = skip_weight
+        ctx.dual = _take_dual(ctx)
+        if ctx.dual:
+            ctx.save_for_forward(a, b, w, skip_weight.detach())
         return out
+
+    @staticmethod
+    def jvp(ctx, u0t, ut, wt):
+        return _blend_jvp(_SkipBlendF64Fn, ctx, u0t, ut, wt)
 
     @staticmethod
     def backward(ctx, g):

@@ -577,3 +577,45 @@ def layer_trajectory(layer, u, steps=None):
     if isinstance(layer, _AdiBase):
         return layer.trajectory(u, steps)
     raise TypeError(f"{type(layer).__name__} has no time loop to return the trajectory of")
+
+
+def layer_jvp(layer, u, du=None, dparams=None):
+    """Forward-mode derivative of an implicit layer: ``(y, ydot)`` with ``y = layer(u)`` and ``ydot`` its directional
+    derivative along the input tangent ``du`` and the parameter tangents ``dparams`` — a mapping from names of
+    ``layer.named_parameters()`` to tensors of the parameters' shapes; a missing name (and ``du`` None) is a zero tangent.
+
+    The layer's own ``forward`` runs once under ``torch.autograd.forward_ad.dual_level()`` (``torch.func.functional_call``
+    with dual parameters), so the routing is ``forward``'s: fp32, bf16, ``model.half()``, float64, squares and rectangles,
+    launch groups beyond 32 steps.  The sweeps go through functional.adi_diffuse — with a coefficient tangent one
+    tangent-linear launch per group of sweeps (pde_adi*_tangent), with ``du`` alone the layer's usual forward at ``du`` —
+    and a channel operator or skip blend through functional.channel_mix / functional.skip_blend, step by step.  No autograd
+    graph is built.  Every implicit class (Mnist, Fashion, Svhn, Enhanced, Learnable); ``ImprovedDiffusionLayer`` and
+    ``PDELayer`` have no tangent kernels: TypeError."""
+    import torch.autograd.forward_ad as fwad
+    if not isinstance(layer, _AdiBase):
+        raise TypeError(f"{type(layer).__name__} has no forward-mode derivative (the implicit diffusion layers have one)")
+    named = dict(layer.named_parameters())
+    dparams = dict(dparams or {})
+    unknown = sorted(set(dparams) - set(named))
+    if unknown:
+        raise KeyError(f"no such parameters: {unknown} (the layer has {sorted(named)})")
+    with fwad.dual_level():
+        params = {}
+        for name, p in named.items():
+            t = dparams.get(name)
+            if t is None:
+                params[name] = p.detach()
+                continue
+            if tuple(t.shape) != tuple(p.shape):
+                raise ValueError(f"tangent of {name}: shape {tuple(t.shape)}, expected {tuple(p.shape)}")
+            params[name] = fwad.make_dual(p.detach(), t.detach().to(device=p.device, dtype=p.dtype))
+        x = u.detach()
+        if du is not None:
+            if du.shape != u.shape:
+                raise ValueError(f"du of shape {tuple(du.shape)} does not match u {tuple(u.shape)}")
+            x = fwad.make_dual(x, du.detach().to(device=u.device, dtype=u.dtype))
+        out = torch.func.functional_call(layer, params, (x,))
+        y, ydot = fwad.unpack_dual(out)
+        y = y.detach()
+        ydot = torch.zeros_like(y) if ydot is None else ydot.detach()
+    return y, ydot

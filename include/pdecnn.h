@@ -1030,6 +1030,7 @@ const char* pde_version(void);
 #include "pdecnn_small_input.h"
 #include "pdecnn_mixed_input.h"
 #include "pdecnn_explicit_input.h"
+#include "pdecnn_tangent.h"
 
 #ifdef __cplusplus
 }
