@@ -334,6 +334,21 @@ SIGNATURES_TANGENT = {
     "pde_adi_rect_f64_tangent": (C.c_int, [_DR64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+#: include/pdecnn_explicit_tangent.h (included by pdecnn.h): the tangent-linear pass of the explicit 5-point and the Jacobi
+#: layers — u, du, the two parameter vectors, their two tangents, [the step's scalars,] y, dy[, workspace]
+PDE_JACOBI_TANGENT_TILED_K = PDE_JACOBI_TILED_K
+SIGNATURES_EXPLICIT_TANGENT = {
+    "pde_explicit5_tangent_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "pde_explicit5_tangent": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _fp, _fp, _fp, _fp, _f32, _f32, _f32, _f32,
+                                        _i32, _vp, _vp, _vp, _sz, _vp]),
+    "pde_explicit5_f64_tangent_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "pde_explicit5_f64_tangent": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64,
+                                            _i32, _vp, _vp, _vp, _sz, _vp]),
+    "pde_jacobi_io_tangent_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "pde_jacobi_io_tangent": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _fp, _fp, _fp, _fp, _vp, _vp, _vp, _sz, _vp]),
+    "pde_jacobi_f64_tangent": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 
 
@@ -349,7 +364,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_SMALL_INPUT.items()) +
                               list(SIGNATURES_MIXED_INPUT.items()) + list(SIGNATURES_EXPLICIT_INPUT.items()) +
-                              list(SIGNATURES_TANGENT.items())):
+                              list(SIGNATURES_TANGENT.items()) + list(SIGNATURES_EXPLICIT_TANGENT.items())):
         fn = getattr(lib, name)         # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     _lib = lib

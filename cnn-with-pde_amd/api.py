@@ -3,10 +3,11 @@ from . import _lib
 from ._lib import PdeError, LIB_PATH
 from .functional import (Sweep, adi_schedule, adi_diffuse, adi_diffuse_states, adi_diffuse_tangent, adi_diffuse_mixed, adi_diffuse_small, adi_diffuse_small_states, adi_diffuse_multi, gate_combine, bn_pool,
                          plan_checkpoints, channel_mix, explicit5_step, jacobi_diffuse, explicit5_states, jacobi_diffuse_states,
-                         timing_enable, timing_read)
+                         explicit5_tangent, jacobi_diffuse_tangent, timing_enable, timing_read)
 from .dist import shard_range, shard_batch, GradBucket
 from .layers import (MnistDiffusionLayer, FashionDiffusionLayer, SvhnDiffusionLayer, EnhancedDiffusionLayer,
-                     LearnableDiffusionLayer, ImprovedDiffusionLayer, PDELayer, layer_trajectory, layer_jvp)
+                     LearnableDiffusionLayer, ImprovedDiffusionLayer, PDELayer, layer_trajectory, layer_jvp,
+                     explicit_layer_jvp)
 from . import models
 from . import graphs
 from .graphs import freeze_checkpoint_plans, make_graphed, GraphedStep
@@ -49,7 +50,8 @@ def library_version() -> str:
 
 __all__ = ["graphs", "freeze_checkpoint_plans", "make_graphed", "GraphedStep", "PdeError", "LIB_PATH", "Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_tangent", "adi_diffuse_mixed", "adi_diffuse_small",
            "adi_diffuse_multi", "gate_combine", "bn_pool", "plan_checkpoints", "channel_mix", "explicit5_step",
-           "jacobi_diffuse", "explicit5_states", "jacobi_diffuse_states", "layer_trajectory", "layer_jvp", "timing_enable", "timing_read", "MnistDiffusionLayer", "FashionDiffusionLayer",
+           "jacobi_diffuse", "explicit5_states", "jacobi_diffuse_states", "layer_trajectory", "layer_jvp", "explicit_layer_jvp", "explicit5_tangent", "jacobi_diffuse_tangent",
+           "timing_enable", "timing_read", "MnistDiffusionLayer", "FashionDiffusionLayer",
            "SvhnDiffusionLayer", "EnhancedDiffusionLayer", "LearnableDiffusionLayer", "ImprovedDiffusionLayer",
            "PDELayer", "models", "MnistPDEClassifier", "FashionPDEClassifier", "SvhnPDEClassifier", "SpatialAttention",
            "MultiScaleExtractor", "EnhancedFC", "CIFAR10PDENoConv", "SymmetricLayer", "ParabolicBlock", "HamiltonianBlock",

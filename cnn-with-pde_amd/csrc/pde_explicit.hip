@@ -608,6 +608,185 @@ void bwd_input_wave_io(int H, const void* g, const float* alpha, const float* sc
 }
 
 // ---------------------------------------------------------------------------------------
+// tangent-linear pass (pdecnn_explicit_tangent.h: pde_explicit5_tangent): the primal state u and the tangent state du
+// advance together.  Per step, with a = clamp(alpha_c)*dt, s = scale_c, L = Lap0:
+//     u'  = u + relax*((s u + a*(s*L u)) - u)                     the forward kernels' expressions, in their order
+//     du' = the same expressions on du, then + relax*(ds*(u + a*L u) + da*(s*L u)),   u the step's input
+//     da  = [eps <= alpha_c <= max_coeff] * dalpha_c * dt          (the mask of explicit5_pgrad_kernel: equality passes)
+// With both parameter tangents NULL the source is not added at all (src == 0), so dy is bit for bit the forward at du.
+// ---------------------------------------------------------------------------------------
+struct ExTan {          // one channel's coefficients and their tangents
+    float a, s, da, ds;
+};
+__device__ __forceinline__ ExTan ex_tan_coeffs(const float* alpha, const float* scale, const float* d_alpha,
+                                               const float* d_scale, int c, float dt, float eps, float maxc) {
+    ExTan t;
+    const float ab = alpha[c];
+    t.a = fminf(fmaxf(ab, eps), maxc) * dt;
+    t.s = scale[c];
+    t.da = (d_alpha && ab >= eps && ab <= maxc) ? d_alpha[c] * dt : 0.f;
+    t.ds = d_scale ? d_scale[c] : 0.f;
+    return t;
+}
+// One step of one state element, x -> x + relax*((s x + a*(s*L x)) - x), with the forward's roundings.  The forward writes
+// `v + a * (s * lp)` and leaves the contraction to the compiler, which fuses one of the two products into the sum: s*x in
+// every instantiation of the forward kernels but the 16x16 wave kernel (R = 1), where it fuses a*(s*L x).  Here s*L u is
+// used twice and the choice would fall differently, so contraction is off and the forward's fused operations are spelled
+// out (AFMA: the 16x16 form); the identity tests of tests/test_gpu_tangent_explicit.py hold the two to the same bits.
+template <bool AFMA>
+__device__ __forceinline__ float ex_step_elem(float a, float s, float relax, float x, float slx) {
+#pragma clang fp contract(off)
+    const float nw = AFMA ? __builtin_fmaf(a, slx, s * x) : __builtin_fmaf(s, x, a * slx);
+    return __builtin_fmaf(relax, nw - x, x);
+}
+// one element: (u, L u, du, L du) -> (u', du')
+template <bool AFMA>
+__device__ __forceinline__ void ex_tan_elem(const ExTan& t, float relax, int src, float cu, float lp, float dcu, float dlp,
+                                            float& o, float& od) {
+#pragma clang fp contract(off)
+    const float slp = t.s * lp;
+    o = ex_step_elem<AFMA>(t.a, t.s, relax, cu, slp);
+    od = ex_step_elem<AFMA>(t.a, t.s, relax, dcu, t.s * dlp);
+    if (src) od = __builtin_fmaf(relax, __builtin_fmaf(t.ds, __builtin_fmaf(t.a, lp, cu), t.da * slp), od);
+}
+template <bool AFMA>
+__device__ __forceinline__ void ex_tan_elem4(const ExTan& t, float relax, int src, const float4& cu, const float4& lp,
+                                             const float4& dcu, const float4& dlp, float4& o, float4& od) {
+    ex_tan_elem<AFMA>(t, relax, src, cu.x, lp.x, dcu.x, dlp.x, o.x, od.x);
+    ex_tan_elem<AFMA>(t, relax, src, cu.y, lp.y, dcu.y, dlp.y, o.y, od.y);
+    ex_tan_elem<AFMA>(t, relax, src, cu.z, lp.z, dcu.z, dlp.z, o.z, od.z);
+    ex_tan_elem<AFMA>(t, relax, src, cu.w, lp.w, dcu.w, dlp.w, o.w, od.w);
+}
+
+// explicit5_fwd_kernel with a second state.  du NULL (first step only): a zero tangent; out NULL (last step only): y is
+// not wanted.  TI / TO as there: the call's type at its first load and last store, fp32 between the steps.
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void explicit5_tangent_kernel(const TI* __restrict__ u, const TI* __restrict__ du,
+                                                                const float* __restrict__ alpha, const float* __restrict__ scale,
+                                                                const float* __restrict__ d_alpha,
+                                                                const float* __restrict__ d_scale, TO* __restrict__ out,
+                                                                TO* __restrict__ dout, int C, int H, int W, float dt,
+                                                                float eps, float maxc, float relax, int src) {
+    const int pc = blockIdx.x;                         // plane index b*C + c
+    const ExTan t = ex_tan_coeffs(alpha, scale, d_alpha, d_scale, pc % C, dt, eps, maxc);
+    const size_t po = (size_t)pc * H * W;
+    const TI* plane = u + po;
+    const TI* dplane = du ? du + po : nullptr;
+    const int W4 = W / 4;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int f = threadIdx.x; f < H * W4; f += 256) {
+        const int h = f / W4, w0 = 4 * (f % W4);
+        const size_t e = (size_t)h * W + w0;
+        const float4 cu = V4<TI>::ld(plane + e);
+        const float4 lp = lap0_4<TI>(plane, H, W, h, w0, cu);
+        const float4 dcu = dplane ? V4<TI>::ld(dplane + e) : z;
+        const float4 dlp = dplane ? lap0_4<TI>(dplane, H, W, h, w0, dcu) : z;
+        float4 o, od;
+        ex_tan_elem4<false>(t, relax, src, cu, lp, dcu, dlp, o, od);
+        if (out) V4<TO>::st(out + po + e, o);
+        V4<TO>::st(dout + po + e, od);
+    }
+}
+
+// explicit5_fwd_col_kernel with a second state (widths that are not a multiple of 4)
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void explicit5_tangent_col_kernel(const TI* __restrict__ u, const TI* __restrict__ du,
+                                                                    const float* __restrict__ alpha,
+                                                                    const float* __restrict__ scale,
+                                                                    const float* __restrict__ d_alpha,
+                                                                    const float* __restrict__ d_scale, TO* __restrict__ out,
+                                                                    TO* __restrict__ dout, int C, int H, int W, float dt,
+                                                                    float eps, float maxc, float relax, int src) {
+    const int pc = blockIdx.x;
+    const ExTan t = ex_tan_coeffs(alpha, scale, d_alpha, d_scale, pc % C, dt, eps, maxc);
+    const size_t po = (size_t)pc * H * W;
+    const TI* plane = u + po;
+    const TI* dplane = du ? du + po : nullptr;
+    for (int f = threadIdx.x; f < H * W; f += 256) {
+        const int h = f / W, w = f % W;
+        const float cu = S1<TI>::ld(plane + f);
+        const float lp = lap0_1<TI>(plane, H, W, h, w, cu);
+        const float dcu = dplane ? S1<TI>::ld(dplane + f) : 0.f;
+        const float dlp = dplane ? lap0_1<TI>(dplane, H, W, h, w, dcu) : 0.f;
+        float o, od;
+        ex_tan_elem<false>(t, relax, src, cu, lp, dcu, dlp, o, od);
+        if (out) S1<TO>::st(out + po + f, o);
+        S1<TO>::st(dout + po + f, od);
+    }
+}
+
+// Lap0 of one of the lane's rows from the row above, itself and the row below: lap0_rows' operations, in its order
+template <int W4>
+__device__ __forceinline__ float4 lap0_row(const float4& n, const float4& c, const float4& s, int cg) {
+    float l = dpp_shift<kWaveShr1>(c.w), r = dpp_shift<kWaveShl1>(c.x);
+    if (cg == 0) l = 0.f;
+    if (cg == W4 - 1) r = 0.f;
+    float4 lp;
+    lp.x = n.x + s.x + l + c.y - 4.f * c.x;
+    lp.y = n.y + s.y + c.x + c.z - 4.f * c.y;
+    lp.z = n.z + s.z + c.y + c.w - 4.f * c.z;
+    lp.w = n.w + s.w + c.z + r - 4.f * c.w;
+    return lp;
+}
+
+// explicit5_fwd_wave with a second state: both planes in registers over all steps, one launch.  The two Laplacians are
+// formed row by row (the halo rows are fetched before the first row changes, the old row above is carried along), so a
+// 64x64 plane holds cur and dcur (128 registers) and two rows of Laplacians, not four plane-sized arrays: no scratch.
+template <typename IO, int R, int W4>
+__global__ __launch_bounds__(256) void explicit5_tangent_wave(const IO* __restrict__ u, const IO* __restrict__ du,
+                                                              const float* __restrict__ alpha, const float* __restrict__ scale,
+                                                              const float* __restrict__ d_alpha,
+                                                              const float* __restrict__ d_scale, IO* __restrict__ out,
+                                                              IO* __restrict__ dout, int nplanes, int C, int num_steps,
+                                                              float dt, float eps, float maxc, float relax, int src) {
+    constexpr int W = 4 * W4, H = R * (64 / W4), RG = 64 / W4;
+    const int lane = threadIdx.x & 63;
+    const int pc = blockIdx.x * 4 + (threadIdx.x >> 6);          // one wave per plane
+    if (pc >= nplanes) return;
+    const ExTan t = ex_tan_coeffs(alpha, scale, d_alpha, d_scale, pc % C, dt, eps, maxc);
+    const int cg = lane % W4, rg = lane / W4;
+    const size_t off = (size_t)pc * H * W + (size_t)(rg * R) * W + 4 * cg;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 cur[R], dcur[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        cur[i] = V4<IO>::ld_once(u + off + (size_t)i * W);
+        dcur[i] = du ? V4<IO>::ld_once(du + off + (size_t)i * W) : z;
+    }
+    for (int step = 0; step < num_steps; ++step) {
+        float4 top = shfl_up4(cur[R - 1], W4), bot = shfl_down4(cur[0], W4);
+        float4 dtop = shfl_up4(dcur[R - 1], W4), dbot = shfl_down4(dcur[0], W4);
+        if (rg == 0) { top = z; dtop = z; }
+        if (rg == RG - 1) { bot = z; dbot = z; }
+        float4 pn = top, dpn = dtop;                              // the row above, as it was before this step
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const float4 c = cur[i], dc = dcur[i];
+            const float4 lp = lap0_row<W4>(pn, c, (i < R - 1) ? cur[i + 1] : bot, cg);
+            const float4 dlp = lap0_row<W4>(dpn, dc, (i < R - 1) ? dcur[i + 1] : dbot, cg);
+            ex_tan_elem4<R == 1>(t, relax, src, c, lp, dc, dlp, cur[i], dcur[i]);
+            pn = c;
+            dpn = dc;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        if (out) V4<IO>::st(out + off + (size_t)i * W, cur[i]);
+        V4<IO>::st(dout + off + (size_t)i * W, dcur[i]);
+    }
+}
+
+template <typename IO>
+void tangent_wave_io(int H, const void* u, const void* du, const float* alpha, const float* scale, const float* d_alpha,
+                     const float* d_scale, void* out, void* dout, int nplanes, int C, int num_steps, float dt, float eps,
+                     float maxc, float relax, int src, hipStream_t st) {
+    const dim3 grid((nplanes + 3) / 4), block(256);
+    if (H == 64) hipLaunchKernelGGL((explicit5_tangent_wave<IO, 16, 16>), grid, block, 0, st, (const IO*)u, (const IO*)du, alpha, scale, d_alpha, d_scale, (IO*)out, (IO*)dout, nplanes, C, num_steps, dt, eps, maxc, relax, src);
+    else if (H == 32) hipLaunchKernelGGL((explicit5_tangent_wave<IO, 4, 8>), grid, block, 0, st, (const IO*)u, (const IO*)du, alpha, scale, d_alpha, d_scale, (IO*)out, (IO*)dout, nplanes, C, num_steps, dt, eps, maxc, relax, src);
+    else hipLaunchKernelGGL((explicit5_tangent_wave<IO, 1, 4>), grid, block, 0, st, (const IO*)u, (const IO*)du, alpha, scale, d_alpha, d_scale, (IO*)out, (IO*)dout, nplanes, C, num_steps, dt, eps, maxc, relax, src);
+}
+
+// ---------------------------------------------------------------------------------------
 // jacobi (emotion_recognition.PDELayer)
 // ---------------------------------------------------------------------------------------
 constexpr int kJMax = 64;                  // max H, W
@@ -866,6 +1045,73 @@ __global__ __launch_bounds__(256) void jacobi_bwd_input_kernel(const IO* __restr
             }
         }
         S1<IO>::st(gub + e, v);
+    }
+}
+
+// The tangent-linear pass (pdecnn_explicit_tangent.h: pde_jacobi_io_tangent), planes up to 64x64: jacobi_fwd_kernel with a
+// second state.  dP is the reflect-padded du (zeros when du is NULL); both rings stay frozen.  Interior, per step:
+//     P'  = P + a_i d1(P) + b_j d2(P)                              jacobi_step's expressions, in their order
+//     dP' = the same on dP, then + da_i d1(P) + db_j d2(P),        P the step's input; not added at all when src == 0
+// LDS (dynamic): P, Q, dP, dQ, a, b, da, db — 70720 bytes at 64x64.
+__device__ __forceinline__ void jacobi_tangent_step(const float* P, float* Q, const float* dP, float* dQ, const float* a,
+                                                    const float* b, const float* da, const float* db, int H, int W, int src) {
+    const int Wp = W + 2;
+    for (int e = threadIdx.x; e < (H + 2) * Wp; e += blockDim.x) {
+        const int i = e / Wp, j = e % Wp;
+        float v = P[e], dv = dP[e];
+        if (i >= 1 && i <= H && j >= 1 && j <= W) {
+            const float d1 = P[e + Wp] - 2.f * v + P[e - Wp];
+            const float d2 = P[e + 1] - 2.f * v + P[e - 1];
+            const float dd1 = dP[e + Wp] - 2.f * dv + dP[e - Wp];
+            const float dd2 = dP[e + 1] - 2.f * dv + dP[e - 1];
+            v = v + a[i - 1] * d1 + b[j - 1] * d2;
+            dv = dv + a[i - 1] * dd1 + b[j - 1] * dd2;
+            if (src) dv = dv + da[i - 1] * d1 + db[j - 1] * d2;
+        }
+        Q[e] = v;
+        dQ[e] = dv;
+    }
+}
+
+template <typename IO>
+__global__ __launch_bounds__(256) void jacobi_tangent_kernel(const IO* __restrict__ u, const IO* __restrict__ du,
+                                                             const float* __restrict__ a_row, const float* __restrict__ b_col,
+                                                             const float* __restrict__ d_a_row,
+                                                             const float* __restrict__ d_b_col, IO* __restrict__ out,
+                                                             IO* __restrict__ dout, int H, int W, int nt, int src) {
+    extern __shared__ float sm[];
+    const int Wp = W + 2, PN = (H + 2) * Wp;
+    float* P = sm;
+    float* Q = sm + PN;
+    float* dP = sm + 2 * PN;
+    float* dQ = sm + 3 * PN;
+    float* a = sm + 4 * PN;
+    float* b = a + H;
+    float* da = b + W;
+    float* db = da + H;
+    const IO* ub = u + (size_t)blockIdx.x * H * W;
+    const IO* dub = du ? du + (size_t)blockIdx.x * H * W : nullptr;
+    for (int e = threadIdx.x; e < H; e += blockDim.x) { a[e] = a_row[e]; da[e] = d_a_row ? d_a_row[e] : 0.f; }
+    for (int e = threadIdx.x; e < W; e += blockDim.x) { b[e] = b_col[e]; db[e] = d_b_col ? d_b_col[e] : 0.f; }
+    for (int e = threadIdx.x; e < PN; e += blockDim.x) {
+        const int i = e / Wp, j = e % Wp;
+        const int o = reflect_src(i, H) * W + reflect_src(j, W);                    // F.pad(..., mode='reflect')
+        P[e] = S1<IO>::ld(ub + o);
+        dP[e] = dub ? S1<IO>::ld(dub + o) : 0.f;
+    }
+    __syncthreads();
+    for (int n = 0; n < nt; ++n) {
+        jacobi_tangent_step(P, Q, dP, dQ, a, b, da, db, H, W, src);
+        __syncthreads();
+        float* t = P; P = Q; Q = t;
+        t = dP; dP = dQ; dQ = t;
+    }
+    IO* ob = out ? out + (size_t)blockIdx.x * H * W : nullptr;
+    IO* dob = dout + (size_t)blockIdx.x * H * W;
+    for (int e = threadIdx.x; e < H * W; e += blockDim.x) {
+        const int l = (e / W + 1) * Wp + (e % W) + 1;
+        if (ob) S1<IO>::st(ob + e, P[l]);
+        S1<IO>::st(dob + e, dP[l]);
     }
 }
 
@@ -1469,6 +1715,167 @@ int pde_jacobi_io_backward_input_states(int32_t B, int32_t H, int32_t W, int32_t
     if (io_dtype == PDE_IO_BF16)
         return jacobi_backward_input_io<bf16e>(path, B, H, W, nt, gout, a_row, b_col, gu, workspace, gstates, em, st);
     return jacobi_backward_input_io<f16e>(path, B, H, W, nt, gout, a_row, b_col, gu, workspace, gstates, em, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// the tangent-linear pass (pdecnn_explicit_tangent.h): (y, dy) from (u, du) and the parameter tangents
+// ---------------------------------------------------------------------------------------
+namespace {
+
+// one step of the generic-size path: T at the call's first load and last store, fp32 images between the steps
+template <typename TI, typename TO>
+void ex_tangent(const ExArgs& a, const float* d_alpha, const float* d_scale, const void* src, const void* dsrc, void* dst,
+                void* ddst, int has_src, hipStream_t st) {
+    if (a.W % 4)
+        hipLaunchKernelGGL((explicit5_tangent_col_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src,
+                           (const TI*)dsrc, a.alpha, a.scale, d_alpha, d_scale, (TO*)dst, (TO*)ddst, a.C, a.H, a.W, a.dt, a.eps,
+                           a.maxc, a.relax, has_src);
+    else
+        hipLaunchKernelGGL((explicit5_tangent_kernel<TI, TO>), dim3(a.nplanes), dim3(256), 0, st, (const TI*)src,
+                           (const TI*)dsrc, a.alpha, a.scale, d_alpha, d_scale, (TO*)dst, (TO*)ddst, a.C, a.H, a.W, a.dt, a.eps,
+                           a.maxc, a.relax, has_src);
+}
+template <typename T>
+void ex_tangent_step(const ExArgs& a, const float* d_alpha, const float* d_scale, bool first, bool last, const void* src,
+                     const void* dsrc, void* dst, void* ddst, int has_src, hipStream_t st) {
+    if (first && last) ex_tangent<T, T>(a, d_alpha, d_scale, src, dsrc, dst, ddst, has_src, st);
+    else if (first) ex_tangent<T, float>(a, d_alpha, d_scale, src, dsrc, dst, ddst, has_src, st);
+    else if (last) ex_tangent<float, T>(a, d_alpha, d_scale, src, dsrc, dst, ddst, has_src, st);
+    else ex_tangent<float, float>(a, d_alpha, d_scale, src, dsrc, dst, ddst, has_src, st);
+}
+
+size_t jacobi_tangent_lds(int H, int W) { return (4 * (size_t)(H + 2) * (W + 2) + 2 * (size_t)(H + W)) * sizeof(float); }
+
+template <typename IO>
+int jacobi_tangent_io(int path, int B, int H, int W, int nt, const void* u, const void* du, const float* a_row,
+                      const float* b_col, const float* d_a_row, const float* d_b_col, void* y, void* dy, void* workspace,
+                      hipStream_t st) {
+    const int has_src = (d_a_row || d_b_col) ? 1 : 0;
+    static unsigned long long configured = 0, configured_tiled = 0;
+    if (path == 1) {
+        if (ensure_dynamic_lds(reinterpret_cast<const void*>(jacobi_tangent_kernel<IO>), (int)jacobi_tangent_lds(kJMax, kJMax),
+                               configured) != PDE_OK)
+            return PDE_E_LAUNCH;
+        hipLaunchKernelGGL((jacobi_tangent_kernel<IO>), dim3(B), dim3(256), jacobi_tangent_lds(H, W), st, (const IO*)u,
+                           (const IO*)du, a_row, b_col, d_a_row, d_b_col, (IO*)y, (IO*)dy, H, W, nt, has_src);
+        return check_launch();
+    }
+    const size_t lds = kJTanFloats * sizeof(float);
+    if (ensure_dynamic_lds(reinterpret_cast<const void*>(jacobi_tiled_tangent_kernel<IO>), (int)lds, configured_tiled) != PDE_OK)
+        return PDE_E_LAUNCH;
+    const int nTy = jtiles(H), nTx = jtiles(W);
+    const dim3 grid((unsigned)((size_t)B * nTy * nTx));
+    // the launches hand P and dP on through two fp32 images each: P0, P1, dP0, dP1
+    const size_t ib = align256((size_t)B * H * W * sizeof(float));
+    char* base = static_cast<char*>(workspace);
+    float* img[2] = {reinterpret_cast<float*>(base), base ? reinterpret_cast<float*>(base + ib) : nullptr};
+    float* dimg[2] = {base ? reinterpret_cast<float*>(base + 2 * ib) : nullptr,
+                      base ? reinterpret_cast<float*>(base + 3 * ib) : nullptr};
+    int n0 = 0, l = 0;
+    do {                                                    // nt = 0: one launch of no steps copies
+        const int k = nt - n0 < kJTanK ? nt - n0 : kJTanK;
+        const bool last = n0 + k == nt;
+        hipLaunchKernelGGL((jacobi_tiled_tangent_kernel<IO>), grid, dim3(256), lds, st, (const IO*)u, (const IO*)du,
+                           l == 0 ? (const float*)nullptr : (const float*)img[(l - 1) & 1],
+                           l == 0 ? (const float*)nullptr : (const float*)dimg[(l - 1) & 1], a_row, b_col, d_a_row, d_b_col,
+                           last ? y : (void*)img[l & 1], last ? dy : (void*)dimg[l & 1], last ? 0 : 1, H, W, nTy, nTx, k,
+                           has_src);
+        n0 += k;
+        ++l;
+    } while (n0 < nt);
+    return check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t pde_explicit5_tangent_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype,
+                                             int32_t num_steps) {
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return 0;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 2 || wave_plane_ok(H, W)) return 0;
+    return 4 * align256((size_t)B * C * H * W * sizeof(float));     // generic sizes: u and du ping-pong through two images each
+}
+
+int pde_explicit5_tangent(int32_t B, int32_t C, int32_t H, int32_t W, int32_t io_dtype, const void* u, const void* du,
+                          const float* alpha_base, const float* channel_scaling, const float* d_alpha_base,
+                          const float* d_channel_scaling, float dt, float eps, float max_coeff, float relax,
+                          int32_t num_steps, void* y, void* dy, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_steps < 1 || !u || !alpha_base || !channel_scaling || !dy)
+        return PDE_E_BADARG;
+    if (!du && !d_alpha_base && !d_channel_scaling) return PDE_E_BADARG;       // nothing to differentiate: call the forward
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    if (misaligned(ex_tensor_align(W, io_dtype), u, du, y, dy) ||
+        misaligned(4, alpha_base, channel_scaling, d_alpha_base, d_channel_scaling))
+        return PDE_E_BADARG;
+    // the four images are read and written as float4 on the generic float4 path
+    const size_t need = pde_explicit5_tangent_workspace_bytes(B, C, H, W, io_dtype, num_steps);
+    if ((need && (!workspace || workspace_bytes < need)) || misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nplanes = B * C;
+    const int has_src = (d_alpha_base || d_channel_scaling) ? 1 : 0;
+    if (wave_plane_ok(H, W)) {                             // both planes stay in registers over all steps
+        if (io_dtype == PDE_IO_F32)
+            tangent_wave_io<float>(H, u, du, alpha_base, channel_scaling, d_alpha_base, d_channel_scaling, y, dy, nplanes, C,
+                                   num_steps, dt, eps, max_coeff, relax, has_src, st);
+        else if (io_dtype == PDE_IO_F16)
+            tangent_wave_io<f16e>(H, u, du, alpha_base, channel_scaling, d_alpha_base, d_channel_scaling, y, dy, nplanes, C,
+                                  num_steps, dt, eps, max_coeff, relax, has_src, st);
+        else
+            tangent_wave_io<bf16e>(H, u, du, alpha_base, channel_scaling, d_alpha_base, d_channel_scaling, y, dy, nplanes, C,
+                                   num_steps, dt, eps, max_coeff, relax, has_src, st);
+        return check_launch();
+    }
+    const size_t ib = align256((size_t)nplanes * H * W * sizeof(float));
+    char* base = static_cast<char*>(workspace);
+    float* img[2] = {need ? reinterpret_cast<float*>(base) : nullptr, need ? reinterpret_cast<float*>(base + ib) : nullptr};
+    float* dimg[2] = {need ? reinterpret_cast<float*>(base + 2 * ib) : nullptr,
+                      need ? reinterpret_cast<float*>(base + 3 * ib) : nullptr};
+    const ExArgs ea{alpha_base, channel_scaling, nplanes, C, H, W, dt, eps, max_coeff, relax};
+    for (int k = 0; k < num_steps; ++k) {
+        const bool first = k == 0, last = k == num_steps - 1;
+        const void* src = first ? u : static_cast<const void*>(img[(k - 1) & 1]);
+        const void* dsrc = first ? du : static_cast<const void*>(dimg[(k - 1) & 1]);
+        void* dst = last ? y : static_cast<void*>(img[k & 1]);
+        void* ddst = last ? dy : static_cast<void*>(dimg[k & 1]);
+        if (io_dtype == PDE_IO_F32)
+            ex_tangent_step<float>(ea, d_alpha_base, d_channel_scaling, first, last, src, dsrc, dst, ddst, has_src, st);
+        else if (io_dtype == PDE_IO_F16)
+            ex_tangent_step<f16e>(ea, d_alpha_base, d_channel_scaling, first, last, src, dsrc, dst, ddst, has_src, st);
+        else
+            ex_tangent_step<bf16e>(ea, d_alpha_base, d_channel_scaling, first, last, src, dsrc, dst, ddst, has_src, st);
+    }
+    return check_launch();
+}
+
+size_t pde_jacobi_io_tangent_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype) {
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return 0;
+    if (B <= 0 || nt <= kJTanK || jacobi_path(H, W) != 2 || !jacobi_tiled_grid_ok(B, H, W)) return 0;
+    return 4 * align256((size_t)B * H * W * sizeof(float));         // P and dP, two fp32 images each, for the launches to alternate between
+}
+
+int pde_jacobi_io_tangent(int32_t B, int32_t H, int32_t W, int32_t nt, int32_t io_dtype, const void* u, const void* du,
+                          const float* a_row, const float* b_col, const float* d_a_row, const float* d_b_col, void* y,
+                          void* dy, void* workspace, size_t workspace_bytes, void* stream) {
+    const int path = jacobi_path(H, W);
+    if (B <= 0 || path == 0 || nt < 0 || !u || !a_row || !b_col || !dy) return PDE_E_BADARG;
+    if (!du && !d_a_row && !d_b_col) return PDE_E_BADARG;                     // nothing to differentiate: call the forward
+    if (io_dtype != PDE_IO_F32 && io_dtype != PDE_IO_BF16 && io_dtype != PDE_IO_F16) return PDE_E_BADARG;
+    if (misaligned(io_elem_bytes(io_dtype), u, du, y, dy) || misaligned(4, a_row, b_col, d_a_row, d_b_col)) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, workspace)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (path == 2) {
+        if (!jacobi_tiled_grid_ok(B, H, W)) return PDE_E_BADARG;
+        const size_t need = pde_jacobi_io_tangent_workspace_bytes(B, H, W, nt, io_dtype);
+        if (need && (!workspace || workspace_bytes < need)) return PDE_E_WORKSPACE;
+    }
+    if (io_dtype == PDE_IO_F32)
+        return jacobi_tangent_io<float>(path, B, H, W, nt, u, du, a_row, b_col, d_a_row, d_b_col, y, dy, workspace, st);
+    if (io_dtype == PDE_IO_BF16)
+        return jacobi_tangent_io<bf16e>(path, B, H, W, nt, u, du, a_row, b_col, d_a_row, d_b_col, y, dy, workspace, st);
+    return jacobi_tangent_io<f16e>(path, B, H, W, nt, u, du, a_row, b_col, d_a_row, d_b_col, y, dy, workspace, st);
 }
 
 }  // extern "C"

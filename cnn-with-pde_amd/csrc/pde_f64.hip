@@ -229,6 +229,53 @@ __global__ __launch_bounds__(256) void expl64_bwd_input_kernel(int C, int H, int
     }
 }
 
+// the tangent-linear pass of one step (pde_explicit5_f64_tangent): expl64_fwd_kernel with a second state.  dx' is the same
+// expressions on dx, then + relax*(ds*(x + k*Lap0 x) + dk*(s*Lap0 x)) with x the step's input,
+// dk = [eps <= alpha_c <= max_coeff] * dalpha_c * dt; src == 0 (both parameter tangents NULL): the source is not added.
+// dx NULL (first step only): a zero tangent; out NULL (last step only): y is not wanted.
+__global__ __launch_bounds__(256) void expl64_tangent_kernel(int C, int H, int W, const double* __restrict__ x,
+                                                             const double* __restrict__ dx, const double* __restrict__ ab,
+                                                             const double* __restrict__ sc, const double* __restrict__ dab,
+                                                             const double* __restrict__ dsc, double dt, double eps,
+                                                             double maxc, double relax, double* __restrict__ out,
+                                                             double* __restrict__ dout, int src) {
+#pragma clang fp contract(off)
+    // contraction off, the forward's fused operations spelled out (expl64_fwd_kernel compiles to lap = fma(-4, v, sum),
+    // nw = fma(k, lap, v), o = fma(relax, nw - x, x)): y keeps the forward's bits whatever else this kernel computes
+    const int HW = H * W, p = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+    if (p >= HW) return;
+    const int i = p / W, j = p % W;
+    const size_t po = ((size_t)b * C + c) * HW;
+    const double* xp = x + po;
+    const double s = sc[c], k = clamp64(ab[c], eps, maxc) * dt;
+    const double v = s * xp[p];
+    const double up = i > 0 ? s * xp[p - W] : 0.0, dn = i + 1 < H ? s * xp[p + W] : 0.0;
+    const double lf = j > 0 ? s * xp[p - 1] : 0.0, rt = j + 1 < W ? s * xp[p + 1] : 0.0;
+    const double lap = fma(-4.0, v, ((up + dn) + lf) + rt);
+    const double nw = fma(k, lap, v);
+    const double o = fma(relax, nw - xp[p], xp[p]);
+    double od = 0.0;
+    if (dx) {
+        const double* dp = dx + po;
+        const double dv = s * dp[p];
+        const double dup = i > 0 ? s * dp[p - W] : 0.0, ddn = i + 1 < H ? s * dp[p + W] : 0.0;
+        const double dlf = j > 0 ? s * dp[p - 1] : 0.0, drt = j + 1 < W ? s * dp[p + 1] : 0.0;
+        const double dlap = fma(-4.0, dv, ((dup + ddn) + dlf) + drt);
+        const double dnw = fma(k, dlap, dv);
+        od = fma(relax, dnw - dp[p], dp[p]);
+    }
+    if (src) {
+        const double xu = i > 0 ? xp[p - W] : 0.0, xd = i + 1 < H ? xp[p + W] : 0.0;
+        const double xl = j > 0 ? xp[p - 1] : 0.0, xr = j + 1 < W ? xp[p + 1] : 0.0;
+        const double lx = fma(-4.0, xp[p], ((xu + xd) + xl) + xr);         // Lap0 x, unscaled
+        const double ds = dsc ? dsc[c] : 0.0;
+        const double dk = (dab && ab[c] >= eps && ab[c] <= maxc) ? dab[c] * dt : 0.0;
+        od = fma(relax, fma(ds, fma(k, lx, xp[p]), dk * lap), od);
+    }
+    if (out) out[po + p] = o;
+    dout[po + p] = od;
+}
+
 __global__ void expl64_reduce_kernel(int B, int C, const double* __restrict__ part, const double* __restrict__ ab,
                                      double dt, double eps, double maxc, double* __restrict__ ga, double* __restrict__ gs) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -415,6 +462,54 @@ __global__ __launch_bounds__(256) void jac64_bwd_input_kernel(int H, int W, int 
         for (int x = 0; x < nr; ++x)
             for (int y = 0; y < nc; ++y) s += G[rows[x] * Wp + cols[y]];
         gu[(size_t)b * H * W + e] = s;
+    }
+}
+
+// the tangent-linear pass (pde_jacobi_f64_tangent): jac64_fwd_kernel with a second state.  dP is the reflect-padded du
+// (zeros when du is NULL), both rings frozen; interior dP' = the forward's expressions on dP, then
+// + da_i d1(P) + db_j d2(P) with P the step's input (not added at all when src == 0).  LDS: P, Q, dP, dQ.
+__global__ __launch_bounds__(256) void jac64_tangent_kernel(int H, int W, int nt, const double* __restrict__ u,
+                                                            const double* __restrict__ du, const double* __restrict__ a,
+                                                            const double* __restrict__ bc, const double* __restrict__ da,
+                                                            const double* __restrict__ dbc, double* __restrict__ out,
+                                                            double* __restrict__ dout, int src) {
+    extern __shared__ double jsm[];
+    const int Hp = H + 2, Wp = W + 2, PP = Hp * Wp, b = blockIdx.x;
+    double* P = jsm;
+    double* Q = jsm + PP;
+    double* dP = jsm + 2 * PP;
+    double* dQ = jsm + 3 * PP;
+    const double* ub = u + (size_t)b * H * W;
+    const double* dub = du ? du + (size_t)b * H * W : nullptr;
+    for (int e = threadIdx.x; e < PP; e += blockDim.x) {
+        const int i = e / Wp, j = e % Wp;
+        const int o = refl(i - 1, H) * W + refl(j - 1, W);
+        Q[e] = P[e] = ub[o];
+        dQ[e] = dP[e] = dub ? dub[o] : 0.0;
+    }
+    __syncthreads();
+    for (int k = 0; k < nt; ++k) {
+        for (int e = threadIdx.x; e < H * W; e += blockDim.x) {
+            const int i = e / W + 1, j = e % W + 1, q = i * Wp + j;
+            const double in = P[q];
+            const double d1 = (P[q + Wp] - 2.0 * in) + P[q - Wp];
+            const double d2 = (P[q + 1] - 2.0 * in) + P[q - 1];
+            Q[q] = (in + a[i - 1] * d1) + bc[j - 1] * d2;
+            const double din = dP[q];
+            const double dd1 = (dP[q + Wp] - 2.0 * din) + dP[q - Wp];
+            const double dd2 = (dP[q + 1] - 2.0 * din) + dP[q - 1];
+            double dn = (din + a[i - 1] * dd1) + bc[j - 1] * dd2;
+            if (src) dn = (dn + (da ? da[i - 1] : 0.0) * d1) + (dbc ? dbc[j - 1] : 0.0) * d2;
+            dQ[q] = dn;
+        }
+        __syncthreads();
+        double* t = P; P = Q; Q = t;        // the rings are the same in both
+        t = dP; dP = dQ; dQ = t;
+    }
+    for (int e = threadIdx.x; e < H * W; e += blockDim.x) {
+        const int l = (e / W + 1) * Wp + e % W + 1;
+        if (out) out[(size_t)b * H * W + e] = P[l];
+        dout[(size_t)b * H * W + e] = dP[l];
     }
 }
 
@@ -765,6 +860,59 @@ int pde_jacobi_f64_backward_input_states(int32_t B, int32_t H, int32_t W, int32_
     else
         hipLaunchKernelGGL(jac64_bwd_input_kernel<false>, dim3(B), dim3(256), jac64_lds(H, W), st, H, W, nt, gout, a_row, b_col,
                            gu, (const double*)nullptr, em);
+    return check_launch();
+}
+
+}  // extern "C"
+
+// ---- the tangent-linear pass (pdecnn_explicit_tangent.h): (y, dy) from (u, du) and the parameter tangents ---------------
+extern "C" {
+
+size_t pde_explicit5_f64_tangent_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_steps) {
+    if (B <= 0 || B > 65535 || C <= 0 || C > 65535 || H <= 0 || W <= 0 || num_steps < 2) return 0;
+    return 4 * up256((size_t)B * C * H * W * sizeof(double));       // u and du ping-pong through two images each
+}
+
+int pde_explicit5_f64_tangent(int32_t B, int32_t C, int32_t H, int32_t W, const double* u, const double* du,
+                              const double* alpha_base, const double* channel_scaling, const double* d_alpha_base,
+                              const double* d_channel_scaling, double dt, double eps, double max_coeff, double relax,
+                              int32_t num_steps, double* y, double* dy, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    if (B <= 0 || B > 65535 || C <= 0 || C > 65535 || H <= 0 || W <= 0 || num_steps < 1 || !u || !alpha_base ||
+        !channel_scaling || !dy)
+        return PDE_E_BADARG;
+    if (!du && !d_alpha_base && !d_channel_scaling) return PDE_E_BADARG;       // nothing to differentiate: call the forward
+    if (misaligned(8, u, du, alpha_base, channel_scaling, d_alpha_base, d_channel_scaling, y, dy)) return PDE_E_BADARG;
+    const size_t need = pde_explicit5_f64_tangent_workspace_bytes(B, C, H, W, num_steps);
+    if ((need && (!workspace || workspace_bytes < need)) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t ib = up256((size_t)B * C * H * W * sizeof(double));
+    char* ws = static_cast<char*>(workspace);
+    double* img[2] = {need ? reinterpret_cast<double*>(ws) : nullptr, need ? reinterpret_cast<double*>(ws + ib) : nullptr};
+    double* dimg[2] = {need ? reinterpret_cast<double*>(ws + 2 * ib) : nullptr,
+                       need ? reinterpret_cast<double*>(ws + 3 * ib) : nullptr};
+    const int src = (d_alpha_base || d_channel_scaling) ? 1 : 0;
+    const dim3 grid((H * W + 255) / 256, C, B);
+    for (int k = 0; k < num_steps; ++k) {
+        const bool first = k == 0, last = k == num_steps - 1;
+        hipLaunchKernelGGL(expl64_tangent_kernel, grid, dim3(256), 0, st, C, H, W, first ? u : (const double*)img[(k - 1) & 1],
+                           first ? du : (const double*)dimg[(k - 1) & 1], alpha_base, channel_scaling, d_alpha_base,
+                           d_channel_scaling, dt, eps, max_coeff, relax, last ? y : img[k & 1], last ? dy : dimg[k & 1], src);
+    }
+    return check_launch();
+}
+
+int pde_jacobi_f64_tangent(int32_t B, int32_t H, int32_t W, int32_t nt, const double* u, const double* du,
+                           const double* a_row, const double* b_col, const double* d_a_row, const double* d_b_col,
+                           double* y, double* dy, void* stream) {
+    if (!jac64_ok(B, H, W, nt) || !u || !a_row || !b_col || !dy) return PDE_E_BADARG;
+    if (!du && !d_a_row && !d_b_col) return PDE_E_BADARG;                     // nothing to differentiate: call the forward
+    if (misaligned(8, u, du, a_row, b_col, d_a_row, d_b_col, y, dy)) return PDE_E_BADARG;
+    static unsigned long long done = 0;
+    const int rc = ensure_dynamic_lds((const void*)jac64_tangent_kernel, (int)(2 * jac64_lds(kJacMax, kJacMax)), done);
+    if (rc != PDE_OK) return rc;
+    hipLaunchKernelGGL(jac64_tangent_kernel, dim3(B), dim3(256), 2 * jac64_lds(H, W), static_cast<hipStream_t>(stream), H, W,
+                       nt, u, du, a_row, b_col, d_a_row, d_b_col, y, dy, (d_a_row || d_b_col) ? 1 : 0);
     return check_launch();
 }
 

@@ -414,3 +414,111 @@ __global__ void jacobi_tiled_pgrad_kernel(const float* __restrict__ part, float*
         gb[j] = sum;
     }
 }
+
+// ---- tangent-linear pass (pdecnn_explicit_tangent.h: pde_jacobi_io_tangent on planes above 64x64) -----------------------
+// jacobi_tiled_fwd_kernel with a second state: the same tiles, the same halo, the same shrinking region per step.  Four
+// region images (P, Q, dP, dQ) and four coefficient vectors (a, b, da, db) fit one workgroup's LDS at the forward's own
+// kJK steps per launch, so a launch of the tangent pass advances as many steps as one of the forward:
+constexpr int kJTanK = kJK;                                              // time steps per launch of the tangent pass
+constexpr int kJTanFloats = 4 * kJR * kJS + 4 * kJR;                     // P, Q, dP, dQ, a, b, da, db: 130368 B, dynamic
+static_assert(kJTanK == kJK && kJTanFloats * 4 <= 160 * 1024, "one workgroup's LDS");
+// Ring cells of P come from u and those of dP from du (zero when du is NULL) in every launch; interior cells from the
+// fp32 images the launch continues from (fsrc / dfsrc; NULL: the first launch, from u / du).  dst NULL: y is not wanted
+// (last launch only).  src == 0 (both coefficient tangents NULL): the source term is not added at all.
+template <typename IO>
+__global__ __launch_bounds__(256) void jacobi_tiled_tangent_kernel(const IO* __restrict__ u, const IO* __restrict__ du,
+                                                                   const float* __restrict__ fsrc,
+                                                                   const float* __restrict__ dfsrc,
+                                                                   const float* __restrict__ a_row,
+                                                                   const float* __restrict__ b_col,
+                                                                   const float* __restrict__ d_a_row,
+                                                                   const float* __restrict__ d_b_col, void* __restrict__ dst,
+                                                                   void* __restrict__ ddst, int dst_f32, int H, int W,
+                                                                   int nTy, int nTx, int k, int src) {
+    extern __shared__ float smt[];
+    float* P = smt;
+    float* Q = P + kJR * kJS;
+    float* dP = Q + kJR * kJS;
+    float* dQ = dP + kJR * kJS;
+    float* sa = dQ + kJR * kJS;
+    float* sb = sa + kJR;
+    float* sda = sb + kJR;
+    float* sdb = sda + kJR;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    int bid = blockIdx.x;                                  // one division per workgroup, none per cell
+    const int tX = bid % nTx;
+    bid /= nTx;
+    const int tY = bid % nTy;
+    const size_t s = bid / nTy;
+    const JSpan rs = jspan(tY, nTy, H, k), cs = jspan(tX, nTx, W, k);
+    const size_t plane = (size_t)H * W;
+    const IO* ub = u + s * plane;
+    const IO* dub = du ? du + s * plane : nullptr;
+    for (int e = threadIdx.x; e < rs.hi - rs.lo; e += 256) {
+        const int i = rs.lo + e;
+        const bool in = i >= 1 && i <= H;
+        sa[e] = in ? a_row[i - 1] : 0.f;
+        sda[e] = (in && d_a_row) ? d_a_row[i - 1] : 0.f;
+    }
+    for (int e = threadIdx.x; e < cs.hi - cs.lo; e += 256) {
+        const int j = cs.lo + e;
+        const bool in = j >= 1 && j <= W;
+        sb[e] = in ? b_col[j - 1] : 0.f;
+        sdb[e] = (in && d_b_col) ? d_b_col[j - 1] : 0.f;
+    }
+    for (int i = rs.lo + ty; i < rs.hi; i += 8) {
+        const bool ri = i >= 1 && i <= H;
+        const size_t ro = (size_t)reflect_src(i, H) * W;
+        for (int j = cs.lo + tx; j < cs.hi; j += 32) {
+            const size_t off = ro + reflect_src(j, W);
+            const bool in = ri && j >= 1 && j <= W;
+            const float v = (fsrc && in) ? fsrc[s * plane + off] : S1<IO>::ld(ub + off);
+            const float dv = (dfsrc && in) ? dfsrc[s * plane + off] : (dub ? S1<IO>::ld(dub + off) : 0.f);
+            const int l = (i - rs.lo) * kJS + (j - cs.lo);
+            P[l] = v;
+            Q[l] = v;                                      // the rings are never written again: both images hold them
+            dP[l] = dv;
+            dQ[l] = dv;
+        }
+    }
+    __syncthreads();
+    for (int st = 1; st <= k; ++st) {
+        const int r0 = max(rs.lo == 0 ? 0 : rs.lo + st, 1), r1 = min(rs.hi == H + 2 ? H + 2 : rs.hi - st, H + 1);
+        const int c0 = max(cs.lo == 0 ? 0 : cs.lo + st, 1), c1 = min(cs.hi == W + 2 ? W + 2 : cs.hi - st, W + 1);
+        for (int i = r0 + ty; i < r1; i += 8) {
+            const float ai = sa[i - rs.lo], dai = sda[i - rs.lo];
+            const float* p = P + (i - rs.lo) * kJS - cs.lo;
+            float* q = Q + (i - rs.lo) * kJS - cs.lo;
+            const float* dp = dP + (i - rs.lo) * kJS - cs.lo;
+            float* dq = dQ + (i - rs.lo) * kJS - cs.lo;
+            for (int j = c0 + tx; j < c1; j += 32) {
+                const float v = p[j];
+                const float d1 = p[j + kJS] - 2.f * v + p[j - kJS];
+                const float d2 = p[j + 1] - 2.f * v + p[j - 1];
+                q[j] = v + ai * d1 + sb[j - cs.lo] * d2;
+                const float dv = dp[j];
+                const float dd1 = dp[j + kJS] - 2.f * dv + dp[j - kJS];
+                const float dd2 = dp[j + 1] - 2.f * dv + dp[j - 1];
+                float dn = dv + ai * dd1 + sb[j - cs.lo] * dd2;
+                if (src) dn = dn + dai * d1 + sdb[j - cs.lo] * d2;
+                dq[j] = dn;
+            }
+        }
+        __syncthreads();
+        float* t = P; P = Q; Q = t;
+        t = dP; dP = dQ; dQ = t;
+    }
+    const int oi0 = max(rs.olo, 1), oi1 = min(rs.ohi, H + 1), oj0 = max(cs.olo, 1), oj1 = min(cs.ohi, W + 1);
+    for (int i = oi0 + ty; i < oi1; i += 8)
+        for (int j = oj0 + tx; j < oj1; j += 32) {
+            const int l = (i - rs.lo) * kJS + (j - cs.lo);
+            const size_t o = s * plane + (size_t)(i - 1) * W + (j - 1);
+            if (dst_f32) {
+                static_cast<float*>(dst)[o] = P[l];
+                static_cast<float*>(ddst)[o] = dP[l];
+            } else {
+                if (dst) S1<IO>::st(static_cast<IO*>(dst) + o, P[l]);
+                S1<IO>::st(static_cast<IO*>(ddst) + o, dP[l]);
+            }
+        }
+}

@@ -21,7 +21,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib as L
 
 __all__ = ["Sweep", "adi_schedule", "adi_diffuse", "adi_diffuse_states", "adi_diffuse_mixed", "adi_diffuse_small", "adi_diffuse_small_states", "adi_small_supported", "adi_diffuse_multi", "gate_combine", "plan_checkpoints", "kappa_max_async", "channel_mix", "skip_blend", "explicit5_step", "jacobi_diffuse", "explicit5_states", "jacobi_diffuse_states",
-           "linear_adjoint", "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
+           "explicit5_tangent", "jacobi_diffuse_tangent", "linear_adjoint", "timing_enable", "timing_read", "Schedule", "sym_layer", "sym_layer_supported",
            "sym_layer_f16_supported", "sym_layer_bf16_supported", "sym_k16"]
 
 
@@ -511,8 +511,9 @@ _NO_PARAM_TANGENT = ("the parameter gradients of a PDE layer's first backward ar
 # A node's ``jvp`` needs tensors its backward may not keep (the frozen route keeps neither y nor u), and the C++ nodes of
 # csrc/host_ext.cpp cannot carry one.  So the public functions ask ``_has_tangent`` — one module attribute read outside a
 # dual level — and only then go through ``_apply_dual``, which tells the ctypes node's forward to keep what its jvp reads.
-_NO_TRAJ_JVP = ("forward-mode AD through a trajectory call (adi_diffuse_states) is not implemented: the tangent kernel "
-                "emits no intermediate states; differentiate the plain call, or chain one call per emitted state")
+_NO_TRAJ_JVP = ("forward-mode AD through a trajectory call (adi_diffuse_states, explicit5_states, jacobi_diffuse_states) is "
+                "not implemented: the tangent kernels emit no intermediate states; differentiate the plain call, or chain "
+                "one call per emitted state")
 _NO_JVP_ROUTE = ("this node was not called through the library's public functions under forward_ad.dual_level(): it kept "
                  "nothing for a jvp")
 _dual = threading.local()
@@ -2037,6 +2038,8 @@ def gate_combine(ys, gates, weights):
 # last, and the result is ONE tensor (K', ...) whose last slice is the library's ``out``.  ``f64`` picks the
 # pde_*_f64_* entry points: every tensor in double, no tensor-type argument.
 class _Explicit5Fn(torch.autograd.Function):
+    dual = None                  # set on the ctx by a forward that _apply_dual marked: (alpha_base, channel_scaling) for the jvp
+
     @staticmethod
     def forward(ctx, u, alpha_base, channel_scaling, dt, eps, max_coeff, relax, num_steps, steps, bits, f64):
         lib = L.load()
@@ -2073,7 +2076,28 @@ class _Explicit5Fn(torch.autograd.Function):
         ctx.cfg = (dt, eps, max_coeff, relax, num_steps, steps, bits, f64)
         ctx.p_dtypes = (alpha_base.dtype, channel_scaling.dtype)
         ctx.primal_args = ((alpha_base, channel_scaling), ctx.cfg)
+        if getattr(_dual, "on", False) and _take_dual(ctx):     # a tangent came in (explicit5_step decided): what the jvp reads
+            ctx.save_for_forward(u, a, s)
+            ctx.dual = (alpha_base.detach(), channel_scaling.detach())
         return res
+
+    @staticmethod
+    def jvp(ctx, ut, dat, dst, *_):
+        """Forward mode.  The layer is linear in ``u``: with no parameter tangent the output tangent is the layer's own
+        forward at ``ut``.  Otherwise one ``pde_explicit5[_f64]_tangent`` call."""
+        dt, eps, max_coeff, relax, num_steps, steps, _, f64 = ctx.cfg
+        if steps is not None:
+            raise NotImplementedError(_NO_TRAJ_JVP)
+        if ctx.dual is None:
+            raise NotImplementedError(_NO_JVP_ROUTE)
+        u, a, s = ctx.saved_tensors
+        if dat is None and dst is None:
+            if ut is None:
+                return torch.zeros_like(u)
+            return explicit5_step(ut.to(u.dtype), *ctx.dual, dt, eps, max_coeff, relax, num_steps).to(u.dtype)
+        du = None if ut is None else _aligned(_kernel_input(ut.to(u.dtype), f64, align=1), ctx.align)
+        da, ds = (None if t is None else _kernel_param(t, a.dtype) for t in (dat, dst))
+        return _explicit5_tangent_call(L.load(), f64, u, du, a, s, da, ds, (dt, eps, max_coeff, relax, num_steps), False)[1]
 
     @staticmethod
     def backward(ctx, g):
@@ -2122,13 +2146,70 @@ def explicit5_step(u, alpha_base, channel_scaling, dt=0.01, eps=1e-6, max_coeff=
     f64 = _is_f64(u, alpha_base, channel_scaling)
     if not f64:
         u = _io_in(u, alpha_base, channel_scaling)
+    if _fwad._current_level >= 0 and _has_tangent(u, alpha_base, channel_scaling):
+        # forward mode: the node is told to keep what its jvp reads
+        return _apply_dual(_Explicit5Fn, u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff),
+                           float(relax), int(num_steps), None, None, f64)
     return _Explicit5Fn.apply(u, alpha_base, channel_scaling, float(dt), float(eps), float(max_coeff), float(relax),
                               int(num_steps), None, None, f64)
+
+
+def _explicit5_tangent_call(lib, f64, u, du, a, s, da, ds, cfg, want_y):
+    """One ``pde_explicit5[_f64]_tangent`` call (include/pdecnn_explicit_tangent.h) on kernel-ready tensors: (y or None, dy)."""
+    dt, eps, max_coeff, relax, num_steps = cfg
+    fam = "pde_explicit5_f64_" if f64 else "pde_explicit5_"
+    B, Cc, H, W = u.shape
+    io = () if f64 else (_io_dtype(u),)
+    y = torch.empty_like(u) if want_y else None
+    dy = torch.empty_like(u)
+    n = getattr(lib, fam + "tangent_workspace_bytes")(B, Cc, H, W, *io, num_steps)
+    ws = _workspace(n, u.device) if n else None
+    with torch.cuda.device(u.device):
+        L.check(getattr(lib, fam + "tangent")(B, Cc, H, W, *io, _ptr(u), _ptr(du), _ptr(a), _ptr(s), _ptr(da), _ptr(ds), dt,
+                                              eps, max_coeff, relax, num_steps, _ptr(y), _ptr(dy), _ptr(ws), n, _stream()),
+                fam + "tangent")
+    return y, dy
+
+
+def explicit5_tangent(u, alpha_base, channel_scaling, *, du=None, d_alpha_base=None, d_channel_scaling=None, dt=0.01, eps=1e-6,
+                      max_coeff=0.15, relax=0.1, num_steps=1):
+    """``(y, ydot)``: ``explicit5_step`` and its directional derivative along the input tangent ``du`` and the tangents of
+    ``alpha_base`` and ``channel_scaling`` (None: zero; at least one must be given), the primal and the tangent state
+    advanced together (pde_explicit5[_f64]_tangent: one launch for 64x64, 32x32 and 16x16 planes, one per step otherwise).
+    Plain tensors, no autograd graph.  fp32, bf16, the float16 route and float64 by the rules of ``explicit5_step``; ``y``
+    is bit for bit its result.  Where ``alpha_base`` sits on a bound of the clamp the derivative passes, as torch's does."""
+    dparams = (d_alpha_base, d_channel_scaling)
+    if du is None and all(t is None for t in dparams):
+        raise ValueError("explicit5_tangent needs du or a parameter tangent (use explicit5_step for the value alone)")
+    if u.dim() != 4:
+        raise L.PdeError(f"expected (B,C,H,W), got {tuple(u.shape)}")
+    if du is not None and du.shape != u.shape:
+        raise L.PdeError(f"du of shape {tuple(du.shape)} does not match u {tuple(u.shape)}")
+    if num_steps < 1:
+        raise ValueError(f"num_steps must be at least 1, got {num_steps}")
+    f64 = _is_f64(u, alpha_base, channel_scaling)
+    with torch.no_grad():
+        if not f64:
+            u = _io_in(u, alpha_base, channel_scaling)
+        _require_cuda(u, alpha_base, channel_scaling, du, *dparams)
+        if u.shape[0] == 0:
+            y = u.to(torch.float64) if f64 else u.clone()
+            return y, torch.zeros_like(y)
+        kt = torch.float64 if f64 else torch.float32
+        u = _kernel_input(u.detach(), f64, align=1)
+        align = 1 if (f64 or u.shape[3] % 4) else 4 * u.element_size()
+        u = _aligned(u, align)
+        du = None if du is None else _aligned(_kernel_input(du.detach().to(u.dtype), f64, align=1), align)
+        a, s = _kernel_param(alpha_base, kt), _kernel_param(channel_scaling, kt)
+        da, ds = (None if t is None else _kernel_param(t, kt) for t in dparams)
+        return _explicit5_tangent_call(L.load(), f64, u, du, a, s, da, ds,
+                                       (float(dt), float(eps), float(max_coeff), float(relax), int(num_steps)), True)
 
 
 class _JacobiFn(torch.autograd.Function):
     """fp32 tensors, fp16 ones on the float16 route (pde_jacobi_io_*: the same kernels with fp16 I/O; anything else is
     widened to fp32), or float64 (pde_jacobi_f64_*)."""
+    dual = None                  # set on the ctx by a forward that _apply_dual marked: (a_row, b_col) for the jvp
 
     @staticmethod
     def forward(ctx, u, a_row, b_col, nt, steps, bits, f64):
@@ -2161,7 +2242,28 @@ class _JacobiFn(torch.autograd.Function):
         ctx.cfg = (nt, steps, bits, f64)
         ctx.p_dtypes = (a_row.dtype, b_col.dtype)
         ctx.primal_args = ((a_row, b_col), ctx.cfg)
+        if getattr(_dual, "on", False) and _take_dual(ctx):     # a tangent came in (jacobi_diffuse decided): what the jvp reads
+            ctx.save_for_forward(u, a, b)
+            ctx.dual = (a_row.detach(), b_col.detach())
         return res
+
+    @staticmethod
+    def jvp(ctx, ut, dat, dbt, *_):
+        """Forward mode.  The layer is linear in ``u``: with no coefficient tangent the output tangent is the layer's own
+        forward at ``ut``.  Otherwise one ``pde_jacobi_io_tangent`` / ``pde_jacobi_f64_tangent`` call."""
+        nt, steps, _, f64 = ctx.cfg
+        if steps is not None:
+            raise NotImplementedError(_NO_TRAJ_JVP)
+        if ctx.dual is None:
+            raise NotImplementedError(_NO_JVP_ROUTE)
+        u, a, b = ctx.saved_tensors
+        if dat is None and dbt is None:
+            if ut is None:
+                return torch.zeros_like(u)
+            return jacobi_diffuse(ut.to(u.dtype), *ctx.dual, nt).to(u.dtype)
+        du = None if ut is None else _kernel_input(ut.to(u.dtype), f64, (torch.float32, torch.float16), align=1)
+        da, db = (None if t is None else _kernel_param(t, a.dtype) for t in (dat, dbt))
+        return _jacobi_tangent_call(L.load(), f64, u, du, a, b, da, db, nt, False)[1]
 
     @staticmethod
     def backward(ctx, g):
@@ -2214,7 +2316,60 @@ def jacobi_diffuse(u, a_row, b_col, nt: int):
     f64 = _is_f64(u, a_row, b_col)
     if not f64:
         u = _io_in(u, a_row, b_col)
+    if _fwad._current_level >= 0 and _has_tangent(u, a_row, b_col):
+        # forward mode: the node is told to keep what its jvp reads
+        return _apply_dual(_JacobiFn, u, a_row, b_col, int(nt), None, None, f64)
     return _JacobiFn.apply(u, a_row, b_col, int(nt), None, None, f64)
+
+
+def _jacobi_tangent_call(lib, f64, u, du, a, b, da, db, nt, want_y):
+    """One ``pde_jacobi_io_tangent`` / ``pde_jacobi_f64_tangent`` call (include/pdecnn_explicit_tangent.h) on kernel-ready
+    tensors: (y or None, dy)."""
+    B, H, W = u.shape
+    y = torch.empty_like(u) if want_y else None
+    dy = torch.empty_like(u)
+    with torch.cuda.device(u.device):
+        if f64:
+            L.check(lib.pde_jacobi_f64_tangent(B, H, W, nt, _ptr(u), _ptr(du), _ptr(a), _ptr(b), _ptr(da), _ptr(db), _ptr(y),
+                                               _ptr(dy), _stream()), "pde_jacobi_f64_tangent")
+        else:
+            io = _io_dtype(u)
+            # a tiled plane with more steps than one launch takes: the launches chain through a workspace
+            n = lib.pde_jacobi_io_tangent_workspace_bytes(B, H, W, nt, io)
+            ws = _workspace(n, u.device) if n else None
+            L.check(lib.pde_jacobi_io_tangent(B, H, W, nt, io, _ptr(u), _ptr(du), _ptr(a), _ptr(b), _ptr(da), _ptr(db),
+                                              _ptr(y), _ptr(dy), _ptr(ws), n, _stream()), "pde_jacobi_io_tangent")
+    return y, dy
+
+
+def jacobi_diffuse_tangent(u, a_row, b_col, nt: int, *, du=None, d_a_row=None, d_b_col=None):
+    """``(y, ydot)``: ``jacobi_diffuse`` and its directional derivative along the input tangent ``du`` and the tangents of
+    ``a_row`` and ``b_col`` (None: zero; at least one must be given), the padded plane and its tangent advanced together
+    (pde_jacobi_io_tangent: one workgroup per sample up to 64x64, the tiled kernel above; pde_jacobi_f64_tangent).  Plain
+    tensors, no autograd graph.  fp32, the float16 route and float64 by the rules of ``jacobi_diffuse``; ``y`` is bit for
+    bit its result."""
+    dparams = (d_a_row, d_b_col)
+    if du is None and all(t is None for t in dparams):
+        raise ValueError("jacobi_diffuse_tangent needs du or a coefficient tangent (use jacobi_diffuse for the value alone)")
+    if u.dim() != 3:
+        raise L.PdeError(f"expected (B,H,W), got {tuple(u.shape)}")
+    if du is not None and du.shape != u.shape:
+        raise L.PdeError(f"du of shape {tuple(du.shape)} does not match u {tuple(u.shape)}")
+    f64 = _is_f64(u, a_row, b_col)
+    with torch.no_grad():
+        if not f64:
+            u = _io_in(u, a_row, b_col)
+        _require_cuda(u, a_row, b_col, du, *dparams)
+        if u.shape[0] == 0:
+            y = u.to(torch.float64) if f64 else u.clone()
+            return y, torch.zeros_like(y)
+        kt = torch.float64 if f64 else torch.float32
+        io_types = (torch.float32, torch.float16)
+        u = _kernel_input(u.detach(), f64, io_types, align=1)
+        du = None if du is None else _kernel_input(du.detach().to(u.dtype), f64, io_types, align=1)
+        a, b = _kernel_param(a_row, kt), _kernel_param(b_col, kt)
+        da, db = (None if t is None else _kernel_param(t, kt) for t in dparams)
+        return _jacobi_tangent_call(L.load(), f64, u, du, a, b, da, db, int(nt), True)
 
 
 # --------------------------------------------------------------------------- trajectories of the explicit layers

@@ -590,10 +590,37 @@ def layer_jvp(layer, u, du=None, dparams=None):
     tangent-linear launch per group of sweeps (pde_adi*_tangent), with ``du`` alone the layer's usual forward at ``du`` —
     and a channel operator or skip blend through functional.channel_mix / functional.skip_blend, step by step.  No autograd
     graph is built.  Every implicit class (Mnist, Fashion, Svhn, Enhanced, Learnable); ``ImprovedDiffusionLayer`` and
-    ``PDELayer`` have no tangent kernels: TypeError."""
-    import torch.autograd.forward_ad as fwad
+    ``PDELayer`` are served by ``explicit_layer_jvp``: TypeError here."""
     if not isinstance(layer, _AdiBase):
-        raise TypeError(f"{type(layer).__name__} has no forward-mode derivative (the implicit diffusion layers have one)")
+        hint = "explicit_layer_jvp serves this class" if isinstance(layer, (ImprovedDiffusionLayer, PDELayer)) else \
+            "the implicit diffusion layers have one"
+        raise TypeError(f"{type(layer).__name__} has no forward-mode derivative here ({hint})")
+    return _layer_jvp(layer, u, du, dparams)
+
+
+def explicit_layer_jvp(layer, u, du=None, dparams=None):
+    """``layer_jvp`` for the two explicit layers: ``(y, ydot)`` with ``y = layer(u)`` and ``ydot`` its directional derivative
+    along ``du`` and the parameter tangents ``dparams`` (names of ``layer.named_parameters()``; a missing name, and ``du``
+    None, is a zero tangent; an unknown name is a KeyError, a wrong shape a ValueError).
+
+    The layer's own ``forward`` runs once under ``torch.autograd.forward_ad.dual_level()``, so the routing is
+    ``forward``'s (fp32, bf16 where it takes it, ``model.half()``, float64).  With a parameter tangent the time loop is one
+    tangent-linear call (pde_explicit5_tangent / pde_jacobi_io_tangent and their float64 forms: the primal and the tangent
+    state advanced together), with ``du`` alone the layer's usual forward at ``du``.  No autograd graph is built.
+
+    * ``ImprovedDiffusionLayer``: ``alpha_base`` and ``channel_scaling``; ``beta_base`` is unused by the layer, so a tangent
+      on it contributes exactly zero.
+    * ``PDELayer``: its six scalars reach ``a_row`` / ``b_col`` through torch's own forward AD of ``alpha()`` / ``beta()``.
+
+    Any other class: TypeError (``layer_jvp`` serves the implicit ones)."""
+    if not isinstance(layer, (ImprovedDiffusionLayer, PDELayer)):
+        raise TypeError(f"{type(layer).__name__} is not an explicit PDE layer (layer_jvp serves the implicit ones)")
+    return _layer_jvp(layer, u, du, dparams)
+
+
+def _layer_jvp(layer, u, du, dparams):
+    """The body ``layer_jvp`` and ``explicit_layer_jvp`` share: ``functional_call`` with dual parameters under a dual level."""
+    import torch.autograd.forward_ad as fwad
     named = dict(layer.named_parameters())
     dparams = dict(dparams or {})
     unknown = sorted(set(dparams) - set(named))

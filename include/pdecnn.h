@@ -1015,7 +1015,9 @@ int pde_adi_rect_f64_backward_input_states(const PdeAdiRectDescF64* d, const dou
 /* The same for the one-launch C <= 4 layers (the K1 calls above and their shared-input groups): declared in
  * pdecnn_small_input.h, which this header includes below; for the layers with a channel operator above C = 4 (the
  * pde_adi_mixed_* calls, pde_channel_mix_* and pde_skip_blend_*) in pdecnn_mixed_input.h, included below as well; for
- * the explicit 5-point and the Jacobi layers (pde_explicit5_*, pde_jacobi_*) in pdecnn_explicit_input.h, the third. */
+ * the explicit 5-point and the Jacobi layers (pde_explicit5_*, pde_jacobi_*) in pdecnn_explicit_input.h, the third.
+ * The tangent-linear (forward-mode) passes: pdecnn_tangent.h for the implicit families, pdecnn_explicit_tangent.h for the
+ * explicit 5-point and the Jacobi layers. */
 
 /* ---- utilities ------------------------------------------------------------------------- */
 
@@ -1031,6 +1033,7 @@ const char* pde_version(void);
 #include "pdecnn_mixed_input.h"
 #include "pdecnn_explicit_input.h"
 #include "pdecnn_tangent.h"
+#include "pdecnn_explicit_tangent.h"
 
 #ifdef __cplusplus
 }
