@@ -349,6 +349,13 @@ SIGNATURES_EXPLICIT_TANGENT = {
     "pde_jacobi_f64_tangent": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+#: include/pdecnn_tangent_fused.h (included by pdecnn.h): the tangent-linear pass of the square family on the fused
+#: two-sided solver (N = 8 .. 32) — the arguments of pde_adi_tangent
+SIGNATURES_TANGENT_FUSED = {
+    "pde_adi_tangent_fused_workspace_bytes": (_sz, [_D]),
+    "pde_adi_tangent_fused": (C.c_int, [_D, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -364,7 +371,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_SMALL_INPUT.items()) +
                               list(SIGNATURES_MIXED_INPUT.items()) + list(SIGNATURES_EXPLICIT_INPUT.items()) +
-                              list(SIGNATURES_TANGENT.items()) + list(SIGNATURES_EXPLICIT_TANGENT.items())):
+                              list(SIGNATURES_TANGENT.items()) + list(SIGNATURES_EXPLICIT_TANGENT.items()) +
+                              list(SIGNATURES_TANGENT_FUSED.items())):
         fn = getattr(lib, name)         # AttributeError if the library lacks a declared symbol
         fn.restype, fn.argtypes = res, args
     _lib = lib
@@ -410,6 +418,19 @@ def bwd_input_enabled() -> bool:
     if _bwd_input is None:
         _bwd_input = os.environ.get("PDE_BWD_INPUT", "1") != "0"
     return _bwd_input
+
+
+_tangent_fused = None
+
+
+def tangent_fused_enabled() -> bool:
+    """Whether a coefficient or input tangent of the square family runs on the fused two-sided solver at the line lengths
+    that have one (pde_adi_tangent_fused, N = 8 .. 32).  PDE_TANGENT_FUSED=0 restores the any-size route (pde_adi_tangent)
+    there, so that both can be compared in one build."""
+    global _tangent_fused
+    if _tangent_fused is None:
+        _tangent_fused = os.environ.get("PDE_TANGENT_FUSED", "1") != "0"
+    return _tangent_fused
 
 
 def check(rc, what):

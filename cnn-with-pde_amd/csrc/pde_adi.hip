@@ -39,9 +39,12 @@
 //     FOUR planes per lane so that each coefficient read serves four planes, and the planes of a lane are
 //     written as one value (Pack<J>) so that the packed form stays one flag away (make PACK=1: 4 % slower).
 #include "pde_adi_dev.h"
+#include "pde_adi_factor.h"
 #include "pde_adi_small.h"
 #include "pde_adi_wide.h"
 #include "pde_adi_launch.h"
+#include "pde_adi_tangent_dev.h"
+#include "pde_adi_tangent_launch.h"
 #include "pde_adi_gen.h"
 #include "pde_adi_asm.h"
 
@@ -76,53 +79,6 @@ namespace {
 // ------------------------------------------------------------------------------------
 // factorisation kernel: one thread per (sweep, channel, line)
 // ------------------------------------------------------------------------------------
-struct FactorArgs {
-    SweepTab* tab;
-    int* varying;           // [C] 1 when a clamp mask of the channel differs between sweeps; followed in memory by the
-                            // per-(sweep, channel) partials this kernel writes: int dpart[S][C], float kpart[S][C]
-    float t_first[2];       // time of the earliest sweep of each axis
-    const float* ab;
-    const float* bb;
-    const float* as;
-    const float* bs;
-    float* coef;            // [S][C][kRecAll]
-    float* wide;            // optional [S][C][kWideRec]: lane-major copy of the records (pde_common.h), may be null
-    float* kmax;            // optional [S] (atomic max of coeff), may be null
-    int C, N, S;
-    int win;                // sweeps per launch window: tab[w] describes sweeps w*win .. w*win+win-1 as ONE launch
-    int smooth3, has_max;
-    float cmax, eps;
-    PdeSweep sweep[PDE_MAX_SWEEPS];
-};
-
-// One thread per (sweep, channel, HALF line): the two-sided factorisation makes the halves of a line
-// independent up to the junction factor (one lane exchange), so a wave is 32 lines x 2 halves of one
-// channel — the sweep kernels' own layout — and each thread's serial chain (divisions!) is N/2 long.
-// A thread writes its half of every image row as 16-byte stores.  No LDS.  The row-layout images
-// (KAPX, MASKX) of a y sweep are NOT transposed through memory: thread (h, hf) recomputes the
-// coefficients of its half of row h directly from the parameters (three rows for the smoothed variants).
-template <int N>
-__device__ __forceinline__ void store_half_row(float* row, int hf, const float (&v)[N / 2]) {
-    // image row = [16 floats: half seen from the low end][16: half seen from the high end][4 pad]
-    float h[kHalfPad];
-#pragma unroll
-    for (int k = 0; k < kHalfPad; ++k) h[k] = 0.f;
-#pragma unroll
-    for (int k = 0; k < N / 2; ++k) h[k] = v[k];
-    float4* dst = reinterpret_cast<float4*>(row + hf * kHalfPad);
-#pragma unroll
-    for (int q = 0; q < kHalfPad / 4; ++q) dst[q] = make_float4(h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
-    if (hf) *reinterpret_cast<float4*>(row + 2 * kHalfPad) = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-__device__ __forceinline__ float clamp_theta(float th, const FactorArgs& a, bool& pass) {
-    pass = (th >= a.eps) && (!a.has_max || th <= a.cmax);                  // clamp passes the gradient
-    th = fmaxf(th, a.eps);
-    if (a.has_max) th = fminf(th, a.cmax);
-    return th;
-}
-
-constexpr int kFacLd = PDE_MAX_N + 1;     // LDS row stride of the staged parameter planes
 // ints reserved for the per-channel flags in front of the per-(sweep, channel) partials (64-int granules)
 __host__ __device__ inline int flag_ints(int C) { return (C + 63) / 64 * 64; }
 
@@ -2057,6 +2013,67 @@ int pde_timing_read(double* fwd_ms_sum, int64_t* fwd_launches, double* bwd_ms_su
     if (bwd_ms_sum) *bwd_ms_sum = timing().bwd_ms;
     if (bwd_launches) *bwd_launches = timing().bwd_n;
     return PDE_OK;
+}
+
+// ---- the tangent-linear pass on the fused two-sided solver (include/pdecnn_tangent_fused.h) ----
+static size_t tangent_fused_dco_bytes(const PdeAdiDesc* d) {
+    return align_up((size_t)d->num_sweeps * d->C * kDcoStride * sizeof(float), 256);
+}
+
+size_t pde_adi_tangent_fused_workspace_bytes(const PdeAdiDesc* d) {
+    if (check_desc(d) != PDE_OK) return 0;
+    return coef_bytes(d) + tab_bytes() + flag_bytes(d) + tangent_fused_dco_bytes(d);
+}
+
+int pde_adi_tangent_fused(const PdeAdiDesc* d, const void* u, const void* du, const float* alpha_base,
+                          const float* beta_base, const float* alpha_slope, const float* beta_slope,
+                          const float* d_alpha_base, const float* d_beta_base, const float* d_alpha_slope,
+                          const float* d_beta_slope, void* y, void* dy, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    int rc = check_desc(d);
+    if (rc != PDE_OK) return rc;
+    if (!u || !dy || !alpha_base || !beta_base || !alpha_slope || !beta_slope || !workspace) return PDE_E_BADARG;
+    const bool par = d_alpha_base || d_beta_base || d_alpha_slope || d_beta_slope;
+    if (!du && !par) return PDE_E_BADARG;
+    if (misaligned(kVecAlign, u, du, y, dy) ||
+        misaligned(kVecAlign, alpha_base, beta_base, alpha_slope, beta_slope, d_alpha_base, d_beta_base, d_alpha_slope,
+                   d_beta_slope))
+        return PDE_E_BADARG;
+    if (workspace_bytes < pde_adi_tangent_fused_workspace_bytes(d) || ((uintptr_t)workspace & 15)) return PDE_E_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* coef = reinterpret_cast<float*>(ws);           ws += coef_bytes(d);
+    SweepTab* tab = reinterpret_cast<SweepTab*>(ws);      ws += tab_bytes();
+    ws += flag_bytes(d);                                  // (the forward's channel flags: nothing here reads them, so they
+    float* dco = reinterpret_cast<float*>(ws);            //  are not computed and adi_flags_kernel is not launched)
+    rc = launch_factor(d, alpha_base, beta_base, alpha_slope, beta_slope, coef, tab, nullptr, nullptr, st);
+    if (rc != PDE_OK) return rc;
+    if (par) {
+        FactorTangentArgs fa;
+        fill_factor_args(fa.f, d, alpha_base, beta_base, alpha_slope, beta_slope);
+        fa.dab = d_alpha_base; fa.dbb = d_beta_base; fa.das = d_alpha_slope; fa.dbs = d_beta_slope;
+        fa.dco = dco;
+        const int grid = d->num_sweeps * ((d->C + 1) / 2);
+        switch (d->N) {
+#define PDE_CASE(NN) case NN: rc = adi_launch_factor_tangent_##NN(&fa, grid, st); break;
+            PDE_N_LIST
+#undef PDE_CASE
+            default: return PDE_E_UNSUPPORTED_N;
+        }
+        if (rc != PDE_OK) return rc;
+    }
+    TangentArgs ta{};
+    ta.u = u; ta.du = du; ta.y = y; ta.dy = dy; ta.coef = coef; ta.dco = dco; ta.tab = tab;
+    ta.B = d->B; ta.C = d->C; ta.S = d->num_sweeps;
+    ta.G = groups_per_channel(d, kWaves * kJTan, 16 / kWaves);
+    ta.xcd_map = use_xcd_map(d);
+    const size_t lds = (size_t)(kRing * kRecFwdPad + kWaves * kImage + (par ? kRing * kDcoStride : 0)) * sizeof(float);
+    switch (d->N) {
+#define PDE_CASE(NN) case NN: return adi_launch_tangent_##NN(d->io_dtype, par ? 1 : 0, &ta, ta.G * d->C, lds, st);
+        PDE_N_LIST
+#undef PDE_CASE
+    }
+    return PDE_E_UNSUPPORTED_N;
 }
 
 const char* pde_version(void) { return "pdecnn-hip 0.4 (gfx950)"; }

@@ -767,7 +767,8 @@ class _AdiFn(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, ut, dab, dbb, das, dbs, *_):
         """Forward mode.  The layer is linear in ``u``: with no parameter tangent the output tangent is the layer's own
-        forward at ``ut`` (``adi_diffuse``, the fused kernels at N <= 32).  Otherwise one ``*_tangent`` call."""
+        forward at ``ut`` (``adi_diffuse``, the fused kernels at N <= 32).  Otherwise one ``*_tangent`` call through
+        ``_tangent_call``: the fused tangent kernel at the fused sizes of the square family, the any-size kernels elsewhere."""
         d, fam, _, ebits = ctx.cfg
         if ebits is not None:
             raise NotImplementedError(_NO_TRAJ_JVP)
@@ -1443,13 +1444,25 @@ def adi_diffuse_states(u, alpha_base, beta_base, alpha_time_coeff, beta_time_coe
 
 
 def _tangent_call(lib, fam, d, u, du, p, dp, want_y):
-    """One ``*_tangent`` call of family ``fam`` (include/pdecnn_tangent.h) on kernel-ready tensors: (y or None, dy)."""
+    """One ``*_tangent`` call of family ``fam`` (include/pdecnn_tangent.h) on kernel-ready tensors: (y or None, dy).
+    The square fp32-parameter family at a line length that has fused kernels (N = 8 .. 32) takes
+    ``pde_adi_tangent_fused`` (include/pdecnn_tangent_fused.h) instead, whose kernels read 16 bytes wide: a misaligned
+    view is copied first.  ``PDE_TANGENT_FUSED=0`` keeps every size on the any-size kernels."""
+    name = fam + "tangent"
+    if fam == "pde_adi_" and L.tangent_fused_enabled():
+        nbytes = lib.pde_adi_tangent_fused_workspace_bytes(C.byref(d))
+        if nbytes > 0:
+            name = "pde_adi_tangent_fused"
+            u, du = _aligned(u), _aligned(du)
+            p, dp = [_aligned(t) for t in p], [_aligned(t) for t in dp]
+    if name == fam + "tangent":
+        nbytes = getattr(lib, fam + "tangent_workspace_bytes")(C.byref(d))
     y = torch.empty_like(u) if want_y else None
     dy = torch.empty_like(u)
-    ws = _workspace(getattr(lib, fam + "tangent_workspace_bytes")(C.byref(d)), u.device)
+    ws = _workspace(nbytes, u.device)
     with torch.cuda.device(u.device):
-        L.check(getattr(lib, fam + "tangent")(C.byref(d), _ptr(u), _ptr(du), *[_ptr(t) for t in p], *[_ptr(t) for t in dp],
-                                              _ptr(y), _ptr(dy), _ptr(ws), ws.numel(), _stream()), fam + "tangent")
+        L.check(getattr(lib, name)(C.byref(d), _ptr(u), _ptr(du), *[_ptr(t) for t in p], *[_ptr(t) for t in dp],
+                                   _ptr(y), _ptr(dy), _ptr(ws), ws.numel(), _stream()), name)
     return y, dy
 
 
@@ -1459,8 +1472,10 @@ def adi_diffuse_tangent(u, alpha_base, beta_base, alpha_time_coeff, beta_time_co
     """``(y, ydot)``: ``adi_diffuse`` and its directional derivative along the input tangent ``du`` and the four parameter
     tangents (None: zero; at least one must be given), in one pass of the tangent-linear kernel (pde_adi*_tangent).  Plain
     tensors, no autograd graph.  Squares and rectangles up to 128, fp32 / bf16 / fp16 tensors and float64 by the rules of
-    ``adi_diffuse``; every size runs on the any-size kernels.  At a kink of the clamp the one-sided derivative of the
-    forward's own mask is taken."""
+    ``adi_diffuse``.  Squares of N = 8, 12, ..., 32 that are not float64 run on the fused two-sided solver
+    (pde_adi_tangent_fused: ``y`` is ``adi_diffuse``'s bit for bit); every other size, rectangles and float64 on the
+    any-size kernels, and ``PDE_TANGENT_FUSED=0`` sends the fused sizes there too.  At a kink of the clamp the one-sided
+    derivative of the forward's own mask is taken."""
     params = (alpha_base, beta_base, alpha_time_coeff, beta_time_coeff)
     dparams = (d_alpha_base, d_beta_base, d_alpha_time_coeff, d_beta_time_coeff)
     if du is None and all(t is None for t in dparams):

@@ -587,7 +587,8 @@ def layer_jvp(layer, u, du=None, dparams=None):
     The layer's own ``forward`` runs once under ``torch.autograd.forward_ad.dual_level()`` (``torch.func.functional_call``
     with dual parameters), so the routing is ``forward``'s: fp32, bf16, ``model.half()``, float64, squares and rectangles,
     launch groups beyond 32 steps.  The sweeps go through functional.adi_diffuse — with a coefficient tangent one
-    tangent-linear launch per group of sweeps (pde_adi*_tangent), with ``du`` alone the layer's usual forward at ``du`` —
+    tangent-linear launch per group of sweeps (pde_adi_tangent_fused on square planes of N = 8 .. 32 that are not float64,
+    pde_adi*_tangent on the any-size kernels elsewhere), with ``du`` alone the layer's usual forward at ``du`` —
     and a channel operator or skip blend through functional.channel_mix / functional.skip_blend, step by step.  No autograd
     graph is built.  Every implicit class (Mnist, Fashion, Svhn, Enhanced, Learnable); ``ImprovedDiffusionLayer`` and
     ``PDELayer`` are served by ``explicit_layer_jvp``: TypeError here."""

@@ -1017,7 +1017,7 @@ int pde_adi_rect_f64_backward_input_states(const PdeAdiRectDescF64* d, const dou
  * pde_adi_mixed_* calls, pde_channel_mix_* and pde_skip_blend_*) in pdecnn_mixed_input.h, included below as well; for
  * the explicit 5-point and the Jacobi layers (pde_explicit5_*, pde_jacobi_*) in pdecnn_explicit_input.h, the third.
  * The tangent-linear (forward-mode) passes: pdecnn_tangent.h for the implicit families, pdecnn_explicit_tangent.h for the
- * explicit 5-point and the Jacobi layers. */
+ * explicit 5-point and the Jacobi layers, pdecnn_tangent_fused.h for pde_adi_* on the fused solver at N = 8 .. 32. */
 
 /* ---- utilities ------------------------------------------------------------------------- */
 
@@ -1034,6 +1034,7 @@ const char* pde_version(void);
 #include "pdecnn_explicit_input.h"
 #include "pdecnn_tangent.h"
 #include "pdecnn_explicit_tangent.h"
+#include "pdecnn_tangent_fused.h"
 
 #ifdef __cplusplus
 }

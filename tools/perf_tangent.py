@@ -7,6 +7,9 @@
     tangent_du        y and ydot with du alone (no source term, no factor-tangent launch)
     forward_fused     at fused line lengths (N <= 32): the plain forward, which runs the two-lane register kernels
 
+At the fused line lengths ``tangent`` and ``tangent_du`` take the default route, which is pde_adi_tangent_fused there; run with
+PDE_TANGENT_FUSED=0 for the any-size tangent kernels this tool was written for (perf_tangent_fused.py times both routes).
+
     perf_tangent.py [--shapes any36,headline] [--rounds R] [--iters I] [--procs P] [--json FILE] [--once]
 
 Shapes: any36 = 64 x 16 x 36 x 36, headline = 512 x 64 x 32 x 32, ten Strang steps each, fp32.  At N = 32 the any-size
